@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py — Gaussians/sec of the mesh -> 3DGS conversion pass on N MI355X GPUs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set up, W warm-up steps, EXACTLY K timed steps, the JSON line.  Everything else this file
+measures (the sections listed below, the repetitions of the timed region, the blocking and dedicated kernel-time samples, the copy
+peak, the record exchange and strong scaling at N > 1) runs under --full; the --no-* options switch single parts of it off again.
+--dump-outputs DIR: after the timed steps, what the last one computed (rank 0's records) goes to DIR/*.npy (see dump_outputs).
 
 N > 1 works both ways: started by a launcher that sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* for one process per GPU (the
 driver's torchrun does), or typed as is — bench.py then starts the N ranks itself.  The ranks meet in a directory for the 128-byte
@@ -85,8 +90,13 @@ def parse():
                     help="A/B: force a pipeline setting for the headline workload (default: the library's AUTO)")
     ap.add_argument("--reps", type=int, default=0,
                     help="repetitions of the timed region (each: EXACTLY --steps conversions between barrier + synchronize); ms_per_step / value "
-                         "are the MEDIAN repetition, all of them are in ms_per_step_reps.  Default: 5 when --steps < 100 (a 2.3 ms window "
-                         "must not decide the headline), else 1")
+                         "are the MEDIAN repetition, all of them are in ms_per_step_reps.  Default: 1; with --full 5 when --steps < 100 (a "
+                         "2.3 ms window must not decide the headline), else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other measurement of this file (cold path, extra workloads, viewer passes, CPU "
+                         "baseline, end to end, blocking / dedicated kernel samples, copy peak; N > 1: record exchange, strong scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (a fixed sample of the records, the counters)")
     ap.add_argument("--bringup-timeout", type=float, default=100.0, help="N > 1: seconds the ranks get to meet and create the communicator; "
                     "then every rank leaves non-zero and rank 0 prints scale_record with the error text")
     ap.add_argument("--headline-timeout", type=float, default=240.0, help="N > 1: seconds for the weak-scaling headline after the bring-up")
@@ -726,6 +736,28 @@ def end_to_end(scene_one_mesh, R):
     return out
 
 
+DUMP_ROWS = 1 << 18         # records sampled by --dump-outputs: 262 144 x 96 B = 25 MB
+
+
+def dump_outputs(directory, rig, total):
+    """--dump-outputs: what the timed path returned in its last step, for output-by-output comparison of two builds.
+      counts.npy          float64 [counter, stored]: m2s_convert's counter and the records stored under the cap;
+      records.npy         float32 (k, 24): the stored records at rows_sampled (all of them when there are at most DUMP_ROWS);
+      rows_sampled.npy    float64 (k,): those rows, ascending — a fixed sample (seed 0) that depends on `stored` only."""
+    import numpy as np
+    stored = int(stored_of(rig))
+    if rig.out is None:
+        rec = rig.conv.download()
+    else:                                            # caller-owned buffer (N > 1, --force-dist): this rank's block
+        rig.torch.cuda.synchronize()
+        rec = rig.out[:stored].cpu().numpy()
+    rows = np.arange(stored) if stored <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(stored, DUMP_ROWS, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "counts.npy"), np.array([total, stored], np.float64))
+    np.save(os.path.join(directory, "records.npy"), np.ascontiguousarray(rec[rows], dtype=np.float32))
+    np.save(os.path.join(directory, "rows_sampled.npy"), rows.astype(np.float64))
+
+
 class stdout_to_stderr:
     """gloo and librccl announce themselves on C stdout; the driver reads ONE JSON line from this process's stdout.  While the
     process group / the communicator come up, file descriptor 1 points at stderr."""
@@ -747,6 +779,10 @@ class stdout_to_stderr:
 
 def main():
     a = parse()
+    if not a.full:          # a plain run: the headline only
+        for extra in ("no_cpu_baseline", "no_gather", "no_viewer_extra", "no_overlap_extra", "no_c5", "no_extra_workloads",
+                      "no_strong_scaling", "no_cold", "no_end_to_end"):
+            setattr(a, extra, True)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         if a.dry_scale:
             dry_scale_env(a)
@@ -904,7 +940,7 @@ def main():
     box = TimeBox("weak-scaling headline (timed loop + counter exchange)", a.headline_timeout)
     # The timed region: W warm-up steps, then EXACTLY K steps between barrier + synchronize, max over ranks — repeated `reps` times
     # (warm-up only in front of the first); the line's ms_per_step / value are those of the MEDIAN repetition.
-    reps = a.reps if a.reps > 0 else (5 if a.steps < 100 else 1)
+    reps = a.reps if a.reps > 0 else (5 if a.full and a.steps < 100 else 1)
     rep_dt = []
     for i in range(reps):
         dt_i, total = timed_loop(torch, ctl, multi, rig, a.steps, a.warmup if i == 0 else 0, sync_steps=a.sync_steps, reset=(i == 0))
@@ -920,23 +956,28 @@ def main():
     n_prof = rig.n_prof
     last_pipeline = rig.conv.last_pipeline
     stored_local = stored_of(rig)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rig, total)
 
-    # for the record: the same loop with one blocking call per step (outside the timed region)
-    per_step = []
-    for _ in range(min(a.steps, 20)):
-        p0 = time.perf_counter()
-        rig.step_sync()
-        per_step.append((time.perf_counter() - p0) * 1e3)
-    rig.drain_counts()
-    torch.cuda.synchronize()
-    sync_ms = float(np.mean(per_step))
-    per_step.sort()
-    sync_stats = {"median": per_step[len(per_step) // 2], "p10": per_step[len(per_step) // 10], "p90": per_step[(len(per_step) * 9) // 10]}
-    # a dedicated kernel-time sample: 64 blocking launches, HIP events on every one (not part of `value`)
-    rig.reset_kms()
-    rig.run(64, timed=True, sync_steps=True, prof_every=1)
-    rig.drain_counts()
-    dedicated = rig.kernel_ms()
+    sync_ms = sync_stats = None
+    dedicated = {"what": "measured under --full only"}
+    if a.full:
+        # for the record: the same loop with one blocking call per step (outside the timed region)
+        per_step = []
+        for _ in range(min(a.steps, 20)):
+            p0 = time.perf_counter()
+            rig.step_sync()
+            per_step.append((time.perf_counter() - p0) * 1e3)
+        rig.drain_counts()
+        torch.cuda.synchronize()
+        sync_ms = float(np.mean(per_step))
+        per_step.sort()
+        sync_stats = {"median": per_step[len(per_step) // 2], "p10": per_step[len(per_step) // 10], "p90": per_step[(len(per_step) * 9) // 10]}
+        # a dedicated kernel-time sample: 64 blocking launches, HIP events on every one (not part of `value`)
+        rig.reset_kms()
+        rig.run(64, timed=True, sync_steps=True, prof_every=1)
+        rig.drain_counts()
+        dedicated = {"what": "64 blocking launches after the timed region, HIP events on every one", **rig.kernel_ms()}
 
     overlapped = None
     if not a.no_overlap_extra and not multi:
@@ -949,7 +990,7 @@ def main():
             viewer = {"error": str(e)}
 
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and a.full:
         nbytes = 1 << 30
         src = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
         dstb = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
@@ -997,12 +1038,12 @@ def main():
             "sync_ms_per_step": sync_ms, "sync_ms_stats": sync_stats, "overlapped": overlapped, "viewer_passes": viewer,
             "kernel_ms": kms,
             "kernel_timing": f"HIP events on the launch stream around every 4th launch of the timed region(s) ({n_prof} launches)",
-            "kernel_ms_dedicated": {"what": "64 blocking launches after the timed region, HIP events on every one", **dedicated},
+            "kernel_ms_dedicated": dedicated,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "traffic_source": None, "kernel": kname,
                          "algorithmic_bytes": b_alg, "measured_copy_peak": copy_gbs,
                          "frac_of_measured_copy": (achieved / copy_gbs) if copy_gbs else None,
-                         "frac_dedicated_sample": (b_alg / (dedicated[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if dedicated[dom] > 0 else None,
+                         "frac_dedicated_sample": (b_alg / (dedicated[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if dedicated.get(dom, 0) > 0 else None,
                          "write_only_frac": (96.0 * stored_local / (emit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if emit_ms > 0 else 0.0},
         }
         tr = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -1178,7 +1219,8 @@ def main():
         watchdog.cancel()
     if rank == 0:
         if not multi:
-            one = scene if n in ("grid", "sponza_like") else synth.colocated_spheres(1, n, tex)
+            # (the one-mesh scene of the cold path, the end-to-end leg and the CPU baseline: --full only)
+            one = (scene if n in ("grid", "sponza_like") else synth.colocated_spheres(1, n, tex)) if a.full else None
             if not a.no_cold:
                 try:
                     res["cold_path"] = cold_path(torch, local_rank, one, R, sync_ms)
@@ -1194,7 +1236,7 @@ def main():
             rf, cp = res["roofline"], res.get("cold_path") or {}
             b = rf["algorithmic_bytes"]
             rf["frac_step"] = b / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
-            rf["frac_blocking"] = b / (sync_ms * 1e-3) / 1e9 / HBM_PEAK_GBS       # one blocking m2s_convert per step: the reference's semantics
+            rf["frac_blocking"] = (b / (sync_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if sync_ms else None   # one blocking m2s_convert per step: the reference's semantics
             rf["frac_clock"] = ("frac: HIP events on the launch stream around every 4th launch of the timed region (two conversions in flight); "
                                 "frac_dedicated_sample: HIP events around 64 blocking launches (agrees with rocprofv3's average); "
                                 "frac_step: the driver-timed ms_per_step; frac_blocking: wall clock of one blocking call.  The claim "

@@ -46,7 +46,7 @@ def test_force_dist_with_one_rank_agrees_with_the_plain_line(hiplib):
 
 
 def test_repetitions_and_end_to_end_are_in_the_line(hiplib):
-    line = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--workload", "c2", *QUIET)
+    line = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--workload", "c2", "--full", *QUIET)     # (repetitions, end to end: --full)
     assert line["steps"] == 20 and line["warmup"] == 5
     reps = line["ms_per_step_reps"]
     assert reps["reps"] == 5 and len(reps["all"]) == 5 and reps["min"] <= reps["median"] <= reps["max"]
@@ -58,3 +58,31 @@ def test_repetitions_and_end_to_end_are_in_the_line(hiplib):
         assert t["total_ms"] <= t["wall_ms_whole_process"]
     n = line["config"]["gaussians_per_step"]
     assert e2e["format0"]["ply_bytes"] > 248 * n and e2e["format1"]["ply_bytes"] > 76 * n       # header + rows of the stored Gaussians
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_steps_records(hiplib, tmp_path):
+    """Without --full the line is the headline alone (exactly --steps timed steps, no extra sections); --dump-outputs writes what the
+    last timed step computed, the same arrays from run to run and the same records as one conversion of the same scene."""
+    import numpy as np
+    from mesh2splat_amd import synth
+    from mesh2splat_amd.converter import Converter
+    args = ("--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "small")
+    line = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["ms_per_step_reps"]["reps"] == 1 and line["ms_per_step_reps"]["all"] == [line["ms_per_step"]]
+    assert line["overlapped"] is None and line["viewer_passes"] is None and line["sync_ms_per_step"] is None
+    assert not set(line) & {"cold_path", "extra_workloads", "end_to_end_ms", "cpu_baseline", "gather", "strong_scaling"}
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    out = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("counts", "records", "rows_sampled")}
+    for k, v in out.items():
+        assert v.dtype in (np.float32, np.float64)
+        assert np.array_equal(v.view(np.uint8), np.load(tmp_path / "b" / f"{k}.npy").view(np.uint8)), k
+    n, tex, R = 24, 256, 256                                    # bench.WORKLOADS["small"]
+    conv = Converter(0)
+    conv.upload_scene(synth.colocated_spheres(1, n, tex))
+    total = conv.convert(R)
+    rec = conv.download()
+    conv.close()
+    assert out["counts"].tolist() == [total, len(rec)] and total == line["config"]["gaussians_per_step"]
+    rows = out["rows_sampled"].astype(np.int64)
+    assert len(rows) == min(len(rec), 1 << 18) and np.array_equal(out["records"].view(np.uint32), rec[rows].view(np.uint32))

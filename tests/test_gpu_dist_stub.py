@@ -170,7 +170,7 @@ def test_bench_multi_rank_goes_through_the_c_abi_or_fails(hiplib, tmp_path):
     and when the communicator cannot be created the run exits non-zero WITHOUT a measurement (no silent fall-back): rank 0's line
     then has value null and a scale_record that carries the error text."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--workload", "c2", "--steps", "4", "--warmup", "1",
-           "--no-extra-workloads", "--extras-timeout", "200"]
+           "--full", "--no-extra-workloads", "--extras-timeout", "200"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=stub_env(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -212,7 +212,7 @@ def test_bench_dry_scale_prints_the_scale_record(hiplib, tmp_path, world):
     bench.py itself), no torch.distributed anywhere: the line carries the record the driver reads — ranks, per-rank Gaussians,
     whole-job value, the counter exchange's and the bring-up's time — and says that it is a dry run."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dry-scale", "--workload", "small", "--steps", "3", "--warmup", "1",
-           "--no-extra-workloads", "--no-strong-scaling", "--extras-timeout", "200"]
+           "--full", "--no-extra-workloads", "--no-strong-scaling", "--extras-timeout", "200"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("M2S_RCCL_PATH", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
