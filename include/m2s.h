@@ -356,6 +356,54 @@ float m2s_last_sort_prepass_ms(const m2s_ctx* ctx);
  * of m2s_prepass are not produced.  m2s_last_sort_stage_ms: [0] keys, [1] radix sort, [2] the prepass through the permutation. */
 m2s_status m2s_prepass_sorted(m2s_ctx* ctx, const m2s_prepass_params* params, uint64_t* out_visible);
 
+/* ---- splat pass == GaussianSplattingPass::execute (GaussianSplattingPass.cpp:50-95) ----------------------- */
+/* Draws one quad per entry of perQuadTransformationBufferSorted (gaussianSplattingVS.glsl:31-40) and blends the fragment shader's
+ * five outputs (gaussianSplattingPS.glsl:29-45) into the G-buffer of renderer.cpp:325-380.  GL semantics restated for a compute
+ * pass; these choices are the pin (tests/splat_ref.py restates them operation for operation, fp32 without contraction):
+ *  - Quads are blended in ARRAY order, quad 0 first (the depth sort's ascending keys put the nearest Gaussian first).
+ *  - Targets, all cleared to 0 at the start of the call (GaussianSplattingPass.cpp:59-60), W x H pixels, row 0 = the BOTTOM row
+ *    (GL orientation, as m2s_prepass_params.depth): attachment 0 position, 1 normal, 3 depth: RGBA16F (half4 per pixel);
+ *    2 albedo, 4 metallic-roughness: RGBA8 unorm (uchar4 per pixel).
+ *  - Geometry: vertices mean.xy + (vx * scale.xy + vy * scale.zw), (vx, vy) in {(-1,-1), (-1,1), (1,1), (1,-1)}, triangles (0,1,2)
+ *    and (0,2,3); the sum of the two axis terms rounds, then the addition of the mean.  Viewport xw = (W/2) x + W/2, yw = (H/2) y + H/2,
+ *    then the project's pinned rasteriser (the conversion's, with a W x H viewport): snap to 1/256 px (RNE), int64 edge functions,
+ *    both windings (GL_CULL_FACE off), top-left rule, pixel centres (x + 0.5, y + 0.5).  A pixel centre on the shared diagonal
+ *    belongs to exactly one of the two triangles.
+ *  - A quad with a non-finite value in any field the pass reads (mean.xy, scale, color, conic, normal, ws_pos) or with a vertex
+ *    beyond the +-16384 px guard band is SKIPPED and counted (*out_skipped) — GL would clip it instead.  Quads made by m2s_prepass
+ *    never get there for W, H <= 8192: their means lie inside the 1.05 w frustum and their axes are capped at 1024 px
+ *    (gaussianSplattingPrepassCS.glsl:185-186).
+ *  - Fragment (VS:34-40, PS:30-45): screen = ((mean.xy + 1) * 0.5) * (W, H); d = screen - fragcoord;
+ *    alpha = ((-0.5 cx) * (dx dx) + (-0.5 cz) * (dy dy)) + (-cy) * (dx dy) with conic = (cx, cy, cz); g = exp(alpha) (the device's
+ *    fast exp: the one step allowed to differ from the restatement).  Sources: albedo ((rgb * a) * g, a * g) — in render mode 4
+ *    (overdraw) the constant (0.01, 0.005, 0, 0.01) —; position (ws.xyz * g, g); normal (normal.xyz * g, a * g);
+ *    depth (conic.w * g x 3, a * g); metallic-roughness (normal.w * g, ws.w * g, 0, g).
+ *  - Blend (GaussianSplattingPass.cpp:63-66), per attachment with its own destination alpha: t = 1 - dst.a, r = src * t + dst, each
+ *    operation rounded to fp32; render mode 4: r = src + dst.  RGBA16F: no clamp, r rounded to half (RNE, subnormals kept, overflow
+ *    to +-inf) after EVERY fragment.  RGBA8: the source is clamped to [0, 1] first, q = rint(clamp(r, 0, 1) * 255), read back as q / 255.
+ *  - A pixel whose five alphas are exactly 1.0 stops early only where that leaves its bytes unchanged.
+ * Synchronous.  Errors: M2S_ERR_INVALID for a resolution outside 1..8192, a render mode outside 0..6, reserved != 0, or d_quads NULL
+ * while the context holds no sorted quads.  n = 0 with a non-NULL d_quads: five cleared planes. */
+typedef struct m2s_splat_params {
+    int32_t resolution[2];  /* rendererResolution == u_resolution == viewport, 1..8192 each: the W x H the quads were made for */
+    int32_t render_mode;    /* u_renderMode 0..6: 4 = overdraw (constant albedo, blend ONE/ONE); any other ONE_MINUS_DST_ALPHA/ONE */
+    uint32_t reserved;      /* 0 */
+} m2s_splat_params;
+/* d_quads == NULL: the context's sorted quads (m2s_sort_prepass / m2s_prepass_sorted / m2s_upload_quads), n ignored; else n m2s_quad
+ * at a device pointer on the context's device.  *out_skipped (may be NULL) = quads skipped by the rule above. */
+m2s_status m2s_splat(m2s_ctx* ctx, const m2s_splat_params* params, const void* d_quads, uint64_t n, uint64_t* out_skipped);
+/* n host quads become the context's sorted quads (what m2s_device_sorted_quads returns and m2s_splat draws with d_quads == NULL). */
+m2s_status m2s_upload_quads(m2s_ctx* ctx, const m2s_quad* host_quads, uint64_t n);
+/* Attachment 0..4 of the last m2s_splat: 0, 1, 3: half4[W * H]; 2, 4: uchar4[W * H]; row 0 = bottom.  NULL before any splat. */
+const void* m2s_device_gbuffer(const m2s_ctx* ctx, uint32_t attachment);
+m2s_status m2s_download_gbuffer(m2s_ctx* ctx, uint32_t attachment, void* dst, uint64_t capacity_bytes);
+/* Duration (ms) of the last profiled m2s_splat (sum of its three stages), and the stages: [0] setup + bin, [1] grouping by tile
+ * (radix sort, tile ranges, tile order), [2] blend. */
+float m2s_last_splat_ms(const m2s_ctx* ctx);
+m2s_status m2s_last_splat_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* What the last m2s_splat did: [0] (tile, quad) pairs, [1] fragments blended (after the early exit), [2] quads skipped. */
+m2s_status m2s_last_splat_counts(const m2s_ctx* ctx, uint64_t out[3]);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

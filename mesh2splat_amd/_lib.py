@@ -35,6 +35,8 @@ EXPORTS = (
     "m2s_dist_clamp_to_cap", "m2s_dist_gather_records", "m2s_dist_wait", "m2s_set_records", "m2s_reserve_records", "m2s_prepare",
     "m2s_dist_local_id", "m2s_dist_sort_by_depth", "m2s_device_sorted_keys", "m2s_num_sorted", "m2s_last_resolution",
     "m2s_set_resolution_hint", "m2s_last_warm_ms", "m2s_dist_transport", "m2s_last_sort_stage_ms",
+    "m2s_splat", "m2s_upload_quads", "m2s_device_gbuffer", "m2s_download_gbuffer", "m2s_last_splat_ms", "m2s_last_splat_stage_ms",
+    "m2s_last_splat_counts",
 )
 
 
@@ -180,6 +182,13 @@ def load():
         "m2s_last_warm_ms": (C.c_float, [vp]),
         "m2s_dist_transport": (C.c_char_p, [vp]),
         "m2s_last_sort_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_splat": (C.c_int, [vp, vp, vp, u64, C.POINTER(u64)]),
+        "m2s_upload_quads": (C.c_int, [vp, vp, u64]),
+        "m2s_device_gbuffer": (vp, [vp, u32]),
+        "m2s_download_gbuffer": (C.c_int, [vp, u32, vp, u64]),
+        "m2s_last_splat_ms": (C.c_float, [vp]),
+        "m2s_last_splat_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_last_splat_counts": (C.c_int, [vp, C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -63,6 +63,7 @@ class Converter:
         self._h = h
         self.device = int(device)
         self._keep = None
+        self._last_splat_wh = (0, 0)
 
     # -- helpers ------------------------------------------------------------------------------------
     def _check(self, st: int):
@@ -295,6 +296,59 @@ class Converter:
     def last_sort_prepass_ms(self) -> float:
         return float(self._L.m2s_last_sort_prepass_ms(self._h))
 
+    def upload_quads(self, quads: np.ndarray):
+        """(n, 24) float32 host quads (m2s_quad) become the context's sorted quads: what splat() draws without `quads`."""
+        q = np.ascontiguousarray(quads, np.float32).reshape(-1, 24)
+        self._check(self._L.m2s_upload_quads(self._h, q.ctypes.data if q.shape[0] else None, q.shape[0]))
+
+    def splat(self, params, quads=None, download: bool = True):
+        """GaussianSplattingPass (m2s_splat): blend the context's sorted quads (or `quads`, a contiguous CUDA torch tensor (n, 24)
+        float32) in array order into the five-target G-buffer.  `params`: mesh2splat_amd.splat.SplatParams.
+        -> (planes, skipped): planes = five (H, W, 4) arrays (float16 for attachments 0, 1, 3, uint8 for 2, 4), row 0 = the bottom
+        row; with download=False just `skipped` (the planes stay on the device: device_gbuffer(k))."""
+        from . import splat as _sp
+        pc = _sp.to_c(params)
+        ptr, n = None, 0
+        if quads is not None:
+            if not (hasattr(quads, "data_ptr") and quads.is_cuda and quads.is_contiguous()):
+                raise ValueError("quads must be a contiguous CUDA tensor (n, 24) float32")
+            n = int(quads.shape[0])
+            ptr = quads.data_ptr() if n else 1          # n = 0: cleared planes (a NULL pointer would mean "the sorted quads")
+        skipped = C.c_uint64()
+        self._check(self._L.m2s_splat(self._h, C.byref(pc), ptr, n, C.byref(skipped)))
+        self._last_splat_wh = (int(pc.resolution[0]), int(pc.resolution[1]))
+        if not download:
+            return skipped.value
+        return self.download_gbuffer(), skipped.value
+
+    def download_gbuffer(self):
+        """The five planes of the last splat as (H, W, 4) arrays."""
+        from . import splat as _sp
+        W, H = self._last_splat_wh
+        out = []
+        for k, (_, dt) in enumerate(_sp.ATTACHMENTS):
+            a = np.empty((H, W, 4), dt)
+            self._check(self._L.m2s_download_gbuffer(self._h, k, a.ctypes.data, a.nbytes))
+            out.append(a)
+        return out
+
+    def device_gbuffer(self, attachment: int) -> int:
+        return int(self._L.m2s_device_gbuffer(self._h, int(attachment)) or 0)
+
+    @property
+    def last_splat_ms(self) -> float:
+        return float(self._L.m2s_last_splat_ms(self._h))
+
+    def last_splat_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_splat_stage_ms(self._h, ms))
+        return {"setup_bin": float(ms[0]), "grouping": float(ms[1]), "blend": float(ms[2])}
+
+    def last_splat_counts(self) -> dict:
+        v = (C.c_uint64 * 3)()
+        self._check(self._L.m2s_last_splat_counts(self._h, v))
+        return {"pairs": int(v[0]), "fragments": int(v[1]), "skipped": int(v[2])}
+
     def set_pipeline(self, name: str):
         """'auto' (single-pass kernel or multi-pass pipeline, chosen per scene and R), 'multipass', or the single-pass
         kernel forced in one of its forms: 'team' (k_fused2, workgroup-cooperative), 'lean' (k_fused3), 'sparse' (k_sparse)."""
@@ -352,6 +406,10 @@ class RenderContext:
         self.numberOfGaussians = 0                # written by ConversionPass::execute
         self.device = int(device)
         self.converter: Optional[Converter] = None  # owns gaussianBuffer (the SSBO equivalent)
+        self.rendererResolution = (1280, 720)     # RenderContext::rendererResolution (GaussianSplattingPass)
+        self.renderMode = 0                       # RenderContext::renderMode
+        self.gBuffer = None                       # written by GaussianSplattingPass::execute: the five planes
+        self.splatSkipped = 0
         self._uploaded_scene = None
 
 
@@ -385,6 +443,21 @@ class ConversionPass(IRenderPass):
             context.converter.upload_scene(context.scene)
             context._uploaded_scene = context.scene
         context.numberOfGaussians = context.converter.convert(context.resolutionTarget)
+
+
+class GaussianSplattingPass(IRenderPass):
+    """GaussianSplattingPass::execute (GaussianSplattingPass.cpp:50-95): blends the sorted quads (what RadixSortPass left in the
+    context: Converter.sort_prepass / prepass_sorted / upload_quads) into the G-buffer at context.rendererResolution with
+    context.renderMode.  The five planes end up in context.gBuffer as (H, W, 4) arrays, row 0 = bottom, in attachment order
+    position, normal, albedo, depth, metallic-roughness (renderer.cpp:325-380)."""
+
+    def execute(self, context: RenderContext):
+        from .splat import SplatParams
+        if context.converter is None:
+            raise RuntimeError("no quads: run the conversion, the prepass and the depth sort first")
+        res = getattr(context, "rendererResolution", (1280, 720))
+        mode = getattr(context, "renderMode", 0)
+        context.gBuffer, context.splatSkipped = context.converter.splat(SplatParams(renderer_resolution=tuple(res), render_mode=int(mode)))
 
 
 class SceneManager:

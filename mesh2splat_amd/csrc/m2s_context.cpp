@@ -189,6 +189,11 @@ void m2s_destroy(m2s_ctx* c) {
     if (c->d_sorted) (void)hipFree(c->d_sorted);
     if (c->d_quads) (void)hipFree(c->d_quads);
     if (c->d_sorted_quads) (void)hipFree(c->d_sorted_quads);
+    for (int k = 0; k < 5; ++k) if (c->d_gbuf[k]) (void)hipFree(c->d_gbuf[k]);
+    for (void* p : { (void*)c->d_splat_rec, (void*)c->d_splat_cnt, (void*)c->d_splat_off, (void*)c->d_splat_pairs, (void*)c->d_splat_tiles,
+                     c->d_splat_temp, (void*)c->d_splat_totals })
+        if (p) (void)hipFree(p);
+    if (c->h_splat) (void)hipHostFree(c->h_splat);
     if (c->d_loaded) (void)hipFree(c->d_loaded);
     if (c->d_rows) (void)hipFree(c->d_rows);
     for (int k = 0; k < 2; ++k) if (c->h_export[k]) (void)hipHostFree(c->h_export[k]);

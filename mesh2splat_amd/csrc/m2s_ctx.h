@@ -2,6 +2,7 @@
 //   m2s_context.cpp  lifetime, setters, record pool, launch tags          m2s_upload.cpp   m2s_upload_scene / m2s_prepare
 //   m2s_pass.cpp     the conversion pass driver (== ConversionPass::execute)   m2s_async.cpp    m2s_convert_submit / _wait
 //   m2s_records.cpp  read-back, .ply export, record adoption               m2s_viewer.cpp   depth sort, viewer prepass
+//   m2s_splat.cpp    the splat pass (== GaussianSplattingPass::execute) and its G-buffer
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -173,6 +174,25 @@ struct m2s_ctx {
     void* d_sorted_quads = nullptr;          // m2s_sort_prepass
     uint64_t sq_cap = 0, sq_n = 0;
     float last_sort_prepass_ms = 0.0f;
+    // splat pass (m2s_splat.cpp): the five G-buffer planes of the last call and the pass's grow-only work buffers
+    void* d_gbuf[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    uint64_t gbuf_cap_px = 0;                // pixels every plane has room for
+    int32_t gbuf_w = 0, gbuf_h = 0;          // resolution of the planes' contents (0: no splat has run)
+    void* d_splat_rec = nullptr;             // per quad: 128-byte record, tile count (u32), exclusive scan of the counts (u64)
+    uint32_t* d_splat_cnt = nullptr;
+    unsigned long long* d_splat_off = nullptr;
+    uint64_t splat_quad_cap = 0;
+    uint32_t* d_splat_pairs = nullptr;       // keys_in | vals_in | keys_out | vals_out, splat_pairs_cap each
+    uint64_t splat_pairs_cap = 0;
+    uint32_t* d_splat_tiles = nullptr;       // ranges (2 words) | lengths | sorted lengths | order, splat_tiles_cap tiles each
+    uint64_t splat_tiles_cap = 0;
+    void* d_splat_temp = nullptr;            // scan / radix sort work area
+    size_t splat_temp_cap = 0;
+    unsigned long long* d_splat_totals = nullptr;   // [0] pairs, [1] skipped quads, [2] fragments blended
+    unsigned long long* h_splat = nullptr;          // pinned copy of those three words
+    float last_splat_ms = 0.0f;
+    float last_splat_stage_ms[3] = { 0, 0, 0 };     // setup + bin, grouping, blend (profiling on)
+    uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
 
     // measurement
     bool profiling = false;

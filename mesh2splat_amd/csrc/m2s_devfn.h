@@ -300,6 +300,55 @@ __device__ __forceinline__ bool raster_setup(const Geo& g, uint32_t R, Raster& s
     return true;
 }
 
+// The same rasteriser for a W x H viewport (glViewport(0, 0, W, H): the splat pass, m2s_splat.hip): clip-space x, y of the three
+// vertices with w = 1, xw = (W/2) x + W/2, yw = (H/2) y + H/2, then the 24.8 snap, the guard band, the pixel box clamped to
+// W x H, int64 edge functions with both windings and the top-left rule — operation for operation raster_head / raster_setup.
+__device__ __forceinline__ bool raster_head_wh(const float ndx[3], const float ndy[3], int W, int H, RasterHead& h) {
+    const float hw = (float)W * 0.5f, hh = (float)H * 0.5f;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        float xw = hw * ndx[i] + hw, yw = hh * ndy[i] + hh;
+        ok = ok && (fabsf(xw) < kGuardPx) && (fabsf(yw) < kGuardPx);     // false for NaN
+        h.X[i] = (int)rintf(xw * 256.0f);
+        h.Y[i] = (int)rintf(yw * 256.0f);
+    }
+    if (!ok) return false;
+    const int xmin = min(h.X[0], min(h.X[1], h.X[2])), xmax = max(h.X[0], max(h.X[1], h.X[2]));
+    const int ymin = min(h.Y[0], min(h.Y[1], h.Y[2])), ymax = max(h.Y[0], max(h.Y[1], h.Y[2]));
+    h.ext = max(xmax - xmin, ymax - ymin);
+    h.x0 = max((xmin - 128 + 255) >> 8, 0);
+    h.x1 = min((xmax - 128) >> 8, W - 1);
+    h.y0 = max((ymin - 128 + 255) >> 8, 0);
+    h.y1 = min((ymax - 128) >> 8, H - 1);
+    return h.x0 <= h.x1 && h.y0 <= h.y1;
+}
+
+__device__ __forceinline__ bool raster_setup_wh(const float ndx[3], const float ndy[3], int W, int H, Raster& s) {
+    RasterHead h;
+    const bool box = raster_head_wh(ndx, ndy, W, H, h);
+    const int* X = h.X;
+    const int* Y = h.Y;
+    if (!box) return false;
+    long long area2 = (long long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long long)(Y[1] - Y[0]) * (X[2] - X[0]);
+    if (area2 == 0) return false;
+    const int sgn = area2 < 0 ? -1 : 1;  // no culling (GaussianSplattingPass.cpp:57)
+    s.area2 = area2 < 0 ? -area2 : area2;
+    s.bias = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int ia = (i + 1) % 3, ib = (i + 2) % 3;
+        int dy = Y[ib] - Y[ia], dx = X[ib] - X[ia];
+        s.a[i] = -dy * sgn;
+        s.b[i] = dx * sgn;
+        s.c[i] = ((long long)dy * X[ia] - (long long)dx * Y[ia]) * sgn;
+        if (s.a[i] > 0 || (s.a[i] == 0 && s.b[i] > 0)) s.bias |= 1 << i;
+    }
+    s.ext = h.ext;
+    s.x0 = h.x0; s.x1 = h.x1; s.y0 = h.y0; s.y1 = h.y1;
+    return true;
+}
+
 // The same setup for a triangle whose sub-pixel extent is at most 2304 (so |a|, |b| <= 2304) in a pixel box of at most 8 x 8
 // (k_fused3): every quantity fits 32 bits and every product 24 x 24 bits.  E_i(P) = a_i (Px - X_ia) + b_i (Py - Y_ia) — the edge
 // function written from the edge's first vertex, equal to a_i Px + b_i Py + c_i of raster_setup — and the centre of the box-origin

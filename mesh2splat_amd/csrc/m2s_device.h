@@ -223,6 +223,24 @@ hipError_t sort_prepass_permutation(const float4* rec, uint32_t n, const float m
                                     uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, float4* plane, bool plane_valid,
                                     hipEvent_t* ev, hipStream_t st, uint32_t* pinned_mm4, uint32_t* n_visible, bool* clash);
 
+// ---- splat pass (m2s_splat.hip): GaussianSplattingPass over sorted quads into the five-target G-buffer ---------------------------
+constexpr int kSplatTile = 16;                 // tiles of 16 x 16 pixels, one workgroup (one lane per pixel) each
+constexpr size_t kSplatRecBytes = 128;         // compact per-quad record written by the setup kernel
+size_t splat_scan_temp_bytes(uint32_t n);
+size_t splat_sort_temp_bytes(uint32_t pairs, uint32_t n_tiles);
+// setup: records, per-quad tile counts, their exclusive scan; totals[0] = (tile, quad) pairs, totals[1] += skipped quads
+hipError_t splat_setup(const float4* quads, uint32_t n, int W, int H, float4* rec, uint32_t* cnt, unsigned long long* off, void* temp,
+                       size_t temp_bytes, unsigned long long* totals, hipStream_t st);
+hipError_t splat_pairs(const float4* rec, const uint32_t* cnt, const unsigned long long* off, uint32_t n, int tiles_x, uint32_t* keys,
+                       uint32_t* vals, hipStream_t st);
+// stable grouping of the pairs by tile, every tile's [start, end), the tiles ordered by list length (longest first)
+hipError_t splat_group(uint32_t* keys_in, uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t pairs, uint32_t n_tiles,
+                       uint2* ranges, uint32_t* len, uint32_t* len_sorted, uint32_t* order, void* temp, size_t temp_bytes, hipStream_t st);
+// ranges / order NULL: every tile empty (cleared planes); frag_count (or NULL) += fragments blended
+hipError_t splat_blend(const float4* rec, const uint32_t* vals, const uint2* ranges, const uint32_t* order, int W, int H, int render_mode,
+                       void* const planes[5], unsigned long long* frag_count, hipStream_t st);
+hipError_t preload_splat();
+
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);
 void launch_lower_bounds(const uint32_t* keys, uint64_t n, const unsigned long long* splitters, uint32_t m, unsigned long long* out, hipStream_t st);

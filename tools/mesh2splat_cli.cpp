@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -55,6 +56,8 @@ struct Options {
     bool timing = false, gather = false, force_sharded = false;   // force_sharded: the --gpus code path with one rank (tests)
     bool one_device = false;                                       // tests: every rank on --device (several processes share one GPU)
     bool threads = false;                                          // ranks as threads of this process
+    std::string preview;                                           // --preview view.png: prepass + depth sort + splat of the result
+    int preview_w = 1280, preview_h = 720;
     uint32_t R() const { return density > 0 ? (uint32_t)density : (uint32_t)(int)(16 + quality * (double)(max_res - 16)); }  // ImGuiUI.cpp:512
 };
 
@@ -63,7 +66,137 @@ void usage() {
                  "usage: mesh2splat in.glb out.ply [options]\n"
                  "       mesh2splat --batch in_dir --out out_dir [options]\n"
                  "options: [--density R | --quality q [--max-res M]] [--std s] [--format 0|1|2] [--device d] [--gpus N [--gather]]\n"
-                 "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n");
+                 "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
+                 "         [--preview view.png [--preview-size WxH (default 1280x720)]]\n"
+                 "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
+                 "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
+                 "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
+                 "  dist = 1.1 * radius / tan(radians(22.5)), eye = centre + (0, 0, dist), up = (0, 1, 0), looking at centre,\n"
+                 "  45 deg vertical field of view, aspect W / H, near = dist / 100, far = dist * 10.\n");
+}
+
+// ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
+uint32_t crc32_of(const uint8_t* p, size_t n, uint32_t crc = 0) {
+    crc = ~crc;
+    for (size_t i = 0; i < n; ++i) {
+        crc ^= p[i];
+        for (int k = 0; k < 8; ++k) crc = (crc >> 1) ^ (0xEDB88320u & (0u - (crc & 1u)));
+    }
+    return ~crc;
+}
+
+bool write_png_rgba(const char* path, const uint8_t* rgba_bottom_up, int W, int H) {
+    std::vector<uint8_t> raw;                         // filter byte 0 + the row, top row first
+    raw.reserve((size_t)H * (1 + 4 * (size_t)W));
+    for (int y = H - 1; y >= 0; --y) {
+        raw.push_back(0);
+        const uint8_t* row = rgba_bottom_up + (size_t)y * 4 * W;
+        raw.insert(raw.end(), row, row + 4 * (size_t)W);
+    }
+    std::vector<uint8_t> z = { 0x78, 0x01 };          // zlib header, then stored blocks of at most 65535 bytes
+    uint32_t s1 = 1, s2 = 0;
+    for (size_t off = 0; off < raw.size() || off == 0;) {
+        const size_t len = std::min<size_t>(65535, raw.size() - off);
+        const bool last = off + len == raw.size();
+        z.push_back(last ? 1 : 0);
+        z.push_back(len & 0xFF); z.push_back(len >> 8);
+        z.push_back(~len & 0xFF); z.push_back((~len >> 8) & 0xFF);
+        for (size_t i = off; i < off + len; ++i) { s1 = (s1 + raw[i]) % 65521u; s2 = (s2 + s1) % 65521u; }
+        z.insert(z.end(), raw.begin() + off, raw.begin() + off + len);
+        off += len;
+        if (last) break;
+    }
+    const uint32_t adler = (s2 << 16) | s1;
+    for (int k = 3; k >= 0; --k) z.push_back((adler >> (8 * k)) & 0xFF);
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return false;
+    auto be32 = [](std::vector<uint8_t>& v, uint32_t x) { for (int k = 3; k >= 0; --k) v.push_back((x >> (8 * k)) & 0xFF); };
+    auto chunk = [&](const char* type, const std::vector<uint8_t>& body) {
+        std::vector<uint8_t> c;
+        be32(c, (uint32_t)body.size());
+        c.insert(c.end(), type, type + 4);
+        c.insert(c.end(), body.begin(), body.end());
+        be32(c, crc32_of(c.data() + 4, c.size() - 4));
+        std::fwrite(c.data(), 1, c.size(), f);
+    };
+    static const uint8_t sig[8] = { 0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n' };
+    std::fwrite(sig, 1, 8, f);
+    std::vector<uint8_t> ihdr;
+    be32(ihdr, (uint32_t)W); be32(ihdr, (uint32_t)H);
+    ihdr.insert(ihdr.end(), { 8, 6, 0, 0, 0 });       // 8 bits, RGBA, deflate, no filter method, no interlace
+    chunk("IHDR", ihdr);
+    chunk("IDAT", z);
+    chunk("IEND", {});
+    return std::fclose(f) == 0;
+}
+
+// glm::lookAt / glm::perspective in double, column-major (m[c * 4 + r]), rounded to float (tests/camera.py does the same)
+void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, float view[16], float proj[16], double eye[3], double ctr[3],
+                    double* near_p, double* far_p) {
+    double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
+    for (uint32_t i = 0; i < n_meshes; ++i)
+        for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], (double)meshes[i].bbox_min[k]); mx[k] = std::max(mx[k], (double)meshes[i].bbox_max[k]); }
+    double d2 = 0;
+    for (int k = 0; k < 3; ++k) { ctr[k] = (mn[k] + mx[k]) / 2; d2 += (mx[k] - mn[k]) * (mx[k] - mn[k]); }
+    const double radius = std::sqrt(d2) / 2;
+    const double dist = 1.1 * radius / std::tan(22.5 * (M_PI / 180.0));
+    for (int k = 0; k < 3; ++k) eye[k] = ctr[k];
+    eye[2] += dist;
+    *near_p = dist / 100;
+    *far_p = dist * 10;
+    // lookAt: f = normalize(ctr - eye), s = normalize(cross(f, up)), u = cross(s, f)
+    double f[3] = { ctr[0] - eye[0], ctr[1] - eye[1], ctr[2] - eye[2] };
+    double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    for (double& v : f) v /= fl;
+    const double up[3] = { 0, 1, 0 };
+    double s[3] = { f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0] };
+    double sl = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    for (double& v : s) v /= sl;
+    const double u[3] = { s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0] };
+    double m[16] = { 0 };
+    m[15] = 1;
+    for (int k = 0; k < 3; ++k) { m[k * 4 + 0] = s[k]; m[k * 4 + 1] = u[k]; m[k * 4 + 2] = -f[k]; }
+    m[12] = -(s[0] * eye[0] + s[1] * eye[1] + s[2] * eye[2]);
+    m[13] = -(u[0] * eye[0] + u[1] * eye[1] + u[2] * eye[2]);
+    m[14] = f[0] * eye[0] + f[1] * eye[1] + f[2] * eye[2];
+    for (int k = 0; k < 16; ++k) view[k] = (float)m[k];
+    const double t = std::tan(45.0 * (M_PI / 180.0) / 2.0), aspect = (double)W / (double)H;
+    for (int k = 0; k < 16; ++k) proj[k] = 0.0f;
+    proj[0] = (float)(1.0 / (aspect * t));
+    proj[5] = (float)(1.0 / t);
+    proj[10] = (float)(-(*far_p + *near_p) / (*far_p - *near_p));
+    proj[11] = -1.0f;
+    proj[14] = (float)(-(2.0 * *far_p * *near_p) / (*far_p - *near_p));
+}
+
+// GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path`
+int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+    const int W = o.preview_w, H = o.preview_h;
+    m2s_prepass_params pp;
+    std::memset(&pp, 0, sizeof(pp));
+    double eye[3], ctr[3], near_p, far_p;
+    preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p);
+    for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
+    pp.resolution[0] = W; pp.resolution[1] = H;
+    pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
+    pp.gaussian_std = (float)o.std_dev;
+    pp.resolution_target = R;
+    pp.render_mode = 0;
+    pp.format = 0;
+    std::printf("preview camera: eye=%.17g,%.17g,%.17g centre=%.17g,%.17g,%.17g near=%.17g far=%.17g\n", eye[0], eye[1], eye[2], ctr[0],
+                ctr[1], ctr[2], near_p, far_p);
+    uint64_t visible = 0, n = 0, skipped = 0;
+    if (m2s_prepass(ctx, &pp, nullptr, 0, &visible) != M2S_OK) return 1;
+    if (m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
+    std::vector<uint8_t> img((size_t)W * H * 4, 0);
+    if (n) {
+        m2s_splat_params sp = { { W, H }, 0, 0 };
+        if (m2s_splat(ctx, &sp, nullptr, 0, &skipped) != M2S_OK) return 1;
+        if (m2s_download_gbuffer(ctx, 2, img.data(), img.size()) != M2S_OK) return 1;
+    }
+    if (!write_png_rgba(o.preview.c_str(), img.data(), W, H)) { std::fprintf(stderr, "cannot write %s\n", o.preview.c_str()); return 2; }
+    std::printf("preview %dx%d: %llu quads splatted -> %s\n", W, H, (unsigned long long)n, o.preview.c_str());
+    return 0;
 }
 
 using Clock = std::chrono::steady_clock;
@@ -101,6 +234,11 @@ int convert_one(const Options& o) {
     if (m2s_convert(ctx, R, &total) != M2S_OK) return die("convert");
     const auto t3 = Clock::now();
     if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
+    if (!o.preview.empty()) {
+        const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
+        if (pr == 1) return die("preview");
+        if (pr) { m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; }
+    }
     const auto t4 = Clock::now();
     std::printf("%s: %u mesh(es), %llu triangles, density %u -> %llu Gaussians (%llu stored) -> %s (format %ld)\n", o.in.c_str(),
                 m2s_host_scene_num_meshes(scene), (unsigned long long)m2s_num_triangles(ctx), R, (unsigned long long)total,
@@ -423,6 +561,11 @@ int main(int argc, char** argv) {
         else if (a == "--out") o.out_dir = next();
         else if (a == "--pipeline") o.pipeline = std::string(next()) == "multipass" ? M2S_PIPELINE_MULTIPASS : M2S_PIPELINE_AUTO;
         else if (a == "--timing") o.timing = true;
+        else if (a == "--preview") o.preview = next();
+        else if (a == "--preview-size") {
+            if (std::sscanf(next(), "%dx%d", &o.preview_w, &o.preview_h) != 2 || o.preview_w < 1 || o.preview_h < 1 || o.preview_w > 8192 ||
+                o.preview_h > 8192) { usage(); return 2; }
+        }
         else if (!a.empty() && a[0] == '-') { usage(); return 2; }
         else pos.push_back(a);
     }
