@@ -30,15 +30,20 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
     m2s_ctx::Slot& sl = c->slot[k];
     const uint64_t cap = resolve_cap(c, R);
     m2s_ctx::RInfo& ri = rinfo_for(c, R);
-    // Fast path: this scene at this R already converted cleanly with the single kernel (no deferred triangles, so no
-    // host decision between kernels) and the output buffer needs no (re)allocation.
+    uint64_t limit = d_records ? (cap ? std::min(cap, capacity_records) : capacity_records) : cap ? cap : c->records_cap;
+    if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
+    const uint32_t n_start = emit2_slices(limit);
+    // Fast path, enqueued without waiting: this scene at this R already converted cleanly with the single kernel (no deferred
+    // triangles, so no host decision between kernels), or with the multi-pass pipeline, which has no host decision between its
+    // kernels either (work buffers sized; under AUTO and MULTIPASS — a forced single-pass setting that fell back to it converts
+    // synchronously; with kernel timing on it runs synchronously: the per-kernel events are shared); and the output buffer needs no
+    // (re)allocation.
+    const bool mp = ri.form == M2S_PIPELINE_MULTIPASS;
     const bool own_ready = d_records || (c->d_records && c->buf_R[0] == R && (cap ? c->records_cap >= cap : true));
-    const bool fast = c->scene.n_tri > 0 && ri.async_ok && c->pipeline != M2S_PIPELINE_MULTIPASS && !ri.multipass && own_ready;
-    // Multi-pass conversions have no host decision between their four kernels either; once this (scene, R) has been
-    // converted that way (work buffers sized, AUTO decision taken) they are enqueued without waiting as well.
-    // (With kernel timing on they run synchronously: the per-kernel events are shared.)
-    const bool fast_mp = !fast && c->scene.n_tri > 0 && own_ready && !c->profiling && ri.mp_ready &&
-                         (c->pipeline == M2S_PIPELINE_MULTIPASS || (ri.decided && ri.multipass));
+    const bool fast = c->scene.n_tri > 0 && own_ready &&
+                      (mp ? ri.mp_ready && !c->profiling && (c->pipeline == M2S_PIPELINE_AUTO || c->pipeline == M2S_PIPELINE_MULTIPASS) &&
+                                c->start_cap >= n_start && c->d_setup
+                          : ri.async_ok);
     sl.R = R;
     sl.wrote_bands = false;
     sl.own_lane = d_records ? -1 : 0;
@@ -56,46 +61,6 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
         }
         return hipSuccess;
     };
-    if (fast_mp) {
-        HIPCHK(c, hipSetDevice(c->device));
-        uint64_t limit;
-        void* d_out;
-        if (d_records) { limit = cap ? std::min(cap, capacity_records) : capacity_records; d_out = d_records; }
-        else { limit = cap ? cap : c->records_cap; d_out = c->d_records; }
-        if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
-        const uint32_t n_start = emit2_slices(limit);
-        if (c->start_cap >= n_start && c->d_setup) {
-            // odd slots of a two-lane context: the second lane, with work buffers of its own — nothing is shared with the
-            // conversion before it, so its k_count_scan runs beside that conversion's k_emit2
-            bool second_lane = false;
-            if (!d_records && (k & 1u) && c->lanes == 2) {
-                { const m2s_status s2 = ensure_second_lane(c); if (s2 != M2S_OK) return s2; }
-                { const m2s_status s2 = ensure_second_lane_multipass(c, n_start); if (s2 != M2S_OK) return s2; }
-                st = c->stream_b;
-                d_out = c->d_records_b;
-                second_lane = true;
-                sl.own_lane = 1;
-            }
-            if (!second_lane) HIPCHK(c, chain_behind_newest(st));
-            if (sl.own_lane >= 0) {
-                if (c->buf_R[sl.own_lane] != R) { c->buf_R[sl.own_lane] = R; ++c->buf_gen[sl.own_lane]; }
-                sl.gen = c->buf_gen[sl.own_lane];
-            }
-            unsigned long long* res = &c->h_total[2 + 2 * k];
-            res[0] = 0; res[1] = 0;
-            { const m2s_status ms_ = enqueue_multipass(c, R, (float4*)d_out, limit, false, res, st, second_lane); if (ms_ != M2S_OK) return ms_; }
-            HIPCHK(c, hipEventRecord(sl.done, st));
-            c->last_pipeline = M2S_PIPELINE_MULTIPASS;
-            if (!second_lane) c->last_submit_stream = st;
-            sl.prof = false;
-            sl.sync_result = false;
-            sl.limit = limit;
-            sl.d_out = d_out;
-            sl.st = st; sl.shared_work = !second_lane; sl.ri_gen = ri.gen;
-            ++c->slot_count;
-            return M2S_OK;
-        }
-    }
     if (!fast) {
         // first conversion of a (scene, R), or one that needs the second stage / the multi-pass pipeline: run it now
         // (run_pass first lets everything in flight finish: it may re-allocate the record pool and reuses the work buffers)
@@ -113,26 +78,21 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
         return M2S_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    uint64_t limit;
-    void* d_out;
+    void* d_out = d_records ? d_records : c->d_records;
     unsigned long long* chain = c->d_chain;
     bool second_lane = false;
-    if (d_records) { limit = cap ? std::min(cap, capacity_records) : capacity_records; d_out = d_records; }
-    else {
-        limit = cap ? cap : c->records_cap;
-        d_out = c->d_records;
-        if ((k & 1u) && c->lanes == 2) {
-            // odd slots: the second lane (allocated on first use).  Records of consecutive conversions then alternate
-            // between two context-owned buffers; m2s_device_records / m2s_download follow the conversion last waited for.
-            { const m2s_status s2 = ensure_second_lane(c); if (s2 != M2S_OK) return s2; }
-            st = c->stream_b;
-            chain = c->d_chain_b;
-            d_out = c->d_records_b;
-            second_lane = true;
-            sl.own_lane = 1;
-        }
+    if (!d_records && (k & 1u) && c->lanes == 2) {
+        // odd slots: the second lane (allocated on first use), with work buffers of its own — nothing is shared with the conversion
+        // before it, so its kernels run beside that conversion's tail.  Records of consecutive conversions then alternate between
+        // two context-owned buffers; m2s_device_records / m2s_download follow the conversion last waited for.
+        { const m2s_status s2 = ensure_second_lane(c); if (s2 != M2S_OK) return s2; }
+        if (mp) { const m2s_status s2 = ensure_second_lane_multipass(c, n_start); if (s2 != M2S_OK) return s2; }
+        st = c->stream_b;
+        chain = c->d_chain_b;
+        d_out = c->d_records_b;
+        second_lane = true;
+        sl.own_lane = 1;
     }
-    if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
     // (every submission that uses the shared chain is ordered behind the newest one that did, whatever stream that ran on — a
     //  first-lane submission after a conversion into a caller's buffer on the caller's stream included: ADVICE r2)
     if (!second_lane) HIPCHK(c, chain_behind_newest(st));
@@ -143,22 +103,21 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
     unsigned long long* res = &c->h_total[2 + 2 * k];
     res[0] = 0; res[1] = 0;
     sl.prof = c->profiling;
-    uint32_t epoch;
-    HIPCHK(c, next_epoch(c, &epoch));
-    if (sl.prof) HIPCHK(c, hipEventRecord(sl.t0, st));
-    const bool sparse = use_sparse(c, ri);
-    const bool lean = !sparse && use_lean(c, ri);
-    c->last_pipeline = sparse ? M2S_PIPELINE_SPARSE : lean ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
-    sl.bands_unit = sparse ? kSparseTrianglesPerWorkgroup : 256u;
-    if (sparse) launch_sparse(c->scene, R, chain, limit, (float4*)d_out, &res[0], reinterpret_cast<uint32_t*>(&res[1]), epoch,
-                              c->d_biglist, c->d_bigmeta, bands_for(c, ri, sl.bands_unit, !second_lane && c->lanes == 1, &sl.wrote_bands), st);
-    else if (lean) launch_fused3(c->scene, R, chain, limit, (float4*)d_out, &res[0], reinterpret_cast<uint32_t*>(&res[1]), epoch,
-                            c->d_biglist, c->d_bigmeta, bands_for(c, ri, sl.bands_unit, !second_lane && c->lanes == 1, &sl.wrote_bands), batches_for(c, ri), st);
-    else launch_fused2(c->scene, R, chain, limit, (float4*)d_out, &res[0], reinterpret_cast<uint32_t*>(&res[1]), epoch,
-                       c->d_biglist, c->d_bigmeta, bands_for(c, ri, sl.bands_unit, !second_lane && c->lanes == 1, &sl.wrote_bands), batches_for(c, ri), st);
-    if (sl.prof) HIPCHK(c, hipEventRecord(sl.t1, st));
-    HIPCHK(c, hipGetLastError());
+    if (mp) {
+        const m2s_status s = enqueue_multipass(c, R, (float4*)d_out, limit, false, res, st, second_lane);
+        if (s != M2S_OK) return s;
+    } else {
+        uint32_t epoch;
+        HIPCHK(c, next_epoch(c, &epoch));
+        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t0, st));
+        sl.bands_unit = unit_of(ri.form);
+        launch_single(c, ri, R, chain, limit, (float4*)d_out, res, epoch, bands_for(c, ri, sl.bands_unit, !second_lane && c->lanes == 1, &sl.wrote_bands),
+                      st, nullptr);
+        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t1, st));
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipEventRecord(sl.done, st));
+    c->last_pipeline = ri.form;
     if (!second_lane) c->last_submit_stream = st;
     sl.st = st; sl.shared_work = !second_lane; sl.ri_gen = ri.gen;
     sl.sync_result = false;

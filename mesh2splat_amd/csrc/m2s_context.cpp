@@ -47,8 +47,8 @@ void free_scene(m2s_ctx* c) {
     c->has_scene = false;
 }
 
-// What is remembered about this scene at resolution R (created on first use; the table is bounded: a slider dragged
-// through hundreds of densities simply starts over).
+// What is remembered about this scene at resolution R (created on first use, its form decided before its first launch: decide in
+// m2s_pass.cpp; the table is bounded: a slider dragged through hundreds of densities simply starts over).
 m2s_ctx::RInfo& rinfo_for(m2s_ctx* c, uint32_t R) {
     auto it = c->rinfo.find(R);
     if (it != c->rinfo.end()) return it->second;
@@ -59,10 +59,6 @@ m2s_ctx::RInfo& rinfo_for(m2s_ctx* c, uint32_t R) {
     m2s_ctx::RInfo ri;
     ri.gen = c->rinfo_gen;
     ri.band_slot = (int)c->rinfo.size();
-    ri.sparse_off = R >= c->sparse_off_R;
-    ri.team_off = R >= c->team_off_R;
-    if (ri.team_off) ri.multipass = true;       // (decide() keeps it; a forced single-pass setting hands such an R to the multi-pass pipeline)
-    ri.lean_off = R >= c->lean_off_R;
     return c->rinfo.emplace(R, ri).first->second;
 }
 

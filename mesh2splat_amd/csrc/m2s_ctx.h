@@ -57,13 +57,9 @@ struct m2s_ctx {
     // before, so nothing here may be REQUIRED for a fast conversion: a new R costs no counting pass and no extra host
     // round trip (the AUTO decision is taken from frag_per_R2, the band bases are a by-product of the first launch).
     struct RInfo {
-        bool decided = false;      // AUTO: single-pass / multi-pass decision taken
-        bool multipass = false;    // ... and it was "multi-pass"
-        bool sparse = false;       // AUTO: fewer fragments than triangles, the sparse form of the single-pass kernel (k_sparse)
-        bool sparse_off = false;   // k_sparse reported a workgroup that did not fit its LDS stream: use k_fused2
-        bool team_off = false;     // k_fused2 reported a workgroup that did not fit its LDS stream: the multi-pass pipeline from this R on
+        int form = M2S_PIPELINE_AUTO;   // what the next conversion at this R runs: M2S_PIPELINE_SPARSE / _LEAN / _TEAM / _MULTIPASS
+                                        // (m2s_pass.cpp: decide() sets it, demote() moves it down the ladder); AUTO: not decided yet
         uint32_t tpw = 0;          // AUTO: k_fused2 in batches of this many triangles (0: fused_tpw) — the 11-18 fragments-per-triangle band
-        bool lean_off = false;     // k_fused3 overflowed its LDS stream or deferred many triangles at this R: use k_fused2
         bool async_ok = false;     // a completed conversion needed no host decision between kernels
         bool mp_ready = false;     // a multi-pass conversion has completed (its work buffers are sized)
         bool bands_ready = false;  // the run table of this R (slot band_slot of d_bands: where every run's output starts) is in place ...
@@ -71,9 +67,10 @@ struct m2s_ctx {
         int band_slot = 0;
         uint32_t gen = 0;          // generation of the table this entry belongs to (the table starts over when it is full)
     };
-    // smallest R at which a workgroup of k_sparse / k_fused2 did not fit its LDS stream: a property of the SCENE (fragments grow
-    // with R), so a new R above it starts with the next form at once instead of re-discovering the overflow
-    uint32_t sparse_off_R = UINT32_MAX, team_off_R = UINT32_MAX, lean_off_R = UINT32_MAX;   // (lean: k_fused3 -> k_fused2)
+    // smallest R at which a workgroup of k_sparse / k_fused3 / k_fused2 did not fit its LDS stream (k_fused3: or deferred many
+    // triangles): a property of the SCENE (fragments grow with R), so a new R above it starts with the next form at once instead
+    // of re-discovering the overflow (demote() lowers them, decide() applies them)
+    uint32_t sparse_off_R = UINT32_MAX, team_off_R = UINT32_MAX, lean_off_R = UINT32_MAX;
     uint32_t rinfo_gen = 0;
     std::map<uint32_t, RInfo> rinfo;
     double frag_per_R2 = -1.0;              // fragments / R^2 of this scene: from the exact count m2s_upload_scene takes (warm_scene), refreshed by every conversion
@@ -230,9 +227,9 @@ m2s_status ensure_records(m2s_ctx* c, uint64_t want);
 // m2s_upload.cpp
 m2s_status ensure_stage(m2s_ctx* c);
 // m2s_pass.cpp
-bool use_team(const m2s_ctx* c, const m2s_ctx::RInfo& ri);
-bool use_lean(const m2s_ctx* c, const m2s_ctx::RInfo& ri);   // the team kernel in its lean form (k_fused3)
-bool use_sparse(const m2s_ctx* c, const m2s_ctx::RInfo& ri);
+uint32_t unit_of(int form);   // triangles per band unit of a single-pass form
+void launch_single(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t R, unsigned long long* chain, uint64_t limit, float4* d_out,
+                   unsigned long long* res, uint32_t epoch, const m2s::RunInfo& runs, hipStream_t st, float4* plane);
 m2s::RunInfo bands_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t unit, bool may_write, bool* writes);
 m2s::BatchTable batches_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri);
 uint64_t resolve_cap(const m2s_ctx* c, uint32_t R);

@@ -32,26 +32,6 @@ static uint32_t band_workgroups(const m2s_ctx* c, uint32_t unit) {
 }  // namespace
 
 namespace m2s_host {
-// The single-pass kernel is the workgroup-cooperative one (m2s_fused2.hip / its lean and sparse forms).  A scene whose workgroups did
-// not fit its LDS stream at this R (team_off) belongs to the multi-pass pipeline from then on (rinfo_for / decide set ri.multipass):
-// the one-wave-per-batch form that used to answer such scenes (k_fused, rounds 1-5) was slower there than the multi-pass pipeline
-// and is gone (round 6).
-bool use_team(const m2s_ctx*, const m2s_ctx::RInfo& ri) {
-    return !ri.team_off;
-}
-// the team kernel in its lean form (m2s_fused3.hip): LEAN uses it where the scene allows it (m2s_ctx::lean_ok) unless a launch at
-// this R overflowed its LDS stream; AUTO only for scenes of more than one generation of workgroups (64 triangles per wave: a fourth
-// workgroup per CU does nothing for a launch that fits the GPU once — C2 stand-in 0.0354 (k_fused2) vs 0.0362 ms, config 3 0.1170 vs
-// 0.1138, profiles/r05/ab_lean_team_kernel.log) and while few triangles are deferred
-bool use_lean(const m2s_ctx* c, const m2s_ctx::RInfo& ri) {
-    if (!(use_team(c, ri) && c->lean_ok && !ri.lean_off) || ri.tpw || debug_on("M2S_NO_LEAN")) return false;
-    return c->pipeline == M2S_PIPELINE_LEAN || (c->pipeline == M2S_PIPELINE_AUTO && fused_tpw(c->scene.n_tri) == 64u);
-}
-// ... or its sparse form (m2s_sparse.hip): meshes with fewer fragments than triangles, large enough for 64-triangle batches
-bool use_sparse(const m2s_ctx* c, const m2s_ctx::RInfo& ri) {
-    return (c->pipeline == M2S_PIPELINE_SPARSE || (c->pipeline == M2S_PIPELINE_AUTO && ri.sparse)) && !ri.sparse_off &&
-           sparse_supported(c->scene.n_tri);
-}
 RunInfo bands_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t unit, bool may_write, bool* writes) {
     RunInfo r{ nullptr, nullptr, 0u, nullptr };
     if (writes) *writes = false;
@@ -74,6 +54,21 @@ BatchTable batches_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri) {
     return c->n_batch_tab ? BatchTable{ c->d_batch_first, c->n_batch_tab, 0u } : BatchTable{ nullptr, 0u, ri.tpw };
 }
 
+uint32_t unit_of(int form) { return form == M2S_PIPELINE_SPARSE ? kSparseTrianglesPerWorkgroup : 256u; }
+
+// One launch of the single-pass form ri.form: the kernel writes its fragment counter to res[0] and its two status words to res[1]
+// (pinned host memory).  Only k_sparse takes the position plane.
+void launch_single(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t R, unsigned long long* chain, uint64_t limit, float4* d_out,
+                   unsigned long long* res, uint32_t epoch, const RunInfo& runs, hipStream_t st, float4* plane) {
+    uint32_t* status = reinterpret_cast<uint32_t*>(&res[1]);
+    if (ri.form == M2S_PIPELINE_SPARSE)
+        launch_sparse(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, st, plane);
+    else if (ri.form == M2S_PIPELINE_LEAN)
+        launch_fused3(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
+    else
+        launch_fused2(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
+}
+
 uint64_t resolve_cap(const m2s_ctx* c, uint32_t R) {
     if (c->cap_policy == 0) return 0;
     if (c->cap_policy > 0) return (uint64_t)c->cap_policy;
@@ -84,8 +79,18 @@ uint64_t resolve_cap(const m2s_ctx* c, uint32_t R) {
 }
 }  // namespace m2s_host
 
-// AUTO's decision for this scene at R from its (exact or predicted) fragment count.
-// The single-pass kernel wins while triangles are small (it does the per-triangle work once and needs no second
+// The team kernel in its lean form (m2s_fused3.hip): LEAN uses it where the scene allows it (m2s_ctx::lean_ok) below the R at which
+// it overflowed its LDS stream or deferred many triangles; AUTO only for scenes of more than one generation of workgroups (64
+// triangles per wave: a fourth workgroup per CU does nothing for a launch that fits the GPU once — C2 stand-in 0.0354 (k_fused2) vs
+// 0.0362 ms, config 3 0.1170 vs 0.1138, profiles/r05/ab_lean_team_kernel.log)
+static bool lean_eligible(const m2s_ctx* c, uint32_t R) {
+    if (!c->lean_ok || R >= c->lean_off_R || debug_on("M2S_NO_LEAN")) return false;
+    return c->pipeline == M2S_PIPELINE_LEAN || (c->pipeline == M2S_PIPELINE_AUTO && fused_tpw(c->scene.n_tri) == 64u);
+}
+
+// The starting form of this scene at R: the setting's, or AUTO's from the (exact or predicted) fragment count; a form whose
+// threshold (m2s_ctx::*_off_R) is at or below R is passed over.
+// AUTO: the single-pass kernel wins while triangles are small (it does the per-triangle work once and needs no second
 // sweep); with more than ~11 fragments per triangle on average the output-partitioned multi-pass pipeline is
 // faster and soon much faster (2.74 M fragments at R = 1024 from 1 M / 250 k / 125 k / 62 k triangles: fused 0.167 /
 // 0.138 / 0.323 / 0.626 ms, multi-pass 0.214 / 0.137 / 0.136 / 0.154 ms; tools/auto_probe.py).
@@ -98,17 +103,57 @@ uint64_t resolve_cap(const m2s_ctx* c, uint32_t R) {
 // 96 fragments — which a single-pass kernel defers — hold less than an eighth of the fragments: a scene whose MEAN falls in the band
 // because it mixes planes with foliage (synth.sponza_like: 16 per triangle) belongs to the multi-pass pipeline and its fine blocks.
 static void decide(const m2s_ctx* c, m2s_ctx::RInfo& ri, double frags, uint32_t R) {
-    ri.decided = true;
-    ri.multipass = frags >= 11.0 * (double)c->scene.n_tri || ri.team_off;
+    const double n_tri = (double)c->scene.n_tri;
     ri.tpw = 0;
-    if (ri.multipass && frags < 13.0 * (double)c->scene.n_tri && R == c->warm_R && c->warm_total > 0 && c->warm_big * 8ull < c->warm_total &&
-        fused_tpw(c->scene.n_tri) == 64u && !c->n_batch_tab && c->team_off_R > R && !debug_on("M2S_NO_BAND_TPW")) {
-        ri.multipass = false;
-        ri.tpw = 40;
+    ri.form = M2S_PIPELINE_MULTIPASS;
+    if (c->pipeline == M2S_PIPELINE_MULTIPASS || R >= c->team_off_R) return;
+    if (c->pipeline == M2S_PIPELINE_AUTO && frags >= 11.0 * n_tri) {
+        if (frags < 13.0 * n_tri && R == c->warm_R && c->warm_total > 0 && c->warm_big * 8ull < c->warm_total &&
+            fused_tpw(c->scene.n_tri) == 64u && !c->n_batch_tab && !debug_on("M2S_NO_BAND_TPW")) {
+            ri.form = M2S_PIPELINE_TEAM;
+            ri.tpw = 40;
+        }
+        return;
     }
     // about as many fragments as triangles, or fewer: many triangles cover no pixel centre, the sparse form drops them cheaply
-    // (crossover measured with tools/sparse_probe.py: see DESIGN.md)
-    ri.sparse = !ri.multipass && frags < sparse_frags_per_triangle(c->scene.n_tri) * (double)c->scene.n_tri && !debug_on("M2S_NO_SPARSE");
+    // (crossover measured with tools/sparse_probe.py: see DESIGN.md); it needs scenes large enough for 64-triangle batches
+    const bool sparse = c->pipeline == M2S_PIPELINE_SPARSE ||
+                        (c->pipeline == M2S_PIPELINE_AUTO && frags < sparse_frags_per_triangle(c->scene.n_tri) * n_tri && !debug_on("M2S_NO_SPARSE"));
+    if (sparse && R < c->sparse_off_R && sparse_supported(c->scene.n_tri)) ri.form = M2S_PIPELINE_SPARSE;
+    else ri.form = lean_eligible(c, R) ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
+}
+
+// What a single-pass launch ran into (run_pass): status 2, a workgroup's entries did not fit the kernel's LDS stream (true of every
+// larger R as well); any other status, a bounded look-back wait gave up (never observed; would need a dispatcher that starves earlier
+// workgroups); many triangles deferred by AUTO's k_fused3; deferred triangles holding much of the output
+enum class Trouble { full, stalled, lean_defers, big_share };
+
+// The ladder: demote() is the only code that moves a (scene, R) down it, after a launch of ri.form ran into `why`.
+//
+//   ri.form  why                          next form                            remembered for every larger R
+//   SPARSE   full / stalled               LEAN if lean_eligible, else TEAM     full: sparse_off_R
+//   LEAN     full / stalled               TEAM                                 full: lean_off_R
+//   LEAN     lean_defers                  TEAM                                 lean_off_R
+//   TEAM     full / stalled, tpw != 0     MULTIPASS, tpw = 0                   -
+//   TEAM     full / stalled               MULTIPASS                            full: team_off_R
+//   any      big_share                    MULTIPASS                            -
+//
+// The multi-pass pipeline has neither limit; it is where every (scene, R) can end.
+static void demote(m2s_ctx* c, m2s_ctx::RInfo& ri, uint32_t R, Trouble why) {
+    const bool every_larger_R = why == Trouble::full || why == Trouble::lean_defers;
+    if (why == Trouble::big_share) {
+        ri.form = M2S_PIPELINE_MULTIPASS;
+    } else if (ri.form == M2S_PIPELINE_SPARSE) {
+        if (every_larger_R) c->sparse_off_R = std::min(c->sparse_off_R, R);
+        ri.form = lean_eligible(c, R) ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
+    } else if (ri.form == M2S_PIPELINE_LEAN) {
+        if (every_larger_R) c->lean_off_R = std::min(c->lean_off_R, R);
+        ri.form = M2S_PIPELINE_TEAM;
+    } else {
+        if (ri.tpw) ri.tpw = 0;
+        else if (every_larger_R) c->team_off_R = std::min(c->team_off_R, R);
+        ri.form = M2S_PIPELINE_MULTIPASS;
+    }
 }
 
 static m2s_status ensure_multipass_buffers(m2s_ctx* c, uint64_t limit);
@@ -138,14 +183,15 @@ m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R) {
     c->warm_spec_unit = 0;
     if (!debug_on("M2S_NO_WARM_BANDS")) {
         m2s_ctx::RInfo& ri = rinfo_for(c, R);
+        const uint32_t unit = unit_of(M2S_PIPELINE_TEAM);
         bool writes = false;
-        const RunInfo table = bands_for(c, ri, 256u, true, &writes);
+        const RunInfo table = bands_for(c, ri, unit, true, &writes);
         if (writes) {
-            const uint32_t n_units = band_workgroups(c, 256u);
-            launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, 256u, table.shift, table.out, st);
+            const uint32_t n_units = band_workgroups(c, unit);
+            launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, unit, table.shift, table.out, st);
             launch_run_order(table.out, n_runs(n_units, table.shift), c->d_total, c->d_run_order, run_order_slots(n_units, table.shift), st);
             HIPCHK(c, hipGetLastError());
-            c->warm_spec_unit = 256u; c->warm_spec_shift = table.shift;
+            c->warm_spec_unit = unit; c->warm_spec_shift = table.shift;
         }
     }
     return M2S_OK;
@@ -213,20 +259,20 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
         } catch (...) { /* no table: uniform batches */ }
     }
     m2s_ctx::RInfo& ri = rinfo_for(c, R);
-    if (c->pipeline == M2S_PIPELINE_AUTO && !ri.decided) decide(c, ri, (double)total, R);
+    if (ri.form == M2S_PIPELINE_AUTO) decide(c, ri, (double)total, R);
     const uint64_t cap = resolve_cap(c, R);
-    const bool single = c->pipeline != M2S_PIPELINE_MULTIPASS && !ri.multipass;
+    const bool single = ri.form != M2S_PIPELINE_MULTIPASS;
     // the code object of the pipeline this scene is about to run: loaded here, not inside the first conversion of the process
     if (!debug_on("M2S_NO_PRELOAD")) {
         if (!single) { (void)preload_multipass(); if (!debug_on("M2S_NO_SCRATCH_WARM")) launch_scratch_warm(st); }
-        else if (use_sparse(c, ri)) { (void)preload_sparse(); (void)preload_fused2(); }   // (the sparse form falls back to the team on a stream overflow)
-        else if (use_lean(c, ri)) { (void)preload_fused3(); }
+        else if (ri.form == M2S_PIPELINE_SPARSE) { (void)preload_sparse(); (void)preload_fused2(); }   // (the sparse form falls back to the team on a stream overflow)
+        else if (ri.form == M2S_PIPELINE_LEAN) { (void)preload_fused3(); }
         else { (void)preload_fused2(); }
         (void)hipGetLastError();
     }
-    if (single && (use_sparse(c, ri) || use_team(c, ri)) && !debug_on("M2S_NO_WARM_BANDS")) {
+    if (single && !debug_on("M2S_NO_WARM_BANDS")) {
         // the run table of the first launch at R, from the exact counts (the same table a launch without runs leaves behind)
-        const uint32_t unit = use_sparse(c, ri) ? kSparseTrianglesPerWorkgroup : 256u;
+        const uint32_t unit = unit_of(ri.form);
         bool writes = false;
         const RunInfo table = bands_for(c, ri, unit, true, &writes);
         if (writes) {
@@ -397,7 +443,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     }
     m2s_ctx::RInfo& ri = rinfo_for(c, R);
 
-    // ---- AUTO: which pipeline for this scene at this R? ---------------------------------------------
+    // ---- which form for this scene at this R (decide; AUTO: from the fragment count)? -------------------
     // The fragment count of a scene is proportional to R^2 (window coordinates scale with R), so the ONE exact count
     // m2s_upload_scene took (warm_scene) decides for every R without touching the device: the threshold is not sharp, and
     // all pipelines produce the same bytes anyway.
@@ -406,7 +452,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
         if (s != M2S_OK) return s;
     }
     const double predicted = c->frag_per_R2 * (double)R * (double)R;
-    if (c->pipeline == M2S_PIPELINE_AUTO && !ri.decided) decide(c, ri, predicted, R);
+    if (ri.form == M2S_PIPELINE_AUTO) decide(c, ri, predicted, R);
 
     // ---- where do the records go, and how many may be stored? ------------------------------------
     uint64_t limit;
@@ -425,31 +471,33 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
 
     bool wrote_plane = false;      // the last single-pass launch also wrote the position plane (k_sparse, m2s_set_keep_positions)
-    for (int round = 0; round < 2; ++round) {
-    // ---- run ---------------------------------------------------------------------------------------
-    bool done = false;
-    if (c->pipeline != M2S_PIPELINE_MULTIPASS && !ri.multipass) {
-        // single-pass kernel; triangles too large for its in-workgroup budget are only counted.
-        // No memset, no memcpy: the look-back chain is epoch-tagged and the kernel writes the fragment
-        // counter and its two status words straight into pinned host memory.
-        uint32_t any_big = 0, err = 0;
-        bool wrote_bands = false;
-        wrote_plane = false;
-        for (int attempt = 0; attempt < 4; ++attempt) {
-            const bool sparse = use_sparse(c, ri);
-            const bool team = !sparse;
-            const bool lean = team && use_lean(c, ri);
+    bool grown = false;
+    // ---- run: one launch of ri.form per pass.  Trouble moves ri.form down the ladder (demote) and the next pass runs that.  At
+    // most nine passes: a repeat after a run-table mismatch (once per context), sparse -> lean -> team -> multi-pass, and those
+    // four again after the pool has grown.
+    for (int pass = 0;; ++pass) {
+        if (pass == 9) return fail(c, M2S_ERR_STATE, "conversion pass: no pipeline settled");
+        if (ri.form == M2S_PIPELINE_MULTIPASS) {
+            const m2s_status s = run_multipass(c, R, d_out, limit, st);
+            if (s != M2S_OK) return s;
+            ri.mp_ready = true;
+            c->last_pipeline = M2S_PIPELINE_MULTIPASS;
+        } else {
+            // single-pass kernel; triangles too large for its in-workgroup budget are only counted.
+            // No memset, no memcpy: the look-back chain is epoch-tagged and the kernel writes the fragment
+            // counter and its two status words straight into pinned host memory.
             c->h_total[0] = 0;
             c->h_total[1] = 0;
             uint32_t epoch;
             HIPCHK(c, next_epoch(c, &epoch));
             if (prof) HIPCHK(c, hipEventRecord(c->ev[5], st));
-            const uint32_t unit = sparse ? kSparseTrianglesPerWorkgroup : 256u;
+            const uint32_t unit = unit_of(ri.form);
+            bool wrote_bands = false;
             const RunInfo runs = bands_for(c, ri, unit, true, &wrote_bands);
             // m2s_set_keep_positions: the sparse kernel — the one that runs on scenes of tens of millions of records, where a depth sort
             // is worth preparing for — also writes the records' positions as a 16-byte plane (the context's, grown here if need be)
             float4* plane = nullptr;
-            if (sparse && c->keep_positions && st == c->stream) {
+            if (ri.form == M2S_PIPELINE_SPARSE && c->keep_positions && st == c->stream) {
                 if (c->pos_plane_cap < limit) {
                     if (c->d_pos_plane) { (void)hipFree(c->d_pos_plane); c->d_pos_plane = nullptr; c->pos_plane_cap = 0; }
                     if (hipMalloc(&c->d_pos_plane, limit * 16) == hipSuccess) c->pos_plane_cap = limit; else (void)hipGetLastError();
@@ -458,19 +506,14 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
                 plane = (float4*)c->d_pos_plane;
             }
             wrote_plane = plane != nullptr;
-            if (sparse) launch_sparse(sc, R, c->d_chain, limit, d_out, &c->h_total[0], reinterpret_cast<uint32_t*>(&c->h_total[1]), epoch,
-                                      c->d_biglist, c->d_bigmeta, runs, st, plane);
-            else if (lean) launch_fused3(sc, R, c->d_chain, limit, d_out, &c->h_total[0], reinterpret_cast<uint32_t*>(&c->h_total[1]), epoch,
-                                    c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
-            else launch_fused2(sc, R, c->d_chain, limit, d_out, &c->h_total[0], reinterpret_cast<uint32_t*>(&c->h_total[1]), epoch,
-                               c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
+            launch_single(c, ri, R, c->d_chain, limit, d_out, c->h_total, epoch, runs, st, plane);
             if (prof) HIPCHK(c, hipEventRecord(c->ev[6], st));
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, wait_stream(st));  // glFinish + counter read-back (ConversionPass.cpp:54-59)
             if (prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_FUSED], c->ev[5], c->ev[6]));
-            any_big = (uint32_t)(c->h_total[1] & 0xFFFFFFFFull);
-            err = (uint32_t)(c->h_total[1] >> 32);
-            c->last_pipeline = sparse ? M2S_PIPELINE_SPARSE : lean ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
+            const uint32_t any_big = (uint32_t)(c->h_total[1] & 0xFFFFFFFFull);
+            const uint32_t err = (uint32_t)(c->h_total[1] >> 32);
+            c->last_pipeline = ri.form;
             if (!err && wrote_bands) { ri.bands_ready = true; ri.bands_unit = unit; }
             // A launch in runs trusts the run table: at the R the scene was counted at (warm_scene), that table comes from k_count's
             // counts, not from a launch of this kernel.  The two must agree on every triangle; if the totals ever differ, the table is
@@ -483,56 +526,36 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
                 HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), st));
                 continue;
             }
-            if (err && debug_on("M2S_DEBUG"))
-                fprintf(stderr, "[m2s] single-pass kernel (%s) reported 0x%x at R = %u: trying the next form\n", sparse ? "sparse" : lean ? "lean" : "team", err, R);
-            if (lean && !err && any_big && c->pipeline == M2S_PIPELINE_AUTO) {
-                // k_fused3 shades only triangles of at most 8 x 8 pixels itself.  A few deferred ones are what k_emit_big is for;
-                // MANY mean the scene at this R belongs to k_fused2, which expands triangles of up to 16 pixel rows in the
-                // workgroup: remember that (for this R and every larger one) and convert again
+            // a clean single-kernel conversion: the same scene at the same R can be submitted asynchronously from now on
+            ri.async_ok = !err && !any_big;
+            if (err) {
+                if (debug_on("M2S_DEBUG")) fprintf(stderr, "[m2s] single-pass kernel (form %d) reported 0x%x at R = %u: trying the next form\n", ri.form, err, R);
+                demote(c, ri, R, (err & 0xFu) == 2u ? Trouble::full : Trouble::stalled);
+                HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), st));   // forget what the aborted launch listed
+                continue;
+            }
+            if (any_big) {
                 uint32_t meta[4] = { 0, 0, 0, 0 };
+                if (ri.form == M2S_PIPELINE_LEAN && c->pipeline == M2S_PIPELINE_AUTO) {
+                    // k_fused3 shades only triangles of at most 8 x 8 pixels itself.  A few deferred ones are what k_emit_big is for;
+                    // MANY mean the scene at this R belongs to k_fused2
+                    HIPCHK(c, hipMemcpyAsync(meta, c->d_bigmeta, sizeof meta, hipMemcpyDeviceToHost, st));
+                    HIPCHK(c, hipStreamSynchronize(st));
+                    if (meta[0] > 64u && (uint64_t)meta[0] * 256u > sc.n_tri) {
+                        demote(c, ri, R, Trouble::lean_defers);
+                        HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, sizeof meta, st));
+                        continue;
+                    }
+                }
                 HIPCHK(c, hipMemcpyAsync(meta, c->d_bigmeta, sizeof meta, hipMemcpyDeviceToHost, st));
                 HIPCHK(c, hipStreamSynchronize(st));
-                if (meta[0] > 64u && (uint64_t)meta[0] * 256u > sc.n_tri) {
-                    ri.lean_off = true;
-                    c->lean_off_R = std::min(c->lean_off_R, R);
-                    HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, sizeof meta, st));
+                HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, sizeof meta, st));   // restore the "zero between conversions" invariant
+                if (meta[0] > 256 && (uint64_t)meta[2] * 8 > c->h_total[0]) {
+                    // Scene dominated by mid-size / big triangles (e.g. a coarse mesh at high density): the output-partitioned
+                    // multi-pass pipeline packs them densely
+                    demote(c, ri, R, Trouble::big_share);
                     continue;
                 }
-            }
-            if (!err) break;
-            if (team && ri.tpw) { ri.tpw = 0; break; }   // a scene of the 11-18 band whose workgroups overflow even in small batches: multi-pass (below)
-            // a workgroup's fragments did not fit the kernel's LDS stream (or a wait timed out): sparse -> team, lean -> team,
-            // team -> the multi-pass pipeline, which has no such limit (below: err != 0).  Remember it for this scene and R, forget
-            // what the aborted launch listed, try again.
-            // (error value 2 = "entries do not fit": true of every larger R as well)
-            if (sparse) { ri.sparse_off = true; if ((err & 0xFu) == 2u) c->sparse_off_R = std::min(c->sparse_off_R, R); }
-            else if (lean) { ri.lean_off = true; if ((err & 0xFu) == 2u) c->lean_off_R = std::min(c->lean_off_R, R); }
-            else { ri.team_off = true; if ((err & 0xFu) == 2u) c->team_off_R = std::min(c->team_off_R, R); break; }
-            HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), st));
-        }
-        done = true;
-        // a clean single-kernel conversion: the same scene at the same R can be submitted asynchronously from now on
-        ri.async_ok = !err && !any_big;
-        if (err) {
-            // The team kernel's workgroups do not fit their LDS stream at this R, or the bounded look-back spin gave up (never
-            // observed; would need a dispatcher that starves earlier workgroups): the multi-pass pipeline, which has neither limit.
-            HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), st));
-            ri.multipass = true;
-            done = false;
-        } else
-        if (any_big) {
-            uint32_t meta[4] = { 0, 0, 0, 0 };
-            HIPCHK(c, hipMemcpyAsync(meta, c->d_bigmeta, sizeof meta, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, sizeof meta, st));   // restore the "zero between conversions" invariant
-            const uint64_t total_now = c->h_total[0];
-            if (meta[0] > 256 && (uint64_t)meta[2] * 8 > total_now) {
-                // Scene dominated by mid-size / big triangles (e.g. a coarse mesh at high density): one workgroup per
-                // triangle chunk would be mostly empty.  The output-partitioned multi-pass pipeline packs them densely;
-                // remember the decision so that later conversions of this scene at this R go straight to it.
-                ri.multipass = true;
-                done = false;
-            } else {
                 // second stage: emit exactly the deferred triangles, one workgroup per 1024-fragment chunk
                 if (prof) HIPCHK(c, hipEventRecord(c->ev[3], st));
                 launch_emit_big(sc, R, c->d_biglist, meta[0], meta[1], limit, d_out, st);
@@ -542,23 +565,17 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
                 if (prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_EMIT], c->ev[3], c->ev[4]));
             }
         }
-    }
-    if (!done) {
-        m2s_status s = run_multipass(c, R, d_out, limit, st);
-        if (s != M2S_OK) return s;
-        ri.mp_ready = true;
-        c->last_pipeline = M2S_PIPELINE_MULTIPASS;
-    }
-    // unlimited policy, context-owned buffer: the prediction was too low — make room for the exact count and repeat
-    // (never seen with the 2 % slack; the fragment count scales with R^2 up to clipping at the viewport edge)
-    if (!d_user && !cap && c->h_total[0] > limit && limit < 0xFFFFFFFFull && round == 0) {
-        const m2s_status s = ensure_records(c, c->h_total[0]);
-        if (s != M2S_OK) return s;
-        limit = std::min<uint64_t>(c->records_cap, 0xFFFFFFFFull);
-        d_out = (float4*)c->d_records;
-        continue;
-    }
-    break;
+        // unlimited policy, context-owned buffer: the prediction was too low — make room for the exact count and repeat
+        // (never seen with the 2 % slack; the fragment count scales with R^2 up to clipping at the viewport edge)
+        if (!d_user && !cap && c->h_total[0] > limit && limit < 0xFFFFFFFFull && !grown) {
+            const m2s_status s = ensure_records(c, c->h_total[0]);
+            if (s != M2S_OK) return s;
+            limit = std::min<uint64_t>(c->records_cap, 0xFFFFFFFFull);
+            d_out = (float4*)c->d_records;
+            grown = true;
+            continue;
+        }
+        break;
     }
     const uint64_t total = c->h_total[0];
     if (total > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 fragments: offsets are 32-bit");
