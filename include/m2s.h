@@ -404,6 +404,120 @@ m2s_status m2s_last_splat_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
 /* What the last m2s_splat did: [0] (tile, quad) pairs, [1] fragments blended (after the early exit), [2] quads skipped. */
 m2s_status m2s_last_splat_counts(const m2s_ctx* ctx, uint64_t out[3]);
 
+/* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
+/* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */
+typedef struct m2s_light_params {
+    float light_position[3];     /* pointLightModel[3].xyz -> u_lightPos / u_LightPosition                                       */
+    float light_color[3];        /* pointLightData.lightColor -> u_lightColor                                                   */
+    float light_intensity;       /* pointLightData.lightIntensity -> u_lightIntensity                                           */
+    float camera_position[3];    /* camera position -> u_camPos                                                                 */
+    float near_far[2];           /* nearPlane, farPlane: the cube's glm::perspective and u_farPlane of both passes               */
+    int32_t render_mode;         /* renderMode 0..6 (m2s_relight: 5 = metallic-roughness view, 6 = lit, any other = albedo)      */
+    int32_t resolution[2];       /* rendererResolution: the W x H of the G-buffer m2s_relight lights (m2s_shadow does not read it:
+                                    its u_resolution is m2s_prepass_params.resolution, the same RenderContext member)            */
+    uint32_t shadow_resolution;  /* S, the side of a cube face: 1..4096; 0 = 1024, the reference's SHADOW_CUBEMAP_SIZE           */
+    uint32_t want_shadow_counts; /* m2s_relight, mode 6: also keep the per-pixel count of shadowed PCF taps (0..20)              */
+    uint32_t reserved;           /* 0 */
+} m2s_light_params;
+
+/* == QuadNdcTransformation of gaussianPointShadowMappingCS.glsl:26-30, 48 bytes */
+typedef struct m2s_shadow_quad {
+    float mean2d_ndc[4];     /* clip position through the face's camera, xyz divided by w; w kept */
+    float quad_scale_ndc[4]; /* major axis xy, minor axis xy, in NDC units of the RENDERER's window (see below) */
+    float ws_pos[4];         /* u_modelToWorld * (P, 1) */
+} m2s_shadow_quad;
+
+/* Stage A == gaussianPointShadowMappingCS.glsl:58-207 over `n` records at `d_records` (or the context's records when d_records is
+ * NULL, n ignored — as m2s_prepass): world position; cube face by the dominant axis of normalize(ws - light) with the shader's `if`
+ * chain (|x| >= |y| and |x| >= |z|: x > 0 ? 0 : 1; else |y| >= |x| and |y| >= |z|: y > 0 ? 2 : 3; else z > 0 ? 4 : 5 — every test is
+ * false for NaN, so a NaN direction lands on face 5); that face's camera; the 1.05 w cull; 3D covariance -> 2D covariance (+0.3) ->
+ * eigenvalues; cull on lambda2 < 0; the two axes capped at 1024; appended to the face's list.  fp32 in the shader's operation
+ * order, one rounding per operation — the covariance code is the viewer prepass's own (shared device functions).  Per-record inputs
+ * come from `prepass` (model_to_world, gaussian_std, resolution_target, format, resolution, near_far -> u_nearFar); its two camera
+ * matrices, render mode, depth test and ordering fields are not read.
+ *  - Cameras: glm::lookAt(light, light + axis, up) for (+X, up -Y), (-X, -Y), (+Y, +Z), (-Y, -Z), (+Z, -Y), (-Z, -Y)
+ *    (GaussianShadowPass.cpp:91-108) and glm::perspective(90 degrees, 1, near, far), built in double and rounded to float, with
+ *    `light + axis - light` taken as the axis itself and 1 / tan(45 degrees) as 1: the rotation part is an exact signed permutation
+ *    (no negative zeros), the translation the permuted, negated light position.
+ *  - normalize in determineFaceIndex is v / sqrt((x x + y y) + z z) with correctly rounded root and division: a record exactly at the
+ *    light gives 0 / 0 = NaN, goes to face 5, and is then culled or kept by the tests that follow, as written.
+ * Oddities of the shader carried over as written, because they change pixels:
+ *  - u_resolution is the RENDERER's resolution (GaussianShadowPass.cpp:123) — it scales the Jacobian and converts the axes to NDC —
+ *    while the faces are S x S: quads on the cube are sized for the window, not for the face.
+ *  - modelScale = (|M[0]|, |M[0]|, |M[1]|) (:97).
+ *  - the colour / normal / depth-colour code of :114-151 writes nothing that leaves the shader: not computed.
+ *  - the reference appends through one atomic per record into fixed regions of 7 000 000 quads per face and overruns silently beyond
+ *    that.  Here the six lists are exact-size (grow-only buffer) and each is in INPUT order, like m2s_prepass.
+ * Stage B == drawToCubeMapFaces + gaussianPointLightCubeMapShadow{VS,PS}.glsl: every quad of a face's list drawn as two triangles,
+ * depth test GL_LESS against a cube cleared to 1.0, blending off, gl_FragDepth = length(ws - light) / farPlane (constant over the
+ * quad).  A texel therefore ends as min(1.0, min over the covering quads of d): order-independent and idempotent.  The pin:
+ *  - Geometry exactly as m2s_splat: vertices mean.xy + (vx * scale.xy + vy * scale.zw), (vx, vy) in {(-1,-1), (-1,1), (1,1), (1,-1)},
+ *    triangles (0,1,2) and (0,2,3), the same rounding order, viewport S x S, the project's pinned rasteriser (24.8 snap RNE, int64
+ *    edge functions, both windings, top-left rule, texel centres (x + 0.5, y + 0.5)).  A quad with a non-finite value in mean.xy,
+ *    scale or ws_pos, or with a vertex beyond the +-16384 px guard band, is SKIPPED and counted (*out_skipped).
+ *  - d: (dx, dy, dz) = ws - light; sqrt((dx dx + dy dy) + dz dz) / farPlane, every operation rounded to fp32, root and division
+ *    correctly rounded; clamped to [0, 1] (a NaN d never passes the depth test).
+ *  - Storage: fp32 (the reference asks for an unsized GL_DEPTH_COMPONENT and leaves the bit depth to the driver; fp32 is what it
+ *    uploads and what texture().r returns unchanged): float[6][S][S], faces in GL order +X, -X, +Y, -Y, +Z, -Z, row 0 = window
+ *    row 0 of that face's framebuffer = t = 0 of the face image.
+ * Synchronous.  out_per_face (may be NULL): the six list lengths.  Errors: M2S_ERR_INVALID for a shadow resolution outside 1..4096,
+ * a renderer resolution outside 1..8192, a render mode outside 0..6, reserved != 0, resolution_target == 0; M2S_ERR_STATE without
+ * records; M2S_ERR_CAPACITY beyond 2^31-1 (tile, quad) pairs.  n = 0 with a non-NULL d_records: six empty lists, a cube of 1.0. */
+m2s_status m2s_shadow(m2s_ctx* ctx, const m2s_prepass_params* prepass, const m2s_light_params* light, const void* d_records, uint64_t n,
+                      uint64_t out_per_face[6], uint64_t* out_skipped);
+/* Stage B alone on quad lists made elsewhere (the counterpart of m2s_upload_quads + m2s_splat): `host_quads` holds the six lists back to
+ * back, per_face[f] quads for face f, in face order.  They become the context's lists (m2s_download_shadow_quads) and are drawn into a
+ * cleared cube exactly as m2s_shadow draws its own; `light` gives the light position, farPlane (near_far[1]) and S.  Same errors as
+ * m2s_shadow where they apply; host_quads may be NULL only when every per_face[f] is 0 (a cube of 1.0). */
+m2s_status m2s_shadow_from_quads(m2s_ctx* ctx, const m2s_light_params* light, const m2s_shadow_quad* host_quads, const uint64_t per_face[6],
+                                 uint64_t* out_skipped);
+/* The cube of the last m2s_shadow / m2s_shadow_from_quads / m2s_upload_shadow_cubemap: float[6][S][S] on the device.  NULL before any. */
+const void* m2s_device_shadow_cubemap(const m2s_ctx* ctx);
+m2s_status m2s_download_shadow_cubemap(m2s_ctx* ctx, float* dst, uint64_t capacity_floats);
+/* The list of face 0..5 of the last m2s_shadow, in input order. */
+m2s_status m2s_download_shadow_quads(m2s_ctx* ctx, uint32_t face, m2s_shadow_quad* dst, uint64_t capacity_quads);
+/* A cube made elsewhere (host float[6][S][S], S in 1..4096) becomes the context's cube: what m2s_relight samples. */
+m2s_status m2s_upload_shadow_cubemap(m2s_ctx* ctx, const float* host, uint32_t S);
+/* Duration (ms) of the last profiled m2s_shadow (sum of its stages), and the stages: [0] stage A (count, scan, emit), [1] stage B
+ * setup + binning (tile counts, pairs, radix sort), [2] stage B raster. */
+float m2s_last_shadow_ms(const m2s_ctx* ctx);
+m2s_status m2s_last_shadow_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* What the last m2s_shadow did: [0..5] quads per face, [6] (tile, quad) pairs, [7] texel updates sent, [8] quads skipped. */
+m2s_status m2s_last_shadow_counts(const m2s_ctx* ctx, uint64_t out[9]);
+
+/* ---- relighting pass == GaussianRelightingPass::execute without split screen (GaussianRelightingPass.cpp:136-143) -------------- */
+/* One full-screen draw of gaussianSplattingDeferredPS.glsl over the G-buffer of the last m2s_splat / m2s_upload_gbuffer and the cube
+ * of the last m2s_shadow / m2s_upload_shadow_cubemap into a W x H RGBA8 frame (uchar4 per pixel, row 0 = bottom, like the G-buffer).
+ *  - The G-buffer textures are GL_LINEAR but sampled at texel centres at 1:1: a texel fetch of pixel (x, y).
+ *  - Mode 5: (mr.r, mr.g, 0, 255); every mode other than 5 and 6: (albedo.rgb, 255).  Byte copies: exact.
+ *  - Mode 6: the shader as written, including what looks like mistakes: PI is the MACRO 22.0f/7.0f, so `PI * denom * denom` is
+ *    ((22/7) denom) denom and `kD * albedo / PI` is ((kD albedo) / 22) / 7; metallic = pbr.b (which m2s_splat always leaves 0); ao,
+ *    gDepth, u_isLightingEnalbed, u_worldToView and u_resolution are unused (the depth plane is not read); position and normal are
+ *    taken without dividing by the accumulated alpha; background pixels are lit like any other.
+ *  - computeShadowFactor is decision arithmetic, fp32 operation by operation without contraction: lightDir = pos - light;
+ *    currentDepth = sqrt((x x + y y) + z z); sampleDir = lightDir / currentDepth (component-wise, correctly rounded); for each of the
+ *    20 offsets o (in the shader's order) v = sampleDir + o * 0.025f; the cube texel of v by the GL rule (OpenGL 4.6 core, table 8.19:
+ *    major axis x if |x| >= |y| and |x| >= |z|, else y if |y| >= |z|, else z; negative face when the major coordinate is < 0;
+ *    (sc, tc) = +X (-z, -y), -X (z, -y), +Y (x, z), -Y (x, -z), +Z (x, -y), -Z (-x, -y); s = 0.5 (sc / |ma| + 1), same for t;
+ *    GL_NEAREST, clamp to edge: texel min(max(floor(s S), 0), S - 1); a NaN s or t reads texel (0, 0) of face 5);
+ *    closest = texel * farPlane; the tap counts when currentDepth - 0.05f > closest.  shadow = count / 20.
+ *  - The rest of mode 6 (three pow, the normalisations, GGX, the tone map) is value arithmetic: fp32 without contraction, with the
+ *    device's fast exp2 / log2 / reciprocal square root / square root (as exp is in m2s_splat); max(x, 0.0) keeps a NaN.
+ *  - Output: rint(clamp(c, 0, 1) * 255), NaN -> 0, alpha 255.
+ * Synchronous.  Errors: M2S_ERR_INVALID for a render mode outside 0..6, reserved != 0, a shadow resolution outside 1..4096 or (when
+ * not 0) different from the cube's, `resolution` different from the G-buffer's, or when no G-buffer or no cube exists yet. */
+m2s_status m2s_relight(m2s_ctx* ctx, const m2s_light_params* light);
+/* Five host planes (layouts of m2s_device_gbuffer; a NULL plane is zero-filled; attachment 3 is never read by m2s_relight) become
+ * the context's G-buffer, as if m2s_splat had left them: the counterpart of m2s_upload_quads.  W, H in 1..8192. */
+m2s_status m2s_upload_gbuffer(m2s_ctx* ctx, const void* const planes[5], int32_t W, int32_t H);
+/* The frame of the last m2s_relight: uchar4[W * H], row 0 = bottom.  NULL before any. */
+const void* m2s_device_frame(const m2s_ctx* ctx);
+m2s_status m2s_download_frame(m2s_ctx* ctx, void* dst, uint64_t capacity_bytes);
+/* uint8[W * H]: the 20-tap counts of the last m2s_relight (mode 6 with want_shadow_counts); M2S_ERR_STATE otherwise. */
+m2s_status m2s_download_shadow_counts(m2s_ctx* ctx, uint8_t* dst, uint64_t capacity_bytes);
+/* Duration (ms) of the last profiled m2s_relight. */
+float m2s_last_relight_ms(const m2s_ctx* ctx);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

@@ -37,6 +37,9 @@ EXPORTS = (
     "m2s_set_resolution_hint", "m2s_last_warm_ms", "m2s_dist_transport", "m2s_last_sort_stage_ms",
     "m2s_splat", "m2s_upload_quads", "m2s_device_gbuffer", "m2s_download_gbuffer", "m2s_last_splat_ms", "m2s_last_splat_stage_ms",
     "m2s_last_splat_counts",
+    "m2s_shadow", "m2s_shadow_from_quads", "m2s_device_shadow_cubemap", "m2s_download_shadow_cubemap", "m2s_download_shadow_quads", "m2s_upload_shadow_cubemap",
+    "m2s_last_shadow_ms", "m2s_last_shadow_stage_ms", "m2s_last_shadow_counts", "m2s_relight", "m2s_upload_gbuffer", "m2s_device_frame",
+    "m2s_download_frame", "m2s_download_shadow_counts", "m2s_last_relight_ms",
 )
 
 
@@ -189,6 +192,21 @@ def load():
         "m2s_last_splat_ms": (C.c_float, [vp]),
         "m2s_last_splat_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_last_splat_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_shadow": (C.c_int, [vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]),
+        "m2s_shadow_from_quads": (C.c_int, [vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "m2s_device_shadow_cubemap": (vp, [vp]),
+        "m2s_download_shadow_cubemap": (C.c_int, [vp, vp, u64]),
+        "m2s_download_shadow_quads": (C.c_int, [vp, u32, vp, u64]),
+        "m2s_upload_shadow_cubemap": (C.c_int, [vp, vp, u32]),
+        "m2s_last_shadow_ms": (C.c_float, [vp]),
+        "m2s_last_shadow_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_last_shadow_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_relight": (C.c_int, [vp, vp]),
+        "m2s_upload_gbuffer": (C.c_int, [vp, C.POINTER(vp), C.c_int32, C.c_int32]),
+        "m2s_device_frame": (vp, [vp]),
+        "m2s_download_frame": (C.c_int, [vp, vp, u64]),
+        "m2s_download_shadow_counts": (C.c_int, [vp, vp, u64]),
+        "m2s_last_relight_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

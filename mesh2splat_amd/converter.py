@@ -66,6 +66,10 @@ class Converter:
         self._last_splat_wh = (0, 0)
 
     # -- helpers ------------------------------------------------------------------------------------
+    _nonnull = C.c_uint64(0)      # a non-NULL address for "n = 0 records at this pointer"
+    _last_shadow_S = 0            # side of the context's shadow cube (0: none yet)
+    _last_splat_wh = (0, 0)       # W x H of the context's G-buffer
+
     def _check(self, st: int):
         if st != _lib.M2S_OK:
             raise _lib.M2SError(st, self._L.m2s_last_error(self._h).decode())
@@ -349,6 +353,143 @@ class Converter:
         self._check(self._L.m2s_last_splat_counts(self._h, v))
         return {"pairs": int(v[0]), "fragments": int(v[1]), "skipped": int(v[2])}
 
+    def shadow(self, prepass_params, light_params, records=None, download: bool = True):
+        """GaussianShadowPass (m2s_shadow): every record of the context (or of `records`, a contiguous CUDA torch tensor (n, 24)
+        float32) through the six cameras of the light into per-face quad lists, those drawn depth-only into the cube.
+        `prepass_params`: mesh2splat_amd.prepass.PrepassParams (its per-record fields), `light_params`: mesh2splat_amd.light.LightParams.
+        -> (per_face, skipped, cube): six list lengths, quads skipped, cube (6, S, S) float32 (faces in GL order, row 0 = t = 0);
+        with download=False (per_face, skipped) — the cube stays on the device (device_shadow_cubemap)."""
+        from . import light as _li, prepass as _pp
+        pc, keep = _pp.to_c(prepass_params)
+        lc = _li.to_c(light_params)
+        ptr, n = None, 0
+        if records is not None:
+            if not (hasattr(records, "data_ptr") and records.is_cuda and records.is_contiguous()):
+                raise ValueError("records must be a contiguous CUDA tensor (n, 24) float32")
+            n = int(records.shape[0])
+            # n = 0: a cube of 1.0.  An empty tensor's data_ptr() is 0, which the C entry point reads as "the context's records": pass the
+            # address of a host word instead — with n = 0 the pointer is only compared with NULL, never dereferenced (include/m2s.h)
+            ptr = records.data_ptr() if n else C.addressof(self._nonnull)
+        per_face = (C.c_uint64 * 6)()
+        skipped = C.c_uint64()
+        self._check(self._L.m2s_shadow(self._h, C.byref(pc), C.byref(lc), ptr, n, per_face, C.byref(skipped)))
+        del keep
+        self._last_shadow_S = int(lc.shadow_resolution) or _li.SHADOW_CUBEMAP_SIZE
+        if not download:
+            return list(per_face), skipped.value
+        return list(per_face), skipped.value, self.download_shadow_cubemap()
+
+    def shadow_from_quads(self, lists, light_params, download: bool = True):
+        """Stage B of the shadow pass alone (m2s_shadow_from_quads): `lists` = six (n_f, 12) float32 host arrays of shadow quads (mean,
+        axes, world position), one per cube face, drawn depth-only into a cleared cube.  -> (skipped, cube) or, download=False, skipped."""
+        from . import light as _li
+        lc = _li.to_c(light_params)
+        arrs = [np.ascontiguousarray(q, np.float32).reshape(-1, 12) for q in lists]
+        assert len(arrs) == 6
+        allq = np.ascontiguousarray(np.concatenate(arrs, 0))
+        per_face = (C.c_uint64 * 6)(*[a.shape[0] for a in arrs])
+        skipped = C.c_uint64()
+        self._check(self._L.m2s_shadow_from_quads(self._h, C.byref(lc), allq.ctypes.data if allq.shape[0] else None, per_face, C.byref(skipped)))
+        self._last_shadow_S = int(lc.shadow_resolution) or _li.SHADOW_CUBEMAP_SIZE
+        return (skipped.value, self.download_shadow_cubemap()) if download else skipped.value
+
+    def download_shadow_cubemap(self) -> np.ndarray:
+        S = self._last_shadow_S or 1                  # (before any cube: the library answers M2S_ERR_STATE)
+        cube = np.empty((6, S, S), np.float32)
+        self._check(self._L.m2s_download_shadow_cubemap(self._h, cube.ctypes.data, cube.size))
+        return cube
+
+    def download_shadow_quads(self, face: int, count: int) -> np.ndarray:
+        """(count, 12) float32: the list of `face` of the last shadow() in input order (m2s_shadow_quad: mean, axes, world position)."""
+        q = np.empty((int(count), 12), np.float32)
+        self._check(self._L.m2s_download_shadow_quads(self._h, int(face), q.ctypes.data if count else None, int(count)))
+        return q
+
+    def upload_shadow_cubemap(self, cube: np.ndarray):
+        """(6, S, S) float32 host cube becomes the context's: what relight() samples."""
+        c = np.ascontiguousarray(cube, np.float32)
+        assert c.ndim == 3 and c.shape[0] == 6 and c.shape[1] == c.shape[2]
+        self._check(self._L.m2s_upload_shadow_cubemap(self._h, c.ctypes.data, c.shape[1]))
+        self._last_shadow_S = int(c.shape[1])
+
+    @property
+    def device_shadow_cubemap(self) -> int:
+        return int(self._L.m2s_device_shadow_cubemap(self._h) or 0)
+
+    def upload_gbuffer(self, planes):
+        """Five (H, W, 4) host planes (float16 for attachments 0, 1, 3, uint8 for 2, 4; None = zeros; row 0 = bottom) become the
+        context's G-buffer, as if splat() had left them."""
+        from . import splat as _sp
+        shape = next(p.shape for p in planes if p is not None)
+        H, W = int(shape[0]), int(shape[1])
+        keep, ptrs = [], (C.c_void_p * 5)()
+        for k, (_, dt) in enumerate(_sp.ATTACHMENTS):
+            if planes[k] is None:
+                ptrs[k] = None
+                continue
+            a = np.ascontiguousarray(planes[k], dt)
+            assert a.shape == (H, W, 4)
+            keep.append(a)
+            ptrs[k] = a.ctypes.data
+        self._check(self._L.m2s_upload_gbuffer(self._h, ptrs, W, H))
+        self._last_splat_wh = (W, H)
+
+    def relight(self, light_params, download: bool = True):
+        """GaussianRelightingPass (m2s_relight) over the context's G-buffer and cube.  -> frame (H, W, 4) uint8, row 0 = bottom (with
+        want_shadow_counts in mode 6: (frame, counts (H, W) uint8)); download=False: None (device_frame)."""
+        from . import light as _li
+        lc = _li.to_c(light_params)
+        self._check(self._L.m2s_relight(self._h, C.byref(lc)))
+        if not download:
+            return None
+        W, H = int(lc.resolution[0]), int(lc.resolution[1])
+        frame = np.empty((H, W, 4), np.uint8)
+        self._check(self._L.m2s_download_frame(self._h, frame.ctypes.data, frame.nbytes))
+        if lc.want_shadow_counts and lc.render_mode == 6:
+            counts = np.empty((H, W), np.uint8)
+            self._check(self._L.m2s_download_shadow_counts(self._h, counts.ctypes.data, counts.nbytes))
+            return frame, counts
+        return frame
+
+    @property
+    def device_frame(self) -> int:
+        return int(self._L.m2s_device_frame(self._h) or 0)
+
+    def render_frame(self, prepass_params, light_params):
+        """One viewer frame of the context's records (renderer.cpp:129-138 without the mesh passes): prepass + depth sort + splat +
+        shadow + relight.  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
+        renderer_resolution must equal `prepass_params`'s.  -> what relight() returns."""
+        from .splat import SplatParams
+        res = tuple(int(v) for v in prepass_params.renderer_resolution)
+        if tuple(int(v) for v in light_params.renderer_resolution) != res:
+            raise ValueError("light_params.renderer_resolution differs from prepass_params.renderer_resolution")
+        self.prepass(prepass_params, download=False)
+        if self.sort_prepass(download=False):
+            self.splat(SplatParams(res, int(prepass_params.render_mode)), download=False)
+        else:
+            import torch
+            self.splat(SplatParams(res, int(prepass_params.render_mode)), quads=torch.empty((0, 24), dtype=torch.float32, device="cuda"), download=False)
+        self.shadow(prepass_params, light_params, download=False)
+        return self.relight(light_params)
+
+    @property
+    def last_shadow_ms(self) -> float:
+        return float(self._L.m2s_last_shadow_ms(self._h))
+
+    def last_shadow_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_shadow_stage_ms(self._h, ms))
+        return {"quads": float(ms[0]), "bin": float(ms[1]), "raster": float(ms[2])}
+
+    def last_shadow_counts(self) -> dict:
+        v = (C.c_uint64 * 9)()
+        self._check(self._L.m2s_last_shadow_counts(self._h, v))
+        return {"quads_per_face": [int(v[k]) for k in range(6)], "pairs": int(v[6]), "texel_updates": int(v[7]), "skipped": int(v[8])}
+
+    @property
+    def last_relight_ms(self) -> float:
+        return float(self._L.m2s_last_relight_ms(self._h))
+
     def set_pipeline(self, name: str):
         """'auto' (single-pass kernel or multi-pass pipeline, chosen per scene and R), 'multipass', or the single-pass
         kernel forced in one of its forms: 'team' (k_fused2, workgroup-cooperative), 'lean' (k_fused3), 'sparse' (k_sparse)."""
@@ -410,6 +551,10 @@ class RenderContext:
         self.renderMode = 0                       # RenderContext::renderMode
         self.gBuffer = None                       # written by GaussianSplattingPass::execute: the five planes
         self.splatSkipped = 0
+        self.prepassParams = None                 # what GaussiansPrepass read: a mesh2splat_amd.prepass.PrepassParams (the shadow pass's per-record inputs)
+        self.lightParams = None                   # RenderContext::pointLightData + camera: a mesh2splat_amd.light.LightParams
+        self.shadowCubemap = None                 # written by GaussianShadowPass::execute: (6, S, S) float32
+        self.frame = None                         # written by GaussianRelightingPass::execute: (H, W, 4) uint8, row 0 = bottom
         self._uploaded_scene = None
 
 
@@ -458,6 +603,28 @@ class GaussianSplattingPass(IRenderPass):
         res = getattr(context, "rendererResolution", (1280, 720))
         mode = getattr(context, "renderMode", 0)
         context.gBuffer, context.splatSkipped = context.converter.splat(SplatParams(renderer_resolution=tuple(res), render_mode=int(mode)))
+
+
+class GaussianShadowPass(IRenderPass):
+    """GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236): the context's records through the six cameras of
+    context.lightParams into the shadow cube (context.shadowCubemap, (6, S, S) float32).  context.prepassParams carries the
+    per-record inputs (model matrix, gaussianStd, resolutionTarget, format, rendererResolution)."""
+
+    def execute(self, context: RenderContext):
+        if context.converter is None or context.prepassParams is None or context.lightParams is None:
+            raise RuntimeError("needs converted records, context.prepassParams and context.lightParams")
+        _, _, context.shadowCubemap = context.converter.shadow(context.prepassParams, context.lightParams)
+
+
+class GaussianRelightingPass(IRenderPass):
+    """GaussianRelightingPass::execute without split screen (GaussianRelightingPass.cpp:136-143): lights the G-buffer of
+    GaussianSplattingPass with the cube of GaussianShadowPass; the RGBA8 frame ends up in context.frame (row 0 = bottom)."""
+
+    def execute(self, context: RenderContext):
+        if context.converter is None or context.lightParams is None:
+            raise RuntimeError("needs a G-buffer, a shadow cube and context.lightParams")
+        r = context.converter.relight(context.lightParams)
+        context.frame = r[0] if isinstance(r, tuple) else r
 
 
 class SceneManager:

@@ -190,6 +190,11 @@ void m2s_destroy(m2s_ctx* c) {
                      c->d_splat_temp, (void*)c->d_splat_totals })
         if (p) (void)hipFree(p);
     if (c->h_splat) (void)hipHostFree(c->h_splat);
+    for (void* p : { c->d_shadow_quads, (void*)c->d_shadow_cube, (void*)c->d_sh_tab, (void*)c->d_sh_views, c->d_sh_rec, (void*)c->d_sh_cnt,
+                     (void*)c->d_sh_off, (void*)c->d_sh_pairs, c->d_sh_temp, (void*)c->d_sh_totals, (void*)c->d_frame, (void*)c->d_shadow_counts })
+        if (p) (void)hipFree(p);
+    if (c->h_sh) (void)hipHostFree(c->h_sh);
+    for (hipEvent_t e : c->light_ev) if (e) (void)hipEventDestroy(e);
     if (c->d_loaded) (void)hipFree(c->d_loaded);
     if (c->d_rows) (void)hipFree(c->d_rows);
     for (int k = 0; k < 2; ++k) if (c->h_export[k]) (void)hipHostFree(c->h_export[k]);

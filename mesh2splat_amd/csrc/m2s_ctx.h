@@ -3,6 +3,7 @@
 //   m2s_pass.cpp     the conversion pass driver (== ConversionPass::execute)   m2s_async.cpp    m2s_convert_submit / _wait
 //   m2s_records.cpp  read-back, .ply export, record adoption               m2s_viewer.cpp   depth sort, viewer prepass
 //   m2s_splat.cpp    the splat pass (== GaussianSplattingPass::execute) and its G-buffer
+//   m2s_light.cpp    the shadow and relighting passes (== GaussianShadowPass / GaussianRelightingPass::execute)
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -190,6 +191,39 @@ struct m2s_ctx {
     float last_splat_ms = 0.0f;
     float last_splat_stage_ms[3] = { 0, 0, 0 };     // setup + bin, grouping, blend (profiling on)
     uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
+    // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
+    // and the pass's grow-only work buffers
+    void* d_shadow_quads = nullptr;          // 48 B each
+    uint64_t shadow_quads_cap = 0;
+    uint32_t shadow_base[7] = { 0, 0, 0, 0, 0, 0, 0 };   // first quad of every face's list; [6] = all quads (of the last m2s_shadow)
+    bool shadow_lists = false;               // the lists of the last m2s_shadow exist (false after m2s_upload_shadow_cubemap)
+    float* d_shadow_cube = nullptr;          // float[6][S][S]
+    uint64_t shadow_cube_cap = 0;            // texels
+    int32_t shadow_S = 0;                    // 0: no cube yet
+    uint32_t* d_sh_tab = nullptr;            // stage A: counts | offsets, sh_tab_cap words each
+    uint64_t sh_tab_cap = 0;
+    float* d_sh_views = nullptr;             // six view matrices (96 floats) | bases (8 words)
+    void* d_sh_rec = nullptr;                // stage B: per quad 48-byte record, tile count (u32), scan of the counts (u64)
+    uint32_t* d_sh_cnt = nullptr;
+    unsigned long long* d_sh_off = nullptr;
+    uint64_t sh_quad_cap = 0;
+    uint32_t* d_sh_pairs = nullptr;          // keys_in | vals_in | keys_out | vals_out, sh_pairs_cap each
+    uint64_t sh_pairs_cap = 0;
+    void* d_sh_temp = nullptr;               // scan / radix sort work area
+    uint64_t sh_temp_cap = 0;
+    unsigned long long* d_sh_totals = nullptr;   // [0] pairs, [1] skipped quads, [2] atomics sent
+    unsigned long long* h_sh = nullptr;          // pinned: those three words, then the bases
+    hipEvent_t light_ev[10] = {};
+    float last_shadow_ms = 0.0f;
+    float last_shadow_stage_ms[3] = { 0, 0, 0 };    // stage A (count + scan + emit), setup + binning, raster (profiling on)
+    uint64_t last_shadow_counts[9] = {};            // quads of face 0..5, (tile, quad) pairs, texel writes (atomics sent), quads skipped
+    // relighting pass: the frame, the optional plane of shadow counts
+    uint32_t* d_frame = nullptr;
+    uint8_t* d_shadow_counts = nullptr;
+    uint64_t frame_cap_px = 0;
+    int32_t frame_w = 0, frame_h = 0;        // 0: no relight has run
+    bool frame_has_counts = false;
+    float last_relight_ms = 0.0f;
 
     // measurement
     bool profiling = false;

@@ -241,6 +241,33 @@ hipError_t splat_blend(const float4* rec, const uint32_t* vals, const uint2* ran
                        void* const planes[5], unsigned long long* frag_count, hipStream_t st);
 hipError_t preload_splat();
 
+// ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
+struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads
+struct RelightK {                              // uniforms of gaussianSplattingDeferredPS.glsl
+    float light[3], cam[3], color[3];
+    float intensity, far_plane;
+    int32_t mode, W, H, S;
+};
+inline uint32_t shadow_blocks(uint32_t n) { return (n + 255u) / 256u; }   // workgroups of stage A; its tables hold 6 * blocks + 1 words
+size_t shadow_temp_bytes(uint32_t n_words, uint32_t n_quads, uint32_t pairs);
+// stage A, first half: per (face, workgroup) survivor counts, their exclusive scan (off), bases[7] (device)
+hipError_t shadow_count(const PrepassK& k, const float* views, const float light[3], const float4* rec, uint32_t n, uint32_t* cnt, uint32_t* off,
+                        void* temp, size_t temp_bytes, uint32_t* bases, hipStream_t st);
+// ... second half: the 48-byte quads, every face's list in input order
+hipError_t shadow_emit(const PrepassK& k, const float* views, const float light[3], const float4* rec, uint32_t n, const uint32_t* off, float4* quads,
+                       hipStream_t st);
+// stage B: per-quad records (48 B), tile counts and their scan; totals[0] = (tile, quad) pairs, totals[1] += skipped quads
+hipError_t shadow_setup(const float4* quads, uint32_t n, const ShadowBases& fb, int S, const float light[3], float far_plane, float4* rec, uint32_t* cnt,
+                        unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st);
+hipError_t shadow_bin(const float4* rec, const uint32_t* cnt, const unsigned long long* off, uint32_t n, int S, uint32_t* keys_in, uint32_t* vals_in,
+                      uint32_t* keys_out, uint32_t* vals_out, uint32_t pairs, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t shadow_clear(float* cube, int S, hipStream_t st);                      // every texel 1.0
+hipError_t shadow_raster(const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, int S, float* cube, unsigned long long* writes,
+                         hipStream_t st);
+// planes: the five G-buffer attachments (3, depth, is not read); counts (or NULL): the 20-tap shadow count per pixel
+hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st);
+hipError_t preload_light();
+
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);
 void launch_lower_bounds(const uint32_t* keys, uint64_t n, const unsigned long long* splitters, uint32_t m, unsigned long long* out, hipStream_t st);

@@ -1,0 +1,412 @@
+// m2s_light.cpp — the shadow pass (GaussianShadowPass.cpp:83-236) and the deferred relighting pass (GaussianRelightingPass.cpp:136-143):
+// host side of m2s_light.hip.
+#include "m2s_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace m2s;
+using namespace m2s_host;
+
+namespace {
+
+// grow-only device buffer: (re)allocated when `want` exceeds `cap` (units of `unit` bytes)
+template <typename T>
+m2s_status grow(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
+    if (cap >= want) return M2S_OK;
+    if (p) { (void)hipFree((void*)p); p = nullptr; }
+    cap = 0;
+    void* q = nullptr;
+    HIPCHK(c, hipMalloc(&q, std::max<size_t>(want * unit, 256)));
+    p = static_cast<T*>(q);
+    cap = want;
+    return M2S_OK;
+}
+
+constexpr int kPinnedBases = 8;     // h_sh: [0..2] totals | 8 x u32 bases from word 8 | 96 floats of view matrices from word 16
+constexpr int kPinnedViews = 16;
+constexpr size_t kPinnedBytes = kPinnedViews * 8 + 96 * sizeof(float);
+
+m2s_status ensure_light_common(m2s_ctx* c) {
+    if (!c->h_sh) HIPCHK(c, hipHostMalloc((void**)&c->h_sh, kPinnedBytes, hipHostMallocDefault));
+    if (!c->d_sh_totals) HIPCHK(c, hipMalloc((void**)&c->d_sh_totals, 4 * sizeof(unsigned long long)));
+    if (!c->d_sh_views) HIPCHK(c, hipMalloc((void**)&c->d_sh_views, 96 * sizeof(float) + 8 * sizeof(uint32_t)));
+    for (hipEvent_t& e : c->light_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    return M2S_OK;
+}
+
+// The six cameras of the light (GaussianShadowPass.cpp:91-108: glm::lookAt(light, light + axis, up)) and the 90 degree / aspect 1
+// glm::perspective, in double, rounded to float, column-major.  `light + axis - light` is taken as the axis itself, so the rotation
+// part is an exact signed permutation and the translation the (exactly representable) negated, permuted light position;
+// 1 / tan(45 degrees) is 1.
+void shadow_cameras(const float light[3], float near_p, float far_p, float views[96], float proj[16]) {
+    static const double F[6][3] = { { 1, 0, 0 }, { -1, 0, 0 }, { 0, 1, 0 }, { 0, -1, 0 }, { 0, 0, 1 }, { 0, 0, -1 } };
+    static const double UP[6][3] = { { 0, -1, 0 }, { 0, -1, 0 }, { 0, 0, 1 }, { 0, 0, -1 }, { 0, -1, 0 }, { 0, -1, 0 } };
+    const double eye[3] = { light[0], light[1], light[2] };
+    for (int fc = 0; fc < 6; ++fc) {
+        const double* f = F[fc];
+        const double* up = UP[fc];
+        const double s[3] = { f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0] };
+        const double u[3] = { s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0] };
+        double m[16] = { 0 };
+        m[15] = 1;
+        for (int k = 0; k < 3; ++k) { m[k * 4 + 0] = s[k]; m[k * 4 + 1] = u[k]; m[k * 4 + 2] = -f[k]; }
+        m[12] = -((s[0] * eye[0] + s[1] * eye[1]) + s[2] * eye[2]);
+        m[13] = -((u[0] * eye[0] + u[1] * eye[1]) + u[2] * eye[2]);
+        m[14] = (f[0] * eye[0] + f[1] * eye[1]) + f[2] * eye[2];
+        for (int k = 0; k < 16; ++k) views[fc * 16 + k] = (float)(m[k] + 0.0);      // (+ 0.0: no negative zeros in the matrix)
+    }
+    const double n = near_p, f = far_p;
+    for (int k = 0; k < 16; ++k) proj[k] = 0.0f;
+    proj[0] = 1.0f;
+    proj[5] = 1.0f;
+    proj[10] = (float)(-(f + n) / (f - n));
+    proj[11] = -1.0f;
+    proj[14] = (float)(-(2.0 * f * n) / (f - n));
+}
+
+m2s_status check_light(m2s_ctx* c, const m2s_light_params* lp, int* S_out) {
+    const int64_t S = lp->shadow_resolution ? (int64_t)lp->shadow_resolution : 1024;
+    if (S < 1 || S > 4096) return fail(c, M2S_ERR_INVALID, "shadow resolution outside 1..4096");
+    if (lp->render_mode < 0 || lp->render_mode > 6 || lp->reserved != 0) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6 or reserved != 0");
+    *S_out = (int)S;
+    return M2S_OK;
+}
+
+// Stage B over `total` quads in c->d_shadow_quads (the six lists back to back, fb: where each starts) into the cleared cube.
+m2s_status shadow_stage_b(m2s_ctx* c, const m2s_light_params* lp, int S, uint32_t total, const ShadowBases& fb, uint64_t* out_skipped, float* b_ms,
+                          float* r_ms) {
+    hipEvent_t* ev = c->light_ev;
+    const bool prof = c->profiling;
+    // ---- stage B: setup, the number of (tile, quad) pairs read back once (the pair buffers are sized from it)
+    if (c->sh_quad_cap < total) {
+        for (void* q : { c->d_sh_rec, (void*)c->d_sh_cnt, (void*)c->d_sh_off }) if (q) (void)hipFree(q);
+        c->d_sh_rec = nullptr; c->d_sh_cnt = nullptr; c->d_sh_off = nullptr;
+        c->sh_quad_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_sh_rec, (size_t)total * 48));
+        HIPCHK(c, hipMalloc((void**)&c->d_sh_cnt, (size_t)total * sizeof(uint32_t)));
+        HIPCHK(c, hipMalloc((void**)&c->d_sh_off, (size_t)total * sizeof(unsigned long long)));
+        c->sh_quad_cap = total;
+    }
+    if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes(1, total, 1), 1)) return s;
+    if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
+    HIPCHK(c, shadow_setup((const float4*)c->d_shadow_quads, total, fb, S, lp->light_position, lp->near_far[1], (float4*)c->d_sh_rec, c->d_sh_cnt,
+                           c->d_sh_off, c->d_sh_temp, c->sh_temp_cap, c->d_sh_totals, c->stream));
+    if (prof) HIPCHK(c, hipEventRecord(ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_sh, c->d_sh_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint64_t pairs = c->h_sh[0];
+    c->last_shadow_counts[8] = c->h_sh[1];
+    if (out_skipped) *out_skipped = c->h_sh[1];
+    if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
+    if (pairs) {
+        if (m2s_status s = grow(c, c->d_sh_pairs, c->sh_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
+        if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes(1, 1, (uint32_t)pairs), 1)) return s;
+        const uint64_t pc = c->sh_pairs_cap;
+        uint32_t* keys_in = c->d_sh_pairs;
+        uint32_t* vals_in = keys_in + pc;
+        uint32_t* keys_out = vals_in + pc;
+        uint32_t* vals_out = keys_out + pc;
+        if (prof) HIPCHK(c, hipEventRecord(ev[6], c->stream));
+        HIPCHK(c, shadow_bin((const float4*)c->d_sh_rec, c->d_sh_cnt, c->d_sh_off, total, S, keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs,
+                             c->d_sh_temp, c->sh_temp_cap, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[7], c->stream));
+        HIPCHK(c, shadow_raster((const float4*)c->d_sh_rec, keys_out, vals_out, (uint32_t)pairs, S, c->d_shadow_cube, c->d_sh_totals + 2, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[8], c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_sh + 2, c->d_sh_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->last_shadow_counts[6] = pairs;
+        c->last_shadow_counts[7] = c->h_sh[2];
+        if (prof) {
+            float x = 0, y = 0;
+            HIPCHK(c, hipEventElapsedTime(&x, ev[6], ev[7]));
+            HIPCHK(c, hipEventElapsedTime(&y, ev[7], ev[8]));
+            *b_ms += x; *r_ms += y;
+        }
+    }
+    if (prof) {
+        float y = 0;
+        HIPCHK(c, hipEventElapsedTime(&y, ev[4], ev[5]));
+        *b_ms += y;
+    }
+    return M2S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// GaussianShadowPass::execute: the compute prepass through the six cameras of the light, then the six depth-only draws.
+m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_params* lp, const void* d_records, uint64_t n,
+                      uint64_t out_per_face[6], uint64_t* out_skipped) {
+    if (!c || !pp || !lp) return M2S_ERR_INVALID;
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    int S = 0;
+    if (m2s_status s = check_light(c, lp, &S)) return s;
+    if (pp->resolution[0] < 1 || pp->resolution[0] > 8192 || pp->resolution[1] < 1 || pp->resolution[1] > 8192)
+        return fail(c, M2S_ERR_INVALID, "renderer resolution outside 1..8192");
+    if (pp->resolution_target == 0) return fail(c, M2S_ERR_INVALID, "resolution_target is 0");
+    if (!d_records) {
+        if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run, no records were uploaded and none were passed");
+        if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+        d_records = c->last_records;
+        n = c->last_stored;
+    }
+    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m2s_status s = ensure_light_common(c)) return s;
+    if (out_per_face) for (int f = 0; f < 6; ++f) out_per_face[f] = 0;
+    if (out_skipped) *out_skipped = 0;
+    c->shadow_S = 0;
+    c->shadow_lists = false;
+    for (uint32_t& b : c->shadow_base) b = 0;
+    for (uint64_t& v : c->last_shadow_counts) v = 0;
+    const uint64_t texels = 6ull * (uint64_t)S * (uint64_t)S;
+    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, texels, sizeof(float))) return s;
+    hipEvent_t* ev = c->light_ev;
+    const bool prof = c->profiling;
+    HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));                      // glClear(GL_DEPTH_BUFFER_BIT), six times
+    HIPCHK(c, hipMemsetAsync(c->d_sh_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    const uint32_t nr = (uint32_t)n;
+    uint32_t total = 0;
+    float a_ms = 0, b_ms = 0, r_ms = 0;
+    if (nr) {
+        // ---- stage A
+        PrepassK k;
+        prepass_prepare(*pp, n, &k);
+        float* h_views = reinterpret_cast<float*>(c->h_sh + kPinnedViews);
+        shadow_cameras(lp->light_position, lp->near_far[0], lp->near_far[1], h_views, k.P);
+        const uint32_t nb = shadow_blocks(nr);
+        const uint64_t words = 6ull * nb + 1;
+        if (c->sh_tab_cap < words) {
+            if (c->d_sh_tab) { (void)hipFree(c->d_sh_tab); c->d_sh_tab = nullptr; }
+            c->sh_tab_cap = 0;
+            HIPCHK(c, hipMalloc((void**)&c->d_sh_tab, 2 * words * sizeof(uint32_t)));
+            c->sh_tab_cap = words;
+        }
+        uint32_t* cnt = c->d_sh_tab;
+        uint32_t* off = c->d_sh_tab + c->sh_tab_cap;
+        if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes((uint32_t)words, 1, 1), 1)) return s;
+        uint32_t* d_bases = reinterpret_cast<uint32_t*>(c->d_sh_views + 96);
+        HIPCHK(c, hipMemcpyAsync(c->d_sh_views, h_views, 96 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, shadow_count(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, cnt, off, c->d_sh_temp, c->sh_temp_cap, d_bases, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+        uint32_t* h_bases = reinterpret_cast<uint32_t*>(c->h_sh + kPinnedBases);
+        HIPCHK(c, hipMemcpyAsync(h_bases, d_bases, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        total = h_bases[6];
+        ShadowBases fb;
+        for (int f = 0; f < 7; ++f) fb.b[f] = h_bases[f];
+        if (total) {
+            if (m2s_status s = grow(c, c->d_shadow_quads, c->shadow_quads_cap, total, 48)) return s;
+            if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+            HIPCHK(c, shadow_emit(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, off, (float4*)c->d_shadow_quads, c->stream));
+            if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+            if (m2s_status st = shadow_stage_b(c, lp, S, total, fb, out_skipped, &b_ms, &r_ms)) return st;
+            if (prof) {
+                float x = 0;
+                HIPCHK(c, hipEventElapsedTime(&x, ev[2], ev[3]));
+                a_ms += x;
+            }
+        }
+        if (prof) {
+            float x = 0;
+            HIPCHK(c, hipEventElapsedTime(&x, ev[0], ev[1]));
+            a_ms += x;
+        }
+        for (int f = 0; f < 7; ++f) c->shadow_base[f] = fb.b[f];
+        for (int f = 0; f < 6; ++f) {
+            c->last_shadow_counts[f] = fb.b[f + 1] - fb.b[f];
+            if (out_per_face) out_per_face[f] = c->last_shadow_counts[f];
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (prof) {
+        c->last_shadow_stage_ms[0] = a_ms; c->last_shadow_stage_ms[1] = b_ms; c->last_shadow_stage_ms[2] = r_ms;
+        c->last_shadow_ms = a_ms + b_ms + r_ms;
+    }
+    c->shadow_S = S;
+    c->shadow_lists = true;
+    return M2S_OK;
+}
+
+// Stage B alone on quad lists made elsewhere: the counterpart of m2s_upload_quads + m2s_splat for the shadow pass.
+m2s_status m2s_shadow_from_quads(m2s_ctx* c, const m2s_light_params* lp, const m2s_shadow_quad* host_quads, const uint64_t per_face[6],
+                                 uint64_t* out_skipped) {
+    if (!c || !lp || !per_face) return M2S_ERR_INVALID;
+    int S = 0;
+    if (m2s_status s = check_light(c, lp, &S)) return s;
+    uint64_t total = 0;
+    ShadowBases fb;
+    for (int f = 0; f < 6; ++f) {
+        if (per_face[f] > 0xFFFFFFFFull || total + per_face[f] > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 quads");
+        fb.b[f] = (uint32_t)total;
+        total += per_face[f];
+    }
+    fb.b[6] = (uint32_t)total;
+    if (total && !host_quads) return fail(c, M2S_ERR_INVALID, "host_quads is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m2s_status s = ensure_light_common(c)) return s;
+    if (out_skipped) *out_skipped = 0;
+    c->shadow_S = 0;
+    c->shadow_lists = false;
+    for (uint32_t& b : c->shadow_base) b = 0;
+    for (uint64_t& v : c->last_shadow_counts) v = 0;
+    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, 6ull * (uint64_t)S * (uint64_t)S, sizeof(float))) return s;
+    HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_sh_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    float b_ms = 0, r_ms = 0;
+    if (total) {
+        if (m2s_status s = grow(c, c->d_shadow_quads, c->shadow_quads_cap, total, 48)) return s;
+        HIPCHK(c, hipMemcpyAsync(c->d_shadow_quads, host_quads, total * 48, hipMemcpyHostToDevice, c->stream));
+        if (m2s_status s = shadow_stage_b(c, lp, S, (uint32_t)total, fb, out_skipped, &b_ms, &r_ms)) return s;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) {
+        c->last_shadow_stage_ms[0] = 0; c->last_shadow_stage_ms[1] = b_ms; c->last_shadow_stage_ms[2] = r_ms;
+        c->last_shadow_ms = b_ms + r_ms;
+    }
+    for (int f = 0; f < 7; ++f) c->shadow_base[f] = fb.b[f];
+    for (int f = 0; f < 6; ++f) c->last_shadow_counts[f] = per_face[f];
+    c->shadow_S = S;
+    c->shadow_lists = true;
+    return M2S_OK;
+}
+
+const void* m2s_device_shadow_cubemap(const m2s_ctx* c) { return c && c->shadow_S ? c->d_shadow_cube : nullptr; }
+
+m2s_status m2s_download_shadow_cubemap(m2s_ctx* c, float* dst, uint64_t capacity_floats) {
+    if (!c || !dst) return M2S_ERR_INVALID;
+    if (!c->shadow_S) return fail(c, M2S_ERR_STATE, "no shadow cube exists");
+    const uint64_t texels = 6ull * (uint64_t)c->shadow_S * (uint64_t)c->shadow_S;
+    if (capacity_floats < texels) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the cube");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_shadow_cube, texels * sizeof(float), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+m2s_status m2s_download_shadow_quads(m2s_ctx* c, uint32_t face, m2s_shadow_quad* dst, uint64_t capacity) {
+    if (!c || face >= 6) return M2S_ERR_INVALID;
+    if (!c->shadow_lists) return fail(c, M2S_ERR_STATE, "no shadow pass has run");
+    const uint64_t first = c->shadow_base[face], cnt = c->shadow_base[face + 1] - first;
+    if (!cnt) return M2S_OK;
+    if (!dst) return fail(c, M2S_ERR_INVALID, "dst is NULL");
+    if (capacity < cnt) return fail(c, M2S_ERR_CAPACITY, "dst holds fewer quads than the face's list");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, (const char*)c->d_shadow_quads + first * 48, cnt * 48, hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+m2s_status m2s_upload_shadow_cubemap(m2s_ctx* c, const float* host, uint32_t S) {
+    if (!c || !host) return M2S_ERR_INVALID;
+    if (S < 1 || S > 4096) return fail(c, M2S_ERR_INVALID, "shadow resolution outside 1..4096");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t texels = 6ull * S * S;
+    c->shadow_S = 0;
+    c->shadow_lists = false;
+    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, texels, sizeof(float))) return s;
+    HIPCHK(c, hipMemcpy(c->d_shadow_cube, host, texels * sizeof(float), hipMemcpyHostToDevice));
+    c->shadow_S = (int32_t)S;
+    return M2S_OK;
+}
+
+m2s_status m2s_upload_gbuffer(m2s_ctx* c, const void* const planes[5], int32_t W, int32_t H) {
+    if (!c || !planes) return M2S_ERR_INVALID;
+    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t px = (uint64_t)W * (uint64_t)H;
+    c->gbuf_w = c->gbuf_h = 0;
+    if (c->gbuf_cap_px < px) {
+        for (int k = 0; k < 5; ++k) if (c->d_gbuf[k]) { (void)hipFree(c->d_gbuf[k]); c->d_gbuf[k] = nullptr; }
+        c->gbuf_cap_px = 0;
+        for (int k = 0; k < 5; ++k) HIPCHK(c, hipMalloc(&c->d_gbuf[k], px * ((k == 2 || k == 4) ? 4 : 8)));
+        c->gbuf_cap_px = px;
+    }
+    for (int k = 0; k < 5; ++k) {
+        const size_t bytes = px * ((k == 2 || k == 4) ? 4 : 8);
+        if (planes[k]) HIPCHK(c, hipMemcpy(c->d_gbuf[k], planes[k], bytes, hipMemcpyHostToDevice));
+        else HIPCHK(c, hipMemset(c->d_gbuf[k], 0, bytes));
+    }
+    c->gbuf_w = W;
+    c->gbuf_h = H;
+    return M2S_OK;
+}
+
+// GaussianRelightingPass::execute, the branch without split screen: one full-screen draw of gaussianSplattingDeferredPS.glsl.
+m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) {
+    if (!c || !lp) return M2S_ERR_INVALID;
+    int S = 0;
+    if (m2s_status s = check_light(c, lp, &S)) return s;
+    if (!c->gbuf_w) return fail(c, M2S_ERR_INVALID, "no G-buffer exists (run m2s_splat or m2s_upload_gbuffer)");
+    if (!c->shadow_S) return fail(c, M2S_ERR_INVALID, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
+    if (lp->resolution[0] != c->gbuf_w || lp->resolution[1] != c->gbuf_h) return fail(c, M2S_ERR_INVALID, "resolution is not the G-buffer's");
+    if (lp->shadow_resolution && (int32_t)lp->shadow_resolution != c->shadow_S) return fail(c, M2S_ERR_INVALID, "shadow resolution is not the cube's");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m2s_status s = ensure_light_common(c)) return s;
+    const uint64_t px = (uint64_t)c->gbuf_w * (uint64_t)c->gbuf_h;
+    c->frame_w = c->frame_h = 0;
+    c->frame_has_counts = false;
+    if (c->frame_cap_px < px) {
+        if (c->d_frame) { (void)hipFree(c->d_frame); c->d_frame = nullptr; }
+        if (c->d_shadow_counts) { (void)hipFree(c->d_shadow_counts); c->d_shadow_counts = nullptr; }
+        c->frame_cap_px = 0;
+        HIPCHK(c, hipMalloc((void**)&c->d_frame, px * 4));
+        HIPCHK(c, hipMalloc((void**)&c->d_shadow_counts, px));
+        c->frame_cap_px = px;
+    }
+    RelightK k;
+    for (int i = 0; i < 3; ++i) { k.light[i] = lp->light_position[i]; k.cam[i] = lp->camera_position[i]; k.color[i] = lp->light_color[i]; }
+    k.intensity = lp->light_intensity;
+    k.far_plane = lp->near_far[1];
+    k.mode = lp->render_mode;
+    k.W = c->gbuf_w; k.H = c->gbuf_h; k.S = c->shadow_S;
+    const bool counts = lp->want_shadow_counts != 0 && lp->render_mode == 6;
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
+    HIPCHK(c, launch_relight(k, c->d_gbuf, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts : nullptr, c->stream));
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
+    c->frame_w = c->gbuf_w;
+    c->frame_h = c->gbuf_h;
+    c->frame_has_counts = counts;
+    return M2S_OK;
+}
+
+const void* m2s_device_frame(const m2s_ctx* c) { return c && c->frame_w ? c->d_frame : nullptr; }
+
+m2s_status m2s_download_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
+    if (!c || !dst) return M2S_ERR_INVALID;
+    if (!c->frame_w) return fail(c, M2S_ERR_STATE, "no relight has run");
+    const uint64_t bytes = (uint64_t)c->frame_w * (uint64_t)c->frame_h * 4;
+    if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_frame, bytes, hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+m2s_status m2s_download_shadow_counts(m2s_ctx* c, uint8_t* dst, uint64_t capacity_bytes) {
+    if (!c || !dst) return M2S_ERR_INVALID;
+    if (!c->frame_w || !c->frame_has_counts) return fail(c, M2S_ERR_STATE, "the last relight kept no shadow counts (want_shadow_counts, render mode 6)");
+    const uint64_t bytes = (uint64_t)c->frame_w * (uint64_t)c->frame_h;
+    if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_shadow_counts, bytes, hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+float m2s_last_shadow_ms(const m2s_ctx* c) { return c ? c->last_shadow_ms : 0.0f; }
+m2s_status m2s_last_shadow_stage_ms(const m2s_ctx* c, float out_ms[3]) {
+    if (!c || !out_ms) return M2S_ERR_INVALID;
+    std::memcpy(out_ms, c->last_shadow_stage_ms, sizeof(c->last_shadow_stage_ms));
+    return M2S_OK;
+}
+m2s_status m2s_last_shadow_counts(const m2s_ctx* c, uint64_t out[9]) {
+    if (!c || !out) return M2S_ERR_INVALID;
+    for (int k = 0; k < 9; ++k) out[k] = c->last_shadow_counts[k];
+    return M2S_OK;
+}
+float m2s_last_relight_ms(const m2s_ctx* c) { return c ? c->last_relight_ms : 0.0f; }
+
+}  // extern "C"

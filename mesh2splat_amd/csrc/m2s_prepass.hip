@@ -22,6 +22,7 @@
 #include "../../include/m2s.h"
 #include "m2s_fused_common.h"
 #include "m2s_viewmath.h"
+#include "m2s_covmath.h"
 
 #include <cmath>
 #include <cstring>
@@ -32,28 +33,7 @@ namespace m2s {
 
 namespace {
 
-struct M3 { float c[3][3]; };   // c[col][row], like the shader's mat3
-
-// mat3 * mat3 in the shader's (glm's) association: a0r*b_c0 + a1r*b_c1 + a2r*b_c2, left to right
-__device__ __forceinline__ M3 m3_mul(const M3& a, const M3& b) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) r.c[c][i] = a.c[0][i] * b.c[c][0] + a.c[1][i] * b.c[c][1] + a.c[2][i] * b.c[c][2];
-    return r;
-}
-__device__ __forceinline__ M3 m3_transpose(const M3& a) {
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) r.c[c][i] = a.c[i][c];
-    return r;
-}
 // (mat4 * vec4 and the projection + frustum test of :67-77: m2s_viewmath.h, shared with the depth sort's key kernel)
-__device__ __forceinline__ float min_glsl(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float max_glsl(float a, float b) { return (a < b) ? b : a; }
 __device__ __forceinline__ float clamp01(float x) { return min_glsl(max_glsl(x, 0.0f), 1.0f); }
 
 // common.glsl:12-19
@@ -87,39 +67,8 @@ __device__ __forceinline__ bool prepass_one(const PrepassK& k, const float4 (&g)
         if (my_depth > depth + 0.00002f) vis = false;
     }
 
-    const float multiplier = (k.format == 0u || k.format == 3u) ? k.std_dev : 1.0f;   // :94
-    // :95-96  modelScale = (|M[0]|, |M[0]|, |M[1]|) as written; k.ms2 = its square (uniform, prepared on the host)
-    const float scale[3] = { (gscl.x * multiplier) * k.ms2[0], (gscl.y * multiplier) * k.ms2[1], (gscl.z * multiplier) * k.ms2[2] };
-
-    M3 rot;                                                                      // :100  castQuatToMat3 on the stored vec4
-    {
-        const float x = grot.x, y = grot.y, z = grot.z, w = grot.w;
-        rot.c[0][0] = 1.f - 2.f * (z * z + w * w);
-        rot.c[0][1] = 2.f * (y * z - x * w);
-        rot.c[0][2] = 2.f * (y * w + x * z);
-        rot.c[1][0] = 2.f * (y * z + x * w);
-        rot.c[1][1] = 1.f - 2.f * (y * y + w * w);
-        rot.c[1][2] = 2.f * (z * w - x * y);
-        rot.c[2][0] = 2.f * (y * w - x * z);
-        rot.c[2][1] = 2.f * (z * w + x * y);
-        rot.c[2][2] = 1.f - 2.f * (y * y + z * z);
-    }
-    M3 mri;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) mri.c[c][i] = k.mr_inv[c * 3 + i];
-    rot = m3_mul(rot, mri);                                                      // :102-108
-    M3 cov3d;                                                                    // :110  computeCov3D
-    {
-        M3 sm;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) sm.c[c][i] = (c == i) ? scale[c] : 0.0f;
-        const M3 mm = m3_mul(sm, rot);
-        cov3d = m3_mul(m3_transpose(mm), mm);
-    }
+    M3 rot;
+    const M3 cov3d = gaussian_cov3d(k, gscl, grot, rot);                       // :94-110
 
     float4 out_color = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 nrm = make_float4(1.f, 0.f, 0.f, 0.f);
@@ -147,38 +96,11 @@ __device__ __forceinline__ bool prepass_one(const PrepassK& k, const float4 (&g)
 
     pos2d.x = pos2d.x / pos2d.w; pos2d.y = pos2d.y / pos2d.w; pos2d.z = pos2d.z / pos2d.w;   // :151
 
-    const float p00 = k.P[0], p11 = k.P[5], p32 = k.P[14];
-    const float tz_sq = vs.z * vs.z;                                             // :154-159
-    const float jsx = -(p00 * k.res[0]) / (2.0f * vs.z);
-    const float jsy = -(p11 * k.res[1]) / (2.0f * vs.z);
-    const float jtx = (p00 * vs.x * k.res[0]) / (2.0f * tz_sq);
-    const float jty = (p11 * vs.y * k.res[1]) / (2.0f * tz_sq);
-    const float jtz = ((k.near_far[1] - k.near_far[0]) * p32) / (2.0f * tz_sq);
-    M3 J, W;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { J.c[c][i] = 0.0f; W.c[c][i] = k.V[c * 4 + i]; }   // :161-165
-    J.c[0][0] = jsx; J.c[1][1] = jsy; J.c[2][0] = jtx; J.c[2][1] = jty; J.c[2][2] = jtz;
-    const M3 JW = m3_mul(J, W);
-    const M3 Vp = m3_mul(m3_mul(JW, cov3d), m3_transpose(JW));                   // :168
-    float c00 = Vp.c[0][0];
-    const float c01 = Vp.c[0][1], c10 = Vp.c[1][0];
-    float c11 = Vp.c[1][1];                                                      // :170
-    c00 += 0.3f;                                                                 // :173-174
-    c11 += 0.3f;
-    const float mid = c00 + c11;
-    const float da = c00 - c11, db = 2.0f * c01;
-    const float delta = sqrtf(da * da + db * db);                                // :178
-    const float lambda1 = 0.5f * (mid + delta), lambda2 = 0.5f * (mid - delta);
-    if (lambda2 < 0.0f) vis = false;                                             // :183
-
-    const float dvy = (-c00 + c01 + lambda1) / (c01 - c11 + lambda1);            // :185
-    const float inv_len = 1.0f / sqrtf(1.0f * 1.0f + dvy * dvy);
-    const float dx = 1.0f * inv_len, dy = dvy * inv_len;
-    const float major_r = min_glsl(3.0f * sqrtf(lambda1), 1024.0f), minor_r = min_glsl(3.0f * sqrtf(lambda2), 1024.0f);
-    const float hx = k.res[0] * 0.5f, hy = k.res[1] * 0.5f;                      // :186-190
-    const float4 quad_scale = make_float4((major_r * dx) / hx, (major_r * dy) / hy, (minor_r * dy) / hx, (minor_r * (-dx)) / hy);
+    Cov2D cv;
+    project_cov(k.V, k.P, k.res, k.near_far, vs, cov3d, cv);                    // :154-190
+    const float c00 = cv.c00, c01 = cv.c01, c10 = cv.c10, c11 = cv.c11;
+    if (cv.lambda2 < 0.0f) vis = false;                                          // :183
+    const float4 quad_scale = cv.quad_scale;
     const float det = c00 * c11 - c01 * c10;                                     // common.glsl:61-76
     float i00 = 0.0f, i01 = 0.0f, i11 = 0.0f;
     if (det != 0.0f) { i00 = c11 / det; i01 = -c01 / det; i11 = c00 / det; }

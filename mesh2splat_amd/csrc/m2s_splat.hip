@@ -24,6 +24,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "m2s_devfn.h"
+#include "m2s_quadraster.h"
 
 #pragma clang fp contract(off)
 
@@ -33,9 +34,8 @@ namespace {
 
 constexpr int kTile = kSplatTile;          // 16 x 16 pixels = 256 lanes
 constexpr int kBatch = 256;                // quads staged in LDS per round (one per staging thread)
-constexpr uint32_t kFlagTri0 = 1u, kFlagTri1 = 2u, kFlagTame = 4u;
+constexpr uint32_t kFlagTri0 = kQuadTri0, kFlagTri1 = kQuadTri1, kFlagTame = 4u;
 constexpr int kWaveShift = 8;              // bits 8..11 of a staged quad's flags: the waves of the tile whose rows its box reaches
-constexpr int kTMax = 1 << 30;             // edge thresholds are clamped to +-2^30 (|a lx + b ly| < 2^28)
 
 // The 128-byte record of one quad (8 x float4):
 //   [0] X[4]  [1] Y[4]  snapped window coordinates (24.8) of the four vertices
@@ -46,16 +46,6 @@ constexpr int kTMax = 1 << 30;             // edge thresholds are clamped to +-2
 //   [6] ws.xyz, normal.x
 //   [7] normal.yz, 0, 0
 constexpr int kRecF4 = 8;
-
-__device__ __forceinline__ bool finite4(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w); }
-
-// Quad vertex v of the pinned order (vx, vy) in {(-1,-1), (-1,1), (1,1), (1,-1)}: mean.xy + (vx * scale.xy + vy * scale.zw)
-// (gaussianSplattingVS.glsl:33); multiplying by +-1 is exact, so the sum of the two axis terms and the mean's addition round.
-__device__ __forceinline__ void quad_vertex(float4 m, float4 s, int v, float& x, float& y) {
-    const float vx = (v == 0 || v == 1) ? -1.0f : 1.0f, vy = (v == 0 || v == 3) ? -1.0f : 1.0f;
-    x = m.x + (vx * s.x + vy * s.z);
-    y = m.y + (vx * s.y + vy * s.w);
-}
 
 // Sources provably finite for every fragment of the quad (what lets a saturated pixel skip it): a positive definite conic with a
 // margin far above the rounding of the fp32 alpha (so alpha <= 0 and 0 <= g <= 1 wherever it is evaluated), magnitudes that keep
@@ -78,38 +68,16 @@ __global__ void __launch_bounds__(256) k_splat_setup(const float4* __restrict__ 
         const float4 m = q[6ull * i + 0], s = q[6ull * i + 1], col = q[6ull * i + 2], co = q[6ull * i + 3], nr = q[6ull * i + 4],
                      ws = q[6ull * i + 5];
         const bool fin = isfinite(m.x) && isfinite(m.y) && finite4(s) && finite4(col) && finite4(co) && finite4(nr) && finite4(ws);
-        float vx[4], vy[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) quad_vertex(m, s, v, vx[v], vy[v]);
-        const float hw = (float)W * 0.5f, hh = (float)H * 0.5f;
-        bool guard = true;
-        int X[4], Y[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float xw = hw * vx[v] + hw, yw = hh * vy[v] + hh;
-            guard = guard && (fabsf(xw) < kGuardPx) && (fabsf(yw) < kGuardPx);
-            X[v] = (int)rintf(xw * 256.0f);
-            Y[v] = (int)rintf(yw * 256.0f);
-        }
-        skip = !(fin && guard);
-        uint32_t flags = 0, c = 0;
-        int x0 = W, x1 = -1, y0 = H, y1 = -1;
-        if (!skip) {
-            const float tx0[3] = { vx[0], vx[1], vx[2] }, ty0[3] = { vy[0], vy[1], vy[2] };
-            const float tx1[3] = { vx[0], vx[2], vx[3] }, ty1[3] = { vy[0], vy[2], vy[3] };
-            Raster r;
-            if (raster_setup_wh(tx0, ty0, W, H, r)) { flags |= kFlagTri0; x0 = min(x0, r.x0); x1 = max(x1, r.x1); y0 = min(y0, r.y0); y1 = max(y1, r.y1); }
-            if (raster_setup_wh(tx1, ty1, W, H, r)) { flags |= kFlagTri1; x0 = min(x0, r.x0); x1 = max(x1, r.x1); y0 = min(y0, r.y0); y1 = max(y1, r.y1); }
-        }
+        QuadBox qb;
+        quad_snap_box(m, s, fin, W, H, qb);
+        skip = qb.skip;
+        uint32_t flags = qb.flags, c = 0;
+        const int* X = qb.X;
+        const int* Y = qb.Y;
         const float3 pre = make_float3(col.x * col.w, col.y * col.w, col.z * col.w);
         if (!skip && quad_tame(m, co, pre)) flags |= kFlagTame;
         uint32_t tb0 = 0, tb1 = 0;
-        if (flags & (kFlagTri0 | kFlagTri1)) {
-            const int t0x = x0 / kTile, t1x = x1 / kTile, t0y = y0 / kTile, t1y = y1 / kTile;
-            c = (uint32_t)(t1x - t0x + 1) * (uint32_t)(t1y - t0y + 1);
-            tb0 = (uint32_t)t0x | ((uint32_t)t0y << 16);
-            tb1 = (uint32_t)t1x | ((uint32_t)t1y << 16);
-        }
+        if (flags & (kFlagTri0 | kFlagTri1)) c = quad_tile_box(qb, 0, tb0, tb1);
         cnt[i] = c;
         float4* o = rec + (size_t)kRecF4 * i;
         o[0] = make_float4(__int_as_float(X[0]), __int_as_float(X[1]), __int_as_float(X[2]), __int_as_float(X[3]));
@@ -140,14 +108,7 @@ __global__ void __launch_bounds__(256) k_splat_pairs(const float4* __restrict__ 
     if (i >= n || cnt[i] == 0) return;
     const float4 r2 = rec[(size_t)kRecF4 * i + 2];
     const uint32_t tb0 = __float_as_uint(r2.y), tb1 = __float_as_uint(r2.z);
-    const int t0x = tb0 & 0xFFFF, t0y = tb0 >> 16, t1x = tb1 & 0xFFFF, t1y = tb1 >> 16;
-    size_t k = off[i];
-    for (int ty = t0y; ty <= t1y; ++ty)
-        for (int tx = t0x; tx <= t1x; ++tx) {
-            keys[k] = (uint32_t)(ty * tiles_x + tx);
-            vals[k] = i;
-            ++k;
-        }
+    emit_tile_pairs(tb0, tb1, tiles_x, (size_t)off[i], i, keys, vals);
 }
 
 // start / end of every tile's run in the sorted pairs (ranges zeroed beforehand), and the run lengths for the tile order
@@ -179,44 +140,6 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f),
 __device__ __forceinline__ float unorm8(float r) {
     const float q = rintf(clamp01(r) * 255.0f);
     return (float)((double)q * (1.0 / 255.0));
-}
-
-// One triangle's edge thresholds for the tile whose first pixel is (px0, py0): pixel (px0 + lx, py0 + ly) is inside edge i iff
-// a_i lx + b_i ly > T_i, with E_i(P) = a_i Px + b_i Py + c_i at the pixel centre P = 256 (x, y) + 128 and the top-left rule's bias:
-// E + bias > 0  <=>  256 (a lx + b ly) > -(E_org + bias)  <=>  a lx + b ly > floor(-(E_org + bias) / 256).
-__device__ __forceinline__ void stage_triangle(const int X[3], const int Y[3], int px0, int py0, int4& ea, int4& eb, int& t2) {
-    const long long area2 = (long long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long long)(Y[1] - Y[0]) * (X[2] - X[0]);
-    const int sgn = area2 < 0 ? -1 : 1;
-    int a[3], b[3], T[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const int ia = (i + 1) % 3, ib = (i + 2) % 3;
-        const int dy = Y[ib] - Y[ia], dx = X[ib] - X[ia];
-        a[i] = -dy * sgn;
-        b[i] = dx * sgn;
-        const long long c = ((long long)dy * X[ia] - (long long)dx * Y[ia]) * sgn;
-        const int bias = (a[i] > 0 || (a[i] == 0 && b[i] > 0)) ? 1 : 0;
-        const long long e = (long long)a[i] * (256ll * px0 + 128) + (long long)b[i] * (256ll * py0 + 128) + c + bias;
-        long long t = (-e) >> 8;                      // floor(-e / 256)
-        t = t < -(long long)kTMax ? -(long long)kTMax : t > (long long)kTMax ? (long long)kTMax : t;
-        T[i] = (int)t;
-    }
-    ea = make_int4(a[0], a[1], a[2], T[0]);
-    eb = make_int4(b[0], b[1], b[2], T[1]);
-    t2 = T[2];
-}
-
-// Does the triangle's pixel box (as raster_head_wh clamps it) meet the tile [px0, px0 + 15] x [py0, py0 + 15]?  If so, the waves
-// whose rows it reaches (wave w holds rows 4w .. 4w + 3 of the tile) as bits 0..3 of *waves.
-__device__ __forceinline__ bool box_meets_tile(const int X[3], const int Y[3], int W, int H, int px0, int py0, uint32_t* waves) {
-    const int xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
-    const int ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
-    const int x0 = max((xmin - 128 + 255) >> 8, 0), x1 = min((xmax - 128) >> 8, W - 1);
-    const int y0 = max((ymin - 128 + 255) >> 8, 0), y1 = min((ymax - 128) >> 8, H - 1);
-    if (!(x0 <= x1 && y0 <= y1 && x0 <= px0 + kTile - 1 && x1 >= px0 && y0 <= py0 + kTile - 1 && y1 >= py0)) return false;
-    const int w0 = (max(y0, py0) - py0) >> 2, w1 = (min(y1, py0 + kTile - 1) - py0) >> 2;
-    *waves |= ((2u << w1) - 1u) & ~((1u << w0) - 1u);
-    return true;
 }
 
 template <bool kOverdraw>

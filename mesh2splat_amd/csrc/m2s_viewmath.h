@@ -17,14 +17,20 @@ __device__ __forceinline__ float4 m4_mul(const float* m, float x, float y, float
     return make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// :73-77: the guard-band frustum test on the clip-space position (false = culled; every comparison is false for NaN: such a record is
+// NOT culled here, as in the shader).  Also gaussianPointShadowMappingCS.glsl:89-94, through the face's camera.
+__device__ __forceinline__ bool clip_inside(float4 pos2d) {
+    const float clip = 1.05f * pos2d.w;                                           // :73
+    return !(pos2d.z < -clip || pos2d.x < -clip || pos2d.x > clip || pos2d.y < -clip || pos2d.y > clip);   // :75-77
+}
+
 // :67-77.  ws = u_modelToWorld * vec4(P, 1); vs = u_worldToView * vec4(ws.xyz, 1); pos2d = u_viewToClip * vs; inside = the guard-band
 // frustum test (false = culled; every comparison is false for NaN: such a record is NOT culled here, as in the shader).
 __device__ __forceinline__ bool view_project(const float* M, const float* V, const float* P, float px, float py, float pz, float4& ws, float4& vs, float4& pos2d) {
     ws = m4_mul(M, px, py, pz, 1.0f);                                             // :67
     vs = m4_mul(V, ws.x, ws.y, ws.z, 1.0f);                                       // :69
     pos2d = m4_mul(P, vs.x, vs.y, vs.z, vs.w);                                    // :71
-    const float clip = 1.05f * pos2d.w;                                           // :73
-    return !(pos2d.z < -clip || pos2d.x < -clip || pos2d.x > clip || pos2d.y < -clip || pos2d.y > clip);   // :75-77
+    return clip_inside(pos2d);
 }
 
 }  // namespace m2s

@@ -58,6 +58,9 @@ struct Options {
     bool threads = false;                                          // ranks as threads of this process
     std::string preview;                                           // --preview view.png: prepass + depth sort + splat of the result
     int preview_w = 1280, preview_h = 720;
+    int preview_mode = 0;                                          // --preview-mode N: 0..4 the albedo plane (as before), 5 / 6 the relit frame
+    bool has_light = false;                                        // --light x,y,z[,intensity]
+    double light[4] = { 0, 0, 0, 0 };
     uint32_t R() const { return density > 0 ? (uint32_t)density : (uint32_t)(int)(16 + quality * (double)(max_res - 16)); }  // ImGuiUI.cpp:512
 };
 
@@ -68,6 +71,7 @@ void usage() {
                  "options: [--density R | --quality q [--max-res M]] [--std s] [--format 0|1|2] [--device d] [--gpus N [--gather]]\n"
                  "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
                  "         [--preview view.png [--preview-size WxH (default 1280x720)]]\n"
+                 "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -169,7 +173,21 @@ void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, flo
     proj[14] = (float)(-(2.0 * *far_p * *near_p) / (*far_p - *near_p));
 }
 
-// GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path`
+// The default point light of --preview-mode 5 / 6 (tests/light_ref.py: default_light mirrors it), in double: above and to the right of the
+// preview camera's side of the scene, 1.5 bounding-sphere radii in front of the centre; intensity 4 radius^2.
+void preview_light(const m2s_mesh* meshes, uint32_t n_meshes, double pos[3], double* intensity) {
+    double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
+    for (uint32_t i = 0; i < n_meshes; ++i)
+        for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], (double)meshes[i].bbox_min[k]); mx[k] = std::max(mx[k], (double)meshes[i].bbox_max[k]); }
+    double ctr[3], d2 = 0;
+    for (int k = 0; k < 3; ++k) { ctr[k] = (mn[k] + mx[k]) / 2; d2 += (mx[k] - mn[k]) * (mx[k] - mn[k]); }
+    const double radius = std::sqrt(d2) / 2;
+    pos[0] = ctr[0] + 0.75 * radius; pos[1] = ctr[1] + 0.75 * radius; pos[2] = ctr[2] + 1.5 * radius;
+    *intensity = 4.0 * radius * radius;
+}
+
+// GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path` — with
+// --preview-mode 5 / 6 followed by GaussianShadowPass -> GaussianRelightingPass, and the relit frame to `path`
 int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
     const int W = o.preview_w, H = o.preview_h;
     m2s_prepass_params pp;
@@ -189,10 +207,30 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     if (m2s_prepass(ctx, &pp, nullptr, 0, &visible) != M2S_OK) return 1;
     if (m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
     std::vector<uint8_t> img((size_t)W * H * 4, 0);
-    if (n) {
+    const bool relit = o.preview_mode == 5 || o.preview_mode == 6;
+    if (n || relit) {
         m2s_splat_params sp = { { W, H }, 0, 0 };
-        if (m2s_splat(ctx, &sp, nullptr, 0, &skipped) != M2S_OK) return 1;
-        if (m2s_download_gbuffer(ctx, 2, img.data(), img.size()) != M2S_OK) return 1;
+        static const m2s_quad none = {};
+        if (m2s_splat(ctx, &sp, n ? nullptr : &none, 0, &skipped) != M2S_OK) return 1;      // (n = 0: cleared planes)
+        if (!relit && m2s_download_gbuffer(ctx, 2, img.data(), img.size()) != M2S_OK) return 1;
+    }
+    if (relit) {
+        m2s_light_params lp;
+        std::memset(&lp, 0, sizeof(lp));
+        double lpos[3], inten;
+        preview_light(meshes, n_meshes, lpos, &inten);
+        if (o.has_light) { for (int k = 0; k < 3; ++k) lpos[k] = o.light[k]; if (o.light[3] > 0) inten = o.light[3]; }
+        for (int k = 0; k < 3; ++k) { lp.light_position[k] = (float)lpos[k]; lp.light_color[k] = 1.0f; lp.camera_position[k] = (float)eye[k]; }
+        lp.light_intensity = (float)inten;
+        lp.near_far[0] = (float)near_p; lp.near_far[1] = (float)far_p;
+        lp.render_mode = o.preview_mode;
+        lp.resolution[0] = W; lp.resolution[1] = H;
+        lp.shadow_resolution = 1024;
+        std::printf("preview light: position=%.17g,%.17g,%.17g intensity=%.17g colour=1,1,1 shadow=1024\n", lpos[0], lpos[1], lpos[2], inten);
+        uint64_t per_face[6], sh_skipped = 0;
+        if (m2s_shadow(ctx, &pp, &lp, nullptr, 0, per_face, &sh_skipped) != M2S_OK) return 1;
+        if (m2s_relight(ctx, &lp) != M2S_OK) return 1;
+        if (m2s_download_frame(ctx, img.data(), img.size()) != M2S_OK) return 1;
     }
     if (!write_png_rgba(o.preview.c_str(), img.data(), W, H)) { std::fprintf(stderr, "cannot write %s\n", o.preview.c_str()); return 2; }
     std::printf("preview %dx%d: %llu quads splatted -> %s\n", W, H, (unsigned long long)n, o.preview.c_str());
@@ -562,6 +600,12 @@ int main(int argc, char** argv) {
         else if (a == "--pipeline") o.pipeline = std::string(next()) == "multipass" ? M2S_PIPELINE_MULTIPASS : M2S_PIPELINE_AUTO;
         else if (a == "--timing") o.timing = true;
         else if (a == "--preview") o.preview = next();
+        else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
+        else if (a == "--light") {
+            const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
+            if (got < 3) { usage(); return 2; }
+            o.has_light = true;
+        }
         else if (a == "--preview-size") {
             if (std::sscanf(next(), "%dx%d", &o.preview_w, &o.preview_h) != 2 || o.preview_w < 1 || o.preview_h < 1 || o.preview_w > 8192 ||
                 o.preview_h > 8192) { usage(); return 2; }
