@@ -518,6 +518,64 @@ m2s_status m2s_download_shadow_counts(m2s_ctx* ctx, uint8_t* dst, uint64_t capac
 /* Duration (ms) of the last profiled m2s_relight. */
 float m2s_last_relight_ms(const m2s_ctx* ctx);
 
+/* ---- mesh depth prepass == DepthPrepass::execute (DepthPrepass.cpp:8-50, depthPrepass{VS,PS}.glsl) ------------------------------- */
+/* Draws the opaque meshes of the UPLOADED SCENE (not records) with the camera of the frame, depth only, depth test GL_LESS, into a
+ * W x H image cleared to 1.0: the reference's meshDepthTexture (renderer.cpp:281-309), which the viewer prepass tests its Gaussians
+ * against (m2s_prepass_params.depth_test_mesh).  Under m2s_set_triangle_range it draws the uploaded range only (the image of a whole
+ * scene is the texel-wise min of its shards' images).  GL semantics restated for a compute pass; these choices are the pin
+ * (tests/meshdepth_ref.py restates them operation for operation).  All of it is decision arithmetic: fp32, no contraction, divisions
+ * correctly rounded.
+ *  - Which meshes: base_color[3] == 1.0f exactly (DepthPrepass.cpp:33).  Both windings: the pass does not enable culling.
+ *  - Vertex: gl_Position = ((P V) M) (p, 1).  The two mat4 x mat4 products are taken once per call in glm's order — element (i, j) =
+ *    ((A[0][i] B[j][0] + A[1][i] B[j][1]) + A[2][i] B[j][2]) + A[3][i] B[j][3] — then one mat4 x vec4 per vertex as
+ *    (m0 x + m1 y) + (m2 z + m3 w).  (Last-bit differences from the prepass's step-by-step transform, as in the reference.)  A vertex
+ *    shared by several triangles gets the same clip coordinates in each: watertight.
+ *  - A triangle with a non-finite clip coordinate is SKIPPED and counted ([2]).
+ *  - Clipping: five planes in the fixed order near (d = z + w), +x (d = 2w - x), -x (2w + x), +y (2w - y), -y (2w + y); a vertex
+ *    is inside a plane when d >= 0.  A triangle whose three vertices are outside ONE plane is rejected.  One whose vertices are
+ *    inside all five is not clipped at all.  Any other goes through Sutherland-Hodgman, plane by plane over the polygon's edges
+ *    (cur, next): emit cur when inside; where the edge crosses, emit in + t (out - in) for the four clip coordinates with
+ *    t = d_in / (d_in - d_out), always from the INSIDE vertex (both triangles at a shared edge get the same point).  The polygon
+ *    (at most 8 vertices) is fanned from its first vertex.  The factor 2 keeps every vertex that reaches the snap inside the
+ *    +-16384 px guard band for W, H <= 8192; the edges it introduces lie outside the window.  No far clip: see z_w.
+ *  - Per piece (the triangle, or one triangle of the fan): x_n = x / w, y_n = y / w, z_w = (z / w) * 0.5 + 0.5 per vertex.  A piece
+ *    none of whose z_w is < 1.0 is rejected (it cannot pass GL_LESS against the clear value).  Viewport xw = (W/2) x_n + W/2,
+ *    yw = (H/2) y_n + H/2, then the project's pinned rasteriser as m2s_splat uses it: snap to 1/256 px (RNE), +-16384 px guard band
+ *    (beyond it, or NaN: rejected), int64 edge functions, both windings, top-left rule, pixel centres (x + 0.5, y + 0.5); zero
+ *    area: rejected.
+ *    The three vertices of a piece are then put in ascending (Y, X) order of their snapped coordinates, so that neither the winding
+ *    nor the order in which a triangle's vertices are stored changes a bit of the image.
+ *  - Depth of a fragment: with E_i the int64 edge function opposite vertex i at the pixel centre (interior positive) and
+ *    inv = 1.0f / (float)|area2|:  b_i = (float)E_i * inv;  z = (b_0 z_w0 + b_1 z_w1) + b_2 z_w2;  clamped to [0, 1]; a NaN never
+ *    passes.  (z_w is affine in window space; these are the conversion's barycentrics.)
+ *  - Storage: fp32 (the reference asks for an unsized GL_DEPTH_COMPONENT; the prepass's eps of 2e-5 is far above either choice):
+ *    float[H][W], row 0 = the BOTTOM row — exactly the layout m2s_prepass_params.depth expects, so m2s_device_mesh_depth() can be
+ *    passed straight back with depth_on_device = 1, depth_w = W, depth_h = H.  A texel ends as min(1.0, min over covering fragments):
+ *    order-independent and idempotent.
+ * Counts (out_counts may be NULL): [0] triangles drawn (opaque, finite, at least one piece not rejected), [1] triangles that went
+ * through the clipper, [2] triangles skipped for a non-finite vertex, [3] (tile, piece) pairs of the binned path, [4] texel updates
+ * sent ([3] and [4] depend on how the work was split, not on the scene alone: [4] also on timing).
+ * Synchronous.  Errors: M2S_ERR_INVALID for a resolution outside 1..8192 or reserved != 0; M2S_ERR_STATE without a scene;
+ * M2S_ERR_CAPACITY beyond 2^31-1 pairs.  A scene with no opaque mesh gives an image of 1.0. */
+typedef struct m2s_mesh_depth_params {
+    float world_to_view[16], view_to_clip[16], model_to_world[16];  /* column-major, as m2s_prepass_params */
+    int32_t resolution[2];      /* rendererResolution, 1..8192 each */
+    uint32_t reserved[2];       /* 0 */
+} m2s_mesh_depth_params;
+m2s_status m2s_mesh_depth(m2s_ctx* ctx, const m2s_mesh_depth_params* params, uint64_t out_counts[5]);
+/* The image of the last m2s_mesh_depth: float[H][W] on the device, row 0 = bottom (context-owned, grow-only).  NULL before any. */
+const void* m2s_device_mesh_depth(const m2s_ctx* ctx);
+m2s_status m2s_download_mesh_depth(m2s_ctx* ctx, float* dst, uint64_t capacity_floats);
+/* Duration (ms) of the last profiled m2s_mesh_depth (sum of its stages), and the stages: [0] clear + setup + triangles covered in
+ * place, [1] clipper + binning (records, tile counts, pairs, radix sort), [2] tile raster. */
+float m2s_last_mesh_depth_ms(const m2s_ctx* ctx);
+m2s_status m2s_last_mesh_depth_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+m2s_status m2s_last_mesh_depth_counts(const m2s_ctx* ctx, uint64_t out[5]);
+/* Test hook: an unclipped triangle whose pixel box is at most max_box pixels wide and high is covered by its own lane instead of
+ * being binned (default 4; -1 restores it).  0 sends every triangle through the binned path, 8192 every unclipped one through the
+ * in-place path.  The image does not depend on it. */
+m2s_status m2s_debug_set_mesh_depth_inplace(m2s_ctx* ctx, int32_t max_box);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

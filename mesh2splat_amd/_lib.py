@@ -40,6 +40,8 @@ EXPORTS = (
     "m2s_shadow", "m2s_shadow_from_quads", "m2s_device_shadow_cubemap", "m2s_download_shadow_cubemap", "m2s_download_shadow_quads", "m2s_upload_shadow_cubemap",
     "m2s_last_shadow_ms", "m2s_last_shadow_stage_ms", "m2s_last_shadow_counts", "m2s_relight", "m2s_upload_gbuffer", "m2s_device_frame",
     "m2s_download_frame", "m2s_download_shadow_counts", "m2s_last_relight_ms",
+    "m2s_mesh_depth", "m2s_device_mesh_depth", "m2s_download_mesh_depth", "m2s_last_mesh_depth_ms", "m2s_last_mesh_depth_stage_ms",
+    "m2s_last_mesh_depth_counts", "m2s_debug_set_mesh_depth_inplace",
 )
 
 
@@ -207,6 +209,13 @@ def load():
         "m2s_download_frame": (C.c_int, [vp, vp, u64]),
         "m2s_download_shadow_counts": (C.c_int, [vp, vp, u64]),
         "m2s_last_relight_ms": (C.c_float, [vp]),
+        "m2s_mesh_depth": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_device_mesh_depth": (vp, [vp]),
+        "m2s_download_mesh_depth": (C.c_int, [vp, vp, u64]),
+        "m2s_last_mesh_depth_ms": (C.c_float, [vp]),
+        "m2s_last_mesh_depth_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_last_mesh_depth_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_debug_set_mesh_depth_inplace": (C.c_int, [vp, C.c_int32]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -51,6 +51,22 @@ def marshal_scene(scene: Scene):
     return arr, keep
 
 
+class _DeviceImage:
+    """A (h, w) float32 image at a device address, in the shape mesh2splat_amd.prepass.to_c reads a CUDA tensor."""
+
+    def __init__(self, ptr: int, h: int, w: int):
+        self._ptr, self.shape = int(ptr), (int(h), int(w))
+
+    def data_ptr(self) -> int:
+        return self._ptr
+
+    def contiguous(self):
+        return self
+
+    def float(self):
+        return self
+
+
 class Converter:
     """Thin owner of one m2s_ctx (one per host thread / per GPU rank)."""
 
@@ -455,16 +471,69 @@ class Converter:
     def device_frame(self) -> int:
         return int(self._L.m2s_device_frame(self._h) or 0)
 
-    def render_frame(self, prepass_params, light_params):
-        """One viewer frame of the context's records (renderer.cpp:129-138 without the mesh passes): prepass + depth sort + splat +
+    def mesh_depth(self, params, download: bool = True):
+        """DepthPrepass (m2s_mesh_depth): the opaque meshes of the uploaded scene drawn depth-only through the camera of `params`
+        (a mesh2splat_amd.meshdepth.MeshDepthParams, or a PrepassParams whose camera, model matrix and resolution are taken).
+        -> (image (H, W) float32 window-space depth, row 0 = bottom, 1.0 = nothing drawn; counts dict); download=False: counts alone
+        (the image stays on the device: device_mesh_depth, ready to be handed to prepass() as a device image)."""
+        from . import meshdepth as _md
+        mc = _md.to_c(params)
+        v = (C.c_uint64 * 5)()
+        self._check(self._L.m2s_mesh_depth(self._h, C.byref(mc), v))
+        self._last_md_wh = (int(mc.resolution[0]), int(mc.resolution[1]))
+        counts = {k: int(v[i]) for i, k in enumerate(_md.COUNT_NAMES)}
+        if not download:
+            return counts
+        return self.download_mesh_depth(), counts
+
+    _last_md_wh = (0, 0)
+
+    def download_mesh_depth(self) -> np.ndarray:
+        W, H = self._last_md_wh
+        img = np.empty((max(H, 1), max(W, 1)), np.float32)          # (before any image: the library answers M2S_ERR_STATE)
+        self._check(self._L.m2s_download_mesh_depth(self._h, img.ctypes.data, img.size))
+        return img
+
+    @property
+    def device_mesh_depth(self) -> int:
+        return int(self._L.m2s_device_mesh_depth(self._h) or 0)
+
+    def debug_set_mesh_depth_inplace(self, max_box: int):
+        """Test hook (m2s_debug_set_mesh_depth_inplace): pixel-box side up to which a triangle is covered in place; -1: default."""
+        self._check(self._L.m2s_debug_set_mesh_depth_inplace(self._h, int(max_box)))
+
+    @property
+    def last_mesh_depth_ms(self) -> float:
+        return float(self._L.m2s_last_mesh_depth_ms(self._h))
+
+    def last_mesh_depth_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_mesh_depth_stage_ms(self._h, ms))
+        return {"setup": float(ms[0]), "bin": float(ms[1]), "raster": float(ms[2])}
+
+    def _with_device_mesh_depth(self, prepass_params):
+        """A copy of `prepass_params` that tests against the context's mesh depth image in place (depth_on_device)."""
+        import dataclasses
+        W, H = self._last_md_wh
+        return dataclasses.replace(prepass_params, perform_mesh_depth_test=True, mesh_depth=_DeviceImage(self.device_mesh_depth, H, W))
+
+    def render_frame(self, prepass_params, light_params, mesh_depth_test: bool = False):
+        """One viewer frame of the context's records (renderer.cpp:129-138 without the mesh render pass): prepass + depth sort + splat +
         shadow + relight.  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
-        renderer_resolution must equal `prepass_params`'s.  -> what relight() returns."""
+        renderer_resolution must equal `prepass_params`'s.  mesh_depth_test: the frame starts with the mesh depth prepass of the uploaded
+        scene (mesh_depth) and the Gaussian prepass — then m2s_prepass_sorted — tests against its image on the device, the reference's
+        "use the mesh as occluder in depth prepass".  -> what relight() returns."""
         from .splat import SplatParams
         res = tuple(int(v) for v in prepass_params.renderer_resolution)
         if tuple(int(v) for v in light_params.renderer_resolution) != res:
             raise ValueError("light_params.renderer_resolution differs from prepass_params.renderer_resolution")
-        self.prepass(prepass_params, download=False)
-        if self.sort_prepass(download=False):
+        if mesh_depth_test:
+            self.mesh_depth(prepass_params, download=False)
+            visible = self.prepass_sorted(self._with_device_mesh_depth(prepass_params), download=False)
+        else:
+            self.prepass(prepass_params, download=False)
+            visible = self.sort_prepass(download=False)
+        if visible:
             self.splat(SplatParams(res, int(prepass_params.render_mode)), download=False)
         else:
             import torch
@@ -554,6 +623,7 @@ class RenderContext:
         self.prepassParams = None                 # what GaussiansPrepass read: a mesh2splat_amd.prepass.PrepassParams (the shadow pass's per-record inputs)
         self.lightParams = None                   # RenderContext::pointLightData + camera: a mesh2splat_amd.light.LightParams
         self.shadowCubemap = None                 # written by GaussianShadowPass::execute: (6, S, S) float32
+        self.mesh_depth = None                    # written by DepthPrepass::execute: (H, W) float32 window-space depth, row 0 = bottom
         self.frame = None                         # written by GaussianRelightingPass::execute: (H, W, 4) uint8, row 0 = bottom
         self._uploaded_scene = None
 
@@ -588,6 +658,19 @@ class ConversionPass(IRenderPass):
             context.converter.upload_scene(context.scene)
             context._uploaded_scene = context.scene
         context.numberOfGaussians = context.converter.convert(context.resolutionTarget)
+
+
+class DepthPrepass(IRenderPass):
+    """DepthPrepass::execute (DepthPrepass.cpp:8-50): the opaque meshes of the uploaded scene drawn depth-only with the camera of
+    context.prepassParams.  The image ends up in context.mesh_depth ((H, W) float32, row 0 = bottom) and, when
+    context.prepassParams.perform_mesh_depth_test is set, in context.prepassParams.mesh_depth — where Converter.prepass picks it up."""
+
+    def execute(self, context: RenderContext):
+        if context.converter is None or context.prepassParams is None or context._uploaded_scene is None:
+            raise RuntimeError("needs an uploaded scene (ConversionPass) and context.prepassParams")
+        context.mesh_depth, _ = context.converter.mesh_depth(context.prepassParams)
+        if context.prepassParams.perform_mesh_depth_test:
+            context.prepassParams.mesh_depth = context.mesh_depth
 
 
 class GaussianSplattingPass(IRenderPass):

@@ -195,6 +195,11 @@ void m2s_destroy(m2s_ctx* c) {
         if (p) (void)hipFree(p);
     if (c->h_sh) (void)hipHostFree(c->h_sh);
     for (hipEvent_t e : c->light_ev) if (e) (void)hipEventDestroy(e);
+    for (void* p : { (void*)c->d_md_image, (void*)c->d_md_deferred, c->d_md_rec, (void*)c->d_md_cnt, (void*)c->d_md_off, (void*)c->d_md_pairs, c->d_md_temp,
+                     (void*)c->d_md_totals })
+        if (p) (void)hipFree(p);
+    if (c->h_md) (void)hipHostFree(c->h_md);
+    for (hipEvent_t e : c->md_ev) if (e) (void)hipEventDestroy(e);
     if (c->d_loaded) (void)hipFree(c->d_loaded);
     if (c->d_rows) (void)hipFree(c->d_rows);
     for (int k = 0; k < 2; ++k) if (c->h_export[k]) (void)hipHostFree(c->h_export[k]);

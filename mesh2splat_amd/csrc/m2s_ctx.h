@@ -4,6 +4,7 @@
 //   m2s_records.cpp  read-back, .ply export, record adoption               m2s_viewer.cpp   depth sort, viewer prepass
 //   m2s_splat.cpp    the splat pass (== GaussianSplattingPass::execute) and its G-buffer
 //   m2s_light.cpp    the shadow and relighting passes (== GaussianShadowPass / GaussianRelightingPass::execute)
+//   m2s_meshdepth.cpp  the mesh depth prepass (== DepthPrepass::execute)
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -224,6 +225,27 @@ struct m2s_ctx {
     int32_t frame_w = 0, frame_h = 0;        // 0: no relight has run
     bool frame_has_counts = false;
     float last_relight_ms = 0.0f;
+    // mesh depth prepass (m2s_meshdepth.cpp): the image and the pass's grow-only work buffers
+    float* d_md_image = nullptr;             // float[H][W], row 0 = bottom
+    uint64_t md_image_cap = 0;               // texels
+    int32_t md_w = 0, md_h = 0;              // 0: no image yet
+    int32_t md_inplace = -1;                 // m2s_debug_set_mesh_depth_inplace (-1: the default, kMdInplace)
+    uint32_t* d_md_deferred = nullptr;       // triangles the setup kernel left to the binned path (capacity: md_tri_cap)
+    uint64_t md_tri_cap = 0;
+    void* d_md_rec = nullptr;                // per deferred triangle six slots: 48-byte record, tile count (u32), scan of the counts (u64)
+    uint32_t* d_md_cnt = nullptr;
+    unsigned long long* d_md_off = nullptr;
+    uint64_t md_slot_cap = 0;
+    uint32_t* d_md_pairs = nullptr;          // keys_in | vals_in | keys_out | vals_out, md_pairs_cap each
+    uint64_t md_pairs_cap = 0;
+    void* d_md_temp = nullptr;               // scan / radix sort work area
+    uint64_t md_temp_cap = 0;
+    unsigned long long* d_md_totals = nullptr;   // 8 words: see meshdepth_setup
+    unsigned long long* h_md = nullptr;          // pinned copy
+    hipEvent_t md_ev[6] = {};
+    float last_md_ms = 0.0f;
+    float last_md_stage_ms[3] = { 0, 0, 0 };     // setup + in-place, clip + binning, tile raster (profiling on)
+    uint64_t last_md_counts[5] = {};             // drawn, clipped, non-finite, pairs, texel updates sent
 
     // measurement
     bool profiling = false;

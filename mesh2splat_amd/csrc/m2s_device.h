@@ -268,6 +268,26 @@ hipError_t shadow_raster(const float4* rec, const uint32_t* keys, const uint32_t
 hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st);
 hipError_t preload_light();
 
+// ---- mesh depth prepass (m2s_meshdepth.hip): DepthPrepass over the uploaded scene's position planes -------------------------------
+struct MeshDepthK {
+    float PVM[16];      // (view_to_clip * world_to_view) * model_to_world, fp32 in glm's order (m2s_meshdepth.cpp), column-major
+    int32_t W, H;
+    int32_t inplace;    // an unclipped triangle whose pixel box is at most this many pixels wide AND high is covered by its own lane
+};
+constexpr int kMdInplace = 4;                  // the default of MeshDepthK::inplace
+constexpr int kMdSlotsPerTriangle = 6;         // records (48 B) and tile counts per deferred triangle
+size_t meshdepth_temp_bytes(uint32_t n_slots, uint32_t pairs);
+hipError_t meshdepth_clear(float* image, int W, int H, hipStream_t st);        // every texel 1.0
+// totals (zero before): [0] triangles drawn, [1] clipped, [2] non-finite, [3] (tile, piece) pairs, [4] texel updates sent, [5] deferred
+hipError_t meshdepth_setup(const MeshDepthK& k, const SceneDev& sc, float* image, uint32_t* deferred, unsigned long long* totals, hipStream_t st);
+hipError_t meshdepth_deferred(const MeshDepthK& k, const SceneDev& sc, const uint32_t* deferred, uint32_t nd, float4* rec, uint32_t* cnt,
+                              unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st);
+hipError_t meshdepth_bin(const MeshDepthK& k, const float4* rec, const uint32_t* cnt, const unsigned long long* off, uint32_t nd, uint32_t* keys_in,
+                         uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t pairs, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t meshdepth_raster(const MeshDepthK& k, const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, float* image,
+                            unsigned long long* totals, hipStream_t st);
+hipError_t preload_meshdepth();
+
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);
 void launch_lower_bounds(const uint32_t* keys, uint64_t n, const unsigned long long* splitters, uint32_t m, unsigned long long* out, hipStream_t st);

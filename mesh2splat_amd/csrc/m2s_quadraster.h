@@ -1,5 +1,5 @@
-// m2s_quadraster.h — what the two passes that rasterise instanced quads share (m2s_splat.hip: the splat pass into the G-buffer;
-// m2s_light.hip: the shadow pass into the depth cube): the quad's four vertices in the pinned order and rounding, and the per-tile
+// m2s_quadraster.h — what the passes that rasterise per 16 x 16 tile share (m2s_splat.hip: the splat pass into the G-buffer;
+// m2s_light.hip: the shadow pass into the depth cube; m2s_meshdepth.hip: the mesh depth prepass, triangles instead of quads): the quad's four vertices in the pinned order and rounding, and the per-tile
 // form of the pinned rasteriser (raster_setup_wh, m2s_devfn.h) — exact int64 edge arithmetic once per (triangle, 16 x 16 tile), after
 // which the 256 lanes of the tile test coverage with 32-bit products.  One definition, so that both passes cover the same pixels.
 #pragma once
@@ -77,22 +77,49 @@ __device__ __forceinline__ void emit_tile_pairs(uint32_t tb0, uint32_t tb1, int 
         }
 }
 
+// The same pairs written by the 64 lanes of one wave, 64 consecutive pairs per step: `count` = tiles of the box
+__device__ __forceinline__ void emit_tile_pairs_wave(uint32_t tb0, uint32_t tb1, int tiles_x, uint32_t count, size_t k, uint32_t i, int lane,
+                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t t0x = tb0 & 0xFFFF, t0y = tb0 >> 16, bw = (tb1 & 0xFFFF) - t0x + 1u;
+    for (uint32_t j = (uint32_t)lane; j < count; j += 64u) {
+        const uint32_t ry = j / bw, rx = j - ry * bw;
+        keys[k + j] = (t0y + ry) * (uint32_t)tiles_x + t0x + rx;
+        vals[k + j] = i;
+    }
+}
+
+// Edge i (opposite vertex i) of the triangle with doubled signed area `area2`, oriented so that the interior is positive: its
+// coefficients a, b (E_i(P) = a Px + b Py + c), its value e at the centre of pixel (px0, py0) — P = 256 (x, y) + 128 — and the
+// top-left rule's bias (1: the edge's own boundary is inside).  int64, exact: raster_setup_wh's integers.
+__device__ __forceinline__ void tile_edge(const int X[3], const int Y[3], int i, int sgn, int px0, int py0, int& a, int& b, long long& e, int& bias) {
+    const int ia = (i + 1) % 3, ib = (i + 2) % 3;
+    const int dy = Y[ib] - Y[ia], dx = X[ib] - X[ia];
+    a = -dy * sgn;
+    b = dx * sgn;
+    const long long c = ((long long)dy * X[ia] - (long long)dx * Y[ia]) * sgn;
+    bias = (a > 0 || (a == 0 && b > 0)) ? 1 : 0;
+    e = (long long)a * (256ll * px0 + 128) + (long long)b * (256ll * py0 + 128) + c;
+}
+__device__ __forceinline__ long long tri_area2(const int X[3], const int Y[3]) {
+    return (long long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long long)(Y[1] - Y[0]) * (X[2] - X[0]);
+}
+
 // One triangle's edge thresholds for the tile whose first pixel is (px0, py0): pixel (px0 + lx, py0 + ly) is inside edge i iff
 // a_i lx + b_i ly > T_i, with E_i(P) = a_i Px + b_i Py + c_i at the pixel centre P = 256 (x, y) + 128 and the top-left rule's bias:
 // E + bias > 0  <=>  256 (a lx + b ly) > -(E_org + bias)  <=>  a lx + b ly > floor(-(E_org + bias) / 256).
-__device__ __forceinline__ void stage_triangle(const int X[3], const int Y[3], int px0, int py0, int4& ea, int4& eb, int& t2) {
-    const long long area2 = (long long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long long)(Y[1] - Y[0]) * (X[2] - X[0]);
+// E_org (or nullptr): the three edge values at the centre of the tile's first pixel, without the bias — what a pass that interpolates
+// over the triangle (the mesh depth pass) builds its barycentrics from: E_i(lx, ly) = E_org[i] + 256 (a_i lx + b_i ly).
+__device__ __forceinline__ void stage_triangle(const int X[3], const int Y[3], int px0, int py0, int4& ea, int4& eb, int& t2, long long* E_org = nullptr) {
+    const long long area2 = tri_area2(X, Y);
     const int sgn = area2 < 0 ? -1 : 1;
     int a[3], b[3], T[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        const int ia = (i + 1) % 3, ib = (i + 2) % 3;
-        const int dy = Y[ib] - Y[ia], dx = X[ib] - X[ia];
-        a[i] = -dy * sgn;
-        b[i] = dx * sgn;
-        const long long c = ((long long)dy * X[ia] - (long long)dx * Y[ia]) * sgn;
-        const int bias = (a[i] > 0 || (a[i] == 0 && b[i] > 0)) ? 1 : 0;
-        const long long e = (long long)a[i] * (256ll * px0 + 128) + (long long)b[i] * (256ll * py0 + 128) + c + bias;
+        int bias;
+        long long e0;
+        tile_edge(X, Y, i, sgn, px0, py0, a[i], b[i], e0, bias);
+        if (E_org) E_org[i] = e0;
+        const long long e = e0 + bias;
         long long t = (-e) >> 8;                      // floor(-e / 256)
         t = t < -(long long)kTMax ? -(long long)kTMax : t > (long long)kTMax ? (long long)kTMax : t;
         T[i] = (int)t;

@@ -58,6 +58,7 @@ struct Options {
     bool threads = false;                                          // ranks as threads of this process
     std::string preview;                                           // --preview view.png: prepass + depth sort + splat of the result
     int preview_w = 1280, preview_h = 720;
+    bool mesh_depth_test = false;                                  // --mesh-depth-test: the preview uses the mesh as occluder (m2s_mesh_depth)
     int preview_mode = 0;                                          // --preview-mode N: 0..4 the albedo plane (as before), 5 / 6 the relit frame
     bool has_light = false;                                        // --light x,y,z[,intensity]
     double light[4] = { 0, 0, 0, 0 };
@@ -70,7 +71,7 @@ void usage() {
                  "       mesh2splat --batch in_dir --out out_dir [options]\n"
                  "options: [--density R | --quality q [--max-res M]] [--std s] [--format 0|1|2] [--device d] [--gpus N [--gather]]\n"
                  "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
-                 "         [--preview view.png [--preview-size WxH (default 1280x720)]]\n"
+                 "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test]]\n"
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
@@ -204,8 +205,31 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     std::printf("preview camera: eye=%.17g,%.17g,%.17g centre=%.17g,%.17g,%.17g near=%.17g far=%.17g\n", eye[0], eye[1], eye[2], ctr[0],
                 ctr[1], ctr[2], near_p, far_p);
     uint64_t visible = 0, n = 0, skipped = 0;
-    if (m2s_prepass(ctx, &pp, nullptr, 0, &visible) != M2S_OK) return 1;
-    if (m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
+    if (o.mesh_depth_test) {
+        // the mesh as occluder: DepthPrepass with the preview camera, then the Gaussian prepass against its image (on the device)
+        m2s_mesh_depth_params mp;
+        std::memset(&mp, 0, sizeof(mp));
+        std::memcpy(mp.world_to_view, pp.world_to_view, sizeof(mp.world_to_view));
+        std::memcpy(mp.view_to_clip, pp.view_to_clip, sizeof(mp.view_to_clip));
+        std::memcpy(mp.model_to_world, pp.model_to_world, sizeof(mp.model_to_world));
+        mp.resolution[0] = W; mp.resolution[1] = H;
+        uint64_t mc[5] = {};
+        if (m2s_mesh_depth(ctx, &mp, mc) != M2S_OK) return 1;
+        pp.depth_test_mesh = 1;
+        pp.depth = static_cast<const float*>(m2s_device_mesh_depth(ctx));
+        pp.depth_w = (uint32_t)W; pp.depth_h = (uint32_t)H;
+        pp.depth_on_device = 1;
+        if (m2s_prepass_sorted(ctx, &pp, &visible) != M2S_OK) return 1;
+        n = visible;
+        std::printf("mesh depth test: %llu triangles drawn (%llu clipped), %llu Gaussians pass\n", (unsigned long long)mc[0], (unsigned long long)mc[1],
+                    (unsigned long long)visible);
+        pp.depth_test_mesh = 0;          // (the shadow pass below reads the per-record fields only)
+        pp.depth = nullptr;
+        pp.depth_on_device = 0;
+    } else {
+        if (m2s_prepass(ctx, &pp, nullptr, 0, &visible) != M2S_OK) return 1;
+        if (m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
+    }
     std::vector<uint8_t> img((size_t)W * H * 4, 0);
     const bool relit = o.preview_mode == 5 || o.preview_mode == 6;
     if (n || relit) {
@@ -600,6 +624,7 @@ int main(int argc, char** argv) {
         else if (a == "--pipeline") o.pipeline = std::string(next()) == "multipass" ? M2S_PIPELINE_MULTIPASS : M2S_PIPELINE_AUTO;
         else if (a == "--timing") o.timing = true;
         else if (a == "--preview") o.preview = next();
+        else if (a == "--mesh-depth-test") o.mesh_depth_test = true;
         else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
