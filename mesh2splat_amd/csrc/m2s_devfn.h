@@ -1018,6 +1018,19 @@ __device__ __forceinline__ T ld_plane(const T* base, uint32_t t) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)(t * (uint32_t)sizeof(T)));
 }
 
+// ld_plane, or the same read marked non-temporal (word by word: the backend merges them into one dwordx4 nt, as in nt_store)
+template <bool kNT, typename T>
+__device__ __forceinline__ T ld_attr(const T* base, uint32_t t) {
+    if constexpr (!kNT) return ld_plane(base, t);
+    else {
+        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)(t * (uint32_t)sizeof(T)));
+        if constexpr (sizeof(T) == 16) {
+            return make_float4(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y),
+                               __builtin_nontemporal_load(&p->z), __builtin_nontemporal_load(&p->w));
+        } else return __builtin_nontemporal_load(p);
+    }
+}
+
 // The per-fragment part of rasteriser + FS (converterFS.glsl:44-104) for pixel (x,y) of triangle t.
 // `mp` should be wave-uniform (scalar) for speed; correctness does not depend on it.
 // `stamps` (debug timing builds only, else nullptr and folded away): three s_memtime slots.
@@ -1028,10 +1041,12 @@ __device__ __forceinline__ T ld_plane(const T* base, uint32_t t) {
 
 // kComboOnly (k_fused3): the caller guarantees that the mesh samples through its combo texture or has no map at all; the
 // separate-maps sampler is then not compiled into the caller (it is what sets the register count of the fragment stage).
-template <class MP, class TS = TriShade, bool kComboOnly = false>   // TS: TriShade, or the 64-byte TriShadeS (same field names)
+// kStreamAttr (A/B switch of k_fused3): the normal and tangent planes, which a conversion reads once, are loaded non-temporally.
+template <class MP, class TS = TriShade, bool kComboOnly = false, bool kStreamAttr = false>   // TS: TriShade, or the 64-byte TriShadeS (same field names)
 __device__ __forceinline__ void shade_from_tri(const TriPlanes& tp, uint32_t t, int x, int y, MP mp,
                                                const TS& ts, float4 rec[6], unsigned long long* stamps = nullptr,
-                                               const float2* uvl = nullptr /* (u0,v0), (u1-u0,v1-v0), (u2-u0,v2-v0) kept by the caller */) {
+                                               const float2* uvl = nullptr /* (u0,v0), (u1-u0,v1-v0), (u2-u0,v2-v0) kept by the caller */,
+                                               const float* posl = nullptr /* the nine position words (A0, A1, A2) kept by the caller */) {
     // screen-linear barycentrics from the exact integer edge functions, evaluated relative to the
     // triangle's bbox origin pixel: E_i(x,y) = E_i(x0,y0) + a_i*256*(x-x0) + b_i*256*(y-y0)
     const int dx256 = (x - (int)(ts.org & 0xFFFu)) * 256, dy256 = (y - (int)(ts.org >> 12)) * 256;
@@ -1060,11 +1075,20 @@ __device__ __forceinline__ void shade_from_tri(const TriPlanes& tp, uint32_t t, 
         b0 = ld_plane(tp.B0, t);
         b1 = ld_plane(tp.B1, t);
     }
-    const float4 a0 = ld_plane(tp.A0, t), a1 = ld_plane(tp.A1, t);
-    const float a2 = ld_plane(tp.A2, t);
-    const float4 c0 = ld_plane(tp.C0, t), c1 = ld_plane(tp.C1, t);
-    const float c2 = ld_plane(tp.C2, t);
-    const float4 d0 = ld_plane(tp.D0, t), d1 = ld_plane(tp.D1, t), d2 = ld_plane(tp.D2, t);
+    float4 a0, a1;
+    float a2;
+    if (posl == nullptr) {
+        a0 = ld_plane(tp.A0, t); a1 = ld_plane(tp.A1, t);
+        a2 = ld_plane(tp.A2, t);
+    }
+    const float4 c0 = ld_attr<kStreamAttr>(tp.C0, t), c1 = ld_attr<kStreamAttr>(tp.C1, t);
+    const float c2 = ld_attr<kStreamAttr>(tp.C2, t);
+    const float4 d0 = ld_attr<kStreamAttr>(tp.D0, t), d1 = ld_attr<kStreamAttr>(tp.D1, t), d2 = ld_attr<kStreamAttr>(tp.D2, t);
+    if (posl != nullptr) {   // (the same words the planes hold: the caller copied them)
+        a0 = make_float4(posl[0], posl[1], posl[2], posl[3]);
+        a1 = make_float4(posl[4], posl[5], posl[6], posl[7]);
+        a2 = posl[8];
+    }
     float U, V;
     {   // texture coordinates: exact oracle sequence (no FMA), see tri_shade_setup
 #pragma clang fp contract(off)

@@ -13,12 +13,33 @@
 //     k_fused2 does with triangles of more than 16 rows.  The host uses this kernel only while such triangles are rare
 //     (run_pass: a launch that deferred many switches the scene back to k_fused2 at that R);
 //   * fragment constants as TriShadeS (64 B: 16-bit edge coefficients, 32-bit edge values — exact for such boxes), barycentrics
-//     in 32-bit integers; entries are 16 bits (lane << 6 | bit of the mask);
+//     in 32-bit integers; entries are ONE byte (bit of the mask | first << 6, `first` = first fragment of its triangle): the owner
+//     wave follows from the stream position, the triangle from the wave's prefix sums `cum` (below);
 //   * only meshes that sample their combo texture or no map at all (decided at upload: SceneDev has no other mesh);
 //   * fragment constants are computed and stored BEFORE the wave waits for anything: across the waits a lane keeps its mask,
-//     its counts and its triangle index, nothing else; the strip loop re-reads the workgroup's protocol words from LDS.
+//     its counts and its triangle index, nothing else; the strip loop re-reads the workgroup's protocol words from LDS;
+//   * the texture coordinates a strip needs — (uv0, uv1 - uv0, uv2 - uv0) per triangle — are stored next to the fragment constants:
+//     the triangle phase has the B planes in registers anyway, and a strip computes its texel addresses without a global round trip
+//     in front of them (and without fetching the two planes a second time).
+//
+// LDS per workgroup (F3Lds, 40 824 of the 40 960 bytes that four workgroups per CU leave each):
+//     tri      16 384   TriShadeS, [wave][lane]
+//     uv        6 144   float2[3], [wave][lane]
+//     tskip     1 024   [wave][lane]; read only by strips of a workgroup with deferred triangles
+//     cum         512   uint16 [wave][slot]: inclusive prefix of the entry counts over the wave's COVERED triangles (slot = rank of the
+//                       triangle among those with entries; unused slots hold 0xFFFF)
+//     lane_of     256   uint8 [wave][slot]: the lane (triangle of the batch) of that slot
+//     entries   4 096   one byte each
+//     stage    12 288   32 records per wave
+//     ctl         120
+// Decoding a strip: for every owner wave in it, lane l reads cum[ow][l] and the wave ballots cum <= q0 (q0 = the strip's first
+// position inside that wave's entries): the popcount is the slot at that position; a lane's slot is that plus the `first` flags
+// between the wave's first lane in the strip and itself.
 //
 // kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup).
+// Measurement-only switches (compile time; the A/B tables of DESIGN 6): M2S_FUSED3_UV_GLOBAL — the strips load the B planes as they
+// did before the coordinates moved to LDS; M2S_FUSED3_ABL_POS — the strips take the positions from stale LDS words instead of the
+// A planes (WRONG records: what the second read of those planes costs); M2S_FUSED3_NT_ATTR — normals / tangents as non-temporal loads.
 #include "m2s_fused_common.h"
 
 #pragma clang fp contract(off)
@@ -29,7 +50,7 @@ namespace m2s {
 #define M2S_FUSED3_WAVES 4                 // waves per SIMD the kernel is compiled for (= workgroups per CU)
 #endif
 #ifndef M2S_FUSED3_ENTRIES
-#define M2S_FUSED3_ENTRIES 1024            // entry-stream capacity per wave of the team (x2 bytes x 4 of LDS)
+#define M2S_FUSED3_ENTRIES 1024            // entry-stream capacity per wave of the team (x1 byte x 4 of LDS)
 #endif
 #ifndef M2S_FUSED3_STAGE
 #define M2S_FUSED3_STAGE (M2S_FUSED3_WAVES >= 5 ? 16 : 32)   // records staged per wave and round (32 = half a strip)
@@ -57,11 +78,20 @@ struct F3Ctl {
 struct F3Lds {
     float4 tri[kL3Team][64 * 4];           // TriShadeS of the four batches
     uint32_t tskip[kL3Team][64];           // per triangle: (record index - stream position) of its fragments
-    uint16_t entries[kL3Entries];          // lane << 6 | bit of the 8 x 8 mask  (the owning wave follows from the stream position)
+    float2 uv[kL3Team][64 * 3];            // per triangle: uv0, uv1 - uv0, uv2 - uv0 (shade_from_tri's `uvl`)
+    uint16_t cum[kL3Team][64];             // per slot (= covered triangle of the batch, in order): entries of the batch up to and with it
+    uint8_t lane_of[kL3Team][64];          // per slot: its triangle's lane
+    uint8_t entries[kL3Entries];           // bit of the 8 x 8 mask | first << 6  (the owning wave follows from the stream position)
     float4 stage[kL3Team][kL3Stage * 6];   // record staging, one per wave
     F3Ctl ctl;
 };
 static_assert(sizeof(F3Lds) * M2S_FUSED3_WAVES <= 163840, "M2S_FUSED3_WAVES workgroups per CU must fit the 160 KB of LDS");
+static_assert((uint32_t)M2S_FUSED3_ENTRIES * kL3Team < 0xFFFFu && 64u * 64u < 0xFFFFu, "cum is 16 bits wide, 0xFFFF marks an unused slot");
+#ifdef M2S_FUSED3_NT_ATTR
+constexpr bool kF3StreamAttr = true;
+#else
+constexpr bool kF3StreamAttr = false;
+#endif
 constexpr uint32_t kF3Irregular = 1u << 8;
 
 __device__ __forceinline__ uint32_t l3_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -218,6 +248,11 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
             const float4* src = reinterpret_cast<const float4*>(&c);
 #pragma unroll
             for (int k = 0; k < 4; ++k) S.tri[wave][lane * 4 + k] = src[k];
+            // ... and its texture coordinates in the form the strips interpolate (the subtractions shade_from_tri would do itself)
+            float2* const uvs = &S.uv[wave][lane * 3];
+            uvs[0] = make_float2(uvb0.x, uvb0.y);
+            uvs[1] = make_float2(uvb0.z - uvb0.x, uvb0.w - uvb0.y);
+            uvs[2] = make_float2(uvb1.x - uvb0.x, uvb1.y - uvb0.y);
         }
         if (__ballot(kind == kBig) != 0ull) {   // larger triangles (rare): the whole wave counts one of them, a pixel row per lane
             // (inline on purpose: as a non-inlined function this path gave the kernel a stack — 64 bytes of scratch per lane — and the
@@ -297,6 +332,16 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
     // ======================= my tskip and entries =======================
     if (alive) {
         if (cntc) S.tskip[wave][lane] = (uint32_t)((out0 + toff) - ((unsigned long long)stream0 + ctoff));
+        {   // the wave's prefix sums over its covered triangles, and which lane each of them is
+            const unsigned long long cov = __ballot(cntc != 0);
+            const uint32_t ncov = (uint32_t)__popcll(cov);
+            if ((uint32_t)lane >= ncov) S.cum[wave][lane] = 0xFFFFu;
+            if (cntc) {
+                const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(cov >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cov, 0u));
+                S.cum[wave][slot] = (uint16_t)inclc;
+                S.lane_of[wave][slot] = (uint8_t)lane;
+            }
+        }
         if (anybig) {   // deferred triangles: reserve their slice of the output, list them for k_emit_big
             unsigned long long bb;
             if (f3_get_base(C, chain, b0, lane, epoch, status, bb)) {
@@ -314,15 +359,16 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         if (kind == kSmall) {
             unsigned long long mm = mask;
             uint32_t ci = stream0 + ctoff;
-            const uint32_t tag = (uint32_t)lane << 6;
+            uint32_t first = 64u;
             while (mm) {
                 const int bit = __ffsll((long long)mm) - 1;
                 mm &= mm - 1;
-                S.entries[ci++] = (uint16_t)(tag | (uint32_t)bit);
+                S.entries[ci++] = (uint8_t)(first | (uint32_t)bit);
+                first = 0u;
             }
         }
     }
-    l3_store(&C.expanded[wave], 1u);   // release: TriShadeS, tskip, entries (set even on error so that nobody waits for it)
+    l3_store(&C.expanded[wave], 1u);   // release: TriShadeS, uv, tskip, cum, lane_of, entries (set even on error so that nobody waits for it)
     TLF(2);
     [[maybe_unused]] unsigned long long tl_strips = 0;
 
@@ -352,8 +398,8 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         ++tl_strips;
 #endif
         const uint32_t n = min(64u, stream_total - pos0);
+        const uint32_t lo[4] = { 0u, c1, c2, c3 }, hi[4] = { c1, c2, c3, stream_total };
         if (exp_seen != 15u) {   // the waves whose entries this strip contains must have expanded them
-            const uint32_t lo[4] = { 0u, c1, c2, c3 }, hi[4] = { c1, c2, c3, stream_total };
 #pragma unroll
             for (int k = 0; k < kL3Team; ++k) {
                 if ((exp_seen >> k) & 1u) continue;
@@ -375,7 +421,24 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         uint32_t en = 0;
         if (have) en = S.entries[pos];
         const uint32_t ow = (pos >= c1 ? 1u : 0u) + (pos >= c2 ? 1u : 0u) + (pos >= c3 ? 1u : 0u);   // owner wave of my entry
-        const uint32_t tl = (en >> 6) & 63u, bit = en & 63u;
+        const uint32_t bit = en & 63u;
+        // my triangle: the slot at the strip's first position inside my owner wave's entries + the `first` flags from there to me
+        uint32_t slot = 0;
+        {
+            const unsigned long long fm = __ballot(have && (en & 64u) != 0u);
+#pragma unroll
+            for (int k = 0; k < kL3Team; ++k) {
+                if (hi[k] <= pos0 || lo[k] >= pos0 + n || hi[k] == lo[k]) continue;   // (wave-uniform)
+                const uint32_t p0 = max(pos0, lo[k]);
+                const uint32_t q0 = p0 - lo[k], sl = p0 - pos0;   // position in that wave's entries / lane of the strip
+                const uint32_t s0 = (uint32_t)__popcll(__ballot((uint32_t)S.cum[k][lane] <= q0));
+                const unsigned long long fk = fm & ~((2ull << sl) - 1ull);      // flags above the wave's first lane in the strip
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(fk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fk, 0u));
+                if (ow == (uint32_t)k) slot = s0 + below + (uint32_t)((fk >> lane) & 1ull);
+            }
+        }
+        uint32_t tl = 0;
+        if (have) tl = S.lane_of[ow][slot & 63u] & 63u;
         float4 rec[6];
         // fragments of one strip almost always belong to one mesh; if not, the meshes take turns (every turn shades through a
         // wave-uniform descriptor: scalar loads, one instantiation of the shader)
@@ -392,7 +455,18 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
                 const int x = (int)(org & 0xFFFu) + (int)(bit & 7u), y = (int)(org >> 12) + (int)(bit >> 3);
                 // (readfirstlane, not m_now: inside this branch the optimiser knows my_mesh == m_now and substitutes the per-lane
                 //  value — the descriptor loads then become vector loads through a per-lane pointer, the texel reads 64-bit addresses)
-                shade_from_tri<ConstMeshPtr, TriShadeS, true>(sc.tri, tt, x, y, kConstMesh(sc.meshes + __builtin_amdgcn_readfirstlane(my_mesh)), ts, rec);
+#ifdef M2S_FUSED3_UV_GLOBAL
+                const float2* const uvl = nullptr;
+#else
+                const float2* const uvl = &S.uv[ow][tl * 3];
+#endif
+#ifdef M2S_FUSED3_ABL_POS
+                const float* const posl = reinterpret_cast<const float*>(&S.tri[ow][tl * 4]);
+#else
+                const float* const posl = nullptr;
+#endif
+                shade_from_tri<ConstMeshPtr, TriShadeS, true, kF3StreamAttr>(sc.tri, tt, x, y, kConstMesh(sc.meshes + __builtin_amdgcn_readfirstlane(my_mesh)),
+                                                                              ts, rec, nullptr, uvl, posl);
             }
             todo &= ~__ballot(mine);
         }
