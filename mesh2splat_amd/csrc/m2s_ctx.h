@@ -81,6 +81,7 @@ struct m2s_ctx {
     bool warm_mismatch_seen = false;        // a launch in runs disagreed with that count once (run_pass): not retried again
     uint32_t hint_R = 0;                    // m2s_set_resolution_hint: the R the next upload prepares for (0: the last R converted at, else 1024)
     uint32_t warm_R = 0;                    // the R the resident scene was prepared for
+    int warm_spec_form = 0;                             // ... ordered for the first resident set of this single-pass form's kernel
     uint32_t warm_spec_unit = 0, warm_spec_shift = 0;   // run table + dispatch order enqueued with the upload's count, for units of this many triangles (0: none)
     unsigned long long* d_bands = nullptr;  // kBandSlots run tables of run_table_words words each (RunInfo, m2s_device.h)
     size_t run_table_words = 0;

@@ -109,7 +109,24 @@ void launch_unit_bases(const uint32_t* cnt, const uint32_t* partials, uint32_t n
 // fragments per unit), so the GPU drains for a whole heavy workgroup's lifetime.  With the light runs last the drain is short.  Runs
 // are independent (the look-back chain restarts at every run, whose base comes from the table), so any order is correct.
 // n_slots = runs rounded up to whole groups of eight (slots past the last run map to themselves: their workgroups exit at once).
-void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots, hipStream_t st);
+// first_set (0: none, the shipping build; m2s_pass.cpp first_resident_slots) = the slots whose workgroups all start with the launch: the
+// order is descending behind them; among them every XCD gets heavy and light runs side by side, so that its co-resident workgroups do not
+// all end together (k_run_order).
+void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots,
+                      uint32_t first_set, hipStream_t st);
+// workgroups of `kernel` (of `threads` threads, no dynamic LDS) the current device holds at once: occupancy per CU x CUs; 0 if unknown
+inline uint32_t resident_workgroups(const void* kernel, int threads) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+        (void)hipGetLastError();
+        return 0u;
+    }
+    return (uint32_t)per_cu * (uint32_t)cus;
+}
+uint32_t fused2_resident_workgroups();
+uint32_t fused3_resident_workgroups();
+uint32_t sparse_resident_workgroups();
 inline uint32_t run_order_slots(uint32_t n_units, uint32_t shift) { return ((n_units + (8u << shift) - 1u) / (8u << shift)) * 8u; }
 // multi-pass pipeline (m2s_emit2.hip): count + scan + offsets in one kernel, wave-granular emit
 uint32_t emit2_slices(uint64_t limit);       // entries of start[] needed for `limit` output records

@@ -539,6 +539,7 @@ extern "C" int m2s_debug_read_timing2(unsigned long long* dst, size_t n) {
 #endif
 
 // (m2s_device.h: preload_*) makes the runtime load this file's code object now instead of inside the first launch
+uint32_t fused2_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused2), kTeamThreads); }
 hipError_t preload_fused2() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused2)); }
 
 }  // namespace m2s

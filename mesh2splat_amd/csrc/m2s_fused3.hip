@@ -39,7 +39,16 @@
 // kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup).
 // Measurement-only switches (compile time; the A/B tables of DESIGN 6): M2S_FUSED3_UV_GLOBAL — the strips load the B planes as they
 // did before the coordinates moved to LDS; M2S_FUSED3_ABL_POS — the strips take the positions from stale LDS words instead of the
-// A planes (WRONG records: what the second read of those planes costs); M2S_FUSED3_NT_ATTR — normals / tangents as non-temporal loads.
+// A planes (WRONG records: what the second read of those planes costs); M2S_FUSED3_NT_ATTR — normals / tangents as non-temporal loads;
+// M2S_FUSED3_TRI_PRIO — 0: every wave at one priority throughout, 2: phase classes (below), with M2S_FUSED3_PRIO_FLOOR.
+//
+// Priority (round 7).  A wave runs its triangle phase — ~950 VALU instructions and no wait after its loads — at priority 1 and drops to 0 when
+// its counts are published: the waits and the strips run at 0.  From the second generation of workgroups on, a wave in the triangle phase
+// shares its SIMD with three waves in strips, which issue a few instructions between long waits; ahead of them it leaves the phase ~1 us
+// sooner (mean 6.8 -> 5.7 us on config 3) and its workgroup's texel requests start that much earlier.  Priority only orders issue — nothing a
+// workgroup writes, or where, depends on it.  Measured and NOT shipped: a priority per "phase class" of the workgroup
+// (f3_class: which of the four dispatch slots of its CU it took), to make the waves of one SIMD leave the phase one after another — the
+// first generation's triangle phase is not issue-bound (8 us at any priority), so the classes order nothing.
 #include "m2s_fused_common.h"
 
 #pragma clang fp contract(off)
@@ -93,6 +102,17 @@ constexpr bool kF3StreamAttr = true;
 constexpr bool kF3StreamAttr = false;
 #endif
 constexpr uint32_t kF3Irregular = 1u << 8;
+#ifndef M2S_FUSED3_TRI_PRIO
+#define M2S_FUSED3_TRI_PRIO 1              // 1: the triangle phase at priority 1; 0: no priorities; 2: a priority per phase class (A/B)
+#endif
+#ifndef M2S_FUSED3_PRIO_FLOOR
+#define M2S_FUSED3_PRIO_FLOOR 0            // phase classes: lowest priority of a triangle phase (classes at or below it share it)
+#endif
+// An XCD hands its workgroups (blockIdx.x >> 3 = 0, 1, 2, ...) to its 32 CUs in turn, so the workgroups that share a CU are 32 apart:
+// the class is the index of that group of 32 — on a launch in runs of 32 units (config 3) the dispatch slot of the run.  (Timeline build:
+// all 256 CUs of config 3's first generation hold four distinct classes.)
+constexpr uint32_t kF3ClassShift = 5;
+__device__ __forceinline__ uint32_t f3_class(uint32_t round) { return (round >> kF3ClassShift) & 3u; }
 
 __device__ __forceinline__ uint32_t l3_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void l3_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -143,6 +163,8 @@ __device__ __forceinline__ bool f3_get_base(F3Ctl& C, unsigned long long* chain,
 // measurement build only (tools/timeline_probe.py): 100 MHz timestamps per wave — start, counts known, entries expanded, first strip,
 // last strip done, end — and the strips the wave shaded
 __device__ unsigned long long g_tl_f3[16384 * 4 * 8];
+constexpr int kTlHwId = 4 | (31 << 11);      // s_getreg operand: HW_REG_HW_ID, all 32 bits (wave 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13)
+constexpr int kTlXccId = 20 | (3 << 11);     // HW_REG_XCC_ID, bits 3:0
 #define TLF(k) do { __builtin_amdgcn_sched_barrier(0); if (lane == 0 && blockIdx.x < 16384u) g_tl_f3[((size_t)blockIdx.x * 4 + wave) * 8 + (k)] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define TLFV(k, v) do { if (lane == 0 && blockIdx.x < 16384u) g_tl_f3[((size_t)blockIdx.x * 4 + wave) * 8 + (k)] = (v); } while (0)
 #else
@@ -175,6 +197,16 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
     }
     const bool band_first = in_runs && (round & rmask) == 0u;     // first unit of its run: its base is the run's, known
     if (lb * (uint32_t)kL3Team >= n_batches) return;
+#if M2S_FUSED3_TRI_PRIO == 1
+    __builtin_amdgcn_s_setprio(1);         // the triangle phase ahead of other waves' strips (file header)
+#elif M2S_FUSED3_TRI_PRIO == 2
+    switch (f3_class(round)) {             // (the priority is an immediate operand)
+        case 0: __builtin_amdgcn_s_setprio(3); break;
+        case 1: __builtin_amdgcn_s_setprio(2); break;
+        case 2: __builtin_amdgcn_s_setprio(M2S_FUSED3_PRIO_FLOOR > 1 ? M2S_FUSED3_PRIO_FLOOR : 1); break;
+        default: __builtin_amdgcn_s_setprio(M2S_FUSED3_PRIO_FLOOR); break;
+    }
+#endif
     TLF(0);
     // LDS is not zero on entry: one barrier at the very start makes the flags trustworthy (see k_fused2)
     if (lane == 0) { C.counted[wave] = 0; C.expanded[wave] = 0; }
@@ -300,6 +332,9 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         // the "deferred triangles" flag travels WITH the counts (see k_fused2: a strip of another wave's entries must see it)
         if (anybig) __hip_atomic_fetch_or(&C.flags, kF3Irregular, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+#if M2S_FUSED3_TRI_PRIO
+    __builtin_amdgcn_s_setprio(0);         // the phase is over: the waits and the strips run at the common priority
+#endif
     l3_store(&C.counted[wave], 1u);
     TLF(1);
 
@@ -513,7 +548,8 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         }
     }
     TLF(4);
-    TLFV(6, tl_strips);
+    // (the upper halves of words 6 and 7: where the wave ran — XCC, then the hardware id register with its SE / CU / SIMD fields — and its class)
+    TLFV(6, tl_strips | ((unsigned long long)(__builtin_amdgcn_s_getreg(kTlXccId) | (f3_class(round) << 8)) << 32));
     // ======================= epilogue: the workgroup's inclusive prefix / the counter =======================
     // (by the wave of the last batch; the base is resolved here if no strip needed it, e.g. a workgroup without fragments)
     const uint32_t err = l3_load(&C.flags) & 0xFFu;
@@ -530,7 +566,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
     // status[1] != 0 is what the host acts on; 2 = "a workgroup's entries do not fit", 1 = a bounded wait gave up
     if (err && lane == 0) __hip_atomic_store(&status[1], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     TLF(5);
-    TLFV(7, (unsigned long long)lb);
+    TLFV(7, (unsigned long long)lb | ((unsigned long long)__builtin_amdgcn_s_getreg(kTlHwId) << 32));
 }
 
 void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,
@@ -561,6 +597,7 @@ extern "C" int m2s_debug_timeline_f3_clear() {
 }
 namespace m2s {
 #endif
+uint32_t fused3_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused3), kL3Threads); }
 hipError_t preload_fused3() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused3)); }
 
 }  // namespace m2s

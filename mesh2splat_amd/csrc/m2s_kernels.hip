@@ -259,10 +259,27 @@ void launch_unit_bases(const uint32_t* cnt, const uint32_t* partials, uint32_t n
 }
 
 // ============================================================================================
-// K_run_order: rank sort of the runs by fragment count, descending (ties: lower run first).  n_runs <= a few thousand.
+// K_run_order: rank sort of the runs by fragment count, descending (ties: lower run first), then the slot of every rank.  n_runs <= a few
+// thousand.  The slots past the FIRST RESIDENT SET (the `first_set` slots whose workgroups all start when the launch does) hold the ranking
+// in descending order: the light runs last, a short drain.  Inside the first set the four (first_set / 8) slots of one XCD would otherwise
+// hold runs of nearly the same weight, whose workgroups live equally long and hand their phase to the next generation (m2s_fused3.hip,
+// phase classes); there the earlier half of an XCD's slots takes the heaviest runs and the later half the lightest ones, the lightest in
+// the last slot.  first_set = 0 (the shipping build: measured, config 3 is slower with it — DESIGN 6.3): descending throughout.
 // ============================================================================================
+__device__ __forceinline__ uint32_t run_order_slot_of_rank(uint32_t rank, uint32_t n_runs, uint32_t first_set) {
+    const uint32_t groups = (first_set < n_runs ? first_set : n_runs) / 8u;   // slots per XCD in the first set
+    if (groups < 2u) return rank;
+    const uint32_t heavy = ((groups + 1u) / 2u) * 8u, light = (groups / 2u) * 8u;
+    if (rank < heavy) return rank;
+    if (rank >= n_runs - light) {
+        const uint32_t j = n_runs - 1u - rank;                         // 0: the lightest run
+        return (groups - 1u - (j >> 3)) * 8u + (j & 7u);
+    }
+    return rank + light;                                                // (first set = heavy + light slots)
+}
 __global__ void __launch_bounds__(kBlock) k_run_order(const unsigned long long* __restrict__ run_base, uint32_t n_runs,
-                                                      const unsigned long long* __restrict__ total, uint32_t* __restrict__ order, uint32_t n_slots) {
+                                                      const unsigned long long* __restrict__ total, uint32_t* __restrict__ order, uint32_t n_slots,
+                                                      uint32_t first_set) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n_slots) return;
     if (i >= n_runs) { order[i] = i; return; }
@@ -274,11 +291,12 @@ __global__ void __launch_bounds__(kBlock) k_run_order(const unsigned long long* 
         const unsigned long long cj = cost(j);
         rank += (cj > mine || (cj == mine && j < i)) ? 1u : 0u;
     }
-    order[rank] = i;
+    order[run_order_slot_of_rank(rank, n_runs, first_set)] = i;
 }
-void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots, hipStream_t st) {
+void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots,
+                      uint32_t first_set, hipStream_t st) {
     if (!n_slots) return;
-    hipLaunchKernelGGL(k_run_order, dim3((n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, run_base, n_runs, total, order, n_slots);
+    hipLaunchKernelGGL(k_run_order, dim3((n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, run_base, n_runs, total, order, n_slots, first_set);
 }
 
 // ============================================================================================

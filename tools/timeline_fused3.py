@@ -1,5 +1,7 @@
 """Per-wave timeline of k_fused3 (the lean team kernel) on a -DM2S_TIMELINE build of the library: when workgroups start, how long the
-triangle phase, the wait for the base / the other waves' entries and the strips take, how many waves are alive over time.
+triangle phase, the wait for the base / the other waves' entries and the strips take, how many waves are alive over time; and how far
+the workgroups age in lockstep: the spread of "waves in strips" over the plateau, the triangle phase per phase class, the classes that
+met on one CU (m2s_fused3.hip, phase classes; the hardware ids are recorded by builds from round 7 on).
     M2S_LIB_PATH=mesh2splat_amd/_build_tl/libm2s_hip.so python tools/timeline_fused3.py [c3|c2] [out.json]"""
 import ctypes as C
 import json
@@ -38,7 +40,10 @@ ok = t[:, 0, 0] > 0
 T0 = t[ok][:, :, 0].min()
 ts = (t[:, :, :6] - T0) * 10     # ns
 ts[~ok] = 0
-strips = t[:, :, 6]
+strips = t[:, :, 6] & 0xFFFFFFFF
+xcc, cls_rec, hwid = (t[:, 0, 6] >> 32) & 0xF, (t[:, 0, 6] >> 40) & 0x3, (t[:, 0, 7] >> 32) & 0xFFFFFFFF
+have_hw = bool(hwid[ok].any())
+cls = cls_rec if have_hw else (np.arange(nwg) >> 8) & 3      # (what f3_class computes from blockIdx.x)
 print(json.dumps({"workload": name, "R": R, "gaussians": int(tot), "pipeline": str(c.last_pipeline), "kernel_ms": kms, "workgroups": nwg, "with_work": int(ok.sum())}))
 st, en = ts[ok][:, :, 0], ts[ok][:, :, 5]
 print(f"span {en.max()} ns; workgroup starts p50 {np.percentile(st, 50):.0f} p90 {np.percentile(st, 90):.0f} max {st.max()}")
@@ -56,5 +61,36 @@ print("every 5 us: waves alive", alive)
 print("            in the triangle phase", intri)
 print("            waiting (counts, base, expansion)", inwait)
 print("            in strips", instrips)
+# --- lockstep figures -----------------------------------------------------------------------------------------------------------
+# plateau: from the first moment (nearly) all wave slots are taken to the start of the last workgroup (after it the launch only drains)
+fine = np.arange(0, en.max() + 1, 1000)
+alive_f = np.array([((st <= g) & (en > g)).sum() for g in fine])
+strips_f = np.array([((ts[ok][:, :, 3] <= g) & (ts[ok][:, :, 4] > g)).sum() for g in fine])
+full = fine[np.argmax(alive_f >= 0.9 * alive_f.max())]
+decay = st.max()
+pl = strips_f[(fine >= full) & (fine <= decay)]
+if len(pl):
+    print(f"plateau {full / 1000:.0f} .. {decay / 1000:.0f} us (1 us samples): waves in strips min {pl.min()} max {pl.max()} mean {pl.mean():.0f} "
+          f"coefficient of variation {pl.std() / pl.mean():.3f}")
+# first generation: the workgroups that started before any workgroup had finished
+gen1 = ok & (ts[:, :, 0].min(axis=1) < en.min())
+tri_ns = (ts[:, :, 1] - ts[:, :, 0])
+print("triangle phase, mean ns per class:", {int(k): int(tri_ns[ok & (cls == k)].mean()) for k in range(4) if (ok & (cls == k)).any()},
+      "| first generation only:", {int(k): int(tri_ns[gen1 & (cls == k)].mean()) for k in range(4) if (gen1 & (cls == k)).any()})
+print("end of the triangle phase in the first generation, mean ns after the launch's start, per class:",
+      {int(k): int(ts[:, :, 1][gen1 & (cls == k)].mean()) for k in range(4) if (gen1 & (cls == k)).any()})
+if have_hw:
+    cu = (xcc << 8) | ((hwid >> 8) & 0xFF)          # XCC | SE, SH, CU fields of the hardware id
+    per_cu = {}
+    for w in np.nonzero(gen1)[0]:
+        per_cu.setdefault(int(cu[w]), []).append(int(cls[w]))
+    held = np.bincount([len(v) for v in per_cu.values()])
+    print(f"first generation: {int(gen1.sum())} workgroups on {len(per_cu)} CUs; workgroups per CU -> CUs {dict(enumerate(held.tolist()))}; "
+          f"CUs that held four distinct classes {sum(len(set(v)) == 4 for v in per_cu.values())}, three {sum(len(set(v)) == 3 for v in per_cu.values())}")
+    simd = (hwid >> 4) & 3
+    print("SIMD of a workgroup's first wave, first generation:", np.bincount(simd[gen1], minlength=4).tolist())
+else:
+    print("first generation: hardware ids not recorded by this build")
 if out:
-    json.dump({"t": ts.tolist(), "strips": strips.tolist(), "lb": t[:, :, 7].tolist()}, open(out, "w"))
+    json.dump({"t": ts.tolist(), "strips": strips.tolist(), "lb": (t[:, :, 7] & 0xFFFFFFFF).tolist(), "class": cls.tolist(),
+               "xcc": xcc.tolist(), "hw_id": hwid.tolist()}, open(out, "w"))
