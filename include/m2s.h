@@ -576,6 +576,76 @@ m2s_status m2s_last_mesh_depth_counts(const m2s_ctx* ctx, uint64_t out[5]);
  * in-place path.  The image does not depend on it. */
 m2s_status m2s_debug_set_mesh_depth_inplace(m2s_ctx* ctx, int32_t max_box);
 
+/* ---- mesh render pass == MeshRenderPass::execute (MeshRenderPass.cpp:8-73, meshRender{VS,PS}.glsl) ----------------------------- */
+/* Draws EVERY mesh of the uploaded scene (no alpha filter) with the camera of the frame into a second five-target G-buffer (the
+ * targets of renderer.cpp:473-539, layouts and orientation of m2s_device_gbuffer): what m2s_relight_split shows left of the divider.
+ * GL semantics restated for a compute pass in two stages; these choices are the pin (tests/meshrender_ref.py restates them).
+ * Stage 1, visibility — decision arithmetic, exact:
+ *  - Vertex transform, finite test, five-plane clipper, fan, division, z_w, snap, guard band and the depth of a fragment are exactly
+ *    those of m2s_mesh_depth.  In particular gl_Position = ((P V) M) (p, 1): the reference's mesh vertex shader multiplies step by
+ *    step (P (V (M p))) and differs from that in last bits; sharing the depth pass's transform keeps the two passes' depths identical.
+ *  - GL_CULL_FACE is on (front = CCW, cull back): a piece is drawn only if the int64 doubled area of its snapped vertices, taken in
+ *    the STORED vertex order — (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0), before the canonical (Y, X) reorder, window with y up — is
+ *    > 0.  Zero area is rejected as before.  The test comes after the z_w, guard-band and empty-box rejections.
+ *  - GL_LESS in draw order: per pixel the winner is the minimum of the 64-bit key (bits of z) << 32 | global triangle index, z in
+ *    [0, 1] after the clamp; fragments with z >= 1.0 or NaN never compete; an empty pixel holds (bits of 1.0f) << 32 | 0xFFFFFFFF.
+ *    The lowest index wins a depth tie: the triangle GL drew first.  The index is global under m2s_set_triangle_range, so the
+ *    visibility images of shards combine by 64-bit min.
+ * Stage 2, shading, per pixel — an empty pixel gets zeros in all five planes (the pass's clear).  Otherwise, for the winner:
+ *  - Barycentrics of the ORIGINAL triangle (clipped or not) in homogeneous form, in fp64 from the fp32 clip coordinates
+ *    c_i = (x_i, y_i, w_i): with (j, k) = (i + 1, i + 2) mod 3, A_i = y_j w_k - w_j y_k, B_i = x_j w_k - w_j x_k, C_i = x_j y_k - y_j x_k,
+ *    n = ((2 x + 1) / W - 1, (2 y + 1) / H - 1) at the centre of pixel (x, y): e_i = (n.x A_i - n.y B_i) + C_i (= det[n; c_j; c_k]);
+ *    lambda_i = e_i / ((e_0 + e_1) + e_2), rounded to fp32.  Coverage was decided on SNAPPED vertices, so a covered centre may get a
+ *    slightly negative lambda: accepted (an extrapolation by less than 1/256 px).
+ *  - Varyings as the vertex shader makes them, per corner, fp32: v_worldPos = (M (p, 1)).xyz; v_normal = normalize(N n);
+ *    v_tangent = (normalize(N t.xyz), t.w); v_uv; v_viewDepth = -(V (M (p, 1))).z, step by step; N = mat3(transpose(inverse(M))) taken
+ *    once on the host in float64 from the fp32 matrix and rounded to fp32.  Interpolation: (lambda_0 a_0 + lambda_1 a_1) + lambda_2 a_2.
+ *  - Texture LOD: the implicit derivatives a helper invocation would see: dUV/dx = uv(x + 1, y) - uv(x, y), dUV/dy = uv(x, y + 1) -
+ *    uv(x, y), uv(.) being the winner's own interpolation (fp64 barycentrics, as above) at the neighbouring centre; then the
+ *    conversion's sampler unchanged per map (0.5 log2(max(|dx|^2, |dy|^2)) in texels, levels 0..4, REPEAT, trilinear, fp32 weights).
+ *    A non-finite gradient selects the last level.
+ *  - The fragment shader as written: albedo = baseColorFactor (x texture); N = normalize(v_normal), with a normal map
+ *    normalize(TBN normalize(2 s - 1)), T = normalize(v_tangent.xyz), B = normalize(cross(N, T)) * v_tangent.w; encodeNormal = 0.5 N +
+ *    0.5; metallic-roughness (0.1, 0.5), or the map's (b, g); computeExponentialDepth(v_viewDepth, near_far) =
+ *    clamp(exp(-20 clamp((d - near) / (far - near)))).  Render modes 0 / 6 / 5 (and any not named here) albedo, 1 depth, 2 encoded
+ *    normal, 4 the constant (0.01, 0.005, 0), 3 the per-triangle hash (fract(sin(id 311.7) 43758.5453), fract(sin(id 269.5 + 1.3) ..),
+ *    fract(sin(id 183.3 + 2.7) ..)) with id = gl_PrimitiveID = the triangle's index within its mesh; the argument is an fp32 product
+ *    (and sum), its sine is taken in fp64 and rounded to fp32 (the factor 43758.5453 amplifies any error of it), the rest is fp32.
+ *  - Outputs: 0 position (v_worldPos, 1), 1 normal (encoded, 1), 3 depth (d, d, d, 1): half4, RNE; 2 albedo (rgb of the mode's colour),
+ *    4 metallic-roughness (metallic, roughness, 0): uchar4 = rint(clamp(c, 0, 1) * 255), NaN -> 0, alpha 255.
+ *  - Arithmetic: the normalisations, exp and log2 are value arithmetic with the device's fast forms; everything else is fp32
+ *    operation by operation without contraction.
+ * Counts (out_counts may be NULL): [0]..[4] as m2s_mesh_depth (over every mesh), [5] triangles culled as back-facing (a piece reached
+ * the area test with a negative area and no piece was drawn).
+ * Synchronous.  Errors: M2S_ERR_INVALID for a resolution outside 1..8192, a render mode outside 0..6 or reserved != 0; M2S_ERR_STATE
+ * without a scene; M2S_ERR_CAPACITY beyond 2^31-1 pairs.  An empty scene gives five planes of zeros. */
+typedef struct m2s_mesh_render_params {
+    float world_to_view[16], view_to_clip[16], model_to_world[16];  /* column-major, as m2s_prepass_params */
+    int32_t resolution[2];      /* rendererResolution, 1..8192 each */
+    float near_far[2];          /* u_nearFar */
+    int32_t render_mode;        /* u_renderMode 0..6 */
+    uint32_t reserved;          /* 0 */
+} m2s_mesh_render_params;
+m2s_status m2s_mesh_render(m2s_ctx* ctx, const m2s_mesh_render_params* params, uint64_t out_counts[6]);
+/* Attachment 0..4 of the last m2s_mesh_render (layouts of m2s_device_gbuffer; context-owned, grow-only).  NULL before any. */
+const void* m2s_device_mesh_gbuffer(const m2s_ctx* ctx, uint32_t attachment);
+m2s_status m2s_download_mesh_gbuffer(m2s_ctx* ctx, uint32_t attachment, void* dst, uint64_t capacity_bytes);
+/* The visibility image of the last m2s_mesh_render: uint64[H][W], row 0 = bottom (for tests and for merging shards). */
+m2s_status m2s_download_mesh_visibility(m2s_ctx* ctx, uint64_t* dst, uint64_t capacity_pixels);
+/* Duration (ms) of the last profiled m2s_mesh_render (sum of its stages), and the stages: [0] clear + visibility setup + triangles
+ * covered in place, [1] clipper + binning, [2] tile raster, [3] shading.  [0] + [1] + [2] is the work of m2s_mesh_depth with an 8-byte
+ * payload.  m2s_debug_set_mesh_depth_inplace moves this pass's in-place threshold too. */
+float m2s_last_mesh_render_ms(const m2s_ctx* ctx);
+m2s_status m2s_last_mesh_render_stage_ms(const m2s_ctx* ctx, float out_ms[4]);
+m2s_status m2s_last_mesh_render_counts(const m2s_ctx* ctx, uint64_t out[6]);
+
+/* == GaussianRelightingPass::execute with split screen (GaussianRelightingPass.cpp:90-135): m2s_relight, except that pixels with
+ * x < splitPixelX = (int)(split_position * W) (an fp32 product, truncated) are lit from the mesh G-buffer of the last m2s_mesh_render
+ * instead of the splat G-buffer — same shader, cube and light — and that the columns [dividerX, dividerX + 2) n [0, W),
+ * dividerX = max(0, splitPixelX - 1), are (255, 255, 255, 255).  Errors as m2s_relight, and M2S_ERR_INVALID for a split_position
+ * outside [0, 1], M2S_ERR_STATE without a mesh G-buffer of the G-buffer's W x H. */
+m2s_status m2s_relight_split(m2s_ctx* ctx, const m2s_light_params* light, float split_position);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

@@ -42,6 +42,8 @@ EXPORTS = (
     "m2s_download_frame", "m2s_download_shadow_counts", "m2s_last_relight_ms",
     "m2s_mesh_depth", "m2s_device_mesh_depth", "m2s_download_mesh_depth", "m2s_last_mesh_depth_ms", "m2s_last_mesh_depth_stage_ms",
     "m2s_last_mesh_depth_counts", "m2s_debug_set_mesh_depth_inplace",
+    "m2s_mesh_render", "m2s_device_mesh_gbuffer", "m2s_download_mesh_gbuffer", "m2s_download_mesh_visibility", "m2s_last_mesh_render_ms",
+    "m2s_last_mesh_render_stage_ms", "m2s_last_mesh_render_counts", "m2s_relight_split",
 )
 
 
@@ -216,6 +218,14 @@ def load():
         "m2s_last_mesh_depth_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_last_mesh_depth_counts": (C.c_int, [vp, C.POINTER(u64)]),
         "m2s_debug_set_mesh_depth_inplace": (C.c_int, [vp, C.c_int32]),
+        "m2s_mesh_render": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_device_mesh_gbuffer": (vp, [vp, C.c_uint32]),
+        "m2s_download_mesh_gbuffer": (C.c_int, [vp, C.c_uint32, vp, u64]),
+        "m2s_download_mesh_visibility": (C.c_int, [vp, vp, u64]),
+        "m2s_last_mesh_render_ms": (C.c_float, [vp]),
+        "m2s_last_mesh_render_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_last_mesh_render_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_relight_split": (C.c_int, [vp, vp, C.c_float]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -456,8 +456,10 @@ class Converter:
         from . import light as _li
         lc = _li.to_c(light_params)
         self._check(self._L.m2s_relight(self._h, C.byref(lc)))
-        if not download:
-            return None
+        return self._download_relit(lc) if download else None
+
+    def _download_relit(self, lc):
+        """The frame of the last relight / relight_split (and its shadow counts, where `lc` asked for them)."""
         W, H = int(lc.resolution[0]), int(lc.resolution[1])
         frame = np.empty((H, W, 4), np.uint8)
         self._check(self._L.m2s_download_frame(self._h, frame.ctypes.data, frame.nbytes))
@@ -470,6 +472,60 @@ class Converter:
     @property
     def device_frame(self) -> int:
         return int(self._L.m2s_device_frame(self._h) or 0)
+
+    def relight_split(self, light_params, split_position: float, download: bool = True):
+        """GaussianRelightingPass with the split screen (m2s_relight_split): pixels left of int(split_position * W) are lit from the mesh
+        G-buffer of the last mesh_render(), the others from the splat G-buffer; two white divider columns.  Returns what relight() does."""
+        from . import light as _li
+        lc = _li.to_c(light_params)
+        self._check(self._L.m2s_relight_split(self._h, C.byref(lc), float(split_position)))
+        return self._download_relit(lc) if download else None
+
+    def mesh_render(self, params, download: bool = True):
+        """MeshRenderPass (m2s_mesh_render): every mesh of the uploaded scene drawn through the camera of `params` (a
+        mesh2splat_amd.meshrender.MeshRenderParams, or a PrepassParams whose camera, model matrix, resolution, planes and render mode
+        are taken) into the mesh G-buffer.  -> (five planes as splat() returns them, counts dict); download=False: counts alone (the
+        planes stay on the device: device_mesh_gbuffer, where relight_split() reads them)."""
+        from . import meshrender as _mr
+        mc = _mr.to_c(params)
+        v = (C.c_uint64 * 6)()
+        self._check(self._L.m2s_mesh_render(self._h, C.byref(mc), v))
+        self._last_mr_wh = (int(mc.resolution[0]), int(mc.resolution[1]))
+        counts = {k: int(v[i]) for i, k in enumerate(_mr.COUNT_NAMES)}
+        if not download:
+            return counts
+        return self.download_mesh_gbuffer(), counts
+
+    def download_mesh_gbuffer(self):
+        """The five planes of the last mesh_render(): (H, W, 4) float16 for attachments 0, 1, 3, uint8 for 2, 4; row 0 = bottom."""
+        from . import splat as _sp
+        W, H = self._last_mr_wh
+        planes = []
+        for k, (_, dt) in enumerate(_sp.ATTACHMENTS):
+            a = np.empty((max(H, 1), max(W, 1), 4), dt)             # (before any: the library answers M2S_ERR_STATE)
+            self._check(self._L.m2s_download_mesh_gbuffer(self._h, k, a.ctypes.data, a.nbytes))
+            planes.append(a)
+        return planes
+
+    def download_mesh_visibility(self) -> np.ndarray:
+        """(H, W) uint64 of the last mesh_render(): (bits of z) << 32 | global triangle index; meshrender.EMPTY where nothing was drawn."""
+        W, H = self._last_mr_wh
+        vis = np.empty((max(H, 1), max(W, 1)), np.uint64)
+        self._check(self._L.m2s_download_mesh_visibility(self._h, vis.ctypes.data, vis.size))
+        return vis
+
+    def device_mesh_gbuffer(self, attachment: int) -> int:
+        return int(self._L.m2s_device_mesh_gbuffer(self._h, int(attachment)) or 0)
+
+    @property
+    def last_mesh_render_ms(self) -> float:
+        return float(self._L.m2s_last_mesh_render_ms(self._h))
+
+    def last_mesh_render_stage_ms(self) -> dict:
+        from . import meshrender as _mr
+        ms = (C.c_float * 4)()
+        self._check(self._L.m2s_last_mesh_render_stage_ms(self._h, ms))
+        return {k: float(ms[i]) for i, k in enumerate(_mr.STAGE_NAMES)}
 
     def mesh_depth(self, params, download: bool = True):
         """DepthPrepass (m2s_mesh_depth): the opaque meshes of the uploaded scene drawn depth-only through the camera of `params`
@@ -487,6 +543,7 @@ class Converter:
         return self.download_mesh_depth(), counts
 
     _last_md_wh = (0, 0)
+    _last_mr_wh = (0, 0)                 # resolution of the last mesh_render()
 
     def download_mesh_depth(self) -> np.ndarray:
         W, H = self._last_md_wh
@@ -517,9 +574,12 @@ class Converter:
         W, H = self._last_md_wh
         return dataclasses.replace(prepass_params, perform_mesh_depth_test=True, mesh_depth=_DeviceImage(self.device_mesh_depth, H, W))
 
-    def render_frame(self, prepass_params, light_params, mesh_depth_test: bool = False):
-        """One viewer frame of the context's records (renderer.cpp:129-138 without the mesh render pass): prepass + depth sort + splat +
-        shadow + relight.  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
+    def render_frame(self, prepass_params, light_params, mesh_depth_test: bool = False, split_screen: Optional[float] = None):
+        """One viewer frame of the context's records (renderer.cpp:129-138): prepass + depth sort + splat + shadow + relight.
+        split_screen (None: off, the frame is what it was without the argument; else a position in [0, 1]): the mesh render pass of the
+        uploaded scene runs with the frame's camera and render mode (mesh_render) and the relighting pass composes the reference's
+        split screen (relight_split): mesh left of the divider, splats right — subtracting the frames at positions 1 and 0 gives a
+        fidelity figure for the conversion.  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
         renderer_resolution must equal `prepass_params`'s.  mesh_depth_test: the frame starts with the mesh depth prepass of the uploaded
         scene (mesh_depth) and the Gaussian prepass — then m2s_prepass_sorted — tests against its image on the device, the reference's
         "use the mesh as occluder in depth prepass".  -> what relight() returns."""
@@ -539,6 +599,9 @@ class Converter:
             import torch
             self.splat(SplatParams(res, int(prepass_params.render_mode)), quads=torch.empty((0, 24), dtype=torch.float32, device="cuda"), download=False)
         self.shadow(prepass_params, light_params, download=False)
+        if split_screen is not None:
+            self.mesh_render(prepass_params, download=False)
+            return self.relight_split(light_params, split_screen)
         return self.relight(light_params)
 
     @property
@@ -625,6 +688,9 @@ class RenderContext:
         self.shadowCubemap = None                 # written by GaussianShadowPass::execute: (6, S, S) float32
         self.mesh_depth = None                    # written by DepthPrepass::execute: (H, W) float32 window-space depth, row 0 = bottom
         self.frame = None                         # written by GaussianRelightingPass::execute: (H, W, 4) uint8, row 0 = bottom
+        self.meshGBuffer = None                   # written by MeshRenderPass::execute: five planes, as gBuffer
+        self.splitScreenEnabled = False           # RenderContext::splitScreenEnabled / splitScreenPosition (GaussianRelightingPass)
+        self.splitScreenPosition = 0.5
         self._uploaded_scene = None
 
 
@@ -673,6 +739,16 @@ class DepthPrepass(IRenderPass):
             context.prepassParams.mesh_depth = context.mesh_depth
 
 
+class MeshRenderPass(IRenderPass):
+    """MeshRenderPass::execute (MeshRenderPass.cpp:8-73): every mesh of the uploaded scene drawn with the camera of
+    context.prepassParams (its render mode and planes included) into the mesh G-buffer; the planes end up in context.meshGBuffer."""
+
+    def execute(self, context: RenderContext):
+        if context.converter is None or context.prepassParams is None or context._uploaded_scene is None:
+            raise RuntimeError("needs an uploaded scene (ConversionPass) and context.prepassParams")
+        context.meshGBuffer, _ = context.converter.mesh_render(context.prepassParams)
+
+
 class GaussianSplattingPass(IRenderPass):
     """GaussianSplattingPass::execute (GaussianSplattingPass.cpp:50-95): blends the sorted quads (what RadixSortPass left in the
     context: Converter.sort_prepass / prepass_sorted / upload_quads) into the G-buffer at context.rendererResolution with
@@ -700,13 +776,17 @@ class GaussianShadowPass(IRenderPass):
 
 
 class GaussianRelightingPass(IRenderPass):
-    """GaussianRelightingPass::execute without split screen (GaussianRelightingPass.cpp:136-143): lights the G-buffer of
-    GaussianSplattingPass with the cube of GaussianShadowPass; the RGBA8 frame ends up in context.frame (row 0 = bottom)."""
+    """GaussianRelightingPass::execute (GaussianRelightingPass.cpp:83-143): lights the G-buffer of GaussianSplattingPass with the
+    cube of GaussianShadowPass; the RGBA8 frame ends up in context.frame (row 0 = bottom).  With context.splitScreenEnabled and a mesh
+    G-buffer (MeshRenderPass has run) the left of context.splitScreenPosition is lit from the mesh G-buffer, as in the reference."""
 
     def execute(self, context: RenderContext):
         if context.converter is None or context.lightParams is None:
             raise RuntimeError("needs a G-buffer, a shadow cube and context.lightParams")
-        r = context.converter.relight(context.lightParams)
+        if context.splitScreenEnabled and context.meshGBuffer is not None:
+            r = context.converter.relight_split(context.lightParams, context.splitScreenPosition)
+        else:
+            r = context.converter.relight(context.lightParams)
         context.frame = r[0] if isinstance(r, tuple) else r
 
 

@@ -5,6 +5,7 @@
 //   m2s_splat.cpp    the splat pass (== GaussianSplattingPass::execute) and its G-buffer
 //   m2s_light.cpp    the shadow and relighting passes (== GaussianShadowPass / GaussianRelightingPass::execute)
 //   m2s_meshdepth.cpp  the mesh depth prepass (== DepthPrepass::execute)
+//   m2s_meshrender.cpp the mesh render pass (== MeshRenderPass::execute) and the mesh G-buffer
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -247,6 +248,16 @@ struct m2s_ctx {
     float last_md_ms = 0.0f;
     float last_md_stage_ms[3] = { 0, 0, 0 };     // setup + in-place, clip + binning, tile raster (profiling on)
     uint64_t last_md_counts[5] = {};             // drawn, clipped, non-finite, pairs, texel updates sent
+    // mesh render pass (m2s_meshrender.cpp): the visibility image and the mesh G-buffer; its work buffers are the mesh depth prepass's
+    unsigned long long* d_mr_vis = nullptr;      // uint64[H][W], row 0 = bottom: (bits of z) << 32 | global triangle index
+    uint64_t mr_vis_cap = 0;                     // pixels
+    void* d_mr_gbuf[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // layouts of d_gbuf
+    uint64_t mr_gbuf_cap_px[5] = { 0, 0, 0, 0, 0 };   // pixels each plane has room for
+    int32_t mr_w = 0, mr_h = 0;                  // 0: no mesh G-buffer yet
+    hipEvent_t mr_ev[2] = {};
+    float last_mr_ms = 0.0f;
+    float last_mr_stage_ms[4] = { 0, 0, 0, 0 };  // visibility setup + in-place, clip + binning, tile raster, shading (profiling on)
+    uint64_t last_mr_counts[6] = {};             // drawn, clipped, non-finite, pairs, texel updates sent, culled as back-facing
 
     // measurement
     bool profiling = false;
@@ -283,6 +294,25 @@ hipError_t next_epoch(m2s_ctx* c, uint32_t* out);
 m2s_status ensure_records(m2s_ctx* c, uint64_t want);
 // m2s_upload.cpp
 m2s_status ensure_stage(m2s_ctx* c);
+// A grow-only device buffer of `want` units of `unit` bytes: kept when large enough, else freed and allocated anew (contents lost).
+template <typename T>
+inline m2s_status grow_buffer(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
+    if (cap >= want) return M2S_OK;
+    if (p) { (void)hipFree((void*)p); p = nullptr; }
+    cap = 0;
+    void* q = nullptr;
+    HIPCHK(c, hipMalloc(&q, (size_t)want * unit < 256 ? 256 : (size_t)want * unit));
+    p = static_cast<T*>(q);
+    cap = want;
+    return M2S_OK;
+}
+// m2s_meshdepth.cpp
+// What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
+// tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);
+// c->h_md holds the pass's totals afterwards (m2s_device.h: meshdepth_setup, meshvis_setup).
+m2s_status mesh_raster(m2s_ctx* c, const m2s::MeshDepthK& k, bool vis, void* image, float ms[3]);
+// (P V) M in glm's order, every operation rounded to fp32: the clip transform of both passes
+void mesh_pvm(const float* proj, const float* view, const float* model, float* out);
 // m2s_pass.cpp
 uint32_t unit_of(int form);   // triangles per band unit of a single-pass form
 void launch_single(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t R, unsigned long long* chain, uint64_t limit, float4* d_out,

@@ -282,7 +282,9 @@ hipError_t shadow_clear(float* cube, int S, hipStream_t st);                    
 hipError_t shadow_raster(const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, int S, float* cube, unsigned long long* writes,
                          hipStream_t st);
 // planes: the five G-buffer attachments (3, depth, is not read); counts (or NULL): the 20-tap shadow count per pixel
-hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st);
+// left_planes (or NULL): split screen — pixels with x < split_x are lit from these planes, columns div_x and div_x + 1 are white
+hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st,
+                          const void* const left_planes[5] = nullptr, int split_x = 0, int div_x = 0);
 hipError_t preload_light();
 
 // ---- mesh depth prepass (m2s_meshdepth.hip): DepthPrepass over the uploaded scene's position planes -------------------------------
@@ -298,12 +300,31 @@ hipError_t meshdepth_clear(float* image, int W, int H, hipStream_t st);        /
 // totals (zero before): [0] triangles drawn, [1] clipped, [2] non-finite, [3] (tile, piece) pairs, [4] texel updates sent, [5] deferred
 hipError_t meshdepth_setup(const MeshDepthK& k, const SceneDev& sc, float* image, uint32_t* deferred, unsigned long long* totals, hipStream_t st);
 hipError_t meshdepth_deferred(const MeshDepthK& k, const SceneDev& sc, const uint32_t* deferred, uint32_t nd, float4* rec, uint32_t* cnt,
-                              unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st);
+                              unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st, bool vis = false);
 hipError_t meshdepth_bin(const MeshDepthK& k, const float4* rec, const uint32_t* cnt, const unsigned long long* off, uint32_t nd, uint32_t* keys_in,
                          uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t pairs, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t meshdepth_raster(const MeshDepthK& k, const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, float* image,
                             unsigned long long* totals, hipStream_t st);
 hipError_t preload_meshdepth();
+
+// ---- mesh render pass (m2s_meshdepth.hip: the visibility stage, the k_md_* kernels with a 64-bit payload; m2s_meshrender.hip: shading)
+// visibility image: per pixel (bits of z) << 32 | global triangle index, the minimum over the fragments that pass GL_LESS;
+// cleared to (bits of 1.0f) << 32 | 0xFFFFFFFF.  totals as meshdepth_setup, and [6] triangles culled as back-facing; the binning
+// (meshdepth_deferred with vis = true, meshdepth_bin) is the depth pass's.
+hipError_t meshvis_clear(unsigned long long* image, int W, int H, hipStream_t st);
+hipError_t meshvis_setup(const MeshDepthK& k, const SceneDev& sc, unsigned long long* image, uint32_t* deferred, unsigned long long* totals, hipStream_t st);
+hipError_t meshvis_raster(const MeshDepthK& k, const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, unsigned long long* image,
+                          unsigned long long* totals, hipStream_t st);
+struct MeshRenderK {                           // uniforms of meshRender{VS,PS}.glsl
+    float PVM[16];      // MeshDepthK::PVM: the clip positions are the visibility stage's, bit for bit
+    float M[16], V[16]; // u_modelToWorld, u_worldToView
+    float N[9];         // mat3(transpose(inverse(M))), [col * 3 + row]: float64 on the host, rounded
+    float near_far[2];
+    int32_t W, H, mode;
+};
+// one lane per pixel of the visibility image -> the five planes (layouts of the splat G-buffer); an empty pixel gets zeros
+hipError_t meshrender_shade(const MeshRenderK& k, const SceneDev& sc, const unsigned long long* vis, void* const planes[5], hipStream_t st);
+hipError_t preload_meshrender();
 
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);

@@ -334,15 +334,17 @@ m2s_status m2s_upload_gbuffer(m2s_ctx* c, const void* const planes[5], int32_t W
     return M2S_OK;
 }
 
-// GaussianRelightingPass::execute, the branch without split screen: one full-screen draw of gaussianSplattingDeferredPS.glsl.
-m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) {
+// GaussianRelightingPass::execute: one full-screen draw of gaussianSplattingDeferredPS.glsl; split: the branch with the split screen.
+static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, float split_position) {
     if (!c || !lp) return M2S_ERR_INVALID;
+    if (split && !(split_position >= 0.0f && split_position <= 1.0f)) return fail(c, M2S_ERR_INVALID, "split position outside 0..1");
     int S = 0;
     if (m2s_status s = check_light(c, lp, &S)) return s;
     if (!c->gbuf_w) return fail(c, M2S_ERR_INVALID, "no G-buffer exists (run m2s_splat or m2s_upload_gbuffer)");
     if (!c->shadow_S) return fail(c, M2S_ERR_INVALID, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
     if (lp->resolution[0] != c->gbuf_w || lp->resolution[1] != c->gbuf_h) return fail(c, M2S_ERR_INVALID, "resolution is not the G-buffer's");
     if (lp->shadow_resolution && (int32_t)lp->shadow_resolution != c->shadow_S) return fail(c, M2S_ERR_INVALID, "shadow resolution is not the cube's");
+    if (split && (c->mr_w != c->gbuf_w || c->mr_h != c->gbuf_h)) return fail(c, M2S_ERR_STATE, "no mesh G-buffer of the G-buffer's resolution exists (run m2s_mesh_render)");
     HIPCHK(c, hipSetDevice(c->device));
     if (m2s_status s = ensure_light_common(c)) return s;
     const uint64_t px = (uint64_t)c->gbuf_w * (uint64_t)c->gbuf_h;
@@ -364,7 +366,10 @@ m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) {
     k.W = c->gbuf_w; k.H = c->gbuf_h; k.S = c->shadow_S;
     const bool counts = lp->want_shadow_counts != 0 && lp->render_mode == 6;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
-    HIPCHK(c, launch_relight(k, c->d_gbuf, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts : nullptr, c->stream));
+    const int split_x = split ? (int)(split_position * (float)c->gbuf_w) : 0;      // static_cast<int>(splitScreenPosition * w)
+    const int div_x = std::max(0, split_x - 1);                                      // dividerWidth / 2 == 1
+    HIPCHK(c, launch_relight(k, c->d_gbuf, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts : nullptr, c->stream,
+                             split ? c->d_mr_gbuf : nullptr, split_x, div_x));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
@@ -373,6 +378,9 @@ m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) {
     c->frame_has_counts = counts;
     return M2S_OK;
 }
+
+m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) { return relight(c, lp, false, 0.0f); }
+m2s_status m2s_relight_split(m2s_ctx* c, const m2s_light_params* lp, float split_position) { return relight(c, lp, true, split_position); }
 
 const void* m2s_device_frame(const m2s_ctx* c) { return c && c->frame_w ? c->d_frame : nullptr; }
 

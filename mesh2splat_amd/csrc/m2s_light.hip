@@ -271,11 +271,25 @@ __device__ __forceinline__ float cube_fetch(const float* __restrict__ cube, int 
     return cube[(size_t)face * SS + (size_t)j * (size_t)S + (size_t)i];
 }
 
+// kSplit (GaussianRelightingPass.cpp:90-135): pixels left of split_x are lit from the second set of planes (the mesh G-buffer), the
+// two divider columns from div_x on are white; everything else is the one shader.
+struct RelightPlanes { const uint2* pos; const uint2* nrm; const uint32_t* alb; const uint32_t* mr; };
+template <bool kSplit>
 __global__ void __launch_bounds__(256) k_relight(const RelightK k, const uint2* __restrict__ g_pos, const uint2* __restrict__ g_nrm,
                                                  const uint32_t* __restrict__ g_alb, const uint32_t* __restrict__ g_mr,
-                                                 const float* __restrict__ cube, uint32_t* __restrict__ frame, uint8_t* __restrict__ counts) {
+                                                 const float* __restrict__ cube, uint32_t* __restrict__ frame, uint8_t* __restrict__ counts,
+                                                 const RelightPlanes left, int split_x, int div_x) {
     const size_t px = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (px >= (size_t)k.W * (size_t)k.H) return;
+    if constexpr (kSplit) {
+        const int x = (int)(px % (size_t)k.W);
+        if (x >= div_x && x < div_x + 2) {                  // the scissored clear to white, drawn last
+            frame[px] = 0xFFFFFFFFu;
+            if (counts) counts[px] = 0;
+            return;
+        }
+        if (x < split_x) { g_pos = left.pos; g_nrm = left.nrm; g_alb = left.alb; g_mr = left.mr; }
+    }
     const uint32_t alb = g_alb[px];
     if (k.mode != 6) {                                   // :105-117: byte copies
         const uint32_t src = k.mode == 5 ? (g_mr[px] & 0x0000FFFFu) : (alb & 0x00FFFFFFu);
@@ -424,13 +438,20 @@ hipError_t shadow_raster(const float4* rec, const uint32_t* keys, const uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st) {
+hipError_t launch_relight(const RelightK& k, const void* const planes[5], const float* cube, uint32_t* frame, uint8_t* counts, hipStream_t st,
+                          const void* const left_planes[5], int split_x, int div_x) {
     const size_t px = (size_t)k.W * (size_t)k.H;
-    hipLaunchKernelGGL(k_relight, dim3((uint32_t)((px + 255u) / 256u)), dim3(256), 0, st, k, (const uint2*)planes[0], (const uint2*)planes[1],
-                       (const uint32_t*)planes[2], (const uint32_t*)planes[4], cube, frame, counts);
+    if (left_planes) {
+        const RelightPlanes lp = { (const uint2*)left_planes[0], (const uint2*)left_planes[1], (const uint32_t*)left_planes[2], (const uint32_t*)left_planes[4] };
+        hipLaunchKernelGGL(k_relight<true>, dim3((uint32_t)((px + 255u) / 256u)), dim3(256), 0, st, k, (const uint2*)planes[0], (const uint2*)planes[1],
+                           (const uint32_t*)planes[2], (const uint32_t*)planes[4], cube, frame, counts, lp, split_x, div_x);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_relight<false>, dim3((uint32_t)((px + 255u) / 256u)), dim3(256), 0, st, k, (const uint2*)planes[0], (const uint2*)planes[1],
+                       (const uint32_t*)planes[2], (const uint32_t*)planes[4], cube, frame, counts, RelightPlanes{ nullptr, nullptr, nullptr, nullptr }, 0, 0);
     return hipGetLastError();
 }
 
-hipError_t preload_light() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_relight)); }
+hipError_t preload_light() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_relight<false>)); }
 
 }  // namespace m2s

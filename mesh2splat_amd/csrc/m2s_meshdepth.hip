@@ -19,6 +19,11 @@
 //                  belong to, one thread stages one pair (exact int64 edge values at the tile's first pixel, m2s_quadraster.h), then one
 //                  lane per texel: coverage with 32-bit products, barycentrics from the exact edge values, running min in a register,
 //                  atomics only when the tile changes and only where the min is below a plain read.
+//
+// Every kernel that touches the image is a template over kVis.  false: the depth pass above, unchanged.  true: the visibility stage of
+// the mesh render pass (m2s_mesh_render, m2s_meshrender.hip shades its result): every mesh, back faces culled, and the payload of a
+// texel is the 64-bit key (bits of z) << 32 | global triangle index, so that the minimum is GL_LESS in draw order.
+#include <type_traits>
 #include <algorithm>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -36,6 +41,9 @@ namespace {
 
 constexpr int kTile = kSplatTile;
 constexpr uint32_t kOne = 0x3F800000u;      // 1.0f: the clear value
+constexpr unsigned long long kVisEmpty = ((unsigned long long)kOne << 32) | 0xFFFFFFFFull;     // the clear value of the visibility image
+
+template <bool kVis> using Texel = std::conditional_t<kVis, unsigned long long, uint32_t>;
 
 enum { kMdDead = 0, kMdUnclipped = 1, kMdClip = 2, kMdNonFinite = 3 };
 
@@ -63,7 +71,10 @@ __device__ __forceinline__ int md_classify(const MeshDepthK& k, const TriPlanes&
 }
 
 // One triangle after clipping: perspective division, z_w, the far rejection, viewport + snap + box.  false: nothing to draw.
-__device__ __forceinline__ bool md_piece(const MeshDepthK& k, float4 c0, float4 c1, float4 c2, RasterHead& h, float (&zw)[3]) {
+// kCull (GL_CULL_FACE, front = CCW): a piece whose snapped vertices in their STORED order have a doubled area <= 0 (window with y up)
+// is not drawn; *back = it was rejected for a negative one.
+template <bool kCull>
+__device__ __forceinline__ bool md_piece(const MeshDepthK& k, float4 c0, float4 c1, float4 c2, RasterHead& h, float (&zw)[3], bool* back = nullptr) {
     const float4 c[3] = { c0, c1, c2 };
     float nx[3], ny[3];
 #pragma unroll
@@ -74,6 +85,10 @@ __device__ __forceinline__ bool md_piece(const MeshDepthK& k, float4 c0, float4 
     }
     if (!(zw[0] < 1.0f || zw[1] < 1.0f || zw[2] < 1.0f)) return false;     // cannot pass GL_LESS against the clear value (or NaN)
     if (!raster_head_wh(nx, ny, k.W, k.H, h)) return false;
+    if constexpr (kCull) {
+        const long long stored = tri_area2(h.X, h.Y);
+        if (stored <= 0) { if (stored < 0) *back = true; return false; }
+    }
     // canonical vertex order — ascending (Y, X) of the snapped coordinates — so that neither the winding nor the order in which a
     // triangle's vertices are stored changes a bit of the interpolated depth (coverage never depended on it)
     auto cswap = [&](int i, int j) {
@@ -93,24 +108,29 @@ __device__ __forceinline__ float md_clamp(float z) { return z < 0.0f ? 0.0f : z 
 
 __device__ __forceinline__ uint64_t wave_count(bool b) { return (uint64_t)__popcll(__ballot(b)); }
 
-__global__ void __launch_bounds__(256) k_md_setup(const MeshDepthK k, const SceneDev sc, uint32_t* __restrict__ image, uint32_t* __restrict__ deferred,
+template <bool kVis>
+__global__ void __launch_bounds__(256) k_md_setup(const MeshDepthK k, const SceneDev sc, Texel<kVis>* __restrict__ image, uint32_t* __restrict__ deferred,
                                                   unsigned long long* __restrict__ totals) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int cls = kMdDead;
-    bool defer = false, drawn = false;
+    bool defer = false, drawn = false, back = false;
     uint32_t sent = 0;
     if (t < sc.n_tri) {
-        const uint2 mo = sc.mesh_of8[t >> 3];
-        const uint32_t mesh = t < mo.y ? mo.x : find_mesh(sc, sc.tri_first + t);
-        if (sc.meshes[mesh].color[3] == 1.0f) {                 // DepthPrepass.cpp:33
+        bool draw = true;                                       // (the mesh render pass draws every mesh)
+        if constexpr (!kVis) {
+            const uint2 mo = sc.mesh_of8[t >> 3];
+            const uint32_t mesh = t < mo.y ? mo.x : find_mesh(sc, sc.tri_first + t);
+            draw = sc.meshes[mesh].color[3] == 1.0f;            // DepthPrepass.cpp:33
+        }
+        if (draw) {
             float4 c[3];
             cls = md_classify(k, sc.tri, t, c);
             if (cls == kMdClip) defer = true;
             else if (cls == kMdUnclipped) {
                 RasterHead h;
                 float zw[3];
-                if (md_piece(k, c[0], c[1], c[2], h, zw)) {
+                if (md_piece<kVis>(k, c[0], c[1], c[2], h, zw, &back)) {
                     if (h.x1 - h.x0 < k.inplace && h.y1 - h.y0 < k.inplace) {
                         drawn = true;
                         const long long area2 = tri_area2(h.X, h.Y);
@@ -127,8 +147,9 @@ __global__ void __launch_bounds__(256) k_md_setup(const MeshDepthK k, const Scen
                                     const float b0 = i64_to_f32(r0) * inva, b1 = i64_to_f32(r1) * inva, b2 = i64_to_f32(r2) * inva;
                                     const float z = md_clamp((b0 * zw[0] + b1 * zw[1]) + b2 * zw[2]);
                                     if (z < 1.0f) {
-                                        uint32_t* px = image + (size_t)y * (size_t)k.W + (size_t)x;
-                                        const uint32_t bits = __float_as_uint(z);
+                                        Texel<kVis>* px = image + (size_t)y * (size_t)k.W + (size_t)x;
+                                        Texel<kVis> bits = __float_as_uint(z);
+                                        if constexpr (kVis) bits = (bits << 32) | (unsigned long long)(sc.tri_first + t);
                                         if (bits < *px) { atomicMin(px, bits); ++sent; }
                                     }
                                 }
@@ -158,18 +179,23 @@ __global__ void __launch_bounds__(256) k_md_setup(const MeshDepthK k, const Scen
         if (n_bad) atomicAdd(totals + 2, (unsigned long long)n_bad);
         if (s) atomicAdd(totals + 4, (unsigned long long)s);
     }
+    if constexpr (kVis) {
+        const uint64_t n_back = wave_count(back);
+        if (lane == 0 && n_back) atomicAdd(totals + 6, (unsigned long long)n_back);
+    }
 }
 
 // The 48-byte record of one piece (3 x float4): [0] X[3], Y[0]; [1] Y[1], Y[2], z_w[0], z_w[1]; [2] z_w[2], tile box (tx0 | ty0 << 16),
-// (tx1 | ty1 << 16), spare.  Slot 6 j + i holds piece i of deferred triangle j; cnt = its tiles (0: no piece).
+// (tx1 | ty1 << 16), the triangle's global index (visibility stage only).  Slot 6 j + i holds piece i of deferred triangle j; cnt = its tiles (0: no piece).
 constexpr int kMdSlots = 6;      // a triangle clipped by five planes has at most 8 vertices: a fan of 6
 
+template <bool kVis>
 __global__ void __launch_bounds__(64) k_md_deferred(const MeshDepthK k, const SceneDev sc, const uint32_t* __restrict__ deferred, uint32_t nd,
                                                     float4* __restrict__ rec, uint32_t* __restrict__ cnt, unsigned long long* __restrict__ totals) {
     __shared__ float4 poly[2][8][64];
     const int lane = threadIdx.x;
     const uint32_t j = blockIdx.x * 64u + threadIdx.x;
-    bool clipped = false, drawn = false;
+    bool clipped = false, drawn = false, back = false;
     if (j < nd) {
         const uint32_t t = deferred[j];
         float4 c[3];
@@ -206,14 +232,15 @@ __global__ void __launch_bounds__(64) k_md_deferred(const MeshDepthK k, const Sc
             if (i + 2 < n) {
                 RasterHead h;
                 float zw[3];
-                if (md_piece(k, v0, poly[cur][i + 1][lane], poly[cur][i + 2][lane], h, zw)) {
+                if (md_piece<kVis>(k, v0, poly[cur][i + 1][lane], poly[cur][i + 2][lane], h, zw, &back)) {
                     drawn = true;
                     const int t0x = h.x0 / kTile, t1x = h.x1 / kTile, t0y = h.y0 / kTile, t1y = h.y1 / kTile;
                     tiles = (uint32_t)(t1x - t0x + 1) * (uint32_t)(t1y - t0y + 1);
                     float4* o = rec + 3ull * ((size_t)j * kMdSlots + i);
                     o[0] = make_float4(__int_as_float(h.X[0]), __int_as_float(h.X[1]), __int_as_float(h.X[2]), __int_as_float(h.Y[0]));
                     o[1] = make_float4(__int_as_float(h.Y[1]), __int_as_float(h.Y[2]), zw[0], zw[1]);
-                    o[2] = make_float4(zw[2], __uint_as_float((uint32_t)t0x | ((uint32_t)t0y << 16)), __uint_as_float((uint32_t)t1x | ((uint32_t)t1y << 16)), 0.0f);
+                    o[2] = make_float4(zw[2], __uint_as_float((uint32_t)t0x | ((uint32_t)t0y << 16)), __uint_as_float((uint32_t)t1x | ((uint32_t)t1y << 16)),
+                                       kVis ? __uint_as_float(sc.tri_first + t) : 0.0f);
                 }
             }
             cnt[(size_t)j * kMdSlots + i] = tiles;
@@ -223,6 +250,10 @@ __global__ void __launch_bounds__(64) k_md_deferred(const MeshDepthK k, const Sc
     if (lane == 0) {
         if (n_drawn) atomicAdd(totals + 0, (unsigned long long)n_drawn);
         if (n_clip) atomicAdd(totals + 1, (unsigned long long)n_clip);
+    }
+    if constexpr (kVis) {        // culled: a piece was back-facing and none was drawn
+        const uint64_t n_back = wave_count(back && !drawn);
+        if (lane == 0 && n_back) atomicAdd(totals + 6, (unsigned long long)n_back);
     }
 }
 
@@ -246,11 +277,12 @@ struct __align__(16) StagedTri {
     int4 m;                 // T[2], covered by the tile's box (0 / 1), tile key, bits of 1 / area2
     float4 z;               // z_w[0..2]
     long long E[3];         // edge values at the centre of the tile's first pixel
-    long long pad;
+    long long tri;          // visibility stage: the triangle's global index
 };
 
+template <bool kVis>
 __global__ void __launch_bounds__(256) k_md_tiles(const float4* __restrict__ rec, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                  uint32_t pairs, int W, int H, int tiles_x, uint32_t* __restrict__ image,
+                                                  uint32_t pairs, int W, int H, int tiles_x, Texel<kVis>* __restrict__ image,
                                                   unsigned long long* __restrict__ totals) {
     __shared__ StagedTri sq[256];
     __shared__ uint32_t wg_writes;
@@ -269,7 +301,7 @@ __global__ void __launch_bounds__(256) k_md_tiles(const float4* __restrict__ rec
         StagedTri s;
         s.ea = s.eb = make_int4(0, 0, 0, kTMax);
         s.E[0] = s.E[1] = s.E[2] = 0;
-        s.pad = 0;
+        s.tri = kVis ? (long long)__float_as_uint(r2.w) : 0;
         int t2 = kTMax;
         uint32_t waves = 0;
         const bool meets = box_meets_tile(X, Y, W, H, px0, py0, &waves);
@@ -282,21 +314,25 @@ __global__ void __launch_bounds__(256) k_md_tiles(const float4* __restrict__ rec
     }
     __syncthreads();
     uint32_t sent = 0;
-    auto flush = [&](uint32_t key, float zmin) {
+    // the running minimum of a texel: the depth, or (visibility stage) the whole 64-bit key; both start at the clear value
+    using Min = std::conditional_t<kVis, unsigned long long, float>;
+    constexpr Min kClear = kVis ? (Min)kVisEmpty : (Min)1.0f;
+    auto flush = [&](uint32_t key, Min zmin) {
         const int x = (int)(key % (uint32_t)tiles_x) * kTile + lx, y = (int)(key / (uint32_t)tiles_x) * kTile + ly;
-        if (x < W && y < H && zmin < 1.0f) {
-            uint32_t* p = image + (size_t)y * (size_t)W + (size_t)x;
-            const uint32_t bits = __float_as_uint(zmin);
+        if (x < W && y < H && zmin < kClear) {
+            Texel<kVis>* p = image + (size_t)y * (size_t)W + (size_t)x;
+            Texel<kVis> bits;
+            if constexpr (kVis) bits = zmin; else bits = __float_as_uint(zmin);
             // (the plain read races with other workgroups' atomicMin on this texel; a texel only ever decreases, so a stale value is
             //  at least the current one: it can cause a redundant atomic, never a missed one)
             if (bits < *p) { atomicMin(p, bits); ++sent; }
         }
     };
     uint32_t cur = (uint32_t)sq[0].m.z;
-    float zmin = 1.0f;
+    Min zmin = kClear;
     for (uint32_t e = 0; e < m; ++e) {
         const int4 mm = sq[e].m;
-        if ((uint32_t)mm.z != cur) { flush(cur, zmin); cur = (uint32_t)mm.z; zmin = 1.0f; }     // (workgroup-uniform)
+        if ((uint32_t)mm.z != cur) { flush(cur, zmin); cur = (uint32_t)mm.z; zmin = kClear; }     // (workgroup-uniform)
         if (!mm.y) continue;
         const int4 a = sq[e].ea, b = sq[e].eb;
         const int s0 = a.x * lx + b.x * ly, s1 = a.y * lx + b.y * ly, s2 = a.z * lx + b.z * ly;
@@ -306,13 +342,21 @@ __global__ void __launch_bounds__(256) k_md_tiles(const float4* __restrict__ rec
             const float b0 = i64_to_f32(sq[e].E[0] + 256ll * s0) * inva, b1 = i64_to_f32(sq[e].E[1] + 256ll * s1) * inva,
                         b2 = i64_to_f32(sq[e].E[2] + 256ll * s2) * inva;
             const float zz = md_clamp((b0 * z.x + b1 * z.y) + b2 * z.z);
-            if (zz < zmin) zmin = zz;
+            if constexpr (kVis) {
+                const unsigned long long kk = ((unsigned long long)__float_as_uint(zz) << 32) | (unsigned long long)sq[e].tri;
+                if (zz < 1.0f && kk < zmin) zmin = kk;
+            } else if (zz < zmin) zmin = zz;
         }
     }
     flush(cur, zmin);
     if (sent) atomicAdd(&wg_writes, sent);
     __syncthreads();
     if (tid == 0 && wg_writes) atomicAdd(totals + 4, (unsigned long long)wg_writes);
+}
+
+__global__ void __launch_bounds__(256) k_mv_clear(unsigned long long* __restrict__ image, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) image[i] = kVisEmpty;
 }
 
 }  // namespace
@@ -332,13 +376,25 @@ hipError_t meshdepth_clear(float* image, int W, int H, hipStream_t st) {
 }
 
 hipError_t meshdepth_setup(const MeshDepthK& k, const SceneDev& sc, float* image, uint32_t* deferred, unsigned long long* totals, hipStream_t st) {
-    hipLaunchKernelGGL(k_md_setup, dim3((sc.n_tri + 255u) / 256u), dim3(256), 0, st, k, sc, (uint32_t*)image, deferred, totals);
+    hipLaunchKernelGGL(k_md_setup<false>, dim3((sc.n_tri + 255u) / 256u), dim3(256), 0, st, k, sc, (uint32_t*)image, deferred, totals);
+    return hipGetLastError();
+}
+
+hipError_t meshvis_clear(unsigned long long* image, int W, int H, hipStream_t st) {
+    const size_t n = (size_t)W * (size_t)H;
+    hipLaunchKernelGGL(k_mv_clear, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, st, image, n);
+    return hipGetLastError();
+}
+
+hipError_t meshvis_setup(const MeshDepthK& k, const SceneDev& sc, unsigned long long* image, uint32_t* deferred, unsigned long long* totals, hipStream_t st) {
+    hipLaunchKernelGGL(k_md_setup<true>, dim3((sc.n_tri + 255u) / 256u), dim3(256), 0, st, k, sc, image, deferred, totals);
     return hipGetLastError();
 }
 
 hipError_t meshdepth_deferred(const MeshDepthK& k, const SceneDev& sc, const uint32_t* deferred, uint32_t nd, float4* rec, uint32_t* cnt,
-                              unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st) {
-    hipLaunchKernelGGL(k_md_deferred, dim3((nd + 63u) / 64u), dim3(64), 0, st, k, sc, deferred, nd, rec, cnt, totals);
+                              unsigned long long* off, void* temp, size_t temp_bytes, unsigned long long* totals, hipStream_t st, bool vis) {
+    if (vis) hipLaunchKernelGGL(k_md_deferred<true>, dim3((nd + 63u) / 64u), dim3(64), 0, st, k, sc, deferred, nd, rec, cnt, totals);
+    else hipLaunchKernelGGL(k_md_deferred<false>, dim3((nd + 63u) / 64u), dim3(64), 0, st, k, sc, deferred, nd, rec, cnt, totals);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const uint32_t slots = nd * (uint32_t)kMdSlots;
@@ -364,10 +420,17 @@ hipError_t meshdepth_bin(const MeshDepthK& k, const float4* rec, const uint32_t*
 hipError_t meshdepth_raster(const MeshDepthK& k, const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, float* image,
                             unsigned long long* totals, hipStream_t st) {
     const int tiles_x = (k.W + kTile - 1) / kTile;
-    hipLaunchKernelGGL(k_md_tiles, dim3((pairs + 255u) / 256u), dim3(256), 0, st, rec, keys, vals, pairs, k.W, k.H, tiles_x, (uint32_t*)image, totals);
+    hipLaunchKernelGGL(k_md_tiles<false>, dim3((pairs + 255u) / 256u), dim3(256), 0, st, rec, keys, vals, pairs, k.W, k.H, tiles_x, (uint32_t*)image, totals);
     return hipGetLastError();
 }
 
-hipError_t preload_meshdepth() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_md_setup)); }
+hipError_t meshvis_raster(const MeshDepthK& k, const float4* rec, const uint32_t* keys, const uint32_t* vals, uint32_t pairs, unsigned long long* image,
+                          unsigned long long* totals, hipStream_t st) {
+    const int tiles_x = (k.W + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_md_tiles<true>, dim3((pairs + 255u) / 256u), dim3(256), 0, st, rec, keys, vals, pairs, k.W, k.H, tiles_x, image, totals);
+    return hipGetLastError();
+}
+
+hipError_t preload_meshdepth() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_md_setup<false>)); }
 
 }  // namespace m2s

@@ -59,6 +59,7 @@ struct Options {
     std::string preview;                                           // --preview view.png: prepass + depth sort + splat of the result
     int preview_w = 1280, preview_h = 720;
     bool mesh_depth_test = false;                                  // --mesh-depth-test: the preview uses the mesh as occluder (m2s_mesh_depth)
+    double split_screen = -1.0;                                    // --split-screen POS: the preview is the split screen, mesh left of POS * W (m2s_mesh_render + m2s_relight_split)
     int preview_mode = 0;                                          // --preview-mode N: 0..4 the albedo plane (as before), 5 / 6 the relit frame
     bool has_light = false;                                        // --light x,y,z[,intensity]
     double light[4] = { 0, 0, 0, 0 };
@@ -71,13 +72,15 @@ void usage() {
                  "       mesh2splat --batch in_dir --out out_dir [options]\n"
                  "options: [--density R | --quality q [--max-res M]] [--std s] [--format 0|1|2] [--device d] [--gpus N [--gather]]\n"
                  "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
-                 "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test]]\n"
+                 "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test] [--split-screen POS (0..1)]]\n"
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
                  "  dist = 1.1 * radius / tan(radians(22.5)), eye = centre + (0, 0, dist), up = (0, 1, 0), looking at centre,\n"
-                 "  45 deg vertical field of view, aspect W / H, near = dist / 100, far = dist * 10.\n");
+                 "  45 deg vertical field of view, aspect W / H, near = dist / 100, far = dist * 10.\n"
+                 "--split-screen POS: the preview is the reference's split screen (m2s_mesh_render + m2s_relight_split): the source mesh left\n"
+                 "  of column (int)(POS * W), the splats right of it, two white divider columns; with --preview-mode 0..4 both sides show albedo.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -231,7 +234,8 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
         if (m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
     }
     std::vector<uint8_t> img((size_t)W * H * 4, 0);
-    const bool relit = o.preview_mode == 5 || o.preview_mode == 6;
+    const bool split = o.split_screen >= 0.0;
+    const bool relit = o.preview_mode == 5 || o.preview_mode == 6 || split;       // (the split screen is composed by the relighting pass)
     if (n || relit) {
         m2s_splat_params sp = { { W, H }, 0, 0 };
         static const m2s_quad none = {};
@@ -253,7 +257,22 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
         std::printf("preview light: position=%.17g,%.17g,%.17g intensity=%.17g colour=1,1,1 shadow=1024\n", lpos[0], lpos[1], lpos[2], inten);
         uint64_t per_face[6], sh_skipped = 0;
         if (m2s_shadow(ctx, &pp, &lp, nullptr, 0, per_face, &sh_skipped) != M2S_OK) return 1;
-        if (m2s_relight(ctx, &lp) != M2S_OK) return 1;
+        if (split) {
+            // MeshRenderPass with the preview camera, then the relighting pass with the mesh G-buffer left of the divider
+            m2s_mesh_render_params mr;
+            std::memset(&mr, 0, sizeof(mr));
+            std::memcpy(mr.world_to_view, pp.world_to_view, sizeof(mr.world_to_view));
+            std::memcpy(mr.view_to_clip, pp.view_to_clip, sizeof(mr.view_to_clip));
+            std::memcpy(mr.model_to_world, pp.model_to_world, sizeof(mr.model_to_world));
+            mr.resolution[0] = W; mr.resolution[1] = H;
+            mr.near_far[0] = pp.near_far[0]; mr.near_far[1] = pp.near_far[1];
+            mr.render_mode = pp.render_mode;
+            uint64_t mc[6] = {};
+            if (m2s_mesh_render(ctx, &mr, mc) != M2S_OK) return 1;
+            std::printf("split screen at %.17g: %llu triangles drawn (%llu clipped, %llu culled as back-facing)\n", o.split_screen,
+                        (unsigned long long)mc[0], (unsigned long long)mc[1], (unsigned long long)mc[5]);
+            if (m2s_relight_split(ctx, &lp, (float)o.split_screen) != M2S_OK) return 1;
+        } else if (m2s_relight(ctx, &lp) != M2S_OK) return 1;
         if (m2s_download_frame(ctx, img.data(), img.size()) != M2S_OK) return 1;
     }
     if (!write_png_rgba(o.preview.c_str(), img.data(), W, H)) { std::fprintf(stderr, "cannot write %s\n", o.preview.c_str()); return 2; }
@@ -625,6 +644,7 @@ int main(int argc, char** argv) {
         else if (a == "--timing") o.timing = true;
         else if (a == "--preview") o.preview = next();
         else if (a == "--mesh-depth-test") o.mesh_depth_test = true;
+        else if (a == "--split-screen") { o.split_screen = std::atof(next()); if (!(o.split_screen >= 0.0 && o.split_screen <= 1.0)) { usage(); return 2; } }
         else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
