@@ -646,6 +646,64 @@ m2s_status m2s_last_mesh_render_counts(const m2s_ctx* ctx, uint64_t out[6]);
  * outside [0, 1], M2S_ERR_STATE without a mesh G-buffer of the G-buffer's W x H. */
 m2s_status m2s_relight_split(m2s_ctx* ctx, const m2s_light_params* light, float split_position);
 
+/* ---- fidelity score: the mesh frame against the splat frame (no counterpart in the reference, where a person looks at the split screen) */
+/* m2s_relight over the MESH G-buffer of the last m2s_mesh_render, every pixel, no divider: the shader, cube and light m2s_relight_split
+ * uses left of the divider, into a SECOND frame buffer (m2s_device_mesh_frame; uchar4[W * H], row 0 = bottom).  m2s_device_frame and the
+ * shadow counts of the last m2s_relight stay untouched (want_shadow_counts is not read).  By definition its bytes are those of
+ * m2s_upload_gbuffer(the mesh G-buffer's five planes) followed by m2s_relight.  Errors as m2s_relight (`resolution` is compared with the
+ * mesh G-buffer's), and M2S_ERR_STATE without a mesh G-buffer.  m2s_last_relight_ms is this call's time when it was the last profiled. */
+m2s_status m2s_relight_mesh(m2s_ctx* ctx, const m2s_light_params* light);
+/* The frame of the last m2s_relight_mesh.  NULL / M2S_ERR_STATE before any. */
+const void* m2s_device_mesh_frame(const m2s_ctx* ctx);
+m2s_status m2s_download_mesh_frame(m2s_ctx* ctx, void* dst, uint64_t capacity_bytes);
+
+/* Compares image B (under test: the splats) with image A (the reference: the mesh) in one pass over the device images.  All four images
+ * are uchar4[W * H] device pointers, row 0 = bottom.  A NULL pointer means the context's own buffer — d_a: m2s_device_mesh_frame, d_b:
+ * m2s_device_frame, d_cover_a: attachment 2 of the mesh G-buffer, d_cover_b: attachment 2 of the splat G-buffer — and M2S_ERR_STATE when
+ * that buffer does not exist or is not W x H.  Every output is an integer; the pin (tests/score_ref.py restates it in numpy):
+ *  - Coverage: a pixel is covered by A when the alpha byte (bits 24..31) of cover_a is non-zero (m2s_mesh_render leaves 255 or 0 there),
+ *    by B when the alpha byte of cover_b is non-zero (the accumulated alpha m2s_splat leaves in the albedo attachment).  With
+ *    M2S_SCORE_NO_COVER the planes are not read and every pixel counts as covered by both.  cover[] = pixels covered by neither, A only,
+ *    B only, both — over the WHOLE image, whatever the mask.
+ *  - Mask: mode 0 every pixel, 1 covered by A, 2 by A or B, 3 by A and B.  pixels = pixels that pass.
+ *  - Colour, over the pixels that pass, per channel R, G, B (bytes 0, 1, 2) of the frames; frame alpha ignored: sse = sum of (a - b)^2,
+ *    sad = sum of |a - b|, max_abs = max of |a - b|.  (PSNR is left to the caller: 10 log10(255^2 * 3 * pixels / (sse_r + sse_g + sse_b)).)
+ *  - Luma: Y = (77 R + 150 G + 29 B + 128) >> 8, 0..255.
+ *  - SSIM, the integer block form: windows of 8 x 8 pixels with origins (4 i, 4 j), 4 i + 8 <= W, 4 j + 8 <= H.  A window is COUNTED when
+ *    at least 32 of its 64 pixels pass the mask; all 64 pixels enter its sums either way.  s1 = sum Ya, s2 = sum Yb, ssq = sum Ya^2 + sum
+ *    Yb^2, s12 = sum Ya Yb (each < 2^32); c1 = 26634, c2 = 239708 (= (0.01 * 255)^2 * 64^2 and (0.03 * 255)^2 * 64^2, truncated); in int64
+ *    num = (2 s1 s2 + c1) (128 s12 - 2 s1 s2 + c2), den = (s1^2 + s2^2 + c1) (64 ssq - s1^2 - s2^2 + c2) (|num|, den < 2^59, den > 0);
+ *    ssim = (double)num / (double)den, the two conversions and the division correctly rounded (fp64, the one floating-point step);
+ *    q = llrint(ssim * 2^32) (ties to even; the product is exact).  windows = windows counted, ssim_q32 = sum of their q in 64-bit
+ *    integer arithmetic (below 2^55 at 8192 x 8192).  Identical windows give exactly 2^32.  W < 8 or H < 8: no window.
+ *  - Every output is a sum, count or maximum of integers: it does not depend on the order of the reduction, two calls give the same
+ *    bits, and so does the numpy restatement.  No floating-point atomics.
+ *  - M2S_SCORE_WANT_MAP: the context also keeps the error map, uchar4[W * H]: (|dR|, |dG|, |dB|, 255) where the pixel passes the mask,
+ *    zeros elsewhere (m2s_device_score_map / m2s_download_score_map: NULL / M2S_ERR_STATE when the LAST call kept none).
+ * Synchronous.  Errors: M2S_ERR_INVALID for a resolution outside 1..8192, mask_mode > 3, an unknown flag, reserved != 0, a NULL
+ * params / out; M2S_ERR_STATE as above. */
+enum { M2S_SCORE_NO_COVER = 1, M2S_SCORE_WANT_MAP = 2 };
+typedef struct m2s_score_params {      /* 24 bytes */
+    int32_t  resolution[2];  /* W, H, 1..8192 each */
+    uint32_t mask_mode;      /* 0 every pixel, 1 covered by A, 2 by A or B, 3 by A and B */
+    uint32_t flags;          /* M2S_SCORE_* */
+    uint32_t reserved[2];    /* 0 */
+} m2s_score_params;
+typedef struct m2s_score_result {      /* 120 bytes */
+    uint64_t pixels;         /* pixels that pass the mask */
+    uint64_t cover[4];       /* over the WHOLE image: neither, A only, B only, both */
+    uint64_t sse[3], sad[3]; /* R, G, B over the pixels that pass: sum of (a - b)^2, sum of |a - b| */
+    uint32_t max_abs[3], pad;
+    uint64_t windows;        /* SSIM windows counted */
+    int64_t  ssim_q32;       /* sum over the counted windows of llrint(ssim * 2^32) */
+} m2s_score_result;
+m2s_status m2s_score_frames(m2s_ctx* ctx, const m2s_score_params* params, const void* d_a, const void* d_b, const void* d_cover_a,
+                            const void* d_cover_b, m2s_score_result* out);
+const void* m2s_device_score_map(const m2s_ctx* ctx);
+m2s_status m2s_download_score_map(m2s_ctx* ctx, void* dst, uint64_t capacity_bytes);
+/* Duration (ms) of the last profiled m2s_score_frames kernel. */
+float m2s_last_score_ms(const m2s_ctx* ctx);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

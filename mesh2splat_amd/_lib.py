@@ -44,6 +44,8 @@ EXPORTS = (
     "m2s_last_mesh_depth_counts", "m2s_debug_set_mesh_depth_inplace",
     "m2s_mesh_render", "m2s_device_mesh_gbuffer", "m2s_download_mesh_gbuffer", "m2s_download_mesh_visibility", "m2s_last_mesh_render_ms",
     "m2s_last_mesh_render_stage_ms", "m2s_last_mesh_render_counts", "m2s_relight_split",
+    "m2s_relight_mesh", "m2s_device_mesh_frame", "m2s_download_mesh_frame", "m2s_score_frames", "m2s_device_score_map",
+    "m2s_download_score_map", "m2s_last_score_ms",
 )
 
 
@@ -226,6 +228,13 @@ def load():
         "m2s_last_mesh_render_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_last_mesh_render_counts": (C.c_int, [vp, C.POINTER(u64)]),
         "m2s_relight_split": (C.c_int, [vp, vp, C.c_float]),
+        "m2s_relight_mesh": (C.c_int, [vp, vp]),
+        "m2s_device_mesh_frame": (vp, [vp]),
+        "m2s_download_mesh_frame": (C.c_int, [vp, vp, u64]),
+        "m2s_score_frames": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "m2s_device_score_map": (vp, [vp]),
+        "m2s_download_score_map": (C.c_int, [vp, vp, u64]),
+        "m2s_last_score_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

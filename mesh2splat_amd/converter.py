@@ -574,15 +574,16 @@ class Converter:
         W, H = self._last_md_wh
         return dataclasses.replace(prepass_params, perform_mesh_depth_test=True, mesh_depth=_DeviceImage(self.device_mesh_depth, H, W))
 
-    def render_frame(self, prepass_params, light_params, mesh_depth_test: bool = False, split_screen: Optional[float] = None):
+    def render_frame(self, prepass_params, light_params, mesh_depth_test: bool = False, split_screen: Optional[float] = None,
+                     download: bool = True):
         """One viewer frame of the context's records (renderer.cpp:129-138): prepass + depth sort + splat + shadow + relight.
         split_screen (None: off, the frame is what it was without the argument; else a position in [0, 1]): the mesh render pass of the
         uploaded scene runs with the frame's camera and render mode (mesh_render) and the relighting pass composes the reference's
-        split screen (relight_split): mesh left of the divider, splats right — subtracting the frames at positions 1 and 0 gives a
-        fidelity figure for the conversion.  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
+        split screen (relight_split): mesh left of the divider, splats right.  (Both of those frames carry the white divider; the fidelity
+        figure of a conversion is score(), which compares the splat frame with a mesh frame that has none.)  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
         renderer_resolution must equal `prepass_params`'s.  mesh_depth_test: the frame starts with the mesh depth prepass of the uploaded
         scene (mesh_depth) and the Gaussian prepass — then m2s_prepass_sorted — tests against its image on the device, the reference's
-        "use the mesh as occluder in depth prepass".  -> what relight() returns."""
+        "use the mesh as occluder in depth prepass".  -> what relight() returns (download=False: None, the frame stays on the device)."""
         from .splat import SplatParams
         res = tuple(int(v) for v in prepass_params.renderer_resolution)
         if tuple(int(v) for v in light_params.renderer_resolution) != res:
@@ -601,8 +602,98 @@ class Converter:
         self.shadow(prepass_params, light_params, download=False)
         if split_screen is not None:
             self.mesh_render(prepass_params, download=False)
-            return self.relight_split(light_params, split_screen)
-        return self.relight(light_params)
+            return self.relight_split(light_params, split_screen, download=download)
+        return self.relight(light_params, download=download)
+
+    # -- fidelity score ----------------------------------------------------------------------------
+    def relight_mesh(self, light_params, download: bool = True):
+        """m2s_relight_mesh: the relighting pass over the MESH G-buffer of the last mesh_render(), every pixel, no divider, into a second
+        frame buffer (device_mesh_frame); device_frame is left as it was.  -> frame (H, W, 4) uint8, row 0 = bottom; download=False: None."""
+        from . import light as _li
+        lc = _li.to_c(light_params)
+        self._check(self._L.m2s_relight_mesh(self._h, C.byref(lc)))
+        return self.download_mesh_frame(int(lc.resolution[0]), int(lc.resolution[1])) if download else None
+
+    def download_mesh_frame(self, W: int, H: int) -> np.ndarray:
+        """The frame of the last relight_mesh(): (H, W, 4) uint8, row 0 = bottom."""
+        frame = np.empty((int(H), int(W), 4), np.uint8)
+        self._check(self._L.m2s_download_mesh_frame(self._h, frame.ctypes.data, frame.nbytes))
+        return frame
+
+    @property
+    def device_mesh_frame(self) -> int:
+        return int(self._L.m2s_device_mesh_frame(self._h) or 0)
+
+    @staticmethod
+    def _image_ptr(img, what: str, nbytes: int):
+        """Device address of `img`: None (the context's own buffer), a contiguous CUDA torch tensor of W * H * 4 bytes, or a _DeviceImage."""
+        if img is None:
+            return None, False
+        if isinstance(img, _DeviceImage):
+            return img.data_ptr(), False
+        if not (hasattr(img, "data_ptr") and img.is_cuda and img.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous CUDA tensor of W x H uchar4 pixels, or a _DeviceImage")
+        if img.numel() * img.element_size() != nbytes:
+            raise ValueError(f"{what} holds {img.numel() * img.element_size()} bytes, W x H x 4 is {nbytes}")
+        return img.data_ptr(), True
+
+    def score_frames(self, params, a=None, b=None, cover_a=None, cover_b=None, download_map: bool = False):
+        """m2s_score_frames: image `b` (under test: the splats) against image `a` (the reference: the mesh), with their coverage planes.
+        Each is None (the context's own: the mesh frame, the frame, the albedo attachments of the mesh and splat G-buffers), a contiguous
+        CUDA torch tensor of W x H uchar4 pixels (row 0 = bottom), or a _DeviceImage.  `params`: mesh2splat_amd.score.ScoreParams.
+        -> ScoreResult; with download_map (and params.want_map) its error_map is the (H, W, 4) uint8 map."""
+        from . import score as _sc
+        pc = _sc.to_c(params)
+        W, H = int(pc.resolution[0]), int(pc.resolution[1])
+        ptrs, tensors = [], False
+        for img, what in ((a, "a"), (b, "b"), (cover_a, "cover_a"), (cover_b, "cover_b")):
+            ptr, is_tensor = self._image_ptr(img, what, max(W, 0) * max(H, 0) * 4)
+            ptrs.append(ptr)
+            tensors = tensors or is_tensor
+        if tensors:                                     # the context's stream does not wait for torch's
+            import torch
+            torch.cuda.current_stream().synchronize()
+        out = _sc.ScoreResultC()
+        self._check(self._L.m2s_score_frames(self._h, C.byref(pc), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(out)))
+        res = _sc.ScoreResult.from_c(out)
+        if download_map:
+            res.error_map = self.download_score_map(W, H)
+        return res
+
+    def download_score_map(self, W: int, H: int) -> np.ndarray:
+        """The error map of the last score_frames (params.want_map): (H, W, 4) uint8, row 0 = bottom."""
+        m = np.empty((int(H), int(W), 4), np.uint8)
+        self._check(self._L.m2s_download_score_map(self._h, m.ctypes.data, m.nbytes))
+        return m
+
+    @property
+    def device_score_map(self) -> int:
+        return int(self._L.m2s_device_score_map(self._h) or 0)
+
+    @property
+    def last_score_ms(self) -> float:
+        return float(self._L.m2s_last_score_ms(self._h))
+
+    def score(self, prepass_params, light_params, mask_mode: int = 2, mesh_depth_test: bool = False, want_map: bool = False):
+        """How close the splats of the context's records look to the uploaded mesh through one camera: the frame of render_frame() for
+        the splats, mesh_render() + relight_mesh() for the mesh, and score_frames() over the context's own buffers (coverage: the albedo
+        attachments of the two G-buffers).  Nothing but the result leaves the device.  -> ScoreResult (want_map: with its error_map)."""
+        from . import score as _sc
+        self.render_frame(prepass_params, light_params, mesh_depth_test=mesh_depth_test, download=False)
+        self.mesh_render(prepass_params, download=False)
+        self.relight_mesh(light_params, download=False)
+        res = tuple(int(v) for v in prepass_params.renderer_resolution)
+        return self.score_frames(_sc.ScoreParams(res, int(mask_mode), False, bool(want_map)), download_map=bool(want_map))
+
+    def score_views(self, cameras, resolution_target: int, light_position, light_intensity: float, gaussian_std: float = 0.65,
+                    render_mode: int = 6, shadow_resolution: int = 1024, mask_mode: int = 2, mesh_depth_test: bool = False):
+        """score() through each of `cameras` (mesh2splat_amd.score.OrbitCamera, e.g. orbit_cameras(scene, K, W, H)), the frames built as the
+        command line's --score builds them (OrbitCamera.frame_params).  -> (per-view ScoreResults, the pooled ScoreResult: the integers
+        added, the ratios derived from the sums)."""
+        from . import score as _sc
+        views = [self.score(*cam.frame_params(resolution_target, light_position, light_intensity, gaussian_std, render_mode, shadow_resolution),
+                            mask_mode=mask_mode, mesh_depth_test=mesh_depth_test) for cam in cameras]
+        return views, _sc.pool(views)
 
     @property
     def last_shadow_ms(self) -> float:

@@ -6,6 +6,7 @@
 //   m2s_light.cpp    the shadow and relighting passes (== GaussianShadowPass / GaussianRelightingPass::execute)
 //   m2s_meshdepth.cpp  the mesh depth prepass (== DepthPrepass::execute)
 //   m2s_meshrender.cpp the mesh render pass (== MeshRenderPass::execute) and the mesh G-buffer
+//   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -258,6 +259,17 @@ struct m2s_ctx {
     float last_mr_ms = 0.0f;
     float last_mr_stage_ms[4] = { 0, 0, 0, 0 };  // visibility setup + in-place, clip + binning, tile raster, shading (profiling on)
     uint64_t last_mr_counts[6] = {};             // drawn, clipped, non-finite, pairs, texel updates sent, culled as back-facing
+    // fidelity score (m2s_light.cpp: m2s_relight_mesh; m2s_score.cpp): the mesh-lit frame, the comparison's counters and error map
+    uint32_t* d_mesh_frame = nullptr;            // uchar4[H][W], row 0 = bottom
+    uint64_t mesh_frame_cap_px = 0;
+    int32_t mesh_frame_w = 0, mesh_frame_h = 0;  // 0: no m2s_relight_mesh has run
+    unsigned long long* d_score_acc = nullptr;   // kScoreShards x kScoreCounters words (m2s_device.h), summed on the host
+    unsigned long long* h_score = nullptr;       // pinned copy
+    uint32_t* d_score_map = nullptr;             // uchar4[H][W]
+    uint64_t score_map_cap_px = 0;
+    int32_t score_map_w = 0, score_map_h = 0;    // 0: the last m2s_score_frames kept no map
+    hipEvent_t score_ev[2] = {};
+    float last_score_ms = 0.0f;
 
     // measurement
     bool profiling = false;

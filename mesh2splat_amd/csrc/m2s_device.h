@@ -326,6 +326,26 @@ struct MeshRenderK {                           // uniforms of meshRender{VS,PS}.
 hipError_t meshrender_shade(const MeshRenderK& k, const SceneDev& sc, const unsigned long long* vis, void* const planes[5], hipStream_t st);
 hipError_t preload_meshrender();
 
+// ---- fidelity score (m2s_score.hip): image B against image A, integer sums -----------------------------------------------------------
+struct ScoreK {
+    int32_t W, H;
+    uint32_t mask_mode;     // 0 every pixel, 1 covered by A, 2 by A or B, 3 by A and B
+    uint32_t tiles_x;       // workgroup tiles per row of tiles
+};
+constexpr int kScoreTileCells = 16;            // a workgroup's tile: 16 x 16 cells of 4 x 4 pixels (64 x 64 pixels) ...
+constexpr int kScoreGridCells = 17;            // ... plus one cell of halo to the right and above, for the windows that start in its last column / row
+constexpr int kScoreThreads = 320;             // one lane per cell of the 17 x 17 grid (289), rounded up to whole waves
+// counters of one shard: [0] pixels, [1..4] cover, [5..7] sse, [8..10] sad, [11..13] max_abs, [14] windows, [15] ssim_q32 (two's complement)
+constexpr int kScoreCounters = 16;
+constexpr int kScoreMaxFirst = 11, kScoreMaxLast = 13;   // the counters combined by max instead of +
+constexpr int kScoreShards = 32;               // workgroup b adds into shard b % 32: same-address atomics serialise, the host sums the shards
+inline uint32_t score_tiles(int n) { return (uint32_t)((n + 4 * kScoreTileCells - 1) / (4 * kScoreTileCells)); }
+// acc: kScoreShards * kScoreCounters words, zero before.  cover_a / cover_b NULL (both): the planes are not read, every pixel counts as
+// covered by both.  map (or NULL): the error map.  Row loads are 16 bytes wide when W % 4 == 0 and every pointer is 16-byte aligned.
+hipError_t launch_score(const ScoreK& k, const uint32_t* a, const uint32_t* b, const uint32_t* cover_a, const uint32_t* cover_b, uint32_t* map,
+                        unsigned long long* acc, hipStream_t st);
+hipError_t preload_score();
+
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);
 void launch_lower_bounds(const uint32_t* keys, uint64_t n, const unsigned long long* splitters, uint32_t m, unsigned long long* out, hipStream_t st);

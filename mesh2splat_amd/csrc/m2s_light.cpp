@@ -335,15 +335,30 @@ m2s_status m2s_upload_gbuffer(m2s_ctx* c, const void* const planes[5], int32_t W
 }
 
 // GaussianRelightingPass::execute: one full-screen draw of gaussianSplattingDeferredPS.glsl; split: the branch with the split screen.
+static m2s_status relight_checks(m2s_ctx* c, const m2s_light_params* lp, int32_t gw, int32_t gh) {
+    int S = 0;
+    if (m2s_status s = check_light(c, lp, &S)) return s;
+    if (!gw) return fail(c, M2S_ERR_INVALID, "no G-buffer exists (run m2s_splat or m2s_upload_gbuffer)");
+    if (!c->shadow_S) return fail(c, M2S_ERR_INVALID, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
+    if (lp->resolution[0] != gw || lp->resolution[1] != gh) return fail(c, M2S_ERR_INVALID, "resolution is not the G-buffer's");
+    if (lp->shadow_resolution && (int32_t)lp->shadow_resolution != c->shadow_S) return fail(c, M2S_ERR_INVALID, "shadow resolution is not the cube's");
+    return M2S_OK;
+}
+
+static RelightK relight_uniforms(const m2s_ctx* c, const m2s_light_params* lp, int32_t W, int32_t H) {
+    RelightK k;
+    for (int i = 0; i < 3; ++i) { k.light[i] = lp->light_position[i]; k.cam[i] = lp->camera_position[i]; k.color[i] = lp->light_color[i]; }
+    k.intensity = lp->light_intensity;
+    k.far_plane = lp->near_far[1];
+    k.mode = lp->render_mode;
+    k.W = W; k.H = H; k.S = c->shadow_S;
+    return k;
+}
+
 static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, float split_position) {
     if (!c || !lp) return M2S_ERR_INVALID;
     if (split && !(split_position >= 0.0f && split_position <= 1.0f)) return fail(c, M2S_ERR_INVALID, "split position outside 0..1");
-    int S = 0;
-    if (m2s_status s = check_light(c, lp, &S)) return s;
-    if (!c->gbuf_w) return fail(c, M2S_ERR_INVALID, "no G-buffer exists (run m2s_splat or m2s_upload_gbuffer)");
-    if (!c->shadow_S) return fail(c, M2S_ERR_INVALID, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
-    if (lp->resolution[0] != c->gbuf_w || lp->resolution[1] != c->gbuf_h) return fail(c, M2S_ERR_INVALID, "resolution is not the G-buffer's");
-    if (lp->shadow_resolution && (int32_t)lp->shadow_resolution != c->shadow_S) return fail(c, M2S_ERR_INVALID, "shadow resolution is not the cube's");
+    if (m2s_status s = relight_checks(c, lp, c->gbuf_w, c->gbuf_h)) return s;
     if (split && (c->mr_w != c->gbuf_w || c->mr_h != c->gbuf_h)) return fail(c, M2S_ERR_STATE, "no mesh G-buffer of the G-buffer's resolution exists (run m2s_mesh_render)");
     HIPCHK(c, hipSetDevice(c->device));
     if (m2s_status s = ensure_light_common(c)) return s;
@@ -358,12 +373,7 @@ static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, fl
         HIPCHK(c, hipMalloc((void**)&c->d_shadow_counts, px));
         c->frame_cap_px = px;
     }
-    RelightK k;
-    for (int i = 0; i < 3; ++i) { k.light[i] = lp->light_position[i]; k.cam[i] = lp->camera_position[i]; k.color[i] = lp->light_color[i]; }
-    k.intensity = lp->light_intensity;
-    k.far_plane = lp->near_far[1];
-    k.mode = lp->render_mode;
-    k.W = c->gbuf_w; k.H = c->gbuf_h; k.S = c->shadow_S;
+    const RelightK k = relight_uniforms(c, lp, c->gbuf_w, c->gbuf_h);
     const bool counts = lp->want_shadow_counts != 0 && lp->render_mode == 6;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
     const int split_x = split ? (int)(split_position * (float)c->gbuf_w) : 0;      // static_cast<int>(splitScreenPosition * w)
@@ -382,6 +392,27 @@ static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, fl
 m2s_status m2s_relight(m2s_ctx* c, const m2s_light_params* lp) { return relight(c, lp, false, 0.0f); }
 m2s_status m2s_relight_split(m2s_ctx* c, const m2s_light_params* lp, float split_position) { return relight(c, lp, true, split_position); }
 
+// The same draw over the MESH G-buffer, every pixel, into the second frame buffer: the reference image of m2s_score_frames.  The
+// frame and the shadow counts of m2s_relight are not touched.
+m2s_status m2s_relight_mesh(m2s_ctx* c, const m2s_light_params* lp) {
+    if (!c || !lp) return M2S_ERR_INVALID;
+    if (!c->mr_w) return fail(c, M2S_ERR_STATE, "no mesh G-buffer exists (run m2s_mesh_render)");
+    if (m2s_status s = relight_checks(c, lp, c->mr_w, c->mr_h)) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m2s_status s = ensure_light_common(c)) return s;
+    c->mesh_frame_w = c->mesh_frame_h = 0;
+    if (m2s_status s = grow(c, c->d_mesh_frame, c->mesh_frame_cap_px, (uint64_t)c->mr_w * (uint64_t)c->mr_h, 4)) return s;
+    const RelightK k = relight_uniforms(c, lp, c->mr_w, c->mr_h);
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
+    HIPCHK(c, launch_relight(k, c->d_mr_gbuf, c->d_shadow_cube, c->d_mesh_frame, nullptr, c->stream));
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
+    c->mesh_frame_w = c->mr_w;
+    c->mesh_frame_h = c->mr_h;
+    return M2S_OK;
+}
+
 const void* m2s_device_frame(const m2s_ctx* c) { return c && c->frame_w ? c->d_frame : nullptr; }
 
 m2s_status m2s_download_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
@@ -391,6 +422,18 @@ m2s_status m2s_download_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
     if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the frame");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy(dst, c->d_frame, bytes, hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+const void* m2s_device_mesh_frame(const m2s_ctx* c) { return c && c->mesh_frame_w ? c->d_mesh_frame : nullptr; }
+
+m2s_status m2s_download_mesh_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
+    if (!c || !dst) return M2S_ERR_INVALID;
+    if (!c->mesh_frame_w) return fail(c, M2S_ERR_STATE, "no m2s_relight_mesh has run");
+    const uint64_t bytes = (uint64_t)c->mesh_frame_w * (uint64_t)c->mesh_frame_h * 4;
+    if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_mesh_frame, bytes, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

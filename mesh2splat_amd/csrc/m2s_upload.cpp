@@ -323,7 +323,7 @@ m2s_status m2s_prepare(m2s_ctx* c, uint32_t flags) {
             if (!c->h_export[k]) HIPCHK(c, hipHostMalloc((void**)&c->h_export[k], m2s_ply::kChunkRows * sizeof(m2s_gaussian), hipHostMallocDefault));
     if ((flags & M2S_PREPARE_KERNELS) && !debug_on("M2S_NO_PRELOAD")) {
         HIPCHK(c, preload_fused2()); HIPCHK(c, preload_fused3()); HIPCHK(c, preload_sparse()); HIPCHK(c, preload_multipass());
-        HIPCHK(c, preload_export()); HIPCHK(c, preload_prepass()); HIPCHK(c, preload_sort()); HIPCHK(c, preload_splat()); HIPCHK(c, preload_light()); HIPCHK(c, preload_meshdepth()); HIPCHK(c, preload_meshrender());
+        HIPCHK(c, preload_export()); HIPCHK(c, preload_prepass()); HIPCHK(c, preload_sort()); HIPCHK(c, preload_splat()); HIPCHK(c, preload_light()); HIPCHK(c, preload_meshdepth()); HIPCHK(c, preload_meshrender()); HIPCHK(c, preload_score());
     }
     return M2S_OK;
 }

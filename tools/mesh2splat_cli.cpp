@@ -63,6 +63,11 @@ struct Options {
     int preview_mode = 0;                                          // --preview-mode N: 0..4 the albedo plane (as before), 5 / 6 the relit frame
     bool has_light = false;                                        // --light x,y,z[,intensity]
     double light[4] = { 0, 0, 0, 0 };
+    int score_views = 0;                                           // --score K: the fidelity score through K cameras round the scene (m2s_score_frames)
+    double score_elevation = 0.0;                                  // --score-elevation deg
+    int score_mask = 2;                                            // --score-mask 0..3
+    std::string score_map;                                         // --score-map prefix: the error maps as prefix_k.png
+    bool preview_mode_set = false;                                 // (--score lights its frames in mode 6 unless --preview-mode says otherwise)
     uint32_t R() const { return density > 0 ? (uint32_t)density : (uint32_t)(int)(16 + quality * (double)(max_res - 16)); }  // ImGuiUI.cpp:512
 };
 
@@ -74,13 +79,22 @@ void usage() {
                  "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
                  "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test] [--split-screen POS (0..1)]]\n"
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
+                 "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
                  "  dist = 1.1 * radius / tan(radians(22.5)), eye = centre + (0, 0, dist), up = (0, 1, 0), looking at centre,\n"
                  "  45 deg vertical field of view, aspect W / H, near = dist / 100, far = dist * 10.\n"
                  "--split-screen POS: the preview is the reference's split screen (m2s_mesh_render + m2s_relight_split): the source mesh left\n"
-                 "  of column (int)(POS * W), the splats right of it, two white divider columns; with --preview-mode 0..4 both sides show albedo.\n");
+                 "  of column (int)(POS * W), the splats right of it, two white divider columns; with --preview-mode 0..4 both sides show albedo.\n"
+                 "--score K [--score-elevation deg (-90 < deg < 90, default 0)] [--score-mask 0..3 (default 2)] [--score-map prefix]: how close the\n"
+                 "  splats look to the mesh.  K frames at --preview-size, lit with --preview-mode (default 6 here) and --light; per view the splat\n"
+                 "  frame is compared on the device with the mesh-lit frame of the same camera (m2s_relight_mesh, m2s_score_frames) and ONE line\n"
+                 "  `score: {...}` of JSON is printed: per view the eye and the integers of m2s_score_result, pooled (integers added) psnr_db, ssim,\n"
+                 "  coverage_iou (null where undefined or infinite).  Camera rule: view 0 is the --preview camera; view k keeps its centre, distance,\n"
+                 "  near, far and field of view, with the eye at centre + dist * (cos(el) sin(t), sin(el), cos(el) cos(t)), t = 2 pi k / K,\n"
+                 "  el = the elevation.  Mask: 0 every pixel, 1 covered by the mesh, 2 by mesh or splats, 3 by both.\n"
+                 "  --score-map: the error maps (|dR|, |dG|, |dB|, 255 on masked pixels) as prefix_k.png, top row first.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -138,20 +152,22 @@ bool write_png_rgba(const char* path, const uint8_t* rgba_bottom_up, int W, int 
     return std::fclose(f) == 0;
 }
 
-// glm::lookAt / glm::perspective in double, column-major (m[c * 4 + r]), rounded to float (tests/camera.py does the same)
-void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, float view[16], float proj[16], double eye[3], double ctr[3],
-                    double* near_p, double* far_p) {
+// The preview camera rule: the cumulative bounding box's centre, the distance that fits its sphere into a 45 degree view, the planes.
+void preview_rule(const m2s_mesh* meshes, uint32_t n_meshes, double ctr[3], double* dist, double* near_p, double* far_p) {
     double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
     for (uint32_t i = 0; i < n_meshes; ++i)
         for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], (double)meshes[i].bbox_min[k]); mx[k] = std::max(mx[k], (double)meshes[i].bbox_max[k]); }
     double d2 = 0;
     for (int k = 0; k < 3; ++k) { ctr[k] = (mn[k] + mx[k]) / 2; d2 += (mx[k] - mn[k]) * (mx[k] - mn[k]); }
     const double radius = std::sqrt(d2) / 2;
-    const double dist = 1.1 * radius / std::tan(22.5 * (M_PI / 180.0));
-    for (int k = 0; k < 3; ++k) eye[k] = ctr[k];
-    eye[2] += dist;
-    *near_p = dist / 100;
-    *far_p = dist * 10;
+    *dist = 1.1 * radius / std::tan(22.5 * (M_PI / 180.0));
+    *near_p = *dist / 100;
+    *far_p = *dist * 10;
+}
+
+// glm::lookAt(eye, ctr, (0, 1, 0)) / glm::perspective(45 degrees, W / H, near, far) in double, column-major (m[c * 4 + r]), rounded to
+// float (tests/camera.py and mesh2splat_amd/score.py: camera_from_eye do the same)
+void camera_matrices(const double eye[3], const double ctr[3], double near_p, double far_p, int W, int H, float view[16], float proj[16]) {
     // lookAt: f = normalize(ctr - eye), s = normalize(cross(f, up)), u = cross(s, f)
     double f[3] = { ctr[0] - eye[0], ctr[1] - eye[1], ctr[2] - eye[2] };
     double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
@@ -172,9 +188,18 @@ void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, flo
     for (int k = 0; k < 16; ++k) proj[k] = 0.0f;
     proj[0] = (float)(1.0 / (aspect * t));
     proj[5] = (float)(1.0 / t);
-    proj[10] = (float)(-(*far_p + *near_p) / (*far_p - *near_p));
+    proj[10] = (float)(-(far_p + near_p) / (far_p - near_p));
     proj[11] = -1.0f;
-    proj[14] = (float)(-(2.0 * *far_p * *near_p) / (*far_p - *near_p));
+    proj[14] = (float)(-(2.0 * far_p * near_p) / (far_p - near_p));
+}
+
+void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, float view[16], float proj[16], double eye[3], double ctr[3],
+                    double* near_p, double* far_p) {
+    double dist;
+    preview_rule(meshes, n_meshes, ctr, &dist, near_p, far_p);
+    for (int k = 0; k < 3; ++k) eye[k] = ctr[k];
+    eye[2] += dist;
+    camera_matrices(eye, ctr, *near_p, *far_p, W, H, view, proj);
 }
 
 // The default point light of --preview-mode 5 / 6 (tests/light_ref.py: default_light mirrors it), in double: above and to the right of the
@@ -280,6 +305,97 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     return 0;
 }
 
+// --score K: per view GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass -> GaussianShadowPass -> GaussianRelightingPass for the
+// splats, MeshRenderPass -> m2s_relight_mesh for the mesh, m2s_score_frames over the context's own buffers (Converter.score does the same)
+std::string json_num(double v) {
+    if (!std::isfinite(v)) return "null";
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+
+int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+    const int W = o.preview_w, H = o.preview_h, K = o.score_views;
+    const int mode = o.preview_mode_set ? o.preview_mode : 6;
+    double ctr[3], dist, near_p, far_p, lpos[3], inten;
+    preview_rule(meshes, n_meshes, ctr, &dist, &near_p, &far_p);
+    preview_light(meshes, n_meshes, lpos, &inten);
+    if (o.has_light) { for (int k = 0; k < 3; ++k) lpos[k] = o.light[k]; if (o.light[3] > 0) inten = o.light[3]; }
+    auto u64 = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+    auto three = [&](const uint64_t* v) { return "[" + u64(v[0]) + ", " + u64(v[1]) + ", " + u64(v[2]) + "]"; };
+    auto integers = [&](const m2s_score_result& r) {
+        const uint64_t mx[3] = { r.max_abs[0], r.max_abs[1], r.max_abs[2] };
+        return "\"pixels\": " + u64(r.pixels) + ", \"cover\": [" + u64(r.cover[0]) + ", " + u64(r.cover[1]) + ", " + u64(r.cover[2]) + ", " + u64(r.cover[3]) +
+               "], \"sse\": " + three(r.sse) + ", \"sad\": " + three(r.sad) + ", \"max_abs\": " + three(mx) + ", \"windows\": " + u64(r.windows) +
+               ", \"ssim_q32\": " + std::to_string((long long)r.ssim_q32);
+    };
+    m2s_score_result pooled;
+    std::memset(&pooled, 0, sizeof(pooled));
+    std::string views;
+    std::vector<uint8_t> map;
+    for (int v = 0; v < K; ++v) {
+        const double th = 2.0 * M_PI * v / K, el = o.score_elevation * (M_PI / 180.0);
+        const double eye[3] = { ctr[0] + dist * std::cos(el) * std::sin(th), ctr[1] + dist * std::sin(el), ctr[2] + dist * std::cos(el) * std::cos(th) };
+        m2s_prepass_params pp;
+        std::memset(&pp, 0, sizeof(pp));
+        camera_matrices(eye, ctr, near_p, far_p, W, H, pp.world_to_view, pp.view_to_clip);
+        for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
+        pp.resolution[0] = W; pp.resolution[1] = H;
+        pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
+        pp.gaussian_std = (float)o.std_dev;
+        pp.resolution_target = R;
+        m2s_light_params lp;
+        std::memset(&lp, 0, sizeof(lp));
+        for (int k = 0; k < 3; ++k) { lp.light_position[k] = (float)lpos[k]; lp.light_color[k] = 1.0f; lp.camera_position[k] = (float)eye[k]; }
+        lp.light_intensity = (float)inten;
+        lp.near_far[0] = (float)near_p; lp.near_far[1] = (float)far_p;
+        lp.render_mode = mode;
+        lp.resolution[0] = W; lp.resolution[1] = H;
+        lp.shadow_resolution = 1024;
+        uint64_t visible = 0, n = 0, skipped = 0, per_face[6], sh_skipped = 0;
+        if (m2s_prepass(ctx, &pp, nullptr, 0, &visible) != M2S_OK || m2s_sort_prepass(ctx, &n) != M2S_OK) return 1;
+        m2s_splat_params sp = { { W, H }, 0, 0 };
+        static const m2s_quad none = {};
+        if (m2s_splat(ctx, &sp, n ? nullptr : &none, 0, &skipped) != M2S_OK) return 1;        // (n = 0: cleared planes)
+        if (m2s_shadow(ctx, &pp, &lp, nullptr, 0, per_face, &sh_skipped) != M2S_OK || m2s_relight(ctx, &lp) != M2S_OK) return 1;
+        m2s_mesh_render_params mr;
+        std::memset(&mr, 0, sizeof(mr));
+        std::memcpy(mr.world_to_view, pp.world_to_view, sizeof(mr.world_to_view));
+        std::memcpy(mr.view_to_clip, pp.view_to_clip, sizeof(mr.view_to_clip));
+        std::memcpy(mr.model_to_world, pp.model_to_world, sizeof(mr.model_to_world));
+        mr.resolution[0] = W; mr.resolution[1] = H;
+        mr.near_far[0] = pp.near_far[0]; mr.near_far[1] = pp.near_far[1];
+        mr.render_mode = pp.render_mode;
+        if (m2s_mesh_render(ctx, &mr, nullptr) != M2S_OK || m2s_relight_mesh(ctx, &lp) != M2S_OK) return 1;
+        m2s_score_params sc = { { W, H }, (uint32_t)o.score_mask, o.score_map.empty() ? 0u : (uint32_t)M2S_SCORE_WANT_MAP, { 0, 0 } };
+        m2s_score_result r;
+        if (m2s_score_frames(ctx, &sc, nullptr, nullptr, nullptr, nullptr, &r) != M2S_OK) return 1;
+        if (!o.score_map.empty()) {
+            map.resize((size_t)W * H * 4);
+            if (m2s_download_score_map(ctx, map.data(), map.size()) != M2S_OK) return 1;
+            const std::string path = o.score_map + "_" + std::to_string(v) + ".png";
+            if (!write_png_rgba(path.c_str(), map.data(), W, H)) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
+        }
+        pooled.pixels += r.pixels; pooled.windows += r.windows; pooled.ssim_q32 += r.ssim_q32;
+        for (int k = 0; k < 4; ++k) pooled.cover[k] += r.cover[k];
+        for (int k = 0; k < 3; ++k) { pooled.sse[k] += r.sse[k]; pooled.sad[k] += r.sad[k]; pooled.max_abs[k] = std::max(pooled.max_abs[k], r.max_abs[k]); }
+        views += std::string(v ? ", " : "") + "{\"eye\": [" + json_num(eye[0]) + ", " + json_num(eye[1]) + ", " + json_num(eye[2]) + "], \"quads\": " + u64(n) +
+                 ", " + integers(r) + "}";
+    }
+    const double sse = (double)pooled.sse[0] + (double)pooled.sse[1] + (double)pooled.sse[2];
+    const double psnr = pooled.pixels == 0 ? NAN : sse == 0 ? INFINITY : 10.0 * std::log10(65025.0 * 3.0 * (double)pooled.pixels / sse);
+    const double ssim = pooled.windows ? (double)pooled.ssim_q32 / 4294967296.0 / (double)pooled.windows : NAN;
+    const uint64_t uni = pooled.cover[1] + pooled.cover[2] + pooled.cover[3];
+    const double iou = uni ? (double)pooled.cover[3] / (double)uni : NAN;
+    std::printf("score: {\"views\": %d, \"size\": [%d, %d], \"density\": %u, \"mask\": %d, \"mode\": %d, \"elevation\": %s, \"centre\": [%s, %s, %s], \"near\": %s, "
+                "\"far\": %s, \"light\": {\"position\": [%s, %s, %s], \"intensity\": %s}, \"per_view\": [%s], \"pooled\": {\"psnr_db\": %s, \"ssim\": %s, "
+                "\"coverage_iou\": %s, %s}}\n",
+                K, W, H, R, o.score_mask, mode, json_num(o.score_elevation).c_str(), json_num(ctr[0]).c_str(), json_num(ctr[1]).c_str(), json_num(ctr[2]).c_str(),
+                json_num(near_p).c_str(), json_num(far_p).c_str(), json_num(lpos[0]).c_str(), json_num(lpos[1]).c_str(), json_num(lpos[2]).c_str(),
+                json_num(inten).c_str(), views.c_str(), json_num(psnr).c_str(), json_num(ssim).c_str(), json_num(iou).c_str(), integers(pooled).c_str());
+    return 0;
+}
+
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
@@ -319,6 +435,11 @@ int convert_one(const Options& o) {
         const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
         if (pr == 1) return die("preview");
         if (pr) { m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; }
+    }
+    if (o.score_views > 0) {
+        const int sr = write_score(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
+        if (sr == 1) return die("score");
+        if (sr) { m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; }
     }
     const auto t4 = Clock::now();
     std::printf("%s: %u mesh(es), %llu triangles, density %u -> %llu Gaussians (%llu stored) -> %s (format %ld)\n", o.in.c_str(),
@@ -645,7 +766,11 @@ int main(int argc, char** argv) {
         else if (a == "--preview") o.preview = next();
         else if (a == "--mesh-depth-test") o.mesh_depth_test = true;
         else if (a == "--split-screen") { o.split_screen = std::atof(next()); if (!(o.split_screen >= 0.0 && o.split_screen <= 1.0)) { usage(); return 2; } }
-        else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
+        else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); o.preview_mode_set = true; if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
+        else if (a == "--score") { o.score_views = std::atoi(next()); if (o.score_views < 1 || o.score_views > 4096) { usage(); return 2; } }
+        else if (a == "--score-elevation") { o.score_elevation = std::atof(next()); if (!(o.score_elevation > -90.0 && o.score_elevation < 90.0)) { usage(); return 2; } }
+        else if (a == "--score-mask") { o.score_mask = std::atoi(next()); if (o.score_mask < 0 || o.score_mask > 3) { usage(); return 2; } }
+        else if (a == "--score-map") o.score_map = next();
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
             if (got < 3) { usage(); return 2; }
