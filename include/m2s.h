@@ -704,6 +704,76 @@ m2s_status m2s_download_score_map(m2s_ctx* ctx, void* dst, uint64_t capacity_byt
 /* Duration (ms) of the last profiled m2s_score_frames kernel. */
 float m2s_last_score_ms(const m2s_ctx* ctx);
 
+/* ---- the point light baked into spherical harmonics: the lit result in a standard 3DGS .ply ------------------------------------- */
+/* The format-0 .ply carries the flat albedo in f_dc and zeros in its 45 f_rest slots, so a standard 3DGS viewer shows an unlit object.
+ * m2s_bake_light evaluates the deferred shader of m2s_relight (mode 6) per GAUSSIAN instead of per pixel, for a fixed set of view
+ * directions, and projects the view-dependent colour onto the 16 real harmonics the format stores.  No counterpart in the reference.
+ * The pin (tests/bake_ref.py restates it in numpy):
+ *  - Directions: a product quadrature of n_theta Gauss-Legendre nodes in z = cos(theta) (descending) times n_phi azimuths
+ *    phi_j = 2 pi (j + 0.5) / n_phi; row t * n_phi + j holds d = (sin(theta) cos(phi), sin(theta) sin(phi), z) and the weight
+ *    w = w_GL 2 pi / n_phi (sum of w = 4 pi).  n_theta in {4, 8}, n_phi in {8, 16}, 0 = the default 8 x 16: every allowed pair
+ *    integrates a product of two degree-3 harmonics exactly (degree 6 <= 2 n_theta - 1 in z, |m| <= 6 < n_phi in phi).  Nodes, weights
+ *    and the products w B_i(d) are built on the host in double by a fixed sequence of + - * / and sqrt (Newton's iteration on P_n
+ *    from literal starting values, a fixed number of steps; the azimuths' cosines are literals), then rounded to float once:
+ *    m2s_bake_directions returns the rows (20 floats each: d.xyz, w, w B_0..15), mesh2splat_amd/bake.py builds the same bits.
+ *  - Basis, the 3DGS convention colour(dir) = 0.5 + sum_i sh_i B_i(dir), dir = normalize(ws - camera): B_0 = C0; B_1..3 = -C1 y,
+ *    C1 z, -C1 x; B_4..8 = C2[0] xy, C2[1] yz, C2[2] ((2zz - xx) - yy), C2[3] xz, C2[4] (xx - yy); B_9..15 = C3[0] y (3xx - yy),
+ *    C3[1] (xy) z, C3[2] y ((4zz - xx) - yy), C3[3] z ((2zz - 3xx) - 3yy), C3[4] x ((4zz - xx) - yy), C3[5] z (xx - yy),
+ *    C3[6] x (xx - 3yy); C0 = 0.28209479177387814, C1 = 0.4886025119029199, C2 = {1.0925484305920792, -1.0925484305920792,
+ *    0.31539156525252005, -1.0925484305920792, 0.5462742152960396}, C3 = {-0.5900435899266435, 2.890611442640554,
+ *    -0.4570457994644658, 0.3731763325901154, -0.4570457994644658, 1.445305721320277, -0.5900435899266435}.
+ *  - Coefficient: sh_i[c] = sum_k (w_k B_i(d_k)) (L_c(V = -d_k) - 0.5), fp32, one rounding per operation, in table order.  A colour
+ *    that does not depend on V gives sh_0 = (c - 0.5) / C0 — what m2s_write_ply writes — and zeros (to rounding) above it.
+ *  - Per record: ws = model_to_world * (P, 1); N = normalize(normalWs), normalWs = (transpose(inverse(model_to_world)) * vec4(normal.xyz,
+ *    1)).xyz exactly as m2s_prepass computes it (gaussianSplattingPrepassCS.glsl:119, including the vec4's w of 1); albedo =
+ *    min(max(color.rgb, 0), 1) (a NaN channel becomes 0); roughness = pbr[1]; metallic = pbr[0], or 0 with viewer_metallic (what the
+ *    viewer's frame shows: its shader reads the G-buffer's always-zero B channel, see m2s_relight).
+ *  - L(V): mode 6 of m2s_relight as written — the 22/7 macro, 0.3 albedo ambient, c / (c + 1) and the 1 / 2.2 power — with position
+ *    ws, normal N and V from the table instead of normalize(cam - p); value arithmetic with the device's fast log2 / exp2 / reciprocal
+ *    square root / square root.  Left as float: not clamped, not quantised.
+ *  - Shadow factor: decision arithmetic, the 20 taps, cube-texel rule and comparison of m2s_relight taken ONCE per record from ws
+ *    (count / 20); with use_shadows = 0 the factor is 0 and no cube is read.
+ *  - degree 0..3: the coefficients i >= (degree + 1)^2 are written as +0.0; the others are the same bits at every degree.
+ *  - One lane per record, no atomics: two calls give the same bytes.
+ * The result is the context's coefficient plane float[n][48], per record f_dc[3], then f_rest[45] channel-major as the .ply orders
+ * them (f_rest_{15 c + i - 1} for channel c, coefficient i = 1..15); with want_shadow_counts also uint8[n], the tap counts.
+ * d_records == NULL: the context's records (n ignored), as m2s_shadow.  `light`: light_position, light_color, light_intensity and
+ * near_far[1] are read; the cube is the context's (m2s_shadow / m2s_upload_shadow_cubemap), whatever its S.
+ * Synchronous.  Errors: M2S_ERR_INVALID for degree > 3, a node count not listed above, reserved != 0; M2S_ERR_STATE without records,
+ * or without a cube when use_shadows is set; M2S_ERR_CAPACITY beyond 2^32-1 records. */
+typedef struct m2s_bake_params {
+    float model_to_world[16];    /* column-major, as m2s_prepass_params */
+    uint32_t degree;             /* 0..3 */
+    uint32_t n_theta, n_phi;     /* 4 | 8, 8 | 16; 0 = the default 8 x 16 */
+    uint32_t use_shadows;        /* 0: shadow factor 0, no cube needed */
+    uint32_t viewer_metallic;    /* != 0: metallic 0, as the viewer's frame */
+    uint32_t want_shadow_counts; /* also keep the per-record count of shadowed taps (0..20) */
+    uint32_t reserved;           /* 0 */
+} m2s_bake_params;
+m2s_status m2s_bake_light(m2s_ctx* ctx, const m2s_bake_params* params, const m2s_light_params* light, const void* d_records, uint64_t n);
+/* The table of an allowed (n_theta, n_phi) (0 = default): n_theta * n_phi rows of 20 floats.  Host only. */
+m2s_status m2s_bake_directions(uint32_t n_theta, uint32_t n_phi, float* out, uint64_t capacity_floats);
+/* The plane of the last m2s_bake_light: float[n][48] on the device.  NULL before any. */
+const void* m2s_device_sh(const m2s_ctx* ctx);
+m2s_status m2s_download_sh(m2s_ctx* ctx, float* dst, uint64_t capacity_records);
+/* uint8[n]: the tap counts of the last m2s_bake_light (want_shadow_counts); M2S_ERR_STATE otherwise. */
+m2s_status m2s_download_bake_shadow_counts(m2s_ctx* ctx, uint8_t* dst, uint64_t capacity_bytes);
+/* Duration (ms) of the last profiled m2s_bake_light kernel. */
+float m2s_last_bake_ms(const m2s_ctx* ctx);
+/* What a standard 3DGS viewer shows of the baked records from `camera_position`: record i of d_records (NULL: the context's, n ignored;
+ * n must be the plane's) is copied to d_dst[i] (96 bytes each, a device buffer of the caller's) with color.rgb replaced by
+ * max(0, ((0.5 + sh_0 B_0) + sh_1 B_1) + ... + sh_15 B_15) per channel — fp32, one rounding per operation, B(dir) with
+ * dir = (ws - camera) * rsq(|ws - camera|^2) (the device's fast reciprocal square root), max keeps a NaN (a record AT the camera
+ * gives NaN).  color.a and every other field are copied bit for bit.  M2S_ERR_STATE without a plane of n records. */
+m2s_status m2s_sh_shade_records(m2s_ctx* ctx, const float model_to_world[16], const float camera_position[3], const void* d_records,
+                                uint64_t n, void* d_dst);
+/* Format-0 rows as m2s_write_ply writes them, except that the 48 floats f_dc_0..2, f_rest_0..44 of row i are sh[48 i .. 48 i + 47] as
+ * given.  Host only. */
+m2s_status m2s_write_ply_sh(const char* path, const m2s_gaussian* records, const float* sh, uint64_t n, float scale_multiplier);
+/* The context's records and its baked plane as such a file (scale multiplier gaussian_std / R, as m2s_export_ply).  M2S_ERR_STATE
+ * when no conversion has run, no plane exists or the plane's n is not the records'. */
+m2s_status m2s_export_ply_sh(m2s_ctx* ctx, const char* path, float gaussian_std);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what

@@ -46,6 +46,8 @@ EXPORTS = (
     "m2s_last_mesh_render_stage_ms", "m2s_last_mesh_render_counts", "m2s_relight_split",
     "m2s_relight_mesh", "m2s_device_mesh_frame", "m2s_download_mesh_frame", "m2s_score_frames", "m2s_device_score_map",
     "m2s_download_score_map", "m2s_last_score_ms",
+    "m2s_bake_light", "m2s_bake_directions", "m2s_device_sh", "m2s_download_sh", "m2s_download_bake_shadow_counts", "m2s_last_bake_ms",
+    "m2s_sh_shade_records", "m2s_write_ply_sh", "m2s_export_ply_sh",
 )
 
 
@@ -235,6 +237,15 @@ def load():
         "m2s_device_score_map": (vp, [vp]),
         "m2s_download_score_map": (C.c_int, [vp, vp, u64]),
         "m2s_last_score_ms": (C.c_float, [vp]),
+        "m2s_bake_light": (C.c_int, [vp, vp, vp, vp, u64]),
+        "m2s_bake_directions": (C.c_int, [u32, u32, vp, u64]),
+        "m2s_device_sh": (vp, [vp]),
+        "m2s_download_sh": (C.c_int, [vp, vp, u64]),
+        "m2s_download_bake_shadow_counts": (C.c_int, [vp, vp, u64]),
+        "m2s_last_bake_ms": (C.c_float, [vp]),
+        "m2s_sh_shade_records": (C.c_int, [vp, vp, vp, vp, u64, vp]),
+        "m2s_write_ply_sh": (C.c_int, [C.c_char_p, vp, vp, u64, C.c_float]),
+        "m2s_export_ply_sh": (C.c_int, [vp, C.c_char_p, C.c_float]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -85,6 +85,7 @@ class Converter:
     _nonnull = C.c_uint64(0)      # a non-NULL address for "n = 0 records at this pointer"
     _last_shadow_S = 0            # side of the context's shadow cube (0: none yet)
     _last_splat_wh = (0, 0)       # W x H of the context's G-buffer
+    _last_bake_n = 0              # records of the context's baked plane
 
     def _check(self, st: int):
         if st != _lib.M2S_OK:
@@ -604,6 +605,108 @@ class Converter:
             self.mesh_render(prepass_params, download=False)
             return self.relight_split(light_params, split_screen, download=download)
         return self.relight(light_params, download=download)
+
+    # -- the light baked into spherical harmonics -----------------------------------------------------
+    def _records_arg(self, records):
+        """(pointer, n) of `records` (None: the context's; else a contiguous CUDA torch tensor (n, 24) float32) for the C entry points."""
+        if records is None:
+            return None, 0
+        if not (hasattr(records, "data_ptr") and records.is_cuda and records.is_contiguous()):
+            raise ValueError("records must be a contiguous CUDA tensor (n, 24) float32")
+        n = int(records.shape[0])
+        return (records.data_ptr() if n else C.addressof(self._nonnull)), n
+
+    def bake_light(self, bake_params, light_params, records=None, download: bool = True):
+        """m2s_bake_light: the deferred shader per Gaussian over a fixed table of view directions, projected onto the 16 harmonics of
+        the standard .ply.  `bake_params`: mesh2splat_amd.bake.BakeParams, `light_params`: mesh2splat_amd.light.LightParams (position,
+        colour, intensity, far plane); the cube is the context's (shadow() / upload_shadow_cubemap()).  -> the plane (n, 48) float32
+        (with want_shadow_counts: (plane, counts (n,) uint8)); download=False: None (device_sh)."""
+        from . import bake as _bk, light as _li
+        bc, lc = _bk.to_c(bake_params), _li.to_c(light_params)
+        ptr, n = self._records_arg(records)
+        self._check(self._L.m2s_bake_light(self._h, C.byref(bc), C.byref(lc), ptr, n))
+        self._last_bake_n = n if records is not None else self.num_stored
+        if not download:
+            return None
+        sh = self.download_sh()
+        if bc.want_shadow_counts:
+            counts = np.empty(self._last_bake_n, np.uint8)
+            self._check(self._L.m2s_download_bake_shadow_counts(self._h, counts.ctypes.data if counts.size else None, counts.size))
+            return sh, counts
+        return sh
+
+    def download_sh(self) -> np.ndarray:
+        """The plane of the last bake_light(): (n, 48) float32 — f_dc[3], then f_rest[45] channel-major."""
+        sh = np.empty((self._last_bake_n, 48), np.float32)
+        self._check(self._L.m2s_download_sh(self._h, sh.ctypes.data if sh.size else None, sh.shape[0]))
+        return sh
+
+    @property
+    def device_sh(self) -> int:
+        return int(self._L.m2s_device_sh(self._h) or 0)
+
+    @property
+    def last_bake_ms(self) -> float:
+        return float(self._L.m2s_last_bake_ms(self._h))
+
+    def sh_shade_records(self, model_mat, camera_position, records=None, out=None):
+        """m2s_sh_shade_records: the records (None: the context's) with color.rgb replaced by what a standard 3DGS viewer shows of the
+        baked plane from `camera_position`.  -> a CUDA torch tensor (n, 24) float32 (`out`, when given)."""
+        import torch
+        ptr, n = self._records_arg(records)
+        if records is None:
+            n = self.num_stored
+        if out is None:
+            out = torch.empty((n, RECORD_FLOATS), dtype=torch.float32, device="cuda")
+        if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * RECORD_FLOATS):
+            raise ValueError("out must be a contiguous CUDA float32 tensor of n x 24 floats")
+        torch.cuda.current_stream().synchronize()          # the context's stream does not wait for torch's
+        m = (C.c_float * 16)(*np.ascontiguousarray(model_mat, np.float32).reshape(16).tolist())
+        cam = (C.c_float * 3)(*[float(np.float32(v)) for v in camera_position])
+        self._check(self._L.m2s_sh_shade_records(self._h, m, cam, ptr, n, out.data_ptr() if n else None))
+        return out
+
+    def export_ply_sh(self, path: str, gaussian_std: float = 0.65):
+        """m2s_export_ply_sh: the context's records with the baked plane as a standard (format 0) .ply."""
+        self._check(self._L.m2s_export_ply_sh(self._h, os.fsencode(path), float(gaussian_std)))
+
+    def render_baked(self, prepass_params, download: bool = True):
+        """What a standard 3DGS viewer shows of the baked records through `prepass_params`'s camera: sh_shade_records() from the camera
+        position (the view matrix inverted), the viewer prepass in render mode 0 over the shaded copy, depth sort, splat.  -> the albedo
+        attachment (H, W, 4) uint8, row 0 = bottom (download=False: None; it stays on the device: device_gbuffer(2))."""
+        import dataclasses
+        from .splat import SplatParams
+        V = np.asarray(prepass_params.view_mat, np.float64).reshape(4, 4).T           # glm's memory order -> math order
+        cam = -(V[:3, :3].T @ V[:3, 3])                                               # rigid view matrix: eye = -R^T t
+        shaded = self.sh_shade_records(prepass_params.model_mat, cam)
+        pp = dataclasses.replace(prepass_params, render_mode=0)
+        res = tuple(int(v) for v in pp.renderer_resolution)
+        self.prepass(pp, records=shaded, download=False)
+        if self.sort_prepass(download=False):
+            self.splat(SplatParams(res, 0), download=False)
+        else:                                                                         # nothing visible: cleared planes
+            import torch
+            self.splat(SplatParams(res, 0), quads=torch.empty((0, 24), dtype=torch.float32, device="cuda"), download=False)
+        del shaded
+        if not download:
+            return None
+        alb = np.empty((res[1], res[0], 4), np.uint8)
+        self._check(self._L.m2s_download_gbuffer(self._h, 2, alb.ctypes.data, alb.nbytes))
+        return alb
+
+    def score_baked(self, prepass_params, light_params):
+        """How close the baked export looks to the viewer's own lit frame through one camera: m2s_score_frames between the lit splat
+        frame of render_frame() (image A) and render_baked()'s albedo attachment used as a frame (image B), over the pixels the splats
+        cover (the attachment's accumulated alpha; both renders draw the same quads).  Nothing but the result leaves the device.
+        -> ScoreResult (mean squared error per channel value: sum(sse) / (3 * pixels))."""
+        from . import score as _sc
+        res = tuple(int(v) for v in prepass_params.renderer_resolution)
+        self.render_frame(prepass_params, light_params, download=False)               # the frame has its own buffer ...
+        self.render_baked(prepass_params, download=False)                             # ... so this splat leaves it as it is
+        W, H = res
+        baked = _DeviceImage(self.device_gbuffer(2), H, W)
+        return self.score_frames(_sc.ScoreParams(res, _sc.MASK_A_AND_B, False, False),
+                                 a=_DeviceImage(self.device_frame, H, W), b=baked, cover_a=baked, cover_b=baked)
 
     # -- fidelity score ----------------------------------------------------------------------------
     def relight_mesh(self, light_params, download: bool = True):

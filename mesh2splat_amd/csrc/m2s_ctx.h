@@ -7,6 +7,7 @@
 //   m2s_meshdepth.cpp  the mesh depth prepass (== DepthPrepass::execute)
 //   m2s_meshrender.cpp the mesh render pass (== MeshRenderPass::execute) and the mesh G-buffer
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
+//   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_device.h"
@@ -270,6 +271,18 @@ struct m2s_ctx {
     int32_t score_map_w = 0, score_map_h = 0;    // 0: the last m2s_score_frames kept no map
     hipEvent_t score_ev[2] = {};
     float last_score_ms = 0.0f;
+
+    // light baked into spherical harmonics (m2s_bake.cpp): the coefficient plane, the optional tap counts, the quadrature table
+    float* d_sh = nullptr;                       // float[n][48]: f_dc[3], f_rest[45] channel-major
+    uint64_t sh_cap = 0, sh_n = 0;               // records it has room for / holds
+    bool sh_valid = false;                       // a bake has completed since the plane was last (re)allocated
+    uint8_t* d_bake_counts = nullptr;            // uint8[n]
+    uint64_t bake_counts_cap = 0;
+    bool bake_has_counts = false;
+    float* d_bake_table = nullptr;               // n_theta * n_phi rows of kBakeTableRow floats
+    uint32_t bake_table_nt = 0, bake_table_np = 0;
+    hipEvent_t bake_ev[2] = {};
+    float last_bake_ms = 0.0f;
 
     // measurement
     bool profiling = false;

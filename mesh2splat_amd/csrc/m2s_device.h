@@ -287,6 +287,23 @@ hipError_t launch_relight(const RelightK& k, const void* const planes[5], const 
                           const void* const left_planes[5] = nullptr, int split_x = 0, int div_x = 0);
 hipError_t preload_light();
 
+// ---- light baked into spherical harmonics (m2s_bake.hip): the deferred shader per Gaussian, projected onto the 16 harmonics of the .ply ----
+struct BakeK {
+    float M[16], MinvT[16];     // u_modelToWorld, transpose(inverse(u_modelToWorld)): PrepassK's
+    float light[3], color[3];
+    float intensity, far_plane;
+    int32_t S;                  // side of a cube face (0 without shadows)
+    uint32_t n_dirs;            // rows of the table: n_theta * n_phi
+    uint32_t n_coef;            // (degree + 1)^2: coefficients kept per channel
+    uint32_t use_shadows, viewer_metallic;
+};
+struct ShadeK { float M[16]; float cam[3]; };
+constexpr int kBakeTableRow = 20;   // floats per direction: d.xyz, w, w * B_0..15
+// plane: float[n][48] (f_dc[3], f_rest[45] channel-major); counts (or NULL): uint8[n], the 20-tap counts
+hipError_t launch_bake_sh(const BakeK& k, const float4* rec, uint32_t n, const float* table, const float* cube, float* plane, uint8_t* counts,
+                          hipStream_t st);
+hipError_t launch_sh_shade(const ShadeK& k, const float4* rec, const float* sh, uint32_t n, float4* dst, hipStream_t st);
+
 // ---- mesh depth prepass (m2s_meshdepth.hip): DepthPrepass over the uploaded scene's position planes -------------------------------
 struct MeshDepthK {
     float PVM[16];      // (view_to_clip * world_to_view) * model_to_world, fp32 in glm's order (m2s_meshdepth.cpp), column-major

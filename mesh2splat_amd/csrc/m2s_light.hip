@@ -38,6 +38,7 @@
 #include "m2s_quadraster.h"
 #include "m2s_viewmath.h"
 #include "m2s_covmath.h"
+#include "m2s_lightmath.h"
 
 #pragma clang fp contract(off)
 
@@ -246,31 +247,6 @@ __global__ void __launch_bounds__(256) k_shadow_tiles(const float4* __restrict__
 // ---- relighting --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float half_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xFFFFu)); }
 __device__ __forceinline__ float half_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
-// value arithmetic: the device's fast log2 / exp2 / reciprocal square root
-__device__ __forceinline__ float pow_fast(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-    const float r = __builtin_amdgcn_rsqf(dot3(x, y, z, x, y, z));
-    x *= r; y *= r; z *= r;
-}
-__device__ __forceinline__ float max0(float v) { return v > 0.0f ? v : (v == v ? 0.0f : v); }      // max(v, 0.0) with NaN kept
-
-// texture(u_shadowCubemap, v).r: OpenGL 4.6 table 8.19, GL_NEAREST, clamp to edge; a NaN coordinate reads texel 0 of face 5
-__device__ __forceinline__ float cube_fetch(const float* __restrict__ cube, int S, float x, float y, float z) {
-    const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
-    int face;
-    float sc, tc, ma;
-    if (ax >= ay && ax >= az) { ma = ax; if (x < 0.0f) { face = 1; sc = z; tc = -y; } else { face = 0; sc = -z; tc = -y; } }
-    else if (ay >= az) { ma = ay; if (y < 0.0f) { face = 3; sc = x; tc = -z; } else { face = 2; sc = x; tc = z; } }
-    else { ma = az; if (z < 0.0f) { face = 5; sc = -x; tc = -y; } else { face = 4; sc = x; tc = -y; } }
-    const float s = 0.5f * (sc / ma + 1.0f), t = 0.5f * (tc / ma + 1.0f);
-    const size_t SS = (size_t)S * (size_t)S;
-    if (s != s || t != t) return cube[5 * SS];
-    const float fs = floorf(s * (float)S), ft = floorf(t * (float)S), hi = (float)(S - 1);
-    const int i = (int)fminf(fmaxf(fs, 0.0f), hi), j = (int)fminf(fmaxf(ft, 0.0f), hi);
-    return cube[(size_t)face * SS + (size_t)j * (size_t)S + (size_t)i];
-}
-
 // kSplit (GaussianRelightingPass.cpp:90-135): pixels left of split_x are lit from the second set of planes (the mesh G-buffer), the
 // two divider columns from div_x on are white; everything else is the one shader.
 struct RelightPlanes { const uint2* pos; const uint2* nrm; const uint32_t* alb; const uint32_t* mr; };
@@ -305,23 +281,7 @@ __global__ void __launch_bounds__(256) k_relight(const RelightK k, const uint2* 
     float N0 = half_lo(nn.x) * 2.0f - 1.0f, N1 = half_hi(nn.x) * 2.0f - 1.0f, N2 = half_lo(nn.y) * 2.0f - 1.0f;   // :126
     normalize3(N0, N1, N2);
     // ---- computeShadowFactor (:70-99): decision arithmetic, IEEE fp32 operation by operation
-    uint32_t count = 0;
-    {
-        const float dx = p0 - k.light[0], dy = p1 - k.light[1], dz = p2 - k.light[2];
-        const float cur = sqrtf((dx * dx + dy * dy) + dz * dz);
-        const float sx = dx / cur, sy = dy / cur, sz = dz / cur;
-        const float lhs = cur - 0.05f;
-        // sampleOffsetDirections, two bits per component (0: 0, 1: +1, 2: -1)
-        constexpr int8_t OFF[20][3] = { { 1, 1, 1 }, { 1, -1, 1 }, { -1, -1, 1 }, { -1, 1, 1 }, { 1, 1, -1 }, { 1, -1, -1 }, { -1, -1, -1 }, { -1, 1, -1 },
-                                        { 1, 1, 0 }, { 1, -1, 0 }, { -1, -1, 0 }, { -1, 1, 0 }, { 1, 0, 1 }, { -1, 0, 1 }, { 1, 0, -1 }, { -1, 0, -1 },
-                                        { 0, 1, 1 }, { 0, -1, 1 }, { 0, -1, -1 }, { 0, 1, -1 } };
-#pragma unroll
-        for (int i = 0; i < 20; ++i) {
-            const float vx = sx + (float)OFF[i][0] * 0.025f, vy = sy + (float)OFF[i][1] * 0.025f, vz = sz + (float)OFF[i][2] * 0.025f;
-            const float closest = cube_fetch(cube, k.S, vx, vy, vz) * k.far_plane;
-            count += lhs > closest ? 1u : 0u;
-        }
-    }
+    const uint32_t count = shadow_taps(cube, k.S, p0, p1, p2, k.light[0], k.light[1], k.light[2], k.far_plane);
     if (counts) counts[px] = (uint8_t)count;
     const float shadow = (float)count / 20.0f;
     // ---- the rest of main() (:130-164): value arithmetic

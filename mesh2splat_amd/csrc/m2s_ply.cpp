@@ -66,7 +66,7 @@ Format describe(uint32_t format) {
 
 inline uint8_t* put(uint8_t* p, float v) { std::memcpy(p, &v, 4); return p + 4; }
 
-void encode_rows(const m2s_gaussian* g, size_t n, uint32_t format, float sm, uint8_t* p) {
+void encode_rows(const m2s_gaussian* g, size_t n, uint32_t format, float sm, uint8_t* p, const float* sh) {
     for (size_t i = 0; i < n; ++i, ++g) {
         if (format == 2) {
             p = put(p, g->position[0]); p = put(p, g->position[1]); p = put(p, g->position[2]);
@@ -95,9 +95,12 @@ void encode_rows(const m2s_gaussian* g, size_t n, uint32_t format, float sm, uin
         }
         p = put(p, g->position[0]); p = put(p, g->position[1]); p = put(p, g->position[2]);
         p = put(p, g->normal[0]); p = put(p, g->normal[1]); p = put(p, g->normal[2]);
-        for (int k = 0; k < 3; ++k) p = put(p, (g->color[k] - 0.5f) / kShC0);  // utils.cpp:45-49
-        if (format == 1) { p = put(p, g->pbr[0]); p = put(p, g->pbr[1]); }
-        else { std::memset(p, 0, 45 * 4); p += 45 * 4; }
+        if (sh) { std::memcpy(p, sh + i * 48, 48 * 4); p += 48 * 4; }           // format 0 with baked coefficients: f_dc[3], f_rest[45]
+        else {
+            for (int k = 0; k < 3; ++k) p = put(p, (g->color[k] - 0.5f) / kShC0);  // utils.cpp:45-49
+            if (format == 1) { p = put(p, g->pbr[0]); p = put(p, g->pbr[1]); }
+            else { std::memset(p, 0, 45 * 4); p += 45 * 4; }
+        }
         p = put(p, inv_sigmoid(g->color[3]));
         for (int k = 0; k < 3; ++k) p = put(p, std::log(g->scale[k] * sm));
         for (int k = 0; k < 4; ++k) p = put(p, g->rotation[k]);  // stored (w,x,y,z)
@@ -152,9 +155,9 @@ m2s_status Writer::append_encoded(const uint8_t* rows, size_t n_rows) {
     return ok_ ? M2S_OK : M2S_ERR_IO;
 }
 
-m2s_status Writer::append(const m2s_gaussian* records, size_t rows) {
+m2s_status Writer::append(const m2s_gaussian* records, size_t rows, const float* sh) {
     if (!f_) return M2S_ERR_STATE;
-    if (rows && !records) return M2S_ERR_INVALID;
+    if ((rows && !records) || (sh && format_ != 0)) return M2S_ERR_INVALID;
     const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     for (size_t r0 = 0; ok_ && r0 < rows; r0 += kChunkRows) {
         const size_t n = std::min(kChunkRows, rows - r0);
@@ -164,9 +167,9 @@ m2s_status Writer::append(const m2s_gaussian* records, size_t rows) {
         std::vector<std::thread> pool;
         for (unsigned t = 1; t < nt; ++t) {
             const size_t a = n * t / nt, b = n * (t + 1) / nt;
-            pool.emplace_back(encode_rows, records + r0 + a, b - a, format_, sm_, buf.data() + a * row_bytes_);
+            pool.emplace_back(encode_rows, records + r0 + a, b - a, format_, sm_, buf.data() + a * row_bytes_, sh ? sh + (r0 + a) * 48 : nullptr);
         }
-        encode_rows(records + r0, n / nt, format_, sm_, buf.data());
+        encode_rows(records + r0, n / nt, format_, sm_, buf.data(), sh ? sh + r0 * 48 : nullptr);
         for (auto& th : pool) th.join();
         if (pending_.valid()) ok_ = pending_.get() && ok_;       // the OTHER buffer has reached the file
         FILE* f = f_;

@@ -24,7 +24,9 @@ public:
     // returns once `rows` has been read completely
     m2s_status append_encoded(const uint8_t* rows, size_t n_rows);
     size_t row_bytes() const { return row_bytes_; }
-    m2s_status append(const m2s_gaussian* records, size_t rows);   // returns once `records` has been read completely
+    // returns once `records` has been read completely.  sh (or NULL; format 0 only): float[rows][48], the row's f_dc[3] and f_rest[45]
+    // as given instead of the flat colour and zeros (m2s_write_ply_sh)
+    m2s_status append(const m2s_gaussian* records, size_t rows, const float* sh = nullptr);
     m2s_status close();                                            // flushes; M2S_ERR_IO if anything failed or rows are missing
 
 private:

@@ -62,6 +62,8 @@ struct Options {
     double split_screen = -1.0;                                    // --split-screen POS: the preview is the split screen, mesh left of POS * W (m2s_mesh_render + m2s_relight_split)
     int preview_mode = 0;                                          // --preview-mode N: 0..4 the albedo plane (as before), 5 / 6 the relit frame
     bool has_light = false;                                        // --light x,y,z[,intensity]
+    bool bake_light = false;                                       // --bake-light: shadow + m2s_bake_light, the .ply carries the lit result (m2s_export_ply_sh)
+    int bake_degree = 3;                                           // --bake-degree 0..3
     double light[4] = { 0, 0, 0, 0 };
     int score_views = 0;                                           // --score K: the fidelity score through K cameras round the scene (m2s_score_frames)
     double score_elevation = 0.0;                                  // --score-elevation deg
@@ -80,6 +82,7 @@ void usage() {
                  "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test] [--split-screen POS (0..1)]]\n"
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
+                 "         [--bake-light [--bake-degree 0..3]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -94,7 +97,11 @@ void usage() {
                  "  coverage_iou (null where undefined or infinite).  Camera rule: view 0 is the --preview camera; view k keeps its centre, distance,\n"
                  "  near, far and field of view, with the eye at centre + dist * (cos(el) sin(t), sin(el), cos(el) cos(t)), t = 2 pi k / K,\n"
                  "  el = the elevation.  Mask: 0 every pixel, 1 covered by the mesh, 2 by mesh or splats, 3 by both.\n"
-                 "  --score-map: the error maps (|dR|, |dG|, |dB|, 255 on masked pixels) as prefix_k.png, top row first.\n");
+                 "  --score-map: the error maps (|dR|, |dG|, |dB|, 255 on masked pixels) as prefix_k.png, top row first.\n"
+                 "--bake-light [--bake-degree 0..3 (default 3)]: --format 0 only, one GPU, one file.  After the conversion the shadow pass\n"
+                 "  (cube 1024, quads sized for --preview-size, the --preview camera's near / far) and m2s_bake_light with --light (default: the\n"
+                 "  preview light); the .ply's f_dc / f_rest carry the lit, shadowed colour as spherical harmonics (m2s_export_ply_sh), so a\n"
+                 "  standard 3DGS viewer shows the light.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -305,6 +312,43 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     return 0;
 }
 
+// --bake-light: GaussianShadowPass of the converted records (per-record fields as --preview's: identity model matrix, quads sized for
+// --preview-size, the preview camera's near / far), then m2s_bake_light; the plane stays in the context for m2s_export_ply_sh
+int bake_light(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+    const int W = o.preview_w, H = o.preview_h;
+    m2s_prepass_params pp;
+    std::memset(&pp, 0, sizeof(pp));
+    double eye[3], ctr[3], near_p, far_p;
+    preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p);
+    for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
+    pp.resolution[0] = W; pp.resolution[1] = H;
+    pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
+    pp.gaussian_std = (float)o.std_dev;
+    pp.resolution_target = R;
+    m2s_light_params lp;
+    std::memset(&lp, 0, sizeof(lp));
+    double lpos[3], inten;
+    preview_light(meshes, n_meshes, lpos, &inten);
+    if (o.has_light) { for (int k = 0; k < 3; ++k) lpos[k] = o.light[k]; if (o.light[3] > 0) inten = o.light[3]; }
+    for (int k = 0; k < 3; ++k) { lp.light_position[k] = (float)lpos[k]; lp.light_color[k] = 1.0f; lp.camera_position[k] = (float)eye[k]; }
+    lp.light_intensity = (float)inten;
+    lp.near_far[0] = (float)near_p; lp.near_far[1] = (float)far_p;
+    lp.render_mode = 6;
+    lp.resolution[0] = W; lp.resolution[1] = H;
+    lp.shadow_resolution = 1024;
+    uint64_t per_face[6], sh_skipped = 0;
+    if (m2s_shadow(ctx, &pp, &lp, nullptr, 0, per_face, &sh_skipped) != M2S_OK) return 1;
+    m2s_bake_params bp;
+    std::memset(&bp, 0, sizeof(bp));
+    for (int k = 0; k < 4; ++k) bp.model_to_world[k * 5] = 1.0f;
+    bp.degree = (uint32_t)o.bake_degree;
+    bp.use_shadows = 1;
+    if (m2s_bake_light(ctx, &bp, &lp, nullptr, 0) != M2S_OK) return 1;
+    std::printf("bake light: position=%.17g,%.17g,%.17g intensity=%.17g near=%.17g far=%.17g size=%dx%d shadow=1024 degree=%d\n", lpos[0], lpos[1],
+                lpos[2], inten, near_p, far_p, W, H, o.bake_degree);
+    return 0;
+}
+
 // --score K: per view GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass -> GaussianShadowPass -> GaussianRelightingPass for the
 // splats, MeshRenderPass -> m2s_relight_mesh for the mesh, m2s_score_frames over the context's own buffers (Converter.score does the same)
 std::string json_num(double v) {
@@ -430,7 +474,10 @@ int convert_one(const Options& o) {
     const uint32_t R = o.R();
     if (m2s_convert(ctx, R, &total) != M2S_OK) return die("convert");
     const auto t3 = Clock::now();
-    if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
+    if (o.bake_light) {
+        if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
+        if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
+    } else if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
     if (!o.preview.empty()) {
         const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
         if (pr == 1) return die("preview");
@@ -771,6 +818,8 @@ int main(int argc, char** argv) {
         else if (a == "--score-elevation") { o.score_elevation = std::atof(next()); if (!(o.score_elevation > -90.0 && o.score_elevation < 90.0)) { usage(); return 2; } }
         else if (a == "--score-mask") { o.score_mask = std::atoi(next()); if (o.score_mask < 0 || o.score_mask > 3) { usage(); return 2; } }
         else if (a == "--score-map") o.score_map = next();
+        else if (a == "--bake-light") o.bake_light = true;
+        else if (a == "--bake-degree") { o.bake_degree = std::atoi(next()); if (o.bake_degree < 0 || o.bake_degree > 3) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
             if (got < 3) { usage(); return 2; }
@@ -784,6 +833,8 @@ int main(int argc, char** argv) {
         else pos.push_back(a);
     }
     if (o.gpus < 1 || o.gpus > 64) { usage(); return 2; }
+    // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
+    if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
         if (o.out_dir.empty() || !pos.empty()) { usage(); return 2; }
         return convert_batch(o);
