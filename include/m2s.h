@@ -355,6 +355,16 @@ float m2s_last_sort_prepass_ms(const m2s_ctx* ctx);
  * leaves there, byte for byte; *out_visible = their number.  params->arrival_order is ignored (the order IS the result); the unsorted quads
  * of m2s_prepass are not produced.  m2s_last_sort_stage_ms: [0] keys, [1] radix sort, [2] the prepass through the permutation. */
 m2s_status m2s_prepass_sorted(m2s_ctx* ctx, const m2s_prepass_params* params, uint64_t* out_visible);
+/* uint32[visible] after m2s_prepass_sorted: entry i = the index, in the context's current records, of the record sorted quad i was made
+ * from.  Valid until the next prepass or sort of the context.  NULL after any other producer of sorted quads (m2s_sort_prepass,
+ * m2s_upload_quads), once the records changed, and when there are no sorted quads. */
+const void* m2s_device_sorted_sources(const m2s_ctx* ctx);
+/* Copies them to the host, as m2s_download_sorted_quads copies the quads.  M2S_ERR_STATE when there are none; M2S_ERR_CAPACITY when
+ * dst holds fewer entries than there are sorted quads. */
+m2s_status m2s_download_sorted_sources(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity);
+/* The counterpart of m2s_upload_quads for the sources: n host indices become the sources of the context's sorted quads.
+ * M2S_ERR_INVALID unless n is the number of sorted quads and every index is below m2s_num_stored. */
+m2s_status m2s_upload_quad_sources(m2s_ctx* ctx, const uint32_t* host_sources, uint64_t n);
 
 /* ---- splat pass == GaussianSplattingPass::execute (GaussianSplattingPass.cpp:50-95) ----------------------- */
 /* Draws one quad per entry of perQuadTransformationBufferSorted (gaussianSplattingVS.glsl:31-40) and blends the fragment shader's
@@ -403,6 +413,57 @@ float m2s_last_splat_ms(const m2s_ctx* ctx);
 m2s_status m2s_last_splat_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
 /* What the last m2s_splat did: [0] (tile, quad) pairs, [1] fragments blended (after the early exit), [2] quads skipped. */
 m2s_status m2s_last_splat_counts(const m2s_ctx* ctx, uint64_t out[3]);
+
+/* ---- contribution pass and pruning (no counterpart in the reference: it shows every Gaussian it keeps) ------------------------ */
+/* What every record of the context adds to the picture of a view, recorded instead of the picture.  The pin:
+ *  - For render modes other than 4, m2s_splat updates the albedo attachment's alpha per fragment as A3 <- unorm8(sA3 * tA + A3) with
+ *    sA3 = clamp01(a * g) and tA = 1 - A3 (the RGBA8 rule above).  The WEIGHT of a fragment is the fp32 product w = sA3 * tA of
+ *    exactly that update: what the fragment adds to the pixel's coverage before quantisation, with A3 evolving byte-quantised exactly
+ *    as in m2s_splat.
+ *  - Geometry, coverage, quad order, skipped quads and g = exp(alpha) (the device's fast exp) are all those of m2s_splat; a pixel
+ *    covered by both triangles of a quad yields two fragments.
+ *  - w is never NaN: clamp01 is fmin(fmax(x, 0), 1), which returns the other operand for a NaN, so sA3 lies in [0, 1]; tA lies in
+ *    [0, 1] because A3 is one of q / 255.  Hence 0 <= w <= 1, and non-negative floats order as their bits do as unsigned integers.
+ *  - Two accumulators per record, uint32[m2s_num_stored] each: wmax = the bits of the largest w of any fragment of any quad made from
+ *    that record; npix = the number of fragments with w > count_weight (strict: a fragment on a saturated pixel, w = 0, never counts).
+ *    An integer maximum and an integer sum: independent of the order of evaluation, identical from run to run.  They keep accumulating
+ *    over calls (views).  npix cannot overflow within 256 views: a quad's axes are capped at 1024 px by the prepass, so a quad covers at
+ *    most 2048^2 = 2^22 pixels of a view, and 256 * 2^22 = 2^30.
+ *  - A record whose every fragment has w = 0 adds nothing to the ALPHA of the albedo attachment.  It adds nothing to its colour
+ *    either — m2s_splat adds clamp01(colour * g) * tA there, and tA = 0 wherever a positive opacity gave w = 0 — with one exception:
+ *    a record whose opacity is exactly 0 (or NaN, or negative) has sA3 = 0 and w = 0 on pixels that are not saturated, where its
+ *    colour term is still added.  Such a record is invisible to the weight and is dropped by m2s_prune at min_weight = 0, which
+ *    then changes the colour of that plane.  The conversion writes the material's alpha; a .ply can hold anything.
+ * m2s_contrib_begin sizes both accumulators to the context's current records, zeroes them and ties them to those records.
+ * m2s_contrib_accumulate runs over the context's sorted quads and their sources (m2s_prepass_sorted; m2s_device_sorted_sources) at
+ * params->resolution.  It touches neither the G-buffer nor the frame.  Synchronous.  M2S_ERR_INVALID for render mode 4 (the weight is
+ * not defined there), a render mode outside 0..6, reserved != 0, a resolution outside 1..8192, missing sorted quads or sources, no
+ * m2s_contrib_begin, records that changed since it, a count_weight that is negative or not finite. */
+m2s_status m2s_contrib_begin(m2s_ctx* ctx);
+m2s_status m2s_contrib_accumulate(m2s_ctx* ctx, const m2s_splat_params* params, float count_weight);
+/* which = 0: wmax, 1: npix.  uint32[m2s_num_stored]; NULL without valid accumulators. */
+const void* m2s_device_contrib(const m2s_ctx* ctx, uint32_t which);
+/* Either destination may be NULL.  M2S_ERR_STATE without valid accumulators. */
+m2s_status m2s_download_contrib(m2s_ctx* ctx, uint32_t* dst_wmax, uint32_t* dst_npix, uint64_t capacity);
+/* Duration (ms) of the last profiled m2s_contrib_accumulate and its stages: [0] setup + bin, [1] grouping (both m2s_splat's own),
+ * [2] the contribution blend. */
+float m2s_last_contrib_ms(const m2s_ctx* ctx);
+m2s_status m2s_last_contrib_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* Keeps record i iff wmax[i] > min_weight (compared as floats) and npix[i] >= min_pixels: a stable compaction on the device into the
+ * context-owned pool.  The survivors become the context's current records, in their previous order, with the resolutionTarget kept
+ * (records adopted through m2s_set_records are compacted into the pool; the caller's memory is not written).  Cached positions, sorted
+ * quads, sources and the accumulators are invalidated.  A baked plane of these records (m2s_bake_light) is compacted with the same
+ * flags, so that m2s_export_ply_sh still matches.  *out_kept (may be NULL) = survivors.  M2S_ERR_INVALID for a NaN min_weight or
+ * reserved != 0; M2S_ERR_STATE without accumulators of the current records or with conversions in flight. */
+typedef struct m2s_prune_params {
+    float min_weight;
+    uint32_t min_pixels;
+    uint32_t reserved;      /* 0 */
+} m2s_prune_params;
+m2s_status m2s_prune(m2s_ctx* ctx, const m2s_prune_params* params, uint64_t* out_kept);
+/* The last m2s_prune: [0] records before, [1] kept, [2] dropped by weight, [3] dropped by pixels alone. */
+m2s_status m2s_last_prune_counts(const m2s_ctx* ctx, uint64_t out[4]);
+float m2s_last_prune_ms(const m2s_ctx* ctx);
 
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */

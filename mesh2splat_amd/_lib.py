@@ -48,6 +48,8 @@ EXPORTS = (
     "m2s_download_score_map", "m2s_last_score_ms",
     "m2s_bake_light", "m2s_bake_directions", "m2s_device_sh", "m2s_download_sh", "m2s_download_bake_shadow_counts", "m2s_last_bake_ms",
     "m2s_sh_shade_records", "m2s_write_ply_sh", "m2s_export_ply_sh",
+    "m2s_device_sorted_sources", "m2s_download_sorted_sources", "m2s_upload_quad_sources", "m2s_contrib_begin", "m2s_contrib_accumulate", "m2s_device_contrib",
+    "m2s_download_contrib", "m2s_last_contrib_ms", "m2s_last_contrib_stage_ms", "m2s_prune", "m2s_last_prune_counts", "m2s_last_prune_ms",
 )
 
 
@@ -246,6 +248,18 @@ def load():
         "m2s_sh_shade_records": (C.c_int, [vp, vp, vp, vp, u64, vp]),
         "m2s_write_ply_sh": (C.c_int, [C.c_char_p, vp, vp, u64, C.c_float]),
         "m2s_export_ply_sh": (C.c_int, [vp, C.c_char_p, C.c_float]),
+        "m2s_device_sorted_sources": (vp, [vp]),
+        "m2s_download_sorted_sources": (C.c_int, [vp, vp, u64]),
+        "m2s_upload_quad_sources": (C.c_int, [vp, vp, u64]),
+        "m2s_contrib_begin": (C.c_int, [vp]),
+        "m2s_contrib_accumulate": (C.c_int, [vp, vp, C.c_float]),
+        "m2s_device_contrib": (vp, [vp, u32]),
+        "m2s_download_contrib": (C.c_int, [vp, vp, vp, u64]),
+        "m2s_last_contrib_ms": (C.c_float, [vp]),
+        "m2s_last_contrib_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_prune": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_last_prune_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_last_prune_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

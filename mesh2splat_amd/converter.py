@@ -798,6 +798,95 @@ class Converter:
                             mask_mode=mask_mode, mesh_depth_test=mesh_depth_test) for cam in cameras]
         return views, _sc.pool(views)
 
+    # ---- contribution pass and pruning (m2s_contrib_*, m2s_prune) ---------------------------------------------------------------------
+    @property
+    def device_sorted_sources(self) -> int:
+        """Device address of uint32[visible], the record every sorted quad of the last prepass_sorted() was made from; 0 when the sorted
+        quads carry none (m2s_device_sorted_sources)."""
+        return int(self._L.m2s_device_sorted_sources(self._h) or 0)
+
+    def download_sorted_sources(self, n: int) -> np.ndarray:
+        """-> uint32[n], the sources of the context's n sorted quads (m2s_download_sorted_sources)."""
+        out = np.empty(int(n), np.uint32)
+        self._check(self._L.m2s_download_sorted_sources(self._h, out.ctypes.data, out.size))
+        return out
+
+    def upload_quad_sources(self, sources):
+        """The counterpart of upload_quads() for the sources: one record index per sorted quad (m2s_upload_quad_sources)."""
+        s = np.ascontiguousarray(sources, np.uint32).reshape(-1)
+        self._check(self._L.m2s_upload_quad_sources(self._h, s.ctypes.data if s.size else None, s.size))
+
+    def contrib_begin(self):
+        """Size the two per-record accumulators to the context's current records and zero them (m2s_contrib_begin)."""
+        self._check(self._L.m2s_contrib_begin(self._h))
+
+    def contrib_accumulate(self, params, count_weight: float = 1.0 / 255.0):
+        """What every record adds to the picture of the context's sorted quads (prepass_sorted()) at `params` (SplatParams), added to the
+        accumulators: wmax, the largest fragment weight, and npix, the fragments with weight > count_weight (m2s_contrib_accumulate)."""
+        from . import splat as _sp
+        pc = _sp.to_c(params)
+        self._check(self._L.m2s_contrib_accumulate(self._h, C.byref(pc), C.c_float(count_weight)))
+
+    def download_contrib(self):
+        """-> (wmax, npix): float32[n] (the weights themselves; .view(np.uint32) gives the accumulated bits) and uint32[n]."""
+        n = self.num_stored
+        w = np.empty(n, np.float32)
+        k = np.empty(n, np.uint32)
+        self._check(self._L.m2s_download_contrib(self._h, w.ctypes.data, k.ctypes.data, n))
+        return w, k
+
+    def device_contrib(self, which: int) -> int:
+        return int(self._L.m2s_device_contrib(self._h, int(which)) or 0)
+
+    @property
+    def last_contrib_ms(self) -> float:
+        return float(self._L.m2s_last_contrib_ms(self._h))
+
+    def last_contrib_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_contrib_stage_ms(self._h, ms))
+        return {"setup_bin": float(ms[0]), "grouping": float(ms[1]), "blend": float(ms[2])}
+
+    def prune(self, min_weight: float = 0.0, min_pixels: int = 0) -> dict:
+        """Keep the records with wmax > min_weight and npix >= min_pixels (m2s_prune): the survivors become the context's records, in
+        order.  -> {"before", "kept", "dropped_weight", "dropped_pixels"}."""
+        from . import prune as _pr
+        pc = _pr.PruneParamsC(float(min_weight), int(min_pixels), 0)
+        kept = C.c_uint64()
+        had_plane = bool(self.device_sh)
+        self._check(self._L.m2s_prune(self._h, C.byref(pc), C.byref(kept)))
+        counts = self.last_prune_counts()
+        if had_plane and getattr(self, "_last_bake_n", None) == counts["before"]:
+            self._last_bake_n = counts["kept"]          # (the baked plane of these records was compacted with them)
+        return counts
+
+    def last_prune_counts(self) -> dict:
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_last_prune_counts(self._h, v))
+        return {"before": int(v[0]), "kept": int(v[1]), "dropped_weight": int(v[2]), "dropped_pixels": int(v[3])}
+
+    @property
+    def last_prune_ms(self) -> float:
+        return float(self._L.m2s_last_prune_ms(self._h))
+
+    def prune_views(self, cameras, resolution_target: int, size=None, gaussian_std: float = 0.65, count_weight: float = 1.0 / 255.0,
+                    min_weight: float = 1.0 / 255.0, min_pixels: int = 1) -> dict:
+        """prepass_sorted() -> contrib_accumulate() through each of `cameras` (mesh2splat_amd.prune.orbit_cameras), then prune().
+        `size`: (W, H) at which every view is taken instead of the camera's own resolution (the cameras' projections are kept, so keep their
+        aspect ratio; default: each camera's resolution).  -> the counts of prune()."""
+        import dataclasses
+        from . import splat as _sp
+        if size is not None:
+            size = (int(size[0]), int(size[1]))
+        self.contrib_begin()
+        for cam in cameras:
+            pp, _ = cam.frame_params(resolution_target, (0.0, 0.0, 0.0), 0.0, gaussian_std)
+            if size is not None:
+                pp = dataclasses.replace(pp, renderer_resolution=size)
+            if self.prepass_sorted(pp, download=False):
+                self.contrib_accumulate(_sp.SplatParams(tuple(pp.renderer_resolution), 0), count_weight)
+        return self.prune(min_weight, min_pixels)
+
     @property
     def last_shadow_ms(self) -> float:
         return float(self._L.m2s_last_shadow_ms(self._h))

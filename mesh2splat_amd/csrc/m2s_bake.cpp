@@ -162,6 +162,8 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_bake_ms, c->bake_ev[0], c->bake_ev[1]));
     c->sh_n = n;
     c->sh_valid = true;
+    c->sh_of = d_records;
+    c->sh_epoch = d_records == c->last_records ? c->records_epoch : 0;
     c->bake_has_counts = counts;
     return M2S_OK;
 }

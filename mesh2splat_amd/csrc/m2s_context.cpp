@@ -208,6 +208,8 @@ void m2s_destroy(m2s_ctx* c) {
     for (hipEvent_t e : c->score_ev) if (e) (void)hipEventDestroy(e);
     for (void* p : { (void*)c->d_sh, (void*)c->d_bake_counts, (void*)c->d_bake_table }) if (p) (void)hipFree(p);
     for (hipEvent_t e : c->bake_ev) if (e) (void)hipEventDestroy(e);
+    for (void* p : { (void*)c->d_sq_src, (void*)c->d_contrib, (void*)c->d_prune_u32, c->d_prune_temp, c->d_prune_stage }) if (p) (void)hipFree(p);
+    for (hipEvent_t e : c->prune_ev) if (e) (void)hipEventDestroy(e);
     if (c->d_loaded) (void)hipFree(c->d_loaded);
     if (c->d_rows) (void)hipFree(c->d_rows);
     for (int k = 0; k < 2; ++k) if (c->h_export[k]) (void)hipHostFree(c->h_export[k]);

@@ -1,0 +1,185 @@
+// m2s_contrib.cpp — the contribution pass (what every record adds to a view's picture) and the pruning of the records nobody sees:
+// host side of m2s_contrib.hip.  The binning stages in front of the contribution blend are the splat pass's own (splat_bin, m2s_splat.cpp).
+#include "m2s_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace m2s;
+using namespace m2s_host;
+
+namespace {
+
+bool contrib_valid(const m2s_ctx* c) {
+    return c->contrib_active && c->last_records && !c->records_stale && c->contrib_of == c->last_records && c->contrib_n == c->last_stored &&
+           c->contrib_epoch == c->records_epoch;
+}
+
+}  // namespace
+
+extern "C" {
+
+m2s_status m2s_upload_quad_sources(m2s_ctx* c, const uint32_t* host_sources, uint64_t n) {
+    if (!c || (n && !host_sources)) return M2S_ERR_INVALID;
+    if (!c->sq_n || n != c->sq_n) return fail(c, M2S_ERR_INVALID, "the number of sources is not the number of sorted quads");
+    for (uint64_t i = 0; i < n; ++i)
+        if (host_sources[i] >= c->last_stored) return fail(c, M2S_ERR_INVALID, "a source index is not below the number of records");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->sq_src = nullptr;
+    if (m2s_status s = grow_buffer(c, c->d_sq_src, c->sq_src_cap, n, sizeof(uint32_t))) return s;
+    HIPCHK(c, hipMemcpy(c->d_sq_src, host_sources, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->sq_src = c->d_sq_src;
+    c->sq_src_epoch = c->records_epoch;
+    return M2S_OK;
+}
+
+m2s_status m2s_contrib_begin(m2s_ctx* c) {
+    if (!c) return M2S_ERR_INVALID;
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
+    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    const uint64_t n = c->last_stored;
+    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->contrib_active = false;
+    if (m2s_status s = grow_buffer(c, c->d_contrib, c->contrib_cap, std::max<uint64_t>(n, 1), 2 * sizeof(uint32_t))) return s;
+    HIPCHK(c, hipMemsetAsync(c->d_contrib, 0, c->contrib_cap * 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->contrib_of = c->last_records;
+    c->contrib_n = n;
+    c->contrib_epoch = c->records_epoch;
+    c->contrib_active = true;
+    return M2S_OK;
+}
+
+m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float count_weight) {
+    if (!c || !p) return M2S_ERR_INVALID;
+    const int W = p->resolution[0], H = p->resolution[1];
+    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    if (p->render_mode < 0 || p->render_mode > 6 || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6 or reserved != 0");
+    if (p->render_mode == 4) return fail(c, M2S_ERR_INVALID, "render mode 4 (overdraw) has no fragment weight");
+    if (!(count_weight >= 0.0f) || !std::isfinite(count_weight)) return fail(c, M2S_ERR_INVALID, "count_weight is negative or not finite");
+    if (!c->contrib_active) return fail(c, M2S_ERR_INVALID, "no m2s_contrib_begin");
+    if (!contrib_valid(c)) return fail(c, M2S_ERR_INVALID, "the records changed since m2s_contrib_begin");
+    if (!c->sq_n) return fail(c, M2S_ERR_INVALID, "no sorted quads (run m2s_prepass_sorted)");
+    if (!c->sq_src || c->sq_src_epoch != c->records_epoch)
+        return fail(c, M2S_ERR_INVALID, "the sorted quads carry no sources (they come from m2s_prepass_sorted or m2s_upload_quad_sources)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t nq = (uint32_t)c->sq_n;
+    SplatBins bins;
+    if (m2s_status s = splat_bin(c, c->d_sorted_quads, nq, W, H, &bins)) return s;
+    if (bins.pairs)
+        HIPCHK(c, contrib_blend((const float4*)c->d_splat_rec, bins.vals, bins.ranges, bins.order, W, H, c->sq_src, count_weight, c->d_contrib,
+                                c->d_contrib + c->contrib_cap, c->stream));
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) {
+        if (m2s_status s = splat_stage_ms(c, true, c->last_contrib_stage_ms)) return s;
+        c->last_contrib_ms = (c->last_contrib_stage_ms[0] + c->last_contrib_stage_ms[1]) + c->last_contrib_stage_ms[2];
+    }
+    return M2S_OK;
+}
+
+const void* m2s_device_contrib(const m2s_ctx* c, uint32_t which) {
+    return c && which < 2 && contrib_valid(c) ? c->d_contrib + which * c->contrib_cap : nullptr;
+}
+
+m2s_status m2s_download_contrib(m2s_ctx* c, uint32_t* dst_wmax, uint32_t* dst_npix, uint64_t capacity) {
+    if (!c) return M2S_ERR_INVALID;
+    if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin)");
+    if (capacity < c->contrib_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!c->contrib_n) return M2S_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (dst_wmax) HIPCHK(c, hipMemcpy(dst_wmax, c->d_contrib, c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (dst_npix) HIPCHK(c, hipMemcpy(dst_npix, c->d_contrib + c->contrib_cap, c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+float m2s_last_contrib_ms(const m2s_ctx* c) { return c ? c->last_contrib_ms : 0.0f; }
+
+m2s_status m2s_last_contrib_stage_ms(const m2s_ctx* c, float out_ms[3]) {
+    if (!c || !out_ms) return M2S_ERR_INVALID;
+    std::memcpy(out_ms, c->last_contrib_stage_ms, sizeof(c->last_contrib_stage_ms));
+    return M2S_OK;
+}
+
+m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) {
+    if (!c || !p) return M2S_ERR_INVALID;
+    if (p->reserved != 0 || std::isnan(p->min_weight)) return fail(c, M2S_ERR_INVALID, "min_weight is NaN or reserved != 0");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin, m2s_contrib_accumulate)");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (hipEvent_t& e : c->prune_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    const uint64_t n = c->last_stored;
+    const uint32_t R = c->last_R;
+    uint64_t kept = 0, by_w = 0, by_p = 0;
+    const bool sh = c->sh_valid && c->sh_of == c->last_records && c->sh_epoch == c->records_epoch && c->sh_n == n;
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[0], c->stream));
+    if (n) {
+        // flags | offsets | two 64-bit counters
+        if (m2s_status s = grow_buffer(c, c->d_prune_u32, c->prune_cap, n, 2 * sizeof(uint32_t))) return s;
+        unsigned long long* counters = nullptr;
+        {   // (the counters live behind the scan's work area, 16-byte aligned)
+            const uint64_t want = align_up(prune_scan_temp_bytes((uint32_t)n), 16) + 2 * sizeof(unsigned long long);
+            if (m2s_status s = grow_buffer(c, c->d_prune_temp, c->prune_temp_cap, want, 1)) return s;
+            counters = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_prune_temp) + c->prune_temp_cap - 2 * sizeof(unsigned long long));
+        }
+        uint32_t* flags = c->d_prune_u32;
+        uint32_t* offsets = flags + c->prune_cap;
+        HIPCHK(c, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, prune_flags_scan(c->d_contrib, c->d_contrib + c->contrib_cap, (uint32_t)n, p->min_weight, p->min_pixels, flags, offsets, counters,
+                                   c->d_prune_temp, c->prune_temp_cap - 2 * sizeof(unsigned long long), c->stream));
+        unsigned long long h[2] = { 0, 0 };
+        HIPCHK(c, hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        by_w = h[0]; by_p = h[1];
+        kept = n - by_w - by_p;
+        // The survivors go into the pool.  Records that live there already (or a plane compacted in place) cannot be compacted onto
+        // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
+        const bool in_pool = c->last_records == c->d_records;
+        const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
+        if (stage_bytes) if (m2s_status s = grow_buffer(c, c->d_prune_stage, c->prune_stage_cap, stage_bytes, 1)) return s;
+        const void* src = c->last_records;
+        if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
+        if (kept) {
+            float4* dst = in_pool ? (float4*)c->d_prune_stage : (float4*)c->d_records;
+            HIPCHK(c, prune_compact((const float4*)src, flags, offsets, (uint32_t)n, 6, dst, c->stream));
+            if (in_pool) HIPCHK(c, hipMemcpyAsync(c->d_records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+            if (sh) {
+                HIPCHK(c, prune_compact((const float4*)c->d_sh, flags, offsets, (uint32_t)n, 12, (float4*)c->d_prune_stage, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->d_sh, c->d_prune_stage, kept * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            }
+        }
+    } else if (!c->d_records || c->last_records != c->d_records) {
+        if (m2s_status s = ensure_records(c, 1)) return s;
+    }
+    if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_prune_ms, c->prune_ev[0], c->prune_ev[1]));
+    // the survivors are the context's current records now, at the resolutionTarget of the ones they were taken from
+    c->last_records = c->d_records;
+    ++c->records_epoch;
+    c->last_total = c->last_stored = kept;
+    c->last_R = R;
+    c->records_stale = false;
+    c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
+    c->sq_src = nullptr;
+    c->contrib_active = false;
+    if (sh) { c->sh_n = kept; c->sh_of = c->last_records; c->sh_epoch = c->records_epoch; }
+    if (c->bake_has_counts && sh) c->bake_has_counts = false;       // (the tap counts are not compacted)
+    c->last_prune_counts[0] = n; c->last_prune_counts[1] = kept; c->last_prune_counts[2] = by_w; c->last_prune_counts[3] = by_p;
+    if (out_kept) *out_kept = kept;
+    return M2S_OK;
+}
+
+m2s_status m2s_last_prune_counts(const m2s_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return M2S_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = c->last_prune_counts[k];
+    return M2S_OK;
+}
+
+float m2s_last_prune_ms(const m2s_ctx* c) { return c ? c->last_prune_ms : 0.0f; }
+
+}  // extern "C"

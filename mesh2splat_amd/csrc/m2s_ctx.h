@@ -7,6 +7,7 @@
 //   m2s_meshdepth.cpp  the mesh depth prepass (== DepthPrepass::execute)
 //   m2s_meshrender.cpp the mesh render pass (== MeshRenderPass::execute) and the mesh G-buffer
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
+//   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 #pragma once
 #include "../../include/m2s.h"
@@ -196,6 +197,28 @@ struct m2s_ctx {
     float last_splat_ms = 0.0f;
     float last_splat_stage_ms[3] = { 0, 0, 0 };     // setup + bin, grouping, blend (profiling on)
     uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
+    // sources of the sorted quads (m2s_prepass_sorted): which record each was made from.  Dense path: the first sq_n words of the
+    // permutation in d_sort_u32 (an alias: dropped by whatever rewrites those words); compacting path: d_sq_src, written by k_prepass
+    const uint32_t* sq_src = nullptr;        // nullptr: absent
+    uint64_t sq_src_epoch = 0;               // records_epoch they index into
+    uint32_t* d_sq_src = nullptr;
+    uint64_t sq_src_cap = 0;
+    // contribution pass and pruning (m2s_contrib.cpp): wmax | npix, contrib_cap words each, valid for (contrib_of, contrib_n, contrib_epoch)
+    uint32_t* d_contrib = nullptr;
+    uint64_t contrib_cap = 0, contrib_n = 0, contrib_epoch = 0;
+    const void* contrib_of = nullptr;
+    bool contrib_active = false;
+    float last_contrib_ms = 0.0f;
+    float last_contrib_stage_ms[3] = { 0, 0, 0 };
+    uint32_t* d_prune_u32 = nullptr;         // flags | offsets, prune_cap words each, then two counters (u64)
+    uint64_t prune_cap = 0;
+    void* d_prune_temp = nullptr;            // scan work area
+    uint64_t prune_temp_cap = 0;
+    void* d_prune_stage = nullptr;           // survivors on their way back into the buffer they came from
+    uint64_t prune_stage_cap = 0;            // bytes
+    uint64_t last_prune_counts[4] = { 0, 0, 0, 0 };
+    float last_prune_ms = 0.0f;
+    hipEvent_t prune_ev[2] = {};
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     void* d_shadow_quads = nullptr;          // 48 B each
@@ -276,6 +299,8 @@ struct m2s_ctx {
     float* d_sh = nullptr;                       // float[n][48]: f_dc[3], f_rest[45] channel-major
     uint64_t sh_cap = 0, sh_n = 0;               // records it has room for / holds
     bool sh_valid = false;                       // a bake has completed since the plane was last (re)allocated
+    const void* sh_of = nullptr;                 // the records it was baked from, and their records_epoch when they were the context's
+    uint64_t sh_epoch = 0;                       // (0: the caller's records) — m2s_prune compacts the plane of the records it compacts
     uint8_t* d_bake_counts = nullptr;            // uint8[n]
     uint64_t bake_counts_cap = 0;
     bool bake_has_counts = false;
@@ -331,6 +356,13 @@ inline m2s_status grow_buffer(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, s
     cap = want;
     return M2S_OK;
 }
+// m2s_splat.cpp
+// The stages of the splat pass in front of the blend — setup / bin, pairs, grouping by tile, tile order — over n quads on a W x H
+// viewport, in the context's splat work buffers: what m2s_splat and m2s_contrib_accumulate both start with.  Records ev[0..4] when
+// profiling (setup: 0-1, pairs: 2-3, grouping: 3-4); synchronises once (the pair count).  vals / ranges / order are NULL without pairs.
+struct SplatBins { const uint32_t* vals = nullptr; const uint2* ranges = nullptr; const uint32_t* order = nullptr; uint64_t pairs = 0, skipped = 0; };
+m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out);
+m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]);   // ... and their times + the blend's (ev[4..5]), profiling on
 // m2s_meshdepth.cpp
 // What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
 // tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);

@@ -222,7 +222,7 @@ void prepass_prepare(const m2s_prepass_params& p, uint64_t n, PrepassK* out);
 // dense: every one of the n positions is known to survive (the sort in front applied the frustum test): written at its own position, no append
 hipError_t launch_prepass(const PrepassK& k, const float4* rec, uint32_t n, float4* quads, float* depths, unsigned long long* chain,
                           uint32_t epoch, unsigned long long* counter, unsigned long long* total, uint32_t* status, hipStream_t st,
-                          const uint32_t* perm = nullptr, bool dense = false);
+                          const uint32_t* perm = nullptr, bool dense = false, uint32_t* sources = nullptr);
 
 size_t sort_prepass_temp_bytes(uint32_t n);
 hipError_t sort_prepass(const float* depths, const float4* quads, uint32_t n, uint32_t* keys_out, uint32_t* vals_out, void* temp,
@@ -257,6 +257,20 @@ hipError_t splat_group(uint32_t* keys_in, uint32_t* vals_in, uint32_t* keys_out,
 hipError_t splat_blend(const float4* rec, const uint32_t* vals, const uint2* ranges, const uint32_t* order, int W, int H, int render_mode,
                        void* const planes[5], unsigned long long* frag_count, hipStream_t st);
 hipError_t preload_splat();
+
+// ---- contribution pass and pruning (m2s_contrib.hip) -----------------------------------------------------------------------------
+// k_splat_contrib over the records / pairs / ranges / order of the splat pass's binning stages (splat_setup .. splat_group): per record
+// sources[quad], wmax (bits of the largest fragment weight, integer max) and npix (fragments with weight > count_weight, integer sum)
+hipError_t contrib_blend(const float4* rec, const uint32_t* vals, const uint2* ranges, const uint32_t* order, int W, int H,
+                         const uint32_t* sources, float count_weight, uint32_t* wmax, uint32_t* npix, hipStream_t st);
+size_t prune_scan_temp_bytes(uint32_t n);
+// flags[i] = wmax[i] > min_weight && npix[i] >= min_pixels; counters[0] += dropped by weight, [1] += dropped by pixels alone (zeroed by
+// the caller); offsets = exclusive scan of the flags
+hipError_t prune_flags_scan(const uint32_t* wmax, const uint32_t* npix, uint32_t n, float min_weight, uint32_t min_pixels, uint32_t* flags,
+                            uint32_t* offsets, unsigned long long* counters, void* temp, size_t temp_bytes, hipStream_t st);
+// rows of f4_per_row float4 each: row i of src goes to row offsets[i] of dst where flags[i] is set; 16 bytes per lane
+hipError_t prune_compact(const float4* src, const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t f4_per_row, float4* dst,
+                         hipStream_t st);
 
 // ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
 struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads

@@ -127,7 +127,8 @@ constexpr uint32_t kPPTile = kPPWaves * 64u * kPPRec;   // records per workgroup
 __global__ void __launch_bounds__(kPPWaves * 64) k_prepass(const PrepassK k, const float4* __restrict__ rec, uint32_t n, float4* __restrict__ quads,
                                                     float* __restrict__ depths, unsigned long long* __restrict__ chain, uint32_t epoch,
                                                     unsigned long long* __restrict__ counter, unsigned long long* __restrict__ total,
-                                                    uint32_t* __restrict__ status, const uint32_t* __restrict__ perm, uint32_t dense) {
+                                                    uint32_t* __restrict__ status, const uint32_t* __restrict__ perm, uint32_t dense,
+                                                    uint32_t* __restrict__ sources) {
     __shared__ float4 s_rec[kPPWaves][64 * 6];   // survivors of ONE 64-record group, staged for contiguous stores
     __shared__ float s_depth[kPPWaves][64];
     __shared__ uint32_t s_cnt[kPPWaves];
@@ -241,16 +242,17 @@ __global__ void __launch_bounds__(kPPWaves * 64) k_prepass(const PrepassK k, con
             if (idx < n4) nt_store(&dst[idx], S[idx]);       // (the quads are read by the next pass, not by this one: non-temporal, like the records)
         }
         if ((uint32_t)lane < cnt[r]) __builtin_nontemporal_store(s_depth[wave][lane], &depths[base + lane]);
+        if (sources && vis[r]) sources[base + rank[r]] = src[r];   // (m2s_prepass_sorted, compacting: the record this survivor was made from)
         base += cnt[r];
     }
 }
 
 hipError_t launch_prepass(const PrepassK& k, const float4* rec, uint32_t n, float4* quads, float* depths, unsigned long long* chain,
                           uint32_t epoch, unsigned long long* counter, unsigned long long* total, uint32_t* status, hipStream_t st,
-                          const uint32_t* perm, bool dense) {
+                          const uint32_t* perm, bool dense, uint32_t* sources) {
     const uint32_t nb = (n + kPPTile - 1u) / kPPTile;
     hipLaunchKernelGGL(k_prepass, dim3(nb), dim3(kPPWaves * 64), 0, st, k, rec, n, quads, depths, chain, epoch & 0xFFFFu, counter, total, status, perm,
-                       dense ? 1u : 0u);
+                       dense ? 1u : 0u, sources);
     return hipGetLastError();
 }
 

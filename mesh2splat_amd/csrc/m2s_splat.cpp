@@ -24,6 +24,82 @@ m2s_status grow(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
 
 }  // namespace
 
+namespace m2s_host {
+
+m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out) {
+    if (!c->d_splat_totals) HIPCHK(c, hipMalloc((void**)&c->d_splat_totals, 4 * sizeof(unsigned long long)));
+    if (!c->h_splat) HIPCHK(c, hipHostMalloc((void**)&c->h_splat, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    const int tiles_x = (W + kSplatTile - 1) / kSplatTile, tiles_y = (H + kSplatTile - 1) / kSplatTile;
+    const uint32_t n_tiles = (uint32_t)(tiles_x * tiles_y);
+    HIPCHK(c, hipMemsetAsync(c->d_splat_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    hipEvent_t* ev = c->ev;
+    const bool prof = c->profiling;
+    uint64_t pairs = 0;
+    *out = SplatBins();
+    if (nq) {
+        // ---- setup: records, tile counts, their scan; the number of pairs read back once (the pair buffers are sized from it)
+        if (c->splat_quad_cap < nq) {
+            for (void* q : { c->d_splat_rec, (void*)c->d_splat_cnt, (void*)c->d_splat_off }) if (q) (void)hipFree(q);
+            c->d_splat_rec = nullptr; c->d_splat_cnt = nullptr; c->d_splat_off = nullptr;
+            c->splat_quad_cap = 0;
+            HIPCHK(c, hipMalloc(&c->d_splat_rec, (size_t)nq * kSplatRecBytes));
+            HIPCHK(c, hipMalloc((void**)&c->d_splat_cnt, (size_t)nq * sizeof(uint32_t)));
+            HIPCHK(c, hipMalloc((void**)&c->d_splat_off, (size_t)nq * sizeof(unsigned long long)));
+            c->splat_quad_cap = nq;
+        }
+        uint64_t tcap = c->splat_temp_cap;
+        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_scan_temp_bytes(nq), 1)) return s;
+        c->splat_temp_cap = tcap;
+        if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, splat_setup((const float4*)d_quads, nq, W, H, (float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, c->d_splat_temp,
+                              c->splat_temp_cap, c->d_splat_totals, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_splat, c->d_splat_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        pairs = c->h_splat[0];
+        out->skipped = c->h_splat[1];
+        if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
+    }
+    if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    out->pairs = pairs;
+    if (pairs) {
+        if (m2s_status s = grow(c, c->d_splat_pairs, c->splat_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
+        if (m2s_status s = grow(c, c->d_splat_tiles, c->splat_tiles_cap, n_tiles, 5 * sizeof(uint32_t))) return s;
+        uint64_t tcap = c->splat_temp_cap;
+        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_sort_temp_bytes((uint32_t)pairs, n_tiles), 1)) return s;
+        c->splat_temp_cap = tcap;
+        const uint64_t pc = c->splat_pairs_cap, tc = c->splat_tiles_cap;
+        uint32_t* keys_in = c->d_splat_pairs;
+        uint32_t* vals_in = keys_in + pc;
+        uint32_t* keys_out = vals_in + pc;
+        uint32_t* vals_out = keys_out + pc;
+        uint2* rg = reinterpret_cast<uint2*>(c->d_splat_tiles);
+        uint32_t* len = c->d_splat_tiles + 2 * tc;
+        uint32_t* len_sorted = len + tc;
+        uint32_t* ord = len_sorted + tc;
+        HIPCHK(c, splat_pairs((const float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, nq, tiles_x, keys_in, vals_in, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+        HIPCHK(c, splat_group(keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs, n_tiles, rg, len, len_sorted, ord, c->d_splat_temp,
+                              c->splat_temp_cap, c->stream));
+        out->vals = vals_out; out->ranges = rg; out->order = ord;
+    } else if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
+    return M2S_OK;
+}
+
+m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]) {
+    hipEvent_t* ev = c->ev;
+    float a = 0, b = 0, g = 0, bl = 0;
+    if (any_quads) HIPCHK(c, hipEventElapsedTime(&a, ev[0], ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&b, ev[2], ev[3]));
+    HIPCHK(c, hipEventElapsedTime(&g, ev[3], ev[4]));
+    HIPCHK(c, hipEventElapsedTime(&bl, ev[4], ev[5]));
+    out[0] = a + b; out[1] = g; out[2] = bl;
+    return M2S_OK;
+}
+
+}  // namespace m2s_host
+
 extern "C" {
 
 m2s_status m2s_upload_quads(m2s_ctx* c, const m2s_quad* host_quads, uint64_t n) {
@@ -31,6 +107,7 @@ m2s_status m2s_upload_quads(m2s_ctx* c, const m2s_quad* host_quads, uint64_t n) 
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 quads");
     HIPCHK(c, hipSetDevice(c->device));
     c->sq_n = 0;
+    c->sq_src = nullptr;
     if (!n) return M2S_OK;
     if (m2s_status s = grow(c, c->d_sorted_quads, c->sq_cap, n, sizeof(m2s_quad))) return s;
     HIPCHK(c, hipMemcpy(c->d_sorted_quads, host_quads, n * sizeof(m2s_quad), hipMemcpyHostToDevice));
@@ -61,66 +138,18 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
         for (int k = 0; k < 5; ++k) HIPCHK(c, hipMalloc(&c->d_gbuf[k], px * ((k == 2 || k == 4) ? 4 : 8)));
         c->gbuf_cap_px = px;
     }
-    if (!c->d_splat_totals) HIPCHK(c, hipMalloc((void**)&c->d_splat_totals, 4 * sizeof(unsigned long long)));
-    if (!c->h_splat) HIPCHK(c, hipHostMalloc((void**)&c->h_splat, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-    const int tiles_x = (W + kSplatTile - 1) / kSplatTile, tiles_y = (H + kSplatTile - 1) / kSplatTile;
-    const uint32_t n_tiles = (uint32_t)(tiles_x * tiles_y);
     const uint32_t nq = (uint32_t)n;
-    HIPCHK(c, hipMemsetAsync(c->d_splat_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    SplatBins bins;
+    const m2s_status bs = splat_bin(c, d_quads, nq, W, H, &bins);
+    c->last_splat_counts[2] = bins.skipped;
+    if (out_skipped) *out_skipped = bins.skipped;
+    if (bs != M2S_OK) return bs;
+    const uint64_t pairs = bins.pairs;
+    const uint32_t* vals = bins.vals;
+    const uint2* ranges = bins.ranges;
+    const uint32_t* order = bins.order;
     hipEvent_t* ev = c->ev;
     const bool prof = c->profiling;
-    uint64_t pairs = 0;
-    if (nq) {
-        // ---- setup: records, tile counts, their scan; the number of pairs read back once (the pair buffers are sized from it)
-        if (c->splat_quad_cap < nq) {
-            for (void* q : { c->d_splat_rec, (void*)c->d_splat_cnt, (void*)c->d_splat_off }) if (q) (void)hipFree(q);
-            c->d_splat_rec = nullptr; c->d_splat_cnt = nullptr; c->d_splat_off = nullptr;
-            c->splat_quad_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_splat_rec, (size_t)nq * kSplatRecBytes));
-            HIPCHK(c, hipMalloc((void**)&c->d_splat_cnt, (size_t)nq * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc((void**)&c->d_splat_off, (size_t)nq * sizeof(unsigned long long)));
-            c->splat_quad_cap = nq;
-        }
-        uint64_t tcap = c->splat_temp_cap;
-        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_scan_temp_bytes(nq), 1)) return s;
-        c->splat_temp_cap = tcap;
-        if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        HIPCHK(c, splat_setup((const float4*)d_quads, nq, W, H, (float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, c->d_splat_temp,
-                              c->splat_temp_cap, c->d_splat_totals, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_splat, c->d_splat_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        pairs = c->h_splat[0];
-        c->last_splat_counts[2] = c->h_splat[1];
-        if (out_skipped) *out_skipped = c->h_splat[1];
-        if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
-    }
-    if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    const uint32_t* vals = nullptr;
-    const uint2* ranges = nullptr;
-    const uint32_t* order = nullptr;
-    if (pairs) {
-        if (m2s_status s = grow(c, c->d_splat_pairs, c->splat_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
-        if (m2s_status s = grow(c, c->d_splat_tiles, c->splat_tiles_cap, n_tiles, 5 * sizeof(uint32_t))) return s;
-        uint64_t tcap = c->splat_temp_cap;
-        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_sort_temp_bytes((uint32_t)pairs, n_tiles), 1)) return s;
-        c->splat_temp_cap = tcap;
-        const uint64_t pc = c->splat_pairs_cap, tc = c->splat_tiles_cap;
-        uint32_t* keys_in = c->d_splat_pairs;
-        uint32_t* vals_in = keys_in + pc;
-        uint32_t* keys_out = vals_in + pc;
-        uint32_t* vals_out = keys_out + pc;
-        uint2* rg = reinterpret_cast<uint2*>(c->d_splat_tiles);
-        uint32_t* len = c->d_splat_tiles + 2 * tc;
-        uint32_t* len_sorted = len + tc;
-        uint32_t* ord = len_sorted + tc;
-        HIPCHK(c, splat_pairs((const float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, nq, tiles_x, keys_in, vals_in, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-        HIPCHK(c, splat_group(keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs, n_tiles, rg, len, len_sorted, ord, c->d_splat_temp,
-                              c->splat_temp_cap, c->stream));
-        vals = vals_out; ranges = rg; order = ord;
-    } else if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
     // ---- blend: every tile writes its 16 x 16 pixels of all five planes once (tiles without quads write the cleared values)
     void* const planes[5] = { c->d_gbuf[0], c->d_gbuf[1], c->d_gbuf[2], c->d_gbuf[3], c->d_gbuf[4] };
     HIPCHK(c, splat_blend((const float4*)c->d_splat_rec, vals, ranges, order, W, H, p->render_mode, planes, c->d_splat_totals + 2, c->stream));
@@ -130,15 +159,8 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
     c->last_splat_counts[0] = pairs;
     c->last_splat_counts[1] = c->h_splat[2];
     if (prof) {
-        float a = 0, b = 0, g = 0, bl = 0;
-        if (nq) HIPCHK(c, hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIPCHK(c, hipEventElapsedTime(&b, ev[2], ev[3]));
-        HIPCHK(c, hipEventElapsedTime(&g, ev[3], ev[4]));
-        HIPCHK(c, hipEventElapsedTime(&bl, ev[4], ev[5]));
-        c->last_splat_stage_ms[0] = a + b;
-        c->last_splat_stage_ms[1] = g;
-        c->last_splat_stage_ms[2] = bl;
-        c->last_splat_ms = a + b + g + bl;
+        if (m2s_status s = splat_stage_ms(c, nq != 0, c->last_splat_stage_ms)) return s;
+        c->last_splat_ms = (c->last_splat_stage_ms[0] + c->last_splat_stage_ms[1]) + c->last_splat_stage_ms[2];
     }
     c->gbuf_w = W;
     c->gbuf_h = H;

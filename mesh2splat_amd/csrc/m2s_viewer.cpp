@@ -26,6 +26,7 @@ m2s_status m2s_sort_by_depth(m2s_ctx* c, const float world_to_view[16], uint64_t
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t n = c->last_stored;
     c->sorted_n = 0;
+    if (c->sq_src != c->d_sq_src) c->sq_src = nullptr;   // (sources aliasing the permutation words this sort is about to rewrite)
     if (out_n) *out_n = n;
     if (!n) return M2S_OK;
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
@@ -121,6 +122,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     HIPCHK(c, hipSetDevice(c->device));
     c->pp_visible = 0;
     c->sq_n = 0;
+    c->sq_src = nullptr;
     if (out_visible) *out_visible = 0;
     if (!n) return M2S_OK;
     if (!sorted && c->pp_cap < n) {
@@ -213,10 +215,14 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         }
         dense = cull;
         perm = u + 3 * n;
+        // which record every surviving quad was made from: dense, position i holds record perm[i] and every position survives — the
+        // first n_run words of the permutation ARE the sources; compacting, the kernel stores them beside the quads
+        if (!dense && n_run) if (m2s_status s = grow_buffer(c, c->d_sq_src, c->sq_src_cap, n, sizeof(uint32_t))) return s;
     }
+    uint32_t* src_out = sorted && !dense ? c->d_sq_src : nullptr;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
     if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, (float4*)(sorted ? c->d_sorted_quads : c->d_quads), c->d_pp_depths, c->d_pp_chain + 1,
-                                        epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense));
+                                        epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense, src_out));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     if (k.arrival_order) HIPCHK(c, hipMemcpyAsync(&res[0], c->d_pp_chain, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -231,7 +237,11 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     if (reinterpret_cast<uint32_t*>(&res[1])[1] == 2u) return fail(c, M2S_ERR_HIP, "prepass_sorted: the sort's frustum test and the prepass's disagree (internal error)");
     if (reinterpret_cast<uint32_t*>(&res[1])[1]) return fail(c, M2S_ERR_HIP, "prepass: look-back chain timed out");
     if (dense) res[0] = n_run;                  // (the survivors were counted by the sort; the dense prepass appends nothing)
-    if (sorted) c->sq_n = res[0]; else c->pp_visible = res[0];
+    if (sorted) {
+        c->sq_n = res[0];
+        c->sq_src = dense ? perm : c->d_sq_src;
+        c->sq_src_epoch = c->records_epoch;
+    } else c->pp_visible = res[0];
     if (out_visible) *out_visible = res[0];
     return M2S_OK;
 }
@@ -267,6 +277,7 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t n = c->pp_visible;          // the atomic counter the reference reads back (RadixSortPass.cpp:18-22)
     c->sq_n = 0;
+    c->sq_src = nullptr;
     if (out_n) *out_n = n;
     if (!n) return M2S_OK;
     if (c->sq_cap < n) {
@@ -297,6 +308,20 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
 }
 
 const void* m2s_device_sorted_quads(const m2s_ctx* c) { return c && c->sq_n ? c->d_sorted_quads : nullptr; }
+const void* m2s_device_sorted_sources(const m2s_ctx* c) {
+    return c && c->sq_n && c->sq_src_epoch == c->records_epoch ? c->sq_src : nullptr;
+}
+
+m2s_status m2s_download_sorted_sources(m2s_ctx* c, uint32_t* dst, uint64_t capacity) {
+    if (!c) return M2S_ERR_INVALID;
+    const void* src = m2s_device_sorted_sources(c);
+    if (!src) return fail(c, M2S_ERR_STATE, "the sorted quads carry no sources (m2s_prepass_sorted, m2s_upload_quad_sources)");
+    if (!dst) return fail(c, M2S_ERR_INVALID, "dst is NULL");
+    if (capacity < c->sq_n) return fail(c, M2S_ERR_CAPACITY, "dst holds fewer entries than there are sorted quads");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, src, c->sq_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
 
 m2s_status m2s_download_sorted_quads(m2s_ctx* c, m2s_quad* dst, uint64_t capacity) {
     if (!c) return M2S_ERR_INVALID;

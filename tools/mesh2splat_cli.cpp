@@ -69,6 +69,11 @@ struct Options {
     double score_elevation = 0.0;                                  // --score-elevation deg
     int score_mask = 2;                                            // --score-mask 0..3
     std::string score_map;                                         // --score-map prefix: the error maps as prefix_k.png
+    int prune_views = 0;                                           // --prune K: K cameras round the scene per elevation; drop the Gaussians none of them sees (m2s_prune)
+    std::vector<double> prune_elevations = { -35.0, 0.0, 35.0 };   // --prune-elevations e1,e2,...
+    double prune_weight = 1.0 / 255.0;                             // --prune-weight w: keep wmax > w
+    long prune_pixels = 1;                                         // --prune-pixels n: keep npix >= n
+    double prune_count_weight = 1.0 / 255.0;                       // --prune-count-weight c: a fragment counts with weight > c
     bool preview_mode_set = false;                                 // (--score lights its frames in mode 6 unless --preview-mode says otherwise)
     uint32_t R() const { return density > 0 ? (uint32_t)density : (uint32_t)(int)(16 + quality * (double)(max_res - 16)); }  // ImGuiUI.cpp:512
 };
@@ -82,6 +87,7 @@ void usage() {
                  "         [--preview view.png [--preview-size WxH (default 1280x720)] [--mesh-depth-test] [--split-screen POS (0..1)]]\n"
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
+                 "         [--prune K [--prune-elevations e1,e2,...] [--prune-weight w] [--prune-pixels n] [--prune-count-weight c]]\n"
                  "         [--bake-light [--bake-degree 0..3]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
@@ -440,6 +446,44 @@ int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_
     return 0;
 }
 
+// --prune K: K cameras round the scene at each elevation, at --preview-size; per camera m2s_prepass_sorted -> m2s_contrib_accumulate, then
+// m2s_prune (Converter.prune_views does the same).  Prints one JSON line.
+int run_prune(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+    const int W = o.preview_w, H = o.preview_h, K = o.prune_views;
+    double ctr[3], dist, near_p, far_p;
+    preview_rule(meshes, n_meshes, ctr, &dist, &near_p, &far_p);
+    if (m2s_contrib_begin(ctx) != M2S_OK) return 1;
+    std::string eyes, els;
+    for (size_t e = 0; e < o.prune_elevations.size(); ++e) {
+        els += std::string(e ? ", " : "") + json_num(o.prune_elevations[e]);
+        for (int v = 0; v < K; ++v) {
+            const double th = 2.0 * M_PI * v / K, el = o.prune_elevations[e] * (M_PI / 180.0);
+            const double eye[3] = { ctr[0] + dist * std::cos(el) * std::sin(th), ctr[1] + dist * std::sin(el), ctr[2] + dist * std::cos(el) * std::cos(th) };
+            m2s_prepass_params pp;
+            std::memset(&pp, 0, sizeof(pp));
+            camera_matrices(eye, ctr, near_p, far_p, W, H, pp.world_to_view, pp.view_to_clip);
+            for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
+            pp.resolution[0] = W; pp.resolution[1] = H;
+            pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
+            pp.gaussian_std = (float)o.std_dev;
+            pp.resolution_target = R;
+            uint64_t visible = 0;
+            if (m2s_prepass_sorted(ctx, &pp, &visible) != M2S_OK) return 1;
+            m2s_splat_params sp = { { W, H }, 0, 0 };
+            if (visible && m2s_contrib_accumulate(ctx, &sp, (float)o.prune_count_weight) != M2S_OK) return 1;
+            eyes += std::string(eyes.empty() ? "" : ", ") + "[" + json_num(eye[0]) + ", " + json_num(eye[1]) + ", " + json_num(eye[2]) + "]";
+        }
+    }
+    m2s_prune_params pr = { (float)o.prune_weight, (uint32_t)o.prune_pixels, 0 };
+    uint64_t kept = 0, c[4] = { 0, 0, 0, 0 };
+    if (m2s_prune(ctx, &pr, &kept) != M2S_OK || m2s_last_prune_counts(ctx, c) != M2S_OK) return 1;
+    std::printf("prune: {\"views\": %d, \"elevations\": [%s], \"size\": [%d, %d], \"density\": %u, \"min_weight\": %s, \"min_pixels\": %ld, "
+                "\"count_weight\": %s, \"eyes\": [%s], \"before\": %llu, \"kept\": %llu, \"dropped_weight\": %llu, \"dropped_pixels\": %llu}\n",
+                K, els.c_str(), W, H, R, json_num((double)pr.min_weight).c_str(), o.prune_pixels, json_num((double)(float)o.prune_count_weight).c_str(), eyes.c_str(),
+                (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3]);
+    return 0;
+}
+
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
@@ -474,6 +518,7 @@ int convert_one(const Options& o) {
     const uint32_t R = o.R();
     if (m2s_convert(ctx, R, &total) != M2S_OK) return die("convert");
     const auto t3 = Clock::now();
+    if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
     if (o.bake_light) {
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
         if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
@@ -815,6 +860,25 @@ int main(int argc, char** argv) {
         else if (a == "--split-screen") { o.split_screen = std::atof(next()); if (!(o.split_screen >= 0.0 && o.split_screen <= 1.0)) { usage(); return 2; } }
         else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); o.preview_mode_set = true; if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
         else if (a == "--score") { o.score_views = std::atoi(next()); if (o.score_views < 1 || o.score_views > 4096) { usage(); return 2; } }
+        else if (a == "--prune") { o.prune_views = std::atoi(next()); if (o.prune_views < 1 || o.prune_views > 4096) { usage(); return 2; } }
+        else if (a == "--prune-elevations") {
+            o.prune_elevations.clear();
+            std::string v = next();
+            size_t at = 0;
+            while (at <= v.size()) {
+                const size_t c = std::min(v.find(',', at), v.size());
+                char* end = nullptr;
+                const std::string tok = v.substr(at, c - at);
+                const double e = std::strtod(tok.c_str(), &end);
+                if (tok.empty() || *end || !(e > -90.0 && e < 90.0)) { usage(); return 2; }
+                o.prune_elevations.push_back(e);
+                at = c + 1;
+            }
+            if (o.prune_elevations.empty() || o.prune_elevations.size() > 64) { usage(); return 2; }
+        }
+        else if (a == "--prune-weight") { o.prune_weight = std::atof(next()); if (!(o.prune_weight >= 0.0 && o.prune_weight <= 1.0)) { usage(); return 2; } }
+        else if (a == "--prune-pixels") { o.prune_pixels = std::atol(next()); if (o.prune_pixels < 0 || o.prune_pixels > 0x7FFFFFFFl) { usage(); return 2; } }
+        else if (a == "--prune-count-weight") { o.prune_count_weight = std::atof(next()); if (!(o.prune_count_weight >= 0.0 && o.prune_count_weight <= 1.0)) { usage(); return 2; } }
         else if (a == "--score-elevation") { o.score_elevation = std::atof(next()); if (!(o.score_elevation > -90.0 && o.score_elevation < 90.0)) { usage(); return 2; } }
         else if (a == "--score-mask") { o.score_mask = std::atoi(next()); if (o.score_mask < 0 || o.score_mask > 3) { usage(); return 2; } }
         else if (a == "--score-map") o.score_map = next();
@@ -834,6 +898,7 @@ int main(int argc, char** argv) {
     }
     if (o.gpus < 1 || o.gpus > 64) { usage(); return 2; }
     // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
+    if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
         if (o.out_dir.empty() || !pos.empty()) { usage(); return 2; }
