@@ -78,23 +78,6 @@ void build_table(uint32_t nt, uint32_t np, float* out) {
     }
 }
 
-m2s_status ensure_bake_common(m2s_ctx* c) {
-    for (hipEvent_t& e : c->bake_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    return M2S_OK;
-}
-
-// the context's records, or the caller's
-m2s_status pick_records(m2s_ctx* c, const void*& d_records, uint64_t& n) {
-    if (!d_records) {
-        if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run, no records were uploaded and none were passed");
-        if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-        d_records = c->last_records;
-        n = c->last_stored;
-    }
-    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
-    return M2S_OK;
-}
-
 void model_matrices(const float model_to_world[16], float M[16], float MinvT[16]) {
     m2s_prepass_params pp;
     std::memset(&pp, 0, sizeof(pp));
@@ -121,7 +104,7 @@ m2s_status m2s_bake_directions(uint32_t n_theta, uint32_t n_phi, float* out, uin
 
 m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light_params* lp, const void* d_records, uint64_t n) {
     if (!c || !bp || !lp) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     const uint32_t nt = bp->n_theta ? bp->n_theta : 8, np = bp->n_phi ? bp->n_phi : 16;
     if (bp->degree > 3) return fail(c, M2S_ERR_INVALID, "degree above 3");
     if (!table_sizes_ok(nt, np)) return fail(c, M2S_ERR_INVALID, "n_theta must be 4 or 8 and n_phi 8 or 16 (0: the default, 8 x 16)");
@@ -129,16 +112,16 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     if (m2s_status s = pick_records(c, d_records, n)) return s;
     if (bp->use_shadows && !c->shadow_S) return fail(c, M2S_ERR_STATE, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
     HIPCHK(c, hipSetDevice(c->device));
-    if (m2s_status s = ensure_bake_common(c)) return s;
+    M2S_TRY(c->bake_ev.ensure(c->err));
     c->sh_valid = false;
     c->bake_has_counts = false;
     c->sh_n = 0;
-    if (m2s_status s = grow_buffer(c, c->d_sh, c->sh_cap, n, 48 * sizeof(float))) return s;
+    M2S_TRY(c->d_sh.reserve(c->err, n, 48 * sizeof(float)));
     const bool counts = bp->want_shadow_counts != 0;
-    if (counts) if (m2s_status s = grow_buffer(c, c->d_bake_counts, c->bake_counts_cap, n, 1)) return s;
+    if (counts) M2S_TRY(c->d_bake_counts.reserve(c->err, n, 1));
     if (c->bake_table_nt != nt || c->bake_table_np != np) {
         c->bake_table_nt = c->bake_table_np = 0;
-        if (!c->d_bake_table) HIPCHK(c, hipMalloc((void**)&c->d_bake_table, 128 * kBakeTableRow * sizeof(float)));
+        M2S_TRY(c->d_bake_table.reserve(c->err, 128 * kBakeTableRow, sizeof(float)));
         float h_table[128 * kBakeTableRow];
         build_table(nt, np, h_table);
         HIPCHK(c, hipMemcpy(c->d_bake_table, h_table, (size_t)nt * np * kBakeTableRow * sizeof(float), hipMemcpyHostToDevice));
@@ -155,8 +138,8 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     k.use_shadows = bp->use_shadows ? 1u : 0u;
     k.viewer_metallic = bp->viewer_metallic ? 1u : 0u;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->bake_ev[0], c->stream));
-    HIPCHK(c, launch_bake_sh(k, (const float4*)d_records, (uint32_t)n, c->d_bake_table, k.use_shadows ? c->d_shadow_cube : nullptr, c->d_sh,
-                             counts ? c->d_bake_counts : nullptr, c->stream));
+    HIPCHK(c, launch_bake_sh(k, (const float4*)d_records, (uint32_t)n, c->d_bake_table, k.use_shadows ? c->d_shadow_cube.get() : nullptr, c->d_sh,
+                             counts ? c->d_bake_counts.get() : nullptr, c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->bake_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_bake_ms, c->bake_ev[0], c->bake_ev[1]));
@@ -168,7 +151,7 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     return M2S_OK;
 }
 
-const void* m2s_device_sh(const m2s_ctx* c) { return c && c->sh_valid ? c->d_sh : nullptr; }
+const void* m2s_device_sh(const m2s_ctx* c) { return c && c->sh_valid ? c->d_sh.get() : nullptr; }
 
 m2s_status m2s_download_sh(m2s_ctx* c, float* dst, uint64_t capacity_records) {
     if (!c) return M2S_ERR_INVALID;
@@ -197,7 +180,7 @@ float m2s_last_bake_ms(const m2s_ctx* c) { return c ? c->last_bake_ms : 0.0f; }
 m2s_status m2s_sh_shade_records(m2s_ctx* c, const float model_to_world[16], const float camera_position[3], const void* d_records, uint64_t n,
                                 void* d_dst) {
     if (!c || !model_to_world || !camera_position) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (m2s_status s = pick_records(c, d_records, n)) return s;
     if (!c->sh_valid || c->sh_n != n) return fail(c, M2S_ERR_STATE, "no baked coefficients for this many records (run m2s_bake_light on them)");
     if (n && !d_dst) return fail(c, M2S_ERR_INVALID, "d_dst is NULL");

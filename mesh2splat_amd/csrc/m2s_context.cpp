@@ -182,48 +182,11 @@ void m2s_destroy(m2s_ctx* c) {
     if (c->d_records) (void)hipFree(c->d_records);
     if (c->d_records_b) (void)hipFree(c->d_records_b);
     if (c->stream_b) { (void)hipStreamSynchronize(c->stream_b); (void)hipStreamDestroy(c->stream_b); }
-    if (c->d_sorted) (void)hipFree(c->d_sorted);
-    if (c->d_quads) (void)hipFree(c->d_quads);
-    if (c->d_sorted_quads) (void)hipFree(c->d_sorted_quads);
-    for (int k = 0; k < 5; ++k) if (c->d_gbuf[k]) (void)hipFree(c->d_gbuf[k]);
-    for (void* p : { (void*)c->d_splat_rec, (void*)c->d_splat_cnt, (void*)c->d_splat_off, (void*)c->d_splat_pairs, (void*)c->d_splat_tiles,
-                     c->d_splat_temp, (void*)c->d_splat_totals })
-        if (p) (void)hipFree(p);
-    if (c->h_splat) (void)hipHostFree(c->h_splat);
-    for (void* p : { c->d_shadow_quads, (void*)c->d_shadow_cube, (void*)c->d_sh_tab, (void*)c->d_sh_views, c->d_sh_rec, (void*)c->d_sh_cnt,
-                     (void*)c->d_sh_off, (void*)c->d_sh_pairs, c->d_sh_temp, (void*)c->d_sh_totals, (void*)c->d_frame, (void*)c->d_shadow_counts })
-        if (p) (void)hipFree(p);
-    if (c->h_sh) (void)hipHostFree(c->h_sh);
-    for (hipEvent_t e : c->light_ev) if (e) (void)hipEventDestroy(e);
-    for (void* p : { (void*)c->d_md_image, (void*)c->d_md_deferred, c->d_md_rec, (void*)c->d_md_cnt, (void*)c->d_md_off, (void*)c->d_md_pairs, c->d_md_temp,
-                     (void*)c->d_md_totals })
-        if (p) (void)hipFree(p);
-    if (c->h_md) (void)hipHostFree(c->h_md);
-    for (hipEvent_t e : c->md_ev) if (e) (void)hipEventDestroy(e);
-    if (c->d_mr_vis) (void)hipFree((void*)c->d_mr_vis);
-    for (int k = 0; k < 5; ++k) if (c->d_mr_gbuf[k]) (void)hipFree(c->d_mr_gbuf[k]);
-    for (hipEvent_t e : c->mr_ev) if (e) (void)hipEventDestroy(e);
-    for (void* p : { (void*)c->d_mesh_frame, (void*)c->d_score_acc, (void*)c->d_score_map }) if (p) (void)hipFree(p);
-    if (c->h_score) (void)hipHostFree(c->h_score);
-    for (hipEvent_t e : c->score_ev) if (e) (void)hipEventDestroy(e);
-    for (void* p : { (void*)c->d_sh, (void*)c->d_bake_counts, (void*)c->d_bake_table }) if (p) (void)hipFree(p);
-    for (hipEvent_t e : c->bake_ev) if (e) (void)hipEventDestroy(e);
-    for (void* p : { (void*)c->d_sq_src, (void*)c->d_contrib, (void*)c->d_prune_u32, c->d_prune_temp, c->d_prune_stage }) if (p) (void)hipFree(p);
-    for (hipEvent_t e : c->prune_ev) if (e) (void)hipEventDestroy(e);
-    if (c->d_loaded) (void)hipFree(c->d_loaded);
-    if (c->d_rows) (void)hipFree(c->d_rows);
-    for (int k = 0; k < 2; ++k) if (c->h_export[k]) (void)hipHostFree(c->h_export[k]);
     for (int k = 0; k < 2; ++k) {
         if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
         if (c->d_stage[k]) (void)hipFree(c->d_stage[k]);
         if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
     }
-    if (c->d_pp_depths) (void)hipFree(c->d_pp_depths);
-    if (c->d_pp_chain) (void)hipFree(c->d_pp_chain);
-    if (c->d_pp_depthtex) (void)hipFree(c->d_pp_depthtex);
-    if (c->d_sort_u32) (void)hipFree(c->d_sort_u32);
-    if (c->d_pos_plane) (void)hipFree(c->d_pos_plane);
-    if (c->d_sort_temp) (void)hipFree(c->d_sort_temp);
     if (c->d_total) (void)hipFree(c->d_total);
     if (c->h_total) (void)hipHostFree(c->h_total);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
@@ -233,7 +196,7 @@ void m2s_destroy(m2s_ctx* c) {
         if (sl.t1) (void)hipEventDestroy(sl.t1);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the viewer passes' buffers, pinned blocks and events go with their members (m2s_devbuf.h)
 }
 
 m2s_status m2s_set_triangle_range(m2s_ctx* c, uint64_t first, uint64_t count) {
@@ -260,7 +223,7 @@ m2s_status m2s_set_pipeline(m2s_ctx* c, int pipeline) {
     if (!c) return M2S_ERR_INVALID;
     if (pipeline < M2S_PIPELINE_AUTO || pipeline > M2S_PIPELINE_LEAN) return fail(c, M2S_ERR_INVALID, "unknown pipeline");
     if (pipeline == 2) return fail(c, M2S_ERR_INVALID, "pipeline 2 (the one-wave-per-batch kernel of rounds 1-5) no longer exists: use M2S_PIPELINE_TEAM");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (c->pipeline != pipeline) {   // what was remembered about this scene under the old setting no longer applies
         c->rinfo.clear();
         ++c->rinfo_gen;
@@ -284,7 +247,7 @@ m2s_status m2s_set_keep_positions(m2s_ctx* c, int enabled) {
 
 m2s_status m2s_debug_set_launch_counter(m2s_ctx* c, uint32_t value) {
     if (!c) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     c->epoch = value;
     return M2S_OK;
 }
@@ -292,7 +255,7 @@ m2s_status m2s_debug_set_launch_counter(m2s_ctx* c, uint32_t value) {
 m2s_status m2s_set_async_lanes(m2s_ctx* c, int lanes) {
     if (!c) return M2S_ERR_INVALID;
     if (lanes != 1 && lanes != 2) return fail(c, M2S_ERR_INVALID, "lanes must be 1 or 2");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     c->lanes = lanes;
     return M2S_OK;
 }

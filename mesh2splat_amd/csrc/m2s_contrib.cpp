@@ -28,7 +28,7 @@ m2s_status m2s_upload_quad_sources(m2s_ctx* c, const uint32_t* host_sources, uin
         if (host_sources[i] >= c->last_stored) return fail(c, M2S_ERR_INVALID, "a source index is not below the number of records");
     HIPCHK(c, hipSetDevice(c->device));
     c->sq_src = nullptr;
-    if (m2s_status s = grow_buffer(c, c->d_sq_src, c->sq_src_cap, n, sizeof(uint32_t))) return s;
+    M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
     HIPCHK(c, hipMemcpy(c->d_sq_src, host_sources, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->sq_src = c->d_sq_src;
     c->sq_src_epoch = c->records_epoch;
@@ -37,15 +37,15 @@ m2s_status m2s_upload_quad_sources(m2s_ctx* c, const uint32_t* host_sources, uin
 
 m2s_status m2s_contrib_begin(m2s_ctx* c) {
     if (!c) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
     if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
     const uint64_t n = c->last_stored;
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
     HIPCHK(c, hipSetDevice(c->device));
     c->contrib_active = false;
-    if (m2s_status s = grow_buffer(c, c->d_contrib, c->contrib_cap, std::max<uint64_t>(n, 1), 2 * sizeof(uint32_t))) return s;
-    HIPCHK(c, hipMemsetAsync(c->d_contrib, 0, c->contrib_cap * 2 * sizeof(uint32_t), c->stream));
+    M2S_TRY(c->d_contrib.reserve(c->err, std::max<uint64_t>(n, 1), 2 * sizeof(uint32_t)));
+    HIPCHK(c, hipMemsetAsync(c->d_contrib, 0, c->d_contrib.cap() * 2 * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->contrib_of = c->last_records;
     c->contrib_n = n;
@@ -57,7 +57,7 @@ m2s_status m2s_contrib_begin(m2s_ctx* c) {
 m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float count_weight) {
     if (!c || !p) return M2S_ERR_INVALID;
     const int W = p->resolution[0], H = p->resolution[1];
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     if (p->render_mode < 0 || p->render_mode > 6 || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6 or reserved != 0");
     if (p->render_mode == 4) return fail(c, M2S_ERR_INVALID, "render mode 4 (overdraw) has no fragment weight");
     if (!(count_weight >= 0.0f) || !std::isfinite(count_weight)) return fail(c, M2S_ERR_INVALID, "count_weight is negative or not finite");
@@ -71,8 +71,8 @@ m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float c
     SplatBins bins;
     if (m2s_status s = splat_bin(c, c->d_sorted_quads, nq, W, H, &bins)) return s;
     if (bins.pairs)
-        HIPCHK(c, contrib_blend((const float4*)c->d_splat_rec, bins.vals, bins.ranges, bins.order, W, H, c->sq_src, count_weight, c->d_contrib,
-                                c->d_contrib + c->contrib_cap, c->stream));
+        HIPCHK(c, contrib_blend((const float4*)c->splat_work.rec.get(), bins.vals, bins.ranges, bins.order, W, H, c->sq_src, count_weight, c->d_contrib,
+                                c->d_contrib + c->d_contrib.cap(), c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) {
@@ -83,7 +83,7 @@ m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float c
 }
 
 const void* m2s_device_contrib(const m2s_ctx* c, uint32_t which) {
-    return c && which < 2 && contrib_valid(c) ? c->d_contrib + which * c->contrib_cap : nullptr;
+    return c && which < 2 && contrib_valid(c) ? c->d_contrib + which * c->d_contrib.cap() : nullptr;
 }
 
 m2s_status m2s_download_contrib(m2s_ctx* c, uint32_t* dst_wmax, uint32_t* dst_npix, uint64_t capacity) {
@@ -93,7 +93,7 @@ m2s_status m2s_download_contrib(m2s_ctx* c, uint32_t* dst_wmax, uint32_t* dst_np
     if (!c->contrib_n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (dst_wmax) HIPCHK(c, hipMemcpy(dst_wmax, c->d_contrib, c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (dst_npix) HIPCHK(c, hipMemcpy(dst_npix, c->d_contrib + c->contrib_cap, c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (dst_npix) HIPCHK(c, hipMemcpy(dst_npix, c->d_contrib + c->d_contrib.cap(), c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -108,10 +108,10 @@ m2s_status m2s_last_contrib_stage_ms(const m2s_ctx* c, float out_ms[3]) {
 m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) {
     if (!c || !p) return M2S_ERR_INVALID;
     if (p->reserved != 0 || std::isnan(p->min_weight)) return fail(c, M2S_ERR_INVALID, "min_weight is NaN or reserved != 0");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin, m2s_contrib_accumulate)");
     HIPCHK(c, hipSetDevice(c->device));
-    for (hipEvent_t& e : c->prune_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    M2S_TRY(c->prune_ev.ensure(c->err));
     const uint64_t n = c->last_stored;
     const uint32_t R = c->last_R;
     uint64_t kept = 0, by_w = 0, by_p = 0;
@@ -119,18 +119,18 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
     if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[0], c->stream));
     if (n) {
         // flags | offsets | two 64-bit counters
-        if (m2s_status s = grow_buffer(c, c->d_prune_u32, c->prune_cap, n, 2 * sizeof(uint32_t))) return s;
+        M2S_TRY(c->d_prune_u32.reserve(c->err, n, 2 * sizeof(uint32_t)));
         unsigned long long* counters = nullptr;
         {   // (the counters live behind the scan's work area, 16-byte aligned)
             const uint64_t want = align_up(prune_scan_temp_bytes((uint32_t)n), 16) + 2 * sizeof(unsigned long long);
-            if (m2s_status s = grow_buffer(c, c->d_prune_temp, c->prune_temp_cap, want, 1)) return s;
-            counters = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_prune_temp) + c->prune_temp_cap - 2 * sizeof(unsigned long long));
+            M2S_TRY(c->d_prune_temp.reserve(c->err, want, 1));
+            counters = reinterpret_cast<unsigned long long*>(c->d_prune_temp + c->d_prune_temp.cap() - 2 * sizeof(unsigned long long));
         }
         uint32_t* flags = c->d_prune_u32;
-        uint32_t* offsets = flags + c->prune_cap;
+        uint32_t* offsets = flags + c->d_prune_u32.cap();
         HIPCHK(c, hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), c->stream));
-        HIPCHK(c, prune_flags_scan(c->d_contrib, c->d_contrib + c->contrib_cap, (uint32_t)n, p->min_weight, p->min_pixels, flags, offsets, counters,
-                                   c->d_prune_temp, c->prune_temp_cap - 2 * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, prune_flags_scan(c->d_contrib, c->d_contrib + c->d_contrib.cap(), (uint32_t)n, p->min_weight, p->min_pixels, flags, offsets, counters,
+                                   c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
         unsigned long long h[2] = { 0, 0 };
         HIPCHK(c, hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -140,15 +140,15 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
         // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
         const bool in_pool = c->last_records == c->d_records;
         const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
-        if (stage_bytes) if (m2s_status s = grow_buffer(c, c->d_prune_stage, c->prune_stage_cap, stage_bytes, 1)) return s;
+        if (stage_bytes) M2S_TRY(c->d_prune_stage.reserve(c->err, stage_bytes, 1));
         const void* src = c->last_records;
         if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
         if (kept) {
-            float4* dst = in_pool ? (float4*)c->d_prune_stage : (float4*)c->d_records;
+            float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->d_records;
             HIPCHK(c, prune_compact((const float4*)src, flags, offsets, (uint32_t)n, 6, dst, c->stream));
             if (in_pool) HIPCHK(c, hipMemcpyAsync(c->d_records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
             if (sh) {
-                HIPCHK(c, prune_compact((const float4*)c->d_sh, flags, offsets, (uint32_t)n, 12, (float4*)c->d_prune_stage, c->stream));
+                HIPCHK(c, prune_compact((const float4*)c->d_sh.get(), flags, offsets, (uint32_t)n, 12, c->d_prune_stage, c->stream));
                 HIPCHK(c, hipMemcpyAsync(c->d_sh, c->d_prune_stage, kept * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             }
         }

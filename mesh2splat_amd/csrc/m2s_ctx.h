@@ -9,8 +9,10 @@
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
+//   m2s_devbuf.h     the owners of the viewer passes' buffers, pinned blocks and events (DevBuf, PinnedBuf, EventSet, BinWork)
 #pragma once
 #include "../../include/m2s.h"
+#include "m2s_devbuf.h"
 #include "m2s_device.h"
 
 #include <cstdint>
@@ -24,6 +26,20 @@ constexpr uint64_t kMaxTriangles = (1ull << 28) - 1;  // 32-bit byte offsets int
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline const char* const kStaleMsg = "the records of the conversion last waited for have been overwritten by a later submission at another R "
                                      "(wait for it, or submit into your own buffers)";
+inline const char* const kInFlightMsg = "conversions are still in flight: m2s_convert_wait first";
+// The five planes of a G-buffer (8, 8, 4, 8, 4 bytes per pixel), each with room for the same number of pixels; ptr: as the kernels take them.
+struct GBufPlanes {
+    DevBuf<void> plane[5];
+    void* ptr[5] = {};
+    m2s_status reserve(std::string& err, uint64_t px) {
+        for (int k = 0; k < 5; ++k) {
+            const m2s_status s = plane[k].reserve(err, px, (k == 2 || k == 4) ? 4 : 8);
+            ptr[k] = plane[k].get();
+            if (s) return s;
+        }
+        return M2S_OK;
+    }
+};
 }  // namespace m2s_host
 
 constexpr int kBandSlotsMax = 64;   // (scene, R) entries remembered per context: band tables, decisions
@@ -137,33 +153,29 @@ struct m2s_ctx {
     uint32_t last_R = 0;
 
     // depth sort (f-2)
-    void* d_sorted = nullptr;
-    uint64_t sorted_cap = 0, sorted_n = 0;
-    uint32_t* d_sort_u32 = nullptr;   // keys_in | vals_in | keys_out | vals_out
+    m2s_host::DevBuf<float4> d_sorted;     // capacity in records
+    uint64_t sorted_n = 0;
+    m2s_host::DevBuf<uint32_t> d_sort_u32;   // keys_in | vals_in | keys_out | vals_out: capacity in records (four words each), sliced by the CURRENT n
     uint32_t sorted_key_offset = 0;   // keys_out holds key - this (m2s_device_sorted_keys adds it back once)
-    void* d_sort_temp = nullptr;
-    size_t sort_temp_cap = 0;
-    uint64_t sort_u32_cap = 0;
+    m2s_host::DevBuf<void> d_sort_temp;      // capacity: the bytes last asked for
     float last_sort_ms = 0.0f;
     float last_sort_stage_ms[3] = { 0, 0, 0 };   // keys | radix sort | gather of the last m2s_sort_by_depth (profiling on)
     // the positions of the current records as a compact plane (16 B each), left behind by the first depth sort after the records
     // changed and used for the keys of every later one (m2s_sort.hip); valid for (pos_plane_of, pos_plane_n, pos_plane_epoch)
-    void* d_pos_plane = nullptr;
-    uint64_t pos_plane_cap = 0, pos_plane_n = 0, pos_plane_epoch = 0;
+    m2s_host::DevBuf<float4> d_pos_plane;
+    uint64_t pos_plane_n = 0, pos_plane_epoch = 0;
     const void* pos_plane_of = nullptr;
     bool keep_positions = false;      // m2s_set_keep_positions: conversions leave the plane behind themselves where their kernel can (k_sparse)
     uint64_t records_epoch = 1;       // advances whenever the records behind last_records may have changed
     // viewer prepass (m2s_prepass): survivors, their depths, the look-back chain of its kernel, a copy of the depth image
-    void* d_quads = nullptr;
-    float* d_pp_depths = nullptr;
-    uint64_t pp_cap = 0, pp_depths_cap = 0, pp_visible = 0;
-    unsigned long long* d_pp_chain = nullptr;
-    uint64_t pp_chain_words = 0;
+    m2s_host::DevBuf<float4> d_quads;
+    m2s_host::DevBuf<float> d_pp_depths;
+    uint64_t pp_visible = 0;
+    m2s_host::DevBuf<unsigned long long> d_pp_chain;     // capacity in words
     uint32_t pp_epoch = 0;
-    float* d_pp_depthtex = nullptr;
-    uint64_t pp_depthtex_cap = 0;
+    m2s_host::DevBuf<float> d_pp_depthtex;
     float last_prepass_ms = 0.0f;
-    m2s_gaussian* h_export[2] = { nullptr, nullptr };   // pinned chunk buffers of m2s_export_ply
+    m2s_host::PinnedBuf<m2s_gaussian> h_export[2];      // pinned chunk buffers of m2s_export_ply
     // upload staging: two pinned host chunks (filled by a few host threads while the previous chunk is on the bus) and
     // two device chunks for the AoS -> SoA repack; allocated at the first upload, kept
     void* h_stage[2] = { nullptr, nullptr };
@@ -171,29 +183,16 @@ struct m2s_ctx {
     hipEvent_t stage_ev[2] = { nullptr, nullptr };
     void* scene_arena = nullptr;             // one allocation for mesh table, textures, combo textures and work buffers
     float last_upload_ms[5] = { 0, 0, 0, 0, 0 }; // [0] total, [1] geometry, [2] textures + mips + combo, [3] allocations, [4] warm_scene
-    void* d_rows = nullptr;                  // m2s_export_ply: .ply rows encoded on the device (formats 1 and 2)
-    uint64_t rows_cap = 0;                   // bytes
-    void* d_loaded = nullptr;                // m2s_upload_records (a loaded .ply)
-    uint64_t loaded_cap = 0;
-    void* d_sorted_quads = nullptr;          // m2s_sort_prepass
-    uint64_t sq_cap = 0, sq_n = 0;
+    m2s_host::DevBuf<uint8_t> d_rows;        // m2s_export_ply: .ply rows encoded on the device (formats 1 and 2); capacity in bytes
+    m2s_host::DevBuf<void> d_loaded;         // m2s_upload_records (a loaded .ply)
+    m2s_host::DevBuf<float4> d_sorted_quads; // m2s_sort_prepass
+    uint64_t sq_n = 0;
     float last_sort_prepass_ms = 0.0f;
     // splat pass (m2s_splat.cpp): the five G-buffer planes of the last call and the pass's grow-only work buffers
-    void* d_gbuf[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    uint64_t gbuf_cap_px = 0;                // pixels every plane has room for
+    m2s_host::GBufPlanes d_gbuf;
     int32_t gbuf_w = 0, gbuf_h = 0;          // resolution of the planes' contents (0: no splat has run)
-    void* d_splat_rec = nullptr;             // per quad: 128-byte record, tile count (u32), exclusive scan of the counts (u64)
-    uint32_t* d_splat_cnt = nullptr;
-    unsigned long long* d_splat_off = nullptr;
-    uint64_t splat_quad_cap = 0;
-    uint32_t* d_splat_pairs = nullptr;       // keys_in | vals_in | keys_out | vals_out, splat_pairs_cap each
-    uint64_t splat_pairs_cap = 0;
-    uint32_t* d_splat_tiles = nullptr;       // ranges (2 words) | lengths | sorted lengths | order, splat_tiles_cap tiles each
-    uint64_t splat_tiles_cap = 0;
-    void* d_splat_temp = nullptr;            // scan / radix sort work area
-    size_t splat_temp_cap = 0;
-    unsigned long long* d_splat_totals = nullptr;   // [0] pairs, [1] skipped quads, [2] fragments blended
-    unsigned long long* h_splat = nullptr;          // pinned copy of those three words
+    m2s_host::BinWork splat_work;            // per quad a 128-byte record; totals: [0] pairs, [1] skipped quads, [2] fragments blended
+    m2s_host::DevBuf<uint32_t> d_splat_tiles;   // ranges (2 words) | lengths | sorted lengths | order, one capacity of tiles each
     float last_splat_ms = 0.0f;
     float last_splat_stage_ms[3] = { 0, 0, 0 };     // setup + bin, grouping, blend (profiling on)
     uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
@@ -201,112 +200,80 @@ struct m2s_ctx {
     // permutation in d_sort_u32 (an alias: dropped by whatever rewrites those words); compacting path: d_sq_src, written by k_prepass
     const uint32_t* sq_src = nullptr;        // nullptr: absent
     uint64_t sq_src_epoch = 0;               // records_epoch they index into
-    uint32_t* d_sq_src = nullptr;
-    uint64_t sq_src_cap = 0;
-    // contribution pass and pruning (m2s_contrib.cpp): wmax | npix, contrib_cap words each, valid for (contrib_of, contrib_n, contrib_epoch)
-    uint32_t* d_contrib = nullptr;
-    uint64_t contrib_cap = 0, contrib_n = 0, contrib_epoch = 0;
+    m2s_host::DevBuf<uint32_t> d_sq_src;
+    // contribution pass and pruning (m2s_contrib.cpp): wmax | npix, one capacity of words each, valid for (contrib_of, contrib_n, contrib_epoch)
+    m2s_host::DevBuf<uint32_t> d_contrib;
+    uint64_t contrib_n = 0, contrib_epoch = 0;
     const void* contrib_of = nullptr;
     bool contrib_active = false;
     float last_contrib_ms = 0.0f;
     float last_contrib_stage_ms[3] = { 0, 0, 0 };
-    uint32_t* d_prune_u32 = nullptr;         // flags | offsets, prune_cap words each, then two counters (u64)
-    uint64_t prune_cap = 0;
-    void* d_prune_temp = nullptr;            // scan work area
-    uint64_t prune_temp_cap = 0;
-    void* d_prune_stage = nullptr;           // survivors on their way back into the buffer they came from
-    uint64_t prune_stage_cap = 0;            // bytes
+    m2s_host::DevBuf<uint32_t> d_prune_u32;  // flags | offsets, one capacity of words each
+    m2s_host::DevBuf<char> d_prune_temp;     // scan work area, then two counters (u64) in its last 16 bytes; capacity in bytes
+    m2s_host::DevBuf<float4> d_prune_stage;  // survivors on their way back into the buffer they came from; capacity in bytes
     uint64_t last_prune_counts[4] = { 0, 0, 0, 0 };
     float last_prune_ms = 0.0f;
-    hipEvent_t prune_ev[2] = {};
+    m2s_host::EventSet<2> prune_ev;
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
-    void* d_shadow_quads = nullptr;          // 48 B each
-    uint64_t shadow_quads_cap = 0;
+    m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each
     uint32_t shadow_base[7] = { 0, 0, 0, 0, 0, 0, 0 };   // first quad of every face's list; [6] = all quads (of the last m2s_shadow)
     bool shadow_lists = false;               // the lists of the last m2s_shadow exist (false after m2s_upload_shadow_cubemap)
-    float* d_shadow_cube = nullptr;          // float[6][S][S]
-    uint64_t shadow_cube_cap = 0;            // texels
+    m2s_host::DevBuf<float> d_shadow_cube;   // float[6][S][S]; capacity in texels
     int32_t shadow_S = 0;                    // 0: no cube yet
-    uint32_t* d_sh_tab = nullptr;            // stage A: counts | offsets, sh_tab_cap words each
-    uint64_t sh_tab_cap = 0;
-    float* d_sh_views = nullptr;             // six view matrices (96 floats) | bases (8 words)
-    void* d_sh_rec = nullptr;                // stage B: per quad 48-byte record, tile count (u32), scan of the counts (u64)
-    uint32_t* d_sh_cnt = nullptr;
-    unsigned long long* d_sh_off = nullptr;
-    uint64_t sh_quad_cap = 0;
-    uint32_t* d_sh_pairs = nullptr;          // keys_in | vals_in | keys_out | vals_out, sh_pairs_cap each
-    uint64_t sh_pairs_cap = 0;
-    void* d_sh_temp = nullptr;               // scan / radix sort work area
-    uint64_t sh_temp_cap = 0;
-    unsigned long long* d_sh_totals = nullptr;   // [0] pairs, [1] skipped quads, [2] atomics sent
-    unsigned long long* h_sh = nullptr;          // pinned: those three words, then the bases
-    hipEvent_t light_ev[10] = {};
+    m2s_host::DevBuf<uint32_t> d_sh_tab;     // stage A: counts | offsets, one capacity of words each
+    m2s_host::DevBuf<float> d_sh_views;      // six view matrices (96 floats) | bases (8 words)
+    m2s_host::BinWork shadow_work;           // stage B: per quad a 48-byte record; totals: [0] pairs, [1] skipped quads, [2] atomics sent
+                                             // (pinned: those three words, then the bases and the view matrices); its work area serves stage A too
+    m2s_host::EventSet<10> light_ev;
     float last_shadow_ms = 0.0f;
     float last_shadow_stage_ms[3] = { 0, 0, 0 };    // stage A (count + scan + emit), setup + binning, raster (profiling on)
     uint64_t last_shadow_counts[9] = {};            // quads of face 0..5, (tile, quad) pairs, texel writes (atomics sent), quads skipped
     // relighting pass: the frame, the optional plane of shadow counts
-    uint32_t* d_frame = nullptr;
-    uint8_t* d_shadow_counts = nullptr;
-    uint64_t frame_cap_px = 0;
+    m2s_host::DevBuf<uint32_t> d_frame;      // capacities in pixels
+    m2s_host::DevBuf<uint8_t> d_shadow_counts;
     int32_t frame_w = 0, frame_h = 0;        // 0: no relight has run
     bool frame_has_counts = false;
     float last_relight_ms = 0.0f;
     // mesh depth prepass (m2s_meshdepth.cpp): the image and the pass's grow-only work buffers
-    float* d_md_image = nullptr;             // float[H][W], row 0 = bottom
-    uint64_t md_image_cap = 0;               // texels
+    m2s_host::DevBuf<float> d_md_image;      // float[H][W], row 0 = bottom; capacity in texels
     int32_t md_w = 0, md_h = 0;              // 0: no image yet
     int32_t md_inplace = -1;                 // m2s_debug_set_mesh_depth_inplace (-1: the default, kMdInplace)
-    uint32_t* d_md_deferred = nullptr;       // triangles the setup kernel left to the binned path (capacity: md_tri_cap)
-    uint64_t md_tri_cap = 0;
-    void* d_md_rec = nullptr;                // per deferred triangle six slots: 48-byte record, tile count (u32), scan of the counts (u64)
-    uint32_t* d_md_cnt = nullptr;
-    unsigned long long* d_md_off = nullptr;
-    uint64_t md_slot_cap = 0;
-    uint32_t* d_md_pairs = nullptr;          // keys_in | vals_in | keys_out | vals_out, md_pairs_cap each
-    uint64_t md_pairs_cap = 0;
-    void* d_md_temp = nullptr;               // scan / radix sort work area
-    uint64_t md_temp_cap = 0;
-    unsigned long long* d_md_totals = nullptr;   // 8 words: see meshdepth_setup
-    unsigned long long* h_md = nullptr;          // pinned copy
-    hipEvent_t md_ev[6] = {};
+    m2s_host::DevBuf<uint32_t> d_md_deferred;   // triangles the setup kernel left to the binned path (capacity in triangles)
+    m2s_host::BinWork md_work;               // per deferred triangle six slots of a 48-byte record; totals: 8 words, see meshdepth_setup
+    m2s_host::EventSet<6> md_ev;
     float last_md_ms = 0.0f;
     float last_md_stage_ms[3] = { 0, 0, 0 };     // setup + in-place, clip + binning, tile raster (profiling on)
     uint64_t last_md_counts[5] = {};             // drawn, clipped, non-finite, pairs, texel updates sent
     // mesh render pass (m2s_meshrender.cpp): the visibility image and the mesh G-buffer; its work buffers are the mesh depth prepass's
-    unsigned long long* d_mr_vis = nullptr;      // uint64[H][W], row 0 = bottom: (bits of z) << 32 | global triangle index
-    uint64_t mr_vis_cap = 0;                     // pixels
-    void* d_mr_gbuf[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // layouts of d_gbuf
-    uint64_t mr_gbuf_cap_px[5] = { 0, 0, 0, 0, 0 };   // pixels each plane has room for
+    m2s_host::DevBuf<unsigned long long> d_mr_vis;   // uint64[H][W], row 0 = bottom: (bits of z) << 32 | global triangle index
+    m2s_host::GBufPlanes d_mr_gbuf;              // layouts of d_gbuf
     int32_t mr_w = 0, mr_h = 0;                  // 0: no mesh G-buffer yet
-    hipEvent_t mr_ev[2] = {};
+    m2s_host::EventSet<2> mr_ev;
     float last_mr_ms = 0.0f;
     float last_mr_stage_ms[4] = { 0, 0, 0, 0 };  // visibility setup + in-place, clip + binning, tile raster, shading (profiling on)
     uint64_t last_mr_counts[6] = {};             // drawn, clipped, non-finite, pairs, texel updates sent, culled as back-facing
     // fidelity score (m2s_light.cpp: m2s_relight_mesh; m2s_score.cpp): the mesh-lit frame, the comparison's counters and error map
-    uint32_t* d_mesh_frame = nullptr;            // uchar4[H][W], row 0 = bottom
-    uint64_t mesh_frame_cap_px = 0;
+    m2s_host::DevBuf<uint32_t> d_mesh_frame;     // uchar4[H][W], row 0 = bottom
     int32_t mesh_frame_w = 0, mesh_frame_h = 0;  // 0: no m2s_relight_mesh has run
-    unsigned long long* d_score_acc = nullptr;   // kScoreShards x kScoreCounters words (m2s_device.h), summed on the host
-    unsigned long long* h_score = nullptr;       // pinned copy
-    uint32_t* d_score_map = nullptr;             // uchar4[H][W]
-    uint64_t score_map_cap_px = 0;
+    m2s_host::DevBuf<unsigned long long> d_score_acc;    // kScoreShards x kScoreCounters words (m2s_device.h), summed on the host
+    m2s_host::PinnedBuf<unsigned long long> h_score;     // pinned copy
+    m2s_host::DevBuf<uint32_t> d_score_map;      // uchar4[H][W]
     int32_t score_map_w = 0, score_map_h = 0;    // 0: the last m2s_score_frames kept no map
-    hipEvent_t score_ev[2] = {};
+    m2s_host::EventSet<2> score_ev;
     float last_score_ms = 0.0f;
 
     // light baked into spherical harmonics (m2s_bake.cpp): the coefficient plane, the optional tap counts, the quadrature table
-    float* d_sh = nullptr;                       // float[n][48]: f_dc[3], f_rest[45] channel-major
-    uint64_t sh_cap = 0, sh_n = 0;               // records it has room for / holds
+    m2s_host::DevBuf<float> d_sh;                // float[n][48]: f_dc[3], f_rest[45] channel-major; capacity in records
+    uint64_t sh_n = 0;                           // records it holds
     bool sh_valid = false;                       // a bake has completed since the plane was last (re)allocated
     const void* sh_of = nullptr;                 // the records it was baked from, and their records_epoch when they were the context's
     uint64_t sh_epoch = 0;                       // (0: the caller's records) — m2s_prune compacts the plane of the records it compacts
-    uint8_t* d_bake_counts = nullptr;            // uint8[n]
-    uint64_t bake_counts_cap = 0;
+    m2s_host::DevBuf<uint8_t> d_bake_counts;     // uint8[n]
     bool bake_has_counts = false;
-    float* d_bake_table = nullptr;               // n_theta * n_phi rows of kBakeTableRow floats
+    m2s_host::DevBuf<float> d_bake_table;        // n_theta * n_phi rows of kBakeTableRow floats
     uint32_t bake_table_nt = 0, bake_table_np = 0;
-    hipEvent_t bake_ev[2] = {};
+    m2s_host::EventSet<2> bake_ev;
     float last_bake_ms = 0.0f;
 
     // measurement
@@ -323,11 +290,31 @@ struct m2s_ctx {
             return e_ == hipErrorOutOfMemory ? M2S_ERR_OOM : M2S_ERR_HIP;                         \
         }                                                                                         \
     } while (0)
+#define M2S_TRY(expr)                                                                             \
+    do {                                                                                          \
+        if (m2s_status s_ = (expr)) return s_;                                                    \
+    } while (0)
 
 namespace m2s_host {
 inline m2s_status fail(m2s_ctx* c, m2s_status s, const std::string& msg) {
     if (c) c->err = msg;
     return s;
+}
+// argument checks the entry points share
+inline m2s_status check_resolution(m2s_ctx* c, int W, int H, const char* what = "resolution") {
+    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, std::string(what) + " outside 1..8192");
+    return M2S_OK;
+}
+// the context's records, or the caller's
+inline m2s_status pick_records(m2s_ctx* c, const void*& d_records, uint64_t& n) {
+    if (!d_records) {
+        if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run, no records were uploaded and none were passed");
+        if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+        d_records = c->last_records;
+        n = c->last_stored;
+    }
+    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    return M2S_OK;
 }
 constexpr int kBandSlots = kBandSlotsMax;
 
@@ -344,18 +331,6 @@ hipError_t next_epoch(m2s_ctx* c, uint32_t* out);
 m2s_status ensure_records(m2s_ctx* c, uint64_t want);
 // m2s_upload.cpp
 m2s_status ensure_stage(m2s_ctx* c);
-// A grow-only device buffer of `want` units of `unit` bytes: kept when large enough, else freed and allocated anew (contents lost).
-template <typename T>
-inline m2s_status grow_buffer(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
-    if (cap >= want) return M2S_OK;
-    if (p) { (void)hipFree((void*)p); p = nullptr; }
-    cap = 0;
-    void* q = nullptr;
-    HIPCHK(c, hipMalloc(&q, (size_t)want * unit < 256 ? 256 : (size_t)want * unit));
-    p = static_cast<T*>(q);
-    cap = want;
-    return M2S_OK;
-}
 // m2s_splat.cpp
 // The stages of the splat pass in front of the blend — setup / bin, pairs, grouping by tile, tile order — over n quads on a W x H
 // viewport, in the context's splat work buffers: what m2s_splat and m2s_contrib_accumulate both start with.  Records ev[0..4] when
@@ -366,7 +341,7 @@ m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]);   // ... an
 // m2s_meshdepth.cpp
 // What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
 // tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);
-// c->h_md holds the pass's totals afterwards (m2s_device.h: meshdepth_setup, meshvis_setup).
+// c->md_work.h_totals holds the pass's totals afterwards (m2s_device.h: meshdepth_setup, meshvis_setup).
 m2s_status mesh_raster(m2s_ctx* c, const m2s::MeshDepthK& k, bool vis, void* image, float ms[3]);
 // (P V) M in glm's order, every operation rounded to fp32: the clip transform of both passes
 void mesh_pvm(const float* proj, const float* view, const float* model, float* out);

@@ -11,29 +11,14 @@ using namespace m2s_host;
 
 namespace {
 
-// grow-only device buffer: (re)allocated when `want` exceeds `cap` (units of `unit` bytes)
-template <typename T>
-m2s_status grow(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
-    if (cap >= want) return M2S_OK;
-    if (p) { (void)hipFree((void*)p); p = nullptr; }
-    cap = 0;
-    void* q = nullptr;
-    HIPCHK(c, hipMalloc(&q, std::max<size_t>(want * unit, 256)));
-    p = static_cast<T*>(q);
-    cap = want;
-    return M2S_OK;
-}
-
-constexpr int kPinnedBases = 8;     // h_sh: [0..2] totals | 8 x u32 bases from word 8 | 96 floats of view matrices from word 16
+constexpr int kPinnedBases = 8;     // shadow_work.h_totals: [0..2] totals | 8 x u32 bases from word 8 | 96 floats of view matrices from word 16
 constexpr int kPinnedViews = 16;
 constexpr size_t kPinnedBytes = kPinnedViews * 8 + 96 * sizeof(float);
 
 m2s_status ensure_light_common(m2s_ctx* c) {
-    if (!c->h_sh) HIPCHK(c, hipHostMalloc((void**)&c->h_sh, kPinnedBytes, hipHostMallocDefault));
-    if (!c->d_sh_totals) HIPCHK(c, hipMalloc((void**)&c->d_sh_totals, 4 * sizeof(unsigned long long)));
-    if (!c->d_sh_views) HIPCHK(c, hipMalloc((void**)&c->d_sh_views, 96 * sizeof(float) + 8 * sizeof(uint32_t)));
-    for (hipEvent_t& e : c->light_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    return M2S_OK;
+    M2S_TRY(c->shadow_work.reserve_totals(c->err, 4, kPinnedBytes));
+    M2S_TRY(c->d_sh_views.reserve(c->err, 96 + 8, sizeof(float)));
+    return c->light_ev.ensure(c->err);
 }
 
 // The six cameras of the light (GaussianShadowPass.cpp:91-108: glm::lookAt(light, light + axis, up)) and the 90 degree / aspect 1
@@ -80,44 +65,34 @@ m2s_status shadow_stage_b(m2s_ctx* c, const m2s_light_params* lp, int S, uint32_
     hipEvent_t* ev = c->light_ev;
     const bool prof = c->profiling;
     // ---- stage B: setup, the number of (tile, quad) pairs read back once (the pair buffers are sized from it)
-    if (c->sh_quad_cap < total) {
-        for (void* q : { c->d_sh_rec, (void*)c->d_sh_cnt, (void*)c->d_sh_off }) if (q) (void)hipFree(q);
-        c->d_sh_rec = nullptr; c->d_sh_cnt = nullptr; c->d_sh_off = nullptr;
-        c->sh_quad_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_sh_rec, (size_t)total * 48));
-        HIPCHK(c, hipMalloc((void**)&c->d_sh_cnt, (size_t)total * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_sh_off, (size_t)total * sizeof(unsigned long long)));
-        c->sh_quad_cap = total;
-    }
-    if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes(1, total, 1), 1)) return s;
+    BinWork& w = c->shadow_work;
+    M2S_TRY(w.reserve_items(c->err, total, 48));
+    M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes(1, total, 1)));
+    const float4* rec = (const float4*)w.rec.get();
     if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
-    HIPCHK(c, shadow_setup((const float4*)c->d_shadow_quads, total, fb, S, lp->light_position, lp->near_far[1], (float4*)c->d_sh_rec, c->d_sh_cnt,
-                           c->d_sh_off, c->d_sh_temp, c->sh_temp_cap, c->d_sh_totals, c->stream));
+    HIPCHK(c, shadow_setup(c->d_shadow_quads, total, fb, S, lp->light_position, lp->near_far[1], (float4*)w.rec.get(), w.cnt, w.off, w.temp,
+                           w.temp.cap(), w.d_totals, c->stream));
     if (prof) HIPCHK(c, hipEventRecord(ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_sh, c->d_sh_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w.h_totals, w.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t pairs = c->h_sh[0];
-    c->last_shadow_counts[8] = c->h_sh[1];
-    if (out_skipped) *out_skipped = c->h_sh[1];
+    const uint64_t pairs = w.h_totals[0];
+    c->last_shadow_counts[8] = w.h_totals[1];
+    if (out_skipped) *out_skipped = w.h_totals[1];
     if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
     if (pairs) {
-        if (m2s_status s = grow(c, c->d_sh_pairs, c->sh_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
-        if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes(1, 1, (uint32_t)pairs), 1)) return s;
-        const uint64_t pc = c->sh_pairs_cap;
-        uint32_t* keys_in = c->d_sh_pairs;
-        uint32_t* vals_in = keys_in + pc;
-        uint32_t* keys_out = vals_in + pc;
-        uint32_t* vals_out = keys_out + pc;
+        BinWork::Pairs pr;
+        M2S_TRY(w.reserve_pairs(c->err, pairs, &pr));
+        M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes(1, 1, (uint32_t)pairs)));
         if (prof) HIPCHK(c, hipEventRecord(ev[6], c->stream));
-        HIPCHK(c, shadow_bin((const float4*)c->d_sh_rec, c->d_sh_cnt, c->d_sh_off, total, S, keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs,
-                             c->d_sh_temp, c->sh_temp_cap, c->stream));
+        HIPCHK(c, shadow_bin(rec, w.cnt, w.off, total, S, pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, w.temp, w.temp.cap(),
+                             c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[7], c->stream));
-        HIPCHK(c, shadow_raster((const float4*)c->d_sh_rec, keys_out, vals_out, (uint32_t)pairs, S, c->d_shadow_cube, c->d_sh_totals + 2, c->stream));
+        HIPCHK(c, shadow_raster(rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, S, c->d_shadow_cube, w.d_totals + 2, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[8], c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_sh + 2, c->d_sh_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w.h_totals + 2, w.d_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->last_shadow_counts[6] = pairs;
-        c->last_shadow_counts[7] = c->h_sh[2];
+        c->last_shadow_counts[7] = w.h_totals[2];
         if (prof) {
             float x = 0, y = 0;
             HIPCHK(c, hipEventElapsedTime(&x, ev[6], ev[7]));
@@ -141,19 +116,12 @@ extern "C" {
 m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_params* lp, const void* d_records, uint64_t n,
                       uint64_t out_per_face[6], uint64_t* out_skipped) {
     if (!c || !pp || !lp) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     int S = 0;
     if (m2s_status s = check_light(c, lp, &S)) return s;
-    if (pp->resolution[0] < 1 || pp->resolution[0] > 8192 || pp->resolution[1] < 1 || pp->resolution[1] > 8192)
-        return fail(c, M2S_ERR_INVALID, "renderer resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, pp->resolution[0], pp->resolution[1], "renderer resolution"));
     if (pp->resolution_target == 0) return fail(c, M2S_ERR_INVALID, "resolution_target is 0");
-    if (!d_records) {
-        if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run, no records were uploaded and none were passed");
-        if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-        d_records = c->last_records;
-        n = c->last_stored;
-    }
-    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    M2S_TRY(pick_records(c, d_records, n));
     HIPCHK(c, hipSetDevice(c->device));
     if (m2s_status s = ensure_light_common(c)) return s;
     if (out_per_face) for (int f = 0; f < 6; ++f) out_per_face[f] = 0;
@@ -163,11 +131,11 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
     for (uint32_t& b : c->shadow_base) b = 0;
     for (uint64_t& v : c->last_shadow_counts) v = 0;
     const uint64_t texels = 6ull * (uint64_t)S * (uint64_t)S;
-    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, texels, sizeof(float))) return s;
+    M2S_TRY(c->d_shadow_cube.reserve(c->err, texels, sizeof(float)));
     hipEvent_t* ev = c->light_ev;
     const bool prof = c->profiling;
     HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));                      // glClear(GL_DEPTH_BUFFER_BIT), six times
-    HIPCHK(c, hipMemsetAsync(c->d_sh_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->shadow_work.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
     const uint32_t nr = (uint32_t)n;
     uint32_t total = 0;
     float a_ms = 0, b_ms = 0, r_ms = 0;
@@ -175,34 +143,30 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
         // ---- stage A
         PrepassK k;
         prepass_prepare(*pp, n, &k);
-        float* h_views = reinterpret_cast<float*>(c->h_sh + kPinnedViews);
+        BinWork& w = c->shadow_work;
+        float* h_views = reinterpret_cast<float*>(w.h_totals + kPinnedViews);
         shadow_cameras(lp->light_position, lp->near_far[0], lp->near_far[1], h_views, k.P);
         const uint32_t nb = shadow_blocks(nr);
         const uint64_t words = 6ull * nb + 1;
-        if (c->sh_tab_cap < words) {
-            if (c->d_sh_tab) { (void)hipFree(c->d_sh_tab); c->d_sh_tab = nullptr; }
-            c->sh_tab_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_sh_tab, 2 * words * sizeof(uint32_t)));
-            c->sh_tab_cap = words;
-        }
+        M2S_TRY(c->d_sh_tab.reserve(c->err, words, 2 * sizeof(uint32_t)));
         uint32_t* cnt = c->d_sh_tab;
-        uint32_t* off = c->d_sh_tab + c->sh_tab_cap;
-        if (m2s_status s = grow(c, c->d_sh_temp, c->sh_temp_cap, shadow_temp_bytes((uint32_t)words, 1, 1), 1)) return s;
+        uint32_t* off = c->d_sh_tab + c->d_sh_tab.cap();
+        M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes((uint32_t)words, 1, 1)));
         uint32_t* d_bases = reinterpret_cast<uint32_t*>(c->d_sh_views + 96);
         HIPCHK(c, hipMemcpyAsync(c->d_sh_views, h_views, 96 * sizeof(float), hipMemcpyHostToDevice, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        HIPCHK(c, shadow_count(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, cnt, off, c->d_sh_temp, c->sh_temp_cap, d_bases, c->stream));
+        HIPCHK(c, shadow_count(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, cnt, off, w.temp, w.temp.cap(), d_bases, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        uint32_t* h_bases = reinterpret_cast<uint32_t*>(c->h_sh + kPinnedBases);
+        uint32_t* h_bases = reinterpret_cast<uint32_t*>(w.h_totals + kPinnedBases);
         HIPCHK(c, hipMemcpyAsync(h_bases, d_bases, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         total = h_bases[6];
         ShadowBases fb;
         for (int f = 0; f < 7; ++f) fb.b[f] = h_bases[f];
         if (total) {
-            if (m2s_status s = grow(c, c->d_shadow_quads, c->shadow_quads_cap, total, 48)) return s;
+            M2S_TRY(c->d_shadow_quads.reserve(c->err, total, 48));
             if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-            HIPCHK(c, shadow_emit(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, off, (float4*)c->d_shadow_quads, c->stream));
+            HIPCHK(c, shadow_emit(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, off, c->d_shadow_quads, c->stream));
             if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
             if (m2s_status st = shadow_stage_b(c, lp, S, total, fb, out_skipped, &b_ms, &r_ms)) return st;
             if (prof) {
@@ -254,12 +218,12 @@ m2s_status m2s_shadow_from_quads(m2s_ctx* c, const m2s_light_params* lp, const m
     c->shadow_lists = false;
     for (uint32_t& b : c->shadow_base) b = 0;
     for (uint64_t& v : c->last_shadow_counts) v = 0;
-    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, 6ull * (uint64_t)S * (uint64_t)S, sizeof(float))) return s;
+    M2S_TRY(c->d_shadow_cube.reserve(c->err, 6ull * (uint64_t)S * (uint64_t)S, sizeof(float)));
     HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_sh_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->shadow_work.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
     float b_ms = 0, r_ms = 0;
     if (total) {
-        if (m2s_status s = grow(c, c->d_shadow_quads, c->shadow_quads_cap, total, 48)) return s;
+        M2S_TRY(c->d_shadow_quads.reserve(c->err, total, 48));
         HIPCHK(c, hipMemcpyAsync(c->d_shadow_quads, host_quads, total * 48, hipMemcpyHostToDevice, c->stream));
         if (m2s_status s = shadow_stage_b(c, lp, S, (uint32_t)total, fb, out_skipped, &b_ms, &r_ms)) return s;
     }
@@ -275,7 +239,7 @@ m2s_status m2s_shadow_from_quads(m2s_ctx* c, const m2s_light_params* lp, const m
     return M2S_OK;
 }
 
-const void* m2s_device_shadow_cubemap(const m2s_ctx* c) { return c && c->shadow_S ? c->d_shadow_cube : nullptr; }
+const void* m2s_device_shadow_cubemap(const m2s_ctx* c) { return c && c->shadow_S ? c->d_shadow_cube.get() : nullptr; }
 
 m2s_status m2s_download_shadow_cubemap(m2s_ctx* c, float* dst, uint64_t capacity_floats) {
     if (!c || !dst) return M2S_ERR_INVALID;
@@ -295,7 +259,7 @@ m2s_status m2s_download_shadow_quads(m2s_ctx* c, uint32_t face, m2s_shadow_quad*
     if (!dst) return fail(c, M2S_ERR_INVALID, "dst is NULL");
     if (capacity < cnt) return fail(c, M2S_ERR_CAPACITY, "dst holds fewer quads than the face's list");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, (const char*)c->d_shadow_quads + first * 48, cnt * 48, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, (const char*)c->d_shadow_quads.get() + first * 48, cnt * 48, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -306,7 +270,7 @@ m2s_status m2s_upload_shadow_cubemap(m2s_ctx* c, const float* host, uint32_t S) 
     const uint64_t texels = 6ull * S * S;
     c->shadow_S = 0;
     c->shadow_lists = false;
-    if (m2s_status s = grow(c, c->d_shadow_cube, c->shadow_cube_cap, texels, sizeof(float))) return s;
+    M2S_TRY(c->d_shadow_cube.reserve(c->err, texels, sizeof(float)));
     HIPCHK(c, hipMemcpy(c->d_shadow_cube, host, texels * sizeof(float), hipMemcpyHostToDevice));
     c->shadow_S = (int32_t)S;
     return M2S_OK;
@@ -314,20 +278,15 @@ m2s_status m2s_upload_shadow_cubemap(m2s_ctx* c, const float* host, uint32_t S) 
 
 m2s_status m2s_upload_gbuffer(m2s_ctx* c, const void* const planes[5], int32_t W, int32_t H) {
     if (!c || !planes) return M2S_ERR_INVALID;
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t px = (uint64_t)W * (uint64_t)H;
     c->gbuf_w = c->gbuf_h = 0;
-    if (c->gbuf_cap_px < px) {
-        for (int k = 0; k < 5; ++k) if (c->d_gbuf[k]) { (void)hipFree(c->d_gbuf[k]); c->d_gbuf[k] = nullptr; }
-        c->gbuf_cap_px = 0;
-        for (int k = 0; k < 5; ++k) HIPCHK(c, hipMalloc(&c->d_gbuf[k], px * ((k == 2 || k == 4) ? 4 : 8)));
-        c->gbuf_cap_px = px;
-    }
+    M2S_TRY(c->d_gbuf.reserve(c->err, px));
     for (int k = 0; k < 5; ++k) {
         const size_t bytes = px * ((k == 2 || k == 4) ? 4 : 8);
-        if (planes[k]) HIPCHK(c, hipMemcpy(c->d_gbuf[k], planes[k], bytes, hipMemcpyHostToDevice));
-        else HIPCHK(c, hipMemset(c->d_gbuf[k], 0, bytes));
+        if (planes[k]) HIPCHK(c, hipMemcpy(c->d_gbuf.ptr[k], planes[k], bytes, hipMemcpyHostToDevice));
+        else HIPCHK(c, hipMemset(c->d_gbuf.ptr[k], 0, bytes));
     }
     c->gbuf_w = W;
     c->gbuf_h = H;
@@ -365,21 +324,15 @@ static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, fl
     const uint64_t px = (uint64_t)c->gbuf_w * (uint64_t)c->gbuf_h;
     c->frame_w = c->frame_h = 0;
     c->frame_has_counts = false;
-    if (c->frame_cap_px < px) {
-        if (c->d_frame) { (void)hipFree(c->d_frame); c->d_frame = nullptr; }
-        if (c->d_shadow_counts) { (void)hipFree(c->d_shadow_counts); c->d_shadow_counts = nullptr; }
-        c->frame_cap_px = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_frame, px * 4));
-        HIPCHK(c, hipMalloc((void**)&c->d_shadow_counts, px));
-        c->frame_cap_px = px;
-    }
+    M2S_TRY(c->d_frame.reserve(c->err, px, 4));
+    M2S_TRY(c->d_shadow_counts.reserve(c->err, px, 1));
     const RelightK k = relight_uniforms(c, lp, c->gbuf_w, c->gbuf_h);
     const bool counts = lp->want_shadow_counts != 0 && lp->render_mode == 6;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
     const int split_x = split ? (int)(split_position * (float)c->gbuf_w) : 0;      // static_cast<int>(splitScreenPosition * w)
     const int div_x = std::max(0, split_x - 1);                                      // dividerWidth / 2 == 1
-    HIPCHK(c, launch_relight(k, c->d_gbuf, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts : nullptr, c->stream,
-                             split ? c->d_mr_gbuf : nullptr, split_x, div_x));
+    HIPCHK(c, launch_relight(k, c->d_gbuf.ptr, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts.get() : nullptr, c->stream,
+                             split ? c->d_mr_gbuf.ptr : nullptr, split_x, div_x));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
@@ -401,10 +354,10 @@ m2s_status m2s_relight_mesh(m2s_ctx* c, const m2s_light_params* lp) {
     HIPCHK(c, hipSetDevice(c->device));
     if (m2s_status s = ensure_light_common(c)) return s;
     c->mesh_frame_w = c->mesh_frame_h = 0;
-    if (m2s_status s = grow(c, c->d_mesh_frame, c->mesh_frame_cap_px, (uint64_t)c->mr_w * (uint64_t)c->mr_h, 4)) return s;
+    M2S_TRY(c->d_mesh_frame.reserve(c->err, (uint64_t)c->mr_w * (uint64_t)c->mr_h, 4));
     const RelightK k = relight_uniforms(c, lp, c->mr_w, c->mr_h);
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
-    HIPCHK(c, launch_relight(k, c->d_mr_gbuf, c->d_shadow_cube, c->d_mesh_frame, nullptr, c->stream));
+    HIPCHK(c, launch_relight(k, c->d_mr_gbuf.ptr, c->d_shadow_cube, c->d_mesh_frame, nullptr, c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
@@ -413,7 +366,7 @@ m2s_status m2s_relight_mesh(m2s_ctx* c, const m2s_light_params* lp) {
     return M2S_OK;
 }
 
-const void* m2s_device_frame(const m2s_ctx* c) { return c && c->frame_w ? c->d_frame : nullptr; }
+const void* m2s_device_frame(const m2s_ctx* c) { return c && c->frame_w ? c->d_frame.get() : nullptr; }
 
 m2s_status m2s_download_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
     if (!c || !dst) return M2S_ERR_INVALID;
@@ -425,7 +378,7 @@ m2s_status m2s_download_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
     return M2S_OK;
 }
 
-const void* m2s_device_mesh_frame(const m2s_ctx* c) { return c && c->mesh_frame_w ? c->d_mesh_frame : nullptr; }
+const void* m2s_device_mesh_frame(const m2s_ctx* c) { return c && c->mesh_frame_w ? c->d_mesh_frame.get() : nullptr; }
 
 m2s_status m2s_download_mesh_frame(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
     if (!c || !dst) return M2S_ERR_INVALID;

@@ -29,63 +29,53 @@ void mesh_pvm(const float* proj, const float* view, const float* model, float* o
 }
 
 m2s_status mesh_raster(m2s_ctx* c, const MeshDepthK& k, bool vis, void* image, float ms[3]) {
-    if (!c->h_md) HIPCHK(c, hipHostMalloc((void**)&c->h_md, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (!c->d_md_totals) HIPCHK(c, hipMalloc((void**)&c->d_md_totals, 8 * sizeof(unsigned long long)));
-    for (hipEvent_t& e : c->md_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    for (int i = 0; i < 8; ++i) c->h_md[i] = 0;
+    BinWork& w = c->md_work;
+    M2S_TRY(w.reserve_totals(c->err, 8, 8 * sizeof(unsigned long long)));
+    M2S_TRY(c->md_ev.ensure(c->err));
+    unsigned long long* const h_md = w.h_totals;
+    for (int i = 0; i < 8; ++i) h_md[i] = 0;
     ms[0] = ms[1] = ms[2] = 0.0f;
     const int W = k.W, H = k.H;
     const uint32_t n = c->scene.n_tri;
-    if (m2s_status s = grow_buffer(c, c->d_md_deferred, c->md_tri_cap, std::max<uint64_t>(n, 1), sizeof(uint32_t))) return s;
+    M2S_TRY(c->d_md_deferred.reserve(c->err, std::max<uint64_t>(n, 1), sizeof(uint32_t)));
     hipEvent_t* ev = c->md_ev;
     const bool prof = c->profiling;
     if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
     if (vis) HIPCHK(c, meshvis_clear((unsigned long long*)image, W, H, c->stream));
     else HIPCHK(c, meshdepth_clear((float*)image, W, H, c->stream));       // glClear(GL_DEPTH_BUFFER_BIT): part of the pass
-    HIPCHK(c, hipMemsetAsync(c->d_md_totals, 0, 8 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(w.d_totals, 0, 8 * sizeof(unsigned long long), c->stream));
     if (n) {
-        if (vis) HIPCHK(c, meshvis_setup(k, c->scene, (unsigned long long*)image, c->d_md_deferred, c->d_md_totals, c->stream));
-        else HIPCHK(c, meshdepth_setup(k, c->scene, (float*)image, c->d_md_deferred, c->d_md_totals, c->stream));
+        if (vis) HIPCHK(c, meshvis_setup(k, c->scene, (unsigned long long*)image, c->d_md_deferred, w.d_totals, c->stream));
+        else HIPCHK(c, meshdepth_setup(k, c->scene, (float*)image, c->d_md_deferred, w.d_totals, c->stream));
     }
     if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_md, c->d_md_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t nd = c->h_md[5];
+    const uint64_t nd = h_md[5];
     uint64_t pairs = 0;
     if (nd) {
         const uint64_t slots = nd * kMdSlotsPerTriangle;
-        if (c->md_slot_cap < slots) {
-            for (void* q : { c->d_md_rec, (void*)c->d_md_cnt, (void*)c->d_md_off }) if (q) (void)hipFree(q);
-            c->d_md_rec = nullptr; c->d_md_cnt = nullptr; c->d_md_off = nullptr;
-            c->md_slot_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_md_rec, (size_t)slots * 48));
-            HIPCHK(c, hipMalloc((void**)&c->d_md_cnt, (size_t)slots * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc((void**)&c->d_md_off, (size_t)slots * sizeof(unsigned long long)));
-            c->md_slot_cap = slots;
-        }
-        if (m2s_status s = grow_buffer(c, c->d_md_temp, c->md_temp_cap, meshdepth_temp_bytes((uint32_t)slots, 1), 1)) return s;
+        M2S_TRY(w.reserve_items(c->err, slots, 48));
+        M2S_TRY(w.reserve_temp(c->err, meshdepth_temp_bytes((uint32_t)slots, 1)));
+        const float4* rec = (const float4*)w.rec.get();
         if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-        HIPCHK(c, meshdepth_deferred(k, c->scene, c->d_md_deferred, (uint32_t)nd, (float4*)c->d_md_rec, c->d_md_cnt, c->d_md_off, c->d_md_temp,
-                                     c->md_temp_cap, c->d_md_totals, c->stream, vis));
-        HIPCHK(c, hipMemcpyAsync(c->h_md, c->d_md_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, meshdepth_deferred(k, c->scene, c->d_md_deferred, (uint32_t)nd, (float4*)w.rec.get(), w.cnt, w.off, w.temp, w.temp.cap(), w.d_totals,
+                                     c->stream, vis));
+        HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        pairs = c->h_md[3];
+        pairs = h_md[3];
         if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, triangle) pairs");
         if (pairs) {
-            if (m2s_status s = grow_buffer(c, c->d_md_pairs, c->md_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
-            if (m2s_status s = grow_buffer(c, c->d_md_temp, c->md_temp_cap, meshdepth_temp_bytes(1, (uint32_t)pairs), 1)) return s;
-            const uint64_t pc = c->md_pairs_cap;
-            uint32_t* keys_in = c->d_md_pairs;
-            uint32_t* vals_in = keys_in + pc;
-            uint32_t* keys_out = vals_in + pc;
-            uint32_t* vals_out = keys_out + pc;
-            HIPCHK(c, meshdepth_bin(k, (const float4*)c->d_md_rec, c->d_md_cnt, c->d_md_off, (uint32_t)nd, keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs,
-                                    c->d_md_temp, c->md_temp_cap, c->stream));
+            BinWork::Pairs pr;
+            M2S_TRY(w.reserve_pairs(c->err, pairs, &pr));
+            M2S_TRY(w.reserve_temp(c->err, meshdepth_temp_bytes(1, (uint32_t)pairs)));
+            HIPCHK(c, meshdepth_bin(k, rec, w.cnt, w.off, (uint32_t)nd, pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, w.temp,
+                                    w.temp.cap(), c->stream));
             if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-            if (vis) HIPCHK(c, meshvis_raster(k, (const float4*)c->d_md_rec, keys_out, vals_out, (uint32_t)pairs, (unsigned long long*)image, c->d_md_totals, c->stream));
-            else HIPCHK(c, meshdepth_raster(k, (const float4*)c->d_md_rec, keys_out, vals_out, (uint32_t)pairs, (float*)image, c->d_md_totals, c->stream));
+            if (vis) HIPCHK(c, meshvis_raster(k, rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, (unsigned long long*)image, w.d_totals, c->stream));
+            else HIPCHK(c, meshdepth_raster(k, rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, (float*)image, w.d_totals, c->stream));
             if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->h_md, c->d_md_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (prof) {
                 HIPCHK(c, hipEventElapsedTime(&ms[1], ev[2], ev[3]));
@@ -109,7 +99,7 @@ extern "C" {
 m2s_status m2s_mesh_depth(m2s_ctx* c, const m2s_mesh_depth_params* p, uint64_t out_counts[5]) {
     if (!c || !p) return M2S_ERR_INVALID;
     const int W = p->resolution[0], H = p->resolution[1];
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
     if (!c->has_scene) return fail(c, M2S_ERR_STATE, "no scene has been uploaded");
     HIPCHK(c, hipSetDevice(c->device));
@@ -120,21 +110,21 @@ m2s_status m2s_mesh_depth(m2s_ctx* c, const m2s_mesh_depth_params* p, uint64_t o
     mesh_pvm(p->view_to_clip, p->world_to_view, p->model_to_world, k.PVM);
     k.W = W; k.H = H;
     k.inplace = c->md_inplace < 0 ? kMdInplace : c->md_inplace;
-    if (m2s_status s = grow_buffer(c, c->d_md_image, c->md_image_cap, (uint64_t)W * (uint64_t)H, sizeof(float))) return s;
+    M2S_TRY(c->d_md_image.reserve(c->err, (uint64_t)W * (uint64_t)H, sizeof(float)));
     float ms[3] = { 0, 0, 0 };
     if (m2s_status s = mesh_raster(c, k, false, c->d_md_image, ms)) return s;
     if (c->profiling) {
         std::memcpy(c->last_md_stage_ms, ms, sizeof ms);
         c->last_md_ms = ms[0] + ms[1] + ms[2];
     }
-    for (int i = 0; i < 5; ++i) c->last_md_counts[i] = c->h_md[i];
+    for (int i = 0; i < 5; ++i) c->last_md_counts[i] = c->md_work.h_totals[i];
     if (out_counts) for (int i = 0; i < 5; ++i) out_counts[i] = c->last_md_counts[i];
     c->md_w = W;
     c->md_h = H;
     return M2S_OK;
 }
 
-const void* m2s_device_mesh_depth(const m2s_ctx* c) { return c && c->md_w ? c->d_md_image : nullptr; }
+const void* m2s_device_mesh_depth(const m2s_ctx* c) { return c && c->md_w ? c->d_md_image.get() : nullptr; }
 
 m2s_status m2s_download_mesh_depth(m2s_ctx* c, float* dst, uint64_t capacity_floats) {
     if (!c || !dst) return M2S_ERR_INVALID;

@@ -37,19 +37,18 @@ extern "C" {
 m2s_status m2s_mesh_render(m2s_ctx* c, const m2s_mesh_render_params* p, uint64_t out_counts[6]) {
     if (!c || !p) return M2S_ERR_INVALID;
     const int W = p->resolution[0], H = p->resolution[1];
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     if (p->render_mode < 0 || p->render_mode > 6) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6");
     if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
     if (!c->has_scene) return fail(c, M2S_ERR_STATE, "no scene has been uploaded");
     HIPCHK(c, hipSetDevice(c->device));
-    for (hipEvent_t& e : c->mr_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    M2S_TRY(c->mr_ev.ensure(c->err));
     c->mr_w = c->mr_h = 0;
     for (uint64_t& v : c->last_mr_counts) v = 0;
     if (out_counts) for (int k = 0; k < 6; ++k) out_counts[k] = 0;
     const uint64_t px = (uint64_t)W * (uint64_t)H;
-    if (m2s_status s = grow_buffer(c, c->d_mr_vis, c->mr_vis_cap, px, sizeof(unsigned long long))) return s;
-    for (int k = 0; k < 5; ++k)
-        if (m2s_status s = grow_buffer(c, c->d_mr_gbuf[k], c->mr_gbuf_cap_px[k], px, (k == 2 || k == 4) ? 4 : 8)) return s;
+    M2S_TRY(c->d_mr_vis.reserve(c->err, px, sizeof(unsigned long long)));
+    M2S_TRY(c->d_mr_gbuf.reserve(c->err, px));
     MeshDepthK k;
     mesh_pvm(p->view_to_clip, p->world_to_view, p->model_to_world, k.PVM);      // the depth pass's transform: the two passes' depths agree bit for bit
     k.W = W; k.H = H;
@@ -64,7 +63,7 @@ m2s_status m2s_mesh_render(m2s_ctx* c, const m2s_mesh_render_params* p, uint64_t
     r.near_far[0] = p->near_far[0]; r.near_far[1] = p->near_far[1];
     r.W = W; r.H = H; r.mode = p->render_mode;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->mr_ev[0], c->stream));
-    HIPCHK(c, meshrender_shade(r, c->scene, c->d_mr_vis, c->d_mr_gbuf, c->stream));
+    HIPCHK(c, meshrender_shade(r, c->scene, c->d_mr_vis, c->d_mr_gbuf.ptr, c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->mr_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) {
@@ -72,15 +71,15 @@ m2s_status m2s_mesh_render(m2s_ctx* c, const m2s_mesh_render_params* p, uint64_t
         std::memcpy(c->last_mr_stage_ms, ms, sizeof ms);
         c->last_mr_ms = (ms[0] + ms[1]) + (ms[2] + ms[3]);
     }
-    for (int i = 0; i < 5; ++i) c->last_mr_counts[i] = c->h_md[i];
-    c->last_mr_counts[5] = c->h_md[6];
+    for (int i = 0; i < 5; ++i) c->last_mr_counts[i] = c->md_work.h_totals[i];
+    c->last_mr_counts[5] = c->md_work.h_totals[6];
     if (out_counts) for (int i = 0; i < 6; ++i) out_counts[i] = c->last_mr_counts[i];
     c->mr_w = W;
     c->mr_h = H;
     return M2S_OK;
 }
 
-const void* m2s_device_mesh_gbuffer(const m2s_ctx* c, uint32_t attachment) { return c && c->mr_w && attachment < 5 ? c->d_mr_gbuf[attachment] : nullptr; }
+const void* m2s_device_mesh_gbuffer(const m2s_ctx* c, uint32_t attachment) { return c && c->mr_w && attachment < 5 ? c->d_mr_gbuf.ptr[attachment] : nullptr; }
 
 m2s_status m2s_download_mesh_gbuffer(m2s_ctx* c, uint32_t attachment, void* dst, uint64_t capacity_bytes) {
     if (!c || !dst || attachment >= 5) return M2S_ERR_INVALID;
@@ -88,7 +87,7 @@ m2s_status m2s_download_mesh_gbuffer(m2s_ctx* c, uint32_t attachment, void* dst,
     const uint64_t bytes = (uint64_t)c->mr_w * (uint64_t)c->mr_h * ((attachment == 2 || attachment == 4) ? 4 : 8);
     if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_mr_gbuf[attachment], bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_mr_gbuf.ptr[attachment], bytes, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

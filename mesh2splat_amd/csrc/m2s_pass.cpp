@@ -515,12 +515,9 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
             // is worth preparing for — also writes the records' positions as a 16-byte plane (the context's, grown here if need be)
             float4* plane = nullptr;
             if (ri.form == M2S_PIPELINE_SPARSE && c->keep_positions && st == c->stream) {
-                if (c->pos_plane_cap < limit) {
-                    if (c->d_pos_plane) { (void)hipFree(c->d_pos_plane); c->d_pos_plane = nullptr; c->pos_plane_cap = 0; }
-                    if (hipMalloc(&c->d_pos_plane, limit * 16) == hipSuccess) c->pos_plane_cap = limit; else (void)hipGetLastError();
-                }
+                (void)c->d_pos_plane.try_reserve(limit, 16);
                 c->pos_plane_n = 0;
-                plane = (float4*)c->d_pos_plane;
+                plane = c->d_pos_plane;
             }
             wrote_plane = plane != nullptr;
             launch_single(c, ri, R, c->d_chain, limit, d_out, c->h_total, epoch, runs, st, plane);

@@ -66,7 +66,7 @@ static m2s_status export_rows(m2s_ctx* c, const char* path, uint32_t format, flo
     const float scale_multiplier = gaussian_std / static_cast<float>(c->last_R);
     const size_t chunk = m2s_ply::kChunkRows;
     for (int k = 0; k < 2; ++k)
-        if (!c->h_export[k]) HIPCHK(c, hipHostMalloc((void**)&c->h_export[k], chunk * sizeof(m2s_gaussian), hipHostMallocDefault));
+        M2S_TRY(c->h_export[k].ensure(c->err, chunk * sizeof(m2s_gaussian)));
     m2s_ply::Writer w;
     m2s_status s = slice ? w.open_slice(path, total_rows, format, scale_multiplier, first_row, n_rows)
                          : w.open(path, total_rows, format, scale_multiplier);
@@ -75,15 +75,10 @@ static m2s_status export_rows(m2s_ctx* c, const char* path, uint32_t format, flo
     const size_t unit = on_device ? w.row_bytes() : sizeof(m2s_gaussian);     // bytes per row on the bus
     const char* src = static_cast<const char*>(c->last_records);
     if (on_device && n_rows) {
-        const uint64_t need = n_rows * unit;
-        if (c->rows_cap < need) {
-            if (c->d_rows) { (void)hipFree(c->d_rows); c->d_rows = nullptr; c->rows_cap = 0; }
-            HIPCHK(c, hipMalloc(&c->d_rows, need));
-            c->rows_cap = need;
-        }
-        launch_encode_rows((const float4*)c->last_records, n_rows, format, scale_multiplier, (uint8_t*)c->d_rows, c->stream);
+        M2S_TRY(c->d_rows.reserve(c->err, n_rows * unit, 1));
+        launch_encode_rows((const float4*)c->last_records, n_rows, format, scale_multiplier, c->d_rows, c->stream);
         HIPCHK(c, hipGetLastError());
-        src = static_cast<const char*>(c->d_rows);
+        src = reinterpret_cast<const char*>(c->d_rows.get());
     }
     auto rows_of = [&](uint64_t k) { return (size_t)std::min<uint64_t>(chunk, n_rows - k * chunk); };
     const uint64_t n_chunks = (n_rows + chunk - 1) / chunk;
@@ -93,7 +88,7 @@ static m2s_status export_rows(m2s_ctx* c, const char* path, uint32_t format, flo
         if (k + 1 < n_chunks)
             HIPCHK(c, hipMemcpyAsync(c->h_export[(k + 1) & 1], src + (k + 1) * chunk * unit, rows_of(k + 1) * unit, hipMemcpyDeviceToHost, c->stream));
         // (both return once the pinned buffer has been read)
-        s = on_device ? w.append_encoded(reinterpret_cast<const uint8_t*>(c->h_export[k & 1]), rows_of(k)) : w.append(c->h_export[k & 1], rows_of(k));
+        s = on_device ? w.append_encoded(reinterpret_cast<const uint8_t*>(static_cast<m2s_gaussian*>(c->h_export[k & 1])), rows_of(k)) : w.append(c->h_export[k & 1], rows_of(k));
     }
     const m2s_status cs = w.close();
     if (s == M2S_OK) s = cs;
@@ -117,14 +112,10 @@ m2s_status m2s_export_ply_slice(m2s_ctx* c, const char* path, uint32_t format, f
 // host records (e.g. from m2s_read_ply) become the context's current records.
 m2s_status m2s_upload_records(m2s_ctx* c, const m2s_gaussian* records, uint64_t n) {
     if (!c || (!records && n)) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t want = std::max<uint64_t>(n, 1);     // an empty upload still yields a valid (empty) record buffer
-    if (c->loaded_cap < want) {
-        if (c->d_loaded) { (void)hipFree(c->d_loaded); c->d_loaded = nullptr; c->loaded_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_loaded, want * sizeof(m2s_gaussian)));
-        c->loaded_cap = want;
-    }
+    M2S_TRY(c->d_loaded.reserve(c->err, want, sizeof(m2s_gaussian)));
     if (n) HIPCHK(c, hipMemcpy(c->d_loaded, records, n * sizeof(m2s_gaussian), hipMemcpyHostToDevice));
     c->last_records = c->d_loaded;
     ++c->records_epoch;
@@ -141,7 +132,7 @@ m2s_status m2s_upload_records(m2s_ctx* c, const m2s_gaussian* records, uint64_t 
 // records without a copy; R = the resolutionTarget they were converted at (m2s_export_ply's scale multiplier).
 m2s_status m2s_set_records(m2s_ctx* c, const void* d_records, uint64_t n, uint32_t R) {
     if (!c || (!d_records && n)) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     c->last_records = d_records;
     ++c->records_epoch;
     c->last_total = c->last_stored = n;
@@ -155,7 +146,7 @@ m2s_status m2s_set_records(m2s_ctx* c, const void* d_records, uint64_t n, uint32
 // pool themselves (the root of m2s_dist_gather_records) and then call m2s_set_records.
 m2s_status m2s_reserve_records(m2s_ctx* c, uint64_t n, void** out_ptr) {
     if (!c || !out_ptr) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     HIPCHK(c, hipSetDevice(c->device));
     const m2s_status s = ensure_records(c, std::max<uint64_t>(n, 1));
     if (s != M2S_OK) return s;

@@ -12,7 +12,7 @@ m2s_status m2s_score_frames(m2s_ctx* c, const m2s_score_params* p, const void* d
                             m2s_score_result* out) {
     if (!c || !p || !out) return M2S_ERR_INVALID;
     const int W = p->resolution[0], H = p->resolution[1];
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     if (p->mask_mode > 3) return fail(c, M2S_ERR_INVALID, "mask mode outside 0..3");
     if (p->flags & ~(uint32_t)(M2S_SCORE_NO_COVER | M2S_SCORE_WANT_MAP)) return fail(c, M2S_ERR_INVALID, "unknown flag");
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
@@ -28,19 +28,18 @@ m2s_status m2s_score_frames(m2s_ctx* c, const m2s_score_params* p, const void* d
     }
     if (cover && !d_cover_a) {
         if (c->mr_w != W || c->mr_h != H) return fail(c, M2S_ERR_STATE, "no mesh G-buffer of this resolution exists (run m2s_mesh_render)");
-        d_cover_a = c->d_mr_gbuf[2];
+        d_cover_a = c->d_mr_gbuf.ptr[2];
     }
     if (cover && !d_cover_b) {
         if (c->gbuf_w != W || c->gbuf_h != H) return fail(c, M2S_ERR_STATE, "no G-buffer of this resolution exists (run m2s_splat)");
-        d_cover_b = c->d_gbuf[2];
+        d_cover_b = c->d_gbuf.ptr[2];
     }
     HIPCHK(c, hipSetDevice(c->device));
     constexpr size_t kWords = (size_t)kScoreShards * kScoreCounters;
-    if (!c->d_score_acc) HIPCHK(c, hipMalloc((void**)&c->d_score_acc, kWords * sizeof(unsigned long long)));
-    if (!c->h_score) HIPCHK(c, hipHostMalloc((void**)&c->h_score, kWords * sizeof(unsigned long long), hipHostMallocDefault));
-    for (hipEvent_t& e : c->score_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    if (want_map)
-        if (m2s_status s = grow_buffer(c, c->d_score_map, c->score_map_cap_px, (uint64_t)W * (uint64_t)H, 4)) return s;
+    M2S_TRY(c->d_score_acc.reserve(c->err, kWords, sizeof(unsigned long long)));
+    M2S_TRY(c->h_score.ensure(c->err, kWords * sizeof(unsigned long long)));
+    M2S_TRY(c->score_ev.ensure(c->err));
+    if (want_map) M2S_TRY(c->d_score_map.reserve(c->err, (uint64_t)W * (uint64_t)H, 4));
     ScoreK k;
     k.W = W; k.H = H;
     k.mask_mode = p->mask_mode;
@@ -48,7 +47,7 @@ m2s_status m2s_score_frames(m2s_ctx* c, const m2s_score_params* p, const void* d
     HIPCHK(c, hipMemsetAsync(c->d_score_acc, 0, kWords * sizeof(unsigned long long), c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->score_ev[0], c->stream));
     HIPCHK(c, launch_score(k, (const uint32_t*)d_a, (const uint32_t*)d_b, cover ? (const uint32_t*)d_cover_a : nullptr,
-                           cover ? (const uint32_t*)d_cover_b : nullptr, want_map ? c->d_score_map : nullptr, c->d_score_acc, c->stream));
+                           cover ? (const uint32_t*)d_cover_b : nullptr, want_map ? c->d_score_map.get() : nullptr, c->d_score_acc, c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->score_ev[1], c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_score, c->d_score_acc, kWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -71,7 +70,7 @@ m2s_status m2s_score_frames(m2s_ctx* c, const m2s_score_params* p, const void* d
     return M2S_OK;
 }
 
-const void* m2s_device_score_map(const m2s_ctx* c) { return c && c->score_map_w ? c->d_score_map : nullptr; }
+const void* m2s_device_score_map(const m2s_ctx* c) { return c && c->score_map_w ? c->d_score_map.get() : nullptr; }
 
 m2s_status m2s_download_score_map(m2s_ctx* c, void* dst, uint64_t capacity_bytes) {
     if (!c || !dst) return M2S_ERR_INVALID;

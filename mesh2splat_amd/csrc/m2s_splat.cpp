@@ -7,81 +7,48 @@
 using namespace m2s;
 using namespace m2s_host;
 
-namespace {
-
-// grow-only device buffer: (re)allocated when `want` exceeds `cap` (units of `unit` bytes)
-template <typename T>
-m2s_status grow(m2s_ctx* c, T*& p, uint64_t& cap, uint64_t want, size_t unit) {
-    if (cap >= want) return M2S_OK;
-    if (p) { (void)hipFree((void*)p); p = nullptr; }
-    cap = 0;
-    void* q = nullptr;
-    HIPCHK(c, hipMalloc(&q, std::max<size_t>(want * unit, 256)));
-    p = static_cast<T*>(q);
-    cap = want;
-    return M2S_OK;
-}
-
-}  // namespace
-
 namespace m2s_host {
 
 m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out) {
-    if (!c->d_splat_totals) HIPCHK(c, hipMalloc((void**)&c->d_splat_totals, 4 * sizeof(unsigned long long)));
-    if (!c->h_splat) HIPCHK(c, hipHostMalloc((void**)&c->h_splat, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    BinWork& w = c->splat_work;
+    M2S_TRY(w.reserve_totals(c->err, 4, 4 * sizeof(unsigned long long)));
     const int tiles_x = (W + kSplatTile - 1) / kSplatTile, tiles_y = (H + kSplatTile - 1) / kSplatTile;
     const uint32_t n_tiles = (uint32_t)(tiles_x * tiles_y);
-    HIPCHK(c, hipMemsetAsync(c->d_splat_totals, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(w.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
     hipEvent_t* ev = c->ev;
     const bool prof = c->profiling;
     uint64_t pairs = 0;
     *out = SplatBins();
     if (nq) {
         // ---- setup: records, tile counts, their scan; the number of pairs read back once (the pair buffers are sized from it)
-        if (c->splat_quad_cap < nq) {
-            for (void* q : { c->d_splat_rec, (void*)c->d_splat_cnt, (void*)c->d_splat_off }) if (q) (void)hipFree(q);
-            c->d_splat_rec = nullptr; c->d_splat_cnt = nullptr; c->d_splat_off = nullptr;
-            c->splat_quad_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_splat_rec, (size_t)nq * kSplatRecBytes));
-            HIPCHK(c, hipMalloc((void**)&c->d_splat_cnt, (size_t)nq * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc((void**)&c->d_splat_off, (size_t)nq * sizeof(unsigned long long)));
-            c->splat_quad_cap = nq;
-        }
-        uint64_t tcap = c->splat_temp_cap;
-        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_scan_temp_bytes(nq), 1)) return s;
-        c->splat_temp_cap = tcap;
+        M2S_TRY(w.reserve_items(c->err, nq, kSplatRecBytes));
+        M2S_TRY(w.reserve_temp(c->err, splat_scan_temp_bytes(nq)));
         if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        HIPCHK(c, splat_setup((const float4*)d_quads, nq, W, H, (float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, c->d_splat_temp,
-                              c->splat_temp_cap, c->d_splat_totals, c->stream));
+        HIPCHK(c, splat_setup((const float4*)d_quads, nq, W, H, (float4*)w.rec.get(), w.cnt, w.off, w.temp, w.temp.cap(), w.d_totals, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_splat, c->d_splat_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w.h_totals, w.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        pairs = c->h_splat[0];
-        out->skipped = c->h_splat[1];
+        pairs = w.h_totals[0];
+        out->skipped = w.h_totals[1];
         if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
     }
     if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
     out->pairs = pairs;
     if (pairs) {
-        if (m2s_status s = grow(c, c->d_splat_pairs, c->splat_pairs_cap, pairs, 4 * sizeof(uint32_t))) return s;
-        if (m2s_status s = grow(c, c->d_splat_tiles, c->splat_tiles_cap, n_tiles, 5 * sizeof(uint32_t))) return s;
-        uint64_t tcap = c->splat_temp_cap;
-        if (m2s_status s = grow(c, c->d_splat_temp, tcap, splat_sort_temp_bytes((uint32_t)pairs, n_tiles), 1)) return s;
-        c->splat_temp_cap = tcap;
-        const uint64_t pc = c->splat_pairs_cap, tc = c->splat_tiles_cap;
-        uint32_t* keys_in = c->d_splat_pairs;
-        uint32_t* vals_in = keys_in + pc;
-        uint32_t* keys_out = vals_in + pc;
-        uint32_t* vals_out = keys_out + pc;
-        uint2* rg = reinterpret_cast<uint2*>(c->d_splat_tiles);
+        BinWork::Pairs pr;
+        M2S_TRY(w.reserve_pairs(c->err, pairs, &pr));
+        M2S_TRY(c->d_splat_tiles.reserve(c->err, n_tiles, 5 * sizeof(uint32_t)));
+        M2S_TRY(w.reserve_temp(c->err, splat_sort_temp_bytes((uint32_t)pairs, n_tiles)));
+        const uint64_t tc = c->d_splat_tiles.cap();
+        uint2* rg = reinterpret_cast<uint2*>(c->d_splat_tiles.get());
         uint32_t* len = c->d_splat_tiles + 2 * tc;
         uint32_t* len_sorted = len + tc;
         uint32_t* ord = len_sorted + tc;
-        HIPCHK(c, splat_pairs((const float4*)c->d_splat_rec, c->d_splat_cnt, c->d_splat_off, nq, tiles_x, keys_in, vals_in, c->stream));
+        HIPCHK(c, splat_pairs((const float4*)w.rec.get(), w.cnt, w.off, nq, tiles_x, pr.keys_in, pr.vals_in, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-        HIPCHK(c, splat_group(keys_in, vals_in, keys_out, vals_out, (uint32_t)pairs, n_tiles, rg, len, len_sorted, ord, c->d_splat_temp,
-                              c->splat_temp_cap, c->stream));
-        out->vals = vals_out; out->ranges = rg; out->order = ord;
+        HIPCHK(c, splat_group(pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, n_tiles, rg, len, len_sorted, ord, w.temp,
+                              w.temp.cap(), c->stream));
+        out->vals = pr.vals_out; out->ranges = rg; out->order = ord;
     } else if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
     if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
     return M2S_OK;
@@ -109,7 +76,7 @@ m2s_status m2s_upload_quads(m2s_ctx* c, const m2s_quad* host_quads, uint64_t n) 
     c->sq_n = 0;
     c->sq_src = nullptr;
     if (!n) return M2S_OK;
-    if (m2s_status s = grow(c, c->d_sorted_quads, c->sq_cap, n, sizeof(m2s_quad))) return s;
+    M2S_TRY(c->d_sorted_quads.reserve(c->err, n, sizeof(m2s_quad)));
     HIPCHK(c, hipMemcpy(c->d_sorted_quads, host_quads, n * sizeof(m2s_quad), hipMemcpyHostToDevice));
     c->sq_n = n;
     return M2S_OK;
@@ -119,7 +86,7 @@ m2s_status m2s_upload_quads(m2s_ctx* c, const m2s_quad* host_quads, uint64_t n) 
 m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads, uint64_t n, uint64_t* out_skipped) {
     if (!c || !p) return M2S_ERR_INVALID;
     const int W = p->resolution[0], H = p->resolution[1];
-    if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, "resolution outside 1..8192");
+    M2S_TRY(check_resolution(c, W, H));
     if (p->render_mode < 0 || p->render_mode > 6 || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6 or reserved != 0");
     if (!d_quads) {
         if (!c->sq_n) return fail(c, M2S_ERR_INVALID, "no sorted quads (run m2s_sort_prepass / m2s_prepass_sorted / m2s_upload_quads, or pass d_quads)");
@@ -132,12 +99,7 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
     c->gbuf_w = c->gbuf_h = 0;
     for (uint64_t& v : c->last_splat_counts) v = 0;
     const uint64_t px = (uint64_t)W * (uint64_t)H;
-    if (c->gbuf_cap_px < px) {
-        for (int k = 0; k < 5; ++k) if (c->d_gbuf[k]) { (void)hipFree(c->d_gbuf[k]); c->d_gbuf[k] = nullptr; }
-        c->gbuf_cap_px = 0;
-        for (int k = 0; k < 5; ++k) HIPCHK(c, hipMalloc(&c->d_gbuf[k], px * ((k == 2 || k == 4) ? 4 : 8)));
-        c->gbuf_cap_px = px;
-    }
+    M2S_TRY(c->d_gbuf.reserve(c->err, px));
     const uint32_t nq = (uint32_t)n;
     SplatBins bins;
     const m2s_status bs = splat_bin(c, d_quads, nq, W, H, &bins);
@@ -151,13 +113,13 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
     hipEvent_t* ev = c->ev;
     const bool prof = c->profiling;
     // ---- blend: every tile writes its 16 x 16 pixels of all five planes once (tiles without quads write the cleared values)
-    void* const planes[5] = { c->d_gbuf[0], c->d_gbuf[1], c->d_gbuf[2], c->d_gbuf[3], c->d_gbuf[4] };
-    HIPCHK(c, splat_blend((const float4*)c->d_splat_rec, vals, ranges, order, W, H, p->render_mode, planes, c->d_splat_totals + 2, c->stream));
+    BinWork& w = c->splat_work;
+    HIPCHK(c, splat_blend((const float4*)w.rec.get(), vals, ranges, order, W, H, p->render_mode, c->d_gbuf.ptr, w.d_totals + 2, c->stream));
     if (prof) HIPCHK(c, hipEventRecord(ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_splat + 2, c->d_splat_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w.h_totals + 2, w.d_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->last_splat_counts[0] = pairs;
-    c->last_splat_counts[1] = c->h_splat[2];
+    c->last_splat_counts[1] = w.h_totals[2];
     if (prof) {
         if (m2s_status s = splat_stage_ms(c, nq != 0, c->last_splat_stage_ms)) return s;
         c->last_splat_ms = (c->last_splat_stage_ms[0] + c->last_splat_stage_ms[1]) + c->last_splat_stage_ms[2];
@@ -168,7 +130,7 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
 }
 
 const void* m2s_device_gbuffer(const m2s_ctx* c, uint32_t attachment) {
-    return c && c->gbuf_w && attachment < 5 ? c->d_gbuf[attachment] : nullptr;
+    return c && c->gbuf_w && attachment < 5 ? c->d_gbuf.ptr[attachment] : nullptr;
 }
 
 m2s_status m2s_download_gbuffer(m2s_ctx* c, uint32_t attachment, void* dst, uint64_t capacity_bytes) {
@@ -177,7 +139,7 @@ m2s_status m2s_download_gbuffer(m2s_ctx* c, uint32_t attachment, void* dst, uint
     const uint64_t bytes = (uint64_t)c->gbuf_w * (uint64_t)c->gbuf_h * ((attachment == 2 || attachment == 4) ? 4 : 8);
     if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the attachment");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_gbuf[attachment], bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_gbuf.ptr[attachment], bytes, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

@@ -74,7 +74,7 @@ extern "C" {
 
 m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshes) {
     if (!c) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (n_meshes > 0xFFFFFFu) return fail(c, M2S_ERR_INVALID, "more than 2^24-1 meshes");   // TriShade keeps the index in 24 bits
     if (n_meshes && !meshes) return fail(c, M2S_ERR_INVALID, "meshes is NULL");
     HIPCHK(c, hipSetDevice(c->device));
@@ -320,7 +320,7 @@ m2s_status m2s_prepare(m2s_ctx* c, uint32_t flags) {
     if (flags & M2S_PREPARE_UPLOAD) { const m2s_status s = ensure_stage(c); if (s != M2S_OK) return s; }
     if (flags & M2S_PREPARE_EXPORT)
         for (int k = 0; k < 2; ++k)
-            if (!c->h_export[k]) HIPCHK(c, hipHostMalloc((void**)&c->h_export[k], m2s_ply::kChunkRows * sizeof(m2s_gaussian), hipHostMallocDefault));
+            M2S_TRY(c->h_export[k].ensure(c->err, m2s_ply::kChunkRows * sizeof(m2s_gaussian)));
     if ((flags & M2S_PREPARE_KERNELS) && !debug_on("M2S_NO_PRELOAD")) {
         HIPCHK(c, preload_fused2()); HIPCHK(c, preload_fused3()); HIPCHK(c, preload_sparse()); HIPCHK(c, preload_multipass());
         HIPCHK(c, preload_export()); HIPCHK(c, preload_prepass()); HIPCHK(c, preload_sort()); HIPCHK(c, preload_splat()); HIPCHK(c, preload_light()); HIPCHK(c, preload_meshdepth()); HIPCHK(c, preload_meshrender()); HIPCHK(c, preload_score());

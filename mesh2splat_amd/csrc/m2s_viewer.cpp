@@ -16,6 +16,22 @@
 using namespace m2s;
 using namespace m2s_host;
 
+namespace {
+
+// Room for a depth sort of n entries: the keys / permutation words, the radix sort's work area of `temp_bytes` and, with_plane, the
+// position plane (without it every sort reads the records: slower, not wrong).
+m2s_status reserve_sort(m2s_ctx* c, uint64_t n, size_t temp_bytes, bool with_plane) {
+    M2S_TRY(c->d_sort_u32.reserve(c->err, n, 4 * sizeof(uint32_t)));
+    M2S_TRY(c->d_sort_temp.reserve(c->err, temp_bytes, 1));
+    if (with_plane && c->d_pos_plane.cap() < n) {
+        c->pos_plane_n = 0;
+        (void)c->d_pos_plane.try_reserve(n, 16);
+    }
+    return M2S_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // RadixSortPass::execute (RadixSortPass.cpp:8-90) on the records of the last conversion.
@@ -26,36 +42,16 @@ m2s_status m2s_sort_by_depth(m2s_ctx* c, const float world_to_view[16], uint64_t
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t n = c->last_stored;
     c->sorted_n = 0;
-    if (c->sq_src != c->d_sq_src) c->sq_src = nullptr;   // (sources aliasing the permutation words this sort is about to rewrite)
+    if (c->sq_src != c->d_sq_src.get()) c->sq_src = nullptr;   // (sources aliasing the permutation words this sort is about to rewrite)
     if (out_n) *out_n = n;
     if (!n) return M2S_OK;
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
-    if (c->sorted_cap < n) {
-        if (c->d_sorted) { (void)hipFree(c->d_sorted); c->d_sorted = nullptr; c->sorted_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_sorted, n * sizeof(m2s_gaussian)));
-        c->sorted_cap = n;
-    }
-    if (c->sort_u32_cap < n) {
-        if (c->d_sort_u32) { (void)hipFree(c->d_sort_u32); c->d_sort_u32 = nullptr; c->sort_u32_cap = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->d_sort_u32, n * 4 * sizeof(uint32_t)));
-        c->sort_u32_cap = n;
-    }
-    const size_t tb = sort_temp_bytes((uint32_t)n);
-    if (c->sort_temp_cap < tb) {
-        if (c->d_sort_temp) { (void)hipFree(c->d_sort_temp); c->d_sort_temp = nullptr; c->sort_temp_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_sort_temp, std::max<size_t>(tb, 256)));
-        c->sort_temp_cap = tb;
-    }
-    if (c->pos_plane_cap < n) {
-        if (c->d_pos_plane) { (void)hipFree(c->d_pos_plane); c->d_pos_plane = nullptr; c->pos_plane_cap = 0; }
-        c->pos_plane_n = 0;
-        if (hipMalloc(&c->d_pos_plane, n * 16) == hipSuccess) c->pos_plane_cap = n;   // (without it every sort reads the records: slower, not wrong)
-        else (void)hipGetLastError();
-    }
+    M2S_TRY(c->d_sorted.reserve(c->err, n, sizeof(m2s_gaussian)));
+    M2S_TRY(reserve_sort(c, n, sort_temp_bytes((uint32_t)n), true));
     const bool plane_valid = c->d_pos_plane && c->pos_plane_of == c->last_records && c->pos_plane_n == n && c->pos_plane_epoch == c->records_epoch;
     uint32_t* u = c->d_sort_u32;     // keys_in | (unused) | keys_out | vals_out
     HIPCHK(c, sort_by_depth((const float4*)c->last_records, (uint32_t)n, world_to_view, u, u + 2 * n, u + 3 * n, c->d_sort_temp,
-                            c->sort_temp_cap, (float4*)c->d_sorted, (float4*)c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream,
+                            c->d_sort_temp.cap(), c->d_sorted, c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream,
                             &c->sorted_key_offset, reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM])));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->d_pos_plane) { c->pos_plane_of = c->last_records; c->pos_plane_n = n; c->pos_plane_epoch = c->records_epoch; }
@@ -67,7 +63,7 @@ m2s_status m2s_sort_by_depth(m2s_ctx* c, const float world_to_view[16], uint64_t
     return M2S_OK;
 }
 
-const void* m2s_device_sorted_records(const m2s_ctx* c) { return c && c->sorted_n ? c->d_sorted : nullptr; }
+const void* m2s_device_sorted_records(const m2s_ctx* c) { return c && c->sorted_n ? c->d_sorted.get() : nullptr; }
 // the keys of those records (uint32, ascending): keys_out of the radix sort
 // (the sort runs over the bits in which the keys differ, on `key - smallest key`: the smallest key is added back here, once, when
 //  somebody asks for the keys — the distributed sort does; a frame's sort + gather does not)
@@ -108,13 +104,8 @@ m2s_status m2s_last_sort_stage_ms(const m2s_ctx* c, float out_ms[3]) {
 // prepass stores; the prepass then reads the records through it and appends its survivors in that order, straight into the sorted-quads buffer.
 static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const void* d_records, uint64_t n, uint64_t* out_visible, bool sorted) {
     if (!c || !p) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, "conversions are still in flight: m2s_convert_wait first");
-    if (!d_records) {
-        if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run, no records were uploaded and none were passed");
-        if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-        d_records = c->last_records;
-        n = c->last_stored;
-    }
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!d_records) M2S_TRY(pick_records(c, d_records, n));
     if (p->resolution_target == 0) return fail(c, M2S_ERR_INVALID, "resolution_target is 0");
     if (p->depth_test_mesh == 1 && p->format == 0 && (!p->depth || !p->depth_w || !p->depth_h))
         return fail(c, M2S_ERR_INVALID, "depth_test_mesh is set but no depth image was passed");
@@ -125,57 +116,22 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     c->sq_src = nullptr;
     if (out_visible) *out_visible = 0;
     if (!n) return M2S_OK;
-    if (!sorted && c->pp_cap < n) {
-        if (c->d_quads) { (void)hipFree(c->d_quads); c->d_quads = nullptr; }
-        c->pp_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_quads, n * sizeof(m2s_quad)));
-        c->pp_cap = n;
-    }
-    if (c->pp_depths_cap < n) {
-        if (c->d_pp_depths) { (void)hipFree(c->d_pp_depths); c->d_pp_depths = nullptr; }
-        c->pp_depths_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_pp_depths, n * sizeof(float)));
-        c->pp_depths_cap = n;
-    }
+    if (!sorted) M2S_TRY(c->d_quads.reserve(c->err, n, sizeof(m2s_quad)));
+    M2S_TRY(c->d_pp_depths.reserve(c->err, n, sizeof(float)));
     const uint32_t* perm = nullptr;
     if (sorted) {   // room for the sorted survivors, the keys / permutation, the radix sort's work area and the position plane
-        if (c->sq_cap < n) {
-            if (c->d_sorted_quads) { (void)hipFree(c->d_sorted_quads); c->d_sorted_quads = nullptr; c->sq_cap = 0; }
-            HIPCHK(c, hipMalloc(&c->d_sorted_quads, n * sizeof(m2s_quad)));
-            c->sq_cap = n;
-        }
-        if (c->sort_u32_cap < n) {
-            if (c->d_sort_u32) { (void)hipFree(c->d_sort_u32); c->d_sort_u32 = nullptr; c->sort_u32_cap = 0; }
-            HIPCHK(c, hipMalloc((void**)&c->d_sort_u32, n * 4 * sizeof(uint32_t)));
-            c->sort_u32_cap = n;
-        }
-        const size_t tb = sort_temp_bytes((uint32_t)n);
-        if (c->sort_temp_cap < tb) {
-            if (c->d_sort_temp) { (void)hipFree(c->d_sort_temp); c->d_sort_temp = nullptr; c->sort_temp_cap = 0; }
-            HIPCHK(c, hipMalloc(&c->d_sort_temp, std::max<size_t>(tb, 256)));
-            c->sort_temp_cap = tb;
-        }
-        if (c->pos_plane_cap < n) {
-            if (c->d_pos_plane) { (void)hipFree(c->d_pos_plane); c->d_pos_plane = nullptr; c->pos_plane_cap = 0; }
-            c->pos_plane_n = 0;
-            if (hipMalloc(&c->d_pos_plane, n * 16) == hipSuccess) c->pos_plane_cap = n;   // (without it every frame's keys read the records: slower, not wrong)
-            else (void)hipGetLastError();
-        }
+        M2S_TRY(c->d_sorted_quads.reserve(c->err, n, sizeof(m2s_quad)));
+        M2S_TRY(reserve_sort(c, n, sort_temp_bytes((uint32_t)n), true));
         c->sorted_n = 0;          // (the key / permutation words are shared with m2s_sort_by_depth: its sorted keys are gone)
     }
     const uint64_t words = (n + 63) / 64 + 1;          // [0] = the arrival-order counter, [1..] = the look-back chain
     // the chain is tagged with the low 16 bits of a launch counter instead of being cleared per launch; cleared when
     // it is (re)allocated and when the tag wraps (see next_epoch)
     bool clear_chain = false;
-    if (c->pp_chain_words < words) {
-        if (c->d_pp_chain) { (void)hipFree(c->d_pp_chain); c->d_pp_chain = nullptr; c->pp_chain_words = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->d_pp_chain, words * sizeof(unsigned long long)));
-        c->pp_chain_words = words;
-        clear_chain = true;
-    }
+    M2S_TRY(c->d_pp_chain.reserve(c->err, words, sizeof(unsigned long long), &clear_chain));
     const uint32_t epoch = ++c->pp_epoch;
     if (clear_chain || (epoch & 0xFFFFu) == 0)
-        HIPCHK(c, hipMemsetAsync(c->d_pp_chain, 0, c->pp_chain_words * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_pp_chain, 0, c->d_pp_chain.cap() * sizeof(unsigned long long), c->stream));
     PrepassK k;
     prepass_prepare(*p, n, &k);
     if (sorted) k.arrival_order = 0;            // the order of the survivors IS the result
@@ -183,11 +139,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         if (p->depth_on_device) k.depth = p->depth;
         else {
             const uint64_t texels = (uint64_t)p->depth_w * p->depth_h;
-            if (c->pp_depthtex_cap < texels) {
-                if (c->d_pp_depthtex) { (void)hipFree(c->d_pp_depthtex); c->d_pp_depthtex = nullptr; c->pp_depthtex_cap = 0; }
-                HIPCHK(c, hipMalloc((void**)&c->d_pp_depthtex, texels * sizeof(float)));
-                c->pp_depthtex_cap = texels;
-            }
+            M2S_TRY(c->d_pp_depthtex.reserve(c->err, texels, sizeof(float)));
             HIPCHK(c, hipMemcpyAsync(c->d_pp_depthtex, p->depth, texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
             k.depth = c->d_pp_depthtex;
         }
@@ -205,23 +157,23 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         uint32_t* u = c->d_sort_u32;     // keys_in | (unused) | keys_out | vals_out = the permutation
         uint32_t* pinned4 = reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM]);
         bool cull = k.depth_test == 0u, clash = false;
-        HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, cull, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->sort_temp_cap,
-                                           (float4*)c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
+        HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, cull, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
+                                           c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
         if (c->d_pos_plane) { c->pos_plane_of = c->last_records; c->pos_plane_n = n; c->pos_plane_epoch = c->records_epoch; }
         if (cull && clash) {   // a survivor whose depth bits ARE the marker of the culled ones (a NaN with that payload): sort everything, compact in the prepass
             cull = false;
-            HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, false, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->sort_temp_cap,
-                                               (float4*)c->d_pos_plane, true, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
+            HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, false, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
+                                               c->d_pos_plane, true, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
         }
         dense = cull;
         perm = u + 3 * n;
         // which record every surviving quad was made from: dense, position i holds record perm[i] and every position survives — the
         // first n_run words of the permutation ARE the sources; compacting, the kernel stores them beside the quads
-        if (!dense && n_run) if (m2s_status s = grow_buffer(c, c->d_sq_src, c->sq_src_cap, n, sizeof(uint32_t))) return s;
+        if (!dense && n_run) M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
     }
-    uint32_t* src_out = sorted && !dense ? c->d_sq_src : nullptr;
+    uint32_t* src_out = sorted && !dense ? c->d_sq_src.get() : nullptr;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, (float4*)(sorted ? c->d_sorted_quads : c->d_quads), c->d_pp_depths, c->d_pp_chain + 1,
+    if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, sorted ? c->d_sorted_quads.get() : c->d_quads.get(), c->d_pp_depths, c->d_pp_chain + 1,
                                         epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense, src_out));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     if (k.arrival_order) HIPCHK(c, hipMemcpyAsync(&res[0], c->d_pp_chain, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -239,7 +191,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     if (dense) res[0] = n_run;                  // (the survivors were counted by the sort; the dense prepass appends nothing)
     if (sorted) {
         c->sq_n = res[0];
-        c->sq_src = dense ? perm : c->d_sq_src;
+        c->sq_src = dense ? perm : c->d_sq_src.get();
         c->sq_src_epoch = c->records_epoch;
     } else c->pp_visible = res[0];
     if (out_visible) *out_visible = res[0];
@@ -256,8 +208,8 @@ m2s_status m2s_prepass_sorted(m2s_ctx* c, const m2s_prepass_params* p, uint64_t*
     return prepass_impl(c, p, nullptr, 0, out_visible, true);
 }
 
-const void* m2s_device_quads(const m2s_ctx* c) { return c && c->pp_visible ? c->d_quads : nullptr; }
-const void* m2s_device_prepass_depths(const m2s_ctx* c) { return c && c->pp_visible ? c->d_pp_depths : nullptr; }
+const void* m2s_device_quads(const m2s_ctx* c) { return c && c->pp_visible ? c->d_quads.get() : nullptr; }
+const void* m2s_device_prepass_depths(const m2s_ctx* c) { return c && c->pp_visible ? c->d_pp_depths.get() : nullptr; }
 
 m2s_status m2s_download_prepass(m2s_ctx* c, m2s_quad* dst_quads, float* dst_depths, uint64_t capacity) {
     if (!c) return M2S_ERR_INVALID;
@@ -280,26 +232,11 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
     c->sq_src = nullptr;
     if (out_n) *out_n = n;
     if (!n) return M2S_OK;
-    if (c->sq_cap < n) {
-        if (c->d_sorted_quads) { (void)hipFree(c->d_sorted_quads); c->d_sorted_quads = nullptr; c->sq_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_sorted_quads, n * sizeof(m2s_quad)));
-        c->sq_cap = n;
-    }
-    if (c->sort_u32_cap < n) {
-        if (c->d_sort_u32) { (void)hipFree(c->d_sort_u32); c->d_sort_u32 = nullptr; c->sort_u32_cap = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->d_sort_u32, n * 4 * sizeof(uint32_t)));
-        c->sort_u32_cap = n;
-    }
-    const size_t tb = sort_prepass_temp_bytes((uint32_t)n);
-    if (c->sort_temp_cap < tb) {
-        if (c->d_sort_temp) { (void)hipFree(c->d_sort_temp); c->d_sort_temp = nullptr; c->sort_temp_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_sort_temp, std::max<size_t>(tb, 256)));
-        c->sort_temp_cap = tb;
-    }
+    M2S_TRY(c->d_sorted_quads.reserve(c->err, n, sizeof(m2s_quad)));
+    M2S_TRY(reserve_sort(c, n, sort_prepass_temp_bytes((uint32_t)n), false));
     uint32_t* u = c->d_sort_u32;
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    HIPCHK(c, sort_prepass(c->d_pp_depths, (const float4*)c->d_quads, (uint32_t)n, u, u + n, c->d_sort_temp, c->sort_temp_cap,
-                           (float4*)c->d_sorted_quads, c->stream));
+    HIPCHK(c, sort_prepass(c->d_pp_depths, c->d_quads, (uint32_t)n, u, u + n, c->d_sort_temp, c->d_sort_temp.cap(), c->d_sorted_quads, c->stream));
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_sort_prepass_ms, c->ev[0], c->ev[1]));
@@ -307,7 +244,7 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
     return M2S_OK;
 }
 
-const void* m2s_device_sorted_quads(const m2s_ctx* c) { return c && c->sq_n ? c->d_sorted_quads : nullptr; }
+const void* m2s_device_sorted_quads(const m2s_ctx* c) { return c && c->sq_n ? c->d_sorted_quads.get() : nullptr; }
 const void* m2s_device_sorted_sources(const m2s_ctx* c) {
     return c && c->sq_n && c->sq_src_epoch == c->records_epoch ? c->sq_src : nullptr;
 }
