@@ -835,6 +835,54 @@ m2s_status m2s_write_ply_sh(const char* path, const m2s_gaussian* records, const
  * when no conversion has run, no plane exists or the plane's n is not the records'. */
 m2s_status m2s_export_ply_sh(m2s_ctx* ctx, const char* path, float gaussian_std);
 
+/* ---- compact export: Morton-ordered, chunk-quantised rows of 16 bytes ----------------------------------------------------------
+ * A delivery format of 16.3 bytes per Gaussian instead of format 0's 248, laid out after the "compressed PLY" of the PlayCanvas /
+ * SuperSplat tools as remembered — NOT verified against their reader: the header text and the bit layout below are this project's
+ * definition.  All arithmetic is fp32, one rounding per operation, no contraction; `/` and sqrtf are IEEE; the logarithm is the C
+ * library's logf (on the device: logf_glibc, m2s_logf.h).  Every min / max below is taken in the order of the real line with -0 below
+ * +0, so that it does not depend on the order of a reduction.  mesh2splat_amd/csrc/m2s_compactmath.h states every step once, for the
+ * host writer, the device encoder and the reader; tests/compact_ref.py restates it in numpy.
+ *  1. A record is valid iff position.xyz, color.rgba, scale.xyz and rotation are finite, scale.xyz >= 0 and
+ *     n2 = ((w*w + x*x) + y*y) + z*z is finite and > 0.  Invalid records are not written and are counted in `skipped`; N = valid records.
+ *  2. bmin / bmax: per-axis min / max of position.xyz over the valid records.
+ *  3. Per axis ext = bmax - bmin, i = ext > 0 ? min(1023, (uint)floorf(((p - bmin) / ext) * 1024.0f)) : 0 (0 too where that value is
+ *     a NaN, i.e. ext overflowed); key = part1by2(ix) | part1by2(iy) << 1 | part1by2(iz) << 2 (30 bits).
+ *  4. The valid records are sorted by key, stably (equal keys keep record order).  Chunk c = sorted rows [256 c, min(256 c + 256, N)),
+ *     C = ceil(N / 256).
+ *  5. Row values: p = position.xyz; ls_a = min(max(logf(scale_a * sm), -20), 20) with sm = the scale multiplier; col = color.rgb, or
+ *     with a baked plane col_c = sh[row][c] * 0.28209479177387814f + 0.5f; alpha = color.a; a = (w, x, y, z) / sqrtf(n2).
+ *  6. Chunk table, 18 floats per chunk: min_x min_y min_z max_x max_y max_z min_scale_x min_scale_y min_scale_z max_scale_x
+ *     max_scale_y max_scale_z min_r min_g min_b max_r max_g max_b — min / max over the chunk's rows of p, ls and col.
+ *  7. unorm(v, b), t = 2^b - 1: (uint)min(max(floorf(v * t + 0.5f), 0), t), 0 for a NaN.  nrm(v, lo, hi) = (hi - lo < 0.00001f) ? 0 :
+ *     (v - lo) / (hi - lo).  packed_position = unorm(nx, 11) << 21 | unorm(ny, 10) << 11 | unorm(nz, 11); packed_scale the same on ls;
+ *     packed_color = unorm(nr, 8) << 24 | unorm(ng, 8) << 16 | unorm(nb, 8) << 8 | unorm(alpha, 8) (alpha is not chunk-normalised);
+ *     packed_rotation: L = the first index with the largest |a_i| (a later one replaces it only if strictly larger); if a_L < 0 every
+ *     component is negated; word = L, then for i = 0..3, i != L, in order: word = word << 10 | unorm(a_i * 0.70710678f + 0.5f, 10).
+ *  8. SH element, written iff a baked plane of degree d >= 1 is given: K = (d + 1)^2 - 1, properties uchar f_rest_0 .. f_rest_{3K-1},
+ *     f_rest_{c K + i - 1} = coefficient i of channel c = word 3 + 15 c + i - 1 of the plane's float[48] row;
+ *     byte = (uint)min(max(truncf((v / 8.0f + 0.5f) * 256.0f), 0), 255), 0 for a NaN.  Rows in the order of the vertex rows.
+ *  9. File: the header has no comment lines and is exactly `ply`, `format binary_little_endian 1.0`, `element chunk C`, the 18
+ *     `property float` lines, `element vertex N`, `property uint packed_position`, `property uint packed_rotation`,
+ *     `property uint packed_scale`, `property uint packed_color`, with an SH element `element sh N` and its properties, `end_header`;
+ *     then the chunk table, the vertex rows, the SH rows.  N = 0: a valid header with C = 0 and no data.
+ * m2s_read_ply recognises the layout (a `chunk` element and the four packed_* properties) and decodes it: position = lo + t (hi - lo),
+ * scale = exp(ls) (the multiplier stays in it; z as decoded), colour and alpha, the quaternion with its largest component rebuilt as
+ * sqrt(max(0, 1 - a^2 - b^2 - c^2)); normal and pbr zero, has_pbr = 0; the sh element is bounds-checked and ignored. */
+/* Host only, the pin in plain C++ and the yardstick of the device path.  sh (or NULL): float[n][48] as m2s_download_sh gives it, of
+ * degree sh_degree (0..3; 0: the colour comes from the plane, no SH element).  out_counts (may be NULL) = { rows, chunks, skipped }.
+ * M2S_ERR_CAPACITY beyond 2^32-1 records. */
+m2s_status m2s_write_ply_compact(const char* path, const m2s_gaussian* records, const float* sh, uint32_t sh_degree, uint64_t n,
+                                 float scale_multiplier, uint64_t out_counts[3]);
+/* The context's records — converted, pruned, uploaded or adopted — as such a file; everything up to the file's bytes is computed on the
+ * device.  sm = gaussian_std / R as m2s_export_ply; records without a resolutionTarget (m2s_upload_records) are taken as R = 1.
+ * use_baked_sh: colour and SH element from the plane of the last m2s_bake_light, at its degree.  Leaves the records, the position plane,
+ * the sorted quads and their sources, the contribution accumulators and the SH plane as they are.  Synchronous.
+ * M2S_ERR_STATE without records, or with use_baked_sh without a plane of the records' count; M2S_ERR_CAPACITY beyond 2^32-1 records;
+ * M2S_ERR_INVALID for a gaussian_std that is not finite or <= 0. */
+m2s_status m2s_export_ply_compact(m2s_ctx* ctx, const char* path, float gaussian_std, int use_baked_sh, uint64_t out_counts[3]);
+/* Stages (ms) of the last m2s_export_ply_compact: box + keys, sort, pack (device events), download + write (host clock). */
+m2s_status m2s_last_compact_stage_ms(const m2s_ctx* ctx, float out_ms[4]);
+
 /* ---- scene I/O == SceneManager::loadModel (minus GL) and parsers::loadPlyFile ------------------------ */
 /* Host-side scene loaded from a binary glTF file: scene-graph transforms applied, de-indexed 17-float
  * vertex buffers, fallback normals/tangents, cumulative bboxes, RGBA8 textures (PNG) — exactly what
@@ -849,7 +897,7 @@ const m2s_mesh* m2s_host_scene_meshes(const m2s_host_scene* scene);
 const char* m2s_host_scene_mesh_name(const m2s_host_scene* scene, uint32_t i);   /* "<mesh name>_<counter>" */
 const char* m2s_host_scene_warnings(const m2s_host_scene* scene);                 /* skipped primitives etc. */
 /* Reads a binary .ply written by format 0 or 1 back into records (parsers.cpp:516-629): scale = exp,
- * alpha = sigmoid, colour = SH -> RGB, quaternion normalised.  Free with m2s_free_records. */
+ * alpha = sigmoid, colour = SH -> RGB, quaternion normalised; or a compact .ply ("compact export" above).  Free with m2s_free_records. */
 m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr);
 void m2s_free_records(m2s_gaussian* records);
 /* Message of the last failed scene-I/O call on this thread. */

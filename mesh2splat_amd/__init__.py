@@ -1,0 +1,6 @@
+def __getattr__(name):
+    # mesh2splat_amd.write_ply_compact without importing the converter (numpy, ctypes) with the package
+    if name in ("write_ply_compact", "write_ply"):
+        from . import converter
+        return getattr(converter, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

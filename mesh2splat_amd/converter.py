@@ -670,6 +670,19 @@ class Converter:
         """m2s_export_ply_sh: the context's records with the baked plane as a standard (format 0) .ply."""
         self._check(self._L.m2s_export_ply_sh(self._h, os.fsencode(path), float(gaussian_std)))
 
+    def export_ply_compact(self, path: str, gaussian_std: float = 0.65, baked_sh: bool = False) -> dict:
+        """m2s_export_ply_compact: the context's records as a compact .ply (Morton-ordered chunks of 256, 16 bytes per row; with baked_sh the
+        colour and the SH element come from the plane of the last bake_light()).  -> {"rows", "chunks", "skipped", "bytes", "stage_ms"}."""
+        counts = (C.c_uint64 * 3)()
+        self._check(self._L.m2s_export_ply_compact(self._h, os.fsencode(path), float(gaussian_std), 1 if baked_sh else 0, counts))
+        return {"rows": int(counts[0]), "chunks": int(counts[1]), "skipped": int(counts[2]), "bytes": os.path.getsize(path),
+                "stage_ms": self.last_compact_stage_ms()}
+
+    def last_compact_stage_ms(self) -> dict:
+        ms = (C.c_float * 4)()
+        self._check(self._L.m2s_last_compact_stage_ms(self._h, ms))
+        return {"box_keys": float(ms[0]), "sort": float(ms[1]), "pack": float(ms[2]), "download_write": float(ms[3])}
+
     def render_baked(self, prepass_params, download: bool = True):
         """What a standard 3DGS viewer shows of the baked records through `prepass_params`'s camera: sh_shade_records() from the camera
         position (the view matrix inverted), the viewer prepass in render mode 0 over the shaded copy, depth sort, splat.  -> the albedo
@@ -937,6 +950,23 @@ def write_ply(path: str, records: np.ndarray, fmt: int, scale_multiplier: float)
     st = _lib.load().m2s_write_ply(os.fsencode(path), r.ctypes.data, r.shape[0], int(fmt), float(scale_multiplier))
     if st != _lib.M2S_OK:
         raise _lib.M2SError(st, f"could not write {path}")
+
+
+def write_ply_compact(path: str, records: np.ndarray, scale_multiplier: float, sh: np.ndarray | None = None, sh_degree: int = 0) -> dict:
+    """m2s_write_ply_compact: the compact .ply of a host array of 96-byte records, on the CPU.  sh: (n, 48) float32 as download_sh() gives
+    it, of degree sh_degree.  -> {"rows", "chunks", "skipped"}."""
+    r = np.ascontiguousarray(records, np.float32).reshape(-1, RECORD_FLOATS)
+    p = None
+    if sh is not None:
+        p = np.ascontiguousarray(sh, np.float32)
+        if p.shape != (r.shape[0], 48):
+            raise ValueError("sh must be (n, 48) float32")
+    counts = (C.c_uint64 * 3)()
+    st = _lib.load().m2s_write_ply_compact(os.fsencode(path), r.ctypes.data if r.size else None, p.ctypes.data if p is not None else None,
+                                           int(sh_degree), r.shape[0], float(scale_multiplier), counts)
+    if st != _lib.M2S_OK:
+        raise _lib.M2SError(st, f"could not write {path}")
+    return {"rows": int(counts[0]), "chunks": int(counts[1]), "skipped": int(counts[2])}
 
 
 def write_ply_slice(path: str, records: np.ndarray, fmt: int, scale_multiplier: float, first_row: int, total_rows: int):

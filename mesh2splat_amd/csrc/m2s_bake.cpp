@@ -148,6 +148,7 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     c->sh_of = d_records;
     c->sh_epoch = d_records == c->last_records ? c->records_epoch : 0;
     c->bake_has_counts = counts;
+    c->sh_degree = bp->degree;
     return M2S_OK;
 }
 

@@ -9,6 +9,7 @@
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
+//   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of the viewer passes' buffers, pinned blocks and events (DevBuf, PinnedBuf, EventSet, BinWork)
 #pragma once
 #include "../../include/m2s.h"
@@ -275,6 +276,16 @@ struct m2s_ctx {
     uint32_t bake_table_nt = 0, bake_table_np = 0;
     m2s_host::EventSet<2> bake_ev;
     float last_bake_ms = 0.0f;
+    uint32_t sh_degree = 0;                      // degree of the last bake (the compact export's SH element)
+
+    // compact .ply export (m2s_compact.cpp): the pass's own buffers — the depth sort's words are the prune pass's sources and stay as they are
+    m2s_host::DevBuf<uint32_t> d_compact_u32;    // keys_in | vals_in | keys_out | vals_out, one capacity of words each
+    m2s_host::DevBuf<uint32_t> d_compact_waves;  // per-wave boxes (8 words each), then the 8 words of the fold; capacity in waves
+    m2s_host::DevBuf<void> d_compact_temp;       // the sort's work area; capacity in bytes
+    m2s_host::DevBuf<uint8_t> d_compact_out;     // chunk table | rows | SH bytes, each from a 256-byte boundary; capacity in bytes
+    m2s_host::PinnedBuf<uint32_t> h_compact;     // pinned { N, skipped }
+    m2s_host::EventSet<5> compact_ev;
+    float last_compact_stage_ms[4] = { 0, 0, 0, 0 };   // box + keys, sort, pack, download + write
 
     // measurement
     bool profiling = false;

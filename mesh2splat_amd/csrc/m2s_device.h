@@ -377,6 +377,18 @@ hipError_t launch_score(const ScoreK& k, const uint32_t* a, const uint32_t* b, c
                         unsigned long long* acc, hipStream_t st);
 hipError_t preload_score();
 
+// ---- compact .ply export (m2s_compact.hip): validity + box, Morton keys, stable sort, chunk encoder -----------------------------------
+inline uint32_t compact_waves(uint32_t n) { return (n + kBlock - 1) / kBlock * (kBlock / 64); }   // entries of the per-wave box table
+size_t compact_sort_temp_bytes(uint32_t n);
+// keys_in / vals_in / keys_out / vals_out: n words each; wave_box: compact_waves(n) * 8 words; head: 8 words, afterwards { min.xyz,
+// max.xyz of the valid positions in the order of m2s_compactmath.h's ord(), N, skipped }; the first N words of vals_out: the permutation.
+// ev: three events, around box + keys and around the sort.  n > 0.
+hipError_t compact_keys_and_sort(const float4* rec, const float4* plane, uint32_t n, uint32_t* wave_box, uint32_t* head, uint32_t* keys_in, uint32_t* vals_in,
+                                 uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, hipEvent_t* ev, hipStream_t st);
+// table: 18 floats per chunk; rows: N x 16 bytes; sh_out (K = 3 | 8 | 15): WHOLE chunks of 256 x 3 K bytes; sh: the baked plane or NULL
+hipError_t compact_pack(const float4* rec, const float* sh, const uint32_t* perm, uint32_t N, float sm, uint32_t K, float* table, void* rows, void* sh_out,
+                        hipStream_t st);
+
 // sample sort across ranks (m2s_dist.cpp): evenly spaced samples of sorted keys; split points of sorted keys
 void launch_pick_samples(const uint32_t* keys, uint64_t n, uint32_t s, unsigned long long* out, hipStream_t st);
 void launch_lower_bounds(const uint32_t* keys, uint64_t n, const unsigned long long* splitters, uint32_t m, unsigned long long* out, hipStream_t st);

@@ -19,7 +19,9 @@
 
 namespace m2s {
 
-__device__ __constant__ double kLogTab[16][2] = {
+// (m2s_logf.h hands the table and logf_glibc to the other row encoders by including this section alone: the restatement stays in the
+// one file whose constants the tests compare with the check program's)
+static __device__ __constant__ double kLogTab[16][2] = {
     { 0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2 }, { 0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2 },
     { 0x1.49539f0f010b0p+0, -0x1.01eae7f513a67p-2 }, { 0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3 },
     { 0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3 }, { 0x1.25e227b0b8ea0p+0, -0x1.1aa2bc79c8100p-3 },
@@ -57,6 +59,7 @@ __device__ __forceinline__ float logf_glibc(float x) {
     return (float)y;
 }
 
+#ifndef M2S_LOGF_SECTION_ONLY
 constexpr float kShC0 = 0.28209479177387814f;   // params.hpp:17 SH_COEFF0
 
 // glm::clamp == min(max(x, lo), hi) with glm's comparison order
@@ -126,5 +129,6 @@ void launch_encode_rows(const float4* rec, uint64_t n, uint32_t format, float sm
 
 // (m2s_device.h: preload_*) makes the runtime load this file's code object now instead of inside the first launch
 hipError_t preload_export() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_encode_rows)); }
+#endif  // M2S_LOGF_SECTION_ONLY
 
 }  // namespace m2s

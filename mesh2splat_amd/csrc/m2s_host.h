@@ -51,4 +51,11 @@ struct HostScene {
 // SceneManager::parseGltfFile + setupMeshBuffers + loadTextures for a .glb file.
 bool load_glb(const std::string& path, HostScene& scene, std::string& err);
 
+// m2s_compact_host.cpp — the compact layout (include/m2s.h "compact export") behind m2s_read_ply: 0 when the file's header is not that
+// layout (the caller goes on with its own parser), 1 when it was read (*out: malloc'ed records, *out_n of them), -1 when it is that
+// layout and was refused (*st: why; err: the message).  An untrusted-file reader: every count is checked against the file's size first.
+int read_compact_ply(const char* path, m2s_gaussian** out, uint64_t* out_n, std::string& err, m2s_status* st);
+// the exact header of such a file: C chunks, N rows, K coefficients per channel in the SH element (0: no element)
+std::string compact_ply_header(uint64_t n_chunks, uint64_t n_rows, uint32_t sh_k);
+
 }  // namespace m2s_host

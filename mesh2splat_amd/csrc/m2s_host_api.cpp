@@ -63,6 +63,12 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
     if (!path || !out_records || !out_n) { g_io_error = "NULL argument"; return M2S_ERR_INVALID; }
     *out_records = nullptr;
     *out_n = 0;
+    {   // the compact layout (a `chunk` element + the four packed_* properties) has its own decoder; every other file is read as before
+        m2s_status cs = M2S_OK;
+        const int compact = m2s_host::read_compact_ply(path, out_records, out_n, g_io_error, &cs);
+        if (compact > 0 && out_has_pbr) *out_has_pbr = 0;
+        if (compact) return cs;
+    }
     FILE* f = std::fopen(path, "rb");
     if (!f) { g_io_error = std::string("Error loading PLY file: ") + path; return M2S_ERR_IO; }
     m2s_gaussian* rec = nullptr;

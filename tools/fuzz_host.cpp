@@ -5,9 +5,17 @@
 //
 // Every iteration takes one seed file, applies a few mutations (bit flips, byte splats, truncation, 16/32-bit length
 // fields set to extreme values, chunk duplication, a block copied from another seed) and hands the result to the reader for
-// its kind: *.png / *.jpg straight to decode_png / decode_jpeg, *.glb to m2s_load_glb, *.ply to m2s_read_ply.  The readers
+// its kind: *.png / *.jpg straight to decode_png / decode_jpeg, *.glb to m2s_load_glb, *.ply to m2s_read_ply (formats 0 / 1 and the compact
+// layout; a .ply also gets the counts of its header replaced by extreme decimal numbers).  The readers
 // may accept or reject the file; the run fails only when a sanitizer reports, a reader crashes, or an accepted image has
 // an inconsistent size.  A line of statistics is printed at the end.
+//
+//   fuzz_host --compact-seeds <dir>
+//
+// writes the compact .ply seeds with the host writer (m2s_write_ply_compact, so that it runs under the sanitizers too): empty, one row,
+// 700 rows with hostile records among them, with and without an SH element.
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +52,7 @@ void mutate(std::vector<uint8_t>& b, const std::vector<Seed>& seeds) {
     static const uint32_t extremes[] = { 0u, 1u, 0x7Fu, 0x80u, 0xFFu, 0x100u, 0x7FFFu, 0x8000u, 0xFFFFu, 0x10000u, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFFu };
     const int n_mut = 1 + (int)below(6);
     for (int m = 0; m < n_mut && !b.empty(); ++m) {
-        switch (below(9)) {
+        switch (below(10)) {
         case 0: b[below(b.size())] ^= (uint8_t)(1u << below(8)); break;
         case 1: b[below(b.size())] = (uint8_t)rnd(); break;
         case 2: {   // splat a run
@@ -82,6 +90,23 @@ void mutate(std::vector<uint8_t>& b, const std::vector<Seed>& seeds) {
             for (size_t i = 0; i < len && at + i < b.size(); ++i) b[at + i] = o.bytes[from + i];
             break;
         }
+        case 8: {   // a .ply header's count replaced by an extreme decimal number
+            static const char* const counts[] = { "0", "1", "255", "257", "4294967295", "4294967296", "9223372036854775808", "18446744073709551615",
+                                                  "99999999999999999999999", "-1" };
+            const std::string text(b.begin(), b.begin() + std::min<size_t>(b.size(), 4096));
+            std::vector<size_t> at;
+            for (size_t p = text.find("element "); p != std::string::npos; p = text.find("element ", p + 1)) at.push_back(p);
+            if (at.empty()) break;
+            size_t p = text.find(' ', at[below(at.size())] + 8);
+            if (p == std::string::npos) break;
+            ++p;
+            size_t e = p;
+            while (e < text.size() && text[e] != '\n') ++e;
+            const char* c = counts[below(sizeof counts / sizeof *counts)];
+            b.erase(b.begin() + p, b.begin() + e);
+            b.insert(b.begin() + p, c, c + std::strlen(c));
+            break;
+        }
         default: {  // delete a block
             const size_t at = below(b.size()), len = 1 + below(std::min<size_t>(64, b.size() - at));
             b.erase(b.begin() + at, b.begin() + at + len);
@@ -93,7 +118,36 @@ void mutate(std::vector<uint8_t>& b, const std::vector<Seed>& seeds) {
 
 }  // namespace
 
+int write_compact_seeds(const std::string& dir) {
+    g_state = 0x636F6D70;
+    auto unit = [] { return (float)(rnd() >> 40) / (float)(1u << 24); };
+    std::vector<m2s_gaussian> rec(700);
+    std::vector<float> sh(rec.size() * 48);
+    for (auto& g : rec) {
+        for (int k = 0; k < 3; ++k) { g.position[k] = unit() * 4.0f - 2.0f; g.color[k] = unit(); g.scale[k] = unit() * 0.1f; g.normal[k] = 0.0f; }
+        g.position[3] = g.scale[3] = 1.0f; g.color[3] = unit(); g.normal[3] = 0.0f;
+        for (int k = 0; k < 4; ++k) { g.rotation[k] = unit() - 0.5f; g.pbr[k] = 0.0f; }
+    }
+    for (auto& v : sh) v = unit() * 10.0f - 5.0f;
+    rec[3].position[1] = NAN; rec[77].scale[0] = -1.0f; rec[300].rotation[0] = rec[300].rotation[1] = rec[300].rotation[2] = rec[300].rotation[3] = 0.0f;
+    rec[301].color[2] = INFINITY; rec[500].scale[2] = 1e30f;
+    struct { const char* name; uint64_t n; bool sh; uint32_t degree; } seeds[] = { { "compact_0.ply", 0, false, 0 }, { "compact_1.ply", 1, false, 0 },
+        { "compact_257.ply", 257, false, 0 }, { "compact_700_sh1.ply", 700, true, 1 }, { "compact_700_sh3.ply", 700, true, 3 }, { "compact_300_sh0.ply", 300, true, 0 } };
+    for (const auto& s : seeds) {
+        uint64_t counts[3];
+        const std::string path = dir + "/" + s.name;
+        if (m2s_write_ply_compact(path.c_str(), rec.data(), s.sh ? sh.data() : nullptr, s.degree, s.n, 0.01f, counts) != M2S_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
+        m2s_gaussian* back = nullptr;
+        uint64_t n = 0;
+        int pbr = 1;
+        if (m2s_read_ply(path.c_str(), &back, &n, &pbr) != M2S_OK || n != counts[0] || pbr != 0) { std::fprintf(stderr, "%s does not read back: %s\n", path.c_str(), m2s_io_last_error()); return 1; }
+        m2s_free_records(back);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 3 && !std::strcmp(argv[1], "--compact-seeds")) return write_compact_seeds(argv[2]);
     if (argc < 4) { std::fprintf(stderr, "usage: fuzz_host <iterations> <seed> <file>...\n"); return 2; }
     const long iters = std::atol(argv[1]);
     g_state = std::strtoull(argv[2], nullptr, 0);

@@ -69,6 +69,7 @@ struct Options {
     double score_elevation = 0.0;                                  // --score-elevation deg
     int score_mask = 2;                                            // --score-mask 0..3
     std::string score_map;                                         // --score-map prefix: the error maps as prefix_k.png
+    bool compact = false;                                          // --compact: out.ply in the compact layout (m2s_export_ply_compact) instead of --format's
     int prune_views = 0;                                           // --prune K: K cameras round the scene per elevation; drop the Gaussians none of them sees (m2s_prune)
     std::vector<double> prune_elevations = { -35.0, 0.0, 35.0 };   // --prune-elevations e1,e2,...
     double prune_weight = 1.0 / 255.0;                             // --prune-weight w: keep wmax > w
@@ -88,7 +89,7 @@ void usage() {
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
                  "         [--prune K [--prune-elevations e1,e2,...] [--prune-weight w] [--prune-pixels n] [--prune-count-weight c]]\n"
-                 "         [--bake-light [--bake-degree 0..3]]\n"
+                 "         [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -107,7 +108,12 @@ void usage() {
                  "--bake-light [--bake-degree 0..3 (default 3)]: --format 0 only, one GPU, one file.  After the conversion the shadow pass\n"
                  "  (cube 1024, quads sized for --preview-size, the --preview camera's near / far) and m2s_bake_light with --light (default: the\n"
                  "  preview light); the .ply's f_dc / f_rest carry the lit, shadowed colour as spherical harmonics (m2s_export_ply_sh), so a\n"
-                 "  standard 3DGS viewer shows the light.\n");
+                 "  standard 3DGS viewer shows the light.\n"
+                 "--compact: out.ply is written in the compact layout instead of --format's (m2s_export_ply_compact: Morton-ordered chunks of\n"
+                 "  256 rows, 16 bytes per row, laid out after the PlayCanvas compressed PLY; not verified against their reader).  It runs after\n"
+                 "  --prune; with --bake-light the file carries the SH element.  Prints ONE line `compact: {...}` of JSON per file: rows, chunks,\n"
+                 "  skipped, bytes, stage_ms (box + keys, sort, pack, download + write).  Not with --gpus N > 1 (the Morton order is global: slice\n"
+                 "  writers do not apply), hence not with --batch together with --gpus; --batch alone works.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -446,6 +452,18 @@ int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_
     return 0;
 }
 
+// --compact: the context's records as a compact .ply; prints one JSON line
+int export_compact(m2s_ctx* ctx, const std::string& out, const Options& o, bool baked) {
+    uint64_t c[3] = { 0, 0, 0 };
+    float ms[4] = { 0, 0, 0, 0 };
+    if (m2s_export_ply_compact(ctx, out.c_str(), (float)o.std_dev, baked ? 1 : 0, c) != M2S_OK || m2s_last_compact_stage_ms(ctx, ms) != M2S_OK) return 1;
+    long long bytes = -1;
+    if (FILE* f = std::fopen(out.c_str(), "rb")) { if (std::fseek(f, 0, SEEK_END) == 0) bytes = std::ftell(f); std::fclose(f); }
+    std::printf("compact: {\"rows\": %llu, \"chunks\": %llu, \"skipped\": %llu, \"bytes\": %lld, \"stage_ms\": [%.4f, %.4f, %.4f, %.4f]}\n",
+                (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], bytes, ms[0], ms[1], ms[2], ms[3]);
+    return 0;
+}
+
 // --prune K: K cameras round the scene at each elevation, at --preview-size; per camera m2s_prepass_sorted -> m2s_contrib_accumulate, then
 // m2s_prune (Converter.prune_views does the same).  Prints one JSON line.
 int run_prune(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
@@ -521,8 +539,10 @@ int convert_one(const Options& o) {
     if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
     if (o.bake_light) {
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
-        if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
-    } else if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
+        if (o.compact) { if (export_compact(ctx, o.out, o, true) != 0) return die("export"); }
+        else if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
+    } else if (o.compact) { if (export_compact(ctx, o.out, o, false) != 0) return die("export"); }
+    else if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
     if (!o.preview.empty()) {
         const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
         if (pr == 1) return die("preview");
@@ -764,7 +784,8 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
         Converted c;
         while (converted.pop(c)) {
             const auto a = Clock::now();
-            if (m2s_export_ply(ctx[c.slot], c.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) {
+            if (o.compact ? export_compact(ctx[c.slot], c.out, o, false) != 0
+                          : m2s_export_ply(ctx[c.slot], c.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) {
                 std::fprintf(stderr, "%s: export: %s\n", c.in.c_str(), m2s_last_error(ctx[c.slot])); ++failures;
             }
             const double ex = ms_between(a, Clock::now());
@@ -883,6 +904,7 @@ int main(int argc, char** argv) {
         else if (a == "--score-mask") { o.score_mask = std::atoi(next()); if (o.score_mask < 0 || o.score_mask > 3) { usage(); return 2; } }
         else if (a == "--score-map") o.score_map = next();
         else if (a == "--bake-light") o.bake_light = true;
+        else if (a == "--compact") o.compact = true;
         else if (a == "--bake-degree") { o.bake_degree = std::atoi(next()); if (o.bake_degree < 0 || o.bake_degree > 3) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
@@ -899,6 +921,7 @@ int main(int argc, char** argv) {
     if (o.gpus < 1 || o.gpus > 64) { usage(); return 2; }
     // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
     if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
+    if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
         if (o.out_dir.empty() || !pos.empty()) { usage(); return 2; }
