@@ -930,6 +930,12 @@ enum { M2S_PIPELINE_AUTO = 0, M2S_PIPELINE_MULTIPASS = 1,
 m2s_status m2s_set_pipeline(m2s_ctx* ctx, int pipeline);
 /* Which pipeline the last conversion actually ran: M2S_PIPELINE_MULTIPASS, _TEAM (k_fused2), _LEAN (k_fused3) or _SPARSE (k_sparse); 0 before any. */
 int m2s_last_pipeline(const m2s_ctx* ctx);
+/* The vertex table of the last m2s_upload_scene: *out_rows = distinct vertices among the resident triangles' corners (all 12 attribute
+ * floats compared bitwise; 0 when the scene was not counted: it cannot take the LEAN form, or has more than 2^22 triangles);
+ * *out_in_use = 1 when conversions in the LEAN form gather vertex attributes from that table (the indexed instance of k_fused3: fewer
+ * than 2^21 rows and at most half as many rows as corners), 0 when they read the per-corner planes.  m2s_last_pipeline says
+ * M2S_PIPELINE_LEAN for both; the records are the same bytes.  Either pointer may be NULL. */
+m2s_status m2s_vertex_table(const m2s_ctx* ctx, uint64_t* out_rows, int* out_in_use);
 
 /* ---- measurement ------------------------------------------------------------------------------- */
 enum { M2S_K_COUNT = 0, M2S_K_SCAN = 1, M2S_K_OFFSETS = 2, M2S_K_EMIT = 3, M2S_K_FUSED = 4, M2S_K_N = 5 };

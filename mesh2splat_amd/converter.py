@@ -932,6 +932,13 @@ class Converter:
         """What the last conversion ran: 'multipass', 'team' (k_fused2), 'lean' (k_fused3) or 'sparse' (k_sparse)."""
         return {0: "none", 1: "multipass", 3: "team", 4: "sparse", 5: "lean"}[self._L.m2s_last_pipeline(self._h)]
 
+    def vertex_table(self) -> dict:
+        """The last upload's vertex table: {'rows': distinct vertices among the resident corners (0: not counted), 'in_use': whether
+        conversions in the lean form gather from it (the indexed instance of k_fused3) instead of the per-corner planes}."""
+        rows, used = C.c_uint64(0), C.c_int(0)
+        self._check(self._L.m2s_vertex_table(self._h, C.byref(rows), C.byref(used)))
+        return {"rows": int(rows.value), "in_use": bool(used.value)}
+
     # -- measurement --------------------------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self._L.m2s_set_profiling(self._h, 1 if on else 0))

@@ -43,6 +43,8 @@ void free_scene(m2s_ctx* c) {
     c->warm_R = 0; c->warm_total = 0; c->warm_mismatch_seen = false;
     c->sparse_off_R = c->team_off_R = c->lean_off_R = UINT32_MAX;
     c->lean_ok = false;
+    c->d_vt_rows.release(); c->d_vt_ids.release();
+    c->vt_rows = 0; c->vt_use = false;
     c->scene = SceneDev{};
     c->has_scene = false;
 }
@@ -233,6 +235,13 @@ m2s_status m2s_set_pipeline(m2s_ctx* c, int pipeline) {
 }
 
 int m2s_last_pipeline(const m2s_ctx* c) { return c ? c->last_pipeline : 0; }
+
+m2s_status m2s_vertex_table(const m2s_ctx* c, uint64_t* out_rows, int* out_in_use) {
+    if (!c) return M2S_ERR_INVALID;
+    if (out_rows) *out_rows = c->vt_rows;
+    if (out_in_use) *out_in_use = c->vt_use ? 1 : 0;
+    return M2S_OK;
+}
 
 int m2s_positions_ready(const m2s_ctx* c) {
     return c && c->d_pos_plane && c->last_records && c->pos_plane_of == c->last_records && c->pos_plane_n == c->last_stored &&

@@ -15,6 +15,7 @@
 #include "../../include/m2s.h"
 #include "m2s_devbuf.h"
 #include "m2s_device.h"
+#include "m2s_vdedup.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -58,6 +59,12 @@ struct m2s_ctx {
     bool has_scene = false;
     bool lean_ok = false;                   // every mesh of the scene samples its combo texture or no map at all: k_fused3 may run
     uint64_t range_first = 0, range_count = UINT64_MAX;
+    // the resident shard's distinct vertices (m2s_vdedup.hip), decided once per upload: conversions in the lean form gather from the
+    // table (the indexed instance of k_fused3) while vt_use holds; the planes stay for everything else
+    m2s_host::DevBuf<float4> d_vt_rows;     // three float4 per row; capacity in float4
+    m2s_host::DevBuf<m2s::VtIds> d_vt_ids;  // per resident triangle
+    uint32_t vt_rows = 0;                   // distinct vertices of the last upload (0: not counted — the scene was out of the table's range)
+    bool vt_use = false;
 
     // work buffers (sized by the scene)
     uint32_t* d_cnt = nullptr;

@@ -4,6 +4,7 @@
 #pragma once
 #include "m2s_device.h"
 #include "m2s_exact.h"
+#include "m2s_vtable.h"
 
 #pragma clang fp contract(off)
 
@@ -727,6 +728,22 @@ struct TriShadeS {
 };
 static_assert(sizeof(TriShadeS) == 64, "TriShadeS must be four float4");
 
+// TriShadeS of the indexed instance of k_fused3 (the scene has a vertex table, m2s_vtable.h): the 8 bytes of lod1 / lod2 — on the combo
+// path the two level offsets, which follow from the level nibbles in mesh[31:24] and the mesh's (wave-uniform) combo.coff[] — hold the
+// triangle's three row ids instead (vt_pack).  Everything else as in TriShadeS, which k_sparse and the plane instance keep.
+struct TriShadeSI {
+    short a1, b1, a2, b2;
+    int e1, e2;
+    float inva, sx, sy, lod0;
+    float4 rot;
+    uint32_t vid_lo, vid_hi;
+    uint32_t org;
+    uint32_t mesh;
+};
+static_assert(sizeof(TriShadeSI) == 64, "TriShadeSI must be four float4");
+template <class TS> inline constexpr bool kTsHasIds = false;
+template <> inline constexpr bool kTsHasIds<TriShadeSI> = true;
+
 __device__ __forceinline__ float lod_from_grad(float fw, float fh, float dudx, float dvdx, float dudy, float dvdy) {
     const float sx = dudx * fw, tx = dvdx * fh, sy = dudy * fw, ty = dvdy * fh;
     const float r2 = fmaxf(fma_(tx, tx, sx * sx), fma_(ty, ty, sy * sy));
@@ -962,8 +979,16 @@ __device__ __forceinline__ void combo_issue(MP mp, TD t, float uf, float vf, con
     // level selection was done per triangle (tri_shade_setup)
     const uint32_t w = t->w, h = t->h;
     const float f = ts.lod0;
-    const uint32_t off0 = __float_as_uint(ts.lod1), off1 = __float_as_uint(ts.lod2);
     const uint32_t l0 = (ts.mesh >> 24) & 15u, l1 = ts.mesh >> 28;
+    uint32_t off0, off1;
+    if constexpr (kTsHasIds<TS>) {   // the selection tri_shade_rest made, repeated from the same nibbles and the same table
+        const uint32_t c1 = mp->combo.coff[1], c2 = mp->combo.coff[2], c3 = mp->combo.coff[3], c4 = mp->combo.coff[4];
+        off0 = l0 == 0 ? 0u : l0 == 1 ? c1 : l0 == 2 ? c2 : l0 == 3 ? c3 : c4;
+        off1 = l1 == 0 ? 0u : l1 == 1 ? c1 : l1 == 2 ? c2 : l1 == 3 ? c3 : c4;
+    } else {
+        off0 = __float_as_uint(ts.lod1);
+        off1 = __float_as_uint(ts.lod2);
+    }
     const uint32_t* __restrict__ base = mp->combo.texels;
     ComboTap& tlo = cf.tlo;
     ComboTap& thi = cf.thi;
@@ -1031,6 +1056,17 @@ __device__ __forceinline__ T ld_attr(const T* base, uint32_t t) {
     }
 }
 
+// float4 k (0 .. 2) of row `id` of the vertex table (m2s_vtable.h); 32-bit byte offset from a wave-uniform base, as ld_plane.
+// ld_row3: its first three words only (the fourth of rows 0 and 1 is a texture coordinate, which the strips take from LDS).
+__device__ __forceinline__ float4 ld_row4(const float4* rows, uint32_t id, uint32_t k) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(rows) + (size_t)(id * 48u + k * 16u));
+}
+struct RowXYZ { float x, y, z; };
+__device__ __forceinline__ RowXYZ ld_row3(const float4* rows, uint32_t id, uint32_t k) {
+    const float* p = reinterpret_cast<const float*>(__builtin_assume_aligned(reinterpret_cast<const char*>(rows) + (size_t)(id * 48u + k * 16u), 16));
+    return RowXYZ{ p[0], p[1], p[2] };
+}
+
 // The per-fragment part of rasteriser + FS (converterFS.glsl:44-104) for pixel (x,y) of triangle t.
 // `mp` should be wave-uniform (scalar) for speed; correctness does not depend on it.
 // `stamps` (debug timing builds only, else nullptr and folded away): three s_memtime slots.
@@ -1042,11 +1078,13 @@ __device__ __forceinline__ T ld_attr(const T* base, uint32_t t) {
 // kComboOnly (k_fused3): the caller guarantees that the mesh samples through its combo texture or has no map at all; the
 // separate-maps sampler is then not compiled into the caller (it is what sets the register count of the fragment stage).
 // kStreamAttr (A/B switch of k_fused3): the normal and tangent planes, which a conversion reads once, are loaded non-temporally.
+// TS = TriShadeSI (the indexed instance of k_fused3): positions, normals and tangents come from the rows `vrows` of the vertex table
+// through the ids in ts — the words the planes hold, from another address; `tp` and `t` are then not used for them.
 template <class MP, class TS = TriShade, bool kComboOnly = false, bool kStreamAttr = false>   // TS: TriShade, or the 64-byte TriShadeS (same field names)
 __device__ __forceinline__ void shade_from_tri(const TriPlanes& tp, uint32_t t, int x, int y, MP mp,
                                                const TS& ts, float4 rec[6], unsigned long long* stamps = nullptr,
                                                const float2* uvl = nullptr /* (u0,v0), (u1-u0,v1-v0), (u2-u0,v2-v0) kept by the caller */,
-                                               const float* posl = nullptr /* the nine position words (A0, A1, A2) kept by the caller */) {
+                                               const float4* vrows = nullptr /* TriShadeSI: the vertex table */) {
     // screen-linear barycentrics from the exact integer edge functions, evaluated relative to the
     // triangle's bbox origin pixel: E_i(x,y) = E_i(x0,y0) + a_i*256*(x-x0) + b_i*256*(y-y0)
     const int dx256 = (x - (int)(ts.org & 0xFFFu)) * 256, dy256 = (y - (int)(ts.org >> 12)) * 256;
@@ -1075,19 +1113,23 @@ __device__ __forceinline__ void shade_from_tri(const TriPlanes& tp, uint32_t t, 
         b0 = ld_plane(tp.B0, t);
         b1 = ld_plane(tp.B1, t);
     }
-    float4 a0, a1;
-    float a2;
-    if (posl == nullptr) {
+    float4 a0, a1, c0, c1, d0, d1, d2;
+    float a2, c2;
+    if constexpr (kTsHasIds<TS>) {
+        uint32_t i0, i1, i2;
+        vt_unpack(VtIds{ ts.vid_lo, ts.vid_hi }, i0, i1, i2);
+        const RowXYZ p0 = ld_row3(vrows, i0, 0), p1 = ld_row3(vrows, i1, 0), p2 = ld_row3(vrows, i2, 0);
+        const RowXYZ n0 = ld_row3(vrows, i0, 1), n1 = ld_row3(vrows, i1, 1), n2 = ld_row3(vrows, i2, 1);
+        d0 = ld_row4(vrows, i0, 2); d1 = ld_row4(vrows, i1, 2); d2 = ld_row4(vrows, i2, 2);
+        // (in the planes' arrangement, so that the interpolation below is one text for both sources)
+        a0 = make_float4(p0.x, p0.y, p0.z, p1.x); a1 = make_float4(p1.y, p1.z, p2.x, p2.y); a2 = p2.z;
+        c0 = make_float4(n0.x, n0.y, n0.z, n1.x); c1 = make_float4(n1.y, n1.z, n2.x, n2.y); c2 = n2.z;
+    } else {
         a0 = ld_plane(tp.A0, t); a1 = ld_plane(tp.A1, t);
         a2 = ld_plane(tp.A2, t);
-    }
-    const float4 c0 = ld_attr<kStreamAttr>(tp.C0, t), c1 = ld_attr<kStreamAttr>(tp.C1, t);
-    const float c2 = ld_attr<kStreamAttr>(tp.C2, t);
-    const float4 d0 = ld_attr<kStreamAttr>(tp.D0, t), d1 = ld_attr<kStreamAttr>(tp.D1, t), d2 = ld_attr<kStreamAttr>(tp.D2, t);
-    if (posl != nullptr) {   // (the same words the planes hold: the caller copied them)
-        a0 = make_float4(posl[0], posl[1], posl[2], posl[3]);
-        a1 = make_float4(posl[4], posl[5], posl[6], posl[7]);
-        a2 = posl[8];
+        c0 = ld_attr<kStreamAttr>(tp.C0, t); c1 = ld_attr<kStreamAttr>(tp.C1, t);
+        c2 = ld_attr<kStreamAttr>(tp.C2, t);
+        d0 = ld_attr<kStreamAttr>(tp.D0, t); d1 = ld_attr<kStreamAttr>(tp.D1, t); d2 = ld_attr<kStreamAttr>(tp.D2, t);
     }
     float U, V;
     {   // texture coordinates: exact oracle sequence (no FMA), see tri_shade_setup

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "m2s_vtable.h"
+
 namespace m2s {
 
 // Debug / A-B switches of the library (M2S_NO_BANDS, M2S_NO_LEAN, M2S_NO_WARM, ...) exist only in a DEBUG BUILD (`make EXTRA=-DM2S_DEBUG_BUILD
@@ -185,10 +187,11 @@ void launch_fused2(const SceneDev& sc, uint32_t R, unsigned long long* chain, ui
                    unsigned long long* total, uint32_t* status, uint32_t epoch, BigItem* biglist, uint32_t* bigmeta,
                    const RunInfo& runs, const BatchTable& batches, hipStream_t st);
 // lean form of the team kernel (m2s_fused3.hip): same units, same run tables, same output; only for scenes whose meshes all sample
-// a combo texture or no map at all (m2s_ctx::lean_ok); triangles larger than an 8 x 8 pixel box are deferred to k_emit_big
+// a combo texture or no map at all (m2s_ctx::lean_ok); triangles larger than an 8 x 8 pixel box are deferred to k_emit_big.
+// vt (or nullptr): the scene's vertex table (m2s_vtable.h) — the indexed instance runs, whose strips gather from it instead of the planes
 void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,
                    unsigned long long* total, uint32_t* status, uint32_t epoch, BigItem* biglist, uint32_t* bigmeta,
-                   const RunInfo& runs, const BatchTable& batches, hipStream_t st);
+                   const RunInfo& runs, const BatchTable& batches, hipStream_t st, const VtxTable* vt = nullptr);
 // sparse form of the single-pass kernel (m2s_sparse.hip); `runs` as for launch_fused2, in ITS units (512 triangles)
 // plane (or nullptr): the positions of the records as a compact plane (16 B each, record order): what a depth sort builds its keys from
 void launch_sparse(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,

@@ -1,4 +1,4 @@
-// m2s_fused3.hip — single-pass conversion kernel, the LEAN form of the team kernel (gfx950; round 5).
+// m2s_fused3.hip — single-pass conversion kernel, the LEAN form of the team kernel (gfx950).
 //
 // k_fused2 (m2s_fused2.hip) is compiled for every scene the library accepts: triangles of up to 16 pixel rows expanded in the
 // workgroup (a 30-register row walker), edge functions in 64 bits, three separately sized maps sampled in one round trip (75
@@ -22,8 +22,22 @@
 //     the triangle phase has the B planes in registers anyway, and a strip computes its texel addresses without a global round trip
 //     in front of them (and without fetching the two planes a second time).
 //
+// Two instances (template <bool kIndexed>; launch_fused3 picks by whether the upload left a vertex table, m2s_ctx::vt_use):
+//   * k_fused3<false>, the plane instance: a strip gathers its triangle's positions, normals and tangents from the per-corner SoA planes
+//     (A, C, D: 120 B per triangle, every vertex once per corner that uses it);
+//   * k_fused3<true>, the indexed instance: the upload deduplicated the shard's corners into a table of distinct vertices (m2s_vdedup.hip;
+//     rows of three float4: (p.xyz, u), (n.xyz, v), (t.xyzw); config 3: 501 128 rows for 3 006 756 corners) and left three row ids per
+//     triangle, packed in 8 bytes (VtIds, m2s_vtable.h).  The triangle phase reads them with the B planes (one coalesced 8-byte load)
+//     and stores them in the 8 bytes of the fragment constants that otherwise hold the combo texture's two level offsets (TriShadeSI:
+//     the strips re-derive the offsets from the level nibbles in mesh[31:24] and the mesh's wave-uniform combo.coff[]); F3Lds does not
+//     grow.  A strip then takes nine row loads through the ids it has in LDS — no dependent global read in front of them — in place of
+//     the nine plane loads: the same operand bits from another address, the interpolation text unchanged, the records byte for byte
+//     those of the plane instance.  Neighbouring triangles read the same rows, so a workgroup's gathers touch ~48 B per triangle
+//     instead of 120.  The triangle phase itself still reads positions and coordinates from planes A / B, and
+//     k_emit_big (deferred triangles) and every other kernel read planes only.
+//
 // LDS per workgroup (F3Lds, 40 824 of the 40 960 bytes that four workgroups per CU leave each):
-//     tri      16 384   TriShadeS, [wave][lane]
+//     tri      16 384   TriShadeS / TriShadeSI, [wave][lane]
 //     uv        6 144   float2[3], [wave][lane]
 //     tskip     1 024   [wave][lane]; read only by strips of a workgroup with deferred triangles
 //     cum         512   uint16 [wave][slot]: inclusive prefix of the entry counts over the wave's COVERED triangles (slot = rank of the
@@ -36,13 +50,12 @@
 // position inside that wave's entries): the popcount is the slot at that position; a lane's slot is that plus the `first` flags
 // between the wave's first lane in the strip and itself.
 //
-// kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup).
+// kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup; both instances: 110 registers, no scratch).
 // Measurement-only switches (compile time; the A/B tables of DESIGN 6): M2S_FUSED3_UV_GLOBAL — the strips load the B planes as they
-// did before the coordinates moved to LDS; M2S_FUSED3_ABL_POS — the strips take the positions from stale LDS words instead of the
-// A planes (WRONG records: what the second read of those planes costs); M2S_FUSED3_NT_ATTR — normals / tangents as non-temporal loads;
+// did before the coordinates moved to LDS; M2S_FUSED3_NT_ATTR — normals / tangents of the plane instance as non-temporal loads;
 // M2S_FUSED3_TRI_PRIO — 0: every wave at one priority throughout, 2: phase classes (below), with M2S_FUSED3_PRIO_FLOOR.
 //
-// Priority (round 7).  A wave runs its triangle phase — ~950 VALU instructions and no wait after its loads — at priority 1 and drops to 0 when
+// Priority.  A wave runs its triangle phase — ~950 VALU instructions and no wait after its loads — at priority 1 and drops to 0 when
 // its counts are published: the waits and the strips run at 0.  From the second generation of workgroups on, a wave in the triangle phase
 // shares its SIMD with three waves in strips, which issue a few instructions between long waits; ahead of them it leaves the phase ~1 us
 // sooner (mean 6.8 -> 5.7 us on config 3) and its workgroup's texel requests start that much earlier.  Priority only orders issue — nothing a
@@ -50,6 +63,8 @@
 // (f3_class: which of the four dispatch slots of its CU it took), to make the waves of one SIMD leave the phase one after another — the
 // first generation's triangle phase is not issue-bound (8 us at any priority), so the classes order nothing.
 #include "m2s_fused_common.h"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -172,13 +187,17 @@ constexpr int kTlXccId = 20 | (3 << 11);     // HW_REG_XCC_ID, bits 3:0
 #define TLFV(k, v) do { } while (0)
 #endif
 
+struct VtNone { };   // the plane instance takes no table
+template <bool kIndexed>
 __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDev sc, uint32_t R, unsigned long long* __restrict__ chain,
                                                       unsigned long long limit, float4* __restrict__ out,
                                                       unsigned long long* __restrict__ total_out,
                                                       uint32_t* __restrict__ status /* [0]=any big, [1]=error */, uint32_t epoch,
                                                       BigItem* __restrict__ biglist, uint32_t* __restrict__ bigmeta,
                                                       uint32_t tpw /* triangles per wave: 64 .. 8 (fused_tpw) */,
-                                                      RunInfo runs, BatchTable bt) {
+                                                      RunInfo runs, BatchTable bt,
+                                                      std::conditional_t<kIndexed, VtxTable, VtNone> vt) {
+    using TS = std::conditional_t<kIndexed, TriShadeSI, TriShadeS>;   // what the strips read from S.tri
     __shared__ F3Lds S;
     F3Ctl& C = S.ctl;
     const int lane = threadIdx.x & 63;
@@ -244,6 +263,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         uint32_t m = 0;
         float4 uvb0 = make_float4(0, 0, 0, 0);
         float2 uvb1 = make_float2(0, 0);
+        [[maybe_unused]] uint2 vid = make_uint2(0, 0);   // indexed: the triangle's three row ids, packed at upload (VtIds)
         bool uniform_mesh = false;     // the wave's batch lies inside one mesh (m0): mesh uniforms through scalar loads
         uint32_t m0 = 0;
         if (has_batch) {
@@ -254,6 +274,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
                 load_positions(sc.tri, t, p);
                 uvb0 = sc.tri.B0[t];
                 uvb1 = sc.tri.B1[t];
+                if constexpr (kIndexed) vid = ld_plane(reinterpret_cast<const uint2*>(vt.ids), t);
                 if (uniform_mesh) geo_setup_mp(p, kConstMesh(sc.meshes + m0), g);
                 else { m = find_mesh(sc, sc.tri_first + t); geo_setup_mp(p, sc.meshes + m, g); }
                 box = raster_head(g, R, h);
@@ -279,7 +300,10 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
             else tri_shade_small(p, g, h, rs, sc.meshes + m, uvb0, uvb1, m, c);
             const float4* src = reinterpret_cast<const float4*>(&c);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) S.tri[wave][lane * 4 + k] = src[k];
+            for (int k = 0; k < 3; ++k) S.tri[wave][lane * 4 + k] = src[k];
+            // (indexed: the ids take the place of the two level offsets, which the strips re-derive — TriShadeSI)
+            if constexpr (kIndexed) S.tri[wave][lane * 4 + 3] = make_float4(__uint_as_float(vid.x), __uint_as_float(vid.y), src[3].z, src[3].w);
+            else S.tri[wave][lane * 4 + 3] = src[3];
             // ... and its texture coordinates in the form the strips interpolate (the subtractions shade_from_tri would do itself)
             float2* const uvs = &S.uv[wave][lane * 3];
             uvs[0] = make_float2(uvb0.x, uvb0.y);
@@ -484,7 +508,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
             const uint32_t m_now = __builtin_amdgcn_readlane(my_mesh, __ffsll((long long)todo) - 1);
             const bool mine = have && my_mesh == m_now;
             if (mine) {
-                const TriShadeS& ts = *reinterpret_cast<const TriShadeS*>(&S.tri[ow][tl * 4]);
+                const TS& ts = *reinterpret_cast<const TS*>(&S.tri[ow][tl * 4]);
                 const uint32_t tt = C.t0[ow] + tl;
                 const uint32_t org = ts.org;
                 const int x = (int)(org & 0xFFFu) + (int)(bit & 7u), y = (int)(org >> 12) + (int)(bit >> 3);
@@ -495,13 +519,10 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
 #else
                 const float2* const uvl = &S.uv[ow][tl * 3];
 #endif
-#ifdef M2S_FUSED3_ABL_POS
-                const float* const posl = reinterpret_cast<const float*>(&S.tri[ow][tl * 4]);
-#else
-                const float* const posl = nullptr;
-#endif
-                shade_from_tri<ConstMeshPtr, TriShadeS, true, kF3StreamAttr>(sc.tri, tt, x, y, kConstMesh(sc.meshes + __builtin_amdgcn_readfirstlane(my_mesh)),
-                                                                              ts, rec, nullptr, uvl, posl);
+                const float4* vrows = nullptr;
+                if constexpr (kIndexed) vrows = reinterpret_cast<const float4*>(vt.rows);
+                shade_from_tri<ConstMeshPtr, TS, true, kF3StreamAttr>(sc.tri, tt, x, y, kConstMesh(sc.meshes + __builtin_amdgcn_readfirstlane(my_mesh)),
+                                                                       ts, rec, nullptr, uvl, vrows);
             }
             todo &= ~__ballot(mine);
         }
@@ -571,7 +592,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
 
 void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,
                    unsigned long long* total, uint32_t* status, uint32_t epoch, BigItem* biglist, uint32_t* bigmeta,
-                   const RunInfo& runs, const BatchTable& bt, hipStream_t st) {
+                   const RunInfo& runs, const BatchTable& bt, hipStream_t st, const VtxTable* vt) {
     const uint32_t tpw = fused_tpw(sc.n_tri);
     const uint32_t n_batches = bt.first ? bt.n : n_fused_waves(sc.n_tri);
     if (!n_batches) return;
@@ -581,8 +602,12 @@ void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, ui
     if (r.base) r.out = nullptr;
     if (r.base) nb = ((nb + (8u << r.shift) - 1u) / (8u << r.shift)) * (8u << r.shift);   // whole groups of eight runs; surplus workgroups exit at once
     else nb = (nb + 7u) & ~7u;
-    hipLaunchKernelGGL(k_fused3, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
-                       epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt);
+    if (vt && vt->rows && vt->ids)
+        hipLaunchKernelGGL(k_fused3<true>, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
+                           epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt, *vt);
+    else
+        hipLaunchKernelGGL(k_fused3<false>, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
+                           epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt, VtNone{});
 }
 
 #ifdef M2S_TIMELINE
@@ -597,7 +622,8 @@ extern "C" int m2s_debug_timeline_f3_clear() {
 }
 namespace m2s {
 #endif
-uint32_t fused3_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused3), kL3Threads); }
-hipError_t preload_fused3() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused3)); }
+// (both instances are compiled for the same registers and LDS: one answer)
+uint32_t fused3_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused3<false>), kL3Threads); }
+hipError_t preload_fused3() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused3<false>)); }
 
 }  // namespace m2s

@@ -75,8 +75,11 @@ void launch_single(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t R, unsig
     uint32_t* status = reinterpret_cast<uint32_t*>(&res[1]);
     if (ri.form == M2S_PIPELINE_SPARSE)
         launch_sparse(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, st, plane);
-    else if (ri.form == M2S_PIPELINE_LEAN)
-        launch_fused3(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
+    else if (ri.form == M2S_PIPELINE_LEAN) {
+        const VtxTable vt{ c->d_vt_rows.get(), c->d_vt_ids.get() };
+        launch_fused3(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st,
+                      c->vt_use ? &vt : nullptr);
+    }
     else
         launch_fused2(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);
 }

@@ -278,6 +278,15 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     const bool warm = !debug_on("M2S_NO_WARM");
     bool counted = false;
     if (warm && !debug_on("M2S_NO_WARM_OVERLAP")) counted = warm_count_enqueue(c, warm_R) == M2S_OK;
+    // the shard's distinct vertices (m2s_vdedup.hip): hash insertion, flags and scan run behind the repack while the host stages the
+    // textures; the table itself is written after the upload's synchronisation, when its size is known.  A failure here (memory)
+    // costs the scene its table, nothing else.
+    VtWork vt_work;
+    bool vt_begun = false;
+    if (vt_size_ok(c->lean_ok, n_tri) && !debug_on("M2S_NO_VTABLE")) {
+        vt_begun = vt_dedup_begin(tp, n_tri, vt_work, c->stream) == hipSuccess;
+        if (!vt_begun) (void)hipGetLastError();
+    }
 
     // ---- textures: level 0 through the same staging, levels 1..4 on the device (glUtils.cpp:292-313) -----------------
     for (TexPlan& p : tex_plan) {
@@ -298,6 +307,13 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));  // mp / mesh_first are host temporaries; the caller's buffers are released
     HIPCHK(c, hipGetLastError());
+    if (vt_begun) {
+        if (vt_dedup_finish(tp, n_tri, vt_work, kVtIdLimit, kVtMinSharing, c->d_vt_rows, c->d_vt_ids, &c->vt_rows, &c->vt_use, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            c->d_vt_rows.release(); c->d_vt_ids.release();
+            c->vt_use = false;
+        }
+    }
     c->last_upload_ms[2] = ms_since(t_tex);
     c->has_scene = true;
     // what the first conversion would otherwise have to find out inside its own call (see warm_scene)

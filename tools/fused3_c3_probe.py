@@ -5,8 +5,8 @@ tracing beside it) or `rocprofv3 --kernel-trace --stats` when only this kernel i
     python tools/fused3_c3_probe.py [--launches 20] [--check]
 
 The library is the one M2S_LIB_PATH names (A/B and measurement builds), else the package's.  Prints one JSON line: the counter, the
-pipeline that ran and — with --check — a CRC of the records (measurement builds such as -DM2S_FUSED3_ABL_POS write wrong records on
-purpose: compare the CRC with the shipping build's to see that a build is what it claims to be).
+pipeline that ran, whether the strips gathered from the upload's vertex table (the indexed instance) and — with --check — a CRC of the
+records (compare it with the shipping build's to see that a measurement build writes the same bytes).
 """
 import argparse
 import json
@@ -33,7 +33,7 @@ def main():
         total = 0
         for _ in range(a.launches):
             total = c.convert(1024)
-        out = {"total": total, "pipeline": c.last_pipeline, "launches": a.launches}
+        out = {"total": total, "pipeline": c.last_pipeline, "launches": a.launches, "vertex_table": c.vertex_table()}
         if a.check:
             out["crc32"] = "%08x" % zlib.crc32(c.download().tobytes())
     print(json.dumps(out))

@@ -9,7 +9,10 @@ import sys
 def summarise(path):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(path)):
-        agg[r["Kernel_Name"].split("(")[0]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+        name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0]
+        if name.startswith("void "):      # a kernel template: "void m2s::k_fused3<true>(...)" counts as m2s::k_fused3
+            name = name[5:]
+        agg[name.split("<")[0]][r["Counter_Name"]].append(float(r["Counter_Value"]))
     return {k: {c: sum(v) / len(v) for c, v in d.items()} for k, d in agg.items()}
 
 

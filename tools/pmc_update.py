@@ -26,22 +26,29 @@ def traffic(d):
 c3all = json.load(open(os.path.join(O, TAG + "_pmc_c3_summary.json")))
 k3 = "k_fused3" if "m2s::k_fused3" in c3all else "k_fused2"      # the kernel AUTO runs on config 3 (round 5: the lean team kernel)
 c3 = c3all["m2s::" + k3]
-c5 = json.load(open(os.path.join(O, TAG + "_pmc_c5_summary.json")))["m2s::k_sparse"]
-c2 = json.load(open(os.path.join(O, TAG + "_pmc_c2_summary.json")))["m2s::k_fused2"]
+# (a session that measured config 3 only leaves no c5 / c2 summaries: their entries then stay as they are)
+have_rest = all(os.path.exists(os.path.join(O, TAG + f"_pmc_{w_}_summary.json")) for w_ in ("c5", "c2"))
+c5 = json.load(open(os.path.join(O, TAG + "_pmc_c5_summary.json")))["m2s::k_sparse"] if have_rest else None
+c2 = json.load(open(os.path.join(O, TAG + "_pmc_c2_summary.json")))["m2s::k_fused2"] if have_rest else None
 r, w = traffic(c3)
 t.update({"FETCH_SIZE_KB": c3["FETCH_SIZE"], "WRITE_SIZE_KB": c3["WRITE_SIZE"], k3 + "_read_bytes": r, k3 + "_write_bytes": w,
           k3 + "_hbm_bytes_per_launch": r + w, "kernel": k3})
-t.setdefault("binary_sha", {}).update({k3: sha, "k_sparse": sha, "k_fused2_c2": sha})
-t["source_round" + RND[-1]] = ("profiles/" + RND + "/final_pmc_{c3,c2,c5,hetero}_summary.json (tools/ab/" + RND.replace("0", "") + "_final.sh <tag> pmc: separate --pmc "
-                      "passes FETCH_SIZE / WRITE_SIZE / two SQ sets, 23 blocking launches each; mean per launch); library sha256[:16] " + sha)
-r5, w5 = traffic(c5)
-t["c5"] = {"workload": "c5 at full size (50 037 168 triangles, 24 267 048 Gaussians)", "kernel": "k_sparse", "algorithmic_bytes": 9534988800.0,
-           "k_sparse_read_bytes": r5, "k_sparse_write_bytes": w5, "k_sparse_hbm_bytes_per_launch": r5 + w5,
-           "traffic_over_algorithmic": (r5 + w5) / 9534988800.0}
-r2, w2 = traffic(c2)
-t["c2"] = {"workload": "c2 stand-in (69 312 triangles, R = 512, 684 624 Gaussians)", "kernel": "k_fused2", "algorithmic_bytes": 75704832.0,
-           "k_fused2_read_bytes": r2, "k_fused2_write_bytes": w2, "k_fused2_hbm_bytes_per_launch": r2 + w2,
-           "traffic_over_algorithmic": (r2 + w2) / 75704832.0}
+t.setdefault("binary_sha", {}).update({k3: sha, "k_sparse": sha, "k_fused2_c2": sha} if have_rest else {k3: sha})
+if have_rest:
+    t["source_round" + RND[-1]] = ("profiles/" + RND + "/final_pmc_{c3,c2,c5,hetero}_summary.json (tools/ab/" + RND.replace("0", "") + "_final.sh <tag> pmc: separate --pmc "
+                                   "passes FETCH_SIZE / WRITE_SIZE / two SQ sets, 23 blocking launches each; mean per launch); library sha256[:16] " + sha)
+else:
+    t["source_round" + RND[-1]] = ("profiles/" + RND + "/final_pmc_c3_summary.json (one rocprofv3 --pmc pass per counter, FETCH_SIZE and WRITE_SIZE, on "
+                                   "tools/fused3_c3_probe.py: 20 blocking launches of " + k3 + " each; mean per launch); library sha256[:16] " + sha)
+if have_rest:
+    r5, w5 = traffic(c5)
+    t["c5"] = {"workload": "c5 at full size (50 037 168 triangles, 24 267 048 Gaussians)", "kernel": "k_sparse", "algorithmic_bytes": 9534988800.0,
+               "k_sparse_read_bytes": r5, "k_sparse_write_bytes": w5, "k_sparse_hbm_bytes_per_launch": r5 + w5,
+               "traffic_over_algorithmic": (r5 + w5) / 9534988800.0}
+    r2, w2 = traffic(c2)
+    t["c2"] = {"workload": "c2 stand-in (69 312 triangles, R = 512, 684 624 Gaussians)", "kernel": "k_fused2", "algorithmic_bytes": 75704832.0,
+               "k_fused2_read_bytes": r2, "k_fused2_write_bytes": w2, "k_fused2_hbm_bytes_per_launch": r2 + w2,
+               "traffic_over_algorithmic": (r2 + w2) / 75704832.0}
 het = os.path.join(O, TAG + "_pmc_hetero_summary.json")
 if os.path.exists(het):
     h = json.load(open(het))
