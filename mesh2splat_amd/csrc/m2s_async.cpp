@@ -1,17 +1,9 @@
 // m2s_async.cpp — m2s_convert_submit / m2s_convert_wait: a ring of result slots so that consecutive conversions run back to
 // back (the reference blocks in glFinish once per conversion, ConversionPass.cpp:54).
 #include "m2s_ctx.h"
-#include "m2s_ply.h"
 
 #include <algorithm>
-#include <array>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <thread>
-#include <tuple>
-#include <vector>
 
 using namespace m2s;
 using namespace m2s_host;
@@ -25,12 +17,12 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
     if (c->slot_count == M2S_MAX_IN_FLIGHT) return fail(c, M2S_ERR_STATE, "M2S_MAX_IN_FLIGHT conversions already in flight");
     if (!c->has_scene) return fail(c, M2S_ERR_STATE, "m2s_upload_scene has not been called");
     if (R == 0 || R > 4096) return fail(c, M2S_ERR_INVALID, "R must be in [1, 4096]");
-    hipStream_t st = d_records ? (hipStream_t)hip_stream : c->stream;
     const uint32_t k = (c->slot_head + c->slot_count) % M2S_MAX_IN_FLIGHT;
     m2s_ctx::Slot& sl = c->slot[k];
     const uint64_t cap = resolve_cap(c, R);
     m2s_ctx::RInfo& ri = rinfo_for(c, R);
-    uint64_t limit = d_records ? (cap ? std::min(cap, capacity_records) : capacity_records) : cap ? cap : c->records_cap;
+    const m2s_host::Lane& l0 = c->lane[0];
+    uint64_t limit = d_records ? (cap ? std::min(cap, capacity_records) : capacity_records) : cap ? cap : l0.records.cap();
     if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
     const uint32_t n_start = emit2_slices(limit);
     // Fast path, enqueued without waiting: this scene at this R already converted cleanly with the single kernel (no deferred
@@ -39,87 +31,69 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
     // synchronously; with kernel timing on it runs synchronously: the per-kernel events are shared); and the output buffer needs no
     // (re)allocation.
     const bool mp = ri.form == M2S_PIPELINE_MULTIPASS;
-    const bool own_ready = d_records || (c->d_records && c->buf_R[0] == R && (cap ? c->records_cap >= cap : true));
+    const bool own_ready = d_records || (l0.records && l0.rec_R == R && (cap ? l0.records.cap() >= cap : true));
     const bool fast = c->scene.n_tri > 0 && own_ready &&
                       (mp ? ri.mp_ready && !c->profiling && (c->pipeline == M2S_PIPELINE_AUTO || c->pipeline == M2S_PIPELINE_MULTIPASS) &&
-                                c->start_cap >= n_start && c->d_setup
+                                l0.start.cap() >= n_start && l0.setup
                           : ri.async_ok);
     sl.R = R;
     sl.wrote_bands = false;
-    sl.own_lane = d_records ? -1 : 0;
-    // All conversions of a context share its work buffers (look-back chain, counts, offsets, the deferred-triangle
-    // list): they must execute in submission order.  On one stream that is automatic; a submission on ANOTHER stream
-    // than the newest one in flight is ordered behind it with an event.  (The second lane is exempt: it has its own
-    // chain and is only taken by single-kernel conversions that touch nothing else.)
-    auto chain_behind_newest = [&](hipStream_t on) -> hipError_t {
-        // the newest in-flight submission that used the SHARED work buffers (everything but second-lane submissions, which
-        // have a chain of their own): if it runs on another stream, this one is ordered behind it
-        for (uint32_t q = c->slot_count; q-- > 0;) {
-            const m2s_ctx::Slot& prev = c->slot[(c->slot_head + q) % M2S_MAX_IN_FLIGHT];
-            if (prev.sync_result || !prev.shared_work) continue;
-            return prev.st == on ? hipSuccess : hipStreamWaitEvent(on, prev.done, 0);
-        }
-        return hipSuccess;
-    };
     if (!fast) {
         // first conversion of a (scene, R), or one that needs the second stage / the multi-pass pipeline: run it now
         // (run_pass first lets everything in flight finish: it may re-allocate the record pool and reuses the work buffers)
         uint64_t total = 0;
-        const m2s_status s = run_pass(c, R, d_records, capacity_records, st, &total, true);
-        if (s != M2S_OK) return s;
+        M2S_TRY(run_pass(c, R, d_records, capacity_records, d_records ? (hipStream_t)hip_stream : c->stream, &total, true));
         sl.sync_result = true;
         sl.shared_work = false;
         sl.sync_total = total;
         memcpy(sl.ms, c->last_ms, sizeof sl.ms);   // a later submit overwrites last_ms before this slot is waited for
         sl.limit = c->last_stored;   // already clamped
         sl.d_out = const_cast<void*>(c->last_records);
-        sl.gen = c->buf_gen[0];
+        sl.own_lane = d_records ? -1 : 0;
+        sl.gen = l0.rec_gen;
         ++c->slot_count;
         return M2S_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    void* d_out = d_records ? d_records : c->d_records;
-    unsigned long long* chain = c->d_chain;
-    bool second_lane = false;
-    if (!d_records && (k & 1u) && c->lanes == 2) {
-        // odd slots: the second lane (allocated on first use), with work buffers of its own — nothing is shared with the conversion
-        // before it, so its kernels run beside that conversion's tail.  Records of consecutive conversions then alternate between
-        // two context-owned buffers; m2s_device_records / m2s_download follow the conversion last waited for.
-        { const m2s_status s2 = ensure_second_lane(c); if (s2 != M2S_OK) return s2; }
-        if (mp) { const m2s_status s2 = ensure_second_lane_multipass(c, n_start); if (s2 != M2S_OK) return s2; }
-        st = c->stream_b;
-        chain = c->d_chain_b;
-        d_out = c->d_records_b;
-        second_lane = true;
-        sl.own_lane = 1;
-    }
-    // (every submission that uses the shared chain is ordered behind the newest one that did, whatever stream that ran on — a
-    //  first-lane submission after a conversion into a caller's buffer on the caller's stream included: ADVICE r2)
-    if (!second_lane) HIPCHK(c, chain_behind_newest(st));
+    // Odd slots of a context-owned submission take lane 1 where the caller has asked for two lanes: with a stream, a chain, a record
+    // buffer and a work set of its own nothing is shared with the conversion before it, so its kernels run beside that conversion's
+    // tail.  Records of consecutive conversions then alternate between two context-owned buffers; m2s_device_records / m2s_download
+    // follow the conversion last waited for.
+    const int L = !d_records && (k & 1u) && c->lanes == 2 ? 1 : 0;
+    M2S_TRY(ensure_lane(c, L, L && mp, n_start));   // (lane 0: `fast` has seen its work set)
+    m2s_host::Lane& ln = c->lane[L];
+    hipStream_t st = d_records ? (hipStream_t)hip_stream : ln.stream;
+    void* d_out = d_records ? d_records : ln.records.get();
+    sl.own_lane = d_records ? -1 : L;
+    // All conversions on lane 0 share its work buffers (look-back chain, counts, offsets, the deferred-triangle list) whatever stream
+    // they run on: they must execute in submission order.  On one stream that is automatic; otherwise this one is ordered behind the
+    // newest in flight that used them, with an event — a lane-0 submission after a conversion into a caller's buffer on the caller's
+    // stream included
+    if (L == 0)
+        if (m2s_ctx::Slot* prev = newest_in_flight(c, [](const m2s_ctx::Slot& o) { return !o.sync_result && o.shared_work; }))
+            if (prev->st != st) HIPCHK(c, hipStreamWaitEvent(st, prev->done[0], 0));
     if (sl.own_lane >= 0) {
-        if (c->buf_R[sl.own_lane] != R) { c->buf_R[sl.own_lane] = R; ++c->buf_gen[sl.own_lane]; }
-        sl.gen = c->buf_gen[sl.own_lane];
+        if (ln.rec_R != R) { ln.rec_R = R; ++ln.rec_gen; }
+        sl.gen = ln.rec_gen;
     }
     unsigned long long* res = &c->h_total[2 + 2 * k];
     res[0] = 0; res[1] = 0;
     sl.prof = c->profiling;
     if (mp) {
-        const m2s_status s = enqueue_multipass(c, R, (float4*)d_out, limit, false, res, st, second_lane);
-        if (s != M2S_OK) return s;
+        M2S_TRY(enqueue_multipass(c, L, R, (float4*)d_out, limit, false, res, st));
     } else {
         uint32_t epoch;
         HIPCHK(c, next_epoch(c, &epoch));
-        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t0, st));
+        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t[0], st));
         sl.bands_unit = unit_of(ri.form);
-        launch_single(c, ri, R, chain, limit, (float4*)d_out, res, epoch, bands_for(c, ri, sl.bands_unit, !second_lane && c->lanes == 1, &sl.wrote_bands),
+        launch_single(c, ri, R, ln.chain, limit, (float4*)d_out, res, epoch, bands_for(c, ri, sl.bands_unit, L == 0 && c->lanes == 1, &sl.wrote_bands),
                       st, nullptr);
-        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t1, st));
+        if (sl.prof) HIPCHK(c, hipEventRecord(sl.t[1], st));
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(sl.done, st));
+    HIPCHK(c, hipEventRecord(sl.done[0], st));
     c->last_pipeline = ri.form;
-    if (!second_lane) c->last_submit_stream = st;
-    sl.st = st; sl.shared_work = !second_lane; sl.ri_gen = ri.gen;
+    sl.st = st; sl.shared_work = L == 0; sl.ri_gen = ri.gen;
     sl.sync_result = false;
     sl.limit = limit;
     sl.d_out = d_out;
@@ -138,7 +112,7 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
     // LATER submission at another R has been enqueued into the buffer this conversion wrote, its records are not what
     // that buffer holds (any more): consumers (m2s_download, m2s_export_ply, m2s_prepass, sorts) then refuse instead of
     // returning the other conversion's records.
-    const bool stale = sl.own_lane >= 0 && sl.gen != c->buf_gen[sl.own_lane];
+    const bool stale = sl.own_lane >= 0 && sl.gen != c->lane[sl.own_lane].rec_gen;
     if (sl.sync_result) {   // run_pass already filled last_*
         if (out_total) *out_total = sl.sync_total;
         c->last_total = sl.sync_total; c->last_stored = sl.limit; c->last_records = sl.d_out; c->last_R = sl.R;
@@ -147,11 +121,11 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
         memcpy(c->last_ms, sl.ms, sizeof sl.ms);
         return M2S_OK;
     }
-    HIPCHK(c, wait_event(sl.done));
+    HIPCHK(c, wait_event(sl.done[0]));
     const uint64_t total = c->h_total[2 + 2 * k];
     const uint32_t any_big = (uint32_t)(c->h_total[3 + 2 * k] & 0xFFFFFFFFull), err = (uint32_t)(c->h_total[3 + 2 * k] >> 32);
     memset(c->last_ms, 0, sizeof c->last_ms);
-    if (sl.prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_FUSED], sl.t0, sl.t1));
+    if (sl.prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_FUSED], sl.t[0], sl.t[1]));
     // what is remembered about (scene, R) may have been dropped since the submission (full table, m2s_set_pipeline): only an
     // entry of the generation the submission was made under is updated, and none is created here
     auto rit = c->rinfo.find(sl.R);

@@ -1,16 +1,10 @@
 // m2s_context.cpp — context lifetime, policy setters, the record pool and the launch tags of the look-back chains.
 #include "m2s_ctx.h"
-#include "m2s_ply.h"
 
 #include <algorithm>
-#include <array>
 #include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
-#include <tuple>
-#include <vector>
 
 using namespace m2s;
 using namespace m2s_host;
@@ -21,21 +15,12 @@ thread_local std::string g_create_error = "";
 
 namespace m2s_host {
 void free_scene(m2s_ctx* c) {
-    if (c->tri_mem) (void)hipFree(c->tri_mem);
-    if (c->scene_arena) (void)hipFree(c->scene_arena);
-    if (c->d_chain_b) (void)hipFree(c->d_chain_b);
-    if (c->d_setup) (void)hipFree(c->d_setup);
-    if (c->d_off_b) (void)hipFree(c->d_off_b);
-    if (c->d_start_b) (void)hipFree(c->d_start_b);
-    if (c->d_setup_b) (void)hipFree(c->d_setup_b);
-    if (c->d_total_b) (void)hipFree(c->d_total_b);
-    c->d_chain_b = nullptr; c->d_setup = nullptr;
-    c->d_off_b = nullptr; c->d_start_b = nullptr; c->start_b_cap = 0; c->d_setup_b = nullptr; c->d_total_b = nullptr;
-    c->tri_mem = nullptr; c->scene_arena = nullptr;
-    // everything below lived inside the arena
+    c->tri_mem.release(); c->scene_arena.release();
+    c->lane[0].release_scene(false); c->lane[1].release_scene(true);
+    // everything below lived inside the arena (lane 0's chain and offsets too)
     c->d_meshes = nullptr; c->d_mesh_first = nullptr;
-    c->d_cnt = c->d_off = c->d_partials = nullptr;
-    c->d_chain = nullptr; c->d_biglist = nullptr; c->d_bigmeta = nullptr; c->d_bands = nullptr; c->run_table_words = 0; c->d_run_order = nullptr; c->run_order_unit = 0;
+    c->d_cnt = c->d_partials = nullptr;
+    c->d_biglist = nullptr; c->d_bigmeta = nullptr; c->d_bands = nullptr; c->run_table_words = 0; c->d_run_order = nullptr; c->run_order_unit = 0;
     c->d_batch_first = nullptr; c->n_batch_tab = 0; c->chain_words = 0;
     c->rinfo.clear();
     ++c->rinfo_gen;
@@ -82,24 +67,23 @@ hipError_t wait_stream(hipStream_t st) { return spin_then_block([&] { return hip
 hipError_t wait_event(hipEvent_t ev) { return spin_then_block([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); }); }
 
 // every conversion still in flight has finished when this returns (their slots stay queued for m2s_convert_wait)
-void drain_in_flight(m2s_ctx* c) {
-    for (uint32_t k = 0; k < c->slot_count; ++k) {
-        auto& sl = c->slot[(c->slot_head + k) % M2S_MAX_IN_FLIGHT];
-        if (!sl.sync_result) (void)hipEventSynchronize(sl.done);
-    }
+void drain_in_flight(m2s_ctx* c, int lane) {
+    each_in_flight(c, [&](m2s_ctx::Slot& sl) {
+        if (!sl.sync_result && (lane < 0 || sl.own_lane == lane)) (void)hipEventSynchronize(sl.done[0]);
+    });
 }
 
 // Chain words carry a 16-bit launch tag instead of being cleared per launch.  The two single-pass kernels use different
 // numbers of words, so a word one of them left behind could read as freshly published 65 536 launches later: when the
-// tag wraps, everything in flight is drained and both chains are cleared (once per ~10 s of back-to-back conversions).
+// tag wraps, everything in flight is drained and every lane's chain is cleared (once per ~10 s of back-to-back conversions).
 hipError_t next_epoch(m2s_ctx* c, uint32_t* out) {
     const uint32_t e = ++c->epoch;
     *out = e;
     if ((e & 0xFFFFu) != 0) return hipSuccess;
     const size_t bytes = std::max<size_t>(c->chain_words, 1) * sizeof(unsigned long long);
     hipError_t r = hipDeviceSynchronize();
-    if (r == hipSuccess && c->d_chain) r = hipMemset(c->d_chain, 0, bytes);
-    if (r == hipSuccess && c->d_chain_b) r = hipMemset(c->d_chain_b, 0, bytes);
+    for (const Lane& ln : c->lane)
+        if (r == hipSuccess && ln.chain) r = hipMemset(ln.chain, 0, bytes);
     return r;
 }
 
@@ -107,22 +91,19 @@ hipError_t next_epoch(m2s_ctx* c, uint32_t* out) {
 // (ConversionPass.cpp:25-33), i.e. on every move of the density slider; here a change of R costs no allocation: the pool
 // doubles until it reaches the largest size the cap policy can ask for (7 M records = 672 MB for the reference formula).
 m2s_status ensure_records(m2s_ctx* c, uint64_t want) {
-    if (c->records_cap >= want && c->d_records) return M2S_OK;
+    Lane& l0 = c->lane[0];
+    if (l0.records.cap() >= want && l0.records) return M2S_OK;
     uint64_t grow = std::max<uint64_t>(want, 1);
-    if (c->records_cap) grow = std::max(grow, 2 * c->records_cap);
+    if (l0.records.cap()) grow = std::max(grow, 2 * l0.records.cap());
     if (c->cap_policy < 0) grow = std::max(want, std::min<uint64_t>(grow, kMaxGaussiansToSort));
     drain_in_flight(c);   // nothing may still be writing the buffer that is about to be released
-    if (c->d_records && c->last_records == c->d_records) { c->last_records = nullptr; c->last_stored = 0; }   // they go with the old pool
-    if (c->d_records) { (void)hipFree(c->d_records); c->d_records = nullptr; c->records_cap = 0; }
-    hipError_t e = hipMalloc(&c->d_records, grow * sizeof(m2s_gaussian));
-    if (e != hipSuccess && grow > want) { grow = want; e = hipMalloc(&c->d_records, grow * sizeof(m2s_gaussian)); }
-    HIPCHK(c, e);
-    c->records_cap = grow;
+    if (l0.records && c->last_records == l0.records) { c->last_records = nullptr; c->last_stored = 0; }   // they go with the old pool
+    // (the larger request may fail where the one the caller needs still fits)
+    if (grow == want || !l0.records.try_reserve(grow, sizeof(m2s_gaussian))) M2S_TRY(l0.records.reserve(c->err, want, sizeof(m2s_gaussian)));
     // in-flight conversions into the old buffer are complete but their records are gone
-    for (uint32_t k = 0; k < c->slot_count; ++k) {
-        auto& sl = c->slot[(c->slot_head + k) % M2S_MAX_IN_FLIGHT];
-        if (sl.own_lane == 0) { sl.d_out = c->d_records; sl.gen = c->buf_gen[0] - 1u; }
-    }
+    each_in_flight(c, [&](m2s_ctx::Slot& sl) {
+        if (sl.own_lane == 0) { sl.d_out = l0.records; sl.gen = l0.rec_gen - 1u; }
+    });
     return M2S_OK;
 }
 }  // namespace m2s_host
@@ -147,29 +128,28 @@ m2s_status m2s_create(int device, m2s_ctx** out_ctx) {
     m2s_ctx* c = new (std::nothrow) m2s_ctx();
     if (!c) { g_create_error = "host allocation failed"; return M2S_ERR_OOM; }
     c->device = device;
-    auto bail = [&](const char* what, hipError_t he) {
-        g_create_error = std::string(what) + ": " + hipGetErrorString(he);
-        delete c;
-        return M2S_ERR_HIP;
-    };
-    if ((e = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipMalloc(&c->d_total, sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipHostMalloc((void**)&c->h_total, m2s_ctx::kPinnedWords * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
-        return bail("hipHostMalloc", e);
-    for (auto& ev : c->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    for (auto& ev : c->stage_ev)
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     unsigned done_flags = hipEventDisableTiming;   // (completion only: its time is never asked for)
     if (const char* v = debug_env("M2S_DONE_EVENT_FLAGS")) {   // debug: A/B of event kinds; anything but a combination of the known bits is ignored
         const unsigned f = (unsigned)strtoul(v, nullptr, 0);
         if ((f & ~(hipEventBlockingSync | hipEventDisableTiming | hipEventReleaseToDevice | hipEventReleaseToSystem)) == 0u) done_flags = f;
     }
-    for (auto& sl : c->slot)
-        if ((e = hipEventCreateWithFlags(&sl.done, done_flags)) != hipSuccess || (e = hipEventCreate(&sl.t0)) != hipSuccess ||
-            (e = hipEventCreate(&sl.t1)) != hipSuccess)
-            return bail("hipEventCreate", e);
+    // everything a conversion needs is created here, none of it inside one; what exists when a step fails goes with the context
+    m2s_status s = hip_status(c->err, "hipSetDevice", hipSetDevice(device));
+    if (!s) s = c->streams.ensure(c->err, 0);
+    if (!s) s = c->lane[0].total.reserve(c->err, 1, sizeof(unsigned long long));
+    if (!s) s = c->h_total.ensure(c->err, m2s_ctx::kPinnedWords * sizeof(unsigned long long));
+    if (!s) s = c->ev.ensure(c->err);
+    if (!s) s = c->stage_ev.ensure(c->err, hipEventDisableTiming);
+    for (auto& sl : c->slot) {
+        if (!s) s = sl.done.ensure(c->err, done_flags);
+        if (!s) s = sl.t.ensure(c->err);
+    }
+    if (s) {
+        g_create_error = c->err;
+        delete c;
+        return M2S_ERR_HIP;
+    }
+    c->stream = c->lane[0].stream = c->streams[0];
     *out_ctx = c;
     return M2S_OK;
 }
@@ -177,28 +157,10 @@ m2s_status m2s_create(int device, m2s_ctx** out_ctx) {
 void m2s_destroy(m2s_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (const Lane& ln : c->lane)
+        if (ln.stream) (void)hipStreamSynchronize(ln.stream);
     drain_in_flight(c);   // conversions still in flight on a caller's stream
-    free_scene(c);
-    if (c->d_start) (void)hipFree(c->d_start);
-    if (c->d_records) (void)hipFree(c->d_records);
-    if (c->d_records_b) (void)hipFree(c->d_records_b);
-    if (c->stream_b) { (void)hipStreamSynchronize(c->stream_b); (void)hipStreamDestroy(c->stream_b); }
-    for (int k = 0; k < 2; ++k) {
-        if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-        if (c->d_stage[k]) (void)hipFree(c->d_stage[k]);
-        if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
-    }
-    if (c->d_total) (void)hipFree(c->d_total);
-    if (c->h_total) (void)hipHostFree(c->h_total);
-    for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& sl : c->slot) {
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.t0) (void)hipEventDestroy(sl.t0);
-        if (sl.t1) (void)hipEventDestroy(sl.t1);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;   // the viewer passes' buffers, pinned blocks and events go with their members (m2s_devbuf.h)
+    delete c;   // buffers, pinned blocks and events go with their members, the streams last (m2s_devbuf.h)
 }
 
 m2s_status m2s_set_triangle_range(m2s_ctx* c, uint64_t first, uint64_t count) {

@@ -138,28 +138,28 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
         kept = n - by_w - by_p;
         // The survivors go into the pool.  Records that live there already (or a plane compacted in place) cannot be compacted onto
         // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
-        const bool in_pool = c->last_records == c->d_records;
+        const bool in_pool = c->last_records == c->lane[0].records;
         const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
         if (stage_bytes) M2S_TRY(c->d_prune_stage.reserve(c->err, stage_bytes, 1));
         const void* src = c->last_records;
         if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
         if (kept) {
-            float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->d_records;
+            float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
             HIPCHK(c, prune_compact((const float4*)src, flags, offsets, (uint32_t)n, 6, dst, c->stream));
-            if (in_pool) HIPCHK(c, hipMemcpyAsync(c->d_records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+            if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
             if (sh) {
                 HIPCHK(c, prune_compact((const float4*)c->d_sh.get(), flags, offsets, (uint32_t)n, 12, c->d_prune_stage, c->stream));
                 HIPCHK(c, hipMemcpyAsync(c->d_sh, c->d_prune_stage, kept * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             }
         }
-    } else if (!c->d_records || c->last_records != c->d_records) {
+    } else if (!c->lane[0].records || c->last_records != c->lane[0].records) {
         if (m2s_status s = ensure_records(c, 1)) return s;
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_prune_ms, c->prune_ev[0], c->prune_ev[1]));
     // the survivors are the context's current records now, at the resolutionTarget of the ones they were taken from
-    c->last_records = c->d_records;
+    c->last_records = c->lane[0].records;
     ++c->records_epoch;
     c->last_total = c->last_stored = kept;
     c->last_R = R;

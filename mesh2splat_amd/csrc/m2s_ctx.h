@@ -1,6 +1,7 @@
 // m2s_ctx.h — the context behind the C ABI (include/m2s.h) and the helpers its translation units share.  Internal.
-//   m2s_context.cpp  lifetime, setters, record pool, launch tags          m2s_upload.cpp   m2s_upload_scene / m2s_prepare
-//   m2s_pass.cpp     the conversion pass driver (== ConversionPass::execute)   m2s_async.cpp    m2s_convert_submit / _wait
+//   m2s_context.cpp  lifetime, setters, record pool, in-flight waits, launch tags   m2s_upload.cpp   m2s_upload_scene / m2s_prepare
+//   m2s_pass.cpp     the conversion pass driver (== ConversionPass::execute), what a lane needs before a conversion (ensure_lane)
+//   m2s_async.cpp    m2s_convert_submit / _wait
 //   m2s_records.cpp  read-back, .ply export, record adoption               m2s_viewer.cpp   depth sort, viewer prepass
 //   m2s_splat.cpp    the splat pass (== GaussianSplattingPass::execute) and its G-buffer
 //   m2s_light.cpp    the shadow and relighting passes (== GaussianShadowPass / GaussianRelightingPass::execute)
@@ -10,7 +11,7 @@
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
-//   m2s_devbuf.h     the owners of the viewer passes' buffers, pinned blocks and events (DevBuf, PinnedBuf, EventSet, BinWork)
+//   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_devbuf.h"
@@ -47,11 +48,12 @@ struct GBufPlanes {
 constexpr int kBandSlotsMax = 64;   // (scene, R) entries remembered per context: band tables, decisions
 struct m2s_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    m2s_host::StreamSet<2> streams;         // lane k's stream; in front of every buffer and event: destroyed after them
+    hipStream_t stream = nullptr;           // streams[0] == lane[0].stream: what every pass but a second-lane conversion runs on
     std::string err;
 
     // scene
-    void* tri_mem = nullptr;
+    m2s_host::DevBuf<char> tri_mem;         // the geometry planes; released with the scene, like the arena
     m2s::SceneDev scene{};
     m2s::MeshParams* d_meshes = nullptr;
     uint32_t* d_mesh_first = nullptr;
@@ -68,18 +70,13 @@ struct m2s_ctx {
 
     // work buffers (sized by the scene)
     uint32_t* d_cnt = nullptr;
-    uint32_t* d_off = nullptr;
     uint32_t* d_partials = nullptr;
-    uint32_t* d_start = nullptr;
-    size_t start_cap = 0;
-    unsigned long long* d_total = nullptr;
-    unsigned long long* h_total = nullptr;  // pinned, kPinnedWords words: [0] = fragment counter, [1] = status words of the fused kernel,
+    m2s_host::PinnedBuf<unsigned long long> h_total;   // kPinnedWords words: [0] = fragment counter, [1] = status words of the fused kernel,
                                             // [2 + 2k], [3 + 2k] = the same of in-flight slot k, then one word each for the prepass and the depth sort
     static constexpr int kPinnedPrepass = 2 + 2 * M2S_MAX_IN_FLIGHT;   // m2s_prepass: TWO words — survivors, then the status words of its look-back
     static constexpr int kPinnedSortMM = 4 + 2 * M2S_MAX_IN_FLIGHT;    // the depth sorts: {min, max} of the keys (two 32-bit words); NOT the prepass's second word —
                                                                        // m2s_prepass_sorted uses both inside one call
     static constexpr int kPinnedWords = 6 + 2 * M2S_MAX_IN_FLIGHT;                  // (the sorts' word and the one behind it: {min, max}, {survivors, clash})
-    unsigned long long* d_chain = nullptr;  // look-back chain of the fused kernel, one word per wave
     m2s::BigItem* d_biglist = nullptr;           // triangles deferred by the fused kernel (capacity: triangles in range)
     uint32_t* d_bigmeta = nullptr;          // [0] entries in d_biglist, [1] largest, [2] total fragment count; zero between conversions
     // What the context remembers about the uploaded scene at a given resolution R.  The reference converts on load and
@@ -117,44 +114,31 @@ struct m2s_ctx {
     uint32_t run_order_unit = 0, run_order_shift = 0;   // ... for runs of (1 << shift) units of this many triangles (0: none)
     uint32_t* d_batch_first = nullptr;      // work-balanced batches of k_fused2 (small scenes; built from the first exact count)
     uint32_t n_batch_tab = 0;               // batches in it (0: uniform batches)
-    size_t chain_words = 0;                 // words of d_chain (and of the second lane's chain)
-    void* d_setup = nullptr;                // multi-pass pipeline: per-triangle TriSetup records (allocated at its first use)
+    size_t chain_words = 0;                 // words of every lane's chain
     int last_pipeline = 0;                  // what the last conversion ran (m2s_last_pipeline)
-    // second lane for context-owned asynchronous submissions: odd slots run on their own stream with their own chain
-    // and record buffer, so that consecutive single-kernel conversions overlap (the tail of one, where the GPU drains,
-    // with the head of the next) instead of paying ~8 us between dependent kernels on one stream
+    // What conversions work in (m2s_devbuf.h), one set per lane.  Lane 0: every synchronous conversion, and the record pool (records:
+    // ensure_records).  Lane 1, for context-owned asynchronous submissions: odd slots run on their own stream with their own chain
+    // and record buffer, so that consecutive single-kernel conversions overlap (the tail of one, where the GPU drains, with the head
+    // of the next) instead of paying ~8 us between dependent kernels on one stream; and multi-pass conversions too — with a work set
+    // of its own, k_count_scan of conversion i + 1 runs beside k_emit2 of conversion i.  Lane 1 is filled at its first use (ensure_lane).
+    m2s_host::Lane lane[2];
     int lanes = 1;                          // m2s_set_async_lanes
-    hipStream_t stream_b = nullptr;
-    unsigned long long* d_chain_b = nullptr;
-    void* d_records_b = nullptr;
-    uint64_t records_b_cap = 0;
-    // ... and multi-pass conversions too: the second lane's own offsets / slice starts / TriSetup records / counter (allocated at
-    // its first multi-pass submission), so that k_count_scan of conversion i + 1 runs beside k_emit2 of conversion i
-    uint32_t* d_off_b = nullptr;
-    uint32_t* d_start_b = nullptr;
-    size_t start_b_cap = 0;
-    void* d_setup_b = nullptr;
-    unsigned long long* d_total_b = nullptr;
     int pipeline = M2S_PIPELINE_AUTO;
     uint32_t epoch = 0;                     // launch counter of the fused kernel (tags the chain words)
 
     // asynchronous submissions (m2s_convert_submit / m2s_convert_wait): a ring of result slots.  Slot k uses
     // h_total[2 + 2k] (counter) and h_total[3 + 2k] (status words), written by the kernel itself.
-    struct Slot { hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr; uint64_t limit = 0; void* d_out = nullptr; uint32_t R = 0;
+    struct Slot { m2s_host::EventSet<1> done; m2s_host::EventSet<2> t;   // completion (flags: m2s_create); start / end of the kernel, profiling on
+                  uint64_t limit = 0; void* d_out = nullptr; uint32_t R = 0;
                   bool sync_result = false; uint64_t sync_total = 0; bool prof = false; float ms[M2S_K_N] = {};
-                  int own_lane = -1; uint32_t gen = 0;   // context-owned buffer (0 / 1) and its generation at submission; -1: caller's buffer
+                  int own_lane = -1; uint32_t gen = 0;   // the lane whose record buffer it writes and that buffer's generation at submission; -1: caller's buffer
                   bool wrote_bands = false; uint32_t bands_unit = 0; uint32_t ri_gen = 0;   // the launch leaves band bases behind, for the RInfo entry of that table generation
                   hipStream_t st = nullptr; bool shared_work = false; };   // stream it ran on; did it use the context's shared work buffers (chain, deferred list)?
     Slot slot[M2S_MAX_IN_FLIGHT];
     uint32_t slot_head = 0, slot_count = 0; // oldest in-flight slot, number in flight
-    hipStream_t last_submit_stream = nullptr;   // stream of the newest in-flight submission (work buffers are shared: see submit)
-    uint32_t buf_R[2] = { 0, 0 };           // context-owned record buffers (lane a / b): R of the newest conversion enqueued into it ...
-    uint32_t buf_gen[2] = { 0, 0 };         // ... and a generation that advances whenever that R changes
     bool records_stale = false;             // the conversion last waited for has been overwritten by a later submission
 
     // output
-    void* d_records = nullptr;
-    uint64_t records_cap = 0;  // records
     const void* last_records = nullptr;
     int64_t cap_policy = -1;
     uint64_t last_total = 0, last_stored = 0;
@@ -186,10 +170,10 @@ struct m2s_ctx {
     m2s_host::PinnedBuf<m2s_gaussian> h_export[2];      // pinned chunk buffers of m2s_export_ply
     // upload staging: two pinned host chunks (filled by a few host threads while the previous chunk is on the bus) and
     // two device chunks for the AoS -> SoA repack; allocated at the first upload, kept
-    void* h_stage[2] = { nullptr, nullptr };
-    void* d_stage[2] = { nullptr, nullptr };
-    hipEvent_t stage_ev[2] = { nullptr, nullptr };
-    void* scene_arena = nullptr;             // one allocation for mesh table, textures, combo textures and work buffers
+    m2s_host::PinnedBuf<char> h_stage[2];
+    m2s_host::DevBuf<char> d_stage[2];
+    m2s_host::EventSet<2> stage_ev;          // (no timing)
+    m2s_host::DevBuf<char> scene_arena;      // one allocation for mesh table, textures, combo textures and work buffers; released with the scene
     float last_upload_ms[5] = { 0, 0, 0, 0, 0 }; // [0] total, [1] geometry, [2] textures + mips + combo, [3] allocations, [4] warm_scene
     m2s_host::DevBuf<uint8_t> d_rows;        // m2s_export_ply: .ply rows encoded on the device (formats 1 and 2); capacity in bytes
     m2s_host::DevBuf<void> d_loaded;         // m2s_upload_records (a loaded .ply)
@@ -296,7 +280,7 @@ struct m2s_ctx {
 
     // measurement
     bool profiling = false;
-    hipEvent_t ev[8] = {};
+    m2s_host::EventSet<8> ev;
     float last_ms[M2S_K_N] = {};
 };
 
@@ -344,7 +328,21 @@ hipError_t wait_stream(hipStream_t st);
 hipError_t wait_event(hipEvent_t ev);
 void free_scene(m2s_ctx* c);
 m2s_ctx::RInfo& rinfo_for(m2s_ctx* c, uint32_t R);
-void drain_in_flight(m2s_ctx* c);          // every conversion still in flight has finished when this returns
+// The in-flight slots, oldest first; and the newest one that pred holds for (nullptr: none).
+template <class F>
+inline void each_in_flight(m2s_ctx* c, F f) {
+    for (uint32_t q = 0; q < c->slot_count; ++q) f(c->slot[(c->slot_head + q) % M2S_MAX_IN_FLIGHT]);
+}
+template <class P>
+inline m2s_ctx::Slot* newest_in_flight(m2s_ctx* c, P pred) {
+    for (uint32_t q = c->slot_count; q-- > 0;) {
+        m2s_ctx::Slot& sl = c->slot[(c->slot_head + q) % M2S_MAX_IN_FLIGHT];
+        if (pred(sl)) return &sl;
+    }
+    return nullptr;
+}
+// every conversion still in flight (lane >= 0: into that lane's record buffer) has finished when this returns
+void drain_in_flight(m2s_ctx* c, int lane = -1);
 hipError_t next_epoch(m2s_ctx* c, uint32_t* out);
 m2s_status ensure_records(m2s_ctx* c, uint64_t want);
 // m2s_upload.cpp
@@ -372,10 +370,9 @@ m2s::BatchTable batches_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri);
 uint64_t resolve_cap(const m2s_ctx* c, uint32_t R);
 m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted = false);   // called by m2s_upload_scene once the scene is resident
 m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R);                  // ... its exact count, enqueued earlier (in front of the texture copies)
-m2s_status enqueue_multipass(m2s_ctx* c, uint32_t R, float4* d_out, uint64_t limit, bool prof,
-                             unsigned long long* h_res, hipStream_t st, bool second_lane = false);
-m2s_status ensure_second_lane(m2s_ctx* c);                       // stream, chain and record buffer of the second lane
-m2s_status ensure_second_lane_multipass(m2s_ctx* c, uint32_t n_start);   // ... and its multi-pass work buffers
+m2s_status enqueue_multipass(m2s_ctx* c, int lane, uint32_t R, float4* d_out, uint64_t limit, bool prof, unsigned long long* h_res, hipStream_t st);
+// what `lane` needs before a conversion is enqueued on it; multipass: its multi-pass work set for n_start slices included
+m2s_status ensure_lane(m2s_ctx* c, int lane, bool multipass, uint32_t n_start);
 m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hipStream_t st, uint64_t* out_total,
                     bool from_submit = false);
 }  // namespace m2s_host

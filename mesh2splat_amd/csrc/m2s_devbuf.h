@@ -1,6 +1,7 @@
-// m2s_devbuf.h — owners of what the viewer passes keep in the context between calls: grow-only device buffers, pinned host blocks, lazily
-// created events, and the work set of a binned rasteriser.  Each releases in its destructor (the context is deleted after its streams
-// have been synchronised), so a member of m2s_ctx cannot be forgotten in m2s_destroy and a capacity cannot outlive its pointer.
+// m2s_devbuf.h — owners of what the context keeps between calls: grow-only device buffers, pinned host blocks, events, streams, the
+// work set of a binned rasteriser (viewer passes) and what a lane of conversions works in.  Each releases in its destructor (the context
+// is deleted after its streams have been synchronised), so a member of m2s_ctx cannot be forgotten in m2s_destroy, a failed m2s_create
+// leaks nothing and a capacity cannot outlive its pointer.
 // Self-contained on purpose (the runtime's API header, the standard library, m2s.h): a plain host compiler builds tests/devbuf against it.
 #pragma once
 #include "../../include/m2s.h"
@@ -85,7 +86,7 @@ private:
     T* p_ = nullptr;
 };
 
-// N timing events, created at their first use.
+// N events of one kind (timing events, or with the flags of hipEventCreateWithFlags), created by the first ensure().
 template <int N>
 class EventSet {
 public:
@@ -99,9 +100,33 @@ public:
             if (!e) if (m2s_status s = hip_status(err, "hipEventCreate", hipEventCreate(&e))) return s;
         return M2S_OK;
     }
+    m2s_status ensure(std::string& err, unsigned flags) {
+        for (hipEvent_t& e : ev_)
+            if (!e) if (m2s_status s = hip_status(err, "hipEventCreate", hipEventCreateWithFlags(&e, flags))) return s;
+        return M2S_OK;
+    }
 
 private:
     hipEvent_t ev_[N] = {};
+};
+
+// N non-blocking streams, each created by its first ensure().  Declared in front of the buffers and events whose work runs on them, so
+// that it is destroyed after them.
+template <int N>
+class StreamSet {
+public:
+    StreamSet() = default;
+    StreamSet(const StreamSet&) = delete;
+    StreamSet& operator=(const StreamSet&) = delete;
+    ~StreamSet() { for (hipStream_t s : st_) if (s) (void)hipStreamDestroy(s); }
+    hipStream_t operator[](int k) const { return st_[k]; }
+    m2s_status ensure(std::string& err, int k) {
+        if (st_[k]) return M2S_OK;
+        return hip_status(err, "hipStreamCreate", hipStreamCreateWithFlags(&st_[k], hipStreamNonBlocking));
+    }
+
+private:
+    hipStream_t st_[N] = {};
 };
 
 // What a binned rasteriser (splat pass, shadow stage B, mesh depth / visibility) keeps between calls: per item a record, a tile count
@@ -132,6 +157,39 @@ struct BinWork {
     m2s_status reserve_totals(std::string& err, size_t device_words, size_t pinned_bytes) {
         if (m2s_status s = h_totals.ensure(err, pinned_bytes)) return s;
         return d_totals.reserve(err, device_words, sizeof(unsigned long long));
+    }
+};
+
+// What one lane of conversions works in: the stream its kernels run on, the look-back chain they publish to, the record buffer they
+// write, and the work set of the multi-pass pipeline.  Owners, and the pointers as the kernels take them: lane 0's chain and offsets
+// live inside the scene arena (the upload makes one allocation for them and everything else), lane 1 owns its pair.
+struct Lane {
+    hipStream_t stream = nullptr;            // (the context's StreamSet owns it)
+    unsigned long long* chain = nullptr;     // one word per wave
+    uint32_t* off = nullptr;                 // multi-pass: where every triangle's output starts, and the total
+    DevBuf<unsigned long long> chain_own;    // behind chain / off where the lane owns them
+    DevBuf<uint32_t> off_own;
+    DevBuf<void> records;                    // context-owned record buffer; capacity in records
+    uint32_t rec_R = 0;                      // R of the newest conversion enqueued into it ...
+    uint32_t rec_gen = 0;                    // ... and a generation that advances whenever that R changes or the buffer is replaced
+    DevBuf<uint32_t> start;                  // multi-pass: slice starts
+    DevBuf<void> setup;                      // ... per-triangle TriSetup records, then the tall-triangle table; capacity in bytes
+    DevBuf<unsigned long long> total;        // ... the fragment counter
+
+    // The multi-pass work set for n_start slices of a scene whose TriSetup block takes setup_bytes.  *setup_fresh: the block was
+    // allocated by this call (its slot counter has to be zeroed).  The caller lets the readers of an old slice table finish first.
+    m2s_status reserve_work(std::string& err, uint64_t n_start, size_t setup_bytes, bool* setup_fresh) {
+        *setup_fresh = false;
+        if (m2s_status s = total.reserve(err, 1, sizeof(unsigned long long))) return s;
+        if (m2s_status s = start.reserve(err, n_start, sizeof(uint32_t))) return s;
+        return setup.reserve(err, setup_bytes, 1, setup_fresh);
+    }
+    // What is sized by the scene goes with it (released, not kept: the TriSetup block's layout depends on the triangle count); with
+    // `all` (lane 1) the slice starts and the counter as well.
+    void release_scene(bool all) {
+        if (all) { start.release(); total.release(); }
+        chain_own.release(); off_own.release(); setup.release();
+        chain = nullptr; off = nullptr;
     }
 };
 

@@ -1,16 +1,10 @@
 // m2s_pass.cpp — the conversion pass driver (== ConversionPass::execute, src/renderer/renderPasses/ConversionPass.cpp:9-68):
 // pipeline choice, XCD band tables, the single-pass kernels with their fallbacks, the multi-pass pipeline.
 #include "m2s_ctx.h"
-#include "m2s_ply.h"
 
 #include <algorithm>
-#include <array>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <thread>
-#include <tuple>
 #include <vector>
 
 using namespace m2s;
@@ -171,8 +165,6 @@ static void demote(m2s_ctx* c, m2s_ctx::RInfo& ri, uint32_t R, Trouble why) {
     }
 }
 
-static m2s_status ensure_multipass_buffers(m2s_ctx* c, uint64_t limit);
-
 namespace m2s_host {
 // Everything a FIRST conversion of a scene used to find out inside its own call — round 3: an exact count, a host round trip,
 // the record pool's hipMalloc, a launch without bands: 0.45 ms on config 3 against 0.13 ms for a repeated conversion — is
@@ -189,9 +181,9 @@ m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R) {
     if (!sc.n_tri || R == 0 || R > 4096) return M2S_ERR_INVALID;
     hipStream_t st = c->stream;
     launch_count(sc, R, c->d_cnt, c->d_partials, st);
-    launch_scan_partials(c->d_partials, n_count_blocks(sc.n_tri), c->d_total, st);
+    launch_scan_partials(c->d_partials, n_count_blocks(sc.n_tri), c->lane[0].total, st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_total, c->d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_total, c->lane[0].total, 8, hipMemcpyDeviceToHost, st));
     // ... and, on the expectation that AUTO will take the team kernel (units of 256 triangles) — the common case —, the run table and
     // the dispatch order of its first launch at R, which depend on the counts only: if the decision turns out otherwise, warm_scene
     // builds what it needs as before
@@ -205,7 +197,7 @@ m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R) {
             const uint32_t n_units = band_workgroups(c, unit);
             launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, unit, table.shift, table.out, st);
             const int form = lean_eligible(c, R) ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
-            launch_run_order(table.out, n_runs(n_units, table.shift), c->d_total, c->d_run_order, run_order_slots(n_units, table.shift),
+            launch_run_order(table.out, n_runs(n_units, table.shift), c->lane[0].total, c->d_run_order, run_order_slots(n_units, table.shift),
                              first_resident_slots(form, table.shift), st);
             HIPCHK(c, hipGetLastError());
             c->warm_spec_unit = unit; c->warm_spec_shift = table.shift; c->warm_spec_form = form;
@@ -229,15 +221,15 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
     c->warm_total = total;
     c->warm_big = 0;
     if (total >= 11ull * sc.n_tri && total < 13ull * sc.n_tri) {   // (the only case decide() asks for it)
-        HIPCHK(c, hipMemsetAsync(c->d_total, 0, 8, st));
-        launch_big_share(c->d_cnt, sc.n_tri, 96u, c->d_total, st);
+        HIPCHK(c, hipMemsetAsync(c->lane[0].total, 0, 8, st));
+        launch_big_share(c->d_cnt, sc.n_tri, 96u, c->lane[0].total, st);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(&c->h_total[1], c->d_total, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&c->h_total[1], c->lane[0].total, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         c->warm_big = c->h_total[1];
         c->h_total[1] = 0;
         const unsigned long long tot = total;      // (d_total served as the accumulator: the total goes back, launch_run_order below reads it)
-        HIPCHK(c, hipMemcpy(c->d_total, &tot, sizeof tot, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->lane[0].total, &tot, sizeof tot, hipMemcpyHostToDevice));
     }
     // A scene small enough for ONE generation of workgroups (fused_tpw < 64) lasts as long as its slowest workgroup: cut it into
     // batches of equal estimated work instead of equal triangle counts (C2 stand-in: fragments per workgroup vary 1 : 3 over a
@@ -299,7 +291,7 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
             if (!(counted && c->warm_spec_unit == unit && c->warm_spec_shift == table.shift && spec_order)) {
                 launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, unit, table.shift, table.out, st);
                 const uint32_t n_units = band_workgroups(c, unit);
-                launch_run_order(table.out, n_runs(n_units, table.shift), c->d_total, c->d_run_order, run_order_slots(n_units, table.shift),
+                launch_run_order(table.out, n_runs(n_units, table.shift), c->lane[0].total, c->d_run_order, run_order_slots(n_units, table.shift),
                                  first_resident_slots(ri.form, table.shift), st);
                 HIPCHK(c, hipGetLastError());
                 HIPCHK(c, hipStreamSynchronize(st));
@@ -313,8 +305,8 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
     // ConversionPass, the reference's load-then-convert flow) or whose context already owns a record pool: a context that only ever
     // converts into its caller's buffers (m2s_convert_into: the ranks of a multi-GPU job) does not carry 600 MB it never uses.
     const uint64_t want = cap ? cap : std::max<uint64_t>(total, 1);
-    if (c->hint_R != 0 || c->d_records != nullptr) {
-        if (!single || total >= 8ull * sc.n_tri) (void)ensure_multipass_buffers(c, std::min<uint64_t>(cap ? cap : want, 0xFFFFFFFFull));
+    if (c->hint_R != 0 || c->lane[0].records) {
+        if (!single || total >= 8ull * sc.n_tri) (void)ensure_lane(c, 0, true, emit2_slices(std::min<uint64_t>(cap ? cap : want, 0xFFFFFFFFull)));
         // (touching the pool here does not pay: a hipMemset of the part the first conversion writes made that conversion 0.014 ms
         //  SLOWER on config 3, 0.185 vs 0.171 ms — profiles/r04/first_call_probe.jsonl)
         (void)ensure_records(c, want);
@@ -327,102 +319,73 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
 // Multi-pass pipeline: handles every triangle size, output-balanced (m2s_emit2.hip): k_count_scan (count + offsets + per-triangle
 // setup records, one kernel) -> k_emit2 (wave-granular).
 
-static m2s_status ensure_multipass_buffers(m2s_ctx* c, uint64_t limit) {
-    const uint32_t n_start = emit2_slices(limit);
-    if (c->start_cap < n_start) {
-        drain_in_flight(c);
-        if (c->d_start) { (void)hipFree(c->d_start); c->d_start = nullptr; c->start_cap = 0; }
-        const size_t want = std::max<size_t>(std::max<size_t>(n_start, 2 * c->start_cap), 16384);
-        HIPCHK(c, hipMalloc((void**)&c->d_start, want * sizeof(uint32_t)));
-        c->start_cap = want;
-    }
-    if (!c->d_setup) {
-        HIPCHK(c, hipMalloc(&c->d_setup, setup_bytes(c->scene.n_tri)));
-        HIPCHK(c, hipMemsetAsync((char*)c->d_setup + setup_tall_offset(c->scene.n_tri), 0, 16, c->stream));   // the tall-triangle table's slot counter
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return M2S_OK;
-}
-
 namespace m2s_host {
-// The second lane of asynchronous submissions (m2s_set_async_lanes(2)): its stream, its look-back chain and its record buffer,
-// allocated at its first use.  A record buffer that has become too small is replaced after every conversion still writing it has finished.
-m2s_status ensure_second_lane(m2s_ctx* c) {
-    if (!c->stream_b) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-    if (!c->d_chain_b) {
+// What lane L needs before a conversion is enqueued on it.  Lane 0 has its stream, its chain and (ensure_records) its record pool;
+// lane 1 gets them at its first use — the record buffer follows the pool's capacity, and one that has become too small is replaced
+// after every conversion still writing it has finished.  multipass: and the lane's work set for n_start slices.  With a work set per
+// lane, k_count_scan of one conversion runs beside k_emit2 of the previous one.
+m2s_status ensure_lane(m2s_ctx* c, int L, bool multipass, uint32_t n_start) {
+    Lane& ln = c->lane[L];
+    const Lane& l0 = c->lane[0];
+    const uint32_t n_tri = c->scene.n_tri;
+    bool fresh = false;
+    if (L) {
+        M2S_TRY(c->streams.ensure(c->err, L));
+        ln.stream = c->streams[L];
         const size_t words = std::max<size_t>(c->chain_words, 1);
-        HIPCHK(c, hipMalloc((void**)&c->d_chain_b, words * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->d_chain_b, 0, words * sizeof(unsigned long long), c->stream_b));
-    }
-    if (c->records_b_cap < c->records_cap) {
-        for (uint32_t q = 0; q < c->slot_count; ++q) {   // nothing may still be writing the old second buffer
-            auto& o = c->slot[(c->slot_head + q) % M2S_MAX_IN_FLIGHT];
-            if (o.own_lane == 1 && !o.sync_result) (void)hipEventSynchronize(o.done);
+        M2S_TRY(ln.chain_own.reserve(c->err, words, sizeof(unsigned long long), &fresh));
+        ln.chain = ln.chain_own;
+        if (fresh) HIPCHK(c, hipMemsetAsync(ln.chain, 0, words * sizeof(unsigned long long), ln.stream));
+        if (ln.records.cap() < l0.records.cap()) {
+            drain_in_flight(c, L);
+            M2S_TRY(ln.records.reserve(c->err, l0.records.cap(), sizeof(m2s_gaussian)));
+            ++ln.rec_gen;
         }
-        if (c->d_records_b) { (void)hipFree(c->d_records_b); c->d_records_b = nullptr; c->records_b_cap = 0; }
-        HIPCHK(c, hipMalloc(&c->d_records_b, c->records_cap * sizeof(m2s_gaussian)));
-        c->records_b_cap = c->records_cap;
-        ++c->buf_gen[1];
+    }
+    if (!multipass) return M2S_OK;
+    if (L) {   // (lane 0's offsets are the arena's)
+        M2S_TRY(ln.off_own.reserve(c->err, std::max<size_t>(n_tri, 1) + 1, sizeof(uint32_t)));
+        ln.off = ln.off_own;
+    }
+    // A slice table that is too small is replaced by one of at least twice its size, at least lane 0's and at least 16384 slices,
+    // after its readers have finished: lane 0's are whatever is in flight (synchronous conversions use it), lane 1's its own slots
+    uint64_t slices = ln.start.cap();
+    if (slices < n_start) {
+        drain_in_flight(c, L ? L : -1);
+        slices = std::max<uint64_t>(std::max<uint64_t>(n_start, 2 * slices), std::max<uint64_t>(l0.start.cap(), 16384));
+    }
+    M2S_TRY(ln.reserve_work(c->err, slices, setup_bytes(n_tri), &fresh));
+    if (fresh) {   // the tall-triangle table's slot counter
+        HIPCHK(c, hipMemsetAsync((char*)ln.setup.get() + setup_tall_offset(n_tri), 0, 16, ln.stream));
+        HIPCHK(c, hipStreamSynchronize(ln.stream));
     }
     return M2S_OK;
 }
 
-// ... and what a MULTI-PASS conversion on that lane works in: offsets, slice starts, TriSetup records, counter (second generation
-// of the pipeline only).  With these, k_count_scan of one conversion runs beside k_emit2 of the previous one.
-m2s_status ensure_second_lane_multipass(m2s_ctx* c, uint32_t n_start) {
-    const size_t np = std::max<size_t>(c->scene.n_tri, 1);
-    if (!c->d_off_b) HIPCHK(c, hipMalloc((void**)&c->d_off_b, (np + 1) * sizeof(uint32_t)));
-    if (!c->d_setup_b) {
-        HIPCHK(c, hipMalloc(&c->d_setup_b, setup_bytes(c->scene.n_tri)));
-        HIPCHK(c, hipMemsetAsync((char*)c->d_setup_b + setup_tall_offset(c->scene.n_tri), 0, 16, c->stream_b));
-        HIPCHK(c, hipStreamSynchronize(c->stream_b));
-    }
-    if (!c->d_total_b) HIPCHK(c, hipMalloc((void**)&c->d_total_b, sizeof(unsigned long long)));
-    if (c->start_b_cap < n_start) {
-        for (uint32_t q = 0; q < c->slot_count; ++q) {   // (a second-lane conversion in flight reads the old table)
-            auto& o = c->slot[(c->slot_head + q) % M2S_MAX_IN_FLIGHT];
-            if (o.own_lane == 1 && !o.sync_result) (void)hipEventSynchronize(o.done);
-        }
-        if (c->d_start_b) { (void)hipFree(c->d_start_b); c->d_start_b = nullptr; c->start_b_cap = 0; }
-        const size_t want = std::max<size_t>(std::max<size_t>(n_start, c->start_cap), 16384);
-        HIPCHK(c, hipMalloc((void**)&c->d_start_b, want * sizeof(uint32_t)));
-        c->start_b_cap = want;
-    }
-    return M2S_OK;
-}
-
-// enqueues the pipeline's kernels and the read-back of the counter into *h_res (pinned); no synchronisation
-m2s_status enqueue_multipass(m2s_ctx* c, uint32_t R, float4* d_out, uint64_t limit, bool prof,
-                                    unsigned long long* h_res, hipStream_t st, bool second_lane) {
+// enqueues the pipeline's kernels on `st` in lane L's work set, the counter written to *h_res (pinned) by k_count_scan's last
+// workgroup itself; no synchronisation.  prof: lane 0 only (the per-kernel events are the context's)
+m2s_status enqueue_multipass(m2s_ctx* c, int L, uint32_t R, float4* d_out, uint64_t limit, bool prof, unsigned long long* h_res, hipStream_t st) {
     const SceneDev& sc = c->scene;
-    if (second_lane) {   // the second lane's own work buffers (ensure_second_lane_multipass); second generation only
-        uint32_t epoch;
-        HIPCHK(c, next_epoch(c, &epoch));
-        launch_count_scan(sc, R, c->d_off_b, c->d_start_b, emit2_slices(limit), c->d_chain_b, epoch, c->d_total_b, c->d_setup_b,
-                          reinterpret_cast<uint32_t*>(&h_res[1]), &h_res[0], st);
-        launch_emit2(sc, R, c->d_off_b, c->d_start_b, c->d_total_b, limit, c->d_setup_b, d_out, st);
-        HIPCHK(c, hipGetLastError());
-        return M2S_OK;
-    }
+    const Lane& ln = c->lane[L];
+    prof = prof && L == 0;
     uint32_t epoch;
     HIPCHK(c, next_epoch(c, &epoch));
     if (prof) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    launch_count_scan(sc, R, c->d_off, c->d_start, emit2_slices(limit), c->d_chain, epoch, c->d_total, c->d_setup,
-                      reinterpret_cast<uint32_t*>(&h_res[1]), &h_res[0], st);
+    launch_count_scan(sc, R, ln.off, ln.start, emit2_slices(limit), ln.chain, epoch, ln.total, ln.setup, reinterpret_cast<uint32_t*>(&h_res[1]),
+                      &h_res[0], st);
     if (prof) { HIPCHK(c, hipEventRecord(c->ev[1], st)); HIPCHK(c, hipEventRecord(c->ev[3], st)); }
-    launch_emit2(sc, R, c->d_off, c->d_start, c->d_total, limit, c->d_setup, d_out, st);
+    launch_emit2(sc, R, ln.off, ln.start, ln.total, limit, ln.setup, d_out, st);
     if (prof) HIPCHK(c, hipEventRecord(c->ev[4], st));
     HIPCHK(c, hipGetLastError());
-    // (k_count_scan's last workgroup has written the counter to *h_res itself — no copy behind the pipeline)
     return M2S_OK;
 }
-}
+}  // namespace m2s_host
 
 static m2s_status run_multipass(m2s_ctx* c, uint32_t R, float4* d_out, uint64_t limit, hipStream_t st) {
     const bool prof = c->profiling;
-    { const m2s_status s = ensure_multipass_buffers(c, limit); if (s != M2S_OK) return s; }
+    M2S_TRY(ensure_lane(c, 0, true, emit2_slices(limit)));
     c->h_total[0] = 0; c->h_total[1] = 0;
-    { const m2s_status s = enqueue_multipass(c, R, d_out, limit, prof, c->h_total, st); if (s != M2S_OK) return s; }
+    M2S_TRY(enqueue_multipass(c, 0, R, d_out, limit, prof, c->h_total, st));
     HIPCHK(c, wait_stream(st));  // glFinish + counter read-back (ConversionPass.cpp:54-59)
     if (c->h_total[1] >> 32) return fail(c, M2S_ERR_HIP, "multi-pass pipeline: look-back chain timed out");
     if (prof) {
@@ -452,11 +415,11 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
 
     if (sc.n_tri == 0) {
         c->last_total = c->last_stored = 0;
-        if (!d_user && !c->d_records) {   // (an empty shard is a conversion like any other: its consumers see zero records, not "no conversion")
+        if (!d_user && !c->lane[0].records) {   // (an empty shard is a conversion like any other: its consumers see zero records, not "no conversion")
             const m2s_status s = ensure_records(c, 1);
             if (s != M2S_OK) return s;
         }
-        c->last_records = d_user ? d_user : c->d_records;
+        c->last_records = d_user ? d_user : c->lane[0].records.get();
         ++c->records_epoch;
         if (out_total) *out_total = 0;
         return M2S_OK;
@@ -485,8 +448,8 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
         const uint64_t want = cap ? cap : (uint64_t)(predicted * 1.02) + 4096;
         const m2s_status s = ensure_records(c, want);
         if (s != M2S_OK) return s;
-        limit = cap ? cap : c->records_cap;
-        d_out = (float4*)c->d_records;
+        limit = cap ? cap : c->lane[0].records.cap();
+        d_out = (float4*)c->lane[0].records.get();
     }
     if (limit > 0xFFFFFFFFull) limit = 0xFFFFFFFFull;
 
@@ -523,7 +486,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
                 plane = c->d_pos_plane;
             }
             wrote_plane = plane != nullptr;
-            launch_single(c, ri, R, c->d_chain, limit, d_out, c->h_total, epoch, runs, st, plane);
+            launch_single(c, ri, R, c->lane[0].chain, limit, d_out, c->h_total, epoch, runs, st, plane);
             if (prof) HIPCHK(c, hipEventRecord(c->ev[6], st));
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, wait_stream(st));  // glFinish + counter read-back (ConversionPass.cpp:54-59)
@@ -587,8 +550,8 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
         if (!d_user && !cap && c->h_total[0] > limit && limit < 0xFFFFFFFFull && !grown) {
             const m2s_status s = ensure_records(c, c->h_total[0]);
             if (s != M2S_OK) return s;
-            limit = std::min<uint64_t>(c->records_cap, 0xFFFFFFFFull);
-            d_out = (float4*)c->d_records;
+            limit = std::min<uint64_t>(c->lane[0].records.cap(), 0xFFFFFFFFull);
+            d_out = (float4*)c->lane[0].records.get();
             grown = true;
             continue;
         }
@@ -605,7 +568,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     if (wrote_plane && c->last_pipeline == M2S_PIPELINE_SPARSE && !c->h_total[1] && c->d_pos_plane) {
         c->pos_plane_of = d_out; c->pos_plane_n = c->last_stored; c->pos_plane_epoch = c->records_epoch;
     }
-    if (!d_user) { if (c->buf_R[0] != R) { c->buf_R[0] = R; ++c->buf_gen[0]; } }
+    if (!d_user && c->lane[0].rec_R != R) { c->lane[0].rec_R = R; ++c->lane[0].rec_gen; }
     if (out_total) *out_total = total;
     return M2S_OK;
 }

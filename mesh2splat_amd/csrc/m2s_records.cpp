@@ -4,14 +4,7 @@
 #include "m2s_ply.h"
 
 #include <algorithm>
-#include <array>
-#include <chrono>
-#include <cstdio>
-#include <cstring>
 #include <string>
-#include <thread>
-#include <tuple>
-#include <vector>
 
 using namespace m2s;
 using namespace m2s_host;
@@ -150,7 +143,7 @@ m2s_status m2s_reserve_records(m2s_ctx* c, uint64_t n, void** out_ptr) {
     HIPCHK(c, hipSetDevice(c->device));
     const m2s_status s = ensure_records(c, std::max<uint64_t>(n, 1));
     if (s != M2S_OK) return s;
-    *out_ptr = c->d_records;
+    *out_ptr = c->lane[0].records;
     return M2S_OK;
 }
 

@@ -6,9 +6,7 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <thread>
 #include <tuple>
 #include <vector>
@@ -43,8 +41,8 @@ void par_memcpy(void* dst, const void* src, size_t n) {
 namespace m2s_host {
 m2s_status ensure_stage(m2s_ctx* c) {
     for (int k = 0; k < 2; ++k) {
-        if (!c->h_stage[k]) HIPCHK(c, hipHostMalloc(&c->h_stage[k], kStageChunk, hipHostMallocDefault));
-        if (!c->d_stage[k]) HIPCHK(c, hipMalloc(&c->d_stage[k], kStageChunk));
+        M2S_TRY(c->h_stage[k].ensure(c->err, kStageChunk));
+        M2S_TRY(c->d_stage[k].reserve(c->err, kStageChunk, 1));
     }
     return M2S_OK;
 }
@@ -61,7 +59,7 @@ m2s_status staged_h2d(m2s_ctx* c, const char* src, size_t bytes, size_t chunk, c
         const int k = (int)(turn++ & 1u);
         HIPCHK(c, hipEventSynchronize(c->stage_ev[k]));          // the DMA that last read h_stage[k] has finished
         par_memcpy(c->h_stage[k], src + off, n);
-        char* d = dst ? dst + off : (char*)c->d_stage[k];        // d_stage[k]: its previous consumer precedes us on the stream
+        char* d = dst ? dst + off : c->d_stage[k].get();         // d_stage[k]: its previous consumer precedes us on the stream
         HIPCHK(c, hipMemcpyAsync(d, c->h_stage[k], n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->stage_ev[k], c->stream));
         on_chunk(d, off, n);
@@ -119,7 +117,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     size_t offs[11], cur = 0;
     const size_t widths[11] = { 16, 16, 4, 16, 8, 16, 16, 4, 16, 16, 16 };
     for (int k = 0; k < 11; ++k) { offs[k] = cur; cur = align_up(cur + np * widths[k], 256); }
-    HIPCHK(c, hipMalloc(&c->tri_mem, cur));
+    M2S_TRY(c->tri_mem.reserve(c->err, cur, 1));
 
     // textures (deduplicated by host pointer), their mip chains, combo chains: sizes first
     struct TexPlan { const uint8_t* src; TexDesc d; size_t arena_off; };
@@ -195,11 +193,11 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     const size_t o_bands = take(std::max<size_t>((size_t)kBandSlots * run_words, 1) * sizeof(unsigned long long));
     const size_t o_run_order = take(std::max<size_t>(run_shift_for(units) ? run_order_slots(units, run_shift_for(units)) : 0, 1) * sizeof(uint32_t));
     const size_t o_batch = take(std::max<size_t>(batch_table_capacity(n_tri), 1) * sizeof(uint32_t));
-    HIPCHK(c, hipMalloc(&c->scene_arena, arena));
-    { const m2s_status s = ensure_stage(c); if (s != M2S_OK) return s; }
+    M2S_TRY(c->scene_arena.reserve(c->err, arena, 1));
+    M2S_TRY(ensure_stage(c));
     c->last_upload_ms[3] = ms_since(t_alloc);
-    char* A = (char*)c->scene_arena;
-    char* b = (char*)c->tri_mem;
+    char* A = c->scene_arena;
+    char* b = c->tri_mem;
     TriPlanes& tp = c->scene.tri;
     tp.A0 = (const float4*)(b + offs[0]); tp.A1 = (const float4*)(b + offs[1]); tp.A2 = (const float*)(b + offs[2]);
     tp.B0 = (const float4*)(b + offs[3]); tp.B1 = (const float2*)(b + offs[4]);
@@ -260,9 +258,9 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
 
     // ---- work buffers -----------------------------------------------------------------------------
     c->d_cnt = (uint32_t*)(A + o_cnt);
-    c->d_off = (uint32_t*)(A + o_off);
+    c->lane[0].off = (uint32_t*)(A + o_off);
     c->d_partials = (uint32_t*)(A + o_partials);
-    c->d_chain = (unsigned long long*)(A + o_chain);
+    c->lane[0].chain = (unsigned long long*)(A + o_chain);
     c->d_biglist = (BigItem*)(A + o_biglist);
     c->d_bigmeta = (uint32_t*)(A + o_bigmeta);
     c->d_bands = (unsigned long long*)(A + o_bands);
@@ -272,7 +270,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     c->d_batch_first = (uint32_t*)(A + o_batch);
     c->n_batch_tab = 0;
     c->chain_words = chain_words;
-    HIPCHK(c, hipMemsetAsync(c->d_chain, 0, chain_words * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->lane[0].chain, 0, chain_words * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), c->stream));
     const uint32_t warm_R = c->hint_R ? c->hint_R : c->last_R ? c->last_R : 1024u;
     const bool warm = !debug_on("M2S_NO_WARM");
@@ -333,7 +331,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
 m2s_status m2s_prepare(m2s_ctx* c, uint32_t flags) {
     if (!c) return M2S_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    if (flags & M2S_PREPARE_UPLOAD) { const m2s_status s = ensure_stage(c); if (s != M2S_OK) return s; }
+    if (flags & M2S_PREPARE_UPLOAD) M2S_TRY(ensure_stage(c));
     if (flags & M2S_PREPARE_EXPORT)
         for (int k = 0; k < 2; ++k)
             M2S_TRY(c->h_export[k].ensure(c->err, m2s_ply::kChunkRows * sizeof(m2s_gaussian)));

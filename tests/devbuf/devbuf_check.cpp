@@ -9,7 +9,8 @@
 
 namespace {
 std::map<void*, size_t> g_live;          // every live "device" or pinned block and its size
-long g_live_events = 0, g_frees = 0, g_last_error_reads = 0;
+long g_live_events = 0, g_live_streams = 0, g_frees = 0, g_last_error_reads = 0;
+unsigned g_event_flags = 0;              // flags of the event created last
 size_t g_fail_above = SIZE_MAX;          // armed: an allocation of more bytes than this fails (once) ...
 int g_fail_skip = 0;                     // ... after this many such allocations have been let through
 
@@ -39,8 +40,16 @@ hipError_t hipMalloc(void** p, size_t bytes) { return fake_alloc(p, bytes); }
 hipError_t hipFree(void* p) { return fake_free(p); }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int) { return fake_alloc(p, bytes); }
 hipError_t hipHostFree(void* p) { return fake_free(p); }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = static_cast<hipEvent_t>(std::malloc(1)); ++g_live_events; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = static_cast<hipEvent_t>(std::malloc(1)); ++g_live_events; g_event_flags = hipEventDefault; return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
+    *e = static_cast<hipEvent_t>(std::malloc(1));
+    ++g_live_events;
+    g_event_flags = flags;
+    return hipSuccess;
+}
 hipError_t hipEventDestroy(hipEvent_t e) { std::free(e); --g_live_events; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = static_cast<hipStream_t>(std::malloc(1)); ++g_live_streams; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { std::free(s); --g_live_streams; return hipSuccess; }
 hipError_t hipGetLastError(void) { ++g_last_error_reads; return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "error"; }
 }
@@ -149,9 +158,92 @@ static void check_binwork() {
     CHECK(g_live.size() == 7);
 }
 
+// the conversion side: events of a kind, streams, the record pool's fallback, a lane's work set through two scenes
+static void check_conversion_owners() {
+    std::string err;
+    {
+        EventSet<2> stage;
+        EventSet<1> done;
+        CHECK(stage.ensure(err, hipEventDisableTiming) == M2S_OK && g_live_events == 2 && g_event_flags == hipEventDisableTiming);
+        CHECK(done.ensure(err, hipEventDisableTiming | hipEventBlockingSync) == M2S_OK && g_live_events == 3);
+        CHECK(g_event_flags == (hipEventDisableTiming | hipEventBlockingSync));
+        CHECK(stage.ensure(err) == M2S_OK && g_live_events == 3);                       // they exist: none created, whatever the flags
+        EventSet<8> timing;
+        CHECK(timing.ensure(err) == M2S_OK && g_live_events == 11 && g_event_flags == hipEventDefault);
+    }
+    CHECK(g_live_events == 0);                                                          // every event created was destroyed
+    {
+        StreamSet<2> st;
+        CHECK(st[0] == nullptr && st[1] == nullptr);
+        CHECK(st.ensure(err, 0) == M2S_OK && st[0] != nullptr && st[1] == nullptr && g_live_streams == 1);
+        hipStream_t first = st[0];
+        CHECK(st.ensure(err, 0) == M2S_OK && st[0] == first && g_live_streams == 1);
+        CHECK(st.ensure(err, 1) == M2S_OK && st[1] != nullptr && st[1] != first && g_live_streams == 2);
+    }
+    CHECK(g_live_streams == 0);
+
+    // the record pool (ensure_records): the doubled request is tried first and may fail, the one the caller needs is then reported
+    const size_t rec = 96;
+    DevBuf<void> pool;
+    CHECK(pool.reserve(err, 10, rec) == M2S_OK);
+    const long reads = g_last_error_reads;
+    arm(0);                                                                             // the first allocation from here on fails
+    CHECK(!pool.try_reserve(20, rec) && g_last_error_reads == reads + 1 && pool.get() == nullptr && pool.cap() == 0);
+    CHECK(pool.reserve(err, 12, rec) == M2S_OK && pool.cap() == 12 && g_live.at(pool.get()) == 12 * rec && g_live.size() == 1);
+    fill(pool.get(), 12 * rec);
+    arm(0);
+    CHECK(!pool.try_reserve(24, rec));
+    arm(0);
+    err.clear();
+    CHECK(pool.reserve(err, 13, rec) == M2S_ERR_OOM && !err.empty() && pool.get() == nullptr && pool.cap() == 0 && g_live.empty());
+    err.clear();
+
+    // a lane: reserved, grown within a scene, released with the scene, reserved for the next one, destroyed
+    {
+        Lane ln;
+        bool fresh = true;
+        CHECK(ln.reserve_work(err, 16384, 1000, &fresh) == M2S_OK && fresh);            // the TriSetup block is new: its counter gets zeroed
+        CHECK(ln.start.cap() == 16384 && ln.setup.cap() == 1000 && ln.total.cap() == 1 && g_live.size() == 3);
+        fill(ln.start.get(), 16384 * 4); fill(ln.setup.get(), 1000); fill(ln.total.get(), 8);
+        void* block = ln.setup.get();
+        CHECK(ln.reserve_work(err, 100, 1000, &fresh) == M2S_OK && !fresh && ln.setup.get() == block && ln.start.cap() == 16384);
+        long frees = g_frees;
+        CHECK(ln.reserve_work(err, 40000, 1000, &fresh) == M2S_OK && !fresh);           // more slices: the table alone is replaced, once
+        CHECK(g_frees == frees + 1 && ln.start.cap() == 40000 && ln.setup.get() == block && g_live.size() == 3);
+        fill(ln.start.get(), 40000 * 4);
+        CHECK(ln.chain_own.reserve(err, 7, 8, &fresh) == M2S_OK && fresh && ln.off_own.reserve(err, 9, 4) == M2S_OK);
+        ln.chain = ln.chain_own; ln.off = ln.off_own;
+        CHECK(g_live.size() == 5);
+        // lane 0's release: what is sized by the scene goes, its slice starts and its counter stay
+        frees = g_frees;
+        ln.release_scene(false);
+        CHECK(g_frees == frees + 3 && g_live.size() == 2 && ln.chain == nullptr && ln.off == nullptr && !ln.setup && ln.setup.cap() == 0);
+        CHECK(ln.start.cap() == 40000 && ln.total.get() != nullptr);
+        ln.release_scene(false);                                                        // again: nothing left to free
+        CHECK(g_frees == frees + 3);
+        CHECK(ln.reserve_work(err, 100, 500, &fresh) == M2S_OK && fresh && ln.setup.cap() == 500 && g_live.size() == 3);   // the next scene's block
+        fill(ln.setup.get(), 500);
+        // lane 1's release: everything but the record buffer
+        CHECK(ln.records.reserve(err, 5, rec) == M2S_OK);
+        frees = g_frees;
+        ln.release_scene(true);
+        CHECK(g_frees == frees + 3 && g_live.size() == 1 && ln.start.cap() == 0 && !ln.total && ln.records.cap() == 5);
+        CHECK(ln.reserve_work(err, 16384, 700, &fresh) == M2S_OK && fresh && g_live.size() == 4);
+        // a failure in the middle (the slice table) leaves what is live to the lane
+        ln.release_scene(true);
+        arm(0, 1);
+        CHECK(ln.reserve_work(err, 16384, 700, &fresh) == M2S_ERR_OOM && !fresh && ln.total.get() != nullptr && !ln.start && !ln.setup);
+        ln.release_scene(true);
+        // (released, then destroyed: the destructors find nothing but the record buffer)
+    }
+    CHECK(g_live.empty());
+}
+
 int main() {
     check_devbuf();
     CHECK(g_live.empty() && g_live_events == 0);
+    check_conversion_owners();
+    CHECK(g_live.empty() && g_live_events == 0 && g_live_streams == 0);
     check_binwork();
     CHECK(g_live.empty() && g_live_events == 0);
     std::puts("devbuf_check ok");

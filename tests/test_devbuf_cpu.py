@@ -1,4 +1,4 @@
-"""The owning buffer types of mesh2splat_amd/csrc/m2s_devbuf.h (DevBuf, PinnedBuf, EventSet, BinWork) under AddressSanitizer + UBSan:
+"""The owning buffer types of mesh2splat_amd/csrc/m2s_devbuf.h (DevBuf, PinnedBuf, EventSet, StreamSet, BinWork, Lane) under AddressSanitizer + UBSan:
 tests/devbuf/devbuf_check.cpp is built with the HOST compiler against a malloc-backed stand-in for the runtime calls the header makes,
 linked with no HIP runtime, and run as a child process of its own.  What it asserts is listed in that file."""
 import os
