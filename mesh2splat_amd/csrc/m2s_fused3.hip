@@ -50,7 +50,14 @@
 // position inside that wave's entries): the popcount is the slot at that position; a lane's slot is that plus the `first` flags
 // between the wave's first lane in the strip and itself.
 //
-// kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup; both instances: 110 registers, no scratch).
+// kLeanWaves waves per SIMD (M2S_FUSED3_WAVES, default 4: 128 registers, 40 KB of LDS per workgroup).  Registers: this file is compiled with
+// -fno-slp-vectorize (its Makefile rule): plain -O3 packs neighbouring f32 operations into v_pk_*_f32, which have no higher rate than the
+// scalar forms on gfx950 and whose register pairs cost 14 registers and ~100 moves — both instances 110 -> 96 registers, no scratch, the
+// same roundings per component (explicit fma_, contraction off); config 3: step about 2-3 % shorter at the same four workgroups per CU.
+// Five workgroups per CU: 96 registers allow them, and a 32 768 B layout of the indexed instance (no uv: coordinates from the vertex
+// rows; tskip inside the staging area; 3 200 entries) compiled without spills, got 5 from the occupancy query, and was no faster than
+// the four-workgroup build beside it (0.0952 against 0.0948 ms) — but its wave cycles per kernel time were those of four workgroups,
+// so nothing shows that a fifth was ever alive.  Not shipped, and not settled: DESIGN 6.3, profiles/r10.
 // Measurement-only switches (compile time; the A/B tables of DESIGN 6): M2S_FUSED3_UV_GLOBAL — the strips load the B planes as they
 // did before the coordinates moved to LDS; M2S_FUSED3_NT_ATTR — normals / tangents of the plane instance as non-temporal loads;
 // M2S_FUSED3_TRI_PRIO — 0: every wave at one priority throughout, 2: phase classes (below), with M2S_FUSED3_PRIO_FLOOR.
