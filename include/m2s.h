@@ -936,6 +936,12 @@ int m2s_last_pipeline(const m2s_ctx* ctx);
  * than 2^21 rows and at most half as many rows as corners), 0 when they read the per-corner planes.  m2s_last_pipeline says
  * M2S_PIPELINE_LEAN for both; the records are the same bytes.  Either pointer may be NULL. */
 m2s_status m2s_vertex_table(const m2s_ctx* ctx, uint64_t* out_rows, int* out_in_use);
+/* The geometry planes of the last m2s_upload_scene: per resident triangle the Quaternion, the Scale and the box-normalised orthogonal
+ * UVs of the triangle setup (48 bytes), which depend on the positions and the mesh's box but not on the resolution.  Built once per
+ * upload for scenes that can take the LEAN form and have at most 2^22 resident triangles, where memory allows; conversions in the LEAN
+ * form then read them instead of recomputing the setup.  *out_bytes = their size (0: not built), *out_in_use = 1 when LEAN conversions
+ * read them.  The records are the same bytes either way.  Either pointer may be NULL. */
+m2s_status m2s_geo_planes(const m2s_ctx* ctx, uint64_t* out_bytes, int* out_in_use);
 
 /* ---- measurement ------------------------------------------------------------------------------- */
 enum { M2S_K_COUNT = 0, M2S_K_SCAN = 1, M2S_K_OFFSETS = 2, M2S_K_EMIT = 3, M2S_K_FUSED = 4, M2S_K_N = 5 };

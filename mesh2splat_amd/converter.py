@@ -939,6 +939,14 @@ class Converter:
         self._check(self._L.m2s_vertex_table(self._h, C.byref(rows), C.byref(used)))
         return {"rows": int(rows.value), "in_use": bool(used.value)}
 
+    def geo_planes(self) -> dict:
+        """The last upload's geometry planes (Quaternion, Scale and orthogonal UVs per resident triangle, 48 bytes): {'bytes': their size
+        (0: not built), 'in_use': whether conversions in the lean form read them (the kGeo instances of k_fused3) instead of computing
+        the triangle setup from the positions}."""
+        nbytes, used = C.c_uint64(0), C.c_int(0)
+        self._check(self._L.m2s_geo_planes(self._h, C.byref(nbytes), C.byref(used)))
+        return {"bytes": int(nbytes.value), "in_use": bool(used.value)}
+
     # -- measurement --------------------------------------------------------------------------------
     def set_profiling(self, on: bool):
         self._check(self._L.m2s_set_profiling(self._h, 1 if on else 0))

@@ -30,6 +30,7 @@ void free_scene(m2s_ctx* c) {
     c->lean_ok = false;
     c->d_vt_rows.release(); c->d_vt_ids.release();
     c->vt_rows = 0; c->vt_use = false;
+    c->geo_stride = 0; c->geo_use = false;   // (d_geo itself is grow-only: the next upload keeps, regrows or releases it)
     c->scene = SceneDev{};
     c->has_scene = false;
 }
@@ -202,6 +203,13 @@ m2s_status m2s_vertex_table(const m2s_ctx* c, uint64_t* out_rows, int* out_in_us
     if (!c) return M2S_ERR_INVALID;
     if (out_rows) *out_rows = c->vt_rows;
     if (out_in_use) *out_in_use = c->vt_use ? 1 : 0;
+    return M2S_OK;
+}
+
+m2s_status m2s_geo_planes(const m2s_ctx* c, uint64_t* out_bytes, int* out_in_use) {
+    if (!c) return M2S_ERR_INVALID;
+    if (out_bytes) *out_bytes = c->geo_use ? (uint64_t)c->scene.n_tri * 3u * sizeof(float4) : 0u;
+    if (out_in_use) *out_in_use = c->geo_use ? 1 : 0;
     return M2S_OK;
 }
 

@@ -67,6 +67,11 @@ struct m2s_ctx {
     m2s_host::DevBuf<m2s::VtIds> d_vt_ids;  // per resident triangle
     uint32_t vt_rows = 0;                   // distinct vertices of the last upload (0: not counted — the scene was out of the table's range)
     bool vt_use = false;
+    // the resident triangles' geometry planes (m2s_geoplanes.hip): Quaternion, Scale and the orthogonal UVs, built once per upload behind
+    // the repack; conversions in the lean form read them (the kGeo instances of k_fused3) while geo_use holds, every other kernel computes
+    m2s_host::DevBuf<float4> d_geo;         // G0 | G1 | G2, geo_stride float4 apart; capacity in float4
+    size_t geo_stride = 0;
+    bool geo_use = false;
 
     // work buffers (sized by the scene)
     uint32_t* d_cnt = nullptr;

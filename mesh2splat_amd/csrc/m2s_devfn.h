@@ -752,13 +752,15 @@ __device__ __forceinline__ float lod_from_grad(float fw, float fh, float dudx, f
 
 // Everything of the per-triangle fragment constants that does not depend on how the edge functions are stored: Scale, Quaternion,
 // the levels of detail.  Needs ts.inva; a1 .. b2 = the coefficients of edges 1 and 2.
-template <class MP, class TS>   // MP: const MeshParams* in the generic or the constant address space (kConstMesh); TS: TriShade / TriShadeS
+// kFlat = false: Scale and Quaternion are the caller's (k_fused3 with geometry planes takes them from the upload's geo_flat: m2s_geoplanes.hip);
+// p and g are not read.
+template <bool kFlat = true, class MP, class TS>   // MP: const MeshParams* in the generic or the constant address space (kConstMesh); TS: TriShade / TriShadeS
 __device__ __forceinline__ void tri_shade_rest(const float p[9], const Geo& g, int a1, int b1, int a2, int b2, MP mp,
                                                float4 b0, float2 b1uv, TS& ts) {
     ts.mesh = 0;
     const float A1 = (float)a1 * 256.0f * ts.inva, B1 = (float)b1 * 256.0f * ts.inva;
     const float A2 = (float)a2 * 256.0f * ts.inva, B2 = (float)b2 * 256.0f * ts.inva;
-    geo_flat(p, g, ts.sx, ts.sy, ts.rot);
+    if constexpr (kFlat) geo_flat(p, g, ts.sx, ts.sy, ts.rot);
     ts.lod0 = ts.lod1 = ts.lod2 = 0.0f;
     const auto ta = &mp->tex[0];
     const auto tn = &mp->tex[1];
@@ -821,7 +823,7 @@ __device__ __forceinline__ void tri_shade_setup(const float p[9], const Geo& g, 
 
 // TriShadeS of one small triangle, straight from its 32-bit raster setup (raster_small; the same values tri_shade_setup computes
 // in 64 bits and the sparse kernel narrows: m2s_devfn.h, TriShadeS)
-template <class MP>
+template <bool kFlat = true, class MP>   // kFlat: as tri_shade_rest
 __device__ __forceinline__ void tri_shade_small(const float p[9], const Geo& g, const RasterHead& h, const RasterSmall& rs, MP mp, float4 b0, float2 b1,
                                                 uint32_t m, TriShadeS& c) {
     {
@@ -831,7 +833,7 @@ __device__ __forceinline__ void tri_shade_small(const float p[9], const Geo& g, 
     c.a1 = (short)rs.a[1]; c.b1 = (short)rs.b[1]; c.a2 = (short)rs.a[2]; c.b2 = (short)rs.b[2];
     c.e1 = rs.e[1]; c.e2 = rs.e[2];
     c.org = ((uint32_t)h.y0 << 12) | (uint32_t)h.x0;
-    tri_shade_rest(p, g, rs.a[1], rs.b[1], rs.a[2], rs.b[2], mp, b0, b1, c);
+    tri_shade_rest<kFlat>(p, g, rs.a[1], rs.b[1], rs.a[2], rs.b[2], mp, b0, b1, c);
     c.mesh |= m;
 }
 

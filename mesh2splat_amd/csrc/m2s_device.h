@@ -189,9 +189,17 @@ void launch_fused2(const SceneDev& sc, uint32_t R, unsigned long long* chain, ui
 // lean form of the team kernel (m2s_fused3.hip): same units, same run tables, same output; only for scenes whose meshes all sample
 // a combo texture or no map at all (m2s_ctx::lean_ok); triangles larger than an 8 x 8 pixel box are deferred to k_emit_big.
 // vt (or nullptr): the scene's vertex table (m2s_vtable.h) — the indexed instance runs, whose strips gather from it instead of the planes
+// gp (or nullptr): the scene's geometry planes — the kGeo instance runs, whose triangle phase reads them instead of the positions
+struct GeoPlanes {               // per resident triangle, built once per upload (m2s_geoplanes.hip)
+    const float4* G0;            // Quaternion (w, x, y, z)
+    const float4* G1;            // Scale.x, Scale.y, ou[0], ov[0]   (Geo::ou / ov: geo_setup's box-normalised orthogonal UVs)
+    const float4* G2;            // ou[1], ov[1], ou[2], ov[2]
+};
+void launch_geo_planes(const SceneDev& sc, float4* g0, float4* g1, float4* g2, hipStream_t st);   // n_tri entries each; needs mesh_of8
 void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,
                    unsigned long long* total, uint32_t* status, uint32_t epoch, BigItem* biglist, uint32_t* bigmeta,
-                   const RunInfo& runs, const BatchTable& batches, hipStream_t st, const VtxTable* vt = nullptr);
+                   const RunInfo& runs, const BatchTable& batches, hipStream_t st, const VtxTable* vt = nullptr,
+                   const GeoPlanes* gp = nullptr);
 // sparse form of the single-pass kernel (m2s_sparse.hip); `runs` as for launch_fused2, in ITS units (512 triangles)
 // plane (or nullptr): the positions of the records as a compact plane (16 B each, record order): what a depth sort builds its keys from
 void launch_sparse(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,

@@ -22,10 +22,11 @@
 //     the triangle phase has the B planes in registers anyway, and a strip computes its texel addresses without a global round trip
 //     in front of them (and without fetching the two planes a second time).
 //
-// Two instances (template <bool kIndexed>; launch_fused3 picks by whether the upload left a vertex table, m2s_ctx::vt_use):
-//   * k_fused3<false>, the plane instance: a strip gathers its triangle's positions, normals and tangents from the per-corner SoA planes
+// Four instances (template <bool kIndexed, bool kGeo>; launch_fused3 picks by what the upload left: a vertex table, m2s_ctx::vt_use, and
+// geometry planes, m2s_ctx::geo_use; one of them runs per scene).  kIndexed — where the STRIPS gather a triangle's attributes:
+//   * k_fused3<false, *>, the plane instance: a strip gathers its triangle's positions, normals and tangents from the per-corner SoA planes
 //     (A, C, D: 120 B per triangle, every vertex once per corner that uses it);
-//   * k_fused3<true>, the indexed instance: the upload deduplicated the shard's corners into a table of distinct vertices (m2s_vdedup.hip;
+//   * k_fused3<true, *>, the indexed instance: the upload deduplicated the shard's corners into a table of distinct vertices (m2s_vdedup.hip;
 //     rows of three float4: (p.xyz, u), (n.xyz, v), (t.xyzw); config 3: 501 128 rows for 3 006 756 corners) and left three row ids per
 //     triangle, packed in 8 bytes (VtIds, m2s_vtable.h).  The triangle phase reads them with the B planes (one coalesced 8-byte load)
 //     and stores them in the 8 bytes of the fragment constants that otherwise hold the combo texture's two level offsets (TriShadeSI:
@@ -33,8 +34,19 @@
 //     grow.  A strip then takes nine row loads through the ids it has in LDS — no dependent global read in front of them — in place of
 //     the nine plane loads: the same operand bits from another address, the interpolation text unchanged, the records byte for byte
 //     those of the plane instance.  Neighbouring triangles read the same rows, so a workgroup's gathers touch ~48 B per triangle
-//     instead of 120.  The triangle phase itself still reads positions and coordinates from planes A / B, and
-//     k_emit_big (deferred triangles) and every other kernel read planes only.
+//     instead of 120.  k_emit_big (deferred triangles) and every other kernel read planes only.
+// kGeo — what the TRIANGLE PHASE starts from:
+//   * k_fused3<*, false>: the positions (planes A, 36 B per triangle) and the mesh's box: geo_setup (three roots, a reciprocal, two
+//     normalisations, six quotients, the axis selection) in front of the raster setup, geo_flat (yAxis, quat_cast, the 2 x 2 inverse, the
+//     Jacobian, two roots) for every covered triangle;
+//   * k_fused3<*, true>: the scene's geometry planes (GeoPlanes, m2s_device.h; built once per upload by k_geo_planes, m2s_geoplanes.hip, with
+//     the same device functions): three coalesced 16-byte loads per lane — Quaternion; Scale.xy, ou[0], ov[0]; ou[1], ov[1], ou[2], ov[2] —
+//     in place of the A planes.  Geo::ou / ov are all raster_head and raster_setup read, Scale and Quaternion go unchanged into the
+//     triangle's fragment constants; nothing of this depends on R.  The phase has no positions at all: neither geo_setup nor geo_flat
+//     runs (static vector instructions of the indexed instance 2802 -> 1942), 48 B in for 36 B out per triangle.  The coordinates (planes
+//     B), the ids, the raster setup, coverage, the levels of detail and everything behind the phase are the other instance's text; the
+//     records are the same bytes (tests/test_gpu_fused3_geoplanes.py).  The kGeo = false instances are what runs when a scene has no
+//     planes (more than 2^22 resident triangles, or no memory for them).
 //
 // LDS per workgroup (F3Lds, 40 824 of the 40 960 bytes that four workgroups per CU leave each):
 //     tri      16 384   TriShadeS / TriShadeSI, [wave][lane]
@@ -62,7 +74,7 @@
 // did before the coordinates moved to LDS; M2S_FUSED3_NT_ATTR — normals / tangents of the plane instance as non-temporal loads;
 // M2S_FUSED3_TRI_PRIO — 0: every wave at one priority throughout, 2: phase classes (below), with M2S_FUSED3_PRIO_FLOOR.
 //
-// Priority.  A wave runs its triangle phase — ~950 VALU instructions and no wait after its loads — at priority 1 and drops to 0 when
+// Priority.  A wave runs its triangle phase — no wait after its loads — at priority 1 and drops to 0 when
 // its counts are published: the waits and the strips run at 0.  From the second generation of workgroups on, a wave in the triangle phase
 // shares its SIMD with three waves in strips, which issue a few instructions between long waits; ahead of them it leaves the phase ~1 us
 // sooner (mean 6.8 -> 5.7 us on config 3) and its workgroup's texel requests start that much earlier.  Priority only orders issue — nothing a
@@ -195,7 +207,8 @@ constexpr int kTlXccId = 20 | (3 << 11);     // HW_REG_XCC_ID, bits 3:0
 #endif
 
 struct VtNone { };   // the plane instance takes no table
-template <bool kIndexed>
+struct GeoNone { };  // the instances that compute their geometry take no geometry planes
+template <bool kIndexed, bool kGeo>
 __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDev sc, uint32_t R, unsigned long long* __restrict__ chain,
                                                       unsigned long long limit, float4* __restrict__ out,
                                                       unsigned long long* __restrict__ total_out,
@@ -203,7 +216,8 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
                                                       BigItem* __restrict__ biglist, uint32_t* __restrict__ bigmeta,
                                                       uint32_t tpw /* triangles per wave: 64 .. 8 (fused_tpw) */,
                                                       RunInfo runs, BatchTable bt,
-                                                      std::conditional_t<kIndexed, VtxTable, VtNone> vt) {
+                                                      std::conditional_t<kIndexed, VtxTable, VtNone> vt,
+                                                      std::conditional_t<kGeo, GeoPlanes, GeoNone> gp) {
     using TS = std::conditional_t<kIndexed, TriShadeSI, TriShadeS>;   // what the strips read from S.tri
     __shared__ F3Lds S;
     F3Ctl& C = S.ctl;
@@ -262,8 +276,10 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
     unsigned long long mask = 0;
     uint32_t cnt = 0;
     {
-        float p[9];
+        [[maybe_unused]] float p[9];   // (kGeo: no positions in the phase — g.ou / g.ov, Scale and Quaternion come from the geometry planes)
         Geo g;
+        [[maybe_unused]] float4 grot = make_float4(0, 0, 0, 0);
+        [[maybe_unused]] float gsx = 0, gsy = 0;
         RasterHead h;
         h.x0 = h.y0 = 0; h.x1 = h.y1 = -1; h.ext = 0;
         bool box = false;
@@ -278,11 +294,18 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
             m0 = mesh_of_range(sc, t0, lastT, uniform_mesh);
             m = m0;
             if (valid) {
-                load_positions(sc.tri, t, p);
+                [[maybe_unused]] float4 q0, q1, q2;
+                if constexpr (kGeo) { q0 = ld_plane(gp.G0, t); q1 = ld_plane(gp.G1, t); q2 = ld_plane(gp.G2, t); }
+                else load_positions(sc.tri, t, p);
                 uvb0 = sc.tri.B0[t];
                 uvb1 = sc.tri.B1[t];
                 if constexpr (kIndexed) vid = ld_plane(reinterpret_cast<const uint2*>(vt.ids), t);
-                if (uniform_mesh) geo_setup_mp(p, kConstMesh(sc.meshes + m0), g);
+                if constexpr (kGeo) {
+                    grot = q0; gsx = q1.x; gsy = q1.y;
+                    g.ou[0] = q1.z; g.ov[0] = q1.w; g.ou[1] = q2.x; g.ov[1] = q2.y; g.ou[2] = q2.z; g.ov[2] = q2.w;
+                    if (!uniform_mesh) m = find_mesh(sc, sc.tri_first + t);
+                }
+                else if (uniform_mesh) geo_setup_mp(p, kConstMesh(sc.meshes + m0), g);
                 else { m = find_mesh(sc, sc.tri_first + t); geo_setup_mp(p, sc.meshes + m, g); }
                 box = raster_head(g, R, h);
             }
@@ -303,8 +326,9 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
         // fragment constants of the triangles this workgroup shades itself: in place before any wait (see the file header)
         if (cnt != 0 && kind == kSmall) {
             TriShadeS c;
-            if (uniform_mesh) tri_shade_small(p, g, h, rs, kConstMesh(sc.meshes + m0), uvb0, uvb1, m, c);
-            else tri_shade_small(p, g, h, rs, sc.meshes + m, uvb0, uvb1, m, c);
+            if (uniform_mesh) tri_shade_small<!kGeo>(p, g, h, rs, kConstMesh(sc.meshes + m0), uvb0, uvb1, m, c);
+            else tri_shade_small<!kGeo>(p, g, h, rs, sc.meshes + m, uvb0, uvb1, m, c);
+            if constexpr (kGeo) { c.sx = gsx; c.sy = gsy; c.rot = grot; }   // the upload's geo_flat (m2s_geoplanes.hip)
             const float4* src = reinterpret_cast<const float4*>(&c);
 #pragma unroll
             for (int k = 0; k < 3; ++k) S.tri[wave][lane * 4 + k] = src[k];
@@ -599,7 +623,7 @@ __global__ void __launch_bounds__(kL3Threads, M2S_FUSED3_WAVES) k_fused3(SceneDe
 
 void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, uint64_t limit, float4* out,
                    unsigned long long* total, uint32_t* status, uint32_t epoch, BigItem* biglist, uint32_t* bigmeta,
-                   const RunInfo& runs, const BatchTable& bt, hipStream_t st, const VtxTable* vt) {
+                   const RunInfo& runs, const BatchTable& bt, hipStream_t st, const VtxTable* vt, const GeoPlanes* gp) {
     const uint32_t tpw = fused_tpw(sc.n_tri);
     const uint32_t n_batches = bt.first ? bt.n : n_fused_waves(sc.n_tri);
     if (!n_batches) return;
@@ -609,12 +633,15 @@ void launch_fused3(const SceneDev& sc, uint32_t R, unsigned long long* chain, ui
     if (r.base) r.out = nullptr;
     if (r.base) nb = ((nb + (8u << r.shift) - 1u) / (8u << r.shift)) * (8u << r.shift);   // whole groups of eight runs; surplus workgroups exit at once
     else nb = (nb + 7u) & ~7u;
-    if (vt && vt->rows && vt->ids)
-        hipLaunchKernelGGL(k_fused3<true>, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
-                           epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt, *vt);
-    else
-        hipLaunchKernelGGL(k_fused3<false>, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
-                           epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt, VtNone{});
+    const bool indexed = vt && vt->rows && vt->ids, geo = gp && gp->G0 && gp->G1 && gp->G2;
+    auto go = [&](auto kernel, auto table, auto planes) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(kL3Threads), 0, st, sc, R, chain, (unsigned long long)limit, out, total, status,
+                           epoch & 0xFFFFu, biglist, bigmeta, tpw, r, bt, table, planes);
+    };
+    if (indexed && geo) go(k_fused3<true, true>, *vt, *gp);
+    else if (indexed) go(k_fused3<true, false>, *vt, GeoNone{});
+    else if (geo) go(k_fused3<false, true>, VtNone{}, *gp);
+    else go(k_fused3<false, false>, VtNone{}, GeoNone{});
 }
 
 #ifdef M2S_TIMELINE
@@ -629,8 +656,8 @@ extern "C" int m2s_debug_timeline_f3_clear() {
 }
 namespace m2s {
 #endif
-// (both instances are compiled for the same registers and LDS: one answer)
-uint32_t fused3_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused3<false>), kL3Threads); }
-hipError_t preload_fused3() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused3<false>)); }
+// (all instances are compiled for the same registers and LDS: one answer)
+uint32_t fused3_resident_workgroups() { return resident_workgroups(reinterpret_cast<const void*>(&k_fused3<false, false>), kL3Threads); }
+hipError_t preload_fused3() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_fused3<false, false>)); }
 
 }  // namespace m2s

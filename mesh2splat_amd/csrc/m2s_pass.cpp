@@ -71,8 +71,9 @@ void launch_single(const m2s_ctx* c, const m2s_ctx::RInfo& ri, uint32_t R, unsig
         launch_sparse(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, st, plane);
     else if (ri.form == M2S_PIPELINE_LEAN) {
         const VtxTable vt{ c->d_vt_rows.get(), c->d_vt_ids.get() };
+        const GeoPlanes gp{ c->d_geo.get(), c->d_geo.get() + c->geo_stride, c->d_geo.get() + 2 * c->geo_stride };
         launch_fused3(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st,
-                      c->vt_use ? &vt : nullptr);
+                      c->vt_use ? &vt : nullptr, c->geo_use ? &gp : nullptr);
     }
     else
         launch_fused2(c->scene, R, chain, limit, d_out, &res[0], status, epoch, c->d_biglist, c->d_bigmeta, runs, batches_for(c, ri), st);

@@ -285,6 +285,17 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
         vt_begun = vt_dedup_begin(tp, n_tri, vt_work, c->stream) == hipSuccess;
         if (!vt_begun) (void)hipGetLastError();
     }
+    // the geometry planes (m2s_geoplanes.hip): what k_fused3's triangle phase would compute from the positions and the mesh's box at
+    // every conversion, whatever the R.  Enqueued behind the repack and the mesh table; no room for them costs the scene its planes only.
+    if (vt_size_ok(c->lean_ok, n_tri) && !debug_on("M2S_NO_GEOPLANES")) {
+        const size_t stride = align_up((size_t)n_tri * sizeof(float4), 256) / sizeof(float4);
+        if (c->d_geo.try_reserve(3 * stride, sizeof(float4))) {
+            launch_geo_planes(c->scene, c->d_geo.get(), c->d_geo.get() + stride, c->d_geo.get() + 2 * stride, c->stream);
+            c->geo_stride = stride;
+            c->geo_use = true;
+        }
+    }
+    if (!c->geo_use) c->d_geo.release();
 
     // ---- textures: level 0 through the same staging, levels 1..4 on the device (glUtils.cpp:292-313) -----------------
     for (TexPlan& p : tex_plan) {

@@ -5,7 +5,8 @@ tracing beside it) or `rocprofv3 --kernel-trace --stats` when only this kernel i
     python tools/fused3_c3_probe.py [--launches 20] [--check]
 
 The library is the one M2S_LIB_PATH names (A/B and measurement builds), else the package's.  Prints one JSON line: the counter, the
-pipeline that ran, whether the strips gathered from the upload's vertex table (the indexed instance) and — with --check — a CRC of the
+pipeline that ran, whether the strips gathered from the upload's vertex table (the indexed instance), whether the triangle phase read the upload's
+geometry planes (the kGeo instance) and — with --check — a CRC of the
 records (compare it with the shipping build's to see that a measurement build writes the same bytes).
 """
 import argparse
@@ -33,7 +34,7 @@ def main():
         total = 0
         for _ in range(a.launches):
             total = c.convert(1024)
-        out = {"total": total, "pipeline": c.last_pipeline, "launches": a.launches, "vertex_table": c.vertex_table()}
+        out = {"total": total, "pipeline": c.last_pipeline, "launches": a.launches, "vertex_table": c.vertex_table(), "geo_planes": c.geo_planes()}
         if a.check:
             out["crc32"] = "%08x" % zlib.crc32(c.download().tobytes())
     print(json.dumps(out))
