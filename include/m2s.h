@@ -465,6 +465,51 @@ m2s_status m2s_prune(m2s_ctx* ctx, const m2s_prune_params* params, uint64_t* out
 m2s_status m2s_last_prune_counts(const m2s_ctx* ctx, uint64_t out[4]);
 float m2s_last_prune_ms(const m2s_ctx* ctx);
 
+/* ---- pruning to a budget (no counterpart in the reference: its cap keeps whatever arrives first, RenderPass.hpp:9) ------------- */
+/* Of the records that pass the thresholds, keeps the max_records with the largest importance.  m2s_set_max_gaussians truncates in
+ * canonical (mesh, triangle, row, column) order — the last meshes go, the first stay at full density —; this chooses which records go.
+ * The pin (tests/budget_ref.py restates it):
+ *  - Candidates.  M2S_IMPORTANCE_VIEWS: the records m2s_prune keeps with the same min_weight / min_pixels — wmax > min_weight compared
+ *    as floats, and npix >= min_pixels —; it needs valid accumulators of the current records exactly as m2s_prune does.
+ *    M2S_IMPORTANCE_AREA: every record; it needs records only (converted, uploaded, adopted or already pruned) and reads neither
+ *    threshold.
+ *  - Key, a uint32 per candidate.  VIEWS: the bits of the fp32 product (float)npix * wmax — the conversion uint32 -> float rounds to
+ *    nearest even, once; the multiply rounds once; wmax lies in [0, 1] and npix < 2^30, so the product is finite and non-negative.
+ *    AREA: a = fminf(fmaxf(color[3], 0), 1), s = fabsf(scale[0]) * fabsf(scale[1]), p = s * a, key = the bits of fmaxf(p, 0.0f) with a
+ *    zero of either sign read as +0 (key = p > 0 ? bits(p) : 0): a NaN anywhere, or inf * 0, gives key 0; +inf is the largest key.  (A
+ *    .ply can hold anything; conversion records are tame.)  Non-negative floats order as their bits do as unsigned integers: from
+ *    here on everything is integer arithmetic, identical from run to run.
+ *  - Selection.  At most max_records candidates: the candidates are kept.  Otherwise let T be the max_records-th largest key among
+ *    the candidates; kept are every candidate with key > T and, of the candidates with key == T, the first
+ *    max_records - #{key > T} in index order.  Exactly max_records survive.  This equals: stable-sort the candidates by key
+ *    descending, take the first max_records, restore index order.  (A radix select over the keys, four rounds of eight bits; the
+ *    96-byte records are not sorted.)
+ *  - Effect, as m2s_prune: a stable compaction into the context-owned pool, order and resolutionTarget kept; a caller's adopted memory
+ *    is not written; a baked SH plane of these records is compacted with the same flags; cached positions, sorted quads, sources and
+ *    the accumulators are invalidated and the records epoch advances.
+ * *out_kept (may be NULL) = survivors.  Synchronous.  M2S_ERR_INVALID: max_records == 0, reserved != 0, an unknown importance, a NaN
+ * min_weight (VIEWS).  M2S_ERR_STATE: VIEWS without accumulators of the current records, no records at all, conversions in flight.
+ * M2S_ERR_CAPACITY: 2^32 records or more. */
+enum { M2S_IMPORTANCE_VIEWS = 0, M2S_IMPORTANCE_AREA = 1 };
+typedef struct m2s_budget_params {
+    uint64_t max_records;   /* >= 1 */
+    float    min_weight;    /* VIEWS: m2s_prune's test; AREA: not read */
+    uint32_t min_pixels;    /* VIEWS: m2s_prune's test; AREA: not read */
+    uint32_t importance;    /* M2S_IMPORTANCE_* */
+    uint32_t reserved;      /* 0 */
+} m2s_budget_params;        /* 24 bytes; offsets 0, 8, 12, 16, 20 */
+m2s_status m2s_prune_budget(m2s_ctx* ctx, const m2s_budget_params* params, uint64_t* out_kept);
+/* The last m2s_prune_budget: [0] records before, [1] candidates, [2] kept, [3] T (0 when nothing had to be selected), [4] kept with
+ * key == T, [5] candidates with key == T. */
+m2s_status m2s_last_budget_counts(const m2s_ctx* ctx, uint64_t out[6]);
+/* Stages (ms) of the last profiled m2s_prune_budget: [0] keys + the four histogram / pick rounds, [1] flags + scans, [2] compaction. */
+m2s_status m2s_last_budget_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* The counterpart of m2s_upload_quad_sources for the accumulators: after m2s_contrib_begin, host arrays of n == m2s_num_stored words
+ * become wmax and npix (either may be NULL: that accumulator stays as it is), so that a caller with an importance measure of its own
+ * — or a test — drives the selection without rendering views.  M2S_ERR_INVALID for another n or a wmax word above 0x3F800000 (not
+ * the bits of a weight in [0, 1]); M2S_ERR_STATE without accumulators of the current records. */
+m2s_status m2s_upload_contrib(m2s_ctx* ctx, const uint32_t* host_wmax, const uint32_t* host_npix, uint64_t n);
+
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */
 typedef struct m2s_light_params {

@@ -882,11 +882,60 @@ class Converter:
     def last_prune_ms(self) -> float:
         return float(self._L.m2s_last_prune_ms(self._h))
 
+    def upload_contrib(self, wmax=None, npix=None):
+        """After contrib_begin(): the two accumulators from host arrays of num_stored words each (m2s_upload_contrib) — wmax as float32
+        weights in [0, 1] or as their uint32 bits, npix as uint32; None leaves that accumulator as it is.  wmax of a floating type is
+        rounded to float32 and its bits are taken; any other array must be of an unsigned integer type that fits 32 bits (TypeError
+        otherwise: a weight must not silently become the word 0)."""
+        def words(a, weights: bool):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if weights and a.dtype.kind == "f":
+                a = np.ascontiguousarray(a, np.float32).view(np.uint32)
+            elif a.dtype.kind != "u" or a.dtype.itemsize > 4:
+                raise TypeError(("wmax takes float weights or uint32 bits" if weights else "npix takes unsigned integers of at most 32 bits") +
+                                f", not {a.dtype}")
+            return np.ascontiguousarray(a, np.uint32).reshape(-1)
+        w, k = words(wmax, True), words(npix, False)
+        for a in (w, k):
+            if a is not None and a.size != self.num_stored:
+                raise ValueError("an accumulator has one word per record")
+        self._check(self._L.m2s_upload_contrib(self._h, w.ctypes.data if w is not None and w.size else None,
+                                               k.ctypes.data if k is not None and k.size else None, self.num_stored))
+
+    def prune_budget(self, max_records: int, importance: str = "views", min_weight: float = 0.0, min_pixels: int = 0) -> dict:
+        """Of the records that pass the thresholds, keep the max_records with the largest importance, ties by index (m2s_prune_budget;
+        the pin is in include/m2s.h).  "views": importance npix * wmax over the accumulated views, the thresholds are prune()'s; "area":
+        |scale x| * |scale y| * alpha of every record, no accumulators needed, the thresholds are not read.  The survivors become the
+        context's records, in order.  -> {"before", "candidates", "kept", "threshold_key", "ties_kept", "ties"}."""
+        from . import prune as _pr
+        pc = _pr.BudgetParamsC(int(max_records), float(min_weight), int(min_pixels), _pr.IMPORTANCE[importance], 0)
+        kept = C.c_uint64()
+        had_plane = bool(self.device_sh)
+        self._check(self._L.m2s_prune_budget(self._h, C.byref(pc), C.byref(kept)))
+        counts = self.last_budget_counts()
+        if had_plane and getattr(self, "_last_bake_n", None) == counts["before"]:
+            self._last_bake_n = counts["kept"]          # (the baked plane of these records was compacted with them)
+        return counts
+
+    def last_budget_counts(self) -> dict:
+        from . import prune as _pr
+        v = (C.c_uint64 * 6)()
+        self._check(self._L.m2s_last_budget_counts(self._h, v))
+        return {name: int(v[k]) for k, name in enumerate(_pr.BUDGET_COUNTS)}
+
+    def last_budget_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_budget_stage_ms(self._h, ms))
+        return {"select": float(ms[0]), "flags_scans": float(ms[1]), "compact": float(ms[2])}
+
     def prune_views(self, cameras, resolution_target: int, size=None, gaussian_std: float = 0.65, count_weight: float = 1.0 / 255.0,
-                    min_weight: float = 1.0 / 255.0, min_pixels: int = 1) -> dict:
+                    min_weight: float = 1.0 / 255.0, min_pixels: int = 1, budget=None) -> dict:
         """prepass_sorted() -> contrib_accumulate() through each of `cameras` (mesh2splat_amd.prune.orbit_cameras), then prune().
         `size`: (W, H) at which every view is taken instead of the camera's own resolution (the cameras' projections are kept, so keep their
-        aspect ratio; default: each camera's resolution).  -> the counts of prune()."""
+        aspect ratio; default: each camera's resolution).  -> the counts of prune().  `budget`: an integer makes the final call
+        prune_budget(budget, "views") with the same thresholds -> its counts."""
         import dataclasses
         from . import splat as _sp
         if size is not None:
@@ -898,6 +947,8 @@ class Converter:
                 pp = dataclasses.replace(pp, renderer_resolution=size)
             if self.prepass_sorted(pp, download=False):
                 self.contrib_accumulate(_sp.SplatParams(tuple(pp.renderer_resolution), 0), count_weight)
+        if budget is not None:
+            return self.prune_budget(int(budget), "views", min_weight, min_pixels)
         return self.prune(min_weight, min_pixels)
 
     @property

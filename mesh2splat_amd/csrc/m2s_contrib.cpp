@@ -10,14 +10,56 @@
 using namespace m2s;
 using namespace m2s_host;
 
-namespace {
+namespace m2s_host {
 
 bool contrib_valid(const m2s_ctx* c) {
     return c->contrib_active && c->last_records && !c->records_stale && c->contrib_of == c->last_records && c->contrib_n == c->last_stored &&
            c->contrib_epoch == c->records_epoch;
 }
 
-}  // namespace
+bool prune_sh_plane(const m2s_ctx* c, uint64_t n) {
+    return c->sh_valid && c->sh_of == c->last_records && c->sh_epoch == c->records_epoch && c->sh_n == n;
+}
+
+m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh) {
+    if (!n) {
+        if (!c->lane[0].records || c->last_records != c->lane[0].records) return ensure_records(c, 1);
+        return M2S_OK;
+    }
+    // The survivors go into the pool.  Records that live there already (or a plane compacted in place) cannot be compacted onto
+    // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
+    const bool in_pool = c->last_records == c->lane[0].records;
+    const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
+    if (stage_bytes) M2S_TRY(c->d_prune_stage.reserve(c->err, stage_bytes, 1));
+    const void* src = c->last_records;
+    if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
+    if (kept) {
+        float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
+        HIPCHK(c, prune_compact((const float4*)src, flags, offsets, (uint32_t)n, 6, dst, c->stream));
+        if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        if (sh) {
+            HIPCHK(c, prune_compact((const float4*)c->d_sh.get(), flags, offsets, (uint32_t)n, 12, c->d_prune_stage, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_sh, c->d_prune_stage, kept * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
+    return M2S_OK;
+}
+
+void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh) {
+    // the survivors are the context's current records now, at the resolutionTarget of the ones they were taken from
+    c->last_records = c->lane[0].records;
+    ++c->records_epoch;
+    c->last_total = c->last_stored = kept;
+    c->last_R = R;
+    c->records_stale = false;
+    c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
+    c->sq_src = nullptr;
+    c->contrib_active = false;
+    if (sh) { c->sh_n = kept; c->sh_of = c->last_records; c->sh_epoch = c->records_epoch; }
+    if (c->bake_has_counts && sh) c->bake_has_counts = false;       // (the tap counts are not compacted)
+}
+
+}  // namespace m2s_host
 
 extern "C" {
 
@@ -51,6 +93,20 @@ m2s_status m2s_contrib_begin(m2s_ctx* c) {
     c->contrib_n = n;
     c->contrib_epoch = c->records_epoch;
     c->contrib_active = true;
+    return M2S_OK;
+}
+
+m2s_status m2s_upload_contrib(m2s_ctx* c, const uint32_t* host_wmax, const uint32_t* host_npix, uint64_t n) {
+    if (!c) return M2S_ERR_INVALID;
+    if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin)");
+    if (n != c->contrib_n) return fail(c, M2S_ERR_INVALID, "the number of words is not the number of records");
+    if (host_wmax)
+        for (uint64_t i = 0; i < n; ++i)
+            if (host_wmax[i] > 0x3F800000u) return fail(c, M2S_ERR_INVALID, "a wmax word is not the bits of a weight in [0, 1]");
+    if (!n) return M2S_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (host_wmax) HIPCHK(c, hipMemcpy(c->d_contrib, host_wmax, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (host_npix) HIPCHK(c, hipMemcpy(c->d_contrib + c->d_contrib.cap(), host_npix, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     return M2S_OK;
 }
 
@@ -115,7 +171,7 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
     const uint64_t n = c->last_stored;
     const uint32_t R = c->last_R;
     uint64_t kept = 0, by_w = 0, by_p = 0;
-    const bool sh = c->sh_valid && c->sh_of == c->last_records && c->sh_epoch == c->records_epoch && c->sh_n == n;
+    const bool sh = prune_sh_plane(c, n);
     if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[0], c->stream));
     if (n) {
         // flags | offsets | two 64-bit counters
@@ -136,39 +192,14 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
         HIPCHK(c, hipStreamSynchronize(c->stream));
         by_w = h[0]; by_p = h[1];
         kept = n - by_w - by_p;
-        // The survivors go into the pool.  Records that live there already (or a plane compacted in place) cannot be compacted onto
-        // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
-        const bool in_pool = c->last_records == c->lane[0].records;
-        const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
-        if (stage_bytes) M2S_TRY(c->d_prune_stage.reserve(c->err, stage_bytes, 1));
-        const void* src = c->last_records;
-        if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
-        if (kept) {
-            float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
-            HIPCHK(c, prune_compact((const float4*)src, flags, offsets, (uint32_t)n, 6, dst, c->stream));
-            if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, kept * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
-            if (sh) {
-                HIPCHK(c, prune_compact((const float4*)c->d_sh.get(), flags, offsets, (uint32_t)n, 12, c->d_prune_stage, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->d_sh, c->d_prune_stage, kept * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            }
-        }
-    } else if (!c->lane[0].records || c->last_records != c->lane[0].records) {
-        if (m2s_status s = ensure_records(c, 1)) return s;
+        M2S_TRY(prune_compact_enqueue(c, n, kept, flags, offsets, sh));
+    } else {
+        M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_prune_ms, c->prune_ev[0], c->prune_ev[1]));
-    // the survivors are the context's current records now, at the resolutionTarget of the ones they were taken from
-    c->last_records = c->lane[0].records;
-    ++c->records_epoch;
-    c->last_total = c->last_stored = kept;
-    c->last_R = R;
-    c->records_stale = false;
-    c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
-    c->sq_src = nullptr;
-    c->contrib_active = false;
-    if (sh) { c->sh_n = kept; c->sh_of = c->last_records; c->sh_epoch = c->records_epoch; }
-    if (c->bake_has_counts && sh) c->bake_has_counts = false;       // (the tap counts are not compacted)
+    prune_adopt(c, kept, R, sh);
     c->last_prune_counts[0] = n; c->last_prune_counts[1] = kept; c->last_prune_counts[2] = by_w; c->last_prune_counts[3] = by_p;
     if (out_kept) *out_kept = kept;
     return M2S_OK;

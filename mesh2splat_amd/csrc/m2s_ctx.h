@@ -9,6 +9,7 @@
 //   m2s_meshrender.cpp the mesh render pass (== MeshRenderPass::execute) and the mesh G-buffer
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
+//   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -211,6 +212,13 @@ struct m2s_ctx {
     uint64_t last_prune_counts[4] = { 0, 0, 0, 0 };
     float last_prune_ms = 0.0f;
     m2s_host::EventSet<2> prune_ev;
+    // pruning to a budget (m2s_budget.cpp): one key per record and the select's words (m2s_device.h); flags, offsets, scan area and
+    // staging are m2s_prune's
+    m2s_host::DevBuf<uint32_t> d_budget_keys;
+    m2s_host::DevBuf<uint32_t> d_budget_state;
+    uint64_t last_budget_counts[6] = { 0, 0, 0, 0, 0, 0 };
+    float last_budget_stage_ms[3] = { 0, 0, 0 };   // keys + select rounds, flags + scans, compaction (profiling on)
+    m2s_host::EventSet<5> budget_ev;               // start, select done, scans done | compaction: start, end
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each
@@ -359,6 +367,15 @@ m2s_status ensure_stage(m2s_ctx* c);
 struct SplatBins { const uint32_t* vals = nullptr; const uint2* ranges = nullptr; const uint32_t* order = nullptr; uint64_t pairs = 0, skipped = 0; };
 m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out);
 m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]);   // ... and their times + the blend's (ev[4..5]), profiling on
+// m2s_contrib.cpp
+bool contrib_valid(const m2s_ctx* c);   // the accumulators belong to the context's current records
+// What m2s_prune and m2s_prune_budget end with.  prune_compact_enqueue: the `kept` flagged records of the n current ones (and the rows of
+// a baked plane, with sh) go into the pool in order, through the staging buffer where they would land on themselves; n = 0: a pool to
+// point at.  prune_adopt, once the stream has drained: they are the context's current records at resolutionTarget R, and everything
+// derived from the old ones is invalid.
+bool prune_sh_plane(const m2s_ctx* c, uint64_t n);   // a baked plane of exactly these records exists
+m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh);
+void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh);
 // m2s_meshdepth.cpp
 // What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
 // tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);

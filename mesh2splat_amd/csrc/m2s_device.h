@@ -283,6 +283,21 @@ hipError_t prune_flags_scan(const uint32_t* wmax, const uint32_t* npix, uint32_t
 hipError_t prune_compact(const float4* src, const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t f4_per_row, float4* dst,
                          hipStream_t st);
 
+// ---- pruning to a budget (m2s_budget.hip): a radix select over one 32-bit key per record --------------------------------------------
+// The select's words on the device: the candidates (kBudgetShards partial counts), then — once the candidates exceed the budget — the
+// digits of T found so far, the quota still to fill (after the last round: how many of the records with key == T are kept), 1 once T is
+// complete, the candidates with key == T; then per round kBudgetShards copies of its 256 bins.  The shards are summed by their readers.
+constexpr uint32_t kBudgetShards = 4;      // (a power of two)
+constexpr uint32_t kBudgetCandidates = 0, kBudgetPrefix = 4, kBudgetQuota = 5, kBudgetActive = 6, kBudgetTies = 7, kBudgetHist = 8;
+constexpr uint32_t kBudgetStateWords = kBudgetHist + 4 * kBudgetShards * 256;
+// keys (importance 0: from wmax / npix and m2s_prune's thresholds; 1: from rec, the accumulators are not read), the four histogram /
+// pick rounds, ev[0]; tie flags, their ranks, keep flags, offsets = exclusive scan of the keep flags, ev[1] (ev NULL: no events).
+// keys, flags, offsets: n words each; state: kBudgetStateWords; temp: prune_scan_temp_bytes(n).  budget >= 1, n > 0.
+hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t* npix, uint32_t n, uint32_t importance, float min_weight,
+                         uint32_t min_pixels, uint32_t budget, uint32_t* keys, uint32_t* state, uint32_t* flags, uint32_t* offsets, void* temp,
+                         size_t temp_bytes, hipEvent_t* ev, hipStream_t st);
+hipError_t preload_budget();
+
 // ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
 struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads
 struct RelightK {                              // uniforms of gaussianSplattingDeferredPS.glsl

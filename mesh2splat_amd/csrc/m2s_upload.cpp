@@ -348,7 +348,7 @@ m2s_status m2s_prepare(m2s_ctx* c, uint32_t flags) {
             M2S_TRY(c->h_export[k].ensure(c->err, m2s_ply::kChunkRows * sizeof(m2s_gaussian)));
     if ((flags & M2S_PREPARE_KERNELS) && !debug_on("M2S_NO_PRELOAD")) {
         HIPCHK(c, preload_fused2()); HIPCHK(c, preload_fused3()); HIPCHK(c, preload_sparse()); HIPCHK(c, preload_multipass());
-        HIPCHK(c, preload_export()); HIPCHK(c, preload_prepass()); HIPCHK(c, preload_sort()); HIPCHK(c, preload_splat()); HIPCHK(c, preload_light()); HIPCHK(c, preload_meshdepth()); HIPCHK(c, preload_meshrender()); HIPCHK(c, preload_score());
+        HIPCHK(c, preload_export()); HIPCHK(c, preload_prepass()); HIPCHK(c, preload_sort()); HIPCHK(c, preload_splat()); HIPCHK(c, preload_light()); HIPCHK(c, preload_meshdepth()); HIPCHK(c, preload_meshrender()); HIPCHK(c, preload_score()); HIPCHK(c, preload_budget());
     }
     return M2S_OK;
 }

@@ -16,6 +16,16 @@ class PruneParamsC(C.Structure):
     _fields_ = [("min_weight", C.c_float), ("min_pixels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+IMPORTANCE = {"views": 0, "area": 1}     # M2S_IMPORTANCE_*
+BUDGET_COUNTS = ("before", "candidates", "kept", "threshold_key", "ties_kept", "ties")     # m2s_last_budget_counts, in order
+
+
+class BudgetParamsC(C.Structure):
+    """== m2s_budget_params (include/m2s.h)."""
+    _fields_ = [("max_records", C.c_uint64), ("min_weight", C.c_float), ("min_pixels", C.c_uint32), ("importance", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 def orbit_cameras(scene_or_bbox, K: int, W: int, H: int, elevations: Sequence[float] = DEFAULT_ELEVATIONS):
     """K cameras round the scene at each of `elevations` (degrees, strictly between -90 and 90): score.orbit_cameras ring by ring, in
     the order of `elevations`.  -> len(elevations) * K cameras."""

@@ -75,6 +75,9 @@ struct Options {
     double prune_weight = 1.0 / 255.0;                             // --prune-weight w: keep wmax > w
     long prune_pixels = 1;                                         // --prune-pixels n: keep npix >= n
     double prune_count_weight = 1.0 / 255.0;                       // --prune-count-weight c: a fragment counts with weight > c
+    long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
+    bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
+    long conversion_cap() const { return budget > 0 && !cap_set ? 0 : cap; }
     bool preview_mode_set = false;                                 // (--score lights its frames in mode 6 unless --preview-mode says otherwise)
     uint32_t R() const { return density > 0 ? (uint32_t)density : (uint32_t)(int)(16 + quality * (double)(max_res - 16)); }  // ImGuiUI.cpp:512
 };
@@ -89,7 +92,7 @@ void usage() {
                  "         [--preview-mode N (0..6; 5 = metallic-roughness view, 6 = lit)] [--light x,y,z[,intensity]]\n"
                  "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
                  "         [--prune K [--prune-elevations e1,e2,...] [--prune-weight w] [--prune-pixels n] [--prune-count-weight c]]\n"
-                 "         [--bake-light [--bake-degree 0..3]] [--compact]\n"
+                 "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -113,7 +116,17 @@ void usage() {
                  "  256 rows, 16 bytes per row, laid out after the PlayCanvas compressed PLY; not verified against their reader).  It runs after\n"
                  "  --prune; with --bake-light the file carries the SH element.  Prints ONE line `compact: {...}` of JSON per file: rows, chunks,\n"
                  "  skipped, bytes, stage_ms (box + keys, sort, pack, download + write).  Not with --gpus N > 1 (the Morton order is global: slice\n"
-                 "  writers do not apply), hence not with --batch together with --gpus; --batch alone works.\n");
+                 "  writers do not apply), hence not with --batch together with --gpus; --batch alone works.\n"
+                 "--budget N (>= 1): keep the N most important Gaussians (m2s_prune_budget), ties by index; fewer when fewer exist.  With\n"
+                 "  --prune K the importance is npix * wmax over the K cameras' views and --prune's thresholds select the candidates; without\n"
+                 "  it |scale x| * |scale y| * alpha of every record, right after the conversion (also with --batch).  It runs where --prune\n"
+                 "  runs: before --bake-light, --compact, the export, --preview and --score.  --cap truncates in canonical order (the last\n"
+                 "  meshes go first): without an explicit --cap the conversion runs with the cap lifted, an explicit one is honoured.  Prints\n"
+                 "  ONE line `budget: {...}` of JSON per file: importance, max_records, before, candidates, kept, threshold_key, ties_kept,\n"
+                 "  ties, cap_lifted.  Not with --gpus N > 1.  With --prune the `prune:` line changes its keys: it carries before, kept,\n"
+                 "  dropped_thresholds (failed --prune's thresholds) and dropped_budget (passed them, cut by the budget) in place of\n"
+                 "  dropped_weight / dropped_pixels, which a budget does not tell apart.  With --batch the per-file report times the selection\n"
+                 "  as `budget`, apart from `convert`.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -464,8 +477,21 @@ int export_compact(m2s_ctx* ctx, const std::string& out, const Options& o, bool 
     return 0;
 }
 
+// --budget N: m2s_prune_budget over the context's records (VIEWS: the accumulators of run_prune); prints one JSON line
+int run_budget(m2s_ctx* ctx, uint32_t importance, float min_weight, uint32_t min_pixels, const Options& o) {
+    m2s_budget_params bp = { (uint64_t)o.budget, min_weight, min_pixels, importance, 0 };
+    uint64_t kept = 0, c[6] = { 0, 0, 0, 0, 0, 0 };
+    if (m2s_prune_budget(ctx, &bp, &kept) != M2S_OK || m2s_last_budget_counts(ctx, c) != M2S_OK) return 1;
+    std::printf("budget: {\"importance\": \"%s\", \"max_records\": %lld, \"before\": %llu, \"candidates\": %llu, \"kept\": %llu, "
+                "\"threshold_key\": %llu, \"ties_kept\": %llu, \"ties\": %llu, \"cap_lifted\": %s}\n",
+                importance == M2S_IMPORTANCE_VIEWS ? "views" : "area", o.budget, (unsigned long long)c[0], (unsigned long long)c[1],
+                (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5], o.cap_set ? "false" : "true");
+    return 0;
+}
+
 // --prune K: K cameras round the scene at each elevation, at --preview-size; per camera m2s_prepass_sorted -> m2s_contrib_accumulate, then
-// m2s_prune (Converter.prune_views does the same).  Prints one JSON line.
+// m2s_prune (Converter.prune_views does the same) — with --budget: m2s_prune_budget with the same thresholds, whose line follows; what the
+// thresholds dropped is then not split into weight and pixels.  Prints one JSON line.
 int run_prune(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
     const int W = o.preview_w, H = o.preview_h, K = o.prune_views;
     double ctr[3], dist, near_p, far_p;
@@ -494,6 +520,15 @@ int run_prune(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t 
     }
     m2s_prune_params pr = { (float)o.prune_weight, (uint32_t)o.prune_pixels, 0 };
     uint64_t kept = 0, c[4] = { 0, 0, 0, 0 };
+    if (o.budget > 0) {
+        uint64_t b[6] = { 0, 0, 0, 0, 0, 0 };
+        if (run_budget(ctx, M2S_IMPORTANCE_VIEWS, pr.min_weight, pr.min_pixels, o) != 0 || m2s_last_budget_counts(ctx, b) != M2S_OK) return 1;
+        std::printf("prune: {\"views\": %d, \"elevations\": [%s], \"size\": [%d, %d], \"density\": %u, \"min_weight\": %s, \"min_pixels\": %ld, "
+                    "\"count_weight\": %s, \"eyes\": [%s], \"before\": %llu, \"kept\": %llu, \"dropped_thresholds\": %llu, \"dropped_budget\": %llu}\n",
+                    K, els.c_str(), W, H, R, json_num((double)pr.min_weight).c_str(), o.prune_pixels, json_num((double)(float)o.prune_count_weight).c_str(),
+                    eyes.c_str(), (unsigned long long)b[0], (unsigned long long)b[2], (unsigned long long)(b[0] - b[1]), (unsigned long long)(b[1] - b[2]));
+        return 0;
+    }
     if (m2s_prune(ctx, &pr, &kept) != M2S_OK || m2s_last_prune_counts(ctx, c) != M2S_OK) return 1;
     std::printf("prune: {\"views\": %d, \"elevations\": [%s], \"size\": [%d, %d], \"density\": %u, \"min_weight\": %s, \"min_pixels\": %ld, "
                 "\"count_weight\": %s, \"eyes\": [%s], \"before\": %llu, \"kept\": %llu, \"dropped_weight\": %llu, \"dropped_pixels\": %llu}\n",
@@ -528,7 +563,7 @@ int convert_one(const Options& o) {
     const auto t1b = Clock::now();
     auto die = [&](const char* what) { std::fprintf(stderr, "%s: %s\n", what, m2s_last_error(ctx)); m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; };
     if (m2s_set_pipeline(ctx, o.pipeline) != M2S_OK) return die("set_pipeline");
-    if (m2s_set_max_gaussians(ctx, o.cap) != M2S_OK) return die("set_max_gaussians");
+    if (m2s_set_max_gaussians(ctx, o.conversion_cap()) != M2S_OK) return die("set_max_gaussians");
     (void)m2s_set_resolution_hint(ctx, o.R());   // the upload prepares for the conversion below
     if (m2s_upload_scene(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene)) != M2S_OK) return die("upload");
     const auto t2 = Clock::now();
@@ -537,6 +572,7 @@ int convert_one(const Options& o) {
     if (m2s_convert(ctx, R, &total) != M2S_OK) return die("convert");
     const auto t3 = Clock::now();
     if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
+    if (o.budget > 0 && o.prune_views == 0 && run_budget(ctx, M2S_IMPORTANCE_AREA, 0.0f, 0, o) != 0) return die("budget");
     if (o.bake_light) {
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
         if (o.compact) { if (export_compact(ctx, o.out, o, true) != 0) return die("export"); }
@@ -758,14 +794,14 @@ private:
 };
 
 struct Loaded { std::string in, out; m2s_host_scene* scene = nullptr; double load_ms = 0; };
-struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0; };
+struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1; };   // budget_ms < 0: no --budget
 
 int batch_on_device(const Options& o, const std::vector<std::pair<std::string, std::string>>& files, int device, int tag) {
     const auto t_begin = Clock::now();
     m2s_ctx* ctx[2] = { nullptr, nullptr };
     for (auto& c : ctx)
         if (m2s_create(device, &c) != M2S_OK) { std::fprintf(stderr, "%s\n", m2s_last_error(nullptr)); return 1; }
-    for (auto c : ctx) { (void)m2s_set_pipeline(c, o.pipeline); (void)m2s_set_max_gaussians(c, o.cap); }
+    for (auto c : ctx) { (void)m2s_set_pipeline(c, o.pipeline); (void)m2s_set_max_gaussians(c, o.conversion_cap()); }
     Channel<Loaded> loaded(2);
     Channel<Converted> converted(1);
     std::mutex slot_m; std::condition_variable slot_cv; bool slot_busy[2] = { false, false };   // a context's records are being exported
@@ -789,8 +825,10 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
                 std::fprintf(stderr, "%s: export: %s\n", c.in.c_str(), m2s_last_error(ctx[c.slot])); ++failures;
             }
             const double ex = ms_between(a, Clock::now());
-            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
-                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, ex);
+            char budget[48] = "";
+            if (c.budget_ms >= 0) std::snprintf(budget, sizeof(budget), ", budget %.2f ms", c.budget_ms);
+            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms%s, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
+                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, budget, ex);
             { std::lock_guard<std::mutex> l(slot_m); slot_busy[c.slot] = false; }
             slot_cv.notify_all();
         }
@@ -808,6 +846,11 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
         a = Clock::now();
         ok = ok && m2s_convert(ctx[slot], o.R(), &c.total) == M2S_OK;
         c.convert_ms = ms_between(a, Clock::now());
+        if (ok && o.budget > 0) {                                                                   // (its lines come in file order)
+            a = Clock::now();
+            ok = run_budget(ctx[slot], M2S_IMPORTANCE_AREA, 0.0f, 0, o) == 0;
+            c.budget_ms = ms_between(a, Clock::now());
+        }
         m2s_free_host_scene(l.scene);
         if (!ok) {
             std::fprintf(stderr, "%s: %s\n", l.in.c_str(), m2s_last_error(ctx[slot])); ++failures;
@@ -866,7 +909,8 @@ int main(int argc, char** argv) {
         else if (a == "--std") o.std_dev = std::atof(next());
         else if (a == "--format") o.format = std::atol(next());
         else if (a == "--device") o.device = std::atol(next());
-        else if (a == "--cap") o.cap = std::atol(next());
+        else if (a == "--cap") { o.cap = std::atol(next()); o.cap_set = true; }
+        else if (a == "--budget") { o.budget = std::atoll(next()); if (o.budget < 1) { usage(); return 2; } }
         else if (a == "--gpus") o.gpus = std::atol(next());
         else if (a == "--gather") o.gather = true;
         else if (a == "--force-sharded") o.force_sharded = true;
@@ -921,6 +965,7 @@ int main(int argc, char** argv) {
     if (o.gpus < 1 || o.gpus > 64) { usage(); return 2; }
     // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
     if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
+    if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
