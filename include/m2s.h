@@ -510,6 +510,71 @@ m2s_status m2s_last_budget_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
  * the bits of a weight in [0, 1]); M2S_ERR_STATE without accumulators of the current records. */
 m2s_status m2s_upload_contrib(m2s_ctx* ctx, const uint32_t* host_wmax, const uint32_t* host_npix, uint64_t n);
 
+/* ---- colour refit (no counterpart in the reference: its Gaussians keep the one texture sample the conversion gave them) -------- */
+/* Carries the per-pixel colour error of the splat picture against the mesh picture of the same camera back to the records, over any
+ * number of views, and applies it: one SART step dc_i = step * sum_p(w_i(p) e(p)) / sum_p(w_i(p)).  The pin (tests/refit_ref.py
+ * restates it):
+ *  - Planes.  Two uchar4[W * H] device images, row 0 = bottom: the target (NULL: attachment 2 of the mesh G-buffer, m2s_mesh_render)
+ *    and the render (NULL: attachment 2 of the splat G-buffer, m2s_splat).  THE CALLER must have rendered the render plane from the
+ *    context's current sorted quads in a colour mode (render mode 0 or 6): the pass recomputes the fragment weights from those quads
+ *    and takes the picture they produced from the plane.  It does not read quad colours.
+ *  - Pixel participation.  A pixel takes part iff the target's alpha byte is non-zero and the render's alpha byte sa >= min_cover
+ *    (1..255).
+ *  - Per-pixel error, integers only, per channel k with m the target byte and s the render byte: n = 4096 * (m * sa - 255 * s) (fits
+ *    int32), d = 255 * sa, eq_k = floor((2 n + d) / (2 d)) — a floor division — clamped to [-4096, 4096]: e = m / 255 - s / sa, the
+ *    error of the un-premultiplied splat colour, in steps of 1 / 4096, |e| <= 1 by the clamp.
+ *  - Fragment weight.  Geometry, coverage, quad order, skipped quads, g = exp(alpha) (the device's fast exp) and w = sA3 * tA are those
+ *    of m2s_contrib_accumulate, with A3 evolving byte-quantised exactly as there; a pixel under both triangles of a quad yields two
+ *    fragments.  wq = (uint32)rintf(w * 65536.0f), 0..65536; the scaling by a power of two is exact.
+ *  - Accumulation.  Four 64-bit words per record, num[3] (signed) and den (unsigned).  Per fragment on a participating pixel, for the
+ *    record the quad was made from: num[k] += (int64)wq * eq_k, den += wq.  A pixel that does not take part adds nothing.  Integer sums:
+ *    independent of the order of evaluation, identical from run to run.  A product is at most 2^28 in magnitude; a record has at most
+ *    2^30 fragments over 256 views (m2s_contrib_accumulate's bound), so |num| < 2^58 and den < 2^46.  The words keep adding over calls
+ *    (views).  Behind a saturated pixel w = +0 and wq = 0: the accumulators receive exactly nothing.
+ * m2s_refit_begin sizes the accumulators to the context's current records, zeroes them and ties them to those records, exactly as
+ * m2s_contrib_begin does, with its error cases.
+ * m2s_refit_accumulate runs over the context's sorted quads and their sources at params->resolution.  out_counts (may be NULL):
+ * [0] participating pixels, [1] (tile, quad) pairs.  Synchronous.  M2S_ERR_INVALID as m2s_contrib_accumulate — no m2s_refit_begin,
+ * records that changed since it, missing sorted quads or sources, a resolution outside 1..8192, reserved != 0 — and for min_cover
+ * outside 1..255; M2S_ERR_STATE for a NULL plane whose G-buffer is missing or not W x H (as m2s_score_frames). */
+typedef struct m2s_refit_params {
+    int32_t  resolution[2];
+    uint32_t min_cover;     /* 1..255 */
+    uint32_t reserved;      /* 0 */
+} m2s_refit_params;         /* 16 bytes */
+m2s_status m2s_refit_begin(m2s_ctx* ctx);
+m2s_status m2s_refit_accumulate(m2s_ctx* ctx, const m2s_refit_params* params, const void* d_target, const void* d_render, uint64_t out_counts[2]);
+/* dst_num: int64[3 * capacity_records], three words per record; dst_den: uint64[capacity_records]; either may be NULL.
+ * M2S_ERR_STATE without valid accumulators, M2S_ERR_CAPACITY for fewer than m2s_num_stored records. */
+m2s_status m2s_download_refit(m2s_ctx* ctx, int64_t* dst_num, uint64_t* dst_den, uint64_t capacity_records);
+/* The counterpart of m2s_upload_contrib: after m2s_refit_begin, host arrays for n == m2s_num_stored records become num (3 n words) and
+ * den (either may be NULL: it stays as it is), so that a caller with an error measure of its own — or a test — drives m2s_refit_apply
+ * without rendering.  M2S_ERR_INVALID for another n; M2S_ERR_STATE without accumulators of the current records. */
+m2s_status m2s_upload_refit(m2s_ctx* ctx, const int64_t* host_num, const uint64_t* host_den, uint64_t n);
+/* which = 0: num, int64[3 * m2s_num_stored]; 1: den, uint64[m2s_num_stored].  NULL without valid accumulators. */
+const void* m2s_device_refit(const m2s_ctx* ctx, uint32_t which);
+/* The update, one lane per record.  D = llrint((double)min_weight_sum * 65536) on the host (saturating at 2^64 - 1).  A record with
+ * den < D or den == 0 is left untouched; so is a channel whose colour is not finite.  Otherwise, per channel k, every operation in
+ * fp64 and correctly rounded: dlt = (double)num_k / ((double)den * 4096.0) — the product is exact, the conversions round once —,
+ * c' = (float)fmin(fmax((double)c + (double)step * dlt, 0.0), 1.0).  Only color[0..2] of the 96-byte record change: alpha and every
+ * other field keep their bits.
+ * Effect on the context, as m2s_prune: the records live in the context-owned pool afterwards (records adopted through
+ * m2s_set_records are copied there first; the caller's memory is not written), the records epoch advances, and cached positions,
+ * sorted quads, sources, the contribution accumulators, the refit accumulators and a baked SH plane (it was baked from the old albedo)
+ * are invalidated.  out_counts (may be NULL): [0] records, [1] updated, [2] updated with at least one channel clamped, [3] left for
+ * lack of weight.  Synchronous.  M2S_ERR_INVALID: a step that is not finite, a min_weight_sum that is negative or not finite,
+ * reserved != 0; M2S_ERR_STATE without accumulators of the current records or with conversions in flight. */
+typedef struct m2s_refit_apply_params {
+    float    step;             /* the SART relaxation: converges for the linearised blend in (0, 2) */
+    float    min_weight_sum;   /* in units of one fully weighted fragment */
+    uint32_t reserved[2];      /* 0 */
+} m2s_refit_apply_params;      /* 16 bytes */
+m2s_status m2s_refit_apply(m2s_ctx* ctx, const m2s_refit_apply_params* params, uint64_t out_counts[4]);
+/* Stages (ms) of the last profiled m2s_refit_accumulate: [0] setup + bin, [1] grouping (both m2s_splat's own), [2] the refit blend;
+ * and the duration of the last profiled m2s_refit_apply. */
+m2s_status m2s_last_refit_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+float m2s_last_refit_apply_ms(const m2s_ctx* ctx);
+
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */
 typedef struct m2s_light_params {

@@ -10,6 +10,7 @@
 //   m2s_score.cpp    the fidelity score (m2s_score_frames): mesh frame against splat frame
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
+//   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -219,6 +220,16 @@ struct m2s_ctx {
     uint64_t last_budget_counts[6] = { 0, 0, 0, 0, 0, 0 };
     float last_budget_stage_ms[3] = { 0, 0, 0 };   // keys + select rounds, flags + scans, compaction (profiling on)
     m2s_host::EventSet<5> budget_ev;               // start, select done, scans done | compaction: start, end
+    // colour refit (m2s_refit.cpp): num (int64, three words per record) | den (uint64), one capacity of records; valid for
+    // (refit_of, refit_n, refit_epoch) as the contribution accumulators are
+    m2s_host::DevBuf<unsigned long long> d_refit;
+    uint64_t refit_n = 0, refit_epoch = 0;
+    const void* refit_of = nullptr;
+    bool refit_active = false;
+    m2s_host::DevBuf<unsigned long long> d_refit_counts;   // m2s_refit_apply: updated, clamped, left for lack of weight
+    float last_refit_stage_ms[3] = { 0, 0, 0 };    // setup + bin, grouping, refit blend (profiling on)
+    float last_refit_apply_ms = 0.0f;
+    m2s_host::EventSet<2> refit_ev;                // the apply
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each

@@ -298,6 +298,18 @@ hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t
                          size_t temp_bytes, hipEvent_t* ev, hipStream_t st);
 hipError_t preload_budget();
 
+// ---- colour refit (m2s_refit.hip) --------------------------------------------------------------------------------------------------
+// k_splat_refit over the records / pairs / ranges / order of the splat pass's binning stages, one workgroup per tile of the W x H
+// viewport (vals / ranges / order NULL: no pairs, the participating pixels are still counted): per record sources[quad],
+// num[3 r + k] += wq * eq_k and den[r] += wq over the fragments on participating pixels; *pixels += participating pixels
+hipError_t refit_blend(const float4* rec, const uint32_t* vals, const uint2* ranges, const uint32_t* order, int W, int H,
+                       const uint32_t* sources, const uint32_t* target, const uint32_t* render, uint32_t min_cover, long long* num,
+                       unsigned long long* den, unsigned long long* pixels, hipStream_t st);
+// k_refit_apply, one lane per 96-byte record: the pinned update of color[0..2] where den >= max(D, 1);
+// counters[0] += updated, [1] += updated with a channel clamped, [2] += left for lack of weight (zeroed by the caller)
+hipError_t refit_apply(float4* records, const long long* num, const unsigned long long* den, uint32_t n, double step, unsigned long long D,
+                       unsigned long long* counters, hipStream_t st);
+
 // ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
 struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads
 struct RelightK {                              // uniforms of gaussianSplattingDeferredPS.glsl

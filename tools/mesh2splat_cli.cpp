@@ -75,6 +75,12 @@ struct Options {
     double prune_weight = 1.0 / 255.0;                             // --prune-weight w: keep wmax > w
     long prune_pixels = 1;                                         // --prune-pixels n: keep npix >= n
     double prune_count_weight = 1.0 / 255.0;                       // --prune-count-weight c: a fragment counts with weight > c
+    int refit_views = 0;                                           // --refit K: K cameras round the scene per elevation; refit the colours to the mesh render (m2s_refit_*)
+    int refit_iters = 2;                                           // --refit-iters n (a guess nobody has tuned, like the two constants below)
+    double refit_step = 1.0;                                       // --refit-step s
+    std::vector<double> refit_elevations = { -35.0, 0.0, 35.0 };   // --refit-elevations e1,e2,...
+    static constexpr uint32_t kRefitMinCover = 128;                // a pixel takes part from this splat alpha on
+    static constexpr float kRefitMinWeightSum = 1.0f;              // a record is updated from this much accumulated weight on
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
     bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
     long conversion_cap() const { return budget > 0 && !cap_set ? 0 : cap; }
@@ -93,6 +99,7 @@ void usage() {
                  "         [--score K [--score-elevation deg] [--score-mask 0..3] [--score-map prefix]]\n"
                  "         [--prune K [--prune-elevations e1,e2,...] [--prune-weight w] [--prune-pixels n] [--prune-count-weight c]]\n"
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
+                 "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -126,7 +133,16 @@ void usage() {
                  "  ties, cap_lifted.  Not with --gpus N > 1.  With --prune the `prune:` line changes its keys: it carries before, kept,\n"
                  "  dropped_thresholds (failed --prune's thresholds) and dropped_budget (passed them, cut by the budget) in place of\n"
                  "  dropped_weight / dropped_pixels, which a budget does not tell apart.  With --batch the per-file report times the selection\n"
-                 "  as `budget`, apart from `convert`.\n");
+                 "  as `budget`, apart from `convert`.\n"
+                 "--refit K [--refit-iters n (default 2)] [--refit-step s (default 1)] [--refit-elevations e1,e2,... (default -35,0,35)]: refit the\n"
+                 "  Gaussians' colours to the mesh render.  Per iteration, through K cameras round the scene at each elevation (the --score camera\n"
+                 "  rule) at --preview-size: m2s_prepass_sorted, m2s_splat and m2s_mesh_render in mode 0, m2s_refit_accumulate over the two albedo\n"
+                 "  planes; then m2s_refit_apply (one SART step; min_cover 128, min_weight_sum 1 and the two iterations are untuned guesses).  It\n"
+                 "  runs after --prune / --budget and before --bake-light, --score, --preview, --compact and the export.  Prints ONE line\n"
+                 "  `refit: {...}` of JSON: iterations, views, size, density, step, sse (the albedo planes' pooled squared error over the pixels\n"
+                 "  both cover, before and after every iteration), pixels, and per iteration updated, clamped, no_weight.  Those are the TRAINING\n"
+                 "  cameras: --score with other elevations (--score-elevation) is the held-out check.  Not with --gpus N > 1; with --batch the\n"
+                 "  per-file report times it as `refit`.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -489,6 +505,70 @@ int run_budget(m2s_ctx* ctx, uint32_t importance, float min_weight, uint32_t min
     return 0;
 }
 
+// --refit K: K cameras round the scene at each elevation, at --preview-size; per iteration and camera m2s_prepass_sorted -> m2s_splat ->
+// m2s_mesh_render -> m2s_refit_accumulate, then m2s_refit_apply (Converter.refit_views does the same).  Prints one JSON line.
+int run_refit(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+    const int W = o.preview_w, H = o.preview_h, K = o.refit_views;
+    double ctr[3], dist, near_p, far_p;
+    preview_rule(meshes, n_meshes, ctr, &dist, &near_p, &far_p);
+    std::string sse, pixels, updated, clamped, starved;
+    auto add = [](std::string& list, unsigned long long v) { list += std::string(list.empty() ? "" : ", ") + std::to_string(v); };
+    for (int it = 0; it <= o.refit_iters; ++it) {
+        const bool last = it == o.refit_iters;                     // (the pass behind the last iteration only measures)
+        if (!last && m2s_refit_begin(ctx) != M2S_OK) return 1;
+        unsigned long long sse_sum = 0, px_sum = 0;
+        for (size_t e = 0; e < o.refit_elevations.size(); ++e) {
+            for (int v = 0; v < K; ++v) {
+                const double th = 2.0 * M_PI * v / K, el = o.refit_elevations[e] * (M_PI / 180.0);
+                const double eye[3] = { ctr[0] + dist * std::cos(el) * std::sin(th), ctr[1] + dist * std::sin(el), ctr[2] + dist * std::cos(el) * std::cos(th) };
+                m2s_prepass_params pp;
+                std::memset(&pp, 0, sizeof(pp));
+                camera_matrices(eye, ctr, near_p, far_p, W, H, pp.world_to_view, pp.view_to_clip);
+                for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
+                pp.resolution[0] = W; pp.resolution[1] = H;
+                pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
+                pp.gaussian_std = (float)o.std_dev;
+                pp.resolution_target = R;
+                uint64_t visible = 0, skipped = 0;
+                if (m2s_prepass_sorted(ctx, &pp, &visible) != M2S_OK) return 1;
+                m2s_splat_params sp = { { W, H }, 0, 0 };
+                static const m2s_quad none = {};
+                if (m2s_splat(ctx, &sp, visible ? nullptr : &none, 0, &skipped) != M2S_OK) return 1;          // (no quads: cleared planes)
+                m2s_mesh_render_params mr;
+                std::memset(&mr, 0, sizeof(mr));
+                std::memcpy(mr.world_to_view, pp.world_to_view, sizeof(mr.world_to_view));
+                std::memcpy(mr.view_to_clip, pp.view_to_clip, sizeof(mr.view_to_clip));
+                std::memcpy(mr.model_to_world, pp.model_to_world, sizeof(mr.model_to_world));
+                mr.resolution[0] = W; mr.resolution[1] = H;
+                mr.near_far[0] = pp.near_far[0]; mr.near_far[1] = pp.near_far[1];
+                mr.render_mode = 0;
+                if (m2s_mesh_render(ctx, &mr, nullptr) != M2S_OK) return 1;
+                m2s_score_params sc = { { W, H }, 3u, 0u, { 0, 0 } };
+                m2s_score_result r;
+                if (m2s_score_frames(ctx, &sc, m2s_device_mesh_gbuffer(ctx, 2), m2s_device_gbuffer(ctx, 2), nullptr, nullptr, &r) != M2S_OK) return 1;
+                sse_sum += r.sse[0] + r.sse[1] + r.sse[2];
+                px_sum += r.pixels;
+                m2s_refit_params rp = { { W, H }, Options::kRefitMinCover, 0 };
+                if (!last && visible && m2s_refit_accumulate(ctx, &rp, nullptr, nullptr, nullptr) != M2S_OK) return 1;
+            }
+        }
+        add(sse, sse_sum);
+        add(pixels, px_sum);
+        if (last) break;
+        m2s_refit_apply_params ap = { (float)o.refit_step, Options::kRefitMinWeightSum, { 0, 0 } };
+        uint64_t c[4] = { 0, 0, 0, 0 };
+        if (m2s_refit_apply(ctx, &ap, c) != M2S_OK) return 1;
+        add(updated, c[1]); add(clamped, c[2]); add(starved, c[3]);
+    }
+    std::string els;
+    for (size_t e = 0; e < o.refit_elevations.size(); ++e) els += std::string(e ? ", " : "") + json_num(o.refit_elevations[e]);
+    std::printf("refit: {\"iterations\": %d, \"views\": %d, \"elevations\": [%s], \"size\": [%d, %d], \"density\": %u, \"step\": %s, \"min_cover\": %u, "
+                "\"min_weight_sum\": %s, \"sse\": [%s], \"pixels\": [%s], \"updated\": [%s], \"clamped\": [%s], \"no_weight\": [%s]}\n",
+                o.refit_iters, K * (int)o.refit_elevations.size(), els.c_str(), W, H, R, json_num((double)(float)o.refit_step).c_str(), Options::kRefitMinCover,
+                json_num((double)Options::kRefitMinWeightSum).c_str(), sse.c_str(), pixels.c_str(), updated.c_str(), clamped.c_str(), starved.c_str());
+    return 0;
+}
+
 // --prune K: K cameras round the scene at each elevation, at --preview-size; per camera m2s_prepass_sorted -> m2s_contrib_accumulate, then
 // m2s_prune (Converter.prune_views does the same) — with --budget: m2s_prune_budget with the same thresholds, whose line follows; what the
 // thresholds dropped is then not split into weight and pixels.  Prints one JSON line.
@@ -573,6 +653,7 @@ int convert_one(const Options& o) {
     const auto t3 = Clock::now();
     if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
     if (o.budget > 0 && o.prune_views == 0 && run_budget(ctx, M2S_IMPORTANCE_AREA, 0.0f, 0, o) != 0) return die("budget");
+    if (o.refit_views > 0 && run_refit(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("refit");
     if (o.bake_light) {
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
         if (o.compact) { if (export_compact(ctx, o.out, o, true) != 0) return die("export"); }
@@ -794,7 +875,7 @@ private:
 };
 
 struct Loaded { std::string in, out; m2s_host_scene* scene = nullptr; double load_ms = 0; };
-struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1; };   // budget_ms < 0: no --budget
+struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1, refit_ms = -1; };   // budget_ms / refit_ms < 0: no --budget / --refit
 
 int batch_on_device(const Options& o, const std::vector<std::pair<std::string, std::string>>& files, int device, int tag) {
     const auto t_begin = Clock::now();
@@ -827,8 +908,10 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
             const double ex = ms_between(a, Clock::now());
             char budget[48] = "";
             if (c.budget_ms >= 0) std::snprintf(budget, sizeof(budget), ", budget %.2f ms", c.budget_ms);
-            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms%s, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
-                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, budget, ex);
+            char refit[48] = "";
+            if (c.refit_ms >= 0) std::snprintf(refit, sizeof(refit), ", refit %.2f ms", c.refit_ms);
+            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms%s%s, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
+                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, budget, refit, ex);
             { std::lock_guard<std::mutex> l(slot_m); slot_busy[c.slot] = false; }
             slot_cv.notify_all();
         }
@@ -850,6 +933,11 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
             a = Clock::now();
             ok = run_budget(ctx[slot], M2S_IMPORTANCE_AREA, 0.0f, 0, o) == 0;
             c.budget_ms = ms_between(a, Clock::now());
+        }
+        if (ok && o.refit_views > 0) {
+            a = Clock::now();
+            ok = run_refit(ctx[slot], m2s_host_scene_meshes(l.scene), m2s_host_scene_num_meshes(l.scene), o.R(), o) == 0;
+            c.refit_ms = ms_between(a, Clock::now());
         }
         m2s_free_host_scene(l.scene);
         if (!ok) {
@@ -926,8 +1014,12 @@ int main(int argc, char** argv) {
         else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); o.preview_mode_set = true; if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
         else if (a == "--score") { o.score_views = std::atoi(next()); if (o.score_views < 1 || o.score_views > 4096) { usage(); return 2; } }
         else if (a == "--prune") { o.prune_views = std::atoi(next()); if (o.prune_views < 1 || o.prune_views > 4096) { usage(); return 2; } }
-        else if (a == "--prune-elevations") {
-            o.prune_elevations.clear();
+        else if (a == "--refit") { o.refit_views = std::atoi(next()); if (o.refit_views < 1 || o.refit_views > 4096) { usage(); return 2; } }
+        else if (a == "--refit-iters") { o.refit_iters = std::atoi(next()); if (o.refit_iters < 1 || o.refit_iters > 64) { usage(); return 2; } }
+        else if (a == "--refit-step") { o.refit_step = std::atof(next()); if (!std::isfinite(o.refit_step)) { usage(); return 2; } }
+        else if (a == "--prune-elevations" || a == "--refit-elevations") {
+            std::vector<double>& list = a == "--prune-elevations" ? o.prune_elevations : o.refit_elevations;
+            list.clear();
             std::string v = next();
             size_t at = 0;
             while (at <= v.size()) {
@@ -936,10 +1028,10 @@ int main(int argc, char** argv) {
                 const std::string tok = v.substr(at, c - at);
                 const double e = std::strtod(tok.c_str(), &end);
                 if (tok.empty() || *end || !(e > -90.0 && e < 90.0)) { usage(); return 2; }
-                o.prune_elevations.push_back(e);
+                list.push_back(e);
                 at = c + 1;
             }
-            if (o.prune_elevations.empty() || o.prune_elevations.size() > 64) { usage(); return 2; }
+            if (list.empty() || list.size() > 64) { usage(); return 2; }
         }
         else if (a == "--prune-weight") { o.prune_weight = std::atof(next()); if (!(o.prune_weight >= 0.0 && o.prune_weight <= 1.0)) { usage(); return 2; } }
         else if (a == "--prune-pixels") { o.prune_pixels = std::atol(next()); if (o.prune_pixels < 0 || o.prune_pixels > 0x7FFFFFFFl) { usage(); return 2; } }
@@ -966,6 +1058,7 @@ int main(int argc, char** argv) {
     // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
     if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
     if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
+    if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
