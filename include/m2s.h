@@ -575,6 +575,71 @@ m2s_status m2s_refit_apply(m2s_ctx* ctx, const m2s_refit_apply_params* params, u
 m2s_status m2s_last_refit_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
 float m2s_last_refit_apply_ms(const m2s_ctx* ctx);
 
+/* ---- merge pass (no counterpart in the reference: its density is chosen once, before the conversion) ---------------------------- */
+/* Replaces groups of neighbouring records by one record that covers what they covered: level of detail without holes, for records of
+ * any origin (converted, pruned, refitted, uploaded, adopted).  A record is read as what the conversion made it, a flat rectangular
+ * texel footprint with edges scale[0], scale[1] along axes 1 and 2 of its rotation, uniform density, second moment
+ * diag(sx^2 / 12, sy^2 / 12, 0) in its own axes; the parent is the moment-matched rectangle of the union (four h x h tiles in a
+ * 2 x 2 block give the 2h x 2h record that half the density would have produced).  The axes are the viewer's: r_1, r_2, r_3 = the rows
+ * of castQuatToMat3 of the stored four floats (x, y, z, w) = rotation[0..3], no normalisation,
+ *    r_1 = (1 - 2(zz + ww), 2(yz + xw), 2(yw - xz)), r_2 = (2(yz - xw), 1 - 2(yy + ww), 2(zw + xy)), r_3 = (2(yw + xz), 2(zw - xy), 1 - 2(yy + zz)),
+ * so that the viewer's covariance is sum_i s_i^2 r_i r_i^T; for a conversion's record r_3 is its normal and r_1, r_2 run along the
+ * triangle's Ju, Jv.  The pin (tests/merge_ref.py restates it):
+ *  1. Order.  Validity, box, key and the stable sort are pins 1 - 4 of the compact export (below), the same functions.  Invalid records
+ *     carry the key 2^30 and sort behind every valid record, in index order.  The sorted sequence is j = 0 .. n-1 with perm[j].
+ *  2. Runs.  Position j starts a run iff j == 0, or record j or j-1 is invalid, or key_j >> (3 level) != key_{j-1} >> (3 level), or
+ *     !(d >= min_axis_dot) with d = ((a0 b0) + a1 b1) + a2 b2 in fp32 without contraction, a and b the r_3 of the two records evaluated
+ *     in fp32 exactly as written above (one rounding per operation).  A NaN breaks the run.
+ *  3. Segments.  A run is cut every max_group members: j is a segment head iff (j - run_start) % max_group == 0.  The number of heads
+ *     is the number of records afterwards; segment s becomes record s.  (Integer logic and exact fp32: reproducible bit for bit.)
+ *  4. A segment of one member is copied byte for byte; every invalid record is such a segment, so they are kept, at the end, unchanged.
+ *  5. A segment of members i = 1..m >= 2, in sorted order, all arithmetic in fp64 (the r_k above evaluated in fp64 from the stored
+ *     floats), every field rounded to fp32 once:
+ *       w_i = sx_i sy_i, or 1 for every member where their sum is 0; W = sum w_i;  d_i = p_i - p_1, mu = sum w_i d_i / W;
+ *       position = p_1 + mu, position[3] = the first member's;
+ *       nb = sum w_i r3_i, or the first member's r_3 where |nb|^2 is 0 or not finite; normalised ((0, 0, 1) where that fails too);
+ *       t1 = the first member's r_1 minus its component along nb, normalised — its r_2 instead where less than 1e-12 |r_1|^2 of the
+ *       squared length is left —, t2 = nb x t1;
+ *       M = sum w_i (A_i + (d_i - mu)(d_i - mu)^T) / W with A_i = (sx_i^2 / 12) r1 r1^T + (sy_i^2 / 12) r2 r2^T;
+ *       a = t1^T M t1, b = t1^T M t2, c = t2^T M t2;  dl = sqrt((a - c)^2 + 4 b^2), l1 = (a + c + dl) / 2, l2 = max((a + c - dl) / 2, 0);
+ *       e1 = t1 where dl == 0, else the normalised one of (b, l1 - a) and (l1 - c, b) (coordinates along t1, t2) with the larger squared
+ *       length, the first on a tie; e2 = nb x e1;
+ *       scale = (sqrt(12 l1), sqrt(12 l2), the first member's scale[2], scale[3]);
+ *       rotation = the quaternion of the matrix with columns e1, e2, nb by the branch selection of the conversion's quat_cast
+ *       (converterGS.glsl:131-183), stored (w, x, y, z) as the conversion stores it, negated as a whole where w < 0;
+ *       alpha = sum w_i alpha_i / W;  rgb = sum w_i alpha_i c_i / sum w_i alpha_i, or sum w_i c_i / W where that denominator is 0;
+ *       normal.xyz = the normalised sum w_i normal_i, all zeros where the sum is zero or not finite; normal[3], pbr[2], pbr[3] are the
+ *       first member's; pbr[0..1] = sum w_i pbr_i / W.
+ *     (Plain moment matching of the rendered Gaussians' covariances is NOT this: it shrinks a 2 x 2 block to 0.82 h where 1.3 h is needed.)
+ *  6. Output order is segment order: the canonical (mesh, triangle, row, column) order of a conversion is gone afterwards.
+ *  7. Effect on the context, as m2s_prune: the parents are written into the context-owned pool (through a staging buffer where the
+ *     sources live there; adopted memory is never written), the resolutionTarget is kept, the records epoch advances; cached positions,
+ *     sorted quads, sources, the contribution and refit accumulators and a baked SH plane (as by m2s_refit_apply: it is not merged)
+ *     are invalidated.  With M2S_MERGE_DRY_RUN nothing of the context changes: only the counts are produced.
+ *  8. out_counts (may be NULL): [0] records before, [1] records after, [2] segments with two members or more, [3] invalid records
+ *     carried.  The counts are monotone in level (a coarser cell only removes run breaks).
+ * Synchronous.  M2S_ERR_INVALID: level > 10, max_group outside 2..64, a NaN min_axis_dot, unknown flag bits, reserved != 0.
+ * M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY: 2^32 records or more. */
+enum { M2S_MERGE_DRY_RUN = 1 };
+typedef struct m2s_merge_params {
+    uint32_t level;          /* 0..10: cell = key >> (3 * level) */
+    uint32_t max_group;      /* 2..64: members per parent, at most */
+    float    min_axis_dot;   /* a run breaks where !(dot(r3_j, r3_prev) >= min_axis_dot); NaN refused */
+    uint32_t flags;          /* M2S_MERGE_DRY_RUN = 1; other bits 0 */
+    uint32_t reserved[2];    /* 0 */
+} m2s_merge_params;          /* 24 bytes */
+m2s_status m2s_merge(m2s_ctx* ctx, const m2s_merge_params* params, uint64_t out_counts[4]);
+/* The counts of the last m2s_merge (a dry run included), and its stages (ms): [0] keys + sort, [1] heads + scans, [2] reduce + adopt
+ * (0 for a dry run). */
+m2s_status m2s_last_merge_counts(const m2s_ctx* ctx, uint64_t out[4]);
+m2s_status m2s_last_merge_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* The map of the last merge that was not a dry run: a uint32 per record of the order before it, the index of its parent in the order
+ * after it.  Valid until the records change again (NULL / M2S_ERR_STATE then); the maps of a chain of merges compose into a hierarchy.
+ * m2s_download_merge_map: *out_n (may be NULL) = its entries; dst NULL with capacity 0 only asks for that; M2S_ERR_CAPACITY for a
+ * smaller destination. */
+const void* m2s_device_merge_map(const m2s_ctx* ctx);
+m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
+
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */
 typedef struct m2s_light_params {

@@ -53,6 +53,7 @@ EXPORTS = (
     "m2s_prune_budget", "m2s_last_budget_counts", "m2s_last_budget_stage_ms", "m2s_upload_contrib",
     "m2s_refit_begin", "m2s_refit_accumulate", "m2s_download_refit", "m2s_upload_refit", "m2s_device_refit", "m2s_refit_apply",
     "m2s_last_refit_stage_ms", "m2s_last_refit_apply_ms",
+    "m2s_merge", "m2s_last_merge_counts", "m2s_last_merge_stage_ms", "m2s_device_merge_map", "m2s_download_merge_map",
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
 )
@@ -277,6 +278,11 @@ def load():
         "m2s_refit_apply": (C.c_int, [vp, vp, C.POINTER(u64)]),
         "m2s_last_refit_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_last_refit_apply_ms": (C.c_float, [vp]),
+        "m2s_merge": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_last_merge_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_last_merge_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_device_merge_map": (vp, [vp]),
+        "m2s_download_merge_map": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
         "m2s_write_ply_compact": (C.c_int, [C.c_char_p, vp, vp, u32, u64, C.c_float, C.POINTER(u64)]),
         "m2s_export_ply_compact": (C.c_int, [vp, C.c_char_p, C.c_float, C.c_int, C.POINTER(u64)]),
         "m2s_last_compact_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

@@ -951,6 +951,70 @@ class Converter:
             return self.prune_budget(int(budget), "views", min_weight, min_pixels)
         return self.prune(min_weight, min_pixels)
 
+    # ---- merge pass (m2s_merge) ----------------------------------------------------------------------------------------------------------
+    def merge(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False) -> dict:
+        """Replace every group of neighbouring records by its moment-matched parent (m2s_merge; the pin is in include/m2s.h): neighbours
+        share a Morton cell of 2^level per axis (level 0..10), a parent takes at most max_group (2..64) members, and a run of members
+        breaks where the third axes of two neighbours have a dot product below min_axis_dot.  The parents become the context's
+        records, in segment order; sorted quads, accumulators and a baked SH plane are invalid.  dry_run: nothing changes, only the
+        counts are produced.  max_group = 4 and min_axis_dot = 0.5 are untuned guesses.
+        -> {"before", "after", "merged": parents of two members or more, "invalid": invalid records carried}."""
+        from . import merge as _mg
+        pc = _mg.to_c(level, max_group, min_axis_dot, dry_run)
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_merge(self._h, C.byref(pc), v))
+        return {name: int(v[k]) for k, name in enumerate(_mg.COUNTS)}
+
+    def merge_count(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5) -> int:
+        """The number of records merge() with these parameters would leave (a dry run)."""
+        return self.merge(level, max_group, min_axis_dot, dry_run=True)["after"]
+
+    def merge_to_budget(self, max_records: int, max_group: int = 4, min_axis_dot: float = 0.5) -> dict:
+        """merge() at the finest level whose dry-run count is <= max_records (the counts are monotone in level: a bisection over
+        0..10; records that fit already are merged at level 0, where only records of one 1 / 1024 cell meet).  Where even level 10
+        leaves more, level 10 is merged and "met" is False.  -> merge()'s counts + {"level", "met"}."""
+        from . import merge as _mg
+        max_records = int(max_records)
+        if max_records < 1:
+            raise ValueError("max_records must be at least 1")
+        lo, hi = 0, _mg.MAX_LEVEL                         # the finest level in [lo, hi] that meets the budget, if hi does
+        met = self.merge_count(hi, max_group, min_axis_dot) <= max_records
+        if met:
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if self.merge_count(mid, max_group, min_axis_dot) <= max_records:
+                    hi = mid
+                else:
+                    lo = mid + 1
+        out = self.merge(hi, max_group, min_axis_dot)
+        out.update(level=hi, met=met)
+        return out
+
+    def last_merge_counts(self) -> dict:
+        from . import merge as _mg
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_last_merge_counts(self._h, v))
+        return {name: int(v[k]) for k, name in enumerate(_mg.COUNTS)}
+
+    def last_merge_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_merge_stage_ms(self._h, ms))
+        return {"keys_sort": float(ms[0]), "heads_scans": float(ms[1]), "reduce": float(ms[2])}
+
+    @property
+    def device_merge_map(self) -> int:
+        return int(self._L.m2s_device_merge_map(self._h) or 0)
+
+    def download_merge_map(self) -> np.ndarray:
+        """uint32 per record of the order before the last merge(): the index of its parent afterwards (m2s_download_merge_map).  Valid
+        until the records change again."""
+        n = C.c_uint64()
+        self._check(self._L.m2s_download_merge_map(self._h, None, 0, C.byref(n)))
+        out = np.empty(int(n.value), np.uint32)
+        if out.size:
+            self._check(self._L.m2s_download_merge_map(self._h, out.ctypes.data, out.size, None))
+        return out
+
     # ---- colour refit (m2s_refit_*) ---------------------------------------------------------------------------------------------------
     def refit_begin(self):
         """Size the four 64-bit accumulators per record (num[3], den) to the context's current records and zero them (m2s_refit_begin)."""

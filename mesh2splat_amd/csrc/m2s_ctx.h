@@ -11,6 +11,7 @@
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
+//   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -230,6 +231,16 @@ struct m2s_ctx {
     float last_refit_stage_ms[3] = { 0, 0, 0 };    // setup + bin, grouping, refit blend (profiling on)
     float last_refit_apply_ms = 0.0f;
     m2s_host::EventSet<2> refit_ev;                // the apply
+    // merge pass (m2s_merge.cpp): flag | run_start | packed (64-bit) | sums (64-bit) | seg_start (7 capacities of words; sized for n + 1), the totals, and the
+    // map of the last merge, valid for (merge_map_of, merge_map_epoch); keys, permutation and the sort's work area are the compact export's
+    m2s_host::DevBuf<uint32_t> d_merge_u32;
+    m2s_host::DevBuf<uint32_t> d_merge_totals;
+    m2s_host::DevBuf<uint32_t> d_merge_map;
+    uint64_t merge_map_n = 0, merge_map_epoch = 0;       // entries (the records before the merge); the records_epoch it leads into
+    const void* merge_map_of = nullptr;
+    uint64_t last_merge_counts[4] = { 0, 0, 0, 0 };
+    float last_merge_stage_ms[3] = { 0, 0, 0 };          // keys + sort, heads + scans, reduce + adopt
+    m2s_host::EventSet<6> merge_ev;                      // keys + sort: 0-2 | segments: 3, 4 | reduce: 4, 5
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each

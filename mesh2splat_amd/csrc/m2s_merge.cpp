@@ -1,0 +1,138 @@
+// m2s_merge.cpp — the merge pass (m2s_merge): host side of m2s_merge.hip.  Order comes from the compact export's helper
+// (compact_keys_and_sort, m2s_compact.hip) in the compact export's own buffers; the parents go into the pool the way m2s_prune's survivors
+// do (through the staging buffer where the sources live there), and what the call does to the context is prune_adopt (m2s_contrib.cpp).
+#include "m2s_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace m2s;
+using namespace m2s_host;
+
+namespace {
+
+bool merge_map_valid(const m2s_ctx* c) {
+    return c->merge_map_of && c->last_records && !c->records_stale && c->merge_map_of == c->last_records && c->merge_map_epoch == c->records_epoch;
+}
+
+}  // namespace
+
+extern "C" {
+
+m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    if (p->level > 10 || p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "level above 10 or max_group outside 2..64");
+    if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
+    if ((p->flags & ~(uint32_t)M2S_MERGE_DRY_RUN) || p->reserved[0] != 0 || p->reserved[1] != 0)
+        return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
+    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    const uint64_t n64 = c->last_stored;
+    if (n64 > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    const uint32_t n = (uint32_t)n64;
+    const bool dry = (p->flags & M2S_MERGE_DRY_RUN) != 0;
+    const uint32_t R = c->last_R;
+    HIPCHK(c, hipSetDevice(c->device));
+    M2S_TRY(c->merge_ev.ensure(c->err));
+    hipEvent_t* ev = c->merge_ev;
+    uint64_t segments = 0, merged = 0, invalid = 0;
+    float ms[3] = { 0, 0, 0 };
+    if (n) {
+        const uint32_t n_waves = compact_waves(n);
+        M2S_TRY(c->d_compact_u32.reserve(c->err, n, 4 * sizeof(uint32_t)));
+        M2S_TRY(c->d_compact_waves.reserve(c->err, (uint64_t)n_waves + 1, 8 * sizeof(uint32_t)));
+        const size_t temp_bytes = std::max(compact_sort_temp_bytes(n), merge_scan_temp_bytes(n));
+        M2S_TRY(c->d_compact_temp.reserve(c->err, temp_bytes, 1));
+        M2S_TRY(c->d_merge_u32.reserve(c->err, (uint64_t)n + 1, 7 * sizeof(uint32_t)));
+        M2S_TRY(c->d_merge_totals.reserve(c->err, kMergeTotalsWords, sizeof(uint32_t)));
+        const uint64_t cap = c->d_compact_u32.cap(), mcap = c->d_merge_u32.cap();
+        uint32_t* const u = c->d_compact_u32.get();
+        uint32_t* const m = c->d_merge_u32.get();
+        uint32_t* const head = c->d_compact_waves.get() + (size_t)n_waves * 8;
+        const uint32_t *keys = u + 2 * cap, *perm = u + 3 * cap;
+        unsigned long long* const packed = reinterpret_cast<unsigned long long*>(m + 2 * mcap);   // (8 mcap bytes in: aligned)
+        unsigned long long* const sums = reinterpret_cast<unsigned long long*>(m + 4 * mcap);
+        uint32_t* const seg_start = m + 6 * mcap;
+        const float4* plane = m2s_positions_ready(c) ? c->d_pos_plane.get() : nullptr;
+        HIPCHK(c, compact_keys_and_sort((const float4*)c->last_records, plane, n, c->d_compact_waves, head, u, u + cap, u + 2 * cap, u + 3 * cap, c->d_compact_temp,
+                                        c->d_compact_temp.cap(), ev, c->stream));
+        HIPCHK(c, hipEventRecord(ev[3], c->stream));
+        HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, p->level, p->max_group, p->min_axis_dot, m, m + mcap, packed, sums, seg_start,
+                                 c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), c->stream));
+        HIPCHK(c, hipEventRecord(ev[4], c->stream));
+        uint32_t h[kMergeTotalsWords] = {}, skipped = 0;
+        HIPCHK(c, hipMemcpyAsync(h, c->d_merge_totals, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&skipped, head + 7, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        segments = h[0];
+        invalid = skipped;
+        merged = h[1];
+        if (segments < 1 || segments > n || invalid > n || merged > segments) return fail(c, M2S_ERR_HIP, "the merge pass's segment count came back inconsistent");
+        HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], ev[2]));
+        HIPCHK(c, hipEventElapsedTime(&ms[1], ev[3], ev[4]));
+        if (!dry) {
+            // The parents go into the pool.  Members that live there already cannot be reduced onto themselves by independent lanes: the
+            // parents go through the staging buffer and are copied back, stream-ordered (as m2s_prune's survivors).
+            const bool in_pool = c->last_records == c->lane[0].records;
+            c->merge_map_of = nullptr;
+            M2S_TRY(c->d_merge_map.reserve(c->err, n, sizeof(uint32_t)));
+            if (in_pool) M2S_TRY(c->d_prune_stage.reserve(c->err, segments * sizeof(m2s_gaussian), 1));
+            const void* src = c->last_records;
+            if (!in_pool) M2S_TRY(ensure_records(c, segments));
+            float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
+            HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, c->stream));
+            if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, segments * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipEventRecord(ev[5], c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipEventElapsedTime(&ms[2], ev[4], ev[5]));
+        }
+    } else if (!dry) {
+        M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->merge_map_of = nullptr;
+    }
+    if (!dry) {
+        prune_adopt(c, segments, R, false);
+        c->refit_active = false;
+        c->sh_valid = false;                    // (a plane of the members is not a plane of their parents: not merged, as m2s_refit_apply)
+        c->merge_map_of = c->last_records;
+        c->merge_map_n = n;
+        c->merge_map_epoch = c->records_epoch;
+    }
+    c->last_merge_counts[0] = n; c->last_merge_counts[1] = segments; c->last_merge_counts[2] = merged; c->last_merge_counts[3] = invalid;
+    std::memcpy(c->last_merge_stage_ms, ms, sizeof(ms));
+    if (out_counts) std::memcpy(out_counts, c->last_merge_counts, sizeof(c->last_merge_counts));
+    return M2S_OK;
+}
+
+m2s_status m2s_last_merge_counts(const m2s_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return M2S_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = c->last_merge_counts[k];
+    return M2S_OK;
+}
+
+m2s_status m2s_last_merge_stage_ms(const m2s_ctx* c, float out_ms[3]) {
+    if (!c || !out_ms) return M2S_ERR_INVALID;
+    std::memcpy(out_ms, c->last_merge_stage_ms, sizeof(c->last_merge_stage_ms));
+    return M2S_OK;
+}
+
+const void* m2s_device_merge_map(const m2s_ctx* c) { return c && merge_map_valid(c) && c->merge_map_n ? c->d_merge_map.get() : nullptr; }
+
+m2s_status m2s_download_merge_map(m2s_ctx* c, uint32_t* dst, uint64_t capacity, uint64_t* out_n) {
+    if (out_n) *out_n = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!merge_map_valid(c)) return fail(c, M2S_ERR_STATE, "no merge map of the current records (m2s_merge; the records changed since)");
+    if (out_n) *out_n = c->merge_map_n;
+    if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
+    if (capacity < c->merge_map_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there were records");
+    if (!c->merge_map_n) return M2S_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_merge_map, c->merge_map_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+}  // extern "C"

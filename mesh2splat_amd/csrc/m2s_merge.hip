@@ -1,0 +1,245 @@
+// m2s_merge.hip — device side of the merge pass (include/m2s.h "merge pass"): neighbouring records are replaced by their
+// moment-matched parent.  Order (validity, box, Morton keys, stable sort) is the compact export's own — compact_keys_and_sort,
+// m2s_compact.hip — and everything behind it is here: the run flags over the sorted sequence, two rocPRIM scans that turn them into
+// segments, and the reduction of every segment into one 96-byte record.  Segmentation is integer logic and exact fp32 (no contraction);
+// the parent is fp64 throughout, one lane per segment walking its members in sorted order: no floating-point atomics, the same bits
+// from run to run.
+#include <rocprim/device/device_scan.hpp>
+
+#include "m2s_compactmath.h"
+#include "m2s_device.h"
+
+#pragma clang fp contract(off)
+
+namespace m2s {
+
+namespace mc = m2s_compact;
+
+// castQuatToMat3's third row (m2s_covmath.h: rot.c[0][2], c[1][2], c[2][2]) of the stored vec4, its own fp32 expressions
+__device__ __forceinline__ void quat_axis3(float4 q, float& a0, float& a1, float& a2) {
+    const float x = q.x, y = q.y, z = q.z, w = q.w;
+    a0 = 2.f * (y * w + x * z);
+    a1 = 2.f * (z * w - x * y);
+    a2 = 1.f - 2.f * (y * y + z * z);
+}
+
+// Pin 2.  flag[j] = j where sorted position j starts a run, else 0 (the inclusive maximum of the flags is every position's run start).
+__global__ void __launch_bounds__(kBlock) k_merge_heads(const float4* __restrict__ rec, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm,
+                                                        uint32_t n, uint32_t shift, float min_axis_dot, uint32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    bool head = j == 0;
+    if (!head) {
+        const uint32_t k1 = keys[j], k0 = keys[j - 1];
+        head = k1 == mc::kInvalidKey || k0 == mc::kInvalidKey || (k1 >> shift) != (k0 >> shift);
+        if (!head) {
+            float a0, a1, a2, b0, b1, b2;
+            quat_axis3(rec[(size_t)perm[j] * 6 + 4], a0, a1, a2);
+            quat_axis3(rec[(size_t)perm[j - 1] * 6 + 4], b0, b1, b2);
+            const float d = ((a0 * b0) + a1 * b1) + a2 * b2;
+            head = !(d >= min_axis_dot);
+        }
+    }
+    flag[j] = head ? j : 0u;
+}
+
+// Pin 3.  Position j starts a segment where it is a whole number of max_group members behind its run's start.  packed[j] = that flag,
+// and in the upper half whether the segment it starts has a second member (the next position starts none): one 64-bit sum then gives
+// the segment ids and counts the segments of two members or more, without an atomic.  Neither half can carry: both sums are <= n < 2^32.
+__global__ void __launch_bounds__(kBlock) k_merge_cuts(const uint32_t* __restrict__ run_start, uint32_t n, uint32_t max_group,
+                                                       unsigned long long* __restrict__ packed) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const bool h = (j - run_start[j]) % max_group == 0u;
+    const bool hn = j + 1 == n || (j + 1 - run_start[j + 1]) % max_group == 0u;
+    packed[j] = (unsigned long long)h | ((unsigned long long)(h && !hn) << 32);
+}
+
+// seg_start[s] = first sorted position of segment s, seg_start[segments] = n; totals = { segments, segments of two members or more }
+__global__ void __launch_bounds__(kBlock) k_merge_starts(const unsigned long long* __restrict__ packed, const unsigned long long* __restrict__ sums, uint32_t n,
+                                                         uint32_t* __restrict__ seg_start, uint32_t* __restrict__ totals) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const unsigned long long in = packed[j], ex = sums[j];
+    const uint32_t h = (uint32_t)in, s = (uint32_t)ex;
+    if (h) seg_start[s] = j;
+    if (j + 1 == n) {
+        seg_start[s + h] = n;
+        totals[0] = s + h;
+        totals[1] = (uint32_t)(ex >> 32) + (uint32_t)(in >> 32);
+    }
+}
+
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
+__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
+__device__ __forceinline__ D3 operator*(double s, D3 a) { return { s * a.x, s * a.y, s * a.z }; }
+__device__ __forceinline__ double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ D3 cross(D3 a, D3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
+__device__ __forceinline__ D3 d3(float4 v) { return { (double)v.x, (double)v.y, (double)v.z }; }
+
+// the three rows of castQuatToMat3 of the stored vec4, in fp64
+__device__ __forceinline__ void quat_rows(float4 q, D3& r1, D3& r2, D3& r3) {
+    const double x = q.x, y = q.y, z = q.z, w = q.w;
+    r1 = { 1.0 - 2.0 * (z * z + w * w), 2.0 * (y * z + x * w), 2.0 * (y * w - x * z) };
+    r2 = { 2.0 * (y * z - x * w), 1.0 - 2.0 * (y * y + w * w), 2.0 * (z * w + x * y) };
+    r3 = { 2.0 * (y * w + x * z), 2.0 * (z * w - x * y), 1.0 - 2.0 * (y * y + z * z) };
+}
+
+// v minus its component along the unit vector nb, normalised; false where less than 1e-6 of its length is left
+__device__ __forceinline__ bool tangent_of(D3 v, D3 nb, D3& t) {
+    const D3 p = v - dot(v, nb) * nb;
+    const double l2 = dot(p, p);
+    if (!(l2 >= 1e-12 * dot(v, v)) || !(l2 > 0.0)) return false;
+    t = (1.0 / sqrt(l2)) * p;
+    return true;
+}
+
+// Pins 4 - 6.  Lane s = segment s: members perm[seg_start[s]] .. perm[seg_start[s + 1] - 1], at most 64.  Two walks: the weights' sum,
+// the centroid and the plane first (the moments are taken about the one and in the other), then everything else.  The second walk finds its records in L2.
+__global__ void __launch_bounds__(kBlock) k_merge_reduce(const float4* __restrict__ rec, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ seg_start,
+                                                         const uint32_t* __restrict__ totals, float4* __restrict__ out, uint32_t* __restrict__ map) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= totals[0]) return;
+    const uint32_t a = seg_start[s], b = seg_start[s + 1];
+    const uint32_t first = perm[a];
+    const float4* g1 = rec + (size_t)first * 6;
+    float4* o = out + (size_t)s * 6;
+    map[first] = s;
+    if (b - a == 1u) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[k] = g1[k];
+        return;
+    }
+    const float4 pos1 = g1[0], scl1 = g1[2], nrm1 = g1[3], rot1 = g1[4], pbr1 = g1[5];
+    const D3 p1 = d3(pos1);
+    // walk 1: W, the centroid and the plane's normal, for both weightings (the area, and 1 where the areas add up to nothing)
+    double W = 0.0;
+    D3 sw = { 0, 0, 0 }, s1 = { 0, 0, 0 }, nsum = { 0, 0, 0 }, n1 = { 0, 0, 0 };
+    for (uint32_t j = a; j < b; ++j) {
+        const uint32_t i = perm[j];
+        const float4* g = rec + (size_t)i * 6;
+        const float4 scl = g[2];
+        const D3 d = d3(g[0]) - p1;
+        D3 q1, q2, q3;
+        quat_rows(g[4], q1, q2, q3);
+        const double w = (double)scl.x * (double)scl.y;
+        W += w;
+        sw = sw + w * d;
+        s1 = s1 + d;
+        nsum = nsum + w * q3;
+        n1 = n1 + q3;
+        map[i] = s;
+    }
+    const bool unit = W == 0.0;
+    if (unit) { W = (double)(b - a); sw = s1; nsum = n1; }
+    const D3 mu = (1.0 / W) * sw;
+    D3 r1, r2, r3;
+    quat_rows(rot1, r1, r2, r3);
+    double l2 = dot(nsum, nsum);
+    if (!(l2 > 0.0) || !isfinite(l2)) { nsum = r3; l2 = dot(r3, r3); }
+    D3 nb = { 0.0, 0.0, 1.0 };
+    if (l2 > 0.0 && isfinite(l2)) nb = (1.0 / sqrt(l2)) * nsum;
+    D3 t1;
+    if (!tangent_of(r1, nb, t1) && !tangent_of(r2, nb, t1)) t1 = r1;
+    const D3 t2 = cross(nb, t1);
+    // walk 2: the in-plane moments about the centroid, alpha, colour, normal, pbr
+    double ma = 0.0, mb = 0.0, mcc = 0.0, swa = 0.0;
+    D3 cwa = { 0, 0, 0 }, cw = { 0, 0, 0 }, ns = { 0, 0, 0 };
+    double pb0 = 0.0, pb1 = 0.0;
+    for (uint32_t j = a; j < b; ++j) {
+        const float4* g = rec + (size_t)perm[j] * 6;
+        const float4 col = g[1], scl = g[2], nrm = g[3], pbr = g[5];
+        D3 q1, q2, q3;
+        quat_rows(g[4], q1, q2, q3);
+        const double w = unit ? 1.0 : (double)scl.x * (double)scl.y;
+        const double kx = (double)scl.x * (double)scl.x / 12.0, ky = (double)scl.y * (double)scl.y / 12.0;
+        const D3 e = (d3(g[0]) - p1) - mu;
+        const double u1 = dot(t1, q1), u2 = dot(t1, q2), v1 = dot(t2, q1), v2 = dot(t2, q2), du = dot(t1, e), dv = dot(t2, e);
+        ma += w * ((kx * u1 * u1 + ky * u2 * u2) + du * du);
+        mb += w * ((kx * u1 * v1 + ky * u2 * v2) + du * dv);
+        mcc += w * ((kx * v1 * v1 + ky * v2 * v2) + dv * dv);
+        const double wa = w * (double)col.w;
+        swa += wa;
+        cwa = cwa + wa * d3(col);
+        cw = cw + w * d3(col);
+        ns = ns + w * d3(nrm);
+        pb0 += w * (double)pbr.x;
+        pb1 += w * (double)pbr.y;
+    }
+    ma /= W; mb /= W; mcc /= W;
+    const double dd = sqrt((ma - mcc) * (ma - mcc) + 4.0 * mb * mb);
+    const double lam1 = ((ma + mcc) + dd) / 2.0;
+    const double lam2 = fmax(((ma + mcc) - dd) / 2.0, 0.0);
+    D3 e1 = t1;
+    if (dd != 0.0) {
+        double ex = mb, ey = lam1 - ma;
+        const double fx = lam1 - mcc, fy = mb;
+        if (fx * fx + fy * fy > ex * ex + ey * ey) { ex = fx; ey = fy; }
+        const double il = 1.0 / sqrt(ex * ex + ey * ey);
+        e1 = (ex * il) * t1 + (ey * il) * t2;
+    }
+    const D3 e2 = cross(nb, e1);
+    // quat_cast (m2s_devfn.h: geo_flat) of the matrix with columns e1, e2, nb, in fp64; stored (w, x, y, z), first float >= 0
+    double qw, qx, qy, qz;
+    {
+        const double m00 = e1.x, m01 = e1.y, m02 = e1.z, m10 = e2.x, m11 = e2.y, m12 = e2.z, m20 = nb.x, m21 = nb.y, m22 = nb.z;
+        const double fx = m00 - m11 - m22, fy = m11 - m00 - m22, fz = m22 - m00 - m11, fw = m00 + m11 + m22;
+        int bi = 0;
+        double fb = fw;
+        if (fx > fb) { fb = fx; bi = 1; }
+        if (fy > fb) { fb = fy; bi = 2; }
+        if (fz > fb) { fb = fz; bi = 3; }
+        const double bv = sqrt(fb + 1.0) * 0.5, mult = 0.25 / bv;
+        const double d0 = m12 - m21, d1 = m20 - m02, d2 = m01 - m10, s0 = m01 + m10, s1_ = m20 + m02, s2 = m12 + m21;
+        if (bi == 0) { qw = bv; qx = d0 * mult; qy = d1 * mult; qz = d2 * mult; }
+        else if (bi == 1) { qw = d0 * mult; qx = bv; qy = s0 * mult; qz = s1_ * mult; }
+        else if (bi == 2) { qw = d1 * mult; qx = s0 * mult; qy = bv; qz = s2 * mult; }
+        else { qw = d2 * mult; qx = s1_ * mult; qy = s2 * mult; qz = bv; }
+        if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+    }
+    const double nl2 = dot(ns, ns);
+    const bool nok = nl2 > 0.0 && isfinite(nl2);
+    const double ni = nok ? 1.0 / sqrt(nl2) : 0.0;
+    const D3 rgb = swa != 0.0 ? (1.0 / swa) * cwa : (1.0 / W) * cw;
+    o[0] = make_float4((float)(p1.x + mu.x), (float)(p1.y + mu.y), (float)(p1.z + mu.z), pos1.w);
+    o[1] = make_float4((float)rgb.x, (float)rgb.y, (float)rgb.z, (float)(swa / W));
+    o[2] = make_float4((float)sqrt(12.0 * lam1), (float)sqrt(12.0 * lam2), scl1.z, scl1.w);
+    o[3] = nok ? make_float4((float)(ns.x * ni), (float)(ns.y * ni), (float)(ns.z * ni), nrm1.w) : make_float4(0.0f, 0.0f, 0.0f, nrm1.w);
+    o[4] = make_float4((float)qw, (float)qx, (float)qy, (float)qz);
+    o[5] = make_float4((float)(pb0 / W), (float)(pb1 / W), pbr1.z, pbr1.w);
+}
+
+size_t merge_scan_temp_bytes(uint32_t n) {
+    size_t a = 0, b = 0;
+    (void)rocprim::inclusive_scan(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, rocprim::maximum<uint32_t>(), (hipStream_t)0);
+    (void)rocprim::exclusive_scan(nullptr, b, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, (size_t)n,
+                                  rocprim::plus<unsigned long long>(), (hipStream_t)0);
+    return a > b ? a : b;
+}
+
+hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_t* perm, uint32_t n, uint32_t level, uint32_t max_group, float min_axis_dot,
+                          uint32_t* flag, uint32_t* run_start, unsigned long long* packed, unsigned long long* sums, uint32_t* seg_start, uint32_t* totals,
+                          void* temp, size_t temp_bytes, hipStream_t st) {
+    if (!n) return hipErrorInvalidValue;
+    const dim3 grid((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_merge_heads, grid, dim3(kBlock), 0, st, rec, keys, perm, n, 3u * level, min_axis_dot, flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = rocprim::inclusive_scan(temp, temp_bytes, (const uint32_t*)flag, run_start, (size_t)n, rocprim::maximum<uint32_t>(), st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_merge_cuts, grid, dim3(kBlock), 0, st, (const uint32_t*)run_start, n, max_group, packed);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = rocprim::exclusive_scan(temp, temp_bytes, (const unsigned long long*)packed, sums, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), st)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_merge_starts, grid, dim3(kBlock), 0, st, (const unsigned long long*)packed, (const unsigned long long*)sums, n, seg_start, totals);
+    return hipGetLastError();
+}
+
+hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
+                        uint32_t* map, hipStream_t st) {
+    if (!segments) return hipSuccess;
+    hipLaunchKernelGGL(k_merge_reduce, dim3((segments + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
+    return hipGetLastError();
+}
+
+}  // namespace m2s

@@ -1,0 +1,24 @@
+"""The merge pass (`Converter.merge` / `.merge_count` / `.merge_to_budget` / `.download_merge_map`, m2s_merge): the ctypes mirror of its
+parameters.  The pin — runs, segments and the moment-matched parent — is in include/m2s.h.
+
+The defaults max_group = 4 and min_axis_dot = 0.5 are guesses: nothing in the repository has tuned them (tools/merge_probe.py reports
+what they cost on one scene)."""
+from __future__ import annotations
+
+import ctypes as C
+
+DRY_RUN = 1                                                  # M2S_MERGE_DRY_RUN
+MAX_LEVEL = 10
+COUNTS = ("before", "after", "merged", "invalid")            # m2s_merge's out_counts, in order
+
+
+class MergeParamsC(C.Structure):
+    """== m2s_merge_params (include/m2s.h)."""
+    _fields_ = [("level", C.c_uint32), ("max_group", C.c_uint32), ("min_axis_dot", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+def to_c(level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False) -> MergeParamsC:
+    c = MergeParamsC()
+    c.level, c.max_group, c.min_axis_dot, c.flags = int(level), int(max_group), float(min_axis_dot), DRY_RUN if dry_run else 0
+    return c

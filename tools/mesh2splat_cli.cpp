@@ -81,6 +81,11 @@ struct Options {
     std::vector<double> refit_elevations = { -35.0, 0.0, 35.0 };   // --refit-elevations e1,e2,...
     static constexpr uint32_t kRefitMinCover = 128;                // a pixel takes part from this splat alpha on
     static constexpr float kRefitMinWeightSum = 1.0f;              // a record is updated from this much accumulated weight on
+    int merge_level = -1;                                          // --merge-level L (0..10): replace neighbouring Gaussians by their moment-matched parent (m2s_merge); -1: off
+    long long merge_to = 0;                                        // --merge-to N: the same at the finest level that leaves at most N; 0: off
+    int merge_group = 4;                                           // --merge-group g (2..64; 4 and the 0.5 below are guesses nobody has tuned)
+    double merge_dot = 0.5;                                        // --merge-dot d
+    bool merging() const { return merge_level >= 0 || merge_to > 0; }
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
     bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
     long conversion_cap() const { return budget > 0 && !cap_set ? 0 : cap; }
@@ -100,6 +105,7 @@ void usage() {
                  "         [--prune K [--prune-elevations e1,e2,...] [--prune-weight w] [--prune-pixels n] [--prune-count-weight c]]\n"
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
+                 "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -142,7 +148,15 @@ void usage() {
                  "  `refit: {...}` of JSON: iterations, views, size, density, step, sse (the albedo planes' pooled squared error over the pixels\n"
                  "  both cover, before and after every iteration), pixels, and per iteration updated, clamped, no_weight.  Those are the TRAINING\n"
                  "  cameras: --score with other elevations (--score-elevation) is the held-out check.  Not with --gpus N > 1; with --batch the\n"
-                 "  per-file report times it as `refit`.\n");
+                 "  per-file report times it as `refit`.\n"
+                 "--merge-level L (0..10) | --merge-to N (>= 1) [--merge-group g (2..64, default 4)] [--merge-dot d (default 0.5)]: level of detail\n"
+                 "  without holes (m2s_merge): Gaussians that share a Morton cell of 2^L per axis are replaced, at most g at a time, by the\n"
+                 "  moment-matched rectangle of their union; a group ends where two neighbours' normals have a dot product below d.  --merge-to\n"
+                 "  takes the finest level whose count is at most N (dry runs, a bisection; level 10 where none is).  g = 4 and d = 0.5 are untuned\n"
+                 "  guesses.  It runs after --prune / --budget and before --refit (which then corrects the parents' colours), --bake-light,\n"
+                 "  --score, --preview, --compact and the export; the canonical record order is gone afterwards.  Prints ONE line `merge: {...}`\n"
+                 "  of JSON per file: level, max_group, min_axis_dot, target, met, before, after, merged, invalid, stage_ms.  Not with\n"
+                 "  --gpus N > 1.  With --batch the per-file report times it as `merge`.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -505,6 +519,44 @@ int run_budget(m2s_ctx* ctx, uint32_t importance, float min_weight, uint32_t min
     return 0;
 }
 
+// --merge-level L / --merge-to N: m2s_merge over the context's records (Converter.merge / .merge_to_budget do the same); prints one JSON line
+int run_merge(m2s_ctx* ctx, const Options& o) {
+    m2s_merge_params mp = { 0, (uint32_t)o.merge_group, (float)o.merge_dot, 0, { 0, 0 } };
+    uint64_t c[4] = {};
+    bool met = true;
+    if (o.merge_to > 0) {
+        auto count = [&](uint32_t level, uint64_t* after) {
+            m2s_merge_params dry = mp;
+            dry.level = level; dry.flags = M2S_MERGE_DRY_RUN;
+            uint64_t d[4] = {};
+            if (m2s_merge(ctx, &dry, d) != M2S_OK) return false;
+            *after = d[1];
+            return true;
+        };
+        uint32_t lo = 0, hi = 10;                                  // the finest level in [lo, hi] that leaves at most N, if hi does
+        uint64_t after = 0;
+        if (!count(hi, &after)) return 1;
+        met = after <= (uint64_t)o.merge_to;
+        while (met && lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (!count(mid, &after)) return 1;
+            if (after <= (uint64_t)o.merge_to) hi = mid; else lo = mid + 1;
+        }
+        mp.level = hi;
+    } else {
+        mp.level = (uint32_t)o.merge_level;
+    }
+    float ms[3] = {};
+    if (m2s_merge(ctx, &mp, c) != M2S_OK || m2s_last_merge_stage_ms(ctx, ms) != M2S_OK) return 1;
+    char target[32] = "null";
+    if (o.merge_to > 0) std::snprintf(target, sizeof(target), "%lld", o.merge_to);
+    std::printf("merge: {\"level\": %u, \"max_group\": %u, \"min_axis_dot\": %s, \"target\": %s, \"met\": %s, \"before\": %llu, \"after\": %llu, "
+                "\"merged\": %llu, \"invalid\": %llu, \"stage_ms\": [%.4f, %.4f, %.4f]}\n",
+                mp.level, mp.max_group, json_num((double)mp.min_axis_dot).c_str(), target, met ? "true" : "false", (unsigned long long)c[0],
+                (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], ms[0], ms[1], ms[2]);
+    return 0;
+}
+
 // --refit K: K cameras round the scene at each elevation, at --preview-size; per iteration and camera m2s_prepass_sorted -> m2s_splat ->
 // m2s_mesh_render -> m2s_refit_accumulate, then m2s_refit_apply (Converter.refit_views does the same).  Prints one JSON line.
 int run_refit(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
@@ -653,6 +705,7 @@ int convert_one(const Options& o) {
     const auto t3 = Clock::now();
     if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
     if (o.budget > 0 && o.prune_views == 0 && run_budget(ctx, M2S_IMPORTANCE_AREA, 0.0f, 0, o) != 0) return die("budget");
+    if (o.merging() && run_merge(ctx, o) != 0) return die("merge");
     if (o.refit_views > 0 && run_refit(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("refit");
     if (o.bake_light) {
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
@@ -875,7 +928,7 @@ private:
 };
 
 struct Loaded { std::string in, out; m2s_host_scene* scene = nullptr; double load_ms = 0; };
-struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1, refit_ms = -1; };   // budget_ms / refit_ms < 0: no --budget / --refit
+struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1, merge_ms = -1, refit_ms = -1; };   // budget_ms / merge_ms / refit_ms < 0: no --budget / --merge-* / --refit
 
 int batch_on_device(const Options& o, const std::vector<std::pair<std::string, std::string>>& files, int device, int tag) {
     const auto t_begin = Clock::now();
@@ -908,10 +961,12 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
             const double ex = ms_between(a, Clock::now());
             char budget[48] = "";
             if (c.budget_ms >= 0) std::snprintf(budget, sizeof(budget), ", budget %.2f ms", c.budget_ms);
+            char merge[48] = "";
+            if (c.merge_ms >= 0) std::snprintf(merge, sizeof(merge), ", merge %.2f ms", c.merge_ms);
             char refit[48] = "";
             if (c.refit_ms >= 0) std::snprintf(refit, sizeof(refit), ", refit %.2f ms", c.refit_ms);
-            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms%s%s, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
-                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, budget, refit, ex);
+            std::printf("[gpu %d] %s -> %s: %llu Gaussians | load %.1f ms, upload %.1f ms, convert %.2f ms%s%s%s, export %.1f ms\n", tag, c.in.c_str(), c.out.c_str(),
+                        (unsigned long long)c.total, c.load_ms, c.upload_ms, c.convert_ms, budget, merge, refit, ex);
             { std::lock_guard<std::mutex> l(slot_m); slot_busy[c.slot] = false; }
             slot_cv.notify_all();
         }
@@ -933,6 +988,11 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
             a = Clock::now();
             ok = run_budget(ctx[slot], M2S_IMPORTANCE_AREA, 0.0f, 0, o) == 0;
             c.budget_ms = ms_between(a, Clock::now());
+        }
+        if (ok && o.merging()) {
+            a = Clock::now();
+            ok = run_merge(ctx[slot], o) == 0;
+            c.merge_ms = ms_between(a, Clock::now());
         }
         if (ok && o.refit_views > 0) {
             a = Clock::now();
@@ -1013,6 +1073,10 @@ int main(int argc, char** argv) {
         else if (a == "--split-screen") { o.split_screen = std::atof(next()); if (!(o.split_screen >= 0.0 && o.split_screen <= 1.0)) { usage(); return 2; } }
         else if (a == "--preview-mode") { o.preview_mode = std::atoi(next()); o.preview_mode_set = true; if (o.preview_mode < 0 || o.preview_mode > 6) { usage(); return 2; } }
         else if (a == "--score") { o.score_views = std::atoi(next()); if (o.score_views < 1 || o.score_views > 4096) { usage(); return 2; } }
+        else if (a == "--merge-level") { o.merge_level = std::atoi(next()); if (o.merge_level < 0 || o.merge_level > 10) { usage(); return 2; } }
+        else if (a == "--merge-to") { o.merge_to = std::atoll(next()); if (o.merge_to < 1) { usage(); return 2; } }
+        else if (a == "--merge-group") { o.merge_group = std::atoi(next()); if (o.merge_group < 2 || o.merge_group > 64) { usage(); return 2; } }
+        else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
         else if (a == "--prune") { o.prune_views = std::atoi(next()); if (o.prune_views < 1 || o.prune_views > 4096) { usage(); return 2; } }
         else if (a == "--refit") { o.refit_views = std::atoi(next()); if (o.refit_views < 1 || o.refit_views > 4096) { usage(); return 2; } }
         else if (a == "--refit-iters") { o.refit_iters = std::atoi(next()); if (o.refit_iters < 1 || o.refit_iters > 64) { usage(); return 2; } }
@@ -1058,6 +1122,7 @@ int main(int argc, char** argv) {
     // --bake-light writes the standard layout only, from the one context that holds the records, the cube and the plane
     if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
     if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
+    if (o.merging() && (o.gpus > 1 || o.force_sharded || (o.merge_level >= 0 && o.merge_to > 0))) { usage(); return 2; }   // (multi-rank merges: out of scope)
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
