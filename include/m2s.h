@@ -640,6 +640,92 @@ m2s_status m2s_last_merge_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
 const void* m2s_device_merge_map(const m2s_ctx* ctx);
 m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
 
+/* ---- level-of-detail tree and its per-camera cut (no counterpart in the reference, which draws every Gaussian it converted) ------- */
+/* m2s_lod_build keeps a chain of m2s_merge steps resident and linked; m2s_lod_select takes a cut through it for one camera: each part
+ * of the surface exactly once, as coarse as the camera allows.  Integer logic and exact fp32 throughout: reproducible bit for bit
+ * (tests/lod_ref.py restates it).  The tree, pinned:
+ *  1. Leaves.  The context's current records are the leaves, tree level 0, copied in their own order into a node pool the tree owns.
+ *  2. Steps.  Step s = 0 .. n_steps-1 runs m2s_merge's own code with (levels[s], max_group, min_axis_dot) on what the previous step
+ *     left.  Its parents are appended to the pool as the next tree level, in segment order; for a node i of the level below,
+ *     parent[i] = first[next] + map[i - first[this]] with map the merge's map.  Nodes of the last level have M2S_LOD_NO_PARENT.
+ *  3. A step that merges nothing — its merge would leave as many records as it found — is not applied (as M2S_MERGE_DRY_RUN): it adds
+ *     no level, is counted, and the records stay in the order of the level below.  (Applied, it would only permute them: the stable
+ *     sort of the next step arrives at the same sequence either way, so the levels above are the same bytes.)
+ *  4. Bounds.  Every node also has a 16-byte entry (x, y, z, e): position[0..2] and e = fmaxf(fabsf(scale[0]), fabsf(scale[1])), the
+ *     longer edge of the flat footprint m2s_merge reads a record as.  The cut reads this plane, never the 96-byte records.
+ *  5. Afterwards.  Where a step merged, the context's current records are the last level — what the chain left, in the context-owned
+ *     pool — with everything m2s_merge invalidates invalid; where none did they are untouched.  The tree is a copy: it stays valid until
+ *     the next m2s_lod_build (one refused for its arguments or the context's state leaves it; one that fails later leaves no tree),
+ *     m2s_lod_release or m2s_destroy, whatever happens to the current records.  The resolutionTarget of the leaves is remembered.
+ *     m2s_last_merge_counts reports the last step.  Scales are read as stored, as by m2s_merge: a conversion's are in units the
+ *     viewer divides by the resolutionTarget (Limits).
+ *  6. out_counts (may be NULL): [0] leaves, [1] nodes, [2] tree levels (the leaves included), [3] steps that added no level.
+ * Synchronous.  M2S_ERR_INVALID: n_steps outside 1..16, a level above 10, levels that decrease, a level past n_steps that is not 0,
+ * max_group outside 2..64, a NaN min_axis_dot, reserved != 0.  M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY:
+ * 2^32 - 1 nodes or more.  Zero records build an empty tree of one level. */
+#define M2S_LOD_MAX_STEPS 16
+#define M2S_LOD_NO_PARENT 0xFFFFFFFFu
+typedef struct m2s_lod_build_params {
+    uint32_t n_steps;                    /* 1..16 */
+    uint32_t levels[M2S_LOD_MAX_STEPS];  /* merge level of step s: 0..10, non-decreasing; entries past n_steps are 0 */
+    uint32_t max_group;                  /* 2..64, as m2s_merge */
+    float    min_axis_dot;               /* as m2s_merge; NaN refused */
+    uint32_t reserved;                   /* 0 */
+} m2s_lod_build_params;                  /* 80 bytes */
+m2s_status m2s_lod_build(m2s_ctx* ctx, const m2s_lod_build_params* params, uint64_t out_counts[4]);
+/* The tree's levels: first[l] is the first node of level l = 0 .. *out_levels - 1, first[*out_levels] and every entry behind it the
+ * node count (either pointer may be NULL).  M2S_ERR_STATE without a tree. */
+m2s_status m2s_lod_levels(const m2s_ctx* ctx, uint32_t* out_levels, uint64_t first[M2S_LOD_MAX_STEPS + 2]);
+/* which = 0: the node records (96 bytes each), 1: parent, a uint32 per node, 2: the bounds, a float4 per node.  m2s_device_lod: NULL
+ * without a tree, for an empty one and for another `which`.  m2s_download_lod: M2S_ERR_STATE without a tree, M2S_ERR_CAPACITY for a
+ * destination of fewer bytes than the plane. */
+const void* m2s_device_lod(const m2s_ctx* ctx, uint32_t which);
+m2s_status m2s_download_lod(m2s_ctx* ctx, uint32_t which, void* dst, uint64_t capacity_bytes);
+/* Frees the tree (M2S_OK without one too).  The current records are not touched. */
+m2s_status m2s_lod_release(m2s_ctx* ctx);
+/* Duration (ms) of the last m2s_lod_build, its merges and host round trips included. */
+float m2s_last_lod_build_ms(const m2s_ctx* ctx);
+
+/* The cut, pinned:
+ *  1. Per node, all in fp32, one rounding per operation, no contraction, no division, no root, with (cx, cy, cz) = camera_position:
+ *       dx = x - cx, dy = y - cy, dz = z - cz;  d2 = fmaxf((dx*dx + dy*dy) + dz*dz, near*near);  s = e * focal_px;
+ *       refine = (s * s > (tau_px * tau_px) * d2).
+ *     The comparison is false for any NaN; equality does not refine; fmaxf returns its other operand for a NaN (a node whose position
+ *     is NaN is taken to be `near` away).  The distance is to the camera POSITION, not the view depth: turning the camera changes no
+ *     cut, and nodes behind it are not refined to the leaves.
+ *  2. A node is selected iff it is a leaf or does not refine, and every proper ancestor refines.  Walking from a node of the last level
+ *     towards any leaf, the first node that is a leaf or does not refine is the selected one: every leaf has exactly one selected
+ *     ancestor-or-self, whatever the sizes do along the chain — no holes, nothing drawn twice.  Invalid records, which m2s_merge
+ *     carries through every level as byte-identical singletons, come out once.
+ *  3. Output: the stable compaction of the selected nodes, in node-index order (the leaves in their own order, then level 1, ...),
+ *     into the context-owned pool.  They become the context's current records at the leaves' resolutionTarget; the records epoch
+ *     advances, everything m2s_prune invalidates is invalid, and a baked SH plane is dropped.  Memory adopted through m2s_set_records
+ *     is not written.  The tree is not changed.
+ *  4. out_counts (may be NULL): [0] nodes, [1] selected, [2] selected leaves, [3] nodes with `refine` (whatever their ancestors do).
+ *     Integer sums, identical from run to run.
+ *  5. With M2S_LOD_DRY_RUN only the counts are produced: nothing of the context changes.
+ * Synchronous.  M2S_ERR_INVALID: a camera position, focal_px, tau_px or near that is not finite, focal_px <= 0, tau_px < 0, near <= 0,
+ * unknown flag bits, reserved != 0.  M2S_ERR_STATE: no tree, or conversions in flight.  No frustum culling here: m2s_prepass does it. */
+enum { M2S_LOD_DRY_RUN = 1 };
+typedef struct m2s_lod_select_params {
+    float    camera_position[3];  /* world space, finite */
+    float    focal_px;            /* view_to_clip[5] * H / 2; finite, > 0 */
+    float    tau_px;              /* finite, >= 0: the longer edge of a drawn node projects to at most this many pixels */
+    float    near;                /* finite, > 0: distances below it count as it */
+    uint32_t flags;               /* M2S_LOD_DRY_RUN; other bits 0 */
+    uint32_t reserved;            /* 0 */
+} m2s_lod_select_params;          /* 32 bytes */
+m2s_status m2s_lod_select(m2s_ctx* ctx, const m2s_lod_select_params* params, uint64_t out_counts[4]);
+/* The selected nodes per tree level of the last m2s_lod_select (a dry run included; levels the tree does not have: 0), and the stages
+ * (ms) of the last profiled one: [0] the sweep over the levels, [1] scan + node indices, [2] compaction (the round trip of the counts
+ * included); [1] and [2] are 0 for a dry run. */
+m2s_status m2s_last_lod_level_counts(const m2s_ctx* ctx, uint64_t out[M2S_LOD_MAX_STEPS + 1]);
+m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* The node index of every record the last m2s_lod_select that was not a dry run left, a uint32 each, in their order.  Valid until the
+ * records change again (NULL / M2S_ERR_STATE then).  m2s_download_lod_nodes: as m2s_download_merge_map. */
+const void* m2s_device_lod_nodes(const m2s_ctx* ctx);
+m2s_status m2s_download_lod_nodes(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
+
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */
 typedef struct m2s_light_params {

@@ -54,6 +54,8 @@ EXPORTS = (
     "m2s_refit_begin", "m2s_refit_accumulate", "m2s_download_refit", "m2s_upload_refit", "m2s_device_refit", "m2s_refit_apply",
     "m2s_last_refit_stage_ms", "m2s_last_refit_apply_ms",
     "m2s_merge", "m2s_last_merge_counts", "m2s_last_merge_stage_ms", "m2s_device_merge_map", "m2s_download_merge_map",
+    "m2s_lod_build", "m2s_lod_levels", "m2s_device_lod", "m2s_download_lod", "m2s_lod_release", "m2s_last_lod_build_ms", "m2s_lod_select",
+    "m2s_last_lod_level_counts", "m2s_last_lod_select_stage_ms", "m2s_device_lod_nodes", "m2s_download_lod_nodes",
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
 )
@@ -283,6 +285,17 @@ def load():
         "m2s_last_merge_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_device_merge_map": (vp, [vp]),
         "m2s_download_merge_map": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
+        "m2s_lod_build": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_lod_levels": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u64)]),
+        "m2s_device_lod": (vp, [vp, u32]),
+        "m2s_download_lod": (C.c_int, [vp, u32, vp, u64]),
+        "m2s_lod_release": (C.c_int, [vp]),
+        "m2s_last_lod_build_ms": (C.c_float, [vp]),
+        "m2s_lod_select": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_last_lod_level_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_last_lod_select_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "m2s_device_lod_nodes": (vp, [vp]),
+        "m2s_download_lod_nodes": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
         "m2s_write_ply_compact": (C.c_int, [C.c_char_p, vp, vp, u32, u64, C.c_float, C.POINTER(u64)]),
         "m2s_export_ply_compact": (C.c_int, [vp, C.c_char_p, C.c_float, C.c_int, C.POINTER(u64)]),
         "m2s_last_compact_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

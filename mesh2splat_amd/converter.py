@@ -1015,6 +1015,89 @@ class Converter:
             self._check(self._L.m2s_download_merge_map(self._h, out.ctypes.data, out.size, None))
         return out
 
+    # ---- level-of-detail tree and its cut (m2s_lod_*) ------------------------------------------------------------------------------------
+    def lod_build(self, levels=(1, 2, 3, 4, 5, 6, 7, 8), max_group: int = 4, min_axis_dot: float = 0.5) -> dict:
+        """Build the resident level-of-detail tree over the context's current records (m2s_lod_build; the pin is in include/m2s.h): they
+        are the leaves, and step s merges what the previous step left at merge level levels[s] (0..10, non-decreasing, at most 16) with
+        merge()'s max_group and min_axis_dot; every step that merges something adds a tree level.  The coarsest level is the context's
+        records afterwards; the tree is a copy and outlives them.  The default chain is an untuned guess, like max_group and min_axis_dot.
+        -> {"leaves", "nodes", "levels": tree levels, the leaves included, "skipped": steps that merged nothing, "first": first node of
+        every level and the node count behind them}."""
+        from . import lod as _ld
+        pc = _ld.build_to_c(levels, max_group, min_axis_dot)
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_lod_build(self._h, C.byref(pc), v))
+        out = {name: int(v[k]) for k, name in enumerate(_ld.BUILD_COUNTS)}
+        out["first"] = self.lod_levels()
+        return out
+
+    def lod_levels(self) -> list:
+        """First node of every tree level, then the node count: len() - 1 levels (m2s_lod_levels)."""
+        from . import lod as _ld
+        n = C.c_uint32()
+        first = (C.c_uint64 * (_ld.MAX_STEPS + 2))()
+        st = self._L.m2s_lod_levels(self._h, C.byref(n), first)
+        if st:
+            raise _lib.M2SError(st, "no level-of-detail tree (lod_build)")
+        return [int(first[k]) for k in range(n.value + 1)]
+
+    def lod_select(self, camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False) -> dict:
+        """Take the cut through the tree for a camera at `camera_position` (world space) whose projection has `focal_px` pixels per unit
+        of tan(angle) (mesh2splat_amd.lod.focal_px, .camera_position): walking down from the coarsest level, a node is drawn as soon as
+        its longer edge projects to at most tau_px pixels at its distance from the camera (at least `near`), or it is a leaf
+        (m2s_lod_select; the pin is in include/m2s.h).  Every leaf is covered exactly once.  The selected nodes become the context's
+        records, in node order; sorted quads, accumulators and a baked SH plane are invalid.  dry_run: only the counts.
+        -> {"nodes", "selected", "selected_leaves", "refine", "per_level": selected nodes of every tree level}."""
+        from . import lod as _ld
+        pc = _ld.select_to_c(camera_position, focal_px, tau_px, near, dry_run)
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_lod_select(self._h, C.byref(pc), v))
+        out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
+        per = (C.c_uint64 * (_ld.MAX_STEPS + 1))()
+        self._check(self._L.m2s_last_lod_level_counts(self._h, per))
+        out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
+        return out
+
+    def download_lod(self, which: int) -> np.ndarray:
+        """A plane of the tree (m2s_download_lod): 0 the node records (nodes, 24) float32, 1 parent (nodes,) uint32 with 0xFFFFFFFF on the
+        last level, 2 the bounds (nodes, 4) float32: position and longer edge."""
+        from . import lod as _ld
+        dtype, row = _ld.PLANES[int(which)]
+        nodes = self.lod_levels()[-1]
+        out = np.empty((nodes, row) if row else (nodes,), dtype)
+        self._check(self._L.m2s_download_lod(self._h, int(which), out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def device_lod(self, which: int) -> int:
+        return int(self._L.m2s_device_lod(self._h, int(which)) or 0)
+
+    @property
+    def device_lod_nodes(self) -> int:
+        return int(self._L.m2s_device_lod_nodes(self._h) or 0)
+
+    def download_lod_nodes(self) -> np.ndarray:
+        """uint32 per record the last lod_select() left: its node index in the tree (m2s_download_lod_nodes).  Valid until the records
+        change again."""
+        n = C.c_uint64()
+        self._check(self._L.m2s_download_lod_nodes(self._h, None, 0, C.byref(n)))
+        out = np.empty(int(n.value), np.uint32)
+        if out.size:
+            self._check(self._L.m2s_download_lod_nodes(self._h, out.ctypes.data, out.size, None))
+        return out
+
+    def lod_release(self):
+        """Free the tree (m2s_lod_release); the context's records stay."""
+        self._check(self._L.m2s_lod_release(self._h))
+
+    @property
+    def last_lod_build_ms(self) -> float:
+        return float(self._L.m2s_last_lod_build_ms(self._h))
+
+    def last_lod_select_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_lod_select_stage_ms(self._h, ms))
+        return {"sweep": float(ms[0]), "scan_ids": float(ms[1]), "compact": float(ms[2])}
+
     # ---- colour refit (m2s_refit_*) ---------------------------------------------------------------------------------------------------
     def refit_begin(self):
         """Size the four 64-bit accumulators per record (num[3], den) to the context's current records and zero them (m2s_refit_begin)."""

@@ -21,17 +21,17 @@ bool prune_sh_plane(const m2s_ctx* c, uint64_t n) {
     return c->sh_valid && c->sh_of == c->last_records && c->sh_epoch == c->records_epoch && c->sh_n == n;
 }
 
-m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh) {
+m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh, const void* src) {
     if (!n) {
         if (!c->lane[0].records || c->last_records != c->lane[0].records) return ensure_records(c, 1);
         return M2S_OK;
     }
     // The survivors go into the pool.  Records that live there already (or a plane compacted in place) cannot be compacted onto
     // themselves by independent lanes: they go through a staging buffer and are copied back, stream-ordered.
-    const bool in_pool = c->last_records == c->lane[0].records;
+    const bool in_pool = !src && c->last_records == c->lane[0].records;
     const uint64_t stage_bytes = std::max<uint64_t>(in_pool ? kept * sizeof(m2s_gaussian) : 0, sh ? kept * 48 * sizeof(float) : 0);
     if (stage_bytes) M2S_TRY(c->d_prune_stage.reserve(c->err, stage_bytes, 1));
-    const void* src = c->last_records;
+    if (!src) src = c->last_records;
     if (!in_pool) if (m2s_status s = ensure_records(c, std::max<uint64_t>(kept, 1))) return s;
     if (kept) {
         float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();

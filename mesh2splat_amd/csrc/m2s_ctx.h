@@ -12,6 +12,7 @@
 //   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
+//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select): a chain of merges kept and linked
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -241,6 +242,27 @@ struct m2s_ctx {
     uint64_t last_merge_counts[4] = { 0, 0, 0, 0 };
     float last_merge_stage_ms[3] = { 0, 0, 0 };          // keys + sort, heads + scans, reduce + adopt
     m2s_host::EventSet<6> merge_ev;                      // keys + sort: 0-2 | segments: 3, 4 | reduce: 4, 5
+    // level-of-detail tree (m2s_lod.cpp): the node pool (leaves, then every level a merging step added), a parent word and a 16-byte
+    // bound (x, y, z, longer edge) per node, one capacity of nodes each, grown together with their contents kept; lod_levels == 0: no tree
+    m2s_host::DevBuf<float4> d_lod_nodes;                // capacity in records
+    m2s_host::DevBuf<uint32_t> d_lod_parent;
+    m2s_host::DevBuf<float4> d_lod_bounds;
+    uint32_t lod_levels = 0;
+    uint64_t lod_first[M2S_LOD_MAX_STEPS + 2] = {};      // first node of every level; [lod_levels] = the nodes
+    uint32_t lod_R = 0;                                  // resolutionTarget of the leaves
+    float last_lod_build_ms = 0.0f;
+    m2s_host::EventSet<2> lod_build_ev;
+    // the cut (m2s_lod_select): a byte per node (every ancestor-or-self refines), the selected counts per level and the refining nodes
+    // behind them, the node index of every output record, valid for (lod_ids_of, lod_ids_epoch); flags, offsets and the scan area are m2s_prune's
+    m2s_host::DevBuf<uint8_t> d_lod_open;
+    m2s_host::DevBuf<uint32_t> d_lod_counts;             // kLodCountWords
+    m2s_host::DevBuf<uint32_t> d_lod_ids;
+    uint64_t lod_ids_n = 0, lod_ids_epoch = 0;
+    const void* lod_ids_of = nullptr;
+    uint64_t last_lod_select_counts[4] = { 0, 0, 0, 0 };
+    uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
+    float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
+    m2s_host::EventSet<4> lod_ev;
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each
@@ -396,8 +418,15 @@ bool contrib_valid(const m2s_ctx* c);   // the accumulators belong to the contex
 // point at.  prune_adopt, once the stream has drained: they are the context's current records at resolutionTarget R, and everything
 // derived from the old ones is invalid.
 bool prune_sh_plane(const m2s_ctx* c, uint64_t n);   // a baked plane of exactly these records exists
-m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh);
+// src (m2s_lod_select): the n records are these, in memory that is not the pool, instead of the current ones; no plane then.
+m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh,
+                                 const void* src = nullptr);
 void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh);
+// m2s_merge.cpp
+// What m2s_merge does behind its argument checks (level 0..10, max_group 2..64, no NaN), m2s_lod_build once per step; the counts are
+// left in last_merge_counts.  Dry: only the counts; IfAny: as Dry where no segment has two members, as Apply otherwise.
+enum class MergeMode { Apply, Dry, IfAny };
+m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode);
 // m2s_meshdepth.cpp
 // What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
 // tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);

@@ -36,6 +36,11 @@ public:
         p_ = nullptr;
         cap_ = 0;
     }
+    // Trade places with another buffer: how a caller grows one whose contents it has copied over (m2s_lod.cpp).
+    void swap(DevBuf& o) {
+        T* const p = p_; p_ = o.p_; o.p_ = p;
+        const uint64_t c = cap_; cap_ = o.cap_; o.cap_ = c;
+    }
     // Room for `want` units of `unit` bytes: kept when large enough, else freed and allocated anew (contents lost; at least 256 bytes).
     // *fresh: this call allocated.  On failure the buffer is empty, so the next call starts clean.
     m2s_status reserve(std::string& err, uint64_t want, size_t unit, bool* fresh = nullptr) {

@@ -324,6 +324,23 @@ hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_
 hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
                         uint32_t* map, hipStream_t st);
 
+// ---- level-of-detail tree and its cut (m2s_lod.hip) ------------------------------------------------------------------------------------
+// k_lod_link.  parent[t] = offset + map[t] for t < n_map (map NULL: M2S_LOD_NO_PARENT, the last level); bounds[t] = (position.xyz,
+// fmaxf(|scale[0]|, |scale[1]|)) of rec[t] for t < n_rec.  parent, rec and bounds point at the first node they concern.
+hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32_t* parent, const float4* rec, uint32_t n_rec, float4* bounds,
+                    hipStream_t st);
+struct LodSelectK { float cx, cy, cz, focal, tau2, near2; };
+constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine
+constexpr uint32_t kLodCountWords = 18;
+// The sweep, one launch per level from the last to the leaves: per node of [first[l], first[l + 1]) the pinned comparison,
+// open[i] = refine && open[parent[i]] (levels above the leaves), flags[i] = selected; counts (zeroed by the caller) as above.
+hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
+                     uint32_t* flags, uint32_t* counts, hipStream_t st);
+// ids[offsets[i]] = i where flags[i] is set
+hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t* ids, hipStream_t st);
+// offsets = exclusive scan of flags (n words each); temp: prune_scan_temp_bytes(n)
+hipError_t lod_scan(const uint32_t* flags, uint32_t* offsets, uint32_t n, void* temp, size_t temp_bytes, hipStream_t st);
+
 // ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
 struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads
 struct RelightK {                              // uniforms of gaussianSplattingDeferredPS.glsl

@@ -1,0 +1,247 @@
+// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select): host side of m2s_lod.hip.  The tree is
+// a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are copied into a node pool and linked by their maps; the
+// cut's flags and offsets live where m2s_prune leaves its own, and the compaction and what follows it are m2s_prune's (m2s_contrib.cpp:
+// prune_compact_enqueue, prune_adopt).
+#include "m2s_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace m2s;
+using namespace m2s_host;
+
+namespace {
+
+constexpr uint64_t kLodMaxNodes = 0xFFFFFFFFull;   // fewer than this: M2S_LOD_NO_PARENT is no node
+
+bool lod_ids_valid(const m2s_ctx* c) {
+    return c->lod_ids_of && c->last_records && !c->records_stale && c->lod_ids_of == c->last_records && c->lod_ids_epoch == c->records_epoch;
+}
+
+// Room for `want` nodes in the three planes of the tree, the first `keep` nodes kept where they have to move.
+m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
+    if (c->d_lod_nodes.cap() >= want && c->d_lod_nodes) return M2S_OK;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, 2 * c->d_lod_nodes.cap()), 1);
+    DevBuf<float4> nodes, bounds;
+    DevBuf<uint32_t> parent;
+    M2S_TRY(nodes.reserve(c->err, cap, sizeof(m2s_gaussian)));
+    M2S_TRY(parent.reserve(c->err, cap, sizeof(uint32_t)));
+    M2S_TRY(bounds.reserve(c->err, cap, sizeof(float4)));
+    if (keep) {
+        HIPCHK(c, hipMemcpyAsync(nodes, c->d_lod_nodes, keep * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(parent, c->d_lod_parent, keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bounds, c->d_lod_bounds, keep * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->d_lod_nodes.swap(nodes);
+    c->d_lod_parent.swap(parent);
+    c->d_lod_bounds.swap(bounds);
+    return M2S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    if (p->n_steps < 1 || p->n_steps > M2S_LOD_MAX_STEPS) return fail(c, M2S_ERR_INVALID, "n_steps outside 1..16");
+    for (uint32_t s = 0; s < M2S_LOD_MAX_STEPS; ++s) {
+        if (s >= p->n_steps ? p->levels[s] != 0 : p->levels[s] > 10) return fail(c, M2S_ERR_INVALID, "a level above 10, or a level past n_steps that is not 0");
+        if (s && s < p->n_steps && p->levels[s] < p->levels[s - 1]) return fail(c, M2S_ERR_INVALID, "the levels decrease");
+    }
+    if (p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "max_group outside 2..64");
+    if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
+    if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
+    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    const uint64_t n0 = c->last_stored;
+    if (n0 >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
+    const uint32_t R = c->last_R;
+    HIPCHK(c, hipSetDevice(c->device));
+    M2S_TRY(c->lod_build_ev.ensure(c->err));
+    c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
+    HIPCHK(c, hipEventRecord(c->lod_build_ev[0], c->stream));
+    M2S_TRY(lod_reserve(c, n0 + n0 / 2, 0));
+    uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
+    uint32_t levels = 1;
+    uint64_t skipped = 0;
+    first[1] = n0;
+    if (n0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_lod_nodes, c->last_records, n0 * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, c->d_lod_nodes, (uint32_t)n0, c->d_lod_bounds, c->stream));
+    }
+    for (uint32_t s = 0; s < p->n_steps; ++s) {
+        const uint64_t below = first[levels - 1], cnt = first[levels] - below;
+        M2S_TRY(merge_run(c, p->levels[s], p->max_group, p->min_axis_dot, MergeMode::IfAny));
+        const uint64_t after = c->last_merge_counts[1];
+        if (after == cnt) { ++skipped; continue; }                      // (nothing merged and nothing changed: no level)
+        const uint64_t total = first[levels] + after;
+        if (total >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
+        M2S_TRY(lod_reserve(c, total, first[levels]));
+        float4* const level = c->d_lod_nodes + 6 * first[levels];
+        HIPCHK(c, hipMemcpyAsync(level, c->last_records, after * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, lod_link(c->d_merge_map, (uint32_t)cnt, (uint32_t)first[levels], c->d_lod_parent + below, level, (uint32_t)after,
+                           c->d_lod_bounds + first[levels], c->stream));
+        first[++levels] = total;                                        // (the next step rewrites the map and the pool behind these, stream-ordered)
+    }
+    HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, c->d_lod_parent + first[levels - 1], nullptr, 0, nullptr, c->stream));
+    HIPCHK(c, hipEventRecord(c->lod_build_ev[1], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->last_lod_build_ms, c->lod_build_ev[0], c->lod_build_ev[1]));
+    for (uint32_t l = 0; l < M2S_LOD_MAX_STEPS + 2; ++l) c->lod_first[l] = first[std::min(l, levels)];
+    c->lod_levels = levels;
+    c->lod_R = R;
+    if (out_counts) { out_counts[0] = n0; out_counts[1] = first[levels]; out_counts[2] = levels; out_counts[3] = skipped; }
+    return M2S_OK;
+}
+
+m2s_status m2s_lod_levels(const m2s_ctx* c, uint32_t* out_levels, uint64_t first[M2S_LOD_MAX_STEPS + 2]) {
+    if (out_levels) *out_levels = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!c->lod_levels) return M2S_ERR_STATE;
+    if (out_levels) *out_levels = c->lod_levels;
+    if (first) std::memcpy(first, c->lod_first, sizeof(c->lod_first));
+    return M2S_OK;
+}
+
+const void* m2s_device_lod(const m2s_ctx* c, uint32_t which) {
+    if (!c || !c->lod_levels || which > 2 || !c->lod_first[c->lod_levels]) return nullptr;
+    return which == 0 ? (const void*)c->d_lod_nodes.get() : which == 1 ? (const void*)c->d_lod_parent.get() : (const void*)c->d_lod_bounds.get();
+}
+
+m2s_status m2s_download_lod(m2s_ctx* c, uint32_t which, void* dst, uint64_t capacity_bytes) {
+    if (!c) return M2S_ERR_INVALID;
+    if (which > 2) return fail(c, M2S_ERR_INVALID, "which outside 0..2");
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    const uint64_t bytes = c->lod_first[c->lod_levels] * (which == 0 ? sizeof(m2s_gaussian) : which == 1 ? sizeof(uint32_t) : sizeof(float4));
+    if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer bytes than the plane");
+    if (!bytes) return M2S_OK;
+    if (!dst) return fail(c, M2S_ERR_INVALID, "no destination");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, m2s_device_lod(c, which), bytes, hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+m2s_status m2s_lod_release(m2s_ctx* c) {
+    if (!c) return M2S_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->lod_levels = 0;
+    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release();
+    return M2S_OK;
+}
+
+float m2s_last_lod_build_ms(const m2s_ctx* c) { return c ? c->last_lod_build_ms : 0.0f; }
+
+m2s_status m2s_lod_select(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
+    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    if ((p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
+    const bool prof = c->profiling;
+    const uint32_t levels = c->lod_levels;
+    const uint64_t N = c->lod_first[levels];
+    HIPCHK(c, hipSetDevice(c->device));
+    if (prof) M2S_TRY(c->lod_ev.ensure(c->err));
+    uint32_t h[kLodCountWords] = {};
+    uint64_t selected = 0;
+    if (N) {
+        M2S_TRY(c->d_lod_open.reserve(c->err, N, 1));
+        M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+        M2S_TRY(c->d_prune_u32.reserve(c->err, N, 2 * sizeof(uint32_t)));
+        if (!dry) {
+            M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)N), 16) + 2 * sizeof(unsigned long long), 1));
+            M2S_TRY(c->d_lod_ids.reserve(c->err, N, sizeof(uint32_t)));
+            c->lod_ids_of = nullptr;
+        }
+        uint32_t* const flags = c->d_prune_u32;
+        uint32_t* const offsets = flags + c->d_prune_u32.cap();
+        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[0], c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[1], c->stream));
+        if (!dry) {
+            HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
+            HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->d_lod_ids, c->stream));
+            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[2], c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t l = 0; l < levels; ++l) selected += h[l];
+        if (selected < 1 || selected > N || h[kLodRefineWord] > N) return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
+        if (!dry) {
+            M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
+            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[3], c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (prof) {
+            float* ms = c->last_lod_select_stage_ms;
+            ms[1] = ms[2] = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_ev[0], c->lod_ev[1]));
+            if (!dry) {
+                HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_ev[1], c->lod_ev[2]));
+                HIPCHK(c, hipEventElapsedTime(&ms[2], c->lod_ev[2], c->lod_ev[3]));   // (the round trip of the counts included)
+            }
+        }
+    } else {
+        if (!dry) {
+            c->lod_ids_of = nullptr;
+            M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (prof) c->last_lod_select_stage_ms[0] = c->last_lod_select_stage_ms[1] = c->last_lod_select_stage_ms[2] = 0.0f;
+    }
+    if (!dry) {
+        prune_adopt(c, selected, c->lod_R, false);
+        c->sh_valid = false;                    // (a plane of other records: dropped, as by m2s_merge)
+        c->lod_ids_of = c->last_records;
+        c->lod_ids_n = selected;
+        c->lod_ids_epoch = c->records_epoch;
+    }
+    c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
+    c->last_lod_select_counts[3] = h[kLodRefineWord];
+    for (uint32_t l = 0; l <= M2S_LOD_MAX_STEPS; ++l) c->last_lod_level_counts[l] = l < levels ? h[l] : 0;
+    if (out_counts) std::memcpy(out_counts, c->last_lod_select_counts, sizeof(c->last_lod_select_counts));
+    return M2S_OK;
+}
+
+m2s_status m2s_last_lod_level_counts(const m2s_ctx* c, uint64_t out[M2S_LOD_MAX_STEPS + 1]) {
+    if (!c || !out) return M2S_ERR_INVALID;
+    std::memcpy(out, c->last_lod_level_counts, sizeof(c->last_lod_level_counts));
+    return M2S_OK;
+}
+
+m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* c, float out_ms[3]) {
+    if (!c || !out_ms) return M2S_ERR_INVALID;
+    std::memcpy(out_ms, c->last_lod_select_stage_ms, sizeof(c->last_lod_select_stage_ms));
+    return M2S_OK;
+}
+
+const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_n ? c->d_lod_ids.get() : nullptr; }
+
+m2s_status m2s_download_lod_nodes(m2s_ctx* c, uint32_t* dst, uint64_t capacity, uint64_t* out_n) {
+    if (out_n) *out_n = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!lod_ids_valid(c)) return fail(c, M2S_ERR_STATE, "no node indices of the current records (m2s_lod_select; the records changed since)");
+    if (out_n) *out_n = c->lod_ids_n;
+    if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
+    if (capacity < c->lod_ids_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!c->lod_ids_n) return M2S_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_lod_ids, c->lod_ids_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+}  // extern "C"

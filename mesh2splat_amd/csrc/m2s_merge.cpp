@@ -1,6 +1,7 @@
 // m2s_merge.cpp — the merge pass (m2s_merge): host side of m2s_merge.hip.  Order comes from the compact export's helper
 // (compact_keys_and_sort, m2s_compact.hip) in the compact export's own buffers; the parents go into the pool the way m2s_prune's survivors
 // do (through the staging buffer where the sources live there), and what the call does to the context is prune_adopt (m2s_contrib.cpp).
+// merge_run is the pass behind m2s_merge's argument checks: the steps of m2s_lod_build (m2s_lod.cpp) are calls of it.
 #include "m2s_ctx.h"
 
 #include <algorithm>
@@ -18,22 +19,17 @@ bool merge_map_valid(const m2s_ctx* c) {
 
 }  // namespace
 
-extern "C" {
+namespace m2s_host {
 
-m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[4]) {
-    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
-    if (!c || !p) return M2S_ERR_INVALID;
-    if (p->level > 10 || p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "level above 10 or max_group outside 2..64");
-    if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
-    if ((p->flags & ~(uint32_t)M2S_MERGE_DRY_RUN) || p->reserved[0] != 0 || p->reserved[1] != 0)
-        return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+// The body of m2s_merge behind its argument checks (m2s_lod_build runs it once per step): level 0..10, max_group 2..64, no NaN.
+m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode) {
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
     if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
     const uint64_t n64 = c->last_stored;
     if (n64 > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
     const uint32_t n = (uint32_t)n64;
-    const bool dry = (p->flags & M2S_MERGE_DRY_RUN) != 0;
+    bool dry = mode == MergeMode::Dry || (mode == MergeMode::IfAny && n == 0);
     const uint32_t R = c->last_R;
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->merge_ev.ensure(c->err));
@@ -60,7 +56,7 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
         HIPCHK(c, compact_keys_and_sort((const float4*)c->last_records, plane, n, c->d_compact_waves, head, u, u + cap, u + 2 * cap, u + 3 * cap, c->d_compact_temp,
                                         c->d_compact_temp.cap(), ev, c->stream));
         HIPCHK(c, hipEventRecord(ev[3], c->stream));
-        HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, p->level, p->max_group, p->min_axis_dot, m, m + mcap, packed, sums, seg_start,
+        HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, level, max_group, min_axis_dot, m, m + mcap, packed, sums, seg_start,
                                  c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), c->stream));
         HIPCHK(c, hipEventRecord(ev[4], c->stream));
         uint32_t h[kMergeTotalsWords] = {}, skipped = 0;
@@ -73,6 +69,7 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
         if (segments < 1 || segments > n || invalid > n || merged > segments) return fail(c, M2S_ERR_HIP, "the merge pass's segment count came back inconsistent");
         HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], ev[2]));
         HIPCHK(c, hipEventElapsedTime(&ms[1], ev[3], ev[4]));
+        if (mode == MergeMode::IfAny && segments == n) dry = true;   // (nothing to merge: nothing changes)
         if (!dry) {
             // The parents go into the pool.  Members that live there already cannot be reduced onto themselves by independent lanes: the
             // parents go through the staging buffer and are copied back, stream-ordered (as m2s_prune's survivors).
@@ -104,6 +101,21 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
     }
     c->last_merge_counts[0] = n; c->last_merge_counts[1] = segments; c->last_merge_counts[2] = merged; c->last_merge_counts[3] = invalid;
     std::memcpy(c->last_merge_stage_ms, ms, sizeof(ms));
+    return M2S_OK;
+}
+
+}  // namespace m2s_host
+
+extern "C" {
+
+m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    if (p->level > 10 || p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "level above 10 or max_group outside 2..64");
+    if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
+    if ((p->flags & ~(uint32_t)M2S_MERGE_DRY_RUN) || p->reserved[0] != 0 || p->reserved[1] != 0)
+        return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+    M2S_TRY(merge_run(c, p->level, p->max_group, p->min_axis_dot, (p->flags & M2S_MERGE_DRY_RUN) ? MergeMode::Dry : MergeMode::Apply));
     if (out_counts) std::memcpy(out_counts, c->last_merge_counts, sizeof(c->last_merge_counts));
     return M2S_OK;
 }

@@ -1,0 +1,63 @@
+"""The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_levels` / `.download_lod` /
+`.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select): the ctypes mirrors of their parameters and the two numbers a
+cut takes from a camera.  The pins are in include/m2s.h.
+
+The default chain of merge levels (1 .. 8), like max_group = 4 and min_axis_dot = 0.5, is a guess: nothing in the repository has
+tuned it (tools/lod_probe.py reports what it does on one scene)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+MAX_STEPS = 16                                               # M2S_LOD_MAX_STEPS
+NO_PARENT = 0xFFFFFFFF                                       # M2S_LOD_NO_PARENT
+DRY_RUN = 1                                                  # M2S_LOD_DRY_RUN
+DEFAULT_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8)
+BUILD_COUNTS = ("leaves", "nodes", "levels", "skipped")      # m2s_lod_build's out_counts, in order
+SELECT_COUNTS = ("nodes", "selected", "selected_leaves", "refine")   # m2s_lod_select's
+PLANES = {0: (np.float32, 24), 1: (np.uint32, None), 2: (np.float32, 4)}    # m2s_download_lod: which -> (dtype, row length)
+
+
+class LodBuildParamsC(C.Structure):
+    """== m2s_lod_build_params (include/m2s.h)."""
+    _fields_ = [("n_steps", C.c_uint32), ("levels", C.c_uint32 * MAX_STEPS), ("max_group", C.c_uint32), ("min_axis_dot", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+class LodSelectParamsC(C.Structure):
+    """== m2s_lod_select_params (include/m2s.h)."""
+    _fields_ = [("camera_position", C.c_float * 3), ("focal_px", C.c_float), ("tau_px", C.c_float), ("near", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5) -> LodBuildParamsC:
+    levels = [int(v) for v in levels]
+    if len(levels) > MAX_STEPS:
+        raise ValueError(f"at most {MAX_STEPS} steps")
+    c = LodBuildParamsC()
+    c.n_steps = len(levels)
+    c.levels[:len(levels)] = levels
+    c.max_group, c.min_axis_dot = int(max_group), float(min_axis_dot)
+    return c
+
+
+def select_to_c(camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False) -> LodSelectParamsC:
+    c = LodSelectParamsC()
+    c.camera_position[:] = [float(v) for v in camera_position]
+    c.focal_px, c.tau_px, c.near, c.flags = float(focal_px), float(tau_px), float(near), DRY_RUN if dry_run else 0
+    return c
+
+
+def focal_px(view_to_clip, H: int) -> float:
+    """Pixels per unit of tan(angle) of a perspective projection on a viewport H pixels high: view_to_clip[5] * H / 2 (glm's memory
+    order: element [1][1]), in float32."""
+    p = np.asarray(view_to_clip, np.float32).reshape(-1)
+    return float(np.float32(p[5] * np.float32(H)) / np.float32(2))
+
+
+def camera_position(world_to_view) -> tuple:
+    """The eye of a rigid world-to-view matrix (glm's memory order, m[4 c + r]): -R^T t, in float64, rounded to float32 once."""
+    m = np.asarray(world_to_view, np.float64).reshape(-1)
+    t = m[12:15]
+    return tuple(float(np.float32(-(m[4 * k + 0] * t[0] + m[4 * k + 1] * t[1] + m[4 * k + 2] * t[2]))) for k in range(3))

@@ -1,0 +1,116 @@
+"""Measures the level-of-detail tree and its cut on C3's 2.74 M records at R = 1024, 1920 x 1080: m2s_lod_build with the default chain
+(nodes per level, time), m2s_lod_select per stage for the preview camera at distance factors 1, 2, 4, 8 and every --tau; beside each
+cut the yardstick — m2s_prune over as many records as the tree has nodes (the node pool itself, adopted), keeping as many as the cut
+selected: the same compaction, so the difference is what the selection costs — and, with --frames, the frame's pass times and `score`
+against the mesh for the cut, for the full records and for merge_to_budget to the cut's count.
+
+    python tools/lod_probe.py [--tau 1,1024] [--factors 1,2,4,8] [--frames] [--reps 5] [--warmup 2] [--out profiles/lod/probe.json]
+
+A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
+tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
+medians of --reps calls after --warmup."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tau", default="1,1024")
+    ap.add_argument("--factors", default="1,2,4,8")
+    ap.add_argument("--frames", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import numpy as np
+    from mesh2splat_amd import lod, synth
+    from mesh2splat_amd.converter import Converter
+    from mesh2splat_amd.score import camera_from_eye, orbit_eye, preview_rule
+    R, W, H = 1024, 1920, 1080
+    scene = synth.cube_sphere(289, tex_size=2048)
+    conv = Converter(0)
+    conv.upload_scene(scene)
+    conv.set_max_gaussians(0)
+    conv.set_profiling(True)
+    ctr, dist, near, far = preview_rule(scene)
+    light = (ctr[0] + dist, ctr[1] + dist, ctr[2] + dist)
+
+    def median_of(rows):
+        return {k: statistics.median(r[k] for r in rows) for k in rows[0]}
+
+    def camera(f):
+        return camera_from_eye(orbit_eye(ctr, dist * f, 0, 1), ctr, near, far * f, W, H)
+
+    def frame(cam):
+        """one lit frame of the current records and its score against the mesh -> pass times, score"""
+        pp, lp = cam.frame_params(R, light, 4.0 * dist * dist)
+        s = conv.score(pp, lp)
+        return ({"prepass": conv.last_prepass_ms, "sort": conv.last_sort_prepass_ms, "splat": conv.last_splat_ms, "shadow": conv.last_shadow_ms,
+                 "relight": conv.last_relight_ms}, {"psnr_db": s.psnr, "ssim": s.ssim})
+
+    records = conv.convert(R)
+    build_ms, build = [], None
+    for k in range(a.warmup + a.reps):
+        conv.convert(R)
+        got = conv.lod_build()
+        assert build is None or got == build
+        build = got
+        if k >= a.warmup:
+            build_ms.append(conv.last_lod_build_ms)
+    first = build["first"]
+    res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup,
+           "build": {"counts": {k: v for k, v in build.items() if k != "first"}, "per_level_nodes": [first[l + 1] - first[l] for l in range(len(first) - 1)],
+                     "ms": statistics.median(build_ms)}, "cuts": []}
+    nodes = build["nodes"]
+    for tau in [float(v) for v in a.tau.split(",")]:
+        for f in [float(v) for v in a.factors.split(",")]:
+            cam = camera(f)
+            eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
+            rows, counts = [], None
+            for k in range(a.warmup + a.reps):
+                got = conv.lod_select(eye, focal, tau, cam.near)
+                assert counts is None or got == counts                                # integer sums: the same from run to run
+                counts = got
+                ms = conv.last_lod_select_stage_ms()
+                ms["total"] = ms["sweep"] + ms["scan_ids"] + ms["compact"]
+                if k >= a.warmup:
+                    rows.append(ms)
+            row = {"tau_px": tau, "factor": f, "counts": counts, "select_stage_ms": median_of(rows)}
+            ids = conv.download_lod_nodes()
+            if a.frames:
+                row["frame_cut"] = dict(zip(("pass_ms", "score"), frame(cam)))
+            # the yardstick: m2s_prune over the node pool, keeping the same nodes
+            keep = np.zeros(nodes, np.uint32)
+            keep[ids] = 1
+            prune_ms = []
+            for k in range(a.warmup + a.reps):
+                conv.set_records(conv.device_lod(0), nodes, R)
+                conv.contrib_begin()
+                conv.upload_contrib(np.ones(nodes, np.float32), keep)
+                assert conv.prune(0.5, 1)["kept"] == counts["selected"]
+                if k >= a.warmup:
+                    prune_ms.append(conv.last_prune_ms)
+            row["prune_same_counts_ms"] = statistics.median(prune_ms)
+            if a.frames:
+                conv.convert(R)
+                row["frame_full"] = dict(zip(("pass_ms", "score"), frame(cam)))
+                mb = conv.merge_to_budget(max(counts["selected"], 1))
+                row["frame_merge_to_budget"] = dict(zip(("pass_ms", "score"), frame(cam)), level=mb["level"], met=mb["met"], after=mb["after"])
+            res["cuts"].append(row)
+            print(json.dumps(row), flush=True)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    conv.close()
+
+
+if __name__ == "__main__":
+    main()

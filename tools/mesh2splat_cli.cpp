@@ -86,6 +86,10 @@ struct Options {
     int merge_group = 4;                                           // --merge-group g (2..64; 4 and the 0.5 below are guesses nobody has tuned)
     double merge_dot = 0.5;                                        // --merge-dot d
     bool merging() const { return merge_level >= 0 || merge_to > 0; }
+    std::vector<uint32_t> lod_levels;                              // --lod-levels a,b,...: the merge levels of the level-of-detail tree's steps (m2s_lod_build); empty: off
+    double lod_pixels = -1.0;                                      // --lod-pixels t: every --preview / --score camera takes its cut at tau_px = t first (m2s_lod_select)
+    double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
+    bool lod() const { return !lod_levels.empty(); }
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
     bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
     long conversion_cap() const { return budget > 0 && !cap_set ? 0 : cap; }
@@ -106,6 +110,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t] [--view-distance f]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -156,7 +161,16 @@ void usage() {
                  "  guesses.  It runs after --prune / --budget and before --refit (which then corrects the parents' colours), --bake-light,\n"
                  "  --score, --preview, --compact and the export; the canonical record order is gone afterwards.  Prints ONE line `merge: {...}`\n"
                  "  of JSON per file: level, max_group, min_axis_dot, target, met, before, after, merged, invalid, stage_ms.  Not with\n"
-                 "  --gpus N > 1.  With --batch the per-file report times it as `merge`.\n");
+                 "  --gpus N > 1.  With --batch the per-file report times it as `merge`.\n"
+                 "--lod-levels a,b,... (1 to 16 merge levels, each 0..10, non-decreasing) --lod-pixels t (>= 0), with --preview and / or --score:\n"
+                 "  level of detail per camera.  After the export (the file keeps the full records) the resident tree is built (m2s_lod_build,\n"
+                 "  with --merge-group and --merge-dot), and the --preview camera and every --score camera first take their cut through it\n"
+                 "  (m2s_lod_select at the eye, focal = view_to_clip[5] * H / 2, tau_px = t, near = the camera's near plane): each part of the\n"
+                 "  surface once, as coarse as t pixels allow; the frame is drawn from the cut.  Prints ONE line `lod: {...}` of JSON per file:\n"
+                 "  levels, nodes, per_level_nodes, skipped, tau_px, build_ms, views (per camera, the preview's first: selected, per_level).\n"
+                 "  With --batch, which draws no frames, --score K names the cameras and every cut is a dry run.  Not with --gpus N > 1.\n"
+                 "--view-distance f (0.25..64, default 1: what it was): the --preview and --score eyes stand at f x the camera rule's distance\n"
+                 "  and the far plane is f x as far; near stays.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -256,9 +270,11 @@ void camera_matrices(const double eye[3], const double ctr[3], double near_p, do
 }
 
 void preview_camera(const m2s_mesh* meshes, uint32_t n_meshes, int W, int H, float view[16], float proj[16], double eye[3], double ctr[3],
-                    double* near_p, double* far_p) {
+                    double* near_p, double* far_p, double view_distance = 1.0) {
     double dist;
     preview_rule(meshes, n_meshes, ctr, &dist, near_p, far_p);
+    dist *= view_distance;                // (--view-distance; a factor of 1 changes no bit)
+    *far_p *= view_distance;
     for (int k = 0; k < 3; ++k) eye[k] = ctr[k];
     eye[2] += dist;
     camera_matrices(eye, ctr, *near_p, *far_p, W, H, view, proj);
@@ -277,14 +293,60 @@ void preview_light(const m2s_mesh* meshes, uint32_t n_meshes, double pos[3], dou
     *intensity = 4.0 * radius * radius;
 }
 
+// --lod-levels / --lod-pixels: the tree over the context's records (Converter.lod_build), then one cut per camera (Converter.lod_select)
+// in front of its frame; the views collect in `views` for the one `lod:` line
+struct LodReport { uint64_t build[4] = {}; std::vector<uint64_t> first; float build_ms = 0; std::string views; };
+
+int lod_build(m2s_ctx* ctx, const Options& o, LodReport* rep) {
+    m2s_lod_build_params bp;
+    std::memset(&bp, 0, sizeof(bp));
+    bp.n_steps = (uint32_t)o.lod_levels.size();
+    for (size_t s = 0; s < o.lod_levels.size(); ++s) bp.levels[s] = o.lod_levels[s];
+    bp.max_group = (uint32_t)o.merge_group;
+    bp.min_axis_dot = (float)o.merge_dot;
+    uint32_t levels = 0;
+    uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
+    if (m2s_lod_build(ctx, &bp, rep->build) != M2S_OK || m2s_lod_levels(ctx, &levels, first) != M2S_OK) return 1;
+    rep->first.assign(first, first + levels + 1);
+    rep->build_ms = m2s_last_lod_build_ms(ctx);
+    return 0;
+}
+
+int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float view_to_clip[16], int H, double near_p, bool dry, LodReport* rep) {
+    m2s_lod_select_params sp;
+    std::memset(&sp, 0, sizeof(sp));
+    for (int k = 0; k < 3; ++k) sp.camera_position[k] = (float)eye[k];
+    sp.focal_px = view_to_clip[5] * (float)H / 2.0f;
+    sp.tau_px = (float)o.lod_pixels;
+    sp.near = (float)near_p;
+    sp.flags = dry ? (uint32_t)M2S_LOD_DRY_RUN : 0u;
+    uint64_t c[4] = {}, per[M2S_LOD_MAX_STEPS + 1] = {};
+    if (m2s_lod_select(ctx, &sp, c) != M2S_OK || m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
+    std::string levels;
+    for (size_t l = 0; l + 1 < rep->first.size(); ++l) levels += std::string(l ? ", " : "") + std::to_string((unsigned long long)per[l]);
+    rep->views += std::string(rep->views.empty() ? "" : ", ") + "{\"selected\": " + std::to_string((unsigned long long)c[1]) + ", \"per_level\": [" + levels + "]}";
+    return 0;
+}
+
+void lod_print(const Options& o, const LodReport& rep) {
+    std::string levels, per;
+    for (size_t s = 0; s < o.lod_levels.size(); ++s) levels += std::string(s ? ", " : "") + std::to_string(o.lod_levels[s]);
+    for (size_t l = 0; l + 1 < rep.first.size(); ++l) per += std::string(l ? ", " : "") + std::to_string((unsigned long long)(rep.first[l + 1] - rep.first[l]));
+    char tau[40];
+    std::snprintf(tau, sizeof tau, "%.9g", (double)(float)o.lod_pixels);
+    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]}\n",
+                levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str());
+}
+
 // GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path` — with
 // --preview-mode 5 / 6 followed by GaussianShadowPass -> GaussianRelightingPass, and the relit frame to `path`
-int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o, LodReport* lod) {
     const int W = o.preview_w, H = o.preview_h;
     m2s_prepass_params pp;
     std::memset(&pp, 0, sizeof(pp));
     double eye[3], ctr[3], near_p, far_p;
-    preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p);
+    preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p, o.view_distance);
+    if (lod && lod_cut(ctx, o, eye, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
     for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
     pp.resolution[0] = W; pp.resolution[1] = H;
     pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
@@ -413,11 +475,13 @@ std::string json_num(double v) {
     return b;
 }
 
-int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
+int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o, LodReport* lod) {
     const int W = o.preview_w, H = o.preview_h, K = o.score_views;
     const int mode = o.preview_mode_set ? o.preview_mode : 6;
     double ctr[3], dist, near_p, far_p, lpos[3], inten;
     preview_rule(meshes, n_meshes, ctr, &dist, &near_p, &far_p);
+    dist *= o.view_distance;              // (--view-distance; a factor of 1 changes no bit)
+    far_p *= o.view_distance;
     preview_light(meshes, n_meshes, lpos, &inten);
     if (o.has_light) { for (int k = 0; k < 3; ++k) lpos[k] = o.light[k]; if (o.light[3] > 0) inten = o.light[3]; }
     auto u64 = [](uint64_t v) { return std::to_string((unsigned long long)v); };
@@ -438,6 +502,7 @@ int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_
         m2s_prepass_params pp;
         std::memset(&pp, 0, sizeof(pp));
         camera_matrices(eye, ctr, near_p, far_p, W, H, pp.world_to_view, pp.view_to_clip);
+        if (lod && lod_cut(ctx, o, eye, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
         for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
         pp.resolution[0] = W; pp.resolution[1] = H;
         pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
@@ -713,16 +778,19 @@ int convert_one(const Options& o) {
         else if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
     } else if (o.compact) { if (export_compact(ctx, o.out, o, false) != 0) return die("export"); }
     else if (m2s_export_ply(ctx, o.out.c_str(), (uint32_t)o.format, (float)o.std_dev) != M2S_OK) return die("export");
+    LodReport lod;
+    if (o.lod() && lod_build(ctx, o, &lod) != 0) return die("lod");       // (after the export: the file keeps the full records)
     if (!o.preview.empty()) {
-        const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
+        const int pr = write_preview(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o, o.lod() ? &lod : nullptr);
         if (pr == 1) return die("preview");
         if (pr) { m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; }
     }
     if (o.score_views > 0) {
-        const int sr = write_score(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o);
+        const int sr = write_score(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o, o.lod() ? &lod : nullptr);
         if (sr == 1) return die("score");
         if (sr) { m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; }
     }
+    if (o.lod()) lod_print(o, lod);
     const auto t4 = Clock::now();
     std::printf("%s: %u mesh(es), %llu triangles, density %u -> %llu Gaussians (%llu stored) -> %s (format %ld)\n", o.in.c_str(),
                 m2s_host_scene_num_meshes(scene), (unsigned long long)m2s_num_triangles(ctx), R, (unsigned long long)total,
@@ -928,7 +996,8 @@ private:
 };
 
 struct Loaded { std::string in, out; m2s_host_scene* scene = nullptr; double load_ms = 0; };
-struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1, merge_ms = -1, refit_ms = -1; };   // budget_ms / merge_ms / refit_ms < 0: no --budget / --merge-* / --refit
+struct Converted { std::string in, out; int slot = 0; uint64_t total = 0; double load_ms = 0, upload_ms = 0, convert_ms = 0, budget_ms = -1, merge_ms = -1, refit_ms = -1;   // budget_ms / merge_ms / refit_ms < 0: no --budget / --merge-* / --refit
+                   double ctr[3] = {}, dist = 0, near_p = 0, far_p = 0; };   // the camera rule of its scene (--lod-*: the scene is gone by then)
 
 int batch_on_device(const Options& o, const std::vector<std::pair<std::string, std::string>>& files, int device, int tag) {
     const auto t_begin = Clock::now();
@@ -959,6 +1028,20 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
                 std::fprintf(stderr, "%s: export: %s\n", c.in.c_str(), m2s_last_error(ctx[c.slot])); ++failures;
             }
             const double ex = ms_between(a, Clock::now());
+            if (o.lod()) {
+                // the tree over the exported records, and a dry-run cut per --score camera (a batch draws no frames)
+                LodReport rep;
+                bool ok = lod_build(ctx[c.slot], o, &rep) == 0;
+                for (int v = 0; ok && v < o.score_views; ++v) {
+                    const double th = 2.0 * M_PI * v / o.score_views, el = o.score_elevation * (M_PI / 180.0), dist = c.dist * o.view_distance;
+                    const double eye[3] = { c.ctr[0] + dist * std::cos(el) * std::sin(th), c.ctr[1] + dist * std::sin(el), c.ctr[2] + dist * std::cos(el) * std::cos(th) };
+                    float view[16], proj[16];
+                    camera_matrices(eye, c.ctr, c.near_p, c.far_p * o.view_distance, o.preview_w, o.preview_h, view, proj);
+                    ok = lod_cut(ctx[c.slot], o, eye, proj, o.preview_h, c.near_p, true, &rep) == 0;
+                }
+                if (ok) lod_print(o, rep);
+                else { std::fprintf(stderr, "%s: lod: %s\n", c.in.c_str(), m2s_last_error(ctx[c.slot])); ++failures; }
+            }
             char budget[48] = "";
             if (c.budget_ms >= 0) std::snprintf(budget, sizeof(budget), ", budget %.2f ms", c.budget_ms);
             char merge[48] = "";
@@ -999,6 +1082,7 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
             ok = run_refit(ctx[slot], m2s_host_scene_meshes(l.scene), m2s_host_scene_num_meshes(l.scene), o.R(), o) == 0;
             c.refit_ms = ms_between(a, Clock::now());
         }
+        if (o.lod()) preview_rule(m2s_host_scene_meshes(l.scene), m2s_host_scene_num_meshes(l.scene), c.ctr, &c.dist, &c.near_p, &c.far_p);
         m2s_free_host_scene(l.scene);
         if (!ok) {
             std::fprintf(stderr, "%s: %s\n", l.in.c_str(), m2s_last_error(ctx[slot])); ++failures;
@@ -1077,6 +1161,23 @@ int main(int argc, char** argv) {
         else if (a == "--merge-to") { o.merge_to = std::atoll(next()); if (o.merge_to < 1) { usage(); return 2; } }
         else if (a == "--merge-group") { o.merge_group = std::atoi(next()); if (o.merge_group < 2 || o.merge_group > 64) { usage(); return 2; } }
         else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
+        else if (a == "--lod-pixels") { o.lod_pixels = std::atof(next()); if (!(o.lod_pixels >= 0.0) || !std::isfinite(o.lod_pixels)) { usage(); return 2; } }
+        else if (a == "--view-distance") { o.view_distance = std::atof(next()); if (!(o.view_distance >= 0.25 && o.view_distance <= 64.0)) { usage(); return 2; } }
+        else if (a == "--lod-levels") {
+            o.lod_levels.clear();
+            const std::string v = next();
+            size_t at = 0;
+            while (at <= v.size()) {
+                const size_t c = std::min(v.find(',', at), v.size());
+                char* end = nullptr;
+                const std::string tok = v.substr(at, c - at);
+                const long lv = std::strtol(tok.c_str(), &end, 10);
+                if (tok.empty() || *end || lv < 0 || lv > 10 || (!o.lod_levels.empty() && (uint32_t)lv < o.lod_levels.back())) { usage(); return 2; }
+                o.lod_levels.push_back((uint32_t)lv);
+                at = c + 1;
+            }
+            if (o.lod_levels.size() > M2S_LOD_MAX_STEPS) { usage(); return 2; }
+        }
         else if (a == "--prune") { o.prune_views = std::atoi(next()); if (o.prune_views < 1 || o.prune_views > 4096) { usage(); return 2; } }
         else if (a == "--refit") { o.refit_views = std::atoi(next()); if (o.refit_views < 1 || o.refit_views > 4096) { usage(); return 2; } }
         else if (a == "--refit-iters") { o.refit_iters = std::atoi(next()); if (o.refit_iters < 1 || o.refit_iters > 64) { usage(); return 2; } }
@@ -1125,6 +1226,9 @@ int main(int argc, char** argv) {
     if (o.merging() && (o.gpus > 1 || o.force_sharded || (o.merge_level >= 0 && o.merge_to > 0))) { usage(); return 2; }   // (multi-rank merges: out of scope)
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
+    // --lod-*: both or neither; the cuts need cameras (--preview / --score; a batch draws no preview) and one context
+    if (o.lod() != (o.lod_pixels >= 0.0)) { usage(); return 2; }
+    if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
         if (o.out_dir.empty() || !pos.empty()) { usage(); return 2; }
