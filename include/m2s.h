@@ -658,7 +658,7 @@ m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity
  *     the next m2s_lod_build (one refused for its arguments or the context's state leaves it; one that fails later leaves no tree),
  *     m2s_lod_release or m2s_destroy, whatever happens to the current records.  The resolutionTarget of the leaves is remembered.
  *     m2s_last_merge_counts reports the last step.  Scales are read as stored, as by m2s_merge: a conversion's are in units the
- *     viewer divides by the resolutionTarget (Limits).
+ *     viewer divides by the resolutionTarget (Limits) until m2s_records_to_world_units has divided them.
  *  6. out_counts (may be NULL): [0] leaves, [1] nodes, [2] tree levels (the leaves included), [3] steps that added no level.
  * Synchronous.  M2S_ERR_INVALID: n_steps outside 1..16, a level above 10, levels that decrease, a level past n_steps that is not 0,
  * max_group outside 2..64, a NaN min_axis_dot, reserved != 0.  M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY:
@@ -725,6 +725,35 @@ m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
  * records change again (NULL / M2S_ERR_STATE then).  m2s_download_lod_nodes: as m2s_download_merge_map. */
 const void* m2s_device_lod_nodes(const m2s_ctx* ctx);
 m2s_status m2s_download_lod_nodes(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
+
+/* ---- world units (no counterpart in the reference, which keeps the resolutionTarget beside its records) ---------------------------- */
+/* Brings the context's current records to world units: scale[k] = scale[k] / (float)R for k = 0, 1, 2, with R the records'
+ * resolutionTarget; afterwards the records' resolutionTarget is 1.  A conversion stores scale = (|Ju|, |Jv|, 1e-7) and leaves the
+ * division by R to the viewer (std / R times the stored scale); m2s_merge, m2s_lod_build and m2s_lod_select read scale[0..1] as world
+ * lengths, which holds for uploaded records and for these, not for a conversion's as stored: run this pass between the conversion and
+ * them, and tau_px of the cut counts screen pixels.  The pin (tests/worldunits_ref.py restates it):
+ *  1. Arithmetic.  Each of scale[0], scale[1], scale[2] is replaced by the correctly rounded (IEEE, round to nearest even) fp32 quotient
+ *     by (float)R; every other word of the 96-byte record keeps its bits, scale[3] included.  This holds for invalid records, NaN
+ *     (a NaN stays a NaN; its payload is the division's), infinities, zeros and negative scales (the sign is kept) and for quotients
+ *     that are subnormal (not flushed).
+ *  2. No-op cases.  With R = 0 (uploaded records, taken as R = 1) or R = 1 the call succeeds and nothing of the context changes: the
+ *     records stay where they are and the records epoch does not advance.
+ *  3. Effect on the context, otherwise as m2s_refit_apply: the records live in the context-owned pool afterwards (records adopted
+ *     through m2s_set_records are divided on their way there; the caller's memory is not written), the records epoch advances, and
+ *     cached positions, sorted quads, sources, the contribution and refit accumulators, the maps of m2s_merge and m2s_lod_select and a
+ *     baked SH plane are invalidated.  m2s_last_resolution reports 1.  A level-of-detail tree built earlier is a copy: it is not
+ *     touched and keeps its leaves' resolutionTarget, which m2s_lod_select hands back to the records it selects.
+ *     m2s_download_triangle_counts and the preparation of the next m2s_upload_scene still see the R of the conversion.
+ *  4. *out_previous_R (may be NULL): the resolutionTarget the records had, also in the no-op cases (0 or 1) — 0 where the call fails.
+ *  5. For the viewer.  For a power-of-two R the division and the viewer's std / R are both exact scalings (short of underflow), so
+ *     every consumer that takes its resolution_target from m2s_last_resolution produces the same bytes before and after: the quads of
+ *     m2s_prepass and the rows of m2s_export_ply in formats 0, 1 and 2.  For another R the results differ by the one rounding: here
+ *     the stored scale is rounded after the division and std is used as it is, there std / R is rounded and the product after it.
+ * Synchronous.  M2S_ERR_INVALID for a NULL context; M2S_ERR_STATE without records or with conversions in flight; M2S_ERR_CAPACITY for
+ * more than 2^32 - 1 records. */
+m2s_status m2s_records_to_world_units(m2s_ctx* ctx, uint32_t* out_previous_R);
+/* Duration (ms) of the last m2s_records_to_world_units that was not a no-op; 0 where it ran with profiling off. */
+float m2s_last_world_units_ms(const m2s_ctx* ctx);
 
 /* ---- shadow pass == GaussianShadowPass::execute (GaussianShadowPass.cpp:83-236) ---------------------------- */
 /* The point light of the frame (RenderContext::pointLightData) and what the two lighting passes read from RenderContext. */

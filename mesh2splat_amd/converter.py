@@ -805,7 +805,8 @@ class Converter:
                     render_mode: int = 6, shadow_resolution: int = 1024, mask_mode: int = 2, mesh_depth_test: bool = False):
         """score() through each of `cameras` (mesh2splat_amd.score.OrbitCamera, e.g. orbit_cameras(scene, K, W, H)), the frames built as the
         command line's --score builds them (OrbitCamera.frame_params).  -> (per-view ScoreResults, the pooled ScoreResult: the integers
-        added, the ratios derived from the sums)."""
+        added, the ratios derived from the sums).  `resolution_target` divides the records' scales: pass `self.resolution` (the R of
+        the conversion, 1 after to_world_units())."""
         from . import score as _sc
         views = [self.score(*cam.frame_params(resolution_target, light_position, light_intensity, gaussian_std, render_mode, shadow_resolution),
                             mask_mode=mask_mode, mesh_depth_test=mesh_depth_test) for cam in cameras]
@@ -935,7 +936,8 @@ class Converter:
         """prepass_sorted() -> contrib_accumulate() through each of `cameras` (mesh2splat_amd.prune.orbit_cameras), then prune().
         `size`: (W, H) at which every view is taken instead of the camera's own resolution (the cameras' projections are kept, so keep their
         aspect ratio; default: each camera's resolution).  -> the counts of prune().  `budget`: an integer makes the final call
-        prune_budget(budget, "views") with the same thresholds -> its counts."""
+        prune_budget(budget, "views") with the same thresholds -> its counts.  `resolution_target` divides the records' scales: pass
+        `self.resolution` (the R of the conversion, 1 after to_world_units())."""
         import dataclasses
         from . import splat as _sp
         if size is not None:
@@ -1098,6 +1100,25 @@ class Converter:
         self._check(self._L.m2s_last_lod_select_stage_ms(self._h, ms))
         return {"sweep": float(ms[0]), "scan_ids": float(ms[1]), "compact": float(ms[2])}
 
+    # ---- world units (m2s_records_to_world_units) ----------------------------------------------------------------------------------------
+    @property
+    def resolution(self) -> int:
+        """The resolutionTarget of the context's current records, the divisor of their scales (m2s_last_resolution): the R of the
+        conversion, 1 after to_world_units(), 0 for uploaded records (taken as 1).  The one place to take `resolution_target` from for
+        prepass parameters, prune_views(), refit_views() and score_views()."""
+        return int(self._L.m2s_last_resolution(self._h))
+
+    def to_world_units(self) -> dict:
+        """scale[0..2] of every record divided by the records' resolutionTarget R (correctly rounded fp32; every other word keeps its
+        bits), after which `resolution` is 1 (m2s_records_to_world_units; the pin is in include/m2s.h).  merge(), lod_build() and
+        lod_select() read scales as world lengths: on a conversion run this first, and tau_px counts screen pixels.  With R <= 1 nothing
+        changes.  Otherwise the records live in the context's pool afterwards; sorted quads, accumulators, maps and a baked SH plane are
+        invalid; a tree built earlier stays as it is.  -> {"records", "previous_R", "ms" (0 unless profiling is on)}."""
+        prev = C.c_uint32(0)
+        self._check(self._L.m2s_records_to_world_units(self._h, C.byref(prev)))
+        ms = float(self._L.m2s_last_world_units_ms(self._h)) if prev.value > 1 else 0.0
+        return {"records": self.num_stored, "previous_R": int(prev.value), "ms": ms}
+
     # ---- colour refit (m2s_refit_*) ---------------------------------------------------------------------------------------------------
     def refit_begin(self):
         """Size the four 64-bit accumulators per record (num[3], den) to the context's current records and zero them (m2s_refit_begin)."""
@@ -1167,7 +1188,8 @@ class Converter:
         refit_begin(), then per camera prepass_sorted() -> splat() in mode 0 -> mesh_render() in mode 0 -> refit_accumulate() over the
         two albedo attachments, then refit_apply(step, min_weight_sum).  Before every iteration and after the last the albedo error is
         pooled over the cameras: score_frames() over the two albedo attachments, mask 3 (covered by both).  `size`: as prune_views().
-        The defaults min_cover = 128, min_weight_sum = 1.0 and iterations = 2 are guesses that nothing has tuned.
+        The defaults min_cover = 128, min_weight_sum = 1.0 and iterations = 2 are guesses that nothing has tuned.  `resolution_target`
+        divides the records' scales: pass `self.resolution` (the R of the conversion, 1 after to_world_units()).
         -> {"iterations", "views", "sse": [before, after iteration 1, ...] (the three channels added), "pixels": the same for the
         pixels compared, "updated", "clamped", "no_weight": per iteration}."""
         import dataclasses

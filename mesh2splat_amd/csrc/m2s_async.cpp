@@ -115,7 +115,7 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
     const bool stale = sl.own_lane >= 0 && sl.gen != c->lane[sl.own_lane].rec_gen;
     if (sl.sync_result) {   // run_pass already filled last_*
         if (out_total) *out_total = sl.sync_total;
-        c->last_total = sl.sync_total; c->last_stored = sl.limit; c->last_records = sl.d_out; c->last_R = sl.R;
+        c->last_total = sl.sync_total; c->last_stored = sl.limit; c->last_records = sl.d_out; c->last_R = sl.R; c->conv_R = 0;
         ++c->records_epoch;
         c->records_stale = stale;
         memcpy(c->last_ms, sl.ms, sizeof sl.ms);
@@ -143,6 +143,7 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
     c->last_records = sl.d_out;
     ++c->records_epoch;
     c->last_R = sl.R;
+    c->conv_R = 0;
     c->records_stale = stale;
     if (out_total) *out_total = total;
     return M2S_OK;

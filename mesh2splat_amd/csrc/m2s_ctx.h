@@ -12,6 +12,7 @@
 //   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
+//   m2s_worldunits.cpp  m2s_records_to_world_units: a conversion's scales divided by its resolutionTarget
 //   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select): a chain of merges kept and linked
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
@@ -151,7 +152,9 @@ struct m2s_ctx {
     const void* last_records = nullptr;
     int64_t cap_policy = -1;
     uint64_t last_total = 0, last_stored = 0;
-    uint32_t last_R = 0;
+    uint32_t last_R = 0;                    // resolutionTarget of the current records: the unit of their scales (0: uploaded, taken as 1)
+    uint32_t conv_R = 0;                    // set by m2s_records_to_world_units alone, which takes last_R to 1: the R those records were converted
+                                            // at (converted_R); 0 again with the next records of another source (conversion, upload, adoption)
 
     // depth sort (f-2)
     m2s_host::DevBuf<float4> d_sorted;     // capacity in records
@@ -263,6 +266,9 @@ struct m2s_ctx {
     uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
     float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
     m2s_host::EventSet<4> lod_ev;
+    // world units (m2s_worldunits.cpp)
+    float last_world_units_ms = 0.0f;
+    m2s_host::EventSet<2> wu_ev;
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each
@@ -359,6 +365,9 @@ inline m2s_status fail(m2s_ctx* c, m2s_status s, const std::string& msg) {
     if (c) c->err = msg;
     return s;
 }
+// the R last converted at, for the readers that mean the scene's density and not the unit of the records (the upload's warm_R,
+// m2s_download_triangle_counts): last_R, unless m2s_records_to_world_units has taken that to 1 since
+inline uint32_t converted_R(const m2s_ctx* c) { return c->conv_R ? c->conv_R : c->last_R; }
 // argument checks the entry points share
 inline m2s_status check_resolution(m2s_ctx* c, int W, int H, const char* what = "resolution") {
     if (W < 1 || W > 8192 || H < 1 || H > 8192) return fail(c, M2S_ERR_INVALID, std::string(what) + " outside 1..8192");

@@ -341,6 +341,11 @@ hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t
 // offsets = exclusive scan of flags (n words each); temp: prune_scan_temp_bytes(n)
 hipError_t lod_scan(const uint32_t* flags, uint32_t* offsets, uint32_t n, void* temp, size_t temp_bytes, hipStream_t st);
 
+// ---- world units (m2s_worldunits.hip) ------------------------------------------------------------------------------------------------
+// dst[i] = src[i] with scale[0..2] divided by (float)R (IEEE, correctly rounded), every other word with its bits, for the n records.
+// src == dst: in place, only the scale words move; else the two do not overlap.  R >= 1.
+hipError_t world_units(const float4* src, float4* dst, uint32_t n, uint32_t R, hipStream_t st);
+
 // ---- shadow and relighting passes (m2s_light.hip): GaussianShadowPass + GaussianRelightingPass ---------------------------------------
 struct ShadowBases { uint32_t b[7]; };         // first quad of every face's list in the one buffer that holds the six lists; b[6] = all quads
 struct RelightK {                              // uniforms of gaussianSplattingDeferredPS.glsl

@@ -411,6 +411,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     const uint64_t cap = resolve_cap(c, R);
     const bool prof = c->profiling;
     c->last_R = R;
+    c->conv_R = 0;
     c->records_stale = false;
     memset(c->last_ms, 0, sizeof c->last_ms);
 

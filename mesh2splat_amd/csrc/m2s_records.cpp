@@ -28,12 +28,13 @@ m2s_status m2s_download(m2s_ctx* c, m2s_gaussian* dst, uint64_t capacity_records
 
 m2s_status m2s_download_triangle_counts(m2s_ctx* c, uint32_t* dst, uint64_t n) {
     if (!c) return M2S_ERR_INVALID;
-    if (!c->has_scene || !c->last_R) return fail(c, M2S_ERR_STATE, "no conversion has run");
+    const uint32_t R = converted_R(c);
+    if (!c->has_scene || !R) return fail(c, M2S_ERR_STATE, "no conversion has run");
     if (n < c->scene.n_tri) return fail(c, M2S_ERR_CAPACITY, "dst holds fewer entries than triangles in range");
     if (!c->scene.n_tri) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
     // the fused pipeline keeps counts in registers only: (re)run the counting kernel for the last R
-    launch_count(c->scene, c->last_R, c->d_cnt, c->d_partials, c->stream);
+    launch_count(c->scene, R, c->d_cnt, c->d_partials, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, c->d_cnt, (size_t)c->scene.n_tri * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -115,6 +116,7 @@ m2s_status m2s_upload_records(m2s_ctx* c, const m2s_gaussian* records, uint64_t 
     c->last_total = c->last_stored = n;
     c->records_stale = false;
     c->last_R = 0;      // uploaded records carry no resolutionTarget: m2s_export_ply (scale multiplier = std / R) refuses them
+    c->conv_R = 0;
     c->sorted_n = 0;
     c->pp_visible = 0;
     c->sq_n = 0;
@@ -130,6 +132,7 @@ m2s_status m2s_set_records(m2s_ctx* c, const void* d_records, uint64_t n, uint32
     ++c->records_epoch;
     c->last_total = c->last_stored = n;
     c->last_R = R;
+    c->conv_R = 0;
     c->records_stale = false;
     c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
     return M2S_OK;

@@ -272,7 +272,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     c->chain_words = chain_words;
     HIPCHK(c, hipMemsetAsync(c->lane[0].chain, 0, chain_words * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_bigmeta, 0, 4 * sizeof(uint32_t), c->stream));
-    const uint32_t warm_R = c->hint_R ? c->hint_R : c->last_R ? c->last_R : 1024u;
+    const uint32_t warm_R = c->hint_R ? c->hint_R : converted_R(c) ? converted_R(c) : 1024u;
     const bool warm = !debug_on("M2S_NO_WARM");
     bool counted = false;
     if (warm && !debug_on("M2S_NO_WARM_OVERLAP")) counted = warm_count_enqueue(c, warm_R) == M2S_OK;

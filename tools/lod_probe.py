@@ -5,6 +5,11 @@ selected: the same compaction, so the difference is what the selection costs —
 against the mesh for the cut, for the full records and for merge_to_budget to the cut's count.
 
     python tools/lod_probe.py [--tau 1,1024] [--factors 1,2,4,8] [--frames] [--reps 5] [--warmup 2] [--out profiles/lod/probe.json]
+    python tools/lod_probe.py --world-units [--tau 1,2,4] [--frames] --out profiles/lod/probe_world.json
+
+--world-units: every conversion is followed by m2s_records_to_world_units, so the tree's edges are world lengths and tau_px counts
+screen pixels (default --tau 1,2,4); the result also carries the pass's own time (in place, and out of place from adopted memory) beside
+its two yardsticks on the same records: m2s_refit_apply with every record updated, and a device-to-device copy of the records.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
 tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
@@ -21,13 +26,15 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tau", default="1,1024")
+    ap.add_argument("--tau", default="")
+    ap.add_argument("--world-units", action="store_true")
     ap.add_argument("--factors", default="1,2,4,8")
     ap.add_argument("--frames", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    a.tau = a.tau or ("1,2,4" if a.world_units else "1,1024")
     import numpy as np
     from mesh2splat_amd import lod, synth
     from mesh2splat_amd.converter import Converter
@@ -49,25 +56,63 @@ def main():
 
     def frame(cam):
         """one lit frame of the current records and its score against the mesh -> pass times, score"""
-        pp, lp = cam.frame_params(R, light, 4.0 * dist * dist)
+        pp, lp = cam.frame_params(conv.resolution, light, 4.0 * dist * dist)
         s = conv.score(pp, lp)
         return ({"prepass": conv.last_prepass_ms, "sort": conv.last_sort_prepass_ms, "splat": conv.last_splat_ms, "shadow": conv.last_shadow_ms,
                  "relight": conv.last_relight_ms}, {"psnr_db": s.psnr, "ssim": s.ssim})
 
+    def convert():
+        n = conv.convert(R)
+        if a.world_units:
+            conv.to_world_units()
+        return n
+
+    def pass_times():
+        """the pass in place and out of place, m2s_refit_apply with every record updated, a device-to-device copy: medians (ms)"""
+        import torch
+        n = conv.convert(R)
+        out = {"in_place": [], "out_of_place": [], "refit_apply": [], "d2d_copy": []}
+        src = torch.empty(n * 24, dtype=torch.float32, device="cuda")
+        dst = torch.empty_like(src)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for k in range(a.warmup + a.reps):
+            conv.convert(R)
+            t = [conv.to_world_units()["ms"]]
+            conv.set_records(src.data_ptr(), n, R)
+            t.append(conv.to_world_units()["ms"])
+            conv.convert(R)
+            conv.refit_begin()
+            conv.upload_refit(np.zeros((n, 3), np.int64), np.full(n, 1 << 17, np.uint64))
+            assert conv.refit_apply(1.0, 1.0)["updated"] == n
+            t.append(conv.last_refit_stage_ms()["apply"])
+            ev[0].record()
+            dst.copy_(src)
+            ev[1].record()
+            torch.cuda.synchronize()
+            t.append(ev[0].elapsed_time(ev[1]))
+            if k >= a.warmup:
+                for key, v in zip(out, t):
+                    out[key].append(v)
+        return {key: statistics.median(v) for key, v in out.items()}
+
     records = conv.convert(R)
     build_ms, build = [], None
     for k in range(a.warmup + a.reps):
-        conv.convert(R)
+        convert()
         got = conv.lod_build()
         assert build is None or got == build
         build = got
         if k >= a.warmup:
             build_ms.append(conv.last_lod_build_ms)
     first = build["first"]
-    res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup,
+    res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup, "world_units": a.world_units,
            "build": {"counts": {k: v for k, v in build.items() if k != "first"}, "per_level_nodes": [first[l + 1] - first[l] for l in range(len(first) - 1)],
                      "ms": statistics.median(build_ms)}, "cuts": []}
+    if a.world_units:
+        res["pass_ms"] = pass_times()
+        print(json.dumps({"pass_ms": res["pass_ms"]}), flush=True)
     nodes = build["nodes"]
+    unit_R = 1 if a.world_units else R                                              # the resolutionTarget of the tree's leaves
     for tau in [float(v) for v in a.tau.split(",")]:
         for f in [float(v) for v in a.factors.split(",")]:
             cam = camera(f)
@@ -90,7 +135,7 @@ def main():
             keep[ids] = 1
             prune_ms = []
             for k in range(a.warmup + a.reps):
-                conv.set_records(conv.device_lod(0), nodes, R)
+                conv.set_records(conv.device_lod(0), nodes, unit_R)
                 conv.contrib_begin()
                 conv.upload_contrib(np.ones(nodes, np.float32), keep)
                 assert conv.prune(0.5, 1)["kept"] == counts["selected"]
@@ -98,7 +143,7 @@ def main():
                     prune_ms.append(conv.last_prune_ms)
             row["prune_same_counts_ms"] = statistics.median(prune_ms)
             if a.frames:
-                conv.convert(R)
+                convert()
                 row["frame_full"] = dict(zip(("pass_ms", "score"), frame(cam)))
                 mb = conv.merge_to_budget(max(counts["selected"], 1))
                 row["frame_merge_to_budget"] = dict(zip(("pass_ms", "score"), frame(cam)), level=mb["level"], met=mb["met"], after=mb["after"])

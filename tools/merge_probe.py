@@ -3,6 +3,10 @@ stages; beside it, in the same process on the same records, the two things the p
 to the count the merge reached, and the box + keys and sort stages of the compact export.
 
     python tools/merge_probe.py [--level 2 | --to 700000] [--group 4] [--dot 0.5] [--reps 5] [--warmup 2] [--out profiles/merge/probe.json]
+    python tools/merge_probe.py --world-units [...] --out profiles/merge/probe_world.json
+
+--world-units: every conversion is followed by m2s_records_to_world_units, so the merge reads the edges the viewer draws; the result
+carries the median longer edge before and after the merge either way (a 2 x 2 block of texels should double it).
 
 Stage times come from device events (m2s_last_merge_stage_ms, m2s_last_budget_stage_ms, m2s_last_compact_stage_ms): medians of --reps
 calls after --warmup; between calls the records are put back by converting again, outside the timed span."""
@@ -25,8 +29,10 @@ def main():
     ap.add_argument("--dot", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--world-units", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    import numpy as np
     from mesh2splat_amd import synth
     from mesh2splat_amd.converter import Converter
     R = 1024
@@ -35,19 +41,30 @@ def main():
     conv.set_max_gaussians(0)
     conv.set_profiling(True)
 
+    def convert():
+        n = conv.convert(R)
+        if a.world_units:
+            conv.to_world_units()
+        return n
+
+    def median_edge():
+        rec = conv.download()
+        return float(np.median(np.fmax(np.abs(rec[:, 8]), np.abs(rec[:, 9]))))
+
     def median_of(rows):
         return {k: statistics.median(r[k] for r in rows) for k in rows[0]}
 
-    records = conv.convert(R)
+    records = convert()
+    edge_before = median_edge()
     per_level = {lv: conv.merge_count(lv, a.group, a.dot) for lv in range(11)}
     level = a.level
     if a.to:
         level = conv.merge_to_budget(a.to, a.group, a.dot)["level"]
     res = {"scene": "c3", "density": R, "records": records, "level": level, "max_group": a.group, "min_axis_dot": a.dot, "reps": a.reps,
-           "warmup": a.warmup, "after_per_level": per_level}
+           "warmup": a.warmup, "world_units": a.world_units, "after_per_level": per_level}
     rows, dry_rows, counts = [], [], None
     for k in range(a.warmup + a.reps):
-        conv.convert(R)
+        convert()
         conv.merge(level, a.group, a.dot, dry_run=True)
         dry = conv.last_merge_stage_ms()
         got = conv.merge(level, a.group, a.dot)
@@ -58,11 +75,12 @@ def main():
         if k >= a.warmup:
             rows.append(ms)
             dry_rows.append({"keys_sort": dry["keys_sort"], "heads_scans": dry["heads_scans"]})
-    res["merge"] = {"counts": counts, "stage_ms": median_of(rows), "dry_run_stage_ms": median_of(dry_rows)}
+    res["merge"] = {"counts": counts, "stage_ms": median_of(rows), "dry_run_stage_ms": median_of(dry_rows),
+                    "median_longer_edge": {"before": edge_before, "after": median_edge()}}
     # what it competes with: dropping to the same count
     rows, bcounts = [], None
     for k in range(a.warmup + a.reps):
-        conv.convert(R)
+        convert()
         bcounts = conv.prune_budget(counts["after"], "area")
         ms = conv.last_budget_stage_ms()
         ms["total"] = ms["select"] + ms["flags_scans"] + ms["compact"]
@@ -72,7 +90,7 @@ def main():
     # what it is made of: the compact export's order
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        conv.convert(R)
+        convert()
         for k in range(a.warmup + a.reps):
             ms = conv.export_ply_compact(os.path.join(tmp, "probe.ply"))["stage_ms"]
             if k >= a.warmup:

@@ -90,6 +90,7 @@ struct Options {
     double lod_pixels = -1.0;                                      // --lod-pixels t: every --preview / --score camera takes its cut at tau_px = t first (m2s_lod_select)
     double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
     bool lod() const { return !lod_levels.empty(); }
+    bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
     bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
     long conversion_cap() const { return budget > 0 && !cap_set ? 0 : cap; }
@@ -110,7 +111,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t] [--view-distance f]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -170,7 +171,14 @@ void usage() {
                  "  levels, nodes, per_level_nodes, skipped, tau_px, build_ms, views (per camera, the preview's first: selected, per_level).\n"
                  "  With --batch, which draws no frames, --score K names the cameras and every cut is a dry run.  Not with --gpus N > 1.\n"
                  "--view-distance f (0.25..64, default 1: what it was): the --preview and --score eyes stand at f x the camera rule's distance\n"
-                 "  and the far plane is f x as far; near stays.\n");
+                 "  and the far plane is f x as far; near stays.\n"
+                 "--world-units: right after the conversion, in front of --prune, --budget, --merge-*, --refit, --bake-light, --score, --preview,\n"
+                 "  --compact, the export and --lod-*, the records' scales are divided by the density and their resolutionTarget becomes 1\n"
+                 "  (m2s_records_to_world_units); every later stage takes the divisor from the context.  --merge-* and --lod-* read scales as\n"
+                 "  world lengths: with it their parents grow as a quadtree's and --lod-pixels counts screen pixels, without it density-ths of a\n"
+                 "  pixel.  For a power-of-two density the export and the frames are the same bytes with and without it.  Prints ONE line\n"
+                 "  `world_units: {\"records\": n, \"previous_R\": R, \"ms\": t}` of JSON per file (t: the call on the host's clock).  Works with\n"
+                 "  --batch; not with --gpus N > 1.\n");
 }
 
 // ---- --preview: the albedo plane as a PNG (stored deflate blocks: no compression library needed) ----------------------------
@@ -351,7 +359,7 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     pp.resolution[0] = W; pp.resolution[1] = H;
     pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
     pp.gaussian_std = (float)o.std_dev;
-    pp.resolution_target = R;
+    pp.resolution_target = m2s_last_resolution(ctx);          // (the density; 1 behind --world-units)
     pp.render_mode = 0;
     pp.format = 0;
     std::printf("preview camera: eye=%.17g,%.17g,%.17g centre=%.17g,%.17g,%.17g near=%.17g far=%.17g\n", eye[0], eye[1], eye[2], ctr[0],
@@ -441,7 +449,7 @@ int bake_light(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t
     pp.resolution[0] = W; pp.resolution[1] = H;
     pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
     pp.gaussian_std = (float)o.std_dev;
-    pp.resolution_target = R;
+    pp.resolution_target = m2s_last_resolution(ctx);          // (the density; 1 behind --world-units)
     m2s_light_params lp;
     std::memset(&lp, 0, sizeof(lp));
     double lpos[3], inten;
@@ -507,7 +515,7 @@ int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_
         pp.resolution[0] = W; pp.resolution[1] = H;
         pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
         pp.gaussian_std = (float)o.std_dev;
-        pp.resolution_target = R;
+        pp.resolution_target = m2s_last_resolution(ctx);          // (the density; 1 behind --world-units)
         m2s_light_params lp;
         std::memset(&lp, 0, sizeof(lp));
         for (int k = 0; k < 3; ++k) { lp.light_position[k] = (float)lpos[k]; lp.light_color[k] = 1.0f; lp.camera_position[k] = (float)eye[k]; }
@@ -622,6 +630,16 @@ int run_merge(m2s_ctx* ctx, const Options& o) {
     return 0;
 }
 
+// --world-units: m2s_records_to_world_units over the context's records (Converter.to_world_units does the same); prints one JSON line
+int run_world_units(m2s_ctx* ctx) {
+    uint32_t prev = 0;
+    const auto a = std::chrono::steady_clock::now();
+    if (m2s_records_to_world_units(ctx, &prev) != M2S_OK) return 1;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    std::printf("world_units: {\"records\": %llu, \"previous_R\": %u, \"ms\": %.4f}\n", (unsigned long long)m2s_num_stored(ctx), prev, ms);
+    return 0;
+}
+
 // --refit K: K cameras round the scene at each elevation, at --preview-size; per iteration and camera m2s_prepass_sorted -> m2s_splat ->
 // m2s_mesh_render -> m2s_refit_accumulate, then m2s_refit_apply (Converter.refit_views does the same).  Prints one JSON line.
 int run_refit(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t R, const Options& o) {
@@ -645,7 +663,7 @@ int run_refit(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t 
                 pp.resolution[0] = W; pp.resolution[1] = H;
                 pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
                 pp.gaussian_std = (float)o.std_dev;
-                pp.resolution_target = R;
+                pp.resolution_target = m2s_last_resolution(ctx);          // (the density; 1 behind --world-units)
                 uint64_t visible = 0, skipped = 0;
                 if (m2s_prepass_sorted(ctx, &pp, &visible) != M2S_OK) return 1;
                 m2s_splat_params sp = { { W, H }, 0, 0 };
@@ -707,7 +725,7 @@ int run_prune(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_t 
             pp.resolution[0] = W; pp.resolution[1] = H;
             pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
             pp.gaussian_std = (float)o.std_dev;
-            pp.resolution_target = R;
+            pp.resolution_target = m2s_last_resolution(ctx);          // (the density; 1 behind --world-units)
             uint64_t visible = 0;
             if (m2s_prepass_sorted(ctx, &pp, &visible) != M2S_OK) return 1;
             m2s_splat_params sp = { { W, H }, 0, 0 };
@@ -768,6 +786,7 @@ int convert_one(const Options& o) {
     const uint32_t R = o.R();
     if (m2s_convert(ctx, R, &total) != M2S_OK) return die("convert");
     const auto t3 = Clock::now();
+    if (o.world_units && run_world_units(ctx) != 0) return die("world units");
     if (o.prune_views > 0 && run_prune(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("prune");
     if (o.budget > 0 && o.prune_views == 0 && run_budget(ctx, M2S_IMPORTANCE_AREA, 0.0f, 0, o) != 0) return die("budget");
     if (o.merging() && run_merge(ctx, o) != 0) return die("merge");
@@ -1067,6 +1086,7 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
         a = Clock::now();
         ok = ok && m2s_convert(ctx[slot], o.R(), &c.total) == M2S_OK;
         c.convert_ms = ms_between(a, Clock::now());
+        if (ok && o.world_units) ok = run_world_units(ctx[slot]) == 0;                              // (its lines come in file order)
         if (ok && o.budget > 0) {                                                                   // (its lines come in file order)
             a = Clock::now();
             ok = run_budget(ctx[slot], M2S_IMPORTANCE_AREA, 0.0f, 0, o) == 0;
@@ -1206,6 +1226,7 @@ int main(int argc, char** argv) {
         else if (a == "--score-map") o.score_map = next();
         else if (a == "--bake-light") o.bake_light = true;
         else if (a == "--compact") o.compact = true;
+        else if (a == "--world-units") o.world_units = true;
         else if (a == "--bake-degree") { o.bake_degree = std::atoi(next()); if (o.bake_degree < 0 || o.bake_degree > 3) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
@@ -1225,6 +1246,7 @@ int main(int argc, char** argv) {
     if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
     if (o.merging() && (o.gpus > 1 || o.force_sharded || (o.merge_level >= 0 && o.merge_to > 0))) { usage(); return 2; }   // (multi-rank merges: out of scope)
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
+    if (o.world_units && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (a rank's slice writer and the gather hand on the density)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
     // --lod-*: both or neither; the cuts need cameras (--preview / --score; a batch draws no preview) and one context
     if (o.lod() != (o.lod_pixels >= 0.0)) { usage(); return 2; }
