@@ -618,14 +618,29 @@ float m2s_last_refit_apply_ms(const m2s_ctx* ctx);
  *     are invalidated.  With M2S_MERGE_DRY_RUN nothing of the context changes: only the counts are produced.
  *  8. out_counts (may be NULL): [0] records before, [1] records after, [2] segments with two members or more, [3] invalid records
  *     carried.  The counts are monotone in level (a coarser cell only removes run breaks).
+ * With M2S_MERGE_UNSIGNED_AXIS the sign of r_3 carries no meaning, as it carries none for the viewer (its covariance is
+ * sum s_i^2 r_i r_i^T) and as the conversion leaves it: the two triangles of a flat quad may store r_3 = +n and -n (tests/
+ * merge_unsigned_ref.py restates these two pins; DESIGN 5.18 has what the signed rule does to a conversion).  Off by default.
+ *  2u. Runs.  d is pin 2's, the same fp32 expression; position j starts a run iff one of pin 2's other conditions holds or
+ *     !(fabsf(d) >= min_axis_dot).  A NaN still breaks the run; min_axis_dot <= 0 still never breaks on the axis.  The breaks are a
+ *     subset of pin 2's on the same input, so records after is never larger than without the flag.
+ *  5u. In the walk over a segment's members in sorted order their third rows are oriented one after the other: o_1 = r3_1, and for
+ *     i >= 2 o_i = -r3_i where dot(r3_i, o_{i-1}) < 0, else r3_i (a zero or a NaN does not flip), the dot in fp64 from the fp64 rows
+ *     above as (x x + y y) + z z without contraction.  o_i takes the place of r3_i in nb's sum, with either weighting; everything else
+ *     of pin 5 is as it is (A_i is made of r_1, r_2, which have no sign to lose; the fallback is still the first member's r_3).  The
+ *     parent's r_3 lies on the first member's side, so a chain of merges is well defined.  The orientation goes against the member
+ *     before, not the first: the run rule bounds the angle between neighbours, not across a group of 64.
+ *     Segments, pins 3, 4, 6, 7, 8, the map, the dry run and the monotonicity in level are unchanged.
  * Synchronous.  M2S_ERR_INVALID: level > 10, max_group outside 2..64, a NaN min_axis_dot, unknown flag bits, reserved != 0.
  * M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY: 2^32 records or more. */
-enum { M2S_MERGE_DRY_RUN = 1 };
+/* The valid flags are 0, 1, 4, 5.  Bit 1 (value 2) names nothing and stays refused: flags 2 and 3 were M2S_ERR_INVALID before the second
+ * flag existed and callers may rely on it, so the second flag took bit 2. */
+enum { M2S_MERGE_DRY_RUN = 1, M2S_MERGE_UNSIGNED_AXIS = 4 };
 typedef struct m2s_merge_params {
     uint32_t level;          /* 0..10: cell = key >> (3 * level) */
     uint32_t max_group;      /* 2..64: members per parent, at most */
     float    min_axis_dot;   /* a run breaks where !(dot(r3_j, r3_prev) >= min_axis_dot); NaN refused */
-    uint32_t flags;          /* M2S_MERGE_DRY_RUN = 1; other bits 0 */
+    uint32_t flags;          /* M2S_MERGE_DRY_RUN = 1 | M2S_MERGE_UNSIGNED_AXIS = 4; other bits 0 */
     uint32_t reserved[2];    /* 0 */
 } m2s_merge_params;          /* 24 bytes */
 m2s_status m2s_merge(m2s_ctx* ctx, const m2s_merge_params* params, uint64_t out_counts[4]);
@@ -645,7 +660,7 @@ m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity
  * of the surface exactly once, as coarse as the camera allows.  Integer logic and exact fp32 throughout: reproducible bit for bit
  * (tests/lod_ref.py restates it).  The tree, pinned:
  *  1. Leaves.  The context's current records are the leaves, tree level 0, copied in their own order into a node pool the tree owns.
- *  2. Steps.  Step s = 0 .. n_steps-1 runs m2s_merge's own code with (levels[s], max_group, min_axis_dot) on what the previous step
+ *  2. Steps.  Step s = 0 .. n_steps-1 runs m2s_merge's own code with (levels[s], max_group, min_axis_dot, flags) on what the previous step
  *     left.  Its parents are appended to the pool as the next tree level, in segment order; for a node i of the level below,
  *     parent[i] = first[next] + map[i - first[this]] with map the merge's map.  Nodes of the last level have M2S_LOD_NO_PARENT.
  *  3. A step that merges nothing — its merge would leave as many records as it found — is not applied (as M2S_MERGE_DRY_RUN): it adds
@@ -661,7 +676,8 @@ m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity
  *     viewer divides by the resolutionTarget (Limits) until m2s_records_to_world_units has divided them.
  *  6. out_counts (may be NULL): [0] leaves, [1] nodes, [2] tree levels (the leaves included), [3] steps that added no level.
  * Synchronous.  M2S_ERR_INVALID: n_steps outside 1..16, a level above 10, levels that decrease, a level past n_steps that is not 0,
- * max_group outside 2..64, a NaN min_axis_dot, reserved != 0.  M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY:
+ * max_group outside 2..64, a NaN min_axis_dot, flags other than 0 or M2S_MERGE_UNSIGNED_AXIS (M2S_MERGE_DRY_RUN too: a build is no dry
+ * run).  M2S_ERR_STATE: no records, or conversions in flight.  M2S_ERR_CAPACITY:
  * 2^32 - 1 nodes or more.  Zero records build an empty tree of one level. */
 #define M2S_LOD_MAX_STEPS 16
 #define M2S_LOD_NO_PARENT 0xFFFFFFFFu
@@ -670,7 +686,10 @@ typedef struct m2s_lod_build_params {
     uint32_t levels[M2S_LOD_MAX_STEPS];  /* merge level of step s: 0..10, non-decreasing; entries past n_steps are 0 */
     uint32_t max_group;                  /* 2..64, as m2s_merge */
     float    min_axis_dot;               /* as m2s_merge; NaN refused */
-    uint32_t reserved;                   /* 0 */
+    union {                              /* one word; `reserved` is the name it had while its only value was 0, kept for existing callers */
+        uint32_t flags;                  /* 0 or M2S_MERGE_UNSIGNED_AXIS (every step merges with pins 2u, 5u); any other value refused */
+        uint32_t reserved;
+    };
 } m2s_lod_build_params;                  /* 80 bytes */
 m2s_status m2s_lod_build(m2s_ctx* ctx, const m2s_lod_build_params* params, uint64_t out_counts[4]);
 /* The tree's levels: first[l] is the first node of level l = 0 .. *out_levels - 1, first[*out_levels] and every entry behind it the

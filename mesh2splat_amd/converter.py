@@ -954,24 +954,26 @@ class Converter:
         return self.prune(min_weight, min_pixels)
 
     # ---- merge pass (m2s_merge) ----------------------------------------------------------------------------------------------------------
-    def merge(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False) -> dict:
+    def merge(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False, unsigned_axis: bool = False) -> dict:
         """Replace every group of neighbouring records by its moment-matched parent (m2s_merge; the pin is in include/m2s.h): neighbours
         share a Morton cell of 2^level per axis (level 0..10), a parent takes at most max_group (2..64) members, and a run of members
         breaks where the third axes of two neighbours have a dot product below min_axis_dot.  The parents become the context's
         records, in segment order; sorted quads, accumulators and a baked SH plane are invalid.  dry_run: nothing changes, only the
-        counts are produced.  max_group = 4 and min_axis_dot = 0.5 are untuned guesses.
+        counts are produced.  max_group = 4 and min_axis_dot = 0.5 are untuned guesses.  unsigned_axis (M2S_MERGE_UNSIGNED_AXIS): the sign
+        of the third axis carries no meaning, as for the viewer — a run breaks where |dot| is below min_axis_dot and the members' axes
+        are turned onto one side before they are averaged; a conversion stores the two triangles of a flat quad with opposite signs.
         -> {"before", "after", "merged": parents of two members or more, "invalid": invalid records carried}."""
         from . import merge as _mg
-        pc = _mg.to_c(level, max_group, min_axis_dot, dry_run)
+        pc = _mg.to_c(level, max_group, min_axis_dot, dry_run, unsigned_axis)
         v = (C.c_uint64 * 4)()
         self._check(self._L.m2s_merge(self._h, C.byref(pc), v))
         return {name: int(v[k]) for k, name in enumerate(_mg.COUNTS)}
 
-    def merge_count(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5) -> int:
+    def merge_count(self, level: int, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> int:
         """The number of records merge() with these parameters would leave (a dry run)."""
-        return self.merge(level, max_group, min_axis_dot, dry_run=True)["after"]
+        return self.merge(level, max_group, min_axis_dot, dry_run=True, unsigned_axis=unsigned_axis)["after"]
 
-    def merge_to_budget(self, max_records: int, max_group: int = 4, min_axis_dot: float = 0.5) -> dict:
+    def merge_to_budget(self, max_records: int, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> dict:
         """merge() at the finest level whose dry-run count is <= max_records (the counts are monotone in level: a bisection over
         0..10; records that fit already are merged at level 0, where only records of one 1 / 1024 cell meet).  Where even level 10
         leaves more, level 10 is merged and "met" is False.  -> merge()'s counts + {"level", "met"}."""
@@ -980,15 +982,15 @@ class Converter:
         if max_records < 1:
             raise ValueError("max_records must be at least 1")
         lo, hi = 0, _mg.MAX_LEVEL                         # the finest level in [lo, hi] that meets the budget, if hi does
-        met = self.merge_count(hi, max_group, min_axis_dot) <= max_records
+        met = self.merge_count(hi, max_group, min_axis_dot, unsigned_axis) <= max_records
         if met:
             while lo < hi:
                 mid = (lo + hi) // 2
-                if self.merge_count(mid, max_group, min_axis_dot) <= max_records:
+                if self.merge_count(mid, max_group, min_axis_dot, unsigned_axis) <= max_records:
                     hi = mid
                 else:
                     lo = mid + 1
-        out = self.merge(hi, max_group, min_axis_dot)
+        out = self.merge(hi, max_group, min_axis_dot, unsigned_axis=unsigned_axis)
         out.update(level=hi, met=met)
         return out
 
@@ -1018,15 +1020,15 @@ class Converter:
         return out
 
     # ---- level-of-detail tree and its cut (m2s_lod_*) ------------------------------------------------------------------------------------
-    def lod_build(self, levels=(1, 2, 3, 4, 5, 6, 7, 8), max_group: int = 4, min_axis_dot: float = 0.5) -> dict:
+    def lod_build(self, levels=(1, 2, 3, 4, 5, 6, 7, 8), max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> dict:
         """Build the resident level-of-detail tree over the context's current records (m2s_lod_build; the pin is in include/m2s.h): they
         are the leaves, and step s merges what the previous step left at merge level levels[s] (0..10, non-decreasing, at most 16) with
-        merge()'s max_group and min_axis_dot; every step that merges something adds a tree level.  The coarsest level is the context's
+        merge()'s max_group, min_axis_dot and unsigned_axis; every step that merges something adds a tree level.  The coarsest level is the context's
         records afterwards; the tree is a copy and outlives them.  The default chain is an untuned guess, like max_group and min_axis_dot.
         -> {"leaves", "nodes", "levels": tree levels, the leaves included, "skipped": steps that merged nothing, "first": first node of
         every level and the node count behind them}."""
         from . import lod as _ld
-        pc = _ld.build_to_c(levels, max_group, min_axis_dot)
+        pc = _ld.build_to_c(levels, max_group, min_axis_dot, unsigned_axis)
         v = (C.c_uint64 * 4)()
         self._check(self._L.m2s_lod_build(self._h, C.byref(pc), v))
         out = {name: int(v[k]) for k, name in enumerate(_ld.BUILD_COUNTS)}

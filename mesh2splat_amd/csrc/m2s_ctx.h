@@ -435,7 +435,7 @@ void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh);
 // What m2s_merge does behind its argument checks (level 0..10, max_group 2..64, no NaN), m2s_lod_build once per step; the counts are
 // left in last_merge_counts.  Dry: only the counts; IfAny: as Dry where no segment has two members, as Apply otherwise.
 enum class MergeMode { Apply, Dry, IfAny };
-m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode);
+m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode, bool unsigned_axis);
 // m2s_meshdepth.cpp
 // What the mesh depth prepass and the visibility stage of the mesh render pass share: clear, setup + in-place lanes, clipper + binning,
 // tile raster over `image` (float[W * H], or uint64[W * H] when vis), synchronous.  ms: the three stage times (profiling on);

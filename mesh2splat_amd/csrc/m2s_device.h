@@ -315,14 +315,15 @@ constexpr uint32_t kMergeTotalsWords = 2;  // segments, segments of two members 
 size_t merge_scan_temp_bytes(uint32_t n);
 // keys / perm: the sorted keys and the permutation of compact_keys_and_sort (n words each).  flag, run_start: n words each, packed,
 // sums: n 64-bit words each of work area; seg_start: n + 1 words, afterwards the first sorted position of every segment and n behind
-// the last; totals: kMergeTotalsWords; temp: merge_scan_temp_bytes(n).  level 0..10, max_group >= 1, n > 0.
+// the last; totals: kMergeTotalsWords; temp: merge_scan_temp_bytes(n).  level 0..10, max_group >= 1, n > 0.  unsigned_axis: the
+// M2S_MERGE_UNSIGNED_AXIS instances of k_merge_heads / k_merge_reduce (pins 2u, 5u), here and in merge_reduce.
 hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_t* perm, uint32_t n, uint32_t level, uint32_t max_group, float min_axis_dot,
                           uint32_t* flag, uint32_t* run_start, unsigned long long* packed, unsigned long long* sums, uint32_t* seg_start, uint32_t* totals,
-                          void* temp, size_t temp_bytes, hipStream_t st);
+                          void* temp, size_t temp_bytes, bool unsigned_axis, hipStream_t st);
 // k_merge_reduce, one lane per segment: out[s] = the parent of segment s (a copy of its member where it has one), map[i] = s for every
 // member i.  out: `segments` records, not the memory rec points into; map: n words.
 hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
-                        uint32_t* map, hipStream_t st);
+                        uint32_t* map, bool unsigned_axis, hipStream_t st);
 
 // ---- level-of-detail tree and its cut (m2s_lod.hip) ------------------------------------------------------------------------------------
 // k_lod_link.  parent[t] = offset + map[t] for t < n_map (map NULL: M2S_LOD_NO_PARENT, the last level); bounds[t] = (position.xyz,

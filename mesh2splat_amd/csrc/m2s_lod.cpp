@@ -54,13 +54,14 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     }
     if (p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "max_group outside 2..64");
     if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
-    if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
+    if (p->flags & ~(uint32_t)M2S_MERGE_UNSIGNED_AXIS) return fail(c, M2S_ERR_INVALID, "flags other than M2S_MERGE_UNSIGNED_AXIS");
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
     if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
     const uint64_t n0 = c->last_stored;
     if (n0 >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
     const uint32_t R = c->last_R;
+    const bool unsigned_axis = (p->flags & M2S_MERGE_UNSIGNED_AXIS) != 0;   // (every step, the ones that merge nothing included)
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->lod_build_ev.ensure(c->err));
     c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
@@ -76,7 +77,7 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     }
     for (uint32_t s = 0; s < p->n_steps; ++s) {
         const uint64_t below = first[levels - 1], cnt = first[levels] - below;
-        M2S_TRY(merge_run(c, p->levels[s], p->max_group, p->min_axis_dot, MergeMode::IfAny));
+        M2S_TRY(merge_run(c, p->levels[s], p->max_group, p->min_axis_dot, MergeMode::IfAny, unsigned_axis));
         const uint64_t after = c->last_merge_counts[1];
         if (after == cnt) { ++skipped; continue; }                      // (nothing merged and nothing changed: no level)
         const uint64_t total = first[levels] + after;

@@ -22,7 +22,8 @@ bool merge_map_valid(const m2s_ctx* c) {
 namespace m2s_host {
 
 // The body of m2s_merge behind its argument checks (m2s_lod_build runs it once per step): level 0..10, max_group 2..64, no NaN.
-m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode) {
+// unsigned_axis (M2S_MERGE_UNSIGNED_AXIS) goes to both launches: the heads (pin 2u) and the reduction (pin 5u).
+m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode, bool unsigned_axis) {
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
     if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
@@ -57,7 +58,7 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
                                         c->d_compact_temp.cap(), ev, c->stream));
         HIPCHK(c, hipEventRecord(ev[3], c->stream));
         HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, level, max_group, min_axis_dot, m, m + mcap, packed, sums, seg_start,
-                                 c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), c->stream));
+                                 c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), unsigned_axis, c->stream));
         HIPCHK(c, hipEventRecord(ev[4], c->stream));
         uint32_t h[kMergeTotalsWords] = {}, skipped = 0;
         HIPCHK(c, hipMemcpyAsync(h, c->d_merge_totals, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -80,7 +81,7 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
             const void* src = c->last_records;
             if (!in_pool) M2S_TRY(ensure_records(c, segments));
             float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
-            HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, c->stream));
+            HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, unsigned_axis, c->stream));
             if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, segments * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipEventRecord(ev[5], c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -113,9 +114,11 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
     if (!c || !p) return M2S_ERR_INVALID;
     if (p->level > 10 || p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "level above 10 or max_group outside 2..64");
     if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
-    if ((p->flags & ~(uint32_t)M2S_MERGE_DRY_RUN) || p->reserved[0] != 0 || p->reserved[1] != 0)
+    // (bit 1 names nothing: callers were promised that flags 2 and 3 are refused, so the second flag is bit 2)
+    if ((p->flags & ~(uint32_t)(M2S_MERGE_DRY_RUN | M2S_MERGE_UNSIGNED_AXIS)) || p->reserved[0] != 0 || p->reserved[1] != 0)
         return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
-    M2S_TRY(merge_run(c, p->level, p->max_group, p->min_axis_dot, (p->flags & M2S_MERGE_DRY_RUN) ? MergeMode::Dry : MergeMode::Apply));
+    M2S_TRY(merge_run(c, p->level, p->max_group, p->min_axis_dot, (p->flags & M2S_MERGE_DRY_RUN) ? MergeMode::Dry : MergeMode::Apply,
+                      (p->flags & M2S_MERGE_UNSIGNED_AXIS) != 0));
     if (out_counts) std::memcpy(out_counts, c->last_merge_counts, sizeof(c->last_merge_counts));
     return M2S_OK;
 }

@@ -24,6 +24,8 @@ __device__ __forceinline__ void quat_axis3(float4 q, float& a0, float& a1, float
 }
 
 // Pin 2.  flag[j] = j where sorted position j starts a run, else 0 (the inclusive maximum of the flags is every position's run start).
+// kUnsigned (M2S_MERGE_UNSIGNED_AXIS, pin 2u): the same d, its sign dropped before the comparison.
+template <bool kUnsigned>
 __global__ void __launch_bounds__(kBlock) k_merge_heads(const float4* __restrict__ rec, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm,
                                                         uint32_t n, uint32_t shift, float min_axis_dot, uint32_t* __restrict__ flag) {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
@@ -37,7 +39,7 @@ __global__ void __launch_bounds__(kBlock) k_merge_heads(const float4* __restrict
             quat_axis3(rec[(size_t)perm[j] * 6 + 4], a0, a1, a2);
             quat_axis3(rec[(size_t)perm[j - 1] * 6 + 4], b0, b1, b2);
             const float d = ((a0 * b0) + a1 * b1) + a2 * b2;
-            head = !(d >= min_axis_dot);
+            head = !((kUnsigned ? fabsf(d) : d) >= min_axis_dot);
         }
     }
     flag[j] = head ? j : 0u;
@@ -97,6 +99,8 @@ __device__ __forceinline__ bool tangent_of(D3 v, D3 nb, D3& t) {
 
 // Pins 4 - 6.  Lane s = segment s: members perm[seg_start[s]] .. perm[seg_start[s + 1] - 1], at most 64.  Two walks: the weights' sum,
 // the centroid and the plane first (the moments are taken about the one and in the other), then everything else.  The second walk finds its records in L2.
+// kUnsigned (pin 5u): the first walk turns every member's r_3 onto the side of the oriented r_3 of the member before it, then sums it.
+template <bool kUnsigned>
 __global__ void __launch_bounds__(kBlock) k_merge_reduce(const float4* __restrict__ rec, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ seg_start,
                                                          const uint32_t* __restrict__ totals, float4* __restrict__ out, uint32_t* __restrict__ map) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
@@ -116,6 +120,7 @@ __global__ void __launch_bounds__(kBlock) k_merge_reduce(const float4* __restric
     // walk 1: W, the centroid and the plane's normal, for both weightings (the area, and 1 where the areas add up to nothing)
     double W = 0.0;
     D3 sw = { 0, 0, 0 }, s1 = { 0, 0, 0 }, nsum = { 0, 0, 0 }, n1 = { 0, 0, 0 };
+    [[maybe_unused]] D3 prev = { 0, 0, 0 };   // o_{i-1}; zero in front of the first member, which therefore never flips
     for (uint32_t j = a; j < b; ++j) {
         const uint32_t i = perm[j];
         const float4* g = rec + (size_t)i * 6;
@@ -123,6 +128,10 @@ __global__ void __launch_bounds__(kBlock) k_merge_reduce(const float4* __restric
         const D3 d = d3(g[0]) - p1;
         D3 q1, q2, q3;
         quat_rows(g[4], q1, q2, q3);
+        if constexpr (kUnsigned) {
+            if (dot(q3, prev) < 0.0) q3 = { -q3.x, -q3.y, -q3.z };   // (false for a zero and for a NaN: no flip)
+            prev = q3;
+        }
         const double w = (double)scl.x * (double)scl.y;
         W += w;
         sw = sw + w * d;
@@ -220,10 +229,11 @@ size_t merge_scan_temp_bytes(uint32_t n) {
 
 hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_t* perm, uint32_t n, uint32_t level, uint32_t max_group, float min_axis_dot,
                           uint32_t* flag, uint32_t* run_start, unsigned long long* packed, unsigned long long* sums, uint32_t* seg_start, uint32_t* totals,
-                          void* temp, size_t temp_bytes, hipStream_t st) {
+                          void* temp, size_t temp_bytes, bool unsigned_axis, hipStream_t st) {
     if (!n) return hipErrorInvalidValue;
     const dim3 grid((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_merge_heads, grid, dim3(kBlock), 0, st, rec, keys, perm, n, 3u * level, min_axis_dot, flag);
+    if (unsigned_axis) hipLaunchKernelGGL(k_merge_heads<true>, grid, dim3(kBlock), 0, st, rec, keys, perm, n, 3u * level, min_axis_dot, flag);
+    else hipLaunchKernelGGL(k_merge_heads<false>, grid, dim3(kBlock), 0, st, rec, keys, perm, n, 3u * level, min_axis_dot, flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((e = rocprim::inclusive_scan(temp, temp_bytes, (const uint32_t*)flag, run_start, (size_t)n, rocprim::maximum<uint32_t>(), st)) != hipSuccess) return e;
@@ -236,9 +246,11 @@ hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_
 }
 
 hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
-                        uint32_t* map, hipStream_t st) {
+                        uint32_t* map, bool unsigned_axis, hipStream_t st) {
     if (!segments) return hipSuccess;
-    hipLaunchKernelGGL(k_merge_reduce, dim3((segments + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
+    const dim3 grid((segments + kBlock - 1) / kBlock);
+    if (unsigned_axis) hipLaunchKernelGGL(k_merge_reduce<true>, grid, dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
+    else hipLaunchKernelGGL(k_merge_reduce<false>, grid, dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@ import numpy as np
 MAX_STEPS = 16                                               # M2S_LOD_MAX_STEPS
 NO_PARENT = 0xFFFFFFFF                                       # M2S_LOD_NO_PARENT
 DRY_RUN = 1                                                  # M2S_LOD_DRY_RUN
+UNSIGNED_AXIS = 4                                            # M2S_MERGE_UNSIGNED_AXIS: the one value m2s_lod_build_params.flags takes beside 0
 DEFAULT_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8)
 BUILD_COUNTS = ("leaves", "nodes", "levels", "skipped")      # m2s_lod_build's out_counts, in order
 SELECT_COUNTS = ("nodes", "selected", "selected_leaves", "refine")   # m2s_lod_select's
@@ -20,9 +21,18 @@ PLANES = {0: (np.float32, 24), 1: (np.uint32, None), 2: (np.float32, 4)}    # m2
 
 
 class LodBuildParamsC(C.Structure):
-    """== m2s_lod_build_params (include/m2s.h)."""
+    """== m2s_lod_build_params (include/m2s.h).  The last word is the header's `flags`; it keeps the name it had while it was reserved,
+    and `flags` reads and writes the same word."""
     _fields_ = [("n_steps", C.c_uint32), ("levels", C.c_uint32 * MAX_STEPS), ("max_group", C.c_uint32), ("min_axis_dot", C.c_float),
                 ("reserved", C.c_uint32)]
+
+    @property
+    def flags(self) -> int:
+        return int(self.reserved)
+
+    @flags.setter
+    def flags(self, value: int) -> None:
+        self.reserved = int(value)
 
 
 class LodSelectParamsC(C.Structure):
@@ -31,7 +41,7 @@ class LodSelectParamsC(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5) -> LodBuildParamsC:
+def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> LodBuildParamsC:
     levels = [int(v) for v in levels]
     if len(levels) > MAX_STEPS:
         raise ValueError(f"at most {MAX_STEPS} steps")
@@ -39,6 +49,7 @@ def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 
     c.n_steps = len(levels)
     c.levels[:len(levels)] = levels
     c.max_group, c.min_axis_dot = int(max_group), float(min_axis_dot)
+    c.flags = UNSIGNED_AXIS if unsigned_axis else 0
     return c
 
 

@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 
 DRY_RUN = 1                                                  # M2S_MERGE_DRY_RUN
+UNSIGNED_AXIS = 4                                            # M2S_MERGE_UNSIGNED_AXIS (bit 1 names nothing: flags 2 and 3 stay refused)
+VALID_FLAGS = (0, DRY_RUN, UNSIGNED_AXIS, DRY_RUN | UNSIGNED_AXIS)
 MAX_LEVEL = 10
 COUNTS = ("before", "after", "merged", "invalid")            # m2s_merge's out_counts, in order
 
@@ -18,7 +20,8 @@ class MergeParamsC(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
-def to_c(level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False) -> MergeParamsC:
+def to_c(level: int, max_group: int = 4, min_axis_dot: float = 0.5, dry_run: bool = False, unsigned_axis: bool = False) -> MergeParamsC:
     c = MergeParamsC()
-    c.level, c.max_group, c.min_axis_dot, c.flags = int(level), int(max_group), float(min_axis_dot), DRY_RUN if dry_run else 0
+    c.level, c.max_group, c.min_axis_dot = int(level), int(max_group), float(min_axis_dot)
+    c.flags = (DRY_RUN if dry_run else 0) | (UNSIGNED_AXIS if unsigned_axis else 0)
     return c

@@ -6,10 +6,17 @@ against the mesh for the cut, for the full records and for merge_to_budget to th
 
     python tools/lod_probe.py [--tau 1,1024] [--factors 1,2,4,8] [--frames] [--reps 5] [--warmup 2] [--out profiles/lod/probe.json]
     python tools/lod_probe.py --world-units [--tau 1,2,4] [--frames] --out profiles/lod/probe_world.json
+    python tools/lod_probe.py --world-units --unsigned-axis [--frames] --out profiles/lod/probe_unsigned.json
 
 --world-units: every conversion is followed by m2s_records_to_world_units, so the tree's edges are world lengths and tau_px counts
 screen pixels (default --tau 1,2,4); the result also carries the pass's own time (in place, and out of place from adopted memory) beside
 its two yardsticks on the same records: m2s_refit_apply with every record updated, and a device-to-device copy of the records.
+
+--unsigned-axis: the tree with and without M2S_MERGE_UNSIGNED_AXIS, alternating in this one process: for every cut the records are
+converted again and the tree is built for one mode, then for the other (the context keeps one tree), so the build is timed
+2 x cuts x (warmup + reps) times; per mode the nodes per level, the build's median and its runs one by one, and per cut the counts,
+the stages and — with --frames — the frame of the cut beside the frame of the full records, both scored against the mesh.  The
+yardsticks of the plain run (m2s_prune, merge_to_budget, the pass's own time) are left out.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
 tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
@@ -28,6 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tau", default="")
     ap.add_argument("--world-units", action="store_true")
+    ap.add_argument("--unsigned-axis", action="store_true")
     ap.add_argument("--factors", default="1,2,4,8")
     ap.add_argument("--frames", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
@@ -95,6 +103,57 @@ def main():
                     out[key].append(v)
         return {key: statistics.median(v) for key, v in out.items()}
 
+    def cut_rows(eye, focal, tau, cam):
+        rows, counts = [], None
+        for k in range(a.warmup + a.reps):
+            got = conv.lod_select(eye, focal, tau, cam.near)
+            assert counts is None or got == counts                                    # integer sums: the same from run to run
+            counts = got
+            ms = conv.last_lod_select_stage_ms()
+            ms["total"] = ms["sweep"] + ms["scan_ids"] + ms["compact"]
+            if k >= a.warmup:
+                rows.append(ms)
+        return counts, median_of(rows)
+
+    if a.unsigned_axis:
+        records = convert()
+        names = {False: "signed", True: "unsigned"}
+        builds, build_ms = {False: None, True: None}, {False: [], True: []}
+        res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup, "world_units": a.world_units, "cuts": []}
+        for tau in [float(v) for v in a.tau.split(",")]:
+            for f in [float(v) for v in a.factors.split(",")]:
+                cam = camera(f)
+                eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
+                row = {"tau_px": tau, "factor": f}
+                for m in (False, True):
+                    for k in range(a.warmup + a.reps):
+                        convert()
+                        got = conv.lod_build(unsigned_axis=m)
+                        assert builds[m] is None or got == builds[m]
+                        builds[m] = got
+                        if k >= a.warmup:
+                            build_ms[m].append(conv.last_lod_build_ms)
+                    counts, stage = cut_rows(eye, focal, tau, cam)
+                    row[names[m]] = {"counts": counts, "select_stage_ms": stage}
+                    if a.frames:
+                        row[names[m]]["frame_cut"] = dict(zip(("pass_ms", "score"), frame(cam)))
+                if a.frames:
+                    convert()
+                    row["frame_full"] = dict(zip(("pass_ms", "score"), frame(cam)))
+                res["cuts"].append(row)
+                print(json.dumps(row), flush=True)
+        for m in (False, True):
+            first = builds[m]["first"]
+            res["build_" + names[m]] = {"counts": {k: v for k, v in builds[m].items() if k != "first"},
+                                        "per_level_nodes": [first[l + 1] - first[l] for l in range(len(first) - 1)],
+                                        "ms": statistics.median(build_ms[m]), "ms_min": min(build_ms[m]), "ms_max": max(build_ms[m]), "runs": len(build_ms[m])}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        conv.close()
+        return
     records = conv.convert(R)
     build_ms, build = [], None
     for k in range(a.warmup + a.reps):
@@ -117,16 +176,8 @@ def main():
         for f in [float(v) for v in a.factors.split(",")]:
             cam = camera(f)
             eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
-            rows, counts = [], None
-            for k in range(a.warmup + a.reps):
-                got = conv.lod_select(eye, focal, tau, cam.near)
-                assert counts is None or got == counts                                # integer sums: the same from run to run
-                counts = got
-                ms = conv.last_lod_select_stage_ms()
-                ms["total"] = ms["sweep"] + ms["scan_ids"] + ms["compact"]
-                if k >= a.warmup:
-                    rows.append(ms)
-            row = {"tau_px": tau, "factor": f, "counts": counts, "select_stage_ms": median_of(rows)}
+            counts, stage = cut_rows(eye, focal, tau, cam)
+            row = {"tau_px": tau, "factor": f, "counts": counts, "select_stage_ms": stage}
             ids = conv.download_lod_nodes()
             if a.frames:
                 row["frame_cut"] = dict(zip(("pass_ms", "score"), frame(cam)))

@@ -90,6 +90,7 @@ struct Options {
     double lod_pixels = -1.0;                                      // --lod-pixels t: every --preview / --score camera takes its cut at tau_px = t first (m2s_lod_select)
     double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
     bool lod() const { return !lod_levels.empty(); }
+    bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
     bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
     bool cap_set = false;                                          // an explicit --cap (without one, --budget converts with the cap lifted)
@@ -111,7 +112,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -170,6 +171,11 @@ void usage() {
                  "  surface once, as coarse as t pixels allow; the frame is drawn from the cut.  Prints ONE line `lod: {...}` of JSON per file:\n"
                  "  levels, nodes, per_level_nodes, skipped, tau_px, build_ms, views (per camera, the preview's first: selected, per_level).\n"
                  "  With --batch, which draws no frames, --score K names the cameras and every cut is a dry run.  Not with --gpus N > 1.\n"
+                 "--merge-unsigned-axis, with --merge-level, --merge-to or --lod-levels: the sign of a record's third axis carries no meaning\n"
+                 "  (M2S_MERGE_UNSIGNED_AXIS: a group ends where |dot| is below d, and the members' axes are turned onto one side before they\n"
+                 "  are averaged).  A conversion stores the two triangles of a flat quad with opposite signs, which the viewer does not see; with\n"
+                 "  this flag they merge.  The `merge:` and `lod:` lines then carry \"unsigned_axis\": true.  Works with --batch; not with\n"
+                 "  --gpus N > 1.\n"
                  "--view-distance f (0.25..64, default 1: what it was): the --preview and --score eyes stand at f x the camera rule's distance\n"
                  "  and the far plane is f x as far; near stays.\n"
                  "--world-units: right after the conversion, in front of --prune, --budget, --merge-*, --refit, --bake-light, --score, --preview,\n"
@@ -312,6 +318,7 @@ int lod_build(m2s_ctx* ctx, const Options& o, LodReport* rep) {
     for (size_t s = 0; s < o.lod_levels.size(); ++s) bp.levels[s] = o.lod_levels[s];
     bp.max_group = (uint32_t)o.merge_group;
     bp.min_axis_dot = (float)o.merge_dot;
+    bp.flags = o.merge_unsigned_axis ? (uint32_t)M2S_MERGE_UNSIGNED_AXIS : 0u;
     uint32_t levels = 0;
     uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
     if (m2s_lod_build(ctx, &bp, rep->build) != M2S_OK || m2s_lod_levels(ctx, &levels, first) != M2S_OK) return 1;
@@ -342,8 +349,9 @@ void lod_print(const Options& o, const LodReport& rep) {
     for (size_t l = 0; l + 1 < rep.first.size(); ++l) per += std::string(l ? ", " : "") + std::to_string((unsigned long long)(rep.first[l + 1] - rep.first[l]));
     char tau[40];
     std::snprintf(tau, sizeof tau, "%.9g", (double)(float)o.lod_pixels);
-    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]}\n",
-                levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str());
+    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s}\n",
+                levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
+                o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
 }
 
 // GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path` — with
@@ -594,13 +602,13 @@ int run_budget(m2s_ctx* ctx, uint32_t importance, float min_weight, uint32_t min
 
 // --merge-level L / --merge-to N: m2s_merge over the context's records (Converter.merge / .merge_to_budget do the same); prints one JSON line
 int run_merge(m2s_ctx* ctx, const Options& o) {
-    m2s_merge_params mp = { 0, (uint32_t)o.merge_group, (float)o.merge_dot, 0, { 0, 0 } };
+    m2s_merge_params mp = { 0, (uint32_t)o.merge_group, (float)o.merge_dot, o.merge_unsigned_axis ? (uint32_t)M2S_MERGE_UNSIGNED_AXIS : 0u, { 0, 0 } };
     uint64_t c[4] = {};
     bool met = true;
     if (o.merge_to > 0) {
         auto count = [&](uint32_t level, uint64_t* after) {
             m2s_merge_params dry = mp;
-            dry.level = level; dry.flags = M2S_MERGE_DRY_RUN;
+            dry.level = level; dry.flags |= M2S_MERGE_DRY_RUN;
             uint64_t d[4] = {};
             if (m2s_merge(ctx, &dry, d) != M2S_OK) return false;
             *after = d[1];
@@ -624,9 +632,10 @@ int run_merge(m2s_ctx* ctx, const Options& o) {
     char target[32] = "null";
     if (o.merge_to > 0) std::snprintf(target, sizeof(target), "%lld", o.merge_to);
     std::printf("merge: {\"level\": %u, \"max_group\": %u, \"min_axis_dot\": %s, \"target\": %s, \"met\": %s, \"before\": %llu, \"after\": %llu, "
-                "\"merged\": %llu, \"invalid\": %llu, \"stage_ms\": [%.4f, %.4f, %.4f]}\n",
+                "\"merged\": %llu, \"invalid\": %llu, \"stage_ms\": [%.4f, %.4f, %.4f]%s}\n",
                 mp.level, mp.max_group, json_num((double)mp.min_axis_dot).c_str(), target, met ? "true" : "false", (unsigned long long)c[0],
-                (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], ms[0], ms[1], ms[2]);
+                (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], ms[0], ms[1], ms[2],
+                o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
     return 0;
 }
 
@@ -1227,6 +1236,7 @@ int main(int argc, char** argv) {
         else if (a == "--bake-light") o.bake_light = true;
         else if (a == "--compact") o.compact = true;
         else if (a == "--world-units") o.world_units = true;
+        else if (a == "--merge-unsigned-axis") o.merge_unsigned_axis = true;
         else if (a == "--bake-degree") { o.bake_degree = std::atoi(next()); if (o.bake_degree < 0 || o.bake_degree > 3) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
@@ -1245,6 +1255,7 @@ int main(int argc, char** argv) {
     if (o.prune_views > 0 && (o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }   // (multi-rank pruning: out of scope)
     if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
     if (o.merging() && (o.gpus > 1 || o.force_sharded || (o.merge_level >= 0 && o.merge_to > 0))) { usage(); return 2; }   // (multi-rank merges: out of scope)
+    if (o.merge_unsigned_axis && !o.merging() && !o.lod()) { usage(); return 2; }   // (a mode of those passes, refused with --gpus N > 1 as they are)
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.world_units && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (a rank's slice writer and the gather hand on the density)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
