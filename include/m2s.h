@@ -745,6 +745,43 @@ m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
 const void* m2s_device_lod_nodes(const m2s_ctx* ctx);
 m2s_status m2s_download_lod_nodes(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
 
+/* The cut that fits a budget: the finest cut of m2s_lod_select that holds at most max_records records for this camera, found on the
+ * device in a handful of passes over the bounds (tests/lod_budget_ref.py restates it).  Pinned:
+ *  1. Keys.  A key k is the bits of a non-negative finite float, 0 .. 0x7F7FFFFF; "at key k" means m2s_lod_select's comparison (pin 1
+ *     of the cut) evaluated with tau_px = the float whose bits are k.  tau_px * tau_px and its product with d2 do not decrease with k,
+ *     roundings included, so per node the comparison is true below one key and false from it on.
+ *  2. T(i) is the smallest key at which node i does not refine (at 0x7F7FFFFF none does: tau_px * tau_px is +inf, the product +inf or
+ *     NaN).  H(i) is the minimum of T over the proper ancestors of i, 0xFFFFFFFF on the last level.  L(i) is 0 for a leaf, else T(i).
+ *     Pin 2 of the cut then reads: node i is selected at key k iff L(i) <= k < H(i), and
+ *       count(k) = #{i: L(i) < H(i), L(i) <= k} - #{i: L(i) < H(i), H(i) <= k}
+ *     is the number of records the cut at key k holds.  It does not increase with k; count(0x7F7FFFFF) is the size of the last level.
+ *  3. Result.  N_eff = max(max_records, nodes of the last level); key* = the smallest key with count(key) <= N_eff, raised to the key
+ *     of tau_min_px where that is larger; tau_px = the float of key*; met = (count(key*) <= max_records); selected_finer =
+ *     count(key* - 1), the cut that did not fit, or count(key*) where key* is 0 or the floor decided.
+ *  4. Every effect on the context is m2s_lod_select's at that tau_px: out_counts, m2s_last_lod_level_counts, m2s_device_lod_nodes, the
+ *     record bytes and their order, what is invalidated, the resolutionTarget handed back, the tree untouched, and with M2S_LOD_DRY_RUN
+ *     nothing of the context changes.  A caller who passes the returned tau_px to m2s_lod_select gets the same bytes.
+ *  5. An empty tree gives tau_px = tau_min_px, met = 1 and 0 selected.
+ * Integer sums throughout: the same result from run to run.  Synchronous.  Errors as m2s_lod_select; in addition max_records == 0 and
+ * a tau_min_px that is negative or not finite are M2S_ERR_INVALID.  `out` may be NULL. */
+typedef struct m2s_lod_budget_params {
+    float    camera_position[3];  /* as m2s_lod_select_params */
+    float    focal_px;            /* finite, > 0 */
+    float    near;                /* finite, > 0 */
+    float    tau_min_px;          /* finite, >= 0: never cut finer than this, even where the budget allows (0: no floor) */
+    uint32_t max_records;         /* >= 1 */
+    uint32_t flags;               /* M2S_LOD_DRY_RUN; other bits 0 */
+} m2s_lod_budget_params;          /* 32 bytes */
+typedef struct m2s_lod_budget_result {
+    float    tau_px;              /* the tau the cut was taken at */
+    uint32_t met;                 /* 1: selected <= max_records */
+    uint64_t selected_finer;      /* count at the next smaller key (the cut that did not fit); = selected where key* is 0 or the floor decided */
+} m2s_lod_budget_result;          /* 16 bytes */
+m2s_status m2s_lod_select_budget(m2s_ctx* ctx, const m2s_lod_budget_params* params, m2s_lod_budget_result* out, uint64_t out_counts[4]);
+/* The stages (ms) of the last profiled m2s_lod_select_budget: [0] thresholds + ancestor minima, [1] the four select rounds, [2] the cut
+ * (m2s_lod_select's three stages summed). */
+m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+
 /* ---- world units (no counterpart in the reference, which keeps the resolutionTarget beside its records) ---------------------------- */
 /* Brings the context's current records to world units: scale[k] = scale[k] / (float)R for k = 0, 1, 2, with R the records'
  * resolutionTarget; afterwards the records' resolutionTarget is 1.  A conversion stores scale = (|Ju|, |Jv|, 1e-7) and leaves the

@@ -1062,6 +1062,25 @@ class Converter:
         out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
         return out
 
+    def lod_select_budget(self, camera_position, focal_px: float, max_records: int, tau_min_px: float = 0.0, near: float = 1e-3,
+                          dry_run: bool = False) -> dict:
+        """Take the finest cut of lod_select() that holds at most `max_records` records for this camera, never finer than tau_min_px: the
+        tau_px is found on the device, without a bisection on the host (m2s_lod_select_budget; the pin is in include/m2s.h).  A budget
+        below the size of the coarsest level returns that level, with "met" False.  Everything else is lod_select()'s at the returned
+        tau_px.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
+        next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}."""
+        from . import lod as _ld
+        pc = _ld.budget_to_c(camera_position, focal_px, max_records, tau_min_px, near, dry_run)
+        res = _ld.LodBudgetResultC()
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_lod_select_budget(self._h, C.byref(pc), C.byref(res), v))
+        out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
+        per = (C.c_uint64 * (_ld.MAX_STEPS + 1))()
+        self._check(self._L.m2s_last_lod_level_counts(self._h, per))
+        out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
+        out["tau_px"], out["met"], out["selected_finer"] = float(res.tau_px), bool(res.met), int(res.selected_finer)
+        return out
+
     def download_lod(self, which: int) -> np.ndarray:
         """A plane of the tree (m2s_download_lod): 0 the node records (nodes, 24) float32, 1 parent (nodes,) uint32 with 0xFFFFFFFF on the
         last level, 2 the bounds (nodes, 4) float32: position and longer edge."""
@@ -1101,6 +1120,12 @@ class Converter:
         ms = (C.c_float * 3)()
         self._check(self._L.m2s_last_lod_select_stage_ms(self._h, ms))
         return {"sweep": float(ms[0]), "scan_ids": float(ms[1]), "compact": float(ms[2])}
+
+    @property
+    def last_lod_budget_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_lod_budget_stage_ms(self._h, ms))
+        return {"thresholds": float(ms[0]), "select": float(ms[1]), "cut": float(ms[2])}
 
     # ---- world units (m2s_records_to_world_units) ----------------------------------------------------------------------------------------
     @property

@@ -13,7 +13,7 @@
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
 //   m2s_worldunits.cpp  m2s_records_to_world_units: a conversion's scales divided by its resolutionTarget
-//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select): a chain of merges kept and linked
+//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): a chain of merges kept and linked
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -266,6 +266,11 @@ struct m2s_ctx {
     uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
     float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
     m2s_host::EventSet<4> lod_ev;
+    // the cut that fits a budget (m2s_lod_select_budget): the keys (L, H) per node and the words of the search
+    m2s_host::DevBuf<uint2> d_lod_lh;
+    m2s_host::DevBuf<uint32_t> d_lod_budget_state;       // kLodBudgetStateWords
+    float last_lod_budget_stage_ms[3] = { 0, 0, 0 };     // thresholds, the four select rounds, the cut (profiling on)
+    m2s_host::EventSet<3> lod_budget_ev;
     // world units (m2s_worldunits.cpp)
     float last_world_units_ms = 0.0f;
     m2s_host::EventSet<2> wu_ev;

@@ -342,6 +342,21 @@ hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t
 // offsets = exclusive scan of flags (n words each); temp: prune_scan_temp_bytes(n)
 hipError_t lod_scan(const uint32_t* flags, uint32_t* offsets, uint32_t n, void* temp, size_t temp_bytes, hipStream_t st);
 
+// ---- the cut that fits a record budget (m2s_lodbudget.hip): a radix descent over two 32-bit key planes ---------------------------------
+// The search's words on the device: the digits of the key found so far, the count at the key just under the prefix's range, the count at
+// the key in front of the answer (written once a digit above 0 is chosen: the answer is not key 0); then per round kLodBudgetShards copies of 256 bins for L and 256 for H.
+constexpr uint32_t kLodBudgetShards = 4;   // (a power of two)
+constexpr uint32_t kLodBudgetPrefix = 0, kLodBudgetBelow = 1, kLodBudgetFiner = 2, kLodBudgetHist = 4;
+constexpr uint32_t kLodBudgetStateWords = kLodBudgetHist + 4 * kLodBudgetShards * 512;
+// One launch per level from the last to the leaves: lh[i] = (L, H), the keys (bits of tau_px) from which node i is no longer refined
+// (0 for a leaf) and from which one of its proper ancestors is not (0xFFFFFFFF on the last level); k.tau2 is not read.
+hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
+                          hipStream_t st);
+// The four histogram / pick rounds over the n nodes: afterwards state[kLodBudgetPrefix] is the smallest key whose cut holds at most
+// `budget` nodes (budget >= the nodes of the last level, n > 0), state[kLodBudgetFiner] the count at the key before it where
+// that key is not 0.  state: kLodBudgetStateWords, zeroed here.
+hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, uint32_t* state, hipStream_t st);
+
 // ---- world units (m2s_worldunits.hip) ------------------------------------------------------------------------------------------------
 // dst[i] = src[i] with scale[0..2] divided by (float)R (IEEE, correctly rounded), every other word with its bits, for the n records.
 // src == dst: in place, only the scale words move; else the two do not overlap.  R >= 1.

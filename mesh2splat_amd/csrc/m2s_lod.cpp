@@ -1,5 +1,6 @@
-// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select): host side of m2s_lod.hip.  The tree is
-// a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are copied into a node pool and linked by their maps; the
+// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): host side of
+// m2s_lod.hip and m2s_lodbudget.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
+// copied into a node pool and linked by their maps; the
 // cut's flags and offsets live where m2s_prune leaves its own, and the compaction and what follows it are m2s_prune's (m2s_contrib.cpp:
 // prune_compact_enqueue, prune_adopt).
 #include "m2s_ctx.h"
@@ -37,6 +38,77 @@ m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
     c->d_lod_nodes.swap(nodes);
     c->d_lod_parent.swap(parent);
     c->d_lod_bounds.swap(bounds);
+    return M2S_OK;
+}
+
+// The cut behind m2s_lod_select's checks of its arguments and the context's state (m2s_lod_select_budget takes its own through it).
+m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4]) {
+    const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
+    const bool prof = c->profiling;
+    const uint32_t levels = c->lod_levels;
+    const uint64_t N = c->lod_first[levels];
+    HIPCHK(c, hipSetDevice(c->device));
+    if (prof) M2S_TRY(c->lod_ev.ensure(c->err));
+    uint32_t h[kLodCountWords] = {};
+    uint64_t selected = 0;
+    if (N) {
+        M2S_TRY(c->d_lod_open.reserve(c->err, N, 1));
+        M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+        M2S_TRY(c->d_prune_u32.reserve(c->err, N, 2 * sizeof(uint32_t)));
+        if (!dry) {
+            M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)N), 16) + 2 * sizeof(unsigned long long), 1));
+            M2S_TRY(c->d_lod_ids.reserve(c->err, N, sizeof(uint32_t)));
+            c->lod_ids_of = nullptr;
+        }
+        uint32_t* const flags = c->d_prune_u32;
+        uint32_t* const offsets = flags + c->d_prune_u32.cap();
+        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[0], c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[1], c->stream));
+        if (!dry) {
+            HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
+            HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->d_lod_ids, c->stream));
+            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[2], c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t l = 0; l < levels; ++l) selected += h[l];
+        if (selected < 1 || selected > N || h[kLodRefineWord] > N) return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
+        if (!dry) {
+            M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
+            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[3], c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (prof) {
+            float* ms = c->last_lod_select_stage_ms;
+            ms[1] = ms[2] = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_ev[0], c->lod_ev[1]));
+            if (!dry) {
+                HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_ev[1], c->lod_ev[2]));
+                HIPCHK(c, hipEventElapsedTime(&ms[2], c->lod_ev[2], c->lod_ev[3]));   // (the round trip of the counts included)
+            }
+        }
+    } else {
+        if (!dry) {
+            c->lod_ids_of = nullptr;
+            M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (prof) c->last_lod_select_stage_ms[0] = c->last_lod_select_stage_ms[1] = c->last_lod_select_stage_ms[2] = 0.0f;
+    }
+    if (!dry) {
+        prune_adopt(c, selected, c->lod_R, false);
+        c->sh_valid = false;                    // (a plane of other records: dropped, as by m2s_merge)
+        c->lod_ids_of = c->last_records;
+        c->lod_ids_n = selected;
+        c->lod_ids_epoch = c->records_epoch;
+    }
+    c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
+    c->last_lod_select_counts[3] = h[kLodRefineWord];
+    for (uint32_t l = 0; l <= M2S_LOD_MAX_STEPS; ++l) c->last_lod_level_counts[l] = l < levels ? h[l] : 0;
+    if (out_counts) std::memcpy(out_counts, c->last_lod_select_counts, sizeof(c->last_lod_select_counts));
     return M2S_OK;
 }
 
@@ -132,7 +204,7 @@ m2s_status m2s_lod_release(m2s_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->lod_levels = 0;
-    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release();
+    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release();
     return M2S_OK;
 }
 
@@ -149,72 +221,76 @@ m2s_status m2s_lod_select(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t o
     if ((p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
+    return lod_cut(c, p, out_counts);
+}
+
+m2s_status m2s_lod_select_budget(m2s_ctx* c, const m2s_lod_budget_params* p, m2s_lod_budget_result* out, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!c || !p) return M2S_ERR_INVALID;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    if (!std::isfinite(p->tau_min_px) || !(p->tau_min_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_min_px is not finite or negative");
+    if (p->max_records < 1) return fail(c, M2S_ERR_INVALID, "max_records is 0");
+    if (p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) return fail(c, M2S_ERR_INVALID, "unknown flag bits");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
     const bool prof = c->profiling;
     const uint32_t levels = c->lod_levels;
-    const uint64_t N = c->lod_first[levels];
+    const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
+    uint32_t floor_key = 0, key = 0;
+    if (p->tau_min_px > 0.0f) std::memcpy(&floor_key, &p->tau_min_px, sizeof(floor_key));
+    uint32_t h[3] = {};                                                 // prefix, below, finer
     HIPCHK(c, hipSetDevice(c->device));
-    if (prof) M2S_TRY(c->lod_ev.ensure(c->err));
-    uint32_t h[kLodCountWords] = {};
-    uint64_t selected = 0;
     if (N) {
-        M2S_TRY(c->d_lod_open.reserve(c->err, N, 1));
-        M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
-        M2S_TRY(c->d_prune_u32.reserve(c->err, N, 2 * sizeof(uint32_t)));
-        if (!dry) {
-            M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)N), 16) + 2 * sizeof(unsigned long long), 1));
-            M2S_TRY(c->d_lod_ids.reserve(c->err, N, sizeof(uint32_t)));
-            c->lod_ids_of = nullptr;
-        }
-        uint32_t* const flags = c->d_prune_u32;
-        uint32_t* const offsets = flags + c->d_prune_u32.cap();
-        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[0], c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
-        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[1], c->stream));
-        if (!dry) {
-            HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
-            HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->d_lod_ids, c->stream));
-            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[2], c->stream));
-        }
-        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        M2S_TRY(c->d_lod_lh.reserve(c->err, N, sizeof(uint2)));
+        M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
+        if (prof) M2S_TRY(c->lod_budget_ev.ensure(c->err));
+        const uint32_t n_eff = (uint32_t)std::max<uint64_t>(p->max_records, last);
+        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[0], c->stream));
+        HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[1], c->stream));
+        HIPCHK(c, lod_budget_search(c->d_lod_lh, (uint32_t)N, n_eff, c->d_lod_budget_state, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[2], c->stream));
+        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (uint32_t l = 0; l < levels; ++l) selected += h[l];
-        if (selected < 1 || selected > N || h[kLodRefineWord] > N) return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
-        if (!dry) {
-            M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
-            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[3], c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        if (prof) {
-            float* ms = c->last_lod_select_stage_ms;
-            ms[1] = ms[2] = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_ev[0], c->lod_ev[1]));
-            if (!dry) {
-                HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_ev[1], c->lod_ev[2]));
-                HIPCHK(c, hipEventElapsedTime(&ms[2], c->lod_ev[2], c->lod_ev[3]));   // (the round trip of the counts included)
-            }
-        }
-    } else {
-        if (!dry) {
-            c->lod_ids_of = nullptr;
-            M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        if (prof) c->last_lod_select_stage_ms[0] = c->last_lod_select_stage_ms[1] = c->last_lod_select_stage_ms[2] = 0.0f;
+        key = h[kLodBudgetPrefix];
+        if (key > 0x7F7FFFFFu) return fail(c, M2S_ERR_HIP, "the budget search came back with no finite tau_px");
     }
-    if (!dry) {
-        prune_adopt(c, selected, c->lod_R, false);
-        c->sh_valid = false;                    // (a plane of other records: dropped, as by m2s_merge)
-        c->lod_ids_of = c->last_records;
-        c->lod_ids_n = selected;
-        c->lod_ids_epoch = c->records_epoch;
+    const bool by_floor = floor_key > key;
+    if (by_floor) key = floor_key;
+    m2s_lod_select_params sp = {};
+    std::memcpy(sp.camera_position, p->camera_position, sizeof(sp.camera_position));
+    sp.focal_px = p->focal_px;
+    std::memcpy(&sp.tau_px, &key, sizeof(key));
+    sp.near = p->near;
+    sp.flags = p->flags;
+    uint64_t counts[4] = {};
+    M2S_TRY(lod_cut(c, &sp, counts));
+    if (prof) {
+        float* ms = c->last_lod_budget_stage_ms;
+        ms[0] = ms[1] = 0.0f;
+        if (N) {
+            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_budget_ev[0], c->lod_budget_ev[1]));
+            HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_budget_ev[1], c->lod_budget_ev[2]));
+        }
+        ms[2] = (c->last_lod_select_stage_ms[0] + c->last_lod_select_stage_ms[1]) + c->last_lod_select_stage_ms[2];
     }
-    c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
-    c->last_lod_select_counts[3] = h[kLodRefineWord];
-    for (uint32_t l = 0; l <= M2S_LOD_MAX_STEPS; ++l) c->last_lod_level_counts[l] = l < levels ? h[l] : 0;
-    if (out_counts) std::memcpy(out_counts, c->last_lod_select_counts, sizeof(c->last_lod_select_counts));
+    if (out) {
+        out->tau_px = sp.tau_px;
+        out->met = counts[1] <= p->max_records ? 1u : 0u;
+        out->selected_finer = (!N || key == 0 || by_floor) ? counts[1] : h[kLodBudgetFiner];
+    }
+    if (out_counts) std::memcpy(out_counts, counts, sizeof(counts));
+    return M2S_OK;
+}
+
+m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) {
+    if (!c || !out_ms) return M2S_ERR_INVALID;
+    std::memcpy(out_ms, c->last_lod_budget_stage_ms, sizeof(c->last_lod_budget_stage_ms));
     return M2S_OK;
 }
 

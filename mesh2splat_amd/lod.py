@@ -1,5 +1,5 @@
-"""The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_levels` / `.download_lod` /
-`.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select): the ctypes mirrors of their parameters and the two numbers a
+"""The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_select_budget` / `.lod_levels` /
+`.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): the ctypes mirrors of their parameters and the two numbers a
 cut takes from a camera.  The pins are in include/m2s.h.
 
 The default chain of merge levels (1 .. 8), like max_group = 4 and min_axis_dot = 0.5, is a guess: nothing in the repository has
@@ -41,6 +41,17 @@ class LodSelectParamsC(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LodBudgetParamsC(C.Structure):
+    """== m2s_lod_budget_params (include/m2s.h)."""
+    _fields_ = [("camera_position", C.c_float * 3), ("focal_px", C.c_float), ("near", C.c_float), ("tau_min_px", C.c_float),
+                ("max_records", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LodBudgetResultC(C.Structure):
+    """== m2s_lod_budget_result (include/m2s.h)."""
+    _fields_ = [("tau_px", C.c_float), ("met", C.c_uint32), ("selected_finer", C.c_uint64)]
+
+
 def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> LodBuildParamsC:
     levels = [int(v) for v in levels]
     if len(levels) > MAX_STEPS:
@@ -57,6 +68,18 @@ def select_to_c(camera_position, focal_px: float, tau_px: float = 1.0, near: flo
     c = LodSelectParamsC()
     c.camera_position[:] = [float(v) for v in camera_position]
     c.focal_px, c.tau_px, c.near, c.flags = float(focal_px), float(tau_px), float(near), DRY_RUN if dry_run else 0
+    return c
+
+
+def budget_to_c(camera_position, focal_px: float, max_records: int, tau_min_px: float = 0.0, near: float = 1e-3,
+                dry_run: bool = False) -> LodBudgetParamsC:
+    max_records = int(max_records)
+    if not 0 <= max_records <= 0xFFFFFFFF:
+        raise ValueError("max_records outside 0..2^32-1")
+    c = LodBudgetParamsC()
+    c.camera_position[:] = [float(v) for v in camera_position]
+    c.focal_px, c.near, c.tau_min_px = float(focal_px), float(near), float(tau_min_px)
+    c.max_records, c.flags = max_records, DRY_RUN if dry_run else 0
     return c
 
 

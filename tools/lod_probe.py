@@ -7,6 +7,7 @@ against the mesh for the cut, for the full records and for merge_to_budget to th
     python tools/lod_probe.py [--tau 1,1024] [--factors 1,2,4,8] [--frames] [--reps 5] [--warmup 2] [--out profiles/lod/probe.json]
     python tools/lod_probe.py --world-units [--tau 1,2,4] [--frames] --out profiles/lod/probe_world.json
     python tools/lod_probe.py --world-units --unsigned-axis [--frames] --out profiles/lod/probe_unsigned.json
+    python tools/lod_probe.py --budget [--budgets 50000,200000,1000000] [--out profiles/lod/probe_budget.json]
 
 --world-units: every conversion is followed by m2s_records_to_world_units, so the tree's edges are world lengths and tau_px counts
 screen pixels (default --tau 1,2,4); the result also carries the pass's own time (in place, and out of place from adopted memory) beside
@@ -17,6 +18,11 @@ converted again and the tree is built for one mode, then for the other (the cont
 2 x cuts x (warmup + reps) times; per mode the nodes per level, the build's median and its runs one by one, and per cut the counts,
 the stages and — with --frames — the frame of the cut beside the frame of the full records, both scored against the mesh.  The
 yardsticks of the plain run (m2s_prune, merge_to_budget, the pass's own time) are left out.
+
+--budget: m2s_lod_select_budget on the tree in world units with M2S_MERGE_UNSIGNED_AXIS, per distance factor and budget: the three
+stages, the tau_px and the count it returns, and in the same process the yardstick a caller had without it: 31 M2S_LOD_DRY_RUN calls of
+m2s_lod_select that build the same key from its top bit down on the host (each a sweep and a round trip of the counts), then the real
+cut at the tau found; their sweeps' device time summed, and the whole search on the host's clock beside the budget call's.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
 tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
@@ -40,8 +46,13 @@ def main():
     ap.add_argument("--frames", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--budget", action="store_true")
+    ap.add_argument("--budgets", default="50000,200000,1000000")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.budget:
+        a.world_units = True
+        a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_budget.json")
     a.tau = a.tau or ("1,2,4" if a.world_units else "1,1024")
     import numpy as np
     from mesh2splat_amd import lod, synth
@@ -115,6 +126,63 @@ def main():
                 rows.append(ms)
         return counts, median_of(rows)
 
+    if a.budget:
+        import time
+        records = convert()
+        build = conv.lod_build(unsigned_axis=True)
+        first = build["first"]
+        last = first[-1] - first[-2]
+        res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup, "world_units": True, "unsigned_axis": True,
+               "build": {"counts": {k: v for k, v in build.items() if k != "first"}, "per_level_nodes": [first[l + 1] - first[l] for l in range(len(first) - 1)],
+                         "ms": conv.last_lod_build_ms}, "cells": []}
+
+        def host_bisection(eye, focal, cam, n_eff):
+            """the smallest key whose cut holds at most n_eff records, by 31 dry runs -> (key, their sweeps' ms summed)"""
+            key, sweep = 0, 0.0
+            for bit in range(30, -1, -1):
+                c = key | (1 << bit)
+                tau = float(np.array([c - 1], np.uint32).view(np.float32)[0])
+                if not np.isfinite(tau):
+                    continue                                                          # (no finite tau_px there: no cut refines at such a key)
+                got = conv.lod_select(eye, focal, tau, cam.near, dry_run=True)
+                sweep += conv.last_lod_select_stage_ms()["sweep"]
+                if got["selected"] > n_eff:
+                    key = c
+            return key, sweep
+
+        for f in [float(v) for v in a.factors.split(",")]:
+            cam = camera(f)
+            eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
+            for budget in [int(v) for v in a.budgets.split(",")]:
+                rows, yard, got = [], [], None
+                for k in range(a.warmup + a.reps):
+                    t0 = time.perf_counter()
+                    now = conv.lod_select_budget(eye, focal, budget, near=cam.near)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    assert got is None or now == got                                  # integer sums: the same from run to run
+                    got = now
+                    ms = dict(conv.last_lod_budget_stage_ms, host_wall=wall)
+                    ms["search"] = ms["thresholds"] + ms["select"]
+                    ms["total"] = ms["search"] + ms["cut"]
+                    t0 = time.perf_counter()
+                    key, sweeps = host_bisection(eye, focal, cam, max(budget, last))
+                    tau = float(np.array([key], np.uint32).view(np.float32)[0])
+                    final = conv.lod_select(eye, focal, tau, cam.near)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    cut = conv.last_lod_select_stage_ms()
+                    assert tau == got["tau_px"] and final == {k: got[k] for k in final}     # the two searches agree
+                    if k >= a.warmup:
+                        rows.append(ms)
+                        yard.append({"search": sweeps, "cut": cut["sweep"] + cut["scan_ids"] + cut["compact"], "host_wall": wall})
+                cell = {"factor": f, "budget": budget, "result": got, "budget_stage_ms": median_of(rows), "host_bisection_31_dry_runs_ms": median_of(yard)}
+                res["cells"].append(cell)
+                print(json.dumps(cell), flush=True)
+        print(json.dumps(res))
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        conv.close()
+        return
     if a.unsigned_axis:
         records = convert()
         names = {False: "signed", True: "unsigned"}

@@ -89,6 +89,7 @@ struct Options {
     std::vector<uint32_t> lod_levels;                              // --lod-levels a,b,...: the merge levels of the level-of-detail tree's steps (m2s_lod_build); empty: off
     double lod_pixels = -1.0;                                      // --lod-pixels t: every --preview / --score camera takes its cut at tau_px = t first (m2s_lod_select)
     double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
+    long long lod_budget = 0;                                      // --lod-budget N: every camera takes the finest cut of at most N records (m2s_lod_select_budget); --lod-pixels is then its floor
     bool lod() const { return !lod_levels.empty(); }
     bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
     bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
@@ -112,7 +113,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -171,6 +172,11 @@ void usage() {
                  "  surface once, as coarse as t pixels allow; the frame is drawn from the cut.  Prints ONE line `lod: {...}` of JSON per file:\n"
                  "  levels, nodes, per_level_nodes, skipped, tau_px, build_ms, views (per camera, the preview's first: selected, per_level).\n"
                  "  With --batch, which draws no frames, --score K names the cameras and every cut is a dry run.  Not with --gpus N > 1.\n"
+                 "--lod-budget N (1 .. 2^32-1), with --lod-levels, in place of --lod-pixels or together with it: every camera takes the finest cut\n"
+                 "  of at most N records instead (m2s_lod_select_budget; the tau_px is found on the device), never finer than t pixels where\n"
+                 "  --lod-pixels t is given too.  A budget below the size of the coarsest level gets that level.  Every entry of `views` then also\n"
+                 "  has tau_px (the tau the cut was taken at), met and selected_finer (the records of the next finer cut, the one that did not\n"
+                 "  fit), and the line has \"budget\": N; its own tau_px is the floor (0 without --lod-pixels).\n"
                  "--merge-unsigned-axis, with --merge-level, --merge-to or --lod-levels: the sign of a record's third axis carries no meaning\n"
                  "  (M2S_MERGE_UNSIGNED_AXIS: a group ends where |dot| is below d, and the members' axes are turned onto one side before they\n"
                  "  are averaged).  A conversion stores the two triangles of a flat quad with opposite signs, which the viewer does not see; with\n"
@@ -307,7 +313,7 @@ void preview_light(const m2s_mesh* meshes, uint32_t n_meshes, double pos[3], dou
     *intensity = 4.0 * radius * radius;
 }
 
-// --lod-levels / --lod-pixels: the tree over the context's records (Converter.lod_build), then one cut per camera (Converter.lod_select)
+// --lod-levels / --lod-pixels / --lod-budget: the tree over the context's records (Converter.lod_build), then one cut per camera (Converter.lod_select / .lod_select_budget)
 // in front of its frame; the views collect in `views` for the one `lod:` line
 struct LodReport { uint64_t build[4] = {}; std::vector<uint64_t> first; float build_ms = 0; std::string views; };
 
@@ -336,10 +342,30 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float vie
     sp.near = (float)near_p;
     sp.flags = dry ? (uint32_t)M2S_LOD_DRY_RUN : 0u;
     uint64_t c[4] = {}, per[M2S_LOD_MAX_STEPS + 1] = {};
-    if (m2s_lod_select(ctx, &sp, c) != M2S_OK || m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
+    std::string budget;
+    if (o.lod_budget > 0) {                                             // the cut that fits: --lod-pixels, where given, is its floor
+        m2s_lod_budget_params bp;
+        std::memset(&bp, 0, sizeof(bp));
+        std::memcpy(bp.camera_position, sp.camera_position, sizeof(bp.camera_position));
+        bp.focal_px = sp.focal_px;
+        bp.near = sp.near;
+        bp.tau_min_px = o.lod_pixels >= 0.0 ? (float)o.lod_pixels : 0.0f;
+        bp.max_records = (uint32_t)o.lod_budget;
+        bp.flags = sp.flags;
+        m2s_lod_budget_result res;
+        if (m2s_lod_select_budget(ctx, &bp, &res, c) != M2S_OK) return 1;
+        char tau[40];
+        std::snprintf(tau, sizeof tau, "%.9g", (double)res.tau_px);
+        budget = std::string(", \"tau_px\": ") + tau + ", \"met\": " + (res.met ? "true" : "false") + ", \"selected_finer\": " +
+                 std::to_string((unsigned long long)res.selected_finer);
+    } else if (m2s_lod_select(ctx, &sp, c) != M2S_OK) {
+        return 1;
+    }
+    if (m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
     std::string levels;
     for (size_t l = 0; l + 1 < rep->first.size(); ++l) levels += std::string(l ? ", " : "") + std::to_string((unsigned long long)per[l]);
-    rep->views += std::string(rep->views.empty() ? "" : ", ") + "{\"selected\": " + std::to_string((unsigned long long)c[1]) + ", \"per_level\": [" + levels + "]}";
+    rep->views += std::string(rep->views.empty() ? "" : ", ") + "{\"selected\": " + std::to_string((unsigned long long)c[1]) + ", \"per_level\": [" + levels + "]" +
+                  budget + "}";
     return 0;
 }
 
@@ -348,10 +374,11 @@ void lod_print(const Options& o, const LodReport& rep) {
     for (size_t s = 0; s < o.lod_levels.size(); ++s) levels += std::string(s ? ", " : "") + std::to_string(o.lod_levels[s]);
     for (size_t l = 0; l + 1 < rep.first.size(); ++l) per += std::string(l ? ", " : "") + std::to_string((unsigned long long)(rep.first[l + 1] - rep.first[l]));
     char tau[40];
-    std::snprintf(tau, sizeof tau, "%.9g", (double)(float)o.lod_pixels);
-    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s}\n",
+    std::snprintf(tau, sizeof tau, "%.9g", o.lod_pixels >= 0.0 ? (double)(float)o.lod_pixels : 0.0);
+    const std::string budget = o.lod_budget > 0 ? ", \"budget\": " + std::to_string(o.lod_budget) : std::string();
+    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
-                o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
+                budget.c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
 }
 
 // GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path` — with
@@ -1191,6 +1218,12 @@ int main(int argc, char** argv) {
         else if (a == "--merge-group") { o.merge_group = std::atoi(next()); if (o.merge_group < 2 || o.merge_group > 64) { usage(); return 2; } }
         else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
         else if (a == "--lod-pixels") { o.lod_pixels = std::atof(next()); if (!(o.lod_pixels >= 0.0) || !std::isfinite(o.lod_pixels)) { usage(); return 2; } }
+        else if (a == "--lod-budget") {
+            const std::string v = next();
+            char* end = nullptr;
+            o.lod_budget = std::strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end || o.lod_budget < 1 || o.lod_budget > 0xFFFFFFFFll) { usage(); return 2; }
+        }
         else if (a == "--view-distance") { o.view_distance = std::atof(next()); if (!(o.view_distance >= 0.25 && o.view_distance <= 64.0)) { usage(); return 2; } }
         else if (a == "--lod-levels") {
             o.lod_levels.clear();
@@ -1259,8 +1292,9 @@ int main(int argc, char** argv) {
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.world_units && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (a rank's slice writer and the gather hand on the density)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
-    // --lod-*: both or neither; the cuts need cameras (--preview / --score; a batch draws no preview) and one context
-    if (o.lod() != (o.lod_pixels >= 0.0)) { usage(); return 2; }
+    // --lod-*: the levels with a bound in pixels, a budget or both, or none of them; the cuts need cameras (--preview / --score; a batch
+    // draws no preview) and one context
+    if (o.lod() != (o.lod_pixels >= 0.0 || o.lod_budget > 0)) { usage(); return 2; }
     if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
