@@ -724,7 +724,8 @@ float m2s_last_lod_build_ms(const m2s_ctx* ctx);
  *     Integer sums, identical from run to run.
  *  5. With M2S_LOD_DRY_RUN only the counts are produced: nothing of the context changes.
  * Synchronous.  M2S_ERR_INVALID: a camera position, focal_px, tau_px or near that is not finite, focal_px <= 0, tau_px < 0, near <= 0,
- * unknown flag bits, reserved != 0.  M2S_ERR_STATE: no tree, or conversions in flight.  No frustum culling here: m2s_prepass does it. */
+ * unknown flag bits, reserved != 0.  M2S_ERR_STATE: no tree, or conversions in flight.  No frustum culling here: m2s_lod_select_frustum
+ * (below) takes the same cut over the nodes a camera can see. */
 enum { M2S_LOD_DRY_RUN = 1 };
 typedef struct m2s_lod_select_params {
     float    camera_position[3];  /* world space, finite */
@@ -781,6 +782,50 @@ m2s_status m2s_lod_select_budget(m2s_ctx* ctx, const m2s_lod_budget_params* para
 /* The stages (ms) of the last profiled m2s_lod_select_budget: [0] thresholds + ancestor minima, [1] the four select rounds, [2] the cut
  * (m2s_lod_select's three stages summed). */
 m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+
+/* The two cuts over what a camera sees: nodes with no leaf inside the view frustum are not selected, so they are neither compacted,
+ * keyed and sorted only for m2s_prepass to discard them, nor charged to a record budget (tests/lod_frustum_ref.py restates it).  Pinned:
+ *  1. Leaf test.  For leaf i with bound (x, y, z, e), in fp32, one rounding per operation, mat4 * vec4 as (m0*x + m1*y) + (m2*z + m3*w):
+ *       ws = model_to_world * (x, y, z, 1);  vs = world_to_view * (ws.xyz, 1);  c = view_to_clip * vs;  clip = guard_band * c.w;
+ *       inside = !(c.z < -clip || c.x < -clip || c.x > clip || c.y < -clip || c.y > clip).
+ *     Every comparison is false for a NaN: such a leaf is inside, as in the viewer's shader.  With guard_band == 1.05f this is
+ *     m2s_prepass's own test operation for operation: the leaves outside are exactly the records m2s_prepass culls with the same
+ *     three matrices and no depth image.
+ *  2. Visibility.  vis(i) = inside(i) for a leaf; for a node above the leaves vis is the OR of vis over the nodes whose parent word
+ *     names it.  A node is visible iff a leaf below it is inside; the position of a node above the leaves is never tested.  (Testing
+ *     each node's own position instead would let the number of selected nodes rise with tau_px, and the budget search has no answer
+ *     then: DESIGN 5.22.)
+ *  3. The cut.  A node is selected iff pin 2 of m2s_lod_select selects it and vis(i).  Every inside leaf has exactly one selected
+ *     ancestor-or-self; every selected node has an inside leaf below it; `refine` is evaluated exactly as by m2s_lod_select.
+ *  4. Everything else is m2s_lod_select's: output order, adoption, what is invalidated, m2s_device_lod_nodes, M2S_LOD_DRY_RUN, the tree
+ *     untouched.  out_counts: [0] nodes, [1] selected, [2] selected leaves, [3] nodes with `refine` (unmasked).
+ *     m2s_last_lod_level_counts reports the counts after masking.  Zero selected is a valid result: the context then holds 0 records,
+ *     as after an m2s_prune that kept none.
+ *  5. The budget.  Pin 2 of m2s_lod_select_budget with "L(i) < H(i)" read as "L(i) < H(i) and vis(i)": count(0x7F7FFFFF) is the number
+ *     of visible nodes of the last level, N_eff the larger of max_records and that number; key*, the floor, met and selected_finer are
+ *     as there, and the cut is pin 3 above at that tau_px.  With no leaf inside: key* = 0 raised to the floor, 0 selected, met 1,
+ *     selected_finer 0.
+ *  6. camera_position is, as for the plain cuts, in the records' own space.  Keeping it consistent with the matrices is the caller's
+ *     business and is not checked.
+ *  7. Errors: those of m2s_lod_select / m2s_lod_select_budget, and M2S_ERR_INVALID for a NULL frustum, a matrix entry that is not
+ *     finite, a guard_band that is not finite or below 1, a reserved word that is not 0.
+ * Where the two rules part from m2s_prepass, which tests the selected node's own position afterwards: a node above the leaves whose
+ * own position passes but none of whose leaves do is not selected, and one whose position fails but which has a leaf inside is
+ * selected and culled by the prepass.  Both sit at the guard band's border; a larger guard_band widens the test. */
+typedef struct m2s_lod_frustum {
+    float    model_to_world[16];  /* as m2s_prepass_params, column-major; finite */
+    float    world_to_view[16];
+    float    view_to_clip[16];
+    float    guard_band;          /* finite, >= 1; 1.05f is the prepass's own */
+    uint32_t reserved[3];         /* 0 */
+} m2s_lod_frustum;                /* 208 bytes */
+m2s_status m2s_lod_select_frustum(m2s_ctx* ctx, const m2s_lod_select_params* params, const m2s_lod_frustum* frustum, uint64_t out_counts[4]);
+m2s_status m2s_lod_select_budget_frustum(m2s_ctx* ctx, const m2s_lod_budget_params* params, const m2s_lod_frustum* frustum,
+                                         m2s_lod_budget_result* out, uint64_t out_counts[4]);
+/* Of the last of the two calls above (a dry run included): [0] leaves inside, [1] nodes the plain cut selects at that tau_px and this
+ * one dropped.  m2s_last_lod_frustum_ms: the visibility stage (ms) of the last profiled one. */
+m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* ctx, uint64_t out[2]);
+float      m2s_last_lod_frustum_ms(const m2s_ctx* ctx);
 
 /* ---- world units (no counterpart in the reference, which keeps the resolutionTarget beside its records) ---------------------------- */
 /* Brings the context's current records to world units: scale[k] = scale[k] / (float)R for k = 0, 1, 2, with R the records'

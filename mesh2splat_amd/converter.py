@@ -1045,40 +1045,61 @@ class Converter:
             raise _lib.M2SError(st, "no level-of-detail tree (lod_build)")
         return [int(first[k]) for k in range(n.value + 1)]
 
-    def lod_select(self, camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False) -> dict:
+    def _lod_frustum_counts(self, out: dict) -> None:
+        from . import lod as _ld
+        fc = (C.c_uint64 * 2)()
+        self._check(self._L.m2s_last_lod_frustum_counts(self._h, fc))
+        out.update({name: int(fc[k]) for k, name in enumerate(_ld.FRUSTUM_COUNTS)})
+
+    def lod_select(self, camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False,
+                   frustum=None) -> dict:
         """Take the cut through the tree for a camera at `camera_position` (world space) whose projection has `focal_px` pixels per unit
         of tan(angle) (mesh2splat_amd.lod.focal_px, .camera_position): walking down from the coarsest level, a node is drawn as soon as
         its longer edge projects to at most tau_px pixels at its distance from the camera (at least `near`), or it is a leaf
         (m2s_lod_select; the pin is in include/m2s.h).  Every leaf is covered exactly once.  The selected nodes become the context's
         records, in node order; sorted quads, accumulators and a baked SH plane are invalid.  dry_run: only the counts.
-        -> {"nodes", "selected", "selected_leaves", "refine", "per_level": selected nodes of every tree level}."""
+        -> {"nodes", "selected", "selected_leaves", "refine", "per_level": selected nodes of every tree level}.
+        frustum (a mesh2splat_amd.lod.LodFrustumC: lod.frustum_to_c, lod.frustum_of): only nodes with a leaf inside it are selected
+        (m2s_lod_select_frustum), possibly none; the dict then also has "visible_leaves" and "culled", the nodes the plain cut selects
+        and this one dropped."""
         from . import lod as _ld
         pc = _ld.select_to_c(camera_position, focal_px, tau_px, near, dry_run)
         v = (C.c_uint64 * 4)()
-        self._check(self._L.m2s_lod_select(self._h, C.byref(pc), v))
+        if frustum is None:
+            self._check(self._L.m2s_lod_select(self._h, C.byref(pc), v))
+        else:
+            self._check(self._L.m2s_lod_select_frustum(self._h, C.byref(pc), C.byref(frustum), v))
         out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
         per = (C.c_uint64 * (_ld.MAX_STEPS + 1))()
         self._check(self._L.m2s_last_lod_level_counts(self._h, per))
         out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
+        if frustum is not None:
+            self._lod_frustum_counts(out)
         return out
 
     def lod_select_budget(self, camera_position, focal_px: float, max_records: int, tau_min_px: float = 0.0, near: float = 1e-3,
-                          dry_run: bool = False) -> dict:
+                          dry_run: bool = False, frustum=None) -> dict:
         """Take the finest cut of lod_select() that holds at most `max_records` records for this camera, never finer than tau_min_px: the
         tau_px is found on the device, without a bisection on the host (m2s_lod_select_budget; the pin is in include/m2s.h).  A budget
         below the size of the coarsest level returns that level, with "met" False.  Everything else is lod_select()'s at the returned
         tau_px.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
-        next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}."""
+        next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}.
+        frustum: as for lod_select(); the budget is then spent on the nodes the camera sees (m2s_lod_select_budget_frustum)."""
         from . import lod as _ld
         pc = _ld.budget_to_c(camera_position, focal_px, max_records, tau_min_px, near, dry_run)
         res = _ld.LodBudgetResultC()
         v = (C.c_uint64 * 4)()
-        self._check(self._L.m2s_lod_select_budget(self._h, C.byref(pc), C.byref(res), v))
+        if frustum is None:
+            self._check(self._L.m2s_lod_select_budget(self._h, C.byref(pc), C.byref(res), v))
+        else:
+            self._check(self._L.m2s_lod_select_budget_frustum(self._h, C.byref(pc), C.byref(frustum), C.byref(res), v))
         out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
         per = (C.c_uint64 * (_ld.MAX_STEPS + 1))()
         self._check(self._L.m2s_last_lod_level_counts(self._h, per))
         out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
         out["tau_px"], out["met"], out["selected_finer"] = float(res.tau_px), bool(res.met), int(res.selected_finer)
+        if frustum is not None:
+            self._lod_frustum_counts(out)
         return out
 
     def download_lod(self, which: int) -> np.ndarray:
@@ -1126,6 +1147,10 @@ class Converter:
         ms = (C.c_float * 3)()
         self._check(self._L.m2s_last_lod_budget_stage_ms(self._h, ms))
         return {"thresholds": float(ms[0]), "select": float(ms[1]), "cut": float(ms[2])}
+
+    def last_lod_frustum_ms(self) -> float:
+        """The visibility stage (ms) of the last profiled lod_select() / lod_select_budget() with a frustum."""
+        return float(self._L.m2s_last_lod_frustum_ms(self._h))
 
     # ---- world units (m2s_records_to_world_units) ----------------------------------------------------------------------------------------
     @property

@@ -13,7 +13,7 @@
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
 //   m2s_worldunits.cpp  m2s_records_to_world_units: a conversion's scales divided by its resolutionTarget
-//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): a chain of merges kept and linked
+//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their _frustum forms): a chain of merges kept and linked
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -271,6 +271,12 @@ struct m2s_ctx {
     m2s_host::DevBuf<uint32_t> d_lod_budget_state;       // kLodBudgetStateWords
     float last_lod_budget_stage_ms[3] = { 0, 0, 0 };     // thresholds, the four select rounds, the cut (profiling on)
     m2s_host::EventSet<3> lod_budget_ev;
+    // the cuts over a frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum): a visibility byte per node, the leaves inside
+    // and the nodes the plain cut selects and the frustum dropped (two more words of d_lod_counts), the visibility stage
+    m2s_host::DevBuf<uint8_t> d_lod_vis;
+    uint64_t last_lod_frustum_counts[2] = { 0, 0 };
+    float last_lod_frustum_ms = 0.0f;
+    m2s_host::EventSet<2> lod_vis_ev;
     // world units (m2s_worldunits.cpp)
     float last_world_units_ms = 0.0f;
     m2s_host::EventSet<2> wu_ev;

@@ -331,12 +331,15 @@ hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t*
 hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32_t* parent, const float4* rec, uint32_t n_rec, float4* bounds,
                     hipStream_t st);
 struct LodSelectK { float cx, cy, cz, focal, tau2, near2; };
-constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine
-constexpr uint32_t kLodCountWords = 18;
+constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine,
+constexpr uint32_t kLodPlainWord = 18;     // [18] nodes the cut selects before the visibility plane masks it (written with a plane only),
+constexpr uint32_t kLodInsideWord = 19;    // [19] leaves inside the frustum (written by lod_visibility)
+constexpr uint32_t kLodCountWords = 20;
 // The sweep, one launch per level from the last to the leaves: per node of [first[l], first[l + 1]) the pinned comparison,
 // open[i] = refine && open[parent[i]] (levels above the leaves), flags[i] = selected; counts (zeroed by the caller) as above.
+// vis (NULL: none): the visibility plane of lod_visibility; flags[i] = selected && vis[i] then, and the per-level counts are the masked ones.
 hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
-                     uint32_t* flags, uint32_t* counts, hipStream_t st);
+                     uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st);
 // ids[offsets[i]] = i where flags[i] is set
 hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t* ids, hipStream_t st);
 // offsets = exclusive scan of flags (n words each); temp: prune_scan_temp_bytes(n)
@@ -346,16 +349,28 @@ hipError_t lod_scan(const uint32_t* flags, uint32_t* offsets, uint32_t n, void* 
 // The search's words on the device: the digits of the key found so far, the count at the key just under the prefix's range, the count at
 // the key in front of the answer (written once a digit above 0 is chosen: the answer is not key 0); then per round kLodBudgetShards copies of 256 bins for L and 256 for H.
 constexpr uint32_t kLodBudgetShards = 4;   // (a power of two)
-constexpr uint32_t kLodBudgetPrefix = 0, kLodBudgetBelow = 1, kLodBudgetFiner = 2, kLodBudgetHist = 4;
+constexpr uint32_t kLodBudgetPrefix = 0, kLodBudgetBelow = 1, kLodBudgetFiner = 2, kLodBudgetEff = 3, kLodBudgetHist = 4;
 constexpr uint32_t kLodBudgetStateWords = kLodBudgetHist + 4 * kLodBudgetShards * 512;
 // One launch per level from the last to the leaves: lh[i] = (L, H), the keys (bits of tau_px) from which node i is no longer refined
 // (0 for a leaf) and from which one of its proper ancestors is not (0xFFFFFFFF on the last level); k.tau2 is not read.
+// vis (NULL: none): the visibility plane of lod_visibility; a node whose byte is 0 gets L = H (selected at no key), H as without.
 hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
-                          hipStream_t st);
+                          const uint8_t* vis, hipStream_t st);
 // The four histogram / pick rounds over the n nodes: afterwards state[kLodBudgetPrefix] is the smallest key whose cut holds at most
 // `budget` nodes (budget >= the nodes of the last level, n > 0), state[kLodBudgetFiner] the count at the key before it where
 // that key is not 0.  state: kLodBudgetStateWords, zeroed here.
-hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, uint32_t* state, hipStream_t st);
+// raise_to_last: the budget is raised on the device to count(0x7F7FFFFF), the nodes of the last level left with L < H, which the first
+// round's sums hold (no key lies in 0x7F800000 .. 0x7FFFFFFF); state[kLodBudgetEff] keeps it.  For planes whose last level is masked.
+hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, bool raise_to_last, uint32_t* state, hipStream_t st);
+
+// ---- the visibility plane of the frustum cuts (m2s_lodfrustum.hip) -----------------------------------------------------------------------
+// The three matrices of m2s_prepass_params (column-major) and the guard band, as a kernel argument.
+struct LodFrustumK { float M[16], V[16], P[16]; float guard; };
+// vis: one byte per node.  Zeroes them (stream-ordered memset), then one launch per level from the leaves up to the level below the last
+// (one launch for a tree of one level): vis[i] = 1 for a leaf whose position passes the prepass's frustum test with this guard band, and
+// for every node with a visible child; the leaves that pass are added to *inside_word (zeroed by the caller).
+hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f, uint8_t* vis,
+                          uint32_t* inside_word, hipStream_t st);
 
 // ---- world units (m2s_worldunits.hip) ------------------------------------------------------------------------------------------------
 // dst[i] = src[i] with scale[0..2] divided by (float)R (IEEE, correctly rounded), every other word with its bits, for the n records.

@@ -1,5 +1,5 @@
-// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): host side of
-// m2s_lod.hip and m2s_lodbudget.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
+// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and their
+// _frustum forms): host side of m2s_lod.hip, m2s_lodbudget.hip and m2s_lodfrustum.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
 // copied into a node pool and linked by their maps; the
 // cut's flags and offsets live where m2s_prune leaves its own, and the compaction and what follows it are m2s_prune's (m2s_contrib.cpp:
 // prune_compact_enqueue, prune_adopt).
@@ -41,8 +41,48 @@ m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
     return M2S_OK;
 }
 
+LodFrustumK lod_frustum_k(const m2s_lod_frustum* fr) {
+    LodFrustumK f;
+    std::memcpy(f.M, fr->model_to_world, sizeof(f.M));
+    std::memcpy(f.V, fr->world_to_view, sizeof(f.V));
+    std::memcpy(f.P, fr->view_to_clip, sizeof(f.P));
+    f.guard = fr->guard_band;
+    return f;
+}
+
+m2s_status lod_frustum_check(m2s_ctx* c, const m2s_lod_frustum* fr) {
+    if (!fr) return fail(c, M2S_ERR_INVALID, "no frustum");
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(fr->model_to_world[k]) || !std::isfinite(fr->world_to_view[k]) || !std::isfinite(fr->view_to_clip[k]))
+            return fail(c, M2S_ERR_INVALID, "a matrix entry of the frustum is not finite");
+    if (!std::isfinite(fr->guard_band) || !(fr->guard_band >= 1.0f)) return fail(c, M2S_ERR_INVALID, "guard_band is not finite or below 1");
+    if (fr->reserved[0] || fr->reserved[1] || fr->reserved[2]) return fail(c, M2S_ERR_INVALID, "a reserved word of the frustum is not 0");
+    return M2S_OK;
+}
+
+// The visibility plane of the tree's N > 0 nodes for one frustum, timed where the context profiles (read after the next synchronisation).
+// The cut's count words are zeroed here, in front of the stage that writes the first of them.
+m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr) {
+    const bool prof = c->profiling;
+    M2S_TRY(c->d_lod_vis.reserve(c->err, c->lod_first[c->lod_levels], 1));
+    M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+    HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+    if (prof) {
+        M2S_TRY(c->lod_vis_ev.ensure(c->err));
+        HIPCHK(c, hipEventRecord(c->lod_vis_ev[0], c->stream));
+    }
+    HIPCHK(c, lod_visibility(c->d_lod_bounds, c->d_lod_parent, c->lod_first, c->lod_levels, lod_frustum_k(fr), c->d_lod_vis,
+                             c->d_lod_counts + kLodInsideWord, c->stream));
+    if (prof) HIPCHK(c, hipEventRecord(c->lod_vis_ev[1], c->stream));
+    return M2S_OK;
+}
+
 // The cut behind m2s_lod_select's checks of its arguments and the context's state (m2s_lod_select_budget takes its own through it).
-m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4]) {
+// fr (NULL: the plain cut): only nodes with a leaf inside this frustum are selected.  vis: who runs lod_vis_enqueue for it, which also
+// zeroes the cut's count words in front of the inside count it adds to them.
+enum class LodVis { None, Here, Enqueued };     // no frustum | lod_cut enqueues it | the caller has, earlier on the stream (the budget search reads the plane first)
+m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4], const m2s_lod_frustum* fr, LodVis vis) {
+    if ((fr != nullptr) != (vis != LodVis::None)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
     const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
     const bool prof = c->profiling;
     const uint32_t levels = c->lod_levels;
@@ -63,9 +103,12 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         uint32_t* const flags = c->d_prune_u32;
         uint32_t* const offsets = flags + c->d_prune_u32.cap();
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
+        if (vis == LodVis::Here) M2S_TRY(lod_vis_enqueue(c, fr));
         if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[0], c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
-        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts, c->stream));
+        // (with a frustum the words were zeroed by lod_vis_enqueue, here or in the caller, and hold the inside count by now: not again)
+        if (vis == LodVis::None) HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts,
+                            fr ? c->d_lod_vis.get() : nullptr, c->stream));
         if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[1], c->stream));
         if (!dry) {
             HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
@@ -75,7 +118,9 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t l = 0; l < levels; ++l) selected += h[l];
-        if (selected < 1 || selected > N || h[kLodRefineWord] > N) return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
+        // (a frustum may leave nothing; the plain cut holds every leaf's ancestor-or-self)
+        if ((selected < 1 && !fr) || selected > N || h[kLodRefineWord] > N || (fr && (h[kLodPlainWord] < selected || h[kLodPlainWord] > N || h[kLodInsideWord] > N)))
+            return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
         if (!dry) {
             M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
             if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[3], c->stream));
@@ -89,6 +134,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
                 HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_ev[1], c->lod_ev[2]));
                 HIPCHK(c, hipEventElapsedTime(&ms[2], c->lod_ev[2], c->lod_ev[3]));   // (the round trip of the counts included)
             }
+            if (fr) HIPCHK(c, hipEventElapsedTime(&c->last_lod_frustum_ms, c->lod_vis_ev[0], c->lod_vis_ev[1]));
         }
     } else {
         if (!dry) {
@@ -97,6 +143,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         if (prof) c->last_lod_select_stage_ms[0] = c->last_lod_select_stage_ms[1] = c->last_lod_select_stage_ms[2] = 0.0f;
+        if (prof && fr) c->last_lod_frustum_ms = 0.0f;
     }
     if (!dry) {
         prune_adopt(c, selected, c->lod_R, false);
@@ -108,7 +155,84 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
     c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
     c->last_lod_select_counts[3] = h[kLodRefineWord];
     for (uint32_t l = 0; l <= M2S_LOD_MAX_STEPS; ++l) c->last_lod_level_counts[l] = l < levels ? h[l] : 0;
+    if (fr) { c->last_lod_frustum_counts[0] = h[kLodInsideWord]; c->last_lod_frustum_counts[1] = h[kLodPlainWord] - selected; }
     if (out_counts) std::memcpy(out_counts, c->last_lod_select_counts, sizeof(c->last_lod_select_counts));
+    return M2S_OK;
+}
+
+m2s_status lod_select_check(m2s_ctx* c, const m2s_lod_select_params* p) {
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
+    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    if ((p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+    return M2S_OK;
+}
+
+m2s_status lod_budget_check(m2s_ctx* c, const m2s_lod_budget_params* p) {
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    if (!std::isfinite(p->tau_min_px) || !(p->tau_min_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_min_px is not finite or negative");
+    if (p->max_records < 1) return fail(c, M2S_ERR_INVALID, "max_records is 0");
+    if (p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) return fail(c, M2S_ERR_INVALID, "unknown flag bits");
+    return M2S_OK;
+}
+
+// m2s_lod_select_budget behind its checks.  fr (NULL: the plain search): the nodes without a leaf inside are selected at no key, and
+// the budget is raised to the visible nodes of the last level on the device.
+m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out, uint64_t out_counts[4]) {
+    const bool prof = c->profiling;
+    const uint32_t levels = c->lod_levels;
+    const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
+    uint32_t floor_key = 0, key = 0;
+    if (p->tau_min_px > 0.0f) std::memcpy(&floor_key, &p->tau_min_px, sizeof(floor_key));
+    uint32_t h[3] = {};                                                 // prefix, below, finer
+    HIPCHK(c, hipSetDevice(c->device));
+    if (N) {
+        M2S_TRY(c->d_lod_lh.reserve(c->err, N, sizeof(uint2)));
+        M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
+        if (prof) M2S_TRY(c->lod_budget_ev.ensure(c->err));
+        const uint32_t n_eff = fr ? p->max_records : (uint32_t)std::max<uint64_t>(p->max_records, last);
+        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
+        if (fr) M2S_TRY(lod_vis_enqueue(c, fr));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[0], c->stream));
+        HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, fr ? c->d_lod_vis.get() : nullptr, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[1], c->stream));
+        HIPCHK(c, lod_budget_search(c->d_lod_lh, (uint32_t)N, n_eff, fr != nullptr, c->d_lod_budget_state, c->stream));
+        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[2], c->stream));
+        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        key = h[kLodBudgetPrefix];
+        if (key > 0x7F7FFFFFu) return fail(c, M2S_ERR_HIP, "the budget search came back with no finite tau_px");
+    }
+    const bool by_floor = floor_key > key;
+    if (by_floor) key = floor_key;
+    m2s_lod_select_params sp = {};
+    std::memcpy(sp.camera_position, p->camera_position, sizeof(sp.camera_position));
+    sp.focal_px = p->focal_px;
+    std::memcpy(&sp.tau_px, &key, sizeof(key));
+    sp.near = p->near;
+    sp.flags = p->flags;
+    uint64_t counts[4] = {};
+    M2S_TRY(lod_cut(c, &sp, counts, fr, fr ? LodVis::Enqueued : LodVis::None));
+    if (prof) {
+        float* ms = c->last_lod_budget_stage_ms;
+        ms[0] = ms[1] = 0.0f;
+        if (N) {
+            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_budget_ev[0], c->lod_budget_ev[1]));
+            HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_budget_ev[1], c->lod_budget_ev[2]));
+        }
+        ms[2] = (c->last_lod_select_stage_ms[0] + c->last_lod_select_stage_ms[1]) + c->last_lod_select_stage_ms[2];
+    }
+    if (out) {
+        out->tau_px = sp.tau_px;
+        out->met = counts[1] <= p->max_records ? 1u : 0u;
+        out->selected_finer = (!N || key == 0 || by_floor) ? counts[1] : h[kLodBudgetFiner];
+    }
+    if (out_counts) std::memcpy(out_counts, counts, sizeof(counts));
     return M2S_OK;
 }
 
@@ -204,7 +328,7 @@ m2s_status m2s_lod_release(m2s_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->lod_levels = 0;
-    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release();
+    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release(); c->d_lod_vis.release();
     return M2S_OK;
 }
 
@@ -213,80 +337,51 @@ float m2s_last_lod_build_ms(const m2s_ctx* c) { return c ? c->last_lod_build_ms 
 m2s_status m2s_lod_select(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4]) {
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
     if (!c || !p) return M2S_ERR_INVALID;
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
-    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
-    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
-    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
-    if ((p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
+    M2S_TRY(lod_select_check(c, p));
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    return lod_cut(c, p, out_counts);
+    return lod_cut(c, p, out_counts, nullptr, LodVis::None);
+}
+
+m2s_status m2s_lod_select_frustum(m2s_ctx* c, const m2s_lod_select_params* p, const m2s_lod_frustum* fr, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    M2S_TRY(lod_select_check(c, p));
+    M2S_TRY(lod_frustum_check(c, fr));
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    return lod_cut(c, p, out_counts, fr, LodVis::Here);
 }
 
 m2s_status m2s_lod_select_budget(m2s_ctx* c, const m2s_lod_budget_params* p, m2s_lod_budget_result* out, uint64_t out_counts[4]) {
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
     if (out) std::memset(out, 0, sizeof(*out));
     if (!c || !p) return M2S_ERR_INVALID;
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
-    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
-    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
-    if (!std::isfinite(p->tau_min_px) || !(p->tau_min_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_min_px is not finite or negative");
-    if (p->max_records < 1) return fail(c, M2S_ERR_INVALID, "max_records is 0");
-    if (p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) return fail(c, M2S_ERR_INVALID, "unknown flag bits");
+    M2S_TRY(lod_budget_check(c, p));
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    const bool prof = c->profiling;
-    const uint32_t levels = c->lod_levels;
-    const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
-    uint32_t floor_key = 0, key = 0;
-    if (p->tau_min_px > 0.0f) std::memcpy(&floor_key, &p->tau_min_px, sizeof(floor_key));
-    uint32_t h[3] = {};                                                 // prefix, below, finer
-    HIPCHK(c, hipSetDevice(c->device));
-    if (N) {
-        M2S_TRY(c->d_lod_lh.reserve(c->err, N, sizeof(uint2)));
-        M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
-        if (prof) M2S_TRY(c->lod_budget_ev.ensure(c->err));
-        const uint32_t n_eff = (uint32_t)std::max<uint64_t>(p->max_records, last);
-        const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[0], c->stream));
-        HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[1], c->stream));
-        HIPCHK(c, lod_budget_search(c->d_lod_lh, (uint32_t)N, n_eff, c->d_lod_budget_state, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[2], c->stream));
-        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        key = h[kLodBudgetPrefix];
-        if (key > 0x7F7FFFFFu) return fail(c, M2S_ERR_HIP, "the budget search came back with no finite tau_px");
-    }
-    const bool by_floor = floor_key > key;
-    if (by_floor) key = floor_key;
-    m2s_lod_select_params sp = {};
-    std::memcpy(sp.camera_position, p->camera_position, sizeof(sp.camera_position));
-    sp.focal_px = p->focal_px;
-    std::memcpy(&sp.tau_px, &key, sizeof(key));
-    sp.near = p->near;
-    sp.flags = p->flags;
-    uint64_t counts[4] = {};
-    M2S_TRY(lod_cut(c, &sp, counts));
-    if (prof) {
-        float* ms = c->last_lod_budget_stage_ms;
-        ms[0] = ms[1] = 0.0f;
-        if (N) {
-            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_budget_ev[0], c->lod_budget_ev[1]));
-            HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_budget_ev[1], c->lod_budget_ev[2]));
-        }
-        ms[2] = (c->last_lod_select_stage_ms[0] + c->last_lod_select_stage_ms[1]) + c->last_lod_select_stage_ms[2];
-    }
-    if (out) {
-        out->tau_px = sp.tau_px;
-        out->met = counts[1] <= p->max_records ? 1u : 0u;
-        out->selected_finer = (!N || key == 0 || by_floor) ? counts[1] : h[kLodBudgetFiner];
-    }
-    if (out_counts) std::memcpy(out_counts, counts, sizeof(counts));
+    return lod_budget(c, p, nullptr, out, out_counts);
+}
+
+m2s_status m2s_lod_select_budget_frustum(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out,
+                                         uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!c || !p) return M2S_ERR_INVALID;
+    M2S_TRY(lod_budget_check(c, p));
+    M2S_TRY(lod_frustum_check(c, fr));
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    return lod_budget(c, p, fr, out, out_counts);
+}
+
+m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return M2S_ERR_INVALID;
+    std::memcpy(out, c->last_lod_frustum_counts, sizeof(c->last_lod_frustum_counts));
     return M2S_OK;
 }
+
+float m2s_last_lod_frustum_ms(const m2s_ctx* c) { return c ? c->last_lod_frustum_ms : 0.0f; }
 
 m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) {
     if (!c || !out_ms) return M2S_ERR_INVALID;

@@ -11,6 +11,8 @@
 //                   selected and refining nodes are counted in registers, then per wave, then per workgroup, and leave as at most two
 //                   integer atomicAdds per workgroup (one word per level and one for the refining nodes: atomics on ONE word retire
 //                   one after the other on MI355X, m2s_budget.hip).  Integer sums: the same from run to run.
+//                   The kVis instances (m2s_lod_select_frustum) mask the selection with the visibility byte of m2s_lodfrustum.hip
+//                   (+1 B per node) and count the unmasked selection as a third sum.
 //   k_lod_ids       ids[offsets[i]] = i for every selected node: which node each output record is
 // The scan of the flags is rocPRIM's, as m2s_prune's; the compaction is m2s_prune's own kernel.  Vector stores only.
 #include <rocprim/device/device_scan.hpp>
@@ -47,21 +49,28 @@ __device__ __forceinline__ bool lod_refines(const float4 b, const LodSelectK& k)
 }
 
 // nodes [first, first + n) of one level.  kTop: no parents (every node's ancestors refine, vacuously); kLeaf: no `open` byte to write,
-// and a leaf that refines is still selected
-template <bool kTop, bool kLeaf>
+// and a leaf that refines is still selected.  kVis (the cuts over a frustum, m2s_lodfrustum.hip builds the plane): a selected node whose
+// visibility byte is 0 is dropped (+1 B read per node); what the plain cut selects is counted beside what is left, in the same launch.
+// The kVis = false instances are the plain cut's.
+template <bool kTop, bool kLeaf, bool kVis>
 __global__ void __launch_bounds__(256) k_lod_select(const float4* __restrict__ bounds, const uint32_t* __restrict__ parent, uint32_t first, uint32_t n,
                                                     LodSelectK k, uint8_t* __restrict__ open, uint32_t* __restrict__ flags,
-                                                    uint32_t* __restrict__ selected_word, uint32_t* __restrict__ refine_word) {
+                                                    uint32_t* __restrict__ selected_word, uint32_t* __restrict__ refine_word,
+                                                    const uint8_t* __restrict__ vis, uint32_t* __restrict__ plain_word) {
     __shared__ uint32_t wave_sel[4], wave_ref[4];
-    uint32_t n_sel = 0, n_ref = 0;
+    uint32_t n_sel = 0, n_ref = 0, n_plain = 0;
     const uint32_t stride = gridDim.x * 256u;
     for (unsigned long long t = blockIdx.x * 256u + threadIdx.x; t < n; t += stride) {       // (64 bits: t + stride may pass 2^32)
         const uint32_t i = first + (uint32_t)t;
         const bool refine = lod_refines(bounds[i], k);
         bool above = true;
         if (!kTop) above = open[parent[i]] != 0;
-        const bool sel = above && (kLeaf || !refine);
+        bool sel = above && (kLeaf || !refine);
         if (!kLeaf) open[i] = (refine && above) ? 1 : 0;
+        if (kVis) {
+            n_plain += sel ? 1u : 0u;
+            sel = sel && vis[i] != 0;
+        }
         flags[i] = sel ? 1u : 0u;
         n_sel += sel ? 1u : 0u;
         n_ref += refine ? 1u : 0u;
@@ -78,6 +87,17 @@ __global__ void __launch_bounds__(256) k_lod_select(const float4* __restrict__ b
         const uint32_t b = (wave_ref[0] + wave_ref[1]) + (wave_ref[2] + wave_ref[3]);
         if (a) atomicAdd(selected_word, a);
         if (b) atomicAdd(refine_word, b);
+    }
+    if (kVis) {                                                         // (a third sum, after the two of the plain cut)
+        __shared__ uint32_t wave_plain[4];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) n_plain += (uint32_t)__shfl_xor((int)n_plain, o);
+        if ((threadIdx.x & 63u) == 0u) wave_plain[threadIdx.x >> 6] = n_plain;
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            const uint32_t p = (wave_plain[0] + wave_plain[1]) + (wave_plain[2] + wave_plain[3]);
+            if (p) atomicAdd(plain_word, p);
+        }
     }
 }
 
@@ -97,8 +117,11 @@ hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32
     return hipGetLastError();
 }
 
-hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
-                     uint32_t* flags, uint32_t* counts, hipStream_t st) {
+namespace {
+
+template <bool kVis>
+hipError_t lod_sweep_levels(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
+                            uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
     for (uint32_t l = levels; l-- > 0;) {
         const uint32_t f = (uint32_t)first[l], n = (uint32_t)(first[l + 1] - first[l]);
         if (!n) continue;
@@ -106,14 +129,23 @@ hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_
         const bool top = l + 1 == levels, leaf = l == 0;
         uint32_t* const sel = counts + l;
         uint32_t* const ref = counts + kLodRefineWord;
-        if (top && leaf) hipLaunchKernelGGL((k_lod_select<true, true>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref);
-        else if (top) hipLaunchKernelGGL((k_lod_select<true, false>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref);
-        else if (leaf) hipLaunchKernelGGL((k_lod_select<false, true>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref);
-        else hipLaunchKernelGGL((k_lod_select<false, false>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref);
+        uint32_t* const pln = counts + kLodPlainWord;
+        if (top && leaf) hipLaunchKernelGGL((k_lod_select<true, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else if (top) hipLaunchKernelGGL((k_lod_select<true, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else if (leaf) hipLaunchKernelGGL((k_lod_select<false, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else hipLaunchKernelGGL((k_lod_select<false, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
+                     uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
+    return vis ? lod_sweep_levels<true>(bounds, parent, first, levels, k, open, flags, counts, vis, st)
+               : lod_sweep_levels<false>(bounds, parent, first, levels, k, open, flags, counts, nullptr, st);
 }
 
 hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t* ids, hipStream_t st) {

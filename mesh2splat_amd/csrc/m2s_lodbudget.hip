@@ -18,6 +18,8 @@
 //                      count at the largest key of digit b, and the first digit at which it fits carries the answer.  Prefix, `below`
 //                      (the count just under the prefix's range) and the count at the key in front of the answer stay on the device,
 //                      so the four rounds run back to back.
+// m2s_lod_select_budget_frustum runs the kVis instances of k_lod_thresholds (a node without a leaf inside the frustum gets L = H: selected
+// at no key) and k_lod_budget_pick<true> (the budget raised to the visible nodes of the last level, on the device).
 // Atomics on ONE word retire one after the other on MI355X (m2s_budget.hip): few, large workgroups and sharded bins.  Integer atomics
 // only: every count is the same from run to run.  Vector stores only.
 #include <algorithm>
@@ -33,15 +35,19 @@ namespace {
 
 constexpr uint32_t kLodBudgetGrid = 512;   // workgroups of the two grid-stride kernels at most: two per CU
 
-// nodes [first, first + n) of one level.  kTop: no parents; kLeaf: L = 0, the bound is not read
-template <bool kTop, bool kLeaf>
+// nodes [first, first + n) of one level.  kTop: no parents; kLeaf: L = 0, the bound is not read.  kVis (the budget over a frustum): a
+// node whose visibility byte is 0 gets L = H, so it is selected at no key, and its children inherit the H it was given (+1 B read per
+// node; its 31 trips are skipped).  The kVis = false instances are the plain search's.
+template <bool kTop, bool kLeaf, bool kVis>
 __global__ void __launch_bounds__(256) k_lod_thresholds(const float4* __restrict__ bounds, const uint32_t* __restrict__ parent, uint32_t first, uint32_t n,
-                                                        LodSelectK k, uint2* __restrict__ lh) {
+                                                        LodSelectK k, uint2* __restrict__ lh, const uint8_t* __restrict__ vis) {
     const uint32_t stride = gridDim.x * 256u;
     for (unsigned long long t = blockIdx.x * 256u + threadIdx.x; t < n; t += stride) {       // (64 bits: t + stride may pass 2^32)
         const uint32_t i = first + (uint32_t)t;
         uint32_t L = 0u;
-        if (!kLeaf) {
+        bool seen = true;
+        if (kVis) seen = vis[i] != 0;
+        if (!kLeaf && seen) {
             const float4 b = bounds[i];
             const float dx = b.x - k.cx, dy = b.y - k.cy, dz = b.z - k.cz;
             const float d2 = fmaxf((dx * dx + dy * dy) + dz * dz, k.near2);
@@ -61,6 +67,7 @@ __global__ void __launch_bounds__(256) k_lod_thresholds(const float4* __restrict
             const uint2 p = lh[parent[i]];
             H = p.x < p.y ? p.x : p.y;
         }
+        if (kVis && !seen) L = H;
         lh[i] = make_uint2(L, H);
     }
 }
@@ -103,6 +110,9 @@ __global__ void __launch_bounds__(256) k_lod_budget_hist(const uint2* __restrict
     if (b) atomicAdd(&out[256u + threadIdx.x], b);
 }
 
+// kRaise (the budget over a frustum): the budget is at least count(0x7F7FFFFF), which round 0 reads off its own sums at digit 0x7F (no L
+// or H lies in 0x7F800000 .. 0x7FFFFFFF: the count at 0x7FFFFFFF is the one at 0x7F7FFFFF) and the later rounds find in the state.
+template <bool kRaise>
 __global__ void __launch_bounds__(256) k_lod_budget_pick(uint32_t pass, uint32_t budget, uint32_t* __restrict__ state) {
     __shared__ uint32_t sum[256];
     const uint32_t t = threadIdx.x;
@@ -127,6 +137,15 @@ __global__ void __launch_bounds__(256) k_lod_budget_pick(uint32_t pass, uint32_t
     // count(largest key of digit t) = below + v, not increasing in t, and it fits at t = 255 (round 0: no node is left there; later
     // rounds: the key the round before chose).  Exactly one digit is the first that fits.
     const uint32_t before = below + (v - d);                            // the count at the key in front of digit t's range
+    if (kRaise) {
+        if (pass == 0u) {
+            const uint32_t last = sum[0x7Fu];                           // (below is 0 in round 0)
+            budget = budget > last ? budget : last;
+            if (t == 0u) state[kLodBudgetEff] = budget;
+        } else {
+            budget = state[kLodBudgetEff];
+        }
+    }
     if (below + v <= budget && (t == 0u || before > budget)) {
         state[kLodBudgetPrefix] |= t << (24u - 8u * pass);
         state[kLodBudgetBelow] = before;
@@ -134,33 +153,41 @@ __global__ void __launch_bounds__(256) k_lod_budget_pick(uint32_t pass, uint32_t
     }
 }
 
-}  // namespace
-
-hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
-                          hipStream_t st) {
+template <bool kVis>
+hipError_t lod_thresholds_levels(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
+                                 const uint8_t* vis, hipStream_t st) {
     for (uint32_t l = levels; l-- > 0;) {
         const uint32_t f = (uint32_t)first[l], n = (uint32_t)(first[l + 1] - first[l]);
         if (!n) continue;
         const dim3 grid(std::min((n + 255u) / 256u, 2u * kLodBudgetGrid)), block(256);
         const bool top = l + 1 == levels, leaf = l == 0;
-        if (top && leaf) hipLaunchKernelGGL((k_lod_thresholds<true, true>), grid, block, 0, st, bounds, parent, f, n, k, lh);
-        else if (top) hipLaunchKernelGGL((k_lod_thresholds<true, false>), grid, block, 0, st, bounds, parent, f, n, k, lh);
-        else if (leaf) hipLaunchKernelGGL((k_lod_thresholds<false, true>), grid, block, 0, st, bounds, parent, f, n, k, lh);
-        else hipLaunchKernelGGL((k_lod_thresholds<false, false>), grid, block, 0, st, bounds, parent, f, n, k, lh);
+        if (top && leaf) hipLaunchKernelGGL((k_lod_thresholds<true, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
+        else if (top) hipLaunchKernelGGL((k_lod_thresholds<true, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
+        else if (leaf) hipLaunchKernelGGL((k_lod_thresholds<false, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
+        else hipLaunchKernelGGL((k_lod_thresholds<false, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, uint32_t* state, hipStream_t st) {
+}  // namespace
+
+hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
+                          const uint8_t* vis, hipStream_t st) {
+    return vis ? lod_thresholds_levels<true>(bounds, parent, first, levels, k, lh, vis, st)
+               : lod_thresholds_levels<false>(bounds, parent, first, levels, k, lh, nullptr, st);
+}
+
+hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, bool raise_to_last, uint32_t* state, hipStream_t st) {
     const hipError_t e = hipMemsetAsync(state, 0, kLodBudgetStateWords * sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     const uint32_t blocks = (uint32_t)(((unsigned long long)n + 1023ull) / 1024ull);       // four trips per lane at least, where there are that many
     const dim3 grid(std::max(1u, std::min(blocks, kLodBudgetGrid))), block(256);
     for (uint32_t pass = 0; pass < 4u; ++pass) {
         hipLaunchKernelGGL(k_lod_budget_hist, grid, block, 0, st, lh, n, pass, state);
-        hipLaunchKernelGGL(k_lod_budget_pick, dim3(1), block, 0, st, pass, budget, state);
+        if (raise_to_last) hipLaunchKernelGGL(k_lod_budget_pick<true>, dim3(1), block, 0, st, pass, budget, state);
+        else hipLaunchKernelGGL(k_lod_budget_pick<false>, dim3(1), block, 0, st, pass, budget, state);
     }
     return hipGetLastError();
 }

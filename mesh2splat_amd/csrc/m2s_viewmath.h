@@ -24,6 +24,13 @@ __device__ __forceinline__ bool clip_inside(float4 pos2d) {
     return !(pos2d.z < -clip || pos2d.x < -clip || pos2d.x > clip || pos2d.y < -clip || pos2d.y > clip);   // :75-77
 }
 
+// The same test with the caller's guard band in place of the shader's 1.05 (m2s_lodfrustum.hip); with guard == 1.05f it is the one above,
+// operation for operation.
+__device__ __forceinline__ bool clip_inside(float4 pos2d, float guard) {
+    const float clip = guard * pos2d.w;
+    return !(pos2d.z < -clip || pos2d.x < -clip || pos2d.x > clip || pos2d.y < -clip || pos2d.y > clip);
+}
+
 // :67-77.  ws = u_modelToWorld * vec4(P, 1); vs = u_worldToView * vec4(ws.xyz, 1); pos2d = u_viewToClip * vs; inside = the guard-band
 // frustum test (false = culled; every comparison is false for NaN: such a record is NOT culled here, as in the shader).
 __device__ __forceinline__ bool view_project(const float* M, const float* V, const float* P, float px, float py, float pz, float4& ws, float4& vs, float4& pos2d) {

@@ -1,6 +1,6 @@
 """The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_select_budget` / `.lod_levels` /
-`.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget): the ctypes mirrors of their parameters and the two numbers a
-cut takes from a camera.  The pins are in include/m2s.h.
+`.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and the _frustum forms
+of the two cuts): the ctypes mirrors of their parameters and the two numbers a cut takes from a camera.  The pins are in include/m2s.h.
 
 The default chain of merge levels (1 .. 8), like max_group = 4 and min_axis_dot = 0.5, is a guess: nothing in the repository has
 tuned it (tools/lod_probe.py reports what it does on one scene)."""
@@ -17,6 +17,7 @@ UNSIGNED_AXIS = 4                                            # M2S_MERGE_UNSIGNE
 DEFAULT_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8)
 BUILD_COUNTS = ("leaves", "nodes", "levels", "skipped")      # m2s_lod_build's out_counts, in order
 SELECT_COUNTS = ("nodes", "selected", "selected_leaves", "refine")   # m2s_lod_select's
+FRUSTUM_COUNTS = ("visible_leaves", "culled")                # m2s_last_lod_frustum_counts', in order
 PLANES = {0: (np.float32, 24), 1: (np.uint32, None), 2: (np.float32, 4)}    # m2s_download_lod: which -> (dtype, row length)
 
 
@@ -52,6 +53,12 @@ class LodBudgetResultC(C.Structure):
     _fields_ = [("tau_px", C.c_float), ("met", C.c_uint32), ("selected_finer", C.c_uint64)]
 
 
+class LodFrustumC(C.Structure):
+    """== m2s_lod_frustum (include/m2s.h)."""
+    _fields_ = [("model_to_world", C.c_float * 16), ("world_to_view", C.c_float * 16), ("view_to_clip", C.c_float * 16),
+                ("guard_band", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> LodBuildParamsC:
     levels = [int(v) for v in levels]
     if len(levels) > MAX_STEPS:
@@ -81,6 +88,24 @@ def budget_to_c(camera_position, focal_px: float, max_records: int, tau_min_px: 
     c.focal_px, c.near, c.tau_min_px = float(focal_px), float(near), float(tau_min_px)
     c.max_records, c.flags = max_records, DRY_RUN if dry_run else 0
     return c
+
+
+def frustum_to_c(model_to_world, world_to_view, view_to_clip, guard_band: float = 1.05) -> LodFrustumC:
+    """The three matrices of a PrepassParams (glm's memory order, 16 floats each) and the guard band of the frustum test; 1.05 is the
+    prepass's own."""
+    c = LodFrustumC()
+    for name, m in (("model_to_world", model_to_world), ("world_to_view", world_to_view), ("view_to_clip", view_to_clip)):
+        a = np.ascontiguousarray(m, np.float32).reshape(-1)
+        if a.size != 16:
+            raise ValueError(f"{name}: 16 floats expected")
+        getattr(c, name)[:] = a.tolist()
+    c.guard_band = float(np.float32(guard_band))
+    return c
+
+
+def frustum_of(prepass_params, guard_band: float = 1.05) -> LodFrustumC:
+    """The frustum of a mesh2splat_amd.prepass.PrepassParams: its model, view and projection matrices."""
+    return frustum_to_c(prepass_params.model_mat, prepass_params.view_mat, prepass_params.proj_mat, guard_band)
 
 
 def focal_px(view_to_clip, H: int) -> float:

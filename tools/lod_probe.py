@@ -8,6 +8,7 @@ against the mesh for the cut, for the full records and for merge_to_budget to th
     python tools/lod_probe.py --world-units [--tau 1,2,4] [--frames] --out profiles/lod/probe_world.json
     python tools/lod_probe.py --world-units --unsigned-axis [--frames] --out profiles/lod/probe_unsigned.json
     python tools/lod_probe.py --budget [--budgets 50000,200000,1000000] [--out profiles/lod/probe_budget.json]
+    python tools/lod_probe.py --frustum [--factors 0.25,0.5,1,2] [--tau 1,2,4] [--budgets ...] [--out profiles/lod/probe_frustum.json]
 
 --world-units: every conversion is followed by m2s_records_to_world_units, so the tree's edges are world lengths and tau_px counts
 screen pixels (default --tau 1,2,4); the result also carries the pass's own time (in place, and out of place from adopted memory) beside
@@ -23,6 +24,12 @@ yardsticks of the plain run (m2s_prune, merge_to_budget, the pass's own time) ar
 stages, the tau_px and the count it returns, and in the same process the yardstick a caller had without it: 31 M2S_LOD_DRY_RUN calls of
 m2s_lod_select that build the same key from its top bit down on the host (each a sweep and a round trip of the counts), then the real
 cut at the tau found; their sweeps' device time summed, and the whole search on the host's clock beside the budget call's.
+
+--frustum: m2s_lod_select_frustum and m2s_lod_select_budget_frustum on the same tree (world units, M2S_MERGE_UNSIGNED_AXIS), per distance
+factor with the preview camera's own matrices and the prepass's guard band: the leaves inside; per --tau the visibility stage and the
+three cut stages beside the plain m2s_lod_select at the same tau, the counts of both, and m2s_prepass_sorted (keys with the frustum
+test, radix sort, prepass over the survivors) + m2s_splat of the frame drawn from either result; per budget the tau_px, the counts and
+the stages of both budget functions.  The yardstick is the plain calls; which of the two runs first alternates between repetitions.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
 tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
@@ -42,14 +49,21 @@ def main():
     ap.add_argument("--tau", default="")
     ap.add_argument("--world-units", action="store_true")
     ap.add_argument("--unsigned-axis", action="store_true")
-    ap.add_argument("--factors", default="1,2,4,8")
+    ap.add_argument("--factors", default=None)
     ap.add_argument("--frames", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--budget", action="store_true")
     ap.add_argument("--budgets", default="50000,200000,1000000")
+    ap.add_argument("--frustum", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.frustum and a.budget:
+        ap.error("--frustum and --budget are two runs: give one of them")
+    a.factors = a.factors or ("0.25,0.5,1,2" if a.frustum else "1,2,4,8")
+    if a.frustum:
+        a.world_units = True
+        a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_frustum.json")
     if a.budget:
         a.world_units = True
         a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_budget.json")
@@ -126,6 +140,84 @@ def main():
                 rows.append(ms)
         return counts, median_of(rows)
 
+    if a.frustum:
+        from mesh2splat_amd.splat import SplatParams
+        records = convert()
+        build = conv.lod_build(unsigned_axis=True)
+        first = build["first"]
+        res = {"scene": "c3", "density": R, "size": [W, H], "records": records, "reps": a.reps, "warmup": a.warmup, "world_units": True, "unsigned_axis": True,
+               "guard_band": 1.05,
+               "build": {"counts": {k: v for k, v in build.items() if k != "first"}, "per_level_nodes": [first[l + 1] - first[l] for l in range(len(first) - 1)],
+                         "ms": conv.last_lod_build_ms}, "cells": []}
+
+        def draw(cam):
+            """m2s_prepass_sorted + m2s_splat of the current records -> (quads drawn, pass times).  prepass_sorted reports its stages
+            through the depth sort's counters: the keys (with the frustum test) over every record handed over, the radix sort, then the
+            prepass over the survivors; last_sort_ms spans the three"""
+            pp, _ = cam.frame_params(conv.resolution, light, 4.0 * dist * dist)
+            drawn = conv.prepass_sorted(pp, download=False)
+            st = conv.last_sort_stage_ms
+            ms = {"keys": st["keys"], "radix_sort": st["radix_sort"], "prepass": st["gather"], "prepass_sorted": conv.last_sort_ms}
+            conv.splat(SplatParams((W, H), 0), download=False)
+            ms["splat"] = conv.last_splat_ms
+            ms["total"] = ms["prepass_sorted"] + ms["splat"]
+            return drawn, ms
+
+        def pair(cam, call, stages, fr):
+            """warmup + reps of one cut without and with the frustum, each followed by its frame; which of the two runs first alternates
+            from one repetition to the next -> {"plain" | "frustum": (result, quads drawn, median stages, median frame passes)}"""
+            modes = (("plain", None), ("frustum", fr))
+            rows, frames, got, drawn = {"plain": [], "frustum": []}, {"plain": [], "frustum": []}, {}, {}
+            for k in range(a.warmup + a.reps):
+                for name, frustum in (modes if k % 2 == 0 else modes[::-1]):
+                    now = call(frustum)
+                    assert name not in got or now == got[name]                        # integer sums: the same from run to run
+                    got[name] = now
+                    ms = stages(frustum)
+                    drawn[name], fm = draw(cam)
+                    if k >= a.warmup:
+                        rows[name].append(ms)
+                        frames[name].append(fm)
+            return {name: (got[name], drawn[name], median_of(rows[name]), median_of(frames[name])) for name, _ in modes}
+
+        def select_stages(frustum):
+            ms = conv.last_lod_select_stage_ms()
+            if frustum:
+                ms["visibility"] = conv.last_lod_frustum_ms()
+            ms["total"] = sum(ms.values())
+            return ms
+
+        def budget_stages(frustum):
+            ms = dict(conv.last_lod_budget_stage_ms)
+            if frustum:
+                ms["visibility"] = conv.last_lod_frustum_ms()
+            ms["total"] = sum(ms.values())
+            return ms
+
+        for f in [float(v) for v in a.factors.split(",")]:
+            cam = camera(f)
+            eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
+            fr = lod.frustum_to_c(np.eye(4, dtype=np.float32), cam.view_mat, cam.proj_mat, 1.05)
+            cell = {"factor": f, "cuts": [], "budgets": []}
+            for tau in [float(v) for v in a.tau.split(",")]:
+                row = {"tau_px": tau}
+                for name, (got, drawn, stage, fm) in pair(cam, lambda frustum: conv.lod_select(eye, focal, tau, cam.near, frustum=frustum), select_stages, fr).items():
+                    row[name] = {"counts": got, "quads_drawn": drawn, "select_stage_ms": stage, "frame_pass_ms": fm}
+                cell["visible_leaves"] = row["frustum"]["counts"]["visible_leaves"]
+                cell["cuts"].append(row)
+            for budget in [int(v) for v in a.budgets.split(",")]:
+                row = {"budget": budget}
+                for name, (got, drawn, stage, fm) in pair(cam, lambda frustum: conv.lod_select_budget(eye, focal, budget, near=cam.near, frustum=frustum),
+                                                          budget_stages, fr).items():
+                    row[name] = {"result": got, "quads_drawn": drawn, "budget_stage_ms": stage, "frame_pass_ms": fm}
+                cell["budgets"].append(row)
+            res["cells"].append(cell)
+            print(json.dumps(cell), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+        conv.close()
+        return
     if a.budget:
         import time
         records = convert()

@@ -90,6 +90,8 @@ struct Options {
     double lod_pixels = -1.0;                                      // --lod-pixels t: every --preview / --score camera takes its cut at tau_px = t first (m2s_lod_select)
     double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
     long long lod_budget = 0;                                      // --lod-budget N: every camera takes the finest cut of at most N records (m2s_lod_select_budget); --lod-pixels is then its floor
+    double lod_guard = -1.0;                                       // --lod-frustum [--lod-guard g]: the cuts select only what their camera sees (m2s_lod_select_frustum,
+    bool lod_frustum = false;                                      //   m2s_lod_select_budget_frustum), the frustum test widened by g (>= 1; 1.05, the prepass's own, without --lod-guard)
     bool lod() const { return !lod_levels.empty(); }
     bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
     bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
@@ -113,7 +115,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -177,6 +179,10 @@ void usage() {
                  "  --lod-pixels t is given too.  A budget below the size of the coarsest level gets that level.  Every entry of `views` then also\n"
                  "  has tau_px (the tau the cut was taken at), met and selected_finer (the records of the next finer cut, the one that did not\n"
                  "  fit), and the line has \"budget\": N; its own tau_px is the floor (0 without --lod-pixels).\n"
+                 "--lod-frustum [--lod-guard g] (g >= 1, default 1.05), with --lod-levels: every cut selects only nodes with a leaf inside its\n"
+                 "  camera's frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum), and a budget is spent on those alone.  The `lod:`\n"
+                 "  line then has \"frustum\": g, and every entry of `views` \"visible_leaves\" and \"culled\" (nodes the plain cut selects\n"
+                 "  and this one dropped).\n"
                  "--merge-unsigned-axis, with --merge-level, --merge-to or --lod-levels: the sign of a record's third axis carries no meaning\n"
                  "  (M2S_MERGE_UNSIGNED_AXIS: a group ends where |dot| is below d, and the members' axes are turned onto one side before they\n"
                  "  are averaged).  A conversion stores the two triangles of a flat quad with opposite signs, which the viewer does not see; with\n"
@@ -333,7 +339,8 @@ int lod_build(m2s_ctx* ctx, const Options& o, LodReport* rep) {
     return 0;
 }
 
-int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float view_to_clip[16], int H, double near_p, bool dry, LodReport* rep) {
+int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float world_to_view[16], const float view_to_clip[16], int H, double near_p,
+            bool dry, LodReport* rep) {
     m2s_lod_select_params sp;
     std::memset(&sp, 0, sizeof(sp));
     for (int k = 0; k < 3; ++k) sp.camera_position[k] = (float)eye[k];
@@ -343,6 +350,12 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float vie
     sp.flags = dry ? (uint32_t)M2S_LOD_DRY_RUN : 0u;
     uint64_t c[4] = {}, per[M2S_LOD_MAX_STEPS + 1] = {};
     std::string budget;
+    m2s_lod_frustum fr;                                                 // --lod-frustum: the camera's matrices, the records' space being the world's
+    std::memset(&fr, 0, sizeof(fr));
+    for (int k = 0; k < 4; ++k) fr.model_to_world[k * 5] = 1.0f;
+    std::memcpy(fr.world_to_view, world_to_view, sizeof(fr.world_to_view));
+    std::memcpy(fr.view_to_clip, view_to_clip, sizeof(fr.view_to_clip));
+    fr.guard_band = (float)o.lod_guard;
     if (o.lod_budget > 0) {                                             // the cut that fits: --lod-pixels, where given, is its floor
         m2s_lod_budget_params bp;
         std::memset(&bp, 0, sizeof(bp));
@@ -353,13 +366,18 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float vie
         bp.max_records = (uint32_t)o.lod_budget;
         bp.flags = sp.flags;
         m2s_lod_budget_result res;
-        if (m2s_lod_select_budget(ctx, &bp, &res, c) != M2S_OK) return 1;
+        if ((o.lod_frustum ? m2s_lod_select_budget_frustum(ctx, &bp, &fr, &res, c) : m2s_lod_select_budget(ctx, &bp, &res, c)) != M2S_OK) return 1;
         char tau[40];
         std::snprintf(tau, sizeof tau, "%.9g", (double)res.tau_px);
         budget = std::string(", \"tau_px\": ") + tau + ", \"met\": " + (res.met ? "true" : "false") + ", \"selected_finer\": " +
                  std::to_string((unsigned long long)res.selected_finer);
-    } else if (m2s_lod_select(ctx, &sp, c) != M2S_OK) {
+    } else if ((o.lod_frustum ? m2s_lod_select_frustum(ctx, &sp, &fr, c) : m2s_lod_select(ctx, &sp, c)) != M2S_OK) {
         return 1;
+    }
+    if (o.lod_frustum) {
+        uint64_t fc[2] = {};
+        if (m2s_last_lod_frustum_counts(ctx, fc) != M2S_OK) return 1;
+        budget += ", \"visible_leaves\": " + std::to_string((unsigned long long)fc[0]) + ", \"culled\": " + std::to_string((unsigned long long)fc[1]);
     }
     if (m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
     std::string levels;
@@ -375,7 +393,12 @@ void lod_print(const Options& o, const LodReport& rep) {
     for (size_t l = 0; l + 1 < rep.first.size(); ++l) per += std::string(l ? ", " : "") + std::to_string((unsigned long long)(rep.first[l + 1] - rep.first[l]));
     char tau[40];
     std::snprintf(tau, sizeof tau, "%.9g", o.lod_pixels >= 0.0 ? (double)(float)o.lod_pixels : 0.0);
-    const std::string budget = o.lod_budget > 0 ? ", \"budget\": " + std::to_string(o.lod_budget) : std::string();
+    std::string budget = o.lod_budget > 0 ? ", \"budget\": " + std::to_string(o.lod_budget) : std::string();
+    if (o.lod_frustum) {
+        char g[40];
+        std::snprintf(g, sizeof g, "%.9g", (double)(float)o.lod_guard);
+        budget += std::string(", \"frustum\": ") + g;
+    }
     std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
                 budget.c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
@@ -389,7 +412,7 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     std::memset(&pp, 0, sizeof(pp));
     double eye[3], ctr[3], near_p, far_p;
     preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p, o.view_distance);
-    if (lod && lod_cut(ctx, o, eye, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
+    if (lod && lod_cut(ctx, o, eye, pp.world_to_view, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
     for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
     pp.resolution[0] = W; pp.resolution[1] = H;
     pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
@@ -545,7 +568,7 @@ int write_score(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint32_
         m2s_prepass_params pp;
         std::memset(&pp, 0, sizeof(pp));
         camera_matrices(eye, ctr, near_p, far_p, W, H, pp.world_to_view, pp.view_to_clip);
-        if (lod && lod_cut(ctx, o, eye, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
+        if (lod && lod_cut(ctx, o, eye, pp.world_to_view, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
         for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
         pp.resolution[0] = W; pp.resolution[1] = H;
         pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
@@ -1092,7 +1115,7 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
                     const double eye[3] = { c.ctr[0] + dist * std::cos(el) * std::sin(th), c.ctr[1] + dist * std::sin(el), c.ctr[2] + dist * std::cos(el) * std::cos(th) };
                     float view[16], proj[16];
                     camera_matrices(eye, c.ctr, c.near_p, c.far_p * o.view_distance, o.preview_w, o.preview_h, view, proj);
-                    ok = lod_cut(ctx[c.slot], o, eye, proj, o.preview_h, c.near_p, true, &rep) == 0;
+                    ok = lod_cut(ctx[c.slot], o, eye, view, proj, o.preview_h, c.near_p, true, &rep) == 0;
                 }
                 if (ok) lod_print(o, rep);
                 else { std::fprintf(stderr, "%s: lod: %s\n", c.in.c_str(), m2s_last_error(ctx[c.slot])); ++failures; }
@@ -1218,6 +1241,8 @@ int main(int argc, char** argv) {
         else if (a == "--merge-group") { o.merge_group = std::atoi(next()); if (o.merge_group < 2 || o.merge_group > 64) { usage(); return 2; } }
         else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
         else if (a == "--lod-pixels") { o.lod_pixels = std::atof(next()); if (!(o.lod_pixels >= 0.0) || !std::isfinite(o.lod_pixels)) { usage(); return 2; } }
+        else if (a == "--lod-frustum") o.lod_frustum = true;
+        else if (a == "--lod-guard") { o.lod_guard = std::atof(next()); if (!(o.lod_guard >= 1.0) || !std::isfinite(o.lod_guard)) { usage(); return 2; } }
         else if (a == "--lod-budget") {
             const std::string v = next();
             char* end = nullptr;
@@ -1295,6 +1320,8 @@ int main(int argc, char** argv) {
     // --lod-*: the levels with a bound in pixels, a budget or both, or none of them; the cuts need cameras (--preview / --score; a batch
     // draws no preview) and one context
     if (o.lod() != (o.lod_pixels >= 0.0 || o.lod_budget > 0)) { usage(); return 2; }
+    if ((o.lod_frustum && !o.lod()) || (o.lod_guard >= 0.0 && !o.lod_frustum)) { usage(); return 2; }   // (--lod-frustum: a mode of the cuts; --lod-guard: of --lod-frustum)
+    if (o.lod_frustum && o.lod_guard < 0.0) o.lod_guard = 1.05;
     if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
