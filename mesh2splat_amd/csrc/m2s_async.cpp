@@ -113,11 +113,9 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
     // that buffer holds (any more): consumers (m2s_download, m2s_export_ply, m2s_prepass, sorts) then refuse instead of
     // returning the other conversion's records.
     const bool stale = sl.own_lane >= 0 && sl.gen != c->lane[sl.own_lane].rec_gen;
-    if (sl.sync_result) {   // run_pass already filled last_*
+    if (sl.sync_result) {   // run_pass has run it already; its records may not be the current ones any more
         if (out_total) *out_total = sl.sync_total;
-        c->last_total = sl.sync_total; c->last_stored = sl.limit; c->last_records = sl.d_out; c->last_R = sl.R; c->conv_R = 0;
-        ++c->records_epoch;
-        c->records_stale = stale;
+        c->slot_adopted(sl.d_out, sl.sync_total, sl.limit, sl.R, stale);
         memcpy(c->last_ms, sl.ms, sizeof sl.ms);
         return M2S_OK;
     }
@@ -138,13 +136,7 @@ m2s_status m2s_convert_wait(m2s_ctx* c, uint64_t* out_total) {
     }
     if (sl.wrote_bands && rip) { rip->bands_ready = true; rip->bands_unit = sl.bands_unit; }   // that launch has completed: its run table is in place
     if (total > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 fragments: offsets are 32-bit");
-    c->last_total = total;
-    c->last_stored = std::min(total, sl.limit);
-    c->last_records = sl.d_out;
-    ++c->records_epoch;
-    c->last_R = sl.R;
-    c->conv_R = 0;
-    c->records_stale = stale;
+    c->slot_adopted(sl.d_out, total, std::min(total, sl.limit), sl.R, stale);
     if (out_total) *out_total = total;
     return M2S_OK;
 }

@@ -113,9 +113,8 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     if (bp->use_shadows && !c->shadow_S) return fail(c, M2S_ERR_STATE, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->bake_ev.ensure(c->err));
-    c->sh_valid = false;
+    c->sh_tag.clear();
     c->bake_has_counts = false;
-    c->sh_n = 0;
     M2S_TRY(c->d_sh.reserve(c->err, n, 48 * sizeof(float)));
     const bool counts = bp->want_shadow_counts != 0;
     if (counts) M2S_TRY(c->d_bake_counts.reserve(c->err, n, 1));
@@ -143,36 +142,34 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     if (c->profiling) HIPCHK(c, hipEventRecord(c->bake_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_bake_ms, c->bake_ev[0], c->bake_ev[1]));
-    c->sh_n = n;
-    c->sh_valid = true;
-    c->sh_of = d_records;
-    c->sh_epoch = d_records == c->last_records ? c->records_epoch : 0;
+    if (d_records == c->last_records) c->sh_tag.set(*c, n);
+    else c->sh_tag.set_foreign(d_records, n);
     c->bake_has_counts = counts;
     c->sh_degree = bp->degree;
     return M2S_OK;
 }
 
-const void* m2s_device_sh(const m2s_ctx* c) { return c && c->sh_valid ? c->d_sh.get() : nullptr; }
+const void* m2s_device_sh(const m2s_ctx* c) { return c && c->sh_tag.is_set() ? c->d_sh.get() : nullptr; }
 
 m2s_status m2s_download_sh(m2s_ctx* c, float* dst, uint64_t capacity_records) {
     if (!c) return M2S_ERR_INVALID;
-    if (!c->sh_valid) return fail(c, M2S_ERR_STATE, "no m2s_bake_light has run");
-    if (!c->sh_n) return M2S_OK;
+    if (!c->sh_tag.is_set()) return fail(c, M2S_ERR_STATE, "no m2s_bake_light has run");
+    if (!c->sh_tag.n) return M2S_OK;
     if (!dst) return fail(c, M2S_ERR_INVALID, "dst is NULL");
-    if (capacity_records < c->sh_n) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
+    if (capacity_records < c->sh_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_sh, c->sh_n * 48 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_sh, c->sh_tag.n * 48 * sizeof(float), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
 m2s_status m2s_download_bake_shadow_counts(m2s_ctx* c, uint8_t* dst, uint64_t capacity_bytes) {
     if (!c) return M2S_ERR_INVALID;
-    if (!c->sh_valid || !c->bake_has_counts) return fail(c, M2S_ERR_STATE, "the last m2s_bake_light kept no shadow counts (want_shadow_counts)");
-    if (!c->sh_n) return M2S_OK;
+    if (!c->sh_tag.is_set() || !c->bake_has_counts) return fail(c, M2S_ERR_STATE, "the last m2s_bake_light kept no shadow counts (want_shadow_counts)");
+    if (!c->sh_tag.n) return M2S_OK;
     if (!dst) return fail(c, M2S_ERR_INVALID, "dst is NULL");
-    if (capacity_bytes < c->sh_n) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
+    if (capacity_bytes < c->sh_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination smaller than the plane");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_bake_counts, c->sh_n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_bake_counts, c->sh_tag.n, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -183,7 +180,7 @@ m2s_status m2s_sh_shade_records(m2s_ctx* c, const float model_to_world[16], cons
     if (!c || !model_to_world || !camera_position) return M2S_ERR_INVALID;
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (m2s_status s = pick_records(c, d_records, n)) return s;
-    if (!c->sh_valid || c->sh_n != n) return fail(c, M2S_ERR_STATE, "no baked coefficients for this many records (run m2s_bake_light on them)");
+    if (!c->sh_tag.is_set() || c->sh_tag.n != n) return fail(c, M2S_ERR_STATE, "no baked coefficients for this many records (run m2s_bake_light on them)");
     if (n && !d_dst) return fail(c, M2S_ERR_INVALID, "d_dst is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     ShadeK k;
@@ -209,8 +206,8 @@ m2s_status m2s_export_ply_sh(m2s_ctx* c, const char* path, float gaussian_std) {
     if (!c || !path) return M2S_ERR_INVALID;
     if (!c->last_R) return fail(c, M2S_ERR_STATE, "no conversion has run (uploaded records carry no resolutionTarget: use m2s_write_ply_sh)");
     if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-    if (!c->sh_valid) return fail(c, M2S_ERR_STATE, "no m2s_bake_light has run");
-    if (c->sh_n != c->last_stored) return fail(c, M2S_ERR_STATE, "the baked plane holds another number of records than the conversion stored");
+    if (!c->sh_tag.is_set()) return fail(c, M2S_ERR_STATE, "no m2s_bake_light has run");
+    if (c->sh_tag.n != c->last_stored) return fail(c, M2S_ERR_STATE, "the baked plane holds another number of records than the conversion stored");
     HIPCHK(c, hipSetDevice(c->device));
     const float scale_multiplier = gaussian_std / static_cast<float>(c->last_R);      // SceneManager.cpp:668, as m2s_export_ply
     const uint64_t n = c->last_stored;

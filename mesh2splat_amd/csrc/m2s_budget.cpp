@@ -1,5 +1,5 @@
 // m2s_budget.cpp — pruning to a budget (m2s_prune_budget): host side of m2s_budget.hip.  The select leaves keep flags and their offsets
-// where m2s_prune leaves its own; the compaction and what follows it are m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue, prune_adopt).
+// where m2s_prune leaves its own; the compaction and what follows it are m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue; m2s_recstate.h: rewritten).
 #include "m2s_ctx.h"
 
 #include <algorithm>
@@ -17,9 +17,7 @@ m2s_status m2s_prune_budget(m2s_ctx* c, const m2s_budget_params* p, uint64_t* ou
     if (p->importance != M2S_IMPORTANCE_VIEWS && p->importance != M2S_IMPORTANCE_AREA) return fail(c, M2S_ERR_INVALID, "unknown importance");
     const bool views = p->importance == M2S_IMPORTANCE_VIEWS;
     if (views && std::isnan(p->min_weight)) return fail(c, M2S_ERR_INVALID, "min_weight is NaN");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    M2S_TRY(have_records(c));
     if (views && !contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin, m2s_contrib_accumulate)");
     const uint64_t n = c->last_stored;
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
@@ -63,7 +61,7 @@ m2s_status m2s_prune_budget(m2s_ctx* c, const m2s_budget_params* p, uint64_t* ou
             c->last_budget_stage_ms[0] = c->last_budget_stage_ms[1] = c->last_budget_stage_ms[2] = 0.0f;
         }
     }
-    prune_adopt(c, kept, R, sh);
+    c->rewritten(c->lane[0].records, kept, R, sh ? Rewrite::PruneWithSh : Rewrite::Prune);
     const bool active = h[kBudgetActive] != 0;
     c->last_budget_counts[0] = n;
     c->last_budget_counts[1] = candidates;

@@ -40,12 +40,9 @@ m2s_status m2s_export_ply_compact(m2s_ctx* c, const char* path, float gaussian_s
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = 0;
     if (!c || !path) return M2S_ERR_INVALID;
     if (!std::isfinite(gaussian_std) || !(gaussian_std > 0.0f)) return fail(c, M2S_ERR_INVALID, "gaussian_std must be finite and > 0");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-    const uint64_t n64 = c->last_stored;
-    if (n64 > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
-    if (use_baked_sh && (!c->sh_valid || c->sh_n != n64)) return fail(c, M2S_ERR_STATE, "no baked coefficients for this many records (run m2s_bake_light on them)");
+    uint64_t n64 = 0;
+    M2S_TRY(need_records(c, &n64));
+    if (use_baked_sh && (!c->sh_tag.is_set() || c->sh_tag.n != n64)) return fail(c, M2S_ERR_STATE, "no baked coefficients for this many records (run m2s_bake_light on them)");
     const uint32_t n = (uint32_t)n64;
     const uint32_t K = use_baked_sh ? m2s_compact::sh_coefficients(c->sh_degree) : 0u;
     // SceneManager.cpp:668, as m2s_export_ply; records without a resolutionTarget (uploaded ones) are taken as converted at R = 1

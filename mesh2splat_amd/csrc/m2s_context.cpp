@@ -98,7 +98,7 @@ m2s_status ensure_records(m2s_ctx* c, uint64_t want) {
     if (l0.records.cap()) grow = std::max(grow, 2 * l0.records.cap());
     if (c->cap_policy < 0) grow = std::max(want, std::min<uint64_t>(grow, kMaxGaussiansToSort));
     drain_in_flight(c);   // nothing may still be writing the buffer that is about to be released
-    if (l0.records && c->last_records == l0.records) { c->last_records = nullptr; c->last_stored = 0; }   // they go with the old pool
+    c->pool_released(l0.records.get());   // current records that live there go with the old pool
     // (the larger request may fail where the one the caller needs still fits)
     if (grow == want || !l0.records.try_reserve(grow, sizeof(m2s_gaussian))) M2S_TRY(l0.records.reserve(c->err, want, sizeof(m2s_gaussian)));
     // in-flight conversions into the old buffer are complete but their records are gone
@@ -214,8 +214,7 @@ m2s_status m2s_geo_planes(const m2s_ctx* c, uint64_t* out_bytes, int* out_in_use
 }
 
 int m2s_positions_ready(const m2s_ctx* c) {
-    return c && c->d_pos_plane && c->last_records && c->pos_plane_of == c->last_records && c->pos_plane_n == c->last_stored &&
-           c->pos_plane_epoch == c->records_epoch && c->last_stored ? 1 : 0;
+    return c && c->last_stored && positions_valid(c, c->last_stored) ? 1 : 0;
 }
 
 m2s_status m2s_set_keep_positions(m2s_ctx* c, int enabled) {

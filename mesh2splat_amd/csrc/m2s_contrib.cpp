@@ -12,15 +12,6 @@ using namespace m2s_host;
 
 namespace m2s_host {
 
-bool contrib_valid(const m2s_ctx* c) {
-    return c->contrib_active && c->last_records && !c->records_stale && c->contrib_of == c->last_records && c->contrib_n == c->last_stored &&
-           c->contrib_epoch == c->records_epoch;
-}
-
-bool prune_sh_plane(const m2s_ctx* c, uint64_t n) {
-    return c->sh_valid && c->sh_of == c->last_records && c->sh_epoch == c->records_epoch && c->sh_n == n;
-}
-
 m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh, const void* src) {
     if (!n) {
         if (!c->lane[0].records || c->last_records != c->lane[0].records) return ensure_records(c, 1);
@@ -45,20 +36,6 @@ m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const ui
     return M2S_OK;
 }
 
-void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh) {
-    // the survivors are the context's current records now, at the resolutionTarget of the ones they were taken from
-    c->last_records = c->lane[0].records;
-    ++c->records_epoch;
-    c->last_total = c->last_stored = kept;
-    c->last_R = R;
-    c->records_stale = false;
-    c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
-    c->sq_src = nullptr;
-    c->contrib_active = false;
-    if (sh) { c->sh_n = kept; c->sh_of = c->last_records; c->sh_epoch = c->records_epoch; }
-    if (c->bake_has_counts && sh) c->bake_has_counts = false;       // (the tap counts are not compacted)
-}
-
 }  // namespace m2s_host
 
 extern "C" {
@@ -73,33 +50,27 @@ m2s_status m2s_upload_quad_sources(m2s_ctx* c, const uint32_t* host_sources, uin
     M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
     HIPCHK(c, hipMemcpy(c->d_sq_src, host_sources, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->sq_src = c->d_sq_src;
-    c->sq_src_epoch = c->records_epoch;
+    c->sq_src_tag.set(*c, n);
     return M2S_OK;
 }
 
 m2s_status m2s_contrib_begin(m2s_ctx* c) {
     if (!c) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-    const uint64_t n = c->last_stored;
-    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    uint64_t n = 0;
+    M2S_TRY(need_records(c, &n));
     HIPCHK(c, hipSetDevice(c->device));
-    c->contrib_active = false;
+    c->contrib_tag.clear();
     M2S_TRY(c->d_contrib.reserve(c->err, std::max<uint64_t>(n, 1), 2 * sizeof(uint32_t)));
     HIPCHK(c, hipMemsetAsync(c->d_contrib, 0, c->d_contrib.cap() * 2 * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->contrib_of = c->last_records;
-    c->contrib_n = n;
-    c->contrib_epoch = c->records_epoch;
-    c->contrib_active = true;
+    c->contrib_tag.set(*c, n);
     return M2S_OK;
 }
 
 m2s_status m2s_upload_contrib(m2s_ctx* c, const uint32_t* host_wmax, const uint32_t* host_npix, uint64_t n) {
     if (!c) return M2S_ERR_INVALID;
     if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin)");
-    if (n != c->contrib_n) return fail(c, M2S_ERR_INVALID, "the number of words is not the number of records");
+    if (n != c->contrib_tag.n) return fail(c, M2S_ERR_INVALID, "the number of words is not the number of records");
     if (host_wmax)
         for (uint64_t i = 0; i < n; ++i)
             if (host_wmax[i] > 0x3F800000u) return fail(c, M2S_ERR_INVALID, "a wmax word is not the bits of a weight in [0, 1]");
@@ -117,10 +88,10 @@ m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float c
     if (p->render_mode < 0 || p->render_mode > 6 || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "render mode outside 0..6 or reserved != 0");
     if (p->render_mode == 4) return fail(c, M2S_ERR_INVALID, "render mode 4 (overdraw) has no fragment weight");
     if (!(count_weight >= 0.0f) || !std::isfinite(count_weight)) return fail(c, M2S_ERR_INVALID, "count_weight is negative or not finite");
-    if (!c->contrib_active) return fail(c, M2S_ERR_INVALID, "no m2s_contrib_begin");
+    if (!c->contrib_tag.is_set()) return fail(c, M2S_ERR_INVALID, "no m2s_contrib_begin");
     if (!contrib_valid(c)) return fail(c, M2S_ERR_INVALID, "the records changed since m2s_contrib_begin");
     if (!c->sq_n) return fail(c, M2S_ERR_INVALID, "no sorted quads (run m2s_prepass_sorted)");
-    if (!c->sq_src || c->sq_src_epoch != c->records_epoch)
+    if (!c->sq_src || !c->sq_src_tag.holds(*c))
         return fail(c, M2S_ERR_INVALID, "the sorted quads carry no sources (they come from m2s_prepass_sorted or m2s_upload_quad_sources)");
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t nq = (uint32_t)c->sq_n;
@@ -145,11 +116,12 @@ const void* m2s_device_contrib(const m2s_ctx* c, uint32_t which) {
 m2s_status m2s_download_contrib(m2s_ctx* c, uint32_t* dst_wmax, uint32_t* dst_npix, uint64_t capacity) {
     if (!c) return M2S_ERR_INVALID;
     if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin)");
-    if (capacity < c->contrib_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
-    if (!c->contrib_n) return M2S_OK;
+    const uint64_t n = c->contrib_tag.n;
+    if (capacity < n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (dst_wmax) HIPCHK(c, hipMemcpy(dst_wmax, c->d_contrib, c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (dst_npix) HIPCHK(c, hipMemcpy(dst_npix, c->d_contrib + c->d_contrib.cap(), c->contrib_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (dst_wmax) HIPCHK(c, hipMemcpy(dst_wmax, c->d_contrib, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (dst_npix) HIPCHK(c, hipMemcpy(dst_npix, c->d_contrib + c->d_contrib.cap(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -199,7 +171,7 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
     if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_prune_ms, c->prune_ev[0], c->prune_ev[1]));
-    prune_adopt(c, kept, R, sh);
+    c->rewritten(c->lane[0].records, kept, R, sh ? Rewrite::PruneWithSh : Rewrite::Prune);
     c->last_prune_counts[0] = n; c->last_prune_counts[1] = kept; c->last_prune_counts[2] = by_w; c->last_prune_counts[3] = by_p;
     if (out_kept) *out_kept = kept;
     return M2S_OK;

@@ -17,10 +17,12 @@
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
+//   m2s_recstate.h   the current records, what hangs on them and the transitions between them: RecordState (a base of m2s_ctx), RecordsTag
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_devbuf.h"
 #include "m2s_device.h"
+#include "m2s_recstate.h"
 #include "m2s_vdedup.h"
 
 #include <cstdint>
@@ -51,7 +53,7 @@ struct GBufPlanes {
 }  // namespace m2s_host
 
 constexpr int kBandSlotsMax = 64;   // (scene, R) entries remembered per context: band tables, decisions
-struct m2s_ctx {
+struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dependents: m2s_recstate.h)
     int device = 0;
     m2s_host::StreamSet<2> streams;         // lane k's stream; in front of every buffer and event: destroyed after them
     hipStream_t stream = nullptr;           // streams[0] == lane[0].stream: what every pass but a second-lane conversion runs on
@@ -146,35 +148,23 @@ struct m2s_ctx {
                   hipStream_t st = nullptr; bool shared_work = false; };   // stream it ran on; did it use the context's shared work buffers (chain, deferred list)?
     Slot slot[M2S_MAX_IN_FLIGHT];
     uint32_t slot_head = 0, slot_count = 0; // oldest in-flight slot, number in flight
-    bool records_stale = false;             // the conversion last waited for has been overwritten by a later submission
 
-    // output
-    const void* last_records = nullptr;
     int64_t cap_policy = -1;
-    uint64_t last_total = 0, last_stored = 0;
-    uint32_t last_R = 0;                    // resolutionTarget of the current records: the unit of their scales (0: uploaded, taken as 1)
-    uint32_t conv_R = 0;                    // set by m2s_records_to_world_units alone, which takes last_R to 1: the R those records were converted
-                                            // at (converted_R); 0 again with the next records of another source (conversion, upload, adoption)
 
     // depth sort (f-2)
-    m2s_host::DevBuf<float4> d_sorted;     // capacity in records
-    uint64_t sorted_n = 0;
+    m2s_host::DevBuf<float4> d_sorted;     // capacity in records (sorted_n of them)
     m2s_host::DevBuf<uint32_t> d_sort_u32;   // keys_in | vals_in | keys_out | vals_out: capacity in records (four words each), sliced by the CURRENT n
     uint32_t sorted_key_offset = 0;   // keys_out holds key - this (m2s_device_sorted_keys adds it back once)
     m2s_host::DevBuf<void> d_sort_temp;      // capacity: the bytes last asked for
     float last_sort_ms = 0.0f;
     float last_sort_stage_ms[3] = { 0, 0, 0 };   // keys | radix sort | gather of the last m2s_sort_by_depth (profiling on)
     // the positions of the current records as a compact plane (16 B each), left behind by the first depth sort after the records
-    // changed and used for the keys of every later one (m2s_sort.hip); valid for (pos_plane_of, pos_plane_n, pos_plane_epoch)
+    // changed and used for the keys of every later one (m2s_sort.hip); valid while pos_plane_tag holds
     m2s_host::DevBuf<float4> d_pos_plane;
-    uint64_t pos_plane_n = 0, pos_plane_epoch = 0;
-    const void* pos_plane_of = nullptr;
     bool keep_positions = false;      // m2s_set_keep_positions: conversions leave the plane behind themselves where their kernel can (k_sparse)
-    uint64_t records_epoch = 1;       // advances whenever the records behind last_records may have changed
     // viewer prepass (m2s_prepass): survivors, their depths, the look-back chain of its kernel, a copy of the depth image
     m2s_host::DevBuf<float4> d_quads;
-    m2s_host::DevBuf<float> d_pp_depths;
-    uint64_t pp_visible = 0;
+    m2s_host::DevBuf<float> d_pp_depths;      // (pp_visible of each)
     m2s_host::DevBuf<unsigned long long> d_pp_chain;     // capacity in words
     uint32_t pp_epoch = 0;
     m2s_host::DevBuf<float> d_pp_depthtex;
@@ -189,8 +179,7 @@ struct m2s_ctx {
     float last_upload_ms[5] = { 0, 0, 0, 0, 0 }; // [0] total, [1] geometry, [2] textures + mips + combo, [3] allocations, [4] warm_scene
     m2s_host::DevBuf<uint8_t> d_rows;        // m2s_export_ply: .ply rows encoded on the device (formats 1 and 2); capacity in bytes
     m2s_host::DevBuf<void> d_loaded;         // m2s_upload_records (a loaded .ply)
-    m2s_host::DevBuf<float4> d_sorted_quads; // m2s_sort_prepass
-    uint64_t sq_n = 0;
+    m2s_host::DevBuf<float4> d_sorted_quads; // m2s_sort_prepass (sq_n of them)
     float last_sort_prepass_ms = 0.0f;
     // splat pass (m2s_splat.cpp): the five G-buffer planes of the last call and the pass's grow-only work buffers
     m2s_host::GBufPlanes d_gbuf;
@@ -202,14 +191,10 @@ struct m2s_ctx {
     uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
     // sources of the sorted quads (m2s_prepass_sorted): which record each was made from.  Dense path: the first sq_n words of the
     // permutation in d_sort_u32 (an alias: dropped by whatever rewrites those words); compacting path: d_sq_src, written by k_prepass
-    const uint32_t* sq_src = nullptr;        // nullptr: absent
-    uint64_t sq_src_epoch = 0;               // records_epoch they index into
+    // (sq_src points at whichever it is, sq_src_tag names the records they index into)
     m2s_host::DevBuf<uint32_t> d_sq_src;
-    // contribution pass and pruning (m2s_contrib.cpp): wmax | npix, one capacity of words each, valid for (contrib_of, contrib_n, contrib_epoch)
+    // contribution pass and pruning (m2s_contrib.cpp): wmax | npix, one capacity of words each, valid while contrib_tag holds
     m2s_host::DevBuf<uint32_t> d_contrib;
-    uint64_t contrib_n = 0, contrib_epoch = 0;
-    const void* contrib_of = nullptr;
-    bool contrib_active = false;
     float last_contrib_ms = 0.0f;
     float last_contrib_stage_ms[3] = { 0, 0, 0 };
     m2s_host::DevBuf<uint32_t> d_prune_u32;  // flags | offsets, one capacity of words each
@@ -225,23 +210,17 @@ struct m2s_ctx {
     uint64_t last_budget_counts[6] = { 0, 0, 0, 0, 0, 0 };
     float last_budget_stage_ms[3] = { 0, 0, 0 };   // keys + select rounds, flags + scans, compaction (profiling on)
     m2s_host::EventSet<5> budget_ev;               // start, select done, scans done | compaction: start, end
-    // colour refit (m2s_refit.cpp): num (int64, three words per record) | den (uint64), one capacity of records; valid for
-    // (refit_of, refit_n, refit_epoch) as the contribution accumulators are
+    // colour refit (m2s_refit.cpp): num (int64, three words per record) | den (uint64), one capacity of records; valid while refit_tag holds
     m2s_host::DevBuf<unsigned long long> d_refit;
-    uint64_t refit_n = 0, refit_epoch = 0;
-    const void* refit_of = nullptr;
-    bool refit_active = false;
     m2s_host::DevBuf<unsigned long long> d_refit_counts;   // m2s_refit_apply: updated, clamped, left for lack of weight
     float last_refit_stage_ms[3] = { 0, 0, 0 };    // setup + bin, grouping, refit blend (profiling on)
     float last_refit_apply_ms = 0.0f;
     m2s_host::EventSet<2> refit_ev;                // the apply
     // merge pass (m2s_merge.cpp): flag | run_start | packed (64-bit) | sums (64-bit) | seg_start (7 capacities of words; sized for n + 1), the totals, and the
-    // map of the last merge, valid for (merge_map_of, merge_map_epoch); keys, permutation and the sort's work area are the compact export's
+    // map of the last merge, valid while merge_map_tag holds; keys, permutation and the sort's work area are the compact export's
     m2s_host::DevBuf<uint32_t> d_merge_u32;
     m2s_host::DevBuf<uint32_t> d_merge_totals;
     m2s_host::DevBuf<uint32_t> d_merge_map;
-    uint64_t merge_map_n = 0, merge_map_epoch = 0;       // entries (the records before the merge); the records_epoch it leads into
-    const void* merge_map_of = nullptr;
     uint64_t last_merge_counts[4] = { 0, 0, 0, 0 };
     float last_merge_stage_ms[3] = { 0, 0, 0 };          // keys + sort, heads + scans, reduce + adopt
     m2s_host::EventSet<6> merge_ev;                      // keys + sort: 0-2 | segments: 3, 4 | reduce: 4, 5
@@ -256,12 +235,10 @@ struct m2s_ctx {
     float last_lod_build_ms = 0.0f;
     m2s_host::EventSet<2> lod_build_ev;
     // the cut (m2s_lod_select): a byte per node (every ancestor-or-self refines), the selected counts per level and the refining nodes
-    // behind them, the node index of every output record, valid for (lod_ids_of, lod_ids_epoch); flags, offsets and the scan area are m2s_prune's
+    // behind them, the node index of every output record, valid while lod_ids_tag holds; flags, offsets and the scan area are m2s_prune's
     m2s_host::DevBuf<uint8_t> d_lod_open;
     m2s_host::DevBuf<uint32_t> d_lod_counts;             // kLodCountWords
     m2s_host::DevBuf<uint32_t> d_lod_ids;
-    uint64_t lod_ids_n = 0, lod_ids_epoch = 0;
-    const void* lod_ids_of = nullptr;
     uint64_t last_lod_select_counts[4] = { 0, 0, 0, 0 };
     uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
     float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
@@ -330,13 +307,9 @@ struct m2s_ctx {
     float last_score_ms = 0.0f;
 
     // light baked into spherical harmonics (m2s_bake.cpp): the coefficient plane, the optional tap counts, the quadrature table
-    m2s_host::DevBuf<float> d_sh;                // float[n][48]: f_dc[3], f_rest[45] channel-major; capacity in records
-    uint64_t sh_n = 0;                           // records it holds
-    bool sh_valid = false;                       // a bake has completed since the plane was last (re)allocated
-    const void* sh_of = nullptr;                 // the records it was baked from, and their records_epoch when they were the context's
-    uint64_t sh_epoch = 0;                       // (0: the caller's records) — m2s_prune compacts the plane of the records it compacts
-    m2s_host::DevBuf<uint8_t> d_bake_counts;     // uint8[n]
-    bool bake_has_counts = false;
+    m2s_host::DevBuf<float> d_sh;                // float[n][48]: f_dc[3], f_rest[45] channel-major; capacity in records; sh_tag: set once a
+                                                 // bake has completed, n rows of the records it names — m2s_prune compacts the plane of the records it compacts
+    m2s_host::DevBuf<uint8_t> d_bake_counts;     // uint8[n] (bake_has_counts)
     m2s_host::DevBuf<float> d_bake_table;        // n_theta * n_phi rows of kBakeTableRow floats
     uint32_t bake_table_nt = 0, bake_table_np = 0;
     m2s_host::EventSet<2> bake_ev;
@@ -395,6 +368,22 @@ inline m2s_status pick_records(m2s_ctx* c, const void*& d_records, uint64_t& n) 
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
     return M2S_OK;
 }
+// What the passes over the context's own records open with: nothing in flight, records, not overwritten (have_records), at most
+// 2^32-1 of them (need_records; *n: how many).
+inline m2s_status have_records(m2s_ctx* c) {
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
+    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    return M2S_OK;
+}
+inline m2s_status need_records(m2s_ctx* c, uint64_t* n) {
+    M2S_TRY(have_records(c));
+    *n = c->last_stored;
+    if (*n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    return M2S_OK;
+}
+// the position plane belongs to the n current records (m2s_positions_ready: and there are some)
+inline bool positions_valid(const m2s_ctx* c, uint64_t n) { return c->d_pos_plane && c->pos_plane_tag.holds(*c, n); }
 constexpr int kBandSlots = kBandSlotsMax;
 
 // m2s_context.cpp
@@ -432,16 +421,14 @@ struct SplatBins { const uint32_t* vals = nullptr; const uint2* ranges = nullptr
 m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out);
 m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]);   // ... and their times + the blend's (ev[4..5]), profiling on
 // m2s_contrib.cpp
-bool contrib_valid(const m2s_ctx* c);   // the accumulators belong to the context's current records
+inline bool contrib_valid(const m2s_ctx* c) { return c->contrib_tag.holds(*c, c->last_stored); }   // the accumulators belong to the current records
 // What m2s_prune and m2s_prune_budget end with.  prune_compact_enqueue: the `kept` flagged records of the n current ones (and the rows of
 // a baked plane, with sh) go into the pool in order, through the staging buffer where they would land on themselves; n = 0: a pool to
-// point at.  prune_adopt, once the stream has drained: they are the context's current records at resolutionTarget R, and everything
-// derived from the old ones is invalid.
-bool prune_sh_plane(const m2s_ctx* c, uint64_t n);   // a baked plane of exactly these records exists
+// point at.  Once the stream has drained the caller records the event: c->rewritten(pool, kept, R, Rewrite::...) (m2s_recstate.h).
+inline bool prune_sh_plane(const m2s_ctx* c, uint64_t n) { return c->sh_tag.holds(*c, n); }   // a baked plane of exactly these n current records exists
 // src (m2s_lod_select): the n records are these, in memory that is not the pool, instead of the current ones; no plane then.
 m2s_status prune_compact_enqueue(m2s_ctx* c, uint64_t n, uint64_t kept, const uint32_t* flags, const uint32_t* offsets, bool sh,
                                  const void* src = nullptr);
-void prune_adopt(m2s_ctx* c, uint64_t kept, uint32_t R, bool sh);
 // m2s_merge.cpp
 // What m2s_merge does behind its argument checks (level 0..10, max_group 2..64, no NaN), m2s_lod_build once per step; the counts are
 // left in last_merge_counts.  Dry: only the counts; IfAny: as Dry where no segment has two members, as Apply otherwise.

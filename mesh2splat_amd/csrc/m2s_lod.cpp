@@ -1,8 +1,8 @@
 // m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and their
 // _frustum forms): host side of m2s_lod.hip, m2s_lodbudget.hip and m2s_lodfrustum.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
 // copied into a node pool and linked by their maps; the
-// cut's flags and offsets live where m2s_prune leaves its own, and the compaction and what follows it are m2s_prune's (m2s_contrib.cpp:
-// prune_compact_enqueue, prune_adopt).
+// cut's flags and offsets live where m2s_prune leaves its own, and the compaction is m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue);
+// what a cut does to the context: m2s_recstate.h, Rewrite::LodCut.
 #include "m2s_ctx.h"
 
 #include <algorithm>
@@ -16,9 +16,7 @@ namespace {
 
 constexpr uint64_t kLodMaxNodes = 0xFFFFFFFFull;   // fewer than this: M2S_LOD_NO_PARENT is no node
 
-bool lod_ids_valid(const m2s_ctx* c) {
-    return c->lod_ids_of && c->last_records && !c->records_stale && c->lod_ids_of == c->last_records && c->lod_ids_epoch == c->records_epoch;
-}
+bool lod_ids_valid(const m2s_ctx* c) { return c->lod_ids_tag.holds(*c); }
 
 // Room for `want` nodes in the three planes of the tree, the first `keep` nodes kept where they have to move.
 m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
@@ -98,7 +96,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         if (!dry) {
             M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)N), 16) + 2 * sizeof(unsigned long long), 1));
             M2S_TRY(c->d_lod_ids.reserve(c->err, N, sizeof(uint32_t)));
-            c->lod_ids_of = nullptr;
+            c->lod_ids_tag.clear();
         }
         uint32_t* const flags = c->d_prune_u32;
         uint32_t* const offsets = flags + c->d_prune_u32.cap();
@@ -138,7 +136,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         }
     } else {
         if (!dry) {
-            c->lod_ids_of = nullptr;
+            c->lod_ids_tag.clear();
             M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
@@ -146,11 +144,8 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         if (prof && fr) c->last_lod_frustum_ms = 0.0f;
     }
     if (!dry) {
-        prune_adopt(c, selected, c->lod_R, false);
-        c->sh_valid = false;                    // (a plane of other records: dropped, as by m2s_merge)
-        c->lod_ids_of = c->last_records;
-        c->lod_ids_n = selected;
-        c->lod_ids_epoch = c->records_epoch;
+        c->rewritten(c->lane[0].records, selected, c->lod_R, Rewrite::LodCut);   // (a baked plane is one of other records: dropped)
+        c->lod_ids_tag.set(*c, selected);
     }
     c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
     c->last_lod_select_counts[3] = h[kLodRefineWord];
@@ -251,9 +246,7 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     if (p->max_group < 2 || p->max_group > 64) return fail(c, M2S_ERR_INVALID, "max_group outside 2..64");
     if (std::isnan(p->min_axis_dot)) return fail(c, M2S_ERR_INVALID, "min_axis_dot is NaN");
     if (p->flags & ~(uint32_t)M2S_MERGE_UNSIGNED_AXIS) return fail(c, M2S_ERR_INVALID, "flags other than M2S_MERGE_UNSIGNED_AXIS");
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
+    M2S_TRY(have_records(c));
     const uint64_t n0 = c->last_stored;
     if (n0 >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
     const uint32_t R = c->last_R;
@@ -401,18 +394,18 @@ m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* c, float out_ms[3]) {
     return M2S_OK;
 }
 
-const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_n ? c->d_lod_ids.get() : nullptr; }
+const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_tag.n ? c->d_lod_ids.get() : nullptr; }
 
 m2s_status m2s_download_lod_nodes(m2s_ctx* c, uint32_t* dst, uint64_t capacity, uint64_t* out_n) {
     if (out_n) *out_n = 0;
     if (!c) return M2S_ERR_INVALID;
     if (!lod_ids_valid(c)) return fail(c, M2S_ERR_STATE, "no node indices of the current records (m2s_lod_select; the records changed since)");
-    if (out_n) *out_n = c->lod_ids_n;
+    if (out_n) *out_n = c->lod_ids_tag.n;
     if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
-    if (capacity < c->lod_ids_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
-    if (!c->lod_ids_n) return M2S_OK;
+    if (capacity < c->lod_ids_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!c->lod_ids_tag.n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_lod_ids, c->lod_ids_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_lod_ids, c->lod_ids_tag.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

@@ -1,6 +1,6 @@
 // m2s_merge.cpp — the merge pass (m2s_merge): host side of m2s_merge.hip.  Order comes from the compact export's helper
 // (compact_keys_and_sort, m2s_compact.hip) in the compact export's own buffers; the parents go into the pool the way m2s_prune's survivors
-// do (through the staging buffer where the sources live there), and what the call does to the context is prune_adopt (m2s_contrib.cpp).
+// do (through the staging buffer where the sources live there); what the call does to the context: m2s_recstate.h, Rewrite::Merge.
 // merge_run is the pass behind m2s_merge's argument checks: the steps of m2s_lod_build (m2s_lod.cpp) are calls of it.
 #include "m2s_ctx.h"
 
@@ -13,9 +13,7 @@ using namespace m2s_host;
 
 namespace {
 
-bool merge_map_valid(const m2s_ctx* c) {
-    return c->merge_map_of && c->last_records && !c->records_stale && c->merge_map_of == c->last_records && c->merge_map_epoch == c->records_epoch;
-}
+bool merge_map_valid(const m2s_ctx* c) { return c->merge_map_tag.holds(*c); }
 
 }  // namespace
 
@@ -24,11 +22,8 @@ namespace m2s_host {
 // The body of m2s_merge behind its argument checks (m2s_lod_build runs it once per step): level 0..10, max_group 2..64, no NaN.
 // unsigned_axis (M2S_MERGE_UNSIGNED_AXIS) goes to both launches: the heads (pin 2u) and the reduction (pin 5u).
 m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_axis_dot, MergeMode mode, bool unsigned_axis) {
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-    const uint64_t n64 = c->last_stored;
-    if (n64 > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    uint64_t n64 = 0;
+    M2S_TRY(need_records(c, &n64));
     const uint32_t n = (uint32_t)n64;
     bool dry = mode == MergeMode::Dry || (mode == MergeMode::IfAny && n == 0);
     const uint32_t R = c->last_R;
@@ -75,7 +70,7 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
             // The parents go into the pool.  Members that live there already cannot be reduced onto themselves by independent lanes: the
             // parents go through the staging buffer and are copied back, stream-ordered (as m2s_prune's survivors).
             const bool in_pool = c->last_records == c->lane[0].records;
-            c->merge_map_of = nullptr;
+            c->merge_map_tag.clear();
             M2S_TRY(c->d_merge_map.reserve(c->err, n, sizeof(uint32_t)));
             if (in_pool) M2S_TRY(c->d_prune_stage.reserve(c->err, segments * sizeof(m2s_gaussian), 1));
             const void* src = c->last_records;
@@ -90,15 +85,11 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
     } else if (!dry) {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->merge_map_of = nullptr;
+        c->merge_map_tag.clear();
     }
     if (!dry) {
-        prune_adopt(c, segments, R, false);
-        c->refit_active = false;
-        c->sh_valid = false;                    // (a plane of the members is not a plane of their parents: not merged, as m2s_refit_apply)
-        c->merge_map_of = c->last_records;
-        c->merge_map_n = n;
-        c->merge_map_epoch = c->records_epoch;
+        c->rewritten(c->lane[0].records, segments, R, Rewrite::Merge);   // (a plane of the members is not a plane of their parents: dropped)
+        c->merge_map_tag.set(*c, n);
     }
     c->last_merge_counts[0] = n; c->last_merge_counts[1] = segments; c->last_merge_counts[2] = merged; c->last_merge_counts[3] = invalid;
     std::memcpy(c->last_merge_stage_ms, ms, sizeof(ms));
@@ -135,18 +126,18 @@ m2s_status m2s_last_merge_stage_ms(const m2s_ctx* c, float out_ms[3]) {
     return M2S_OK;
 }
 
-const void* m2s_device_merge_map(const m2s_ctx* c) { return c && merge_map_valid(c) && c->merge_map_n ? c->d_merge_map.get() : nullptr; }
+const void* m2s_device_merge_map(const m2s_ctx* c) { return c && merge_map_valid(c) && c->merge_map_tag.n ? c->d_merge_map.get() : nullptr; }
 
 m2s_status m2s_download_merge_map(m2s_ctx* c, uint32_t* dst, uint64_t capacity, uint64_t* out_n) {
     if (out_n) *out_n = 0;
     if (!c) return M2S_ERR_INVALID;
     if (!merge_map_valid(c)) return fail(c, M2S_ERR_STATE, "no merge map of the current records (m2s_merge; the records changed since)");
-    if (out_n) *out_n = c->merge_map_n;
+    if (out_n) *out_n = c->merge_map_tag.n;
     if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
-    if (capacity < c->merge_map_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there were records");
-    if (!c->merge_map_n) return M2S_OK;
+    if (capacity < c->merge_map_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there were records");
+    if (!c->merge_map_tag.n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_merge_map, c->merge_map_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->d_merge_map, c->merge_map_tag.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

@@ -410,19 +410,15 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     const SceneDev& sc = c->scene;
     const uint64_t cap = resolve_cap(c, R);
     const bool prof = c->profiling;
-    c->last_R = R;
-    c->conv_R = 0;
-    c->records_stale = false;
+    c->conversion_started(R);
     memset(c->last_ms, 0, sizeof c->last_ms);
 
     if (sc.n_tri == 0) {
-        c->last_total = c->last_stored = 0;
         if (!d_user && !c->lane[0].records) {   // (an empty shard is a conversion like any other: its consumers see zero records, not "no conversion")
             const m2s_status s = ensure_records(c, 1);
             if (s != M2S_OK) return s;
         }
-        c->last_records = d_user ? d_user : c->lane[0].records.get();
-        ++c->records_epoch;
+        c->conversion_finished(d_user ? d_user : c->lane[0].records.get(), 0, 0);
         if (out_total) *out_total = 0;
         return M2S_OK;
     }
@@ -484,7 +480,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
             float4* plane = nullptr;
             if (ri.form == M2S_PIPELINE_SPARSE && c->keep_positions && st == c->stream) {
                 (void)c->d_pos_plane.try_reserve(limit, 16);
-                c->pos_plane_n = 0;
+                c->pos_plane_tag.clear();
                 plane = c->d_pos_plane;
             }
             wrote_plane = plane != nullptr;
@@ -562,14 +558,9 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     const uint64_t total = c->h_total[0];
     if (total > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 fragments: offsets are 32-bit");
     c->frag_per_R2 = (double)total / ((double)R * (double)R);
-    c->last_total = total;
-    c->last_stored = std::min(total, limit);
-    c->last_records = d_out;
-    ++c->records_epoch;
+    c->conversion_finished(d_out, total, std::min(total, limit));
     // the plane is these records' if the sparse kernel wrote every one of them (no deferred triangle went to k_emit_big, no fallback ran)
-    if (wrote_plane && c->last_pipeline == M2S_PIPELINE_SPARSE && !c->h_total[1] && c->d_pos_plane) {
-        c->pos_plane_of = d_out; c->pos_plane_n = c->last_stored; c->pos_plane_epoch = c->records_epoch;
-    }
+    if (wrote_plane && c->last_pipeline == M2S_PIPELINE_SPARSE && !c->h_total[1] && c->d_pos_plane) c->pos_plane_tag.set(*c, c->last_stored);
     if (!d_user && c->lane[0].rec_R != R) { c->lane[0].rec_R = R; ++c->lane[0].rec_gen; }
     if (out_total) *out_total = total;
     return M2S_OK;

@@ -111,15 +111,7 @@ m2s_status m2s_upload_records(m2s_ctx* c, const m2s_gaussian* records, uint64_t 
     const uint64_t want = std::max<uint64_t>(n, 1);     // an empty upload still yields a valid (empty) record buffer
     M2S_TRY(c->d_loaded.reserve(c->err, want, sizeof(m2s_gaussian)));
     if (n) HIPCHK(c, hipMemcpy(c->d_loaded, records, n * sizeof(m2s_gaussian), hipMemcpyHostToDevice));
-    c->last_records = c->d_loaded;
-    ++c->records_epoch;
-    c->last_total = c->last_stored = n;
-    c->records_stale = false;
-    c->last_R = 0;      // uploaded records carry no resolutionTarget: m2s_export_ply (scale multiplier = std / R) refuses them
-    c->conv_R = 0;
-    c->sorted_n = 0;
-    c->pp_visible = 0;
-    c->sq_n = 0;
+    c->records_uploaded(c->d_loaded, n);      // (they carry no resolutionTarget: m2s_export_ply, scale multiplier = std / R, refuses them)
     return M2S_OK;
 }
 
@@ -128,13 +120,7 @@ m2s_status m2s_upload_records(m2s_ctx* c, const m2s_gaussian* records, uint64_t 
 m2s_status m2s_set_records(m2s_ctx* c, const void* d_records, uint64_t n, uint32_t R) {
     if (!c || (!d_records && n)) return M2S_ERR_INVALID;
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    c->last_records = d_records;
-    ++c->records_epoch;
-    c->last_total = c->last_stored = n;
-    c->last_R = R;
-    c->conv_R = 0;
-    c->records_stale = false;
-    c->sorted_n = 0; c->pp_visible = 0; c->sq_n = 0;
+    c->records_adopted(d_records, n, R);
     return M2S_OK;
 }
 

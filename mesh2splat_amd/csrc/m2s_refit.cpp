@@ -1,6 +1,5 @@
 // m2s_refit.cpp — the colour refit (m2s_refit_begin / _accumulate / _apply): host side of m2s_refit.hip.  The binning stages in front of
-// the refit blend are the splat pass's own (splat_bin, m2s_splat.cpp); what the apply does to the context is what m2s_prune does
-// (m2s_contrib.cpp: prune_adopt).
+// the refit blend are the splat pass's own (splat_bin, m2s_splat.cpp); what the apply does to the context: m2s_recstate.h, Rewrite::RefitApply.
 #include "m2s_ctx.h"
 
 #include <algorithm>
@@ -12,10 +11,7 @@ using namespace m2s_host;
 
 namespace {
 
-bool refit_valid(const m2s_ctx* c) {
-    return c->refit_active && c->last_records && !c->records_stale && c->refit_of == c->last_records && c->refit_n == c->last_stored &&
-           c->refit_epoch == c->records_epoch;
-}
+bool refit_valid(const m2s_ctx* c) { return c->refit_tag.holds(*c, c->last_stored); }
 long long* refit_num(const m2s_ctx* c) { return reinterpret_cast<long long*>(c->d_refit.get()); }
 unsigned long long* refit_den(const m2s_ctx* c) { return c->d_refit + 3 * c->d_refit.cap(); }
 const char* const kNoRefitMsg = "no accumulators of the current records (m2s_refit_begin)";
@@ -26,20 +22,14 @@ extern "C" {
 
 m2s_status m2s_refit_begin(m2s_ctx* c) {
     if (!c) return M2S_ERR_INVALID;
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->last_records) return fail(c, M2S_ERR_STATE, "no conversion has run and no records were uploaded");
-    if (c->records_stale) return fail(c, M2S_ERR_STATE, kStaleMsg);
-    const uint64_t n = c->last_stored;
-    if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
+    uint64_t n = 0;
+    M2S_TRY(need_records(c, &n));
     HIPCHK(c, hipSetDevice(c->device));
-    c->refit_active = false;
+    c->refit_tag.clear();
     M2S_TRY(c->d_refit.reserve(c->err, std::max<uint64_t>(n, 1), 4 * sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(c->d_refit, 0, c->d_refit.cap() * 4 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->refit_of = c->last_records;
-    c->refit_n = n;
-    c->refit_epoch = c->records_epoch;
-    c->refit_active = true;
+    c->refit_tag.set(*c, n);
     return M2S_OK;
 }
 
@@ -48,10 +38,10 @@ m2s_status m2s_refit_accumulate(m2s_ctx* c, const m2s_refit_params* p, const voi
     const int W = p->resolution[0], H = p->resolution[1];
     M2S_TRY(check_resolution(c, W, H));
     if (p->min_cover < 1 || p->min_cover > 255 || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "min_cover outside 1..255 or reserved != 0");
-    if (!c->refit_active) return fail(c, M2S_ERR_INVALID, "no m2s_refit_begin");
+    if (!c->refit_tag.is_set()) return fail(c, M2S_ERR_INVALID, "no m2s_refit_begin");
     if (!refit_valid(c)) return fail(c, M2S_ERR_INVALID, "the records changed since m2s_refit_begin");
     if (!c->sq_n) return fail(c, M2S_ERR_INVALID, "no sorted quads (run m2s_prepass_sorted)");
-    if (!c->sq_src || c->sq_src_epoch != c->records_epoch)
+    if (!c->sq_src || !c->sq_src_tag.holds(*c))
         return fail(c, M2S_ERR_INVALID, "the sorted quads carry no sources (they come from m2s_prepass_sorted or m2s_upload_quad_sources)");
     if (!d_target) {
         if (c->mr_w != W || c->mr_h != H) return fail(c, M2S_ERR_STATE, "no mesh G-buffer of this resolution exists (run m2s_mesh_render)");
@@ -84,18 +74,19 @@ const void* m2s_device_refit(const m2s_ctx* c, uint32_t which) {
 m2s_status m2s_download_refit(m2s_ctx* c, int64_t* dst_num, uint64_t* dst_den, uint64_t capacity) {
     if (!c) return M2S_ERR_INVALID;
     if (!refit_valid(c)) return fail(c, M2S_ERR_STATE, kNoRefitMsg);
-    if (capacity < c->refit_n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
-    if (!c->refit_n) return M2S_OK;
+    const uint64_t n = c->refit_tag.n;
+    if (capacity < n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (dst_num) HIPCHK(c, hipMemcpy(dst_num, refit_num(c), c->refit_n * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (dst_den) HIPCHK(c, hipMemcpy(dst_den, refit_den(c), c->refit_n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (dst_num) HIPCHK(c, hipMemcpy(dst_num, refit_num(c), n * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (dst_den) HIPCHK(c, hipMemcpy(dst_den, refit_den(c), n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
 m2s_status m2s_upload_refit(m2s_ctx* c, const int64_t* host_num, const uint64_t* host_den, uint64_t n) {
     if (!c) return M2S_ERR_INVALID;
     if (!refit_valid(c)) return fail(c, M2S_ERR_STATE, kNoRefitMsg);
-    if (n != c->refit_n) return fail(c, M2S_ERR_INVALID, "the number of entries is not the number of records");
+    if (n != c->refit_tag.n) return fail(c, M2S_ERR_INVALID, "the number of entries is not the number of records");
     if (!n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (host_num) HIPCHK(c, hipMemcpy(refit_num(c), host_num, n * 3 * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -135,9 +126,7 @@ m2s_status m2s_refit_apply(m2s_ctx* c, const m2s_refit_apply_params* p, uint64_t
     if (c->profiling) HIPCHK(c, hipEventRecord(c->refit_ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_refit_apply_ms, c->refit_ev[0], c->refit_ev[1]));
-    prune_adopt(c, n, R, false);
-    c->refit_active = false;
-    c->sh_valid = false;                    // (a plane of these records was baked from the old albedo)
+    c->rewritten(c->lane[0].records, n, R, Rewrite::RefitApply);   // (a plane of these records was baked from the old albedo: dropped)
     if (out_counts) { out_counts[0] = n; out_counts[1] = h[0]; out_counts[2] = h[1]; out_counts[3] = h[2]; }
     return M2S_OK;
 }

@@ -24,7 +24,7 @@ m2s_status reserve_sort(m2s_ctx* c, uint64_t n, size_t temp_bytes, bool with_pla
     M2S_TRY(c->d_sort_u32.reserve(c->err, n, 4 * sizeof(uint32_t)));
     M2S_TRY(c->d_sort_temp.reserve(c->err, temp_bytes, 1));
     if (with_plane && c->d_pos_plane.cap() < n) {
-        c->pos_plane_n = 0;
+        c->pos_plane_tag.clear();
         (void)c->d_pos_plane.try_reserve(n, 16);
     }
     return M2S_OK;
@@ -48,13 +48,13 @@ m2s_status m2s_sort_by_depth(m2s_ctx* c, const float world_to_view[16], uint64_t
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
     M2S_TRY(c->d_sorted.reserve(c->err, n, sizeof(m2s_gaussian)));
     M2S_TRY(reserve_sort(c, n, sort_temp_bytes((uint32_t)n), true));
-    const bool plane_valid = c->d_pos_plane && c->pos_plane_of == c->last_records && c->pos_plane_n == n && c->pos_plane_epoch == c->records_epoch;
+    const bool plane_valid = positions_valid(c, n);
     uint32_t* u = c->d_sort_u32;     // keys_in | (unused) | keys_out | vals_out
     HIPCHK(c, sort_by_depth((const float4*)c->last_records, (uint32_t)n, world_to_view, u, u + 2 * n, u + 3 * n, c->d_sort_temp,
                             c->d_sort_temp.cap(), c->d_sorted, c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream,
                             &c->sorted_key_offset, reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM])));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_pos_plane) { c->pos_plane_of = c->last_records; c->pos_plane_n = n; c->pos_plane_epoch = c->records_epoch; }
+    if (c->d_pos_plane) c->pos_plane_tag.set(*c, n);
     if (c->profiling) {
         for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventElapsedTime(&c->last_sort_stage_ms[k], c->ev[k], c->ev[k + 1]));
         HIPCHK(c, hipEventElapsedTime(&c->last_sort_ms, c->ev[0], c->ev[3]));
@@ -153,13 +153,13 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     bool dense = false;
     uint32_t n_run = (uint32_t)n;
     if (sorted) {
-        const bool plane_valid = c->d_pos_plane && c->pos_plane_of == c->last_records && c->pos_plane_n == n && c->pos_plane_epoch == c->records_epoch;
+        const bool plane_valid = positions_valid(c, n);
         uint32_t* u = c->d_sort_u32;     // keys_in | (unused) | keys_out | vals_out = the permutation
         uint32_t* pinned4 = reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM]);
         bool cull = k.depth_test == 0u, clash = false;
         HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, cull, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
                                            c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
-        if (c->d_pos_plane) { c->pos_plane_of = c->last_records; c->pos_plane_n = n; c->pos_plane_epoch = c->records_epoch; }
+        if (c->d_pos_plane) c->pos_plane_tag.set(*c, n);
         if (cull && clash) {   // a survivor whose depth bits ARE the marker of the culled ones (a NaN with that payload): sort everything, compact in the prepass
             cull = false;
             HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, false, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
@@ -192,7 +192,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     if (sorted) {
         c->sq_n = res[0];
         c->sq_src = dense ? perm : c->d_sq_src.get();
-        c->sq_src_epoch = c->records_epoch;
+        c->sq_src_tag.set(*c, n);
     } else c->pp_visible = res[0];
     if (out_visible) *out_visible = res[0];
     return M2S_OK;
@@ -246,7 +246,7 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
 
 const void* m2s_device_sorted_quads(const m2s_ctx* c) { return c && c->sq_n ? c->d_sorted_quads.get() : nullptr; }
 const void* m2s_device_sorted_sources(const m2s_ctx* c) {
-    return c && c->sq_n && c->sq_src_epoch == c->records_epoch ? c->sq_src : nullptr;
+    return c && c->sq_n && c->sq_src_tag.holds(*c) ? c->sq_src : nullptr;
 }
 
 m2s_status m2s_download_sorted_sources(m2s_ctx* c, uint32_t* dst, uint64_t capacity) {

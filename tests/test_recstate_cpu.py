@@ -1,0 +1,34 @@
+"""The record state of mesh2splat_amd/csrc/m2s_recstate.h (RecordsTag, RecordState and its transitions) under AddressSanitizer + UBSan:
+tests/recstate/recstate_check.cpp is built with the HOST compiler — the header includes nothing but <cstdint> — linked with no HIP
+runtime, and run as a child process of its own.  What it asserts is listed in that file."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def test_recstate_under_sanitizers(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    # the sanitizers' runtime linked into the program where the compiler has it as an archive (the program then runs the same whatever
+    # else the process loads), else its shared form
+    for link in (["-static-libasan", "-static-libubsan"], []):
+        r = subprocess.run([cxx, *SAN, *link, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+        if r.returncode == 0:
+            break
+    else:
+        pytest.skip(f"{cxx} lacks the sanitizer runtime: {(r.stderr.strip().splitlines() or ['link failed'])[-1]}")
+    exe = tmp_path / "recstate_check"
+    # (no include path at all: a HIP header reached from m2s_recstate.h would fail the build)
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *SAN, *link, os.path.join(ROOT, "tests", "recstate", "recstate_check.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "recstate_check ok" in r.stdout, r.stdout + r.stderr
