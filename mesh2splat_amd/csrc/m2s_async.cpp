@@ -80,7 +80,7 @@ m2s_status m2s_convert_submit(m2s_ctx* c, uint32_t R, void* d_records, uint64_t 
     res[0] = 0; res[1] = 0;
     sl.prof = c->profiling;
     if (mp) {
-        M2S_TRY(enqueue_multipass(c, L, R, (float4*)d_out, limit, false, res, st));
+        M2S_TRY(enqueue_multipass(c, L, R, (float4*)d_out, limit, StageMarks(), res, st));
     } else {
         uint32_t epoch;
         HIPCHK(c, next_epoch(c, &epoch));

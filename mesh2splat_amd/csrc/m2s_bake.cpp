@@ -112,7 +112,7 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     if (m2s_status s = pick_records(c, d_records, n)) return s;
     if (bp->use_shadows && !c->shadow_S) return fail(c, M2S_ERR_STATE, "no shadow cube exists (run m2s_shadow or m2s_upload_shadow_cubemap)");
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->bake_ev.ensure(c->err));
+    M2S_TRY(c->bake_clock.begin(c->err, c->profiling));
     c->sh_tag.clear();
     c->bake_has_counts = false;
     M2S_TRY(c->d_sh.reserve(c->err, n, 48 * sizeof(float)));
@@ -136,12 +136,12 @@ m2s_status m2s_bake_light(m2s_ctx* c, const m2s_bake_params* bp, const m2s_light
     k.n_coef = (bp->degree + 1) * (bp->degree + 1);
     k.use_shadows = bp->use_shadows ? 1u : 0u;
     k.viewer_metallic = bp->viewer_metallic ? 1u : 0u;
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->bake_ev[0], c->stream));
+    HIPCHK(c, c->bake_clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, launch_bake_sh(k, (const float4*)d_records, (uint32_t)n, c->d_bake_table, k.use_shadows ? c->d_shadow_cube.get() : nullptr, c->d_sh,
                              counts ? c->d_bake_counts.get() : nullptr, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->bake_ev[1], c->stream));
+    HIPCHK(c, c->bake_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_bake_ms, c->bake_ev[0], c->bake_ev[1]));
+    if (c->bake_clock.on()) HIPCHK(c, c->bake_clock.span(SpanMark::Begin, SpanMark::End, &c->last_bake_ms));
     if (d_records == c->last_records) c->sh_tag.set(*c, n);
     else c->sh_tag.set_foreign(d_records, n);
     c->bake_has_counts = counts;

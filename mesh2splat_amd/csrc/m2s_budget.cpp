@@ -22,11 +22,11 @@ m2s_status m2s_prune_budget(m2s_ctx* c, const m2s_budget_params* p, uint64_t* ou
     const uint64_t n = c->last_stored;
     if (n > 0xFFFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^32-1 records");
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->budget_ev.ensure(c->err));
+    ClockOf<BudgetMark>& clock = c->budget_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     const uint32_t R = c->last_R;
     const uint32_t budget = (uint32_t)std::min<uint64_t>(p->max_records, 0xFFFFFFFFull);
     const bool sh = prune_sh_plane(c, n);
-    const bool prof = c->profiling;
     uint32_t h[8] = {};
     uint64_t kept = 0, candidates = 0;
     if (n) {
@@ -34,32 +34,29 @@ m2s_status m2s_prune_budget(m2s_ctx* c, const m2s_budget_params* p, uint64_t* ou
         M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)n), 16) + 2 * sizeof(unsigned long long), 1));
         M2S_TRY(c->d_budget_keys.reserve(c->err, n, sizeof(uint32_t)));
         M2S_TRY(c->d_budget_state.reserve(c->err, kBudgetStateWords, sizeof(uint32_t)));
-        if (prof) HIPCHK(c, hipEventRecord(c->budget_ev[0], c->stream));   // (behind the allocations: stage [0] is keys + rounds)
+        HIPCHK(c, clock.mark(BudgetMark::Start, c->stream));   // (behind the allocations: stage [0] is keys + rounds)
         uint32_t* flags = c->d_prune_u32;
         uint32_t* offsets = flags + c->d_prune_u32.cap();
         const uint32_t* wmax = views ? c->d_contrib.get() : nullptr;
         const uint32_t* npix = views ? c->d_contrib + c->d_contrib.cap() : nullptr;
         HIPCHK(c, budget_select((const float4*)c->last_records, wmax, npix, (uint32_t)n, p->importance, p->min_weight, p->min_pixels, budget,
                                 c->d_budget_keys, c->d_budget_state, flags, offsets, c->d_prune_temp,
-                                c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), prof ? c->budget_ev + 1 : nullptr, c->stream));
+                                c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), clock.marks(BudgetMark::Selected), c->stream));
         HIPCHK(c, hipMemcpyAsync(h, c->d_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t k = 0; k < kBudgetShards; ++k) candidates += h[kBudgetCandidates + k];
         kept = h[kBudgetActive] ? budget : candidates;
-        if (prof) HIPCHK(c, hipEventRecord(c->budget_ev[3], c->stream));   // (the round trip above is in no stage)
+        HIPCHK(c, clock.mark(BudgetMark::Compact, c->stream));   // (the round trip above is in no stage)
         M2S_TRY(prune_compact_enqueue(c, n, kept, flags, offsets, sh));
     } else {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
     }
-    if (prof && n) HIPCHK(c, hipEventRecord(c->budget_ev[4], c->stream));
+    HIPCHK(c, clock.mark(BudgetMark::Compacted, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (prof) {
-        if (n) {
-            for (int k = 0; k < 3; ++k)
-                HIPCHK(c, hipEventElapsedTime(&c->last_budget_stage_ms[k], c->budget_ev[k == 2 ? 3 : k], c->budget_ev[k == 2 ? 4 : k + 1]));
-        } else {
-            c->last_budget_stage_ms[0] = c->last_budget_stage_ms[1] = c->last_budget_stage_ms[2] = 0.0f;
-        }
+    if (clock.on()) {   // (no records: no marks, three zeros)
+        HIPCHK(c, clock.span(BudgetMark::Start, BudgetMark::Selected, &c->last_budget_stage_ms[0]));
+        HIPCHK(c, clock.span(BudgetMark::Selected, BudgetMark::Scanned, &c->last_budget_stage_ms[1]));
+        HIPCHK(c, clock.span(BudgetMark::Compact, BudgetMark::Compacted, &c->last_budget_stage_ms[2]));
     }
     c->rewritten(c->lane[0].records, kept, R, sh ? Rewrite::PruneWithSh : Rewrite::Prune);
     const bool active = h[kBudgetActive] != 0;
@@ -73,16 +70,8 @@ m2s_status m2s_prune_budget(m2s_ctx* c, const m2s_budget_params* p, uint64_t* ou
     return M2S_OK;
 }
 
-m2s_status m2s_last_budget_counts(const m2s_ctx* c, uint64_t out[6]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 6; ++k) out[k] = c->last_budget_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_budget_counts(const m2s_ctx* c, uint64_t out[6]) { return get_array(c, &m2s_ctx::last_budget_counts, out); }
 
-m2s_status m2s_last_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_budget_stage_ms, sizeof(c->last_budget_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_budget_stage_ms, out_ms); }
 
 }  // extern "C"

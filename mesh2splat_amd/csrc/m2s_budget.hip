@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(256) k_budget_flags(const uint32_t* __restrict
 
 hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t* npix, uint32_t n, uint32_t importance, float min_weight,
                          uint32_t min_pixels, uint32_t budget, uint32_t* keys, uint32_t* state, uint32_t* flags, uint32_t* offsets, void* temp,
-                         size_t temp_bytes, hipEvent_t* ev, hipStream_t st) {
+                         size_t temp_bytes, const m2s_host::StageMarks& marks, hipStream_t st) {
     const uint32_t blocks = (uint32_t)(((unsigned long long)n + 255ull) / 256ull);
     const dim3 grid(blocks), block(256);
     hipError_t e = hipMemsetAsync(state, 0, kBudgetStateWords * sizeof(uint32_t), st);
@@ -195,7 +195,7 @@ hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t
         hipLaunchKernelGGL(k_budget_pick, dim3(1), block, 0, st, pass, budget, state);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return e;
+    if ((e = marks.mark(0, st)) != hipSuccess) return e;
     // the ties' ranks pass through the two words per record the compaction is about to use: tie in `flags`, rank in `offsets`
     hipLaunchKernelGGL(k_budget_ties, grid, block, 0, st, keys, n, state, flags);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -203,7 +203,7 @@ hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t
     hipLaunchKernelGGL(k_budget_flags, grid, block, 0, st, keys, offsets, n, state, flags);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = rocprim::exclusive_scan(temp, temp_bytes, (const uint32_t*)flags, offsets, 0u, (size_t)n, rocprim::plus<uint32_t>(), st)) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
+    if ((e = marks.mark(1, st)) != hipSuccess) return e;
     return hipSuccess;
 }
 

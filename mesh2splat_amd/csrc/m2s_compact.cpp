@@ -48,11 +48,11 @@ m2s_status m2s_export_ply_compact(m2s_ctx* c, const char* path, float gaussian_s
     // SceneManager.cpp:668, as m2s_export_ply; records without a resolutionTarget (uploaded ones) are taken as converted at R = 1
     const float sm = c->last_R ? gaussian_std / static_cast<float>(c->last_R) : gaussian_std;
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->compact_ev.ensure(c->err));
+    ClockOf<CompactMark>& clock = c->compact_clock;
+    M2S_TRY(clock.begin(c->err, true));            // (measured whatever m2s_set_profiling says)
     M2S_TRY(c->h_compact.ensure(c->err, 2 * sizeof(uint32_t)));
     for (int k = 0; k < 2; ++k) M2S_TRY(c->h_export[k].ensure(c->err, m2s_ply::kChunkRows * sizeof(m2s_gaussian)));
     for (float& v : c->last_compact_stage_ms) v = 0.0f;
-    hipEvent_t* ev = c->compact_ev;
     uint32_t N = 0, skipped = 0;
     const uint32_t* perm = nullptr;
     if (n) {
@@ -66,7 +66,7 @@ m2s_status m2s_export_ply_compact(m2s_ctx* c, const char* path, float gaussian_s
         uint32_t* const head = c->d_compact_waves.get() + (size_t)n_waves * 8;
         const float4* plane = m2s_positions_ready(c) ? c->d_pos_plane.get() : nullptr;
         HIPCHK(c, compact_keys_and_sort((const float4*)c->last_records, plane, n, c->d_compact_waves, head, u, u + cap, u + 2 * cap, u + 3 * cap, c->d_compact_temp,
-                                        temp_bytes, ev, c->stream));
+                                        temp_bytes, clock.marks(), c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_compact, head + 6, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         N = static_cast<uint32_t*>(c->h_compact)[0];
@@ -81,10 +81,10 @@ m2s_status m2s_export_ply_compact(m2s_ctx* c, const char* path, float gaussian_s
     if (N) {
         M2S_TRY(c->d_compact_out.reserve(c->err, sh_at + sh_room, 1));
         uint8_t* const o = c->d_compact_out.get();
-        HIPCHK(c, hipEventRecord(ev[3], c->stream));
+        HIPCHK(c, clock.mark(CompactMark::Pack, c->stream));
         HIPCHK(c, compact_pack((const float4*)c->last_records, use_baked_sh ? c->d_sh.get() : nullptr, perm, N, sm, K, reinterpret_cast<float*>(o), o + rows_at,
                                K ? o + sh_at : nullptr, c->stream));
-        HIPCHK(c, hipEventRecord(ev[4], c->stream));
+        HIPCHK(c, clock.mark(CompactMark::Packed, c->stream));
     }
     const auto t0 = std::chrono::steady_clock::now();
     FILE* f = std::fopen(path, "wb");
@@ -102,19 +102,14 @@ m2s_status m2s_export_ply_compact(m2s_ctx* c, const char* path, float gaussian_s
     if (s != M2S_OK) { (void)hipStreamSynchronize(c->stream); return s; }
     if (!ok) return fail(c, M2S_ERR_IO, std::string("could not write ") + path);
     c->last_compact_stage_ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n) {
-        HIPCHK(c, hipEventElapsedTime(&c->last_compact_stage_ms[0], ev[0], ev[1]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_compact_stage_ms[1], ev[1], ev[2]));
-        if (N) HIPCHK(c, hipEventElapsedTime(&c->last_compact_stage_ms[2], ev[3], ev[4]));
-    }
+    // (no records: no marks, [0..2] are 0; none of them valid: nothing was packed, [2] is)
+    HIPCHK(c, clock.span(CompactMark::Start, CompactMark::Keyed, &c->last_compact_stage_ms[0]));
+    HIPCHK(c, clock.span(CompactMark::Keyed, CompactMark::Sorted, &c->last_compact_stage_ms[1]));
+    HIPCHK(c, clock.span(CompactMark::Pack, CompactMark::Packed, &c->last_compact_stage_ms[2]));
     if (out_counts) { out_counts[0] = N; out_counts[1] = C; out_counts[2] = skipped; }
     return M2S_OK;
 }
 
-m2s_status m2s_last_compact_stage_ms(const m2s_ctx* c, float out_ms[4]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    for (int k = 0; k < 4; ++k) out_ms[k] = c->last_compact_stage_ms[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_compact_stage_ms(const m2s_ctx* c, float out_ms[4]) { return get_array(c, &m2s_ctx::last_compact_stage_ms, out_ms); }
 
 }  // extern "C"

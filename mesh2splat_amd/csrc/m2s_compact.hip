@@ -193,20 +193,20 @@ size_t compact_sort_temp_bytes(uint32_t n) {
 }
 
 // keys_in / vals_in / keys_out / vals_out: n words each; wave_box: compact_waves(n) * 8 words; head: 8 words.  Afterwards head =
-// { box, N, skipped } and the first N words of vals_out are the permutation.  ev: events around box + keys (0, 1) and the sort (1, 2).
+// { box, N, skipped } and the first N words of vals_out are the permutation.  marks: around box + keys (0, 1) and the sort (1, 2).
 hipError_t compact_keys_and_sort(const float4* rec, const float4* plane, uint32_t n, uint32_t* wave_box, uint32_t* head, uint32_t* keys_in, uint32_t* vals_in,
-                                 uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, hipEvent_t* ev, hipStream_t st) {
+                                 uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, const m2s_host::StageMarks& marks, hipStream_t st) {
     if (!n) return hipErrorInvalidValue;
     const dim3 grid((n + kBlock - 1) / kBlock);
-    (void)hipEventRecord(ev[0], st);
+    (void)marks.mark(0, st);
     hipLaunchKernelGGL(k_compact_box, grid, dim3(kBlock), 0, st, rec, plane, n, keys_in, reinterpret_cast<u32x4*>(wave_box));
     hipLaunchKernelGGL(k_compact_fold, dim3(1), dim3(kBlock), 0, st, reinterpret_cast<const u32x4*>(wave_box), compact_waves(n), n, head);
     hipLaunchKernelGGL(k_compact_keys, grid, dim3(kBlock), 0, st, rec, plane, n, (const uint32_t*)head, keys_in, vals_in);
-    (void)hipEventRecord(ev[1], st);
+    (void)marks.mark(1, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 31, st);
-    (void)hipEventRecord(ev[2], st);
+    (void)marks.mark(2, st);
     return e;
 }
 

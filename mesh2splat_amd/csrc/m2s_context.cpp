@@ -139,7 +139,6 @@ m2s_status m2s_create(int device, m2s_ctx** out_ctx) {
     if (!s) s = c->streams.ensure(c->err, 0);
     if (!s) s = c->lane[0].total.reserve(c->err, 1, sizeof(unsigned long long));
     if (!s) s = c->h_total.ensure(c->err, m2s_ctx::kPinnedWords * sizeof(unsigned long long));
-    if (!s) s = c->ev.ensure(c->err);
     if (!s) s = c->stage_ev.ensure(c->err, hipEventDisableTiming);
     for (auto& sl : c->slot) {
         if (!s) s = sl.done.ensure(c->err, done_flags);
@@ -238,10 +237,6 @@ m2s_status m2s_set_async_lanes(m2s_ctx* c, int lanes) {
     return M2S_OK;
 }
 
-m2s_status m2s_last_kernel_ms(const m2s_ctx* c, float out_ms[M2S_K_N]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    memcpy(out_ms, c->last_ms, sizeof c->last_ms);
-    return M2S_OK;
-}
+m2s_status m2s_last_kernel_ms(const m2s_ctx* c, float out_ms[M2S_K_N]) { return get_array(c, &m2s_ctx::last_ms, out_ms); }
 
 }  // extern "C"

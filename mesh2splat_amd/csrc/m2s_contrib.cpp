@@ -100,10 +100,10 @@ m2s_status m2s_contrib_accumulate(m2s_ctx* c, const m2s_splat_params* p, float c
     if (bins.pairs)
         HIPCHK(c, contrib_blend((const float4*)c->splat_work.rec.get(), bins.vals, bins.ranges, bins.order, W, H, c->sq_src, count_weight, c->d_contrib,
                                 c->d_contrib + c->d_contrib.cap(), c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, c->bin_clock.mark(BinMark::Blended, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) {
-        if (m2s_status s = splat_stage_ms(c, true, c->last_contrib_stage_ms)) return s;
+    if (c->bin_clock.on()) {
+        M2S_TRY(splat_stage_ms(c, c->last_contrib_stage_ms));
         c->last_contrib_ms = (c->last_contrib_stage_ms[0] + c->last_contrib_stage_ms[1]) + c->last_contrib_stage_ms[2];
     }
     return M2S_OK;
@@ -127,11 +127,7 @@ m2s_status m2s_download_contrib(m2s_ctx* c, uint32_t* dst_wmax, uint32_t* dst_np
 
 float m2s_last_contrib_ms(const m2s_ctx* c) { return c ? c->last_contrib_ms : 0.0f; }
 
-m2s_status m2s_last_contrib_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_contrib_stage_ms, sizeof(c->last_contrib_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_contrib_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_contrib_stage_ms, out_ms); }
 
 m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) {
     if (!c || !p) return M2S_ERR_INVALID;
@@ -139,12 +135,12 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!contrib_valid(c)) return fail(c, M2S_ERR_STATE, "no accumulators of the current records (m2s_contrib_begin, m2s_contrib_accumulate)");
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->prune_ev.ensure(c->err));
+    M2S_TRY(c->prune_clock.begin(c->err, c->profiling));
     const uint64_t n = c->last_stored;
     const uint32_t R = c->last_R;
     uint64_t kept = 0, by_w = 0, by_p = 0;
     const bool sh = prune_sh_plane(c, n);
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[0], c->stream));
+    HIPCHK(c, c->prune_clock.mark(SpanMark::Begin, c->stream));
     if (n) {
         // flags | offsets | two 64-bit counters
         M2S_TRY(c->d_prune_u32.reserve(c->err, n, 2 * sizeof(uint32_t)));
@@ -168,20 +164,16 @@ m2s_status m2s_prune(m2s_ctx* c, const m2s_prune_params* p, uint64_t* out_kept) 
     } else {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
     }
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->prune_ev[1], c->stream));
+    HIPCHK(c, c->prune_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_prune_ms, c->prune_ev[0], c->prune_ev[1]));
+    if (c->prune_clock.on()) HIPCHK(c, c->prune_clock.span(SpanMark::Begin, SpanMark::End, &c->last_prune_ms));
     c->rewritten(c->lane[0].records, kept, R, sh ? Rewrite::PruneWithSh : Rewrite::Prune);
     c->last_prune_counts[0] = n; c->last_prune_counts[1] = kept; c->last_prune_counts[2] = by_w; c->last_prune_counts[3] = by_p;
     if (out_kept) *out_kept = kept;
     return M2S_OK;
 }
 
-m2s_status m2s_last_prune_counts(const m2s_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 4; ++k) out[k] = c->last_prune_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_prune_counts(const m2s_ctx* c, uint64_t out[4]) { return get_array(c, &m2s_ctx::last_prune_counts, out); }
 
 float m2s_last_prune_ms(const m2s_ctx* c) { return c ? c->last_prune_ms : 0.0f; }
 

@@ -17,6 +17,7 @@
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
+//   m2s_stageclock.h stage timing: StageClock, one per pass below and the marks of each (the enums of that header), StageMarks for the launchers
 //   m2s_recstate.h   the current records, what hangs on them and the transitions between them: RecordState (a base of m2s_ctx), RecordsTag
 #pragma once
 #include "../../include/m2s.h"
@@ -158,6 +159,7 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<void> d_sort_temp;      // capacity: the bytes last asked for
     float last_sort_ms = 0.0f;
     float last_sort_stage_ms[3] = { 0, 0, 0 };   // keys | radix sort | gather of the last m2s_sort_by_depth (profiling on)
+    m2s_host::ClockOf<m2s_host::SortMark> sort_clock;                // m2s_sort_by_depth and m2s_prepass_sorted: the sort's marks and the prepass's chain
     // the positions of the current records as a compact plane (16 B each), left behind by the first depth sort after the records
     // changed and used for the keys of every later one (m2s_sort.hip); valid while pos_plane_tag holds
     m2s_host::DevBuf<float4> d_pos_plane;
@@ -169,6 +171,7 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     uint32_t pp_epoch = 0;
     m2s_host::DevBuf<float> d_pp_depthtex;
     float last_prepass_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> prepass_clock;   // m2s_prepass's (m2s_prepass_sorted: sort_clock)
     m2s_host::PinnedBuf<m2s_gaussian> h_export[2];      // pinned chunk buffers of m2s_export_ply
     // upload staging: two pinned host chunks (filled by a few host threads while the previous chunk is on the bus) and
     // two device chunks for the AoS -> SoA repack; allocated at the first upload, kept
@@ -181,12 +184,14 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<void> d_loaded;         // m2s_upload_records (a loaded .ply)
     m2s_host::DevBuf<float4> d_sorted_quads; // m2s_sort_prepass (sq_n of them)
     float last_sort_prepass_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> sort_prepass_clock;
     // splat pass (m2s_splat.cpp): the five G-buffer planes of the last call and the pass's grow-only work buffers
     m2s_host::GBufPlanes d_gbuf;
     int32_t gbuf_w = 0, gbuf_h = 0;          // resolution of the planes' contents (0: no splat has run)
     m2s_host::BinWork splat_work;            // per quad a 128-byte record; totals: [0] pairs, [1] skipped quads, [2] fragments blended
     m2s_host::DevBuf<uint32_t> d_splat_tiles;   // ranges (2 words) | lengths | sorted lengths | order, one capacity of tiles each
     float last_splat_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::BinMark> bin_clock;              // splat_bin's, a member like splat_work: m2s_splat, m2s_contrib_accumulate, m2s_refit_accumulate add the blend's mark
     float last_splat_stage_ms[3] = { 0, 0, 0 };     // setup + bin, grouping, blend (profiling on)
     uint64_t last_splat_counts[3] = { 0, 0, 0 };    // pairs, fragments blended, quads skipped
     // sources of the sorted quads (m2s_prepass_sorted): which record each was made from.  Dense path: the first sq_n words of the
@@ -202,20 +207,20 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<float4> d_prune_stage;  // survivors on their way back into the buffer they came from; capacity in bytes
     uint64_t last_prune_counts[4] = { 0, 0, 0, 0 };
     float last_prune_ms = 0.0f;
-    m2s_host::EventSet<2> prune_ev;
+    m2s_host::ClockOf<m2s_host::SpanMark> prune_clock;
     // pruning to a budget (m2s_budget.cpp): one key per record and the select's words (m2s_device.h); flags, offsets, scan area and
     // staging are m2s_prune's
     m2s_host::DevBuf<uint32_t> d_budget_keys;
     m2s_host::DevBuf<uint32_t> d_budget_state;
     uint64_t last_budget_counts[6] = { 0, 0, 0, 0, 0, 0 };
     float last_budget_stage_ms[3] = { 0, 0, 0 };   // keys + select rounds, flags + scans, compaction (profiling on)
-    m2s_host::EventSet<5> budget_ev;               // start, select done, scans done | compaction: start, end
+    m2s_host::ClockOf<m2s_host::BudgetMark> budget_clock;
     // colour refit (m2s_refit.cpp): num (int64, three words per record) | den (uint64), one capacity of records; valid while refit_tag holds
     m2s_host::DevBuf<unsigned long long> d_refit;
     m2s_host::DevBuf<unsigned long long> d_refit_counts;   // m2s_refit_apply: updated, clamped, left for lack of weight
     float last_refit_stage_ms[3] = { 0, 0, 0 };    // setup + bin, grouping, refit blend (profiling on)
     float last_refit_apply_ms = 0.0f;
-    m2s_host::EventSet<2> refit_ev;                // the apply
+    m2s_host::ClockOf<m2s_host::SpanMark> refit_apply_clock;
     // merge pass (m2s_merge.cpp): flag | run_start | packed (64-bit) | sums (64-bit) | seg_start (7 capacities of words; sized for n + 1), the totals, and the
     // map of the last merge, valid while merge_map_tag holds; keys, permutation and the sort's work area are the compact export's
     m2s_host::DevBuf<uint32_t> d_merge_u32;
@@ -223,7 +228,7 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<uint32_t> d_merge_map;
     uint64_t last_merge_counts[4] = { 0, 0, 0, 0 };
     float last_merge_stage_ms[3] = { 0, 0, 0 };          // keys + sort, heads + scans, reduce + adopt
-    m2s_host::EventSet<6> merge_ev;                      // keys + sort: 0-2 | segments: 3, 4 | reduce: 4, 5
+    m2s_host::ClockOf<m2s_host::MergeMark> merge_clock;                      // always on
     // level-of-detail tree (m2s_lod.cpp): the node pool (leaves, then every level a merging step added), a parent word and a 16-byte
     // bound (x, y, z, longer edge) per node, one capacity of nodes each, grown together with their contents kept; lod_levels == 0: no tree
     m2s_host::DevBuf<float4> d_lod_nodes;                // capacity in records
@@ -233,7 +238,7 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     uint64_t lod_first[M2S_LOD_MAX_STEPS + 2] = {};      // first node of every level; [lod_levels] = the nodes
     uint32_t lod_R = 0;                                  // resolutionTarget of the leaves
     float last_lod_build_ms = 0.0f;
-    m2s_host::EventSet<2> lod_build_ev;
+    m2s_host::ClockOf<m2s_host::SpanMark> lod_build_clock;   // always on
     // the cut (m2s_lod_select): a byte per node (every ancestor-or-self refines), the selected counts per level and the refining nodes
     // behind them, the node index of every output record, valid while lod_ids_tag holds; flags, offsets and the scan area are m2s_prune's
     m2s_host::DevBuf<uint8_t> d_lod_open;
@@ -242,21 +247,21 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     uint64_t last_lod_select_counts[4] = { 0, 0, 0, 0 };
     uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
     float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
-    m2s_host::EventSet<4> lod_ev;
+    m2s_host::ClockOf<m2s_host::LodCutMark> lod_cut_clock;
     // the cut that fits a budget (m2s_lod_select_budget): the keys (L, H) per node and the words of the search
     m2s_host::DevBuf<uint2> d_lod_lh;
     m2s_host::DevBuf<uint32_t> d_lod_budget_state;       // kLodBudgetStateWords
     float last_lod_budget_stage_ms[3] = { 0, 0, 0 };     // thresholds, the four select rounds, the cut (profiling on)
-    m2s_host::EventSet<3> lod_budget_ev;
+    m2s_host::ClockOf<m2s_host::LodBudgetMark> lod_budget_clock;
     // the cuts over a frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum): a visibility byte per node, the leaves inside
     // and the nodes the plain cut selects and the frustum dropped (two more words of d_lod_counts), the visibility stage
     m2s_host::DevBuf<uint8_t> d_lod_vis;
     uint64_t last_lod_frustum_counts[2] = { 0, 0 };
     float last_lod_frustum_ms = 0.0f;
-    m2s_host::EventSet<2> lod_vis_ev;
+    m2s_host::ClockOf<m2s_host::SpanMark> lod_vis_clock;
     // world units (m2s_worldunits.cpp)
     float last_world_units_ms = 0.0f;
-    m2s_host::EventSet<2> wu_ev;
+    m2s_host::ClockOf<m2s_host::SpanMark> wu_clock;
     // shadow pass (m2s_light.cpp): the six per-face quad lists back to back in one exact-size, grow-only buffer, the depth cube,
     // and the pass's grow-only work buffers
     m2s_host::DevBuf<float4> d_shadow_quads; // 48 B each
@@ -268,7 +273,7 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<float> d_sh_views;      // six view matrices (96 floats) | bases (8 words)
     m2s_host::BinWork shadow_work;           // stage B: per quad a 48-byte record; totals: [0] pairs, [1] skipped quads, [2] atomics sent
                                              // (pinned: those three words, then the bases and the view matrices); its work area serves stage A too
-    m2s_host::EventSet<10> light_ev;
+    m2s_host::ClockOf<m2s_host::ShadowMark> shadow_clock;
     float last_shadow_ms = 0.0f;
     float last_shadow_stage_ms[3] = { 0, 0, 0 };    // stage A (count + scan + emit), setup + binning, raster (profiling on)
     uint64_t last_shadow_counts[9] = {};            // quads of face 0..5, (tile, quad) pairs, texel writes (atomics sent), quads skipped
@@ -278,13 +283,14 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     int32_t frame_w = 0, frame_h = 0;        // 0: no relight has run
     bool frame_has_counts = false;
     float last_relight_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> relight_clock;   // m2s_relight, m2s_relight_split, m2s_relight_mesh
     // mesh depth prepass (m2s_meshdepth.cpp): the image and the pass's grow-only work buffers
     m2s_host::DevBuf<float> d_md_image;      // float[H][W], row 0 = bottom; capacity in texels
     int32_t md_w = 0, md_h = 0;              // 0: no image yet
     int32_t md_inplace = -1;                 // m2s_debug_set_mesh_depth_inplace (-1: the default, kMdInplace)
     m2s_host::DevBuf<uint32_t> d_md_deferred;   // triangles the setup kernel left to the binned path (capacity in triangles)
     m2s_host::BinWork md_work;               // per deferred triangle six slots of a 48-byte record; totals: 8 words, see meshdepth_setup
-    m2s_host::EventSet<6> md_ev;
+    m2s_host::ClockOf<m2s_host::MeshMark> md_clock;              // mesh_raster: this pass and the visibility stage of the mesh render pass
     float last_md_ms = 0.0f;
     float last_md_stage_ms[3] = { 0, 0, 0 };     // setup + in-place, clip + binning, tile raster (profiling on)
     uint64_t last_md_counts[5] = {};             // drawn, clipped, non-finite, pairs, texel updates sent
@@ -292,8 +298,8 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<unsigned long long> d_mr_vis;   // uint64[H][W], row 0 = bottom: (bits of z) << 32 | global triangle index
     m2s_host::GBufPlanes d_mr_gbuf;              // layouts of d_gbuf
     int32_t mr_w = 0, mr_h = 0;                  // 0: no mesh G-buffer yet
-    m2s_host::EventSet<2> mr_ev;
     float last_mr_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> mr_clock;   // (the shading; the visibility stage: md_clock)
     float last_mr_stage_ms[4] = { 0, 0, 0, 0 };  // visibility setup + in-place, clip + binning, tile raster, shading (profiling on)
     uint64_t last_mr_counts[6] = {};             // drawn, clipped, non-finite, pairs, texel updates sent, culled as back-facing
     // fidelity score (m2s_light.cpp: m2s_relight_mesh; m2s_score.cpp): the mesh-lit frame, the comparison's counters and error map
@@ -303,8 +309,8 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::PinnedBuf<unsigned long long> h_score;     // pinned copy
     m2s_host::DevBuf<uint32_t> d_score_map;      // uchar4[H][W]
     int32_t score_map_w = 0, score_map_h = 0;    // 0: the last m2s_score_frames kept no map
-    m2s_host::EventSet<2> score_ev;
     float last_score_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> score_clock;
 
     // light baked into spherical harmonics (m2s_bake.cpp): the coefficient plane, the optional tap counts, the quadrature table
     m2s_host::DevBuf<float> d_sh;                // float[n][48]: f_dc[3], f_rest[45] channel-major; capacity in records; sh_tag: set once a
@@ -312,8 +318,8 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<uint8_t> d_bake_counts;     // uint8[n] (bake_has_counts)
     m2s_host::DevBuf<float> d_bake_table;        // n_theta * n_phi rows of kBakeTableRow floats
     uint32_t bake_table_nt = 0, bake_table_np = 0;
-    m2s_host::EventSet<2> bake_ev;
     float last_bake_ms = 0.0f;
+    m2s_host::ClockOf<m2s_host::SpanMark> bake_clock;
     uint32_t sh_degree = 0;                      // degree of the last bake (the compact export's SH element)
 
     // compact .ply export (m2s_compact.cpp): the pass's own buffers — the depth sort's words are the prune pass's sources and stay as they are
@@ -322,12 +328,12 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<void> d_compact_temp;       // the sort's work area; capacity in bytes
     m2s_host::DevBuf<uint8_t> d_compact_out;     // chunk table | rows | SH bytes, each from a 256-byte boundary; capacity in bytes
     m2s_host::PinnedBuf<uint32_t> h_compact;     // pinned { N, skipped }
-    m2s_host::EventSet<5> compact_ev;
+    m2s_host::ClockOf<m2s_host::CompactMark> compact_clock;          // always on
     float last_compact_stage_ms[4] = { 0, 0, 0, 0 };   // box + keys, sort, pack, download + write
 
     // measurement
     bool profiling = false;
-    m2s_host::EventSet<8> ev;
+    m2s_host::ClockOf<m2s_host::ConvMark> conv_clock;           // the conversion driver (m2s_pass.cpp)
     float last_ms[M2S_K_N] = {};
 };
 
@@ -348,6 +354,10 @@ namespace m2s_host {
 inline m2s_status fail(m2s_ctx* c, m2s_status s, const std::string& msg) {
     if (c) c->err = msg;
     return s;
+}
+template <class T, size_t N> inline m2s_status get_array(const m2s_ctx* c, T (m2s_ctx::*member)[N], T* out) {   // the getters of a member array
+    if (c && out) for (size_t k = 0; k < N; ++k) out[k] = (c->*member)[k];
+    return c && out ? M2S_OK : M2S_ERR_INVALID;
 }
 // the R last converted at, for the readers that mean the scene's density and not the unit of the records (the upload's warm_R,
 // m2s_download_triangle_counts): last_R, unless m2s_records_to_world_units has taken that to 1 since
@@ -415,11 +425,11 @@ m2s_status ensure_records(m2s_ctx* c, uint64_t want);
 m2s_status ensure_stage(m2s_ctx* c);
 // m2s_splat.cpp
 // The stages of the splat pass in front of the blend — setup / bin, pairs, grouping by tile, tile order — over n quads on a W x H
-// viewport, in the context's splat work buffers: what m2s_splat and m2s_contrib_accumulate both start with.  Records ev[0..4] when
-// profiling (setup: 0-1, pairs: 2-3, grouping: 3-4); synchronises once (the pair count).  vals / ranges / order are NULL without pairs.
+// viewport, in the context's splat work buffers: what m2s_splat, m2s_contrib_accumulate and m2s_refit_accumulate start with.  Opens
+// bin_clock (profiling) and records BinMark::Setup .. Grouped; synchronises once (the pair count).  vals / ranges / order are NULL without pairs.
 struct SplatBins { const uint32_t* vals = nullptr; const uint2* ranges = nullptr; const uint32_t* order = nullptr; uint64_t pairs = 0, skipped = 0; };
 m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H, SplatBins* out);
-m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]);   // ... and their times + the blend's (ev[4..5]), profiling on
+m2s_status splat_stage_ms(m2s_ctx* c, float out[3]);   // ... and their times + the blend's (the caller's BinMark::Blended), bin_clock on
 // m2s_contrib.cpp
 inline bool contrib_valid(const m2s_ctx* c) { return c->contrib_tag.holds(*c, c->last_stored); }   // the accumulators belong to the current records
 // What m2s_prune and m2s_prune_budget end with.  prune_compact_enqueue: the `kept` flagged records of the n current ones (and the rows of
@@ -450,7 +460,7 @@ m2s::BatchTable batches_for(const m2s_ctx* c, const m2s_ctx::RInfo& ri);
 uint64_t resolve_cap(const m2s_ctx* c, uint32_t R);
 m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted = false);   // called by m2s_upload_scene once the scene is resident
 m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R);                  // ... its exact count, enqueued earlier (in front of the texture copies)
-m2s_status enqueue_multipass(m2s_ctx* c, int lane, uint32_t R, float4* d_out, uint64_t limit, bool prof, unsigned long long* h_res, hipStream_t st);
+m2s_status enqueue_multipass(m2s_ctx* c, int lane, uint32_t R, float4* d_out, uint64_t limit, const StageMarks& marks, unsigned long long* h_res, hipStream_t st);
 // what `lane` needs before a conversion is enqueued on it; multipass: its multi-pass work set for n_start slices included
 m2s_status ensure_lane(m2s_ctx* c, int lane, bool multipass, uint32_t n_start);
 m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hipStream_t st, uint64_t* out_total,

@@ -5,9 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "m2s_stageclock.h"   // StageMarks: what the launchers that time their own stages record through
 #include "m2s_vtable.h"
 
 namespace m2s {
+using m2s_host::StageMarks;
 
 // Debug / A-B switches of the library (M2S_NO_BANDS, M2S_NO_LEAN, M2S_NO_WARM, ...) exist only in a DEBUG BUILD (`make EXTRA=-DM2S_DEBUG_BUILD
 // OUT=../_build_debug`: what tools/first_call_probe.py, tools/mp_probe.py and the A/B scripts under tools/ab/ load through M2S_LIB_PATH), and
@@ -240,16 +242,17 @@ hipError_t sort_prepass(const float* depths, const float4* quads, uint32_t n, ui
                         size_t temp_bytes, float4* sorted, hipStream_t st);
 size_t sort_temp_bytes(uint32_t n);
 // *key_offset_out (may be NULL: then keys_out is made whole before returning): keys_out holds `key - offset` (the sort ran over the bits in
-// which the keys differ); launch_add_to_keys puts it back
+// which the keys differ); launch_add_to_keys puts it back.  marks: 0..3 around keys | radix sort | gather
 hipError_t sort_by_depth(const float4* rec, uint32_t n, const float view[16], uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out,
-                         void* temp, size_t temp_bytes, float4* sorted, float4* plane, bool plane_valid, hipEvent_t* stage_ev, hipStream_t st,
+                         void* temp, size_t temp_bytes, float4* sorted, float4* plane, bool plane_valid, const StageMarks& marks, hipStream_t st,
                          uint32_t* key_offset_out, uint32_t* pinned_mm /* two pinned host words for the key range, or NULL */);
 void launch_add_to_keys(uint32_t* keys, uint32_t n, uint32_t offset, hipStream_t st);
 // keys = the depth bits the PREPASS stores (model, view as in PrepassK), stable radix sort, no gather: vals_out = the permutation
 // cull: the prepass's frustum test applied to the keys (survivors first: *n_visible of them; *clash: call again without cull); pinned_mm4: FOUR words
+// marks: 0..2 around keys | radix sort
 hipError_t sort_prepass_permutation(const float4* rec, uint32_t n, const float model[16], const float view[16], const float proj[16], bool cull,
                                     uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, float4* plane, bool plane_valid,
-                                    hipEvent_t* ev, hipStream_t st, uint32_t* pinned_mm4, uint32_t* n_visible, bool* clash);
+                                    const StageMarks& marks, hipStream_t st, uint32_t* pinned_mm4, uint32_t* n_visible, bool* clash);
 
 // ---- splat pass (m2s_splat.hip): GaussianSplattingPass over sorted quads into the five-target G-buffer ---------------------------
 constexpr int kSplatTile = 16;                 // tiles of 16 x 16 pixels, one workgroup (one lane per pixel) each
@@ -291,11 +294,11 @@ constexpr uint32_t kBudgetShards = 4;      // (a power of two)
 constexpr uint32_t kBudgetCandidates = 0, kBudgetPrefix = 4, kBudgetQuota = 5, kBudgetActive = 6, kBudgetTies = 7, kBudgetHist = 8;
 constexpr uint32_t kBudgetStateWords = kBudgetHist + 4 * kBudgetShards * 256;
 // keys (importance 0: from wmax / npix and m2s_prune's thresholds; 1: from rec, the accumulators are not read), the four histogram /
-// pick rounds, ev[0]; tie flags, their ranks, keep flags, offsets = exclusive scan of the keep flags, ev[1] (ev NULL: no events).
+// pick rounds, mark 0; tie flags, their ranks, keep flags, offsets = exclusive scan of the keep flags, mark 1.
 // keys, flags, offsets: n words each; state: kBudgetStateWords; temp: prune_scan_temp_bytes(n).  budget >= 1, n > 0.
 hipError_t budget_select(const float4* rec, const uint32_t* wmax, const uint32_t* npix, uint32_t n, uint32_t importance, float min_weight,
                          uint32_t min_pixels, uint32_t budget, uint32_t* keys, uint32_t* state, uint32_t* flags, uint32_t* offsets, void* temp,
-                         size_t temp_bytes, hipEvent_t* ev, hipStream_t st);
+                         size_t temp_bytes, const StageMarks& marks, hipStream_t st);
 hipError_t preload_budget();
 
 // ---- colour refit (m2s_refit.hip) --------------------------------------------------------------------------------------------------
@@ -487,9 +490,9 @@ inline uint32_t compact_waves(uint32_t n) { return (n + kBlock - 1) / kBlock * (
 size_t compact_sort_temp_bytes(uint32_t n);
 // keys_in / vals_in / keys_out / vals_out: n words each; wave_box: compact_waves(n) * 8 words; head: 8 words, afterwards { min.xyz,
 // max.xyz of the valid positions in the order of m2s_compactmath.h's ord(), N, skipped }; the first N words of vals_out: the permutation.
-// ev: three events, around box + keys and around the sort.  n > 0.
+// marks: 0..2, around box + keys and around the sort.  n > 0.
 hipError_t compact_keys_and_sort(const float4* rec, const float4* plane, uint32_t n, uint32_t* wave_box, uint32_t* head, uint32_t* keys_in, uint32_t* vals_in,
-                                 uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, hipEvent_t* ev, hipStream_t st);
+                                 uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, const StageMarks& marks, hipStream_t st);
 // table: 18 floats per chunk; rows: N x 16 bytes; sh_out (K = 3 | 8 | 15): WHOLE chunks of 256 x 3 K bytes; sh: the baked plane or NULL
 hipError_t compact_pack(const float4* rec, const float* sh, const uint32_t* perm, uint32_t N, float sm, uint32_t K, float* table, void* rows, void* sh_out,
                         hipStream_t st);

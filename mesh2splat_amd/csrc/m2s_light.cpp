@@ -17,8 +17,7 @@ constexpr size_t kPinnedBytes = kPinnedViews * 8 + 96 * sizeof(float);
 
 m2s_status ensure_light_common(m2s_ctx* c) {
     M2S_TRY(c->shadow_work.reserve_totals(c->err, 4, kPinnedBytes));
-    M2S_TRY(c->d_sh_views.reserve(c->err, 96 + 8, sizeof(float)));
-    return c->light_ev.ensure(c->err);
+    return c->d_sh_views.reserve(c->err, 96 + 8, sizeof(float));
 }
 
 // The six cameras of the light (GaussianShadowPass.cpp:91-108: glm::lookAt(light, light + axis, up)) and the 90 degree / aspect 1
@@ -62,17 +61,16 @@ m2s_status check_light(m2s_ctx* c, const m2s_light_params* lp, int* S_out) {
 // Stage B over `total` quads in c->d_shadow_quads (the six lists back to back, fb: where each starts) into the cleared cube.
 m2s_status shadow_stage_b(m2s_ctx* c, const m2s_light_params* lp, int S, uint32_t total, const ShadowBases& fb, uint64_t* out_skipped, float* b_ms,
                           float* r_ms) {
-    hipEvent_t* ev = c->light_ev;
-    const bool prof = c->profiling;
+    ClockOf<ShadowMark>& clock = c->shadow_clock;      // (opened by the caller)
     // ---- stage B: setup, the number of (tile, quad) pairs read back once (the pair buffers are sized from it)
     BinWork& w = c->shadow_work;
     M2S_TRY(w.reserve_items(c->err, total, 48));
     M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes(1, total, 1)));
     const float4* rec = (const float4*)w.rec.get();
-    if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
+    HIPCHK(c, clock.mark(ShadowMark::Setup, c->stream));
     HIPCHK(c, shadow_setup(c->d_shadow_quads, total, fb, S, lp->light_position, lp->near_far[1], (float4*)w.rec.get(), w.cnt, w.off, w.temp,
                            w.temp.cap(), w.d_totals, c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(ev[5], c->stream));
+    HIPCHK(c, clock.mark(ShadowMark::SetupEnd, c->stream));
     HIPCHK(c, hipMemcpyAsync(w.h_totals, w.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t pairs = w.h_totals[0];
@@ -83,28 +81,23 @@ m2s_status shadow_stage_b(m2s_ctx* c, const m2s_light_params* lp, int S, uint32_
         BinWork::Pairs pr;
         M2S_TRY(w.reserve_pairs(c->err, pairs, &pr));
         M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes(1, 1, (uint32_t)pairs)));
-        if (prof) HIPCHK(c, hipEventRecord(ev[6], c->stream));
+        HIPCHK(c, clock.mark(ShadowMark::Bin, c->stream));
         HIPCHK(c, shadow_bin(rec, w.cnt, w.off, total, S, pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, w.temp, w.temp.cap(),
                              c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[7], c->stream));
+        HIPCHK(c, clock.mark(ShadowMark::Binned, c->stream));
         HIPCHK(c, shadow_raster(rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, S, c->d_shadow_cube, w.d_totals + 2, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[8], c->stream));
+        HIPCHK(c, clock.mark(ShadowMark::Rastered, c->stream));
         HIPCHK(c, hipMemcpyAsync(w.h_totals + 2, w.d_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->last_shadow_counts[6] = pairs;
         c->last_shadow_counts[7] = w.h_totals[2];
-        if (prof) {
-            float x = 0, y = 0;
-            HIPCHK(c, hipEventElapsedTime(&x, ev[6], ev[7]));
-            HIPCHK(c, hipEventElapsedTime(&y, ev[7], ev[8]));
-            *b_ms += x; *r_ms += y;
-        }
     }
-    if (prof) {
-        float y = 0;
-        HIPCHK(c, hipEventElapsedTime(&y, ev[4], ev[5]));
-        *b_ms += y;
-    }
+    float x = 0, y = 0, z = 0;                         // (0 where the stage did not run, or the clock is off)
+    HIPCHK(c, clock.span(ShadowMark::Bin, ShadowMark::Binned, &x));
+    HIPCHK(c, clock.span(ShadowMark::Binned, ShadowMark::Rastered, &y));
+    HIPCHK(c, clock.span(ShadowMark::Setup, ShadowMark::SetupEnd, &z));
+    *b_ms += x; *r_ms += y;
+    *b_ms += z;
     return M2S_OK;
 }
 
@@ -132,8 +125,8 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
     for (uint64_t& v : c->last_shadow_counts) v = 0;
     const uint64_t texels = 6ull * (uint64_t)S * (uint64_t)S;
     M2S_TRY(c->d_shadow_cube.reserve(c->err, texels, sizeof(float)));
-    hipEvent_t* ev = c->light_ev;
-    const bool prof = c->profiling;
+    ClockOf<ShadowMark>& clock = c->shadow_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));                      // glClear(GL_DEPTH_BUFFER_BIT), six times
     HIPCHK(c, hipMemsetAsync(c->shadow_work.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
     const uint32_t nr = (uint32_t)n;
@@ -154,9 +147,9 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
         M2S_TRY(w.reserve_temp(c->err, shadow_temp_bytes((uint32_t)words, 1, 1)));
         uint32_t* d_bases = reinterpret_cast<uint32_t*>(c->d_sh_views + 96);
         HIPCHK(c, hipMemcpyAsync(c->d_sh_views, h_views, 96 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, clock.mark(ShadowMark::Count, c->stream));
         HIPCHK(c, shadow_count(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, cnt, off, w.temp, w.temp.cap(), d_bases, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+        HIPCHK(c, clock.mark(ShadowMark::Counted, c->stream));
         uint32_t* h_bases = reinterpret_cast<uint32_t*>(w.h_totals + kPinnedBases);
         HIPCHK(c, hipMemcpyAsync(h_bases, d_bases, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -165,21 +158,16 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
         for (int f = 0; f < 7; ++f) fb.b[f] = h_bases[f];
         if (total) {
             M2S_TRY(c->d_shadow_quads.reserve(c->err, total, 48));
-            if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+            HIPCHK(c, clock.mark(ShadowMark::Emit, c->stream));
             HIPCHK(c, shadow_emit(k, c->d_sh_views, lp->light_position, (const float4*)d_records, nr, off, c->d_shadow_quads, c->stream));
-            if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+            HIPCHK(c, clock.mark(ShadowMark::Emitted, c->stream));
             if (m2s_status st = shadow_stage_b(c, lp, S, total, fb, out_skipped, &b_ms, &r_ms)) return st;
-            if (prof) {
-                float x = 0;
-                HIPCHK(c, hipEventElapsedTime(&x, ev[2], ev[3]));
-                a_ms += x;
-            }
         }
-        if (prof) {
-            float x = 0;
-            HIPCHK(c, hipEventElapsedTime(&x, ev[0], ev[1]));
-            a_ms += x;
-        }
+        float x = 0, y = 0;
+        HIPCHK(c, clock.span(ShadowMark::Emit, ShadowMark::Emitted, &x));
+        HIPCHK(c, clock.span(ShadowMark::Count, ShadowMark::Counted, &y));
+        a_ms += x;
+        a_ms += y;
         for (int f = 0; f < 7; ++f) c->shadow_base[f] = fb.b[f];
         for (int f = 0; f < 6; ++f) {
             c->last_shadow_counts[f] = fb.b[f + 1] - fb.b[f];
@@ -187,7 +175,7 @@ m2s_status m2s_shadow(m2s_ctx* c, const m2s_prepass_params* pp, const m2s_light_
         }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (prof) {
+    if (clock.on()) {
         c->last_shadow_stage_ms[0] = a_ms; c->last_shadow_stage_ms[1] = b_ms; c->last_shadow_stage_ms[2] = r_ms;
         c->last_shadow_ms = a_ms + b_ms + r_ms;
     }
@@ -219,6 +207,7 @@ m2s_status m2s_shadow_from_quads(m2s_ctx* c, const m2s_light_params* lp, const m
     for (uint32_t& b : c->shadow_base) b = 0;
     for (uint64_t& v : c->last_shadow_counts) v = 0;
     M2S_TRY(c->d_shadow_cube.reserve(c->err, 6ull * (uint64_t)S * (uint64_t)S, sizeof(float)));
+    M2S_TRY(c->shadow_clock.begin(c->err, c->profiling));
     HIPCHK(c, shadow_clear(c->d_shadow_cube, S, c->stream));
     HIPCHK(c, hipMemsetAsync(c->shadow_work.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
     float b_ms = 0, r_ms = 0;
@@ -228,7 +217,7 @@ m2s_status m2s_shadow_from_quads(m2s_ctx* c, const m2s_light_params* lp, const m
         if (m2s_status s = shadow_stage_b(c, lp, S, (uint32_t)total, fb, out_skipped, &b_ms, &r_ms)) return s;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) {
+    if (c->shadow_clock.on()) {
         c->last_shadow_stage_ms[0] = 0; c->last_shadow_stage_ms[1] = b_ms; c->last_shadow_stage_ms[2] = r_ms;
         c->last_shadow_ms = b_ms + r_ms;
     }
@@ -328,14 +317,15 @@ static m2s_status relight(m2s_ctx* c, const m2s_light_params* lp, bool split, fl
     M2S_TRY(c->d_shadow_counts.reserve(c->err, px, 1));
     const RelightK k = relight_uniforms(c, lp, c->gbuf_w, c->gbuf_h);
     const bool counts = lp->want_shadow_counts != 0 && lp->render_mode == 6;
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
+    M2S_TRY(c->relight_clock.begin(c->err, c->profiling));
+    HIPCHK(c, c->relight_clock.mark(SpanMark::Begin, c->stream));
     const int split_x = split ? (int)(split_position * (float)c->gbuf_w) : 0;      // static_cast<int>(splitScreenPosition * w)
     const int div_x = std::max(0, split_x - 1);                                      // dividerWidth / 2 == 1
     HIPCHK(c, launch_relight(k, c->d_gbuf.ptr, c->d_shadow_cube, c->d_frame, counts ? c->d_shadow_counts.get() : nullptr, c->stream,
                              split ? c->d_mr_gbuf.ptr : nullptr, split_x, div_x));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
+    HIPCHK(c, c->relight_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
+    if (c->relight_clock.on()) HIPCHK(c, c->relight_clock.span(SpanMark::Begin, SpanMark::End, &c->last_relight_ms));
     c->frame_w = c->gbuf_w;
     c->frame_h = c->gbuf_h;
     c->frame_has_counts = counts;
@@ -356,11 +346,12 @@ m2s_status m2s_relight_mesh(m2s_ctx* c, const m2s_light_params* lp) {
     c->mesh_frame_w = c->mesh_frame_h = 0;
     M2S_TRY(c->d_mesh_frame.reserve(c->err, (uint64_t)c->mr_w * (uint64_t)c->mr_h, 4));
     const RelightK k = relight_uniforms(c, lp, c->mr_w, c->mr_h);
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[0], c->stream));
+    M2S_TRY(c->relight_clock.begin(c->err, c->profiling));
+    HIPCHK(c, c->relight_clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, launch_relight(k, c->d_mr_gbuf.ptr, c->d_shadow_cube, c->d_mesh_frame, nullptr, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->light_ev[1], c->stream));
+    HIPCHK(c, c->relight_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_relight_ms, c->light_ev[0], c->light_ev[1]));
+    if (c->relight_clock.on()) HIPCHK(c, c->relight_clock.span(SpanMark::Begin, SpanMark::End, &c->last_relight_ms));
     c->mesh_frame_w = c->mr_w;
     c->mesh_frame_h = c->mr_h;
     return M2S_OK;
@@ -401,16 +392,8 @@ m2s_status m2s_download_shadow_counts(m2s_ctx* c, uint8_t* dst, uint64_t capacit
 }
 
 float m2s_last_shadow_ms(const m2s_ctx* c) { return c ? c->last_shadow_ms : 0.0f; }
-m2s_status m2s_last_shadow_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_shadow_stage_ms, sizeof(c->last_shadow_stage_ms));
-    return M2S_OK;
-}
-m2s_status m2s_last_shadow_counts(const m2s_ctx* c, uint64_t out[9]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 9; ++k) out[k] = c->last_shadow_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_shadow_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_shadow_stage_ms, out_ms); }
+m2s_status m2s_last_shadow_counts(const m2s_ctx* c, uint64_t out[9]) { return get_array(c, &m2s_ctx::last_shadow_counts, out); }
 float m2s_last_relight_ms(const m2s_ctx* c) { return c ? c->last_relight_ms : 0.0f; }
 
 }  // extern "C"

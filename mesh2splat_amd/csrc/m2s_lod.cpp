@@ -58,20 +58,17 @@ m2s_status lod_frustum_check(m2s_ctx* c, const m2s_lod_frustum* fr) {
     return M2S_OK;
 }
 
-// The visibility plane of the tree's N > 0 nodes for one frustum, timed where the context profiles (read after the next synchronisation).
+// The visibility plane of the tree's N > 0 nodes for one frustum, timed by lod_vis_clock, which whoever calls this has opened for the call
+// (in front of its test for an empty tree, so that the cut reads 0 where this never ran).
 // The cut's count words are zeroed here, in front of the stage that writes the first of them.
 m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr) {
-    const bool prof = c->profiling;
     M2S_TRY(c->d_lod_vis.reserve(c->err, c->lod_first[c->lod_levels], 1));
     M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
     HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
-    if (prof) {
-        M2S_TRY(c->lod_vis_ev.ensure(c->err));
-        HIPCHK(c, hipEventRecord(c->lod_vis_ev[0], c->stream));
-    }
+    HIPCHK(c, c->lod_vis_clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, lod_visibility(c->d_lod_bounds, c->d_lod_parent, c->lod_first, c->lod_levels, lod_frustum_k(fr), c->d_lod_vis,
                              c->d_lod_counts + kLodInsideWord, c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(c->lod_vis_ev[1], c->stream));
+    HIPCHK(c, c->lod_vis_clock.mark(SpanMark::End, c->stream));
     return M2S_OK;
 }
 
@@ -82,11 +79,12 @@ enum class LodVis { None, Here, Enqueued };     // no frustum | lod_cut enqueues
 m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4], const m2s_lod_frustum* fr, LodVis vis) {
     if ((fr != nullptr) != (vis != LodVis::None)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
     const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
-    const bool prof = c->profiling;
+    ClockOf<LodCutMark>& clock = c->lod_cut_clock;
     const uint32_t levels = c->lod_levels;
     const uint64_t N = c->lod_first[levels];
     HIPCHK(c, hipSetDevice(c->device));
-    if (prof) M2S_TRY(c->lod_ev.ensure(c->err));
+    M2S_TRY(clock.begin(c->err, c->profiling));
+    if (vis == LodVis::Here) M2S_TRY(c->lod_vis_clock.begin(c->err, c->profiling));
     uint32_t h[kLodCountWords] = {};
     uint64_t selected = 0;
     if (N) {
@@ -102,16 +100,16 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         uint32_t* const offsets = flags + c->d_prune_u32.cap();
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
         if (vis == LodVis::Here) M2S_TRY(lod_vis_enqueue(c, fr));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[0], c->stream));
+        HIPCHK(c, clock.mark(LodCutMark::Start, c->stream));
         // (with a frustum the words were zeroed by lod_vis_enqueue, here or in the caller, and hold the inside count by now: not again)
         if (vis == LodVis::None) HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
         HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts,
                             fr ? c->d_lod_vis.get() : nullptr, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[1], c->stream));
+        HIPCHK(c, clock.mark(LodCutMark::Swept, c->stream));
         if (!dry) {
             HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
             HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->d_lod_ids, c->stream));
-            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[2], c->stream));
+            HIPCHK(c, clock.mark(LodCutMark::Indexed, c->stream));
         }
         HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -121,18 +119,8 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
             return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
         if (!dry) {
             M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
-            if (prof) HIPCHK(c, hipEventRecord(c->lod_ev[3], c->stream));
+            HIPCHK(c, clock.mark(LodCutMark::Compacted, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        if (prof) {
-            float* ms = c->last_lod_select_stage_ms;
-            ms[1] = ms[2] = 0.0f;
-            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_ev[0], c->lod_ev[1]));
-            if (!dry) {
-                HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_ev[1], c->lod_ev[2]));
-                HIPCHK(c, hipEventElapsedTime(&ms[2], c->lod_ev[2], c->lod_ev[3]));   // (the round trip of the counts included)
-            }
-            if (fr) HIPCHK(c, hipEventElapsedTime(&c->last_lod_frustum_ms, c->lod_vis_ev[0], c->lod_vis_ev[1]));
         }
     } else {
         if (!dry) {
@@ -140,8 +128,13 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
             M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        if (prof) c->last_lod_select_stage_ms[0] = c->last_lod_select_stage_ms[1] = c->last_lod_select_stage_ms[2] = 0.0f;
-        if (prof && fr) c->last_lod_frustum_ms = 0.0f;
+    }
+    if (clock.on()) {   // (a dry run records neither Indexed nor Compacted, an empty tree nothing: those spans are 0)
+        float* ms = c->last_lod_select_stage_ms;
+        HIPCHK(c, clock.span(LodCutMark::Start, LodCutMark::Swept, &ms[0]));
+        HIPCHK(c, clock.span(LodCutMark::Swept, LodCutMark::Indexed, &ms[1]));
+        HIPCHK(c, clock.span(LodCutMark::Indexed, LodCutMark::Compacted, &ms[2]));   // (the round trip of the counts included)
+        if (fr) HIPCHK(c, c->lod_vis_clock.span(SpanMark::Begin, SpanMark::End, &c->last_lod_frustum_ms));   // (an empty tree: 0 too)
     }
     if (!dry) {
         c->rewritten(c->lane[0].records, selected, c->lod_R, Rewrite::LodCut);   // (a baked plane is one of other records: dropped)
@@ -179,25 +172,26 @@ m2s_status lod_budget_check(m2s_ctx* c, const m2s_lod_budget_params* p) {
 // m2s_lod_select_budget behind its checks.  fr (NULL: the plain search): the nodes without a leaf inside are selected at no key, and
 // the budget is raised to the visible nodes of the last level on the device.
 m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out, uint64_t out_counts[4]) {
-    const bool prof = c->profiling;
+    ClockOf<LodBudgetMark>& clock = c->lod_budget_clock;
     const uint32_t levels = c->lod_levels;
     const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
     uint32_t floor_key = 0, key = 0;
     if (p->tau_min_px > 0.0f) std::memcpy(&floor_key, &p->tau_min_px, sizeof(floor_key));
     uint32_t h[3] = {};                                                 // prefix, below, finer
     HIPCHK(c, hipSetDevice(c->device));
+    M2S_TRY(clock.begin(c->err, c->profiling));
+    if (fr) M2S_TRY(c->lod_vis_clock.begin(c->err, c->profiling));
     if (N) {
         M2S_TRY(c->d_lod_lh.reserve(c->err, N, sizeof(uint2)));
         M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
-        if (prof) M2S_TRY(c->lod_budget_ev.ensure(c->err));
         const uint32_t n_eff = fr ? p->max_records : (uint32_t)std::max<uint64_t>(p->max_records, last);
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
         if (fr) M2S_TRY(lod_vis_enqueue(c, fr));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[0], c->stream));
+        HIPCHK(c, clock.mark(LodBudgetMark::Start, c->stream));
         HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, fr ? c->d_lod_vis.get() : nullptr, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[1], c->stream));
+        HIPCHK(c, clock.mark(LodBudgetMark::Thresholds, c->stream));
         HIPCHK(c, lod_budget_search(c->d_lod_lh, (uint32_t)N, n_eff, fr != nullptr, c->d_lod_budget_state, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(c->lod_budget_ev[2], c->stream));
+        HIPCHK(c, clock.mark(LodBudgetMark::Searched, c->stream));
         HIPCHK(c, hipMemcpyAsync(h, c->d_lod_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         key = h[kLodBudgetPrefix];
@@ -213,13 +207,10 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
     sp.flags = p->flags;
     uint64_t counts[4] = {};
     M2S_TRY(lod_cut(c, &sp, counts, fr, fr ? LodVis::Enqueued : LodVis::None));
-    if (prof) {
+    if (clock.on()) {
         float* ms = c->last_lod_budget_stage_ms;
-        ms[0] = ms[1] = 0.0f;
-        if (N) {
-            HIPCHK(c, hipEventElapsedTime(&ms[0], c->lod_budget_ev[0], c->lod_budget_ev[1]));
-            HIPCHK(c, hipEventElapsedTime(&ms[1], c->lod_budget_ev[1], c->lod_budget_ev[2]));
-        }
+        HIPCHK(c, clock.span(LodBudgetMark::Start, LodBudgetMark::Thresholds, &ms[0]));      // (an empty tree: 0, like the next)
+        HIPCHK(c, clock.span(LodBudgetMark::Thresholds, LodBudgetMark::Searched, &ms[1]));
         ms[2] = (c->last_lod_select_stage_ms[0] + c->last_lod_select_stage_ms[1]) + c->last_lod_select_stage_ms[2];
     }
     if (out) {
@@ -252,9 +243,9 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     const uint32_t R = c->last_R;
     const bool unsigned_axis = (p->flags & M2S_MERGE_UNSIGNED_AXIS) != 0;   // (every step, the ones that merge nothing included)
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->lod_build_ev.ensure(c->err));
+    M2S_TRY(c->lod_build_clock.begin(c->err, true));                    // (measured whatever m2s_set_profiling says)
     c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
-    HIPCHK(c, hipEventRecord(c->lod_build_ev[0], c->stream));
+    HIPCHK(c, c->lod_build_clock.mark(SpanMark::Begin, c->stream));
     M2S_TRY(lod_reserve(c, n0 + n0 / 2, 0));
     uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
     uint32_t levels = 1;
@@ -279,9 +270,9 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
         first[++levels] = total;                                        // (the next step rewrites the map and the pool behind these, stream-ordered)
     }
     HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, c->d_lod_parent + first[levels - 1], nullptr, 0, nullptr, c->stream));
-    HIPCHK(c, hipEventRecord(c->lod_build_ev[1], c->stream));
+    HIPCHK(c, c->lod_build_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->last_lod_build_ms, c->lod_build_ev[0], c->lod_build_ev[1]));
+    HIPCHK(c, c->lod_build_clock.span(SpanMark::Begin, SpanMark::End, &c->last_lod_build_ms));
     for (uint32_t l = 0; l < M2S_LOD_MAX_STEPS + 2; ++l) c->lod_first[l] = first[std::min(l, levels)];
     c->lod_levels = levels;
     c->lod_R = R;
@@ -368,31 +359,15 @@ m2s_status m2s_lod_select_budget_frustum(m2s_ctx* c, const m2s_lod_budget_params
     return lod_budget(c, p, fr, out, out_counts);
 }
 
-m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* c, uint64_t out[2]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    std::memcpy(out, c->last_lod_frustum_counts, sizeof(c->last_lod_frustum_counts));
-    return M2S_OK;
-}
+m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* c, uint64_t out[2]) { return get_array(c, &m2s_ctx::last_lod_frustum_counts, out); }
 
 float m2s_last_lod_frustum_ms(const m2s_ctx* c) { return c ? c->last_lod_frustum_ms : 0.0f; }
 
-m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_lod_budget_stage_ms, sizeof(c->last_lod_budget_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_lod_budget_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_lod_budget_stage_ms, out_ms); }
 
-m2s_status m2s_last_lod_level_counts(const m2s_ctx* c, uint64_t out[M2S_LOD_MAX_STEPS + 1]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    std::memcpy(out, c->last_lod_level_counts, sizeof(c->last_lod_level_counts));
-    return M2S_OK;
-}
+m2s_status m2s_last_lod_level_counts(const m2s_ctx* c, uint64_t out[M2S_LOD_MAX_STEPS + 1]) { return get_array(c, &m2s_ctx::last_lod_level_counts, out); }
 
-m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_lod_select_stage_ms, sizeof(c->last_lod_select_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_lod_select_stage_ms, out_ms); }
 
 const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_tag.n ? c->d_lod_ids.get() : nullptr; }
 

@@ -28,8 +28,8 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
     bool dry = mode == MergeMode::Dry || (mode == MergeMode::IfAny && n == 0);
     const uint32_t R = c->last_R;
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->merge_ev.ensure(c->err));
-    hipEvent_t* ev = c->merge_ev;
+    ClockOf<MergeMark>& clock = c->merge_clock;
+    M2S_TRY(clock.begin(c->err, true));            // (measured whatever m2s_set_profiling says)
     uint64_t segments = 0, merged = 0, invalid = 0;
     float ms[3] = { 0, 0, 0 };
     if (n) {
@@ -50,11 +50,11 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
         uint32_t* const seg_start = m + 6 * mcap;
         const float4* plane = m2s_positions_ready(c) ? c->d_pos_plane.get() : nullptr;
         HIPCHK(c, compact_keys_and_sort((const float4*)c->last_records, plane, n, c->d_compact_waves, head, u, u + cap, u + 2 * cap, u + 3 * cap, c->d_compact_temp,
-                                        c->d_compact_temp.cap(), ev, c->stream));
-        HIPCHK(c, hipEventRecord(ev[3], c->stream));
+                                        c->d_compact_temp.cap(), clock.marks(), c->stream));
+        HIPCHK(c, clock.mark(MergeMark::Segments, c->stream));
         HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, level, max_group, min_axis_dot, m, m + mcap, packed, sums, seg_start,
                                  c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), unsigned_axis, c->stream));
-        HIPCHK(c, hipEventRecord(ev[4], c->stream));
+        HIPCHK(c, clock.mark(MergeMark::Segmented, c->stream));
         uint32_t h[kMergeTotalsWords] = {}, skipped = 0;
         HIPCHK(c, hipMemcpyAsync(h, c->d_merge_totals, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&skipped, head + 7, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -63,8 +63,6 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
         invalid = skipped;
         merged = h[1];
         if (segments < 1 || segments > n || invalid > n || merged > segments) return fail(c, M2S_ERR_HIP, "the merge pass's segment count came back inconsistent");
-        HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], ev[2]));
-        HIPCHK(c, hipEventElapsedTime(&ms[1], ev[3], ev[4]));
         if (mode == MergeMode::IfAny && segments == n) dry = true;   // (nothing to merge: nothing changes)
         if (!dry) {
             // The parents go into the pool.  Members that live there already cannot be reduced onto themselves by independent lanes: the
@@ -78,9 +76,8 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
             float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
             HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, unsigned_axis, c->stream));
             if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, segments * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipEventRecord(ev[5], c->stream));
+            HIPCHK(c, clock.mark(MergeMark::Reduced, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipEventElapsedTime(&ms[2], ev[4], ev[5]));
         }
     } else if (!dry) {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
@@ -91,6 +88,10 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
         c->rewritten(c->lane[0].records, segments, R, Rewrite::Merge);   // (a plane of the members is not a plane of their parents: dropped)
         c->merge_map_tag.set(*c, n);
     }
+    // (no records: three zeros; a dry run records no Reduced: [2] is 0)
+    HIPCHK(c, clock.span(MergeMark::Start, MergeMark::Sorted, &ms[0]));
+    HIPCHK(c, clock.span(MergeMark::Segments, MergeMark::Segmented, &ms[1]));
+    HIPCHK(c, clock.span(MergeMark::Segmented, MergeMark::Reduced, &ms[2]));
     c->last_merge_counts[0] = n; c->last_merge_counts[1] = segments; c->last_merge_counts[2] = merged; c->last_merge_counts[3] = invalid;
     std::memcpy(c->last_merge_stage_ms, ms, sizeof(ms));
     return M2S_OK;
@@ -114,17 +115,9 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
     return M2S_OK;
 }
 
-m2s_status m2s_last_merge_counts(const m2s_ctx* c, uint64_t out[4]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 4; ++k) out[k] = c->last_merge_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_merge_counts(const m2s_ctx* c, uint64_t out[4]) { return get_array(c, &m2s_ctx::last_merge_counts, out); }
 
-m2s_status m2s_last_merge_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_merge_stage_ms, sizeof(c->last_merge_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_merge_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_merge_stage_ms, out_ms); }
 
 const void* m2s_device_merge_map(const m2s_ctx* c) { return c && merge_map_valid(c) && c->merge_map_tag.n ? c->d_merge_map.get() : nullptr; }
 

@@ -31,16 +31,15 @@ void mesh_pvm(const float* proj, const float* view, const float* model, float* o
 m2s_status mesh_raster(m2s_ctx* c, const MeshDepthK& k, bool vis, void* image, float ms[3]) {
     BinWork& w = c->md_work;
     M2S_TRY(w.reserve_totals(c->err, 8, 8 * sizeof(unsigned long long)));
-    M2S_TRY(c->md_ev.ensure(c->err));
+    ClockOf<MeshMark>& clock = c->md_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     unsigned long long* const h_md = w.h_totals;
     for (int i = 0; i < 8; ++i) h_md[i] = 0;
     ms[0] = ms[1] = ms[2] = 0.0f;
     const int W = k.W, H = k.H;
     const uint32_t n = c->scene.n_tri;
     M2S_TRY(c->d_md_deferred.reserve(c->err, std::max<uint64_t>(n, 1), sizeof(uint32_t)));
-    hipEvent_t* ev = c->md_ev;
-    const bool prof = c->profiling;
-    if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    HIPCHK(c, clock.mark(MeshMark::Start, c->stream));
     if (vis) HIPCHK(c, meshvis_clear((unsigned long long*)image, W, H, c->stream));
     else HIPCHK(c, meshdepth_clear((float*)image, W, H, c->stream));       // glClear(GL_DEPTH_BUFFER_BIT): part of the pass
     HIPCHK(c, hipMemsetAsync(w.d_totals, 0, 8 * sizeof(unsigned long long), c->stream));
@@ -48,7 +47,7 @@ m2s_status mesh_raster(m2s_ctx* c, const MeshDepthK& k, bool vis, void* image, f
         if (vis) HIPCHK(c, meshvis_setup(k, c->scene, (unsigned long long*)image, c->d_md_deferred, w.d_totals, c->stream));
         else HIPCHK(c, meshdepth_setup(k, c->scene, (float*)image, c->d_md_deferred, w.d_totals, c->stream));
     }
-    if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, clock.mark(MeshMark::SetupEnd, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t nd = h_md[5];
@@ -58,7 +57,7 @@ m2s_status mesh_raster(m2s_ctx* c, const MeshDepthK& k, bool vis, void* image, f
         M2S_TRY(w.reserve_items(c->err, slots, 48));
         M2S_TRY(w.reserve_temp(c->err, meshdepth_temp_bytes((uint32_t)slots, 1)));
         const float4* rec = (const float4*)w.rec.get();
-        if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+        HIPCHK(c, clock.mark(MeshMark::Deferred, c->stream));
         HIPCHK(c, meshdepth_deferred(k, c->scene, c->d_md_deferred, (uint32_t)nd, (float4*)w.rec.get(), w.cnt, w.off, w.temp, w.temp.cap(), w.d_totals,
                                      c->stream, vis));
         HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -71,23 +70,21 @@ m2s_status mesh_raster(m2s_ctx* c, const MeshDepthK& k, bool vis, void* image, f
             M2S_TRY(w.reserve_temp(c->err, meshdepth_temp_bytes(1, (uint32_t)pairs)));
             HIPCHK(c, meshdepth_bin(k, rec, w.cnt, w.off, (uint32_t)nd, pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, w.temp,
                                     w.temp.cap(), c->stream));
-            if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+            HIPCHK(c, clock.mark(MeshMark::Binned, c->stream));
             if (vis) HIPCHK(c, meshvis_raster(k, rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, (unsigned long long*)image, w.d_totals, c->stream));
             else HIPCHK(c, meshdepth_raster(k, rec, pr.keys_out, pr.vals_out, (uint32_t)pairs, (float*)image, w.d_totals, c->stream));
-            if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
+            HIPCHK(c, clock.mark(MeshMark::Rastered, c->stream));
             HIPCHK(c, hipMemcpyAsync(h_md, w.d_totals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (prof) {
-                HIPCHK(c, hipEventElapsedTime(&ms[1], ev[2], ev[3]));
-                HIPCHK(c, hipEventElapsedTime(&ms[2], ev[3], ev[4]));
-            }
-        } else if (prof) {
-            HIPCHK(c, hipEventRecord(ev[3], c->stream));
+        } else if (clock.on()) {   // deferred triangles without pairs: the clipper ran, its span is closed here
+            HIPCHK(c, clock.mark(MeshMark::Binned, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipEventElapsedTime(&ms[1], ev[2], ev[3]));
         }
     }
-    if (prof) HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+    // (nothing deferred: [1] and [2] are 0; no pairs: [2] is)
+    HIPCHK(c, clock.span(MeshMark::Start, MeshMark::SetupEnd, &ms[0]));
+    HIPCHK(c, clock.span(MeshMark::Deferred, MeshMark::Binned, &ms[1]));
+    HIPCHK(c, clock.span(MeshMark::Binned, MeshMark::Rastered, &ms[2]));
     return M2S_OK;
 }
 
@@ -137,16 +134,8 @@ m2s_status m2s_download_mesh_depth(m2s_ctx* c, float* dst, uint64_t capacity_flo
 }
 
 float m2s_last_mesh_depth_ms(const m2s_ctx* c) { return c ? c->last_md_ms : 0.0f; }
-m2s_status m2s_last_mesh_depth_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_md_stage_ms, sizeof(c->last_md_stage_ms));
-    return M2S_OK;
-}
-m2s_status m2s_last_mesh_depth_counts(const m2s_ctx* c, uint64_t out[5]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 5; ++k) out[k] = c->last_md_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_mesh_depth_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_md_stage_ms, out_ms); }
+m2s_status m2s_last_mesh_depth_counts(const m2s_ctx* c, uint64_t out[5]) { return get_array(c, &m2s_ctx::last_md_counts, out); }
 
 m2s_status m2s_debug_set_mesh_depth_inplace(m2s_ctx* c, int32_t max_box) {
     if (!c) return M2S_ERR_INVALID;

@@ -42,7 +42,7 @@ m2s_status m2s_mesh_render(m2s_ctx* c, const m2s_mesh_render_params* p, uint64_t
     if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
     if (!c->has_scene) return fail(c, M2S_ERR_STATE, "no scene has been uploaded");
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->mr_ev.ensure(c->err));
+    M2S_TRY(c->mr_clock.begin(c->err, c->profiling));
     c->mr_w = c->mr_h = 0;
     for (uint64_t& v : c->last_mr_counts) v = 0;
     if (out_counts) for (int k = 0; k < 6; ++k) out_counts[k] = 0;
@@ -62,12 +62,12 @@ m2s_status m2s_mesh_render(m2s_ctx* c, const m2s_mesh_render_params* p, uint64_t
     normal_matrix(p->model_to_world, r.N);
     r.near_far[0] = p->near_far[0]; r.near_far[1] = p->near_far[1];
     r.W = W; r.H = H; r.mode = p->render_mode;
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->mr_ev[0], c->stream));
+    HIPCHK(c, c->mr_clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, meshrender_shade(r, c->scene, c->d_mr_vis, c->d_mr_gbuf.ptr, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->mr_ev[1], c->stream));
+    HIPCHK(c, c->mr_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) {
-        HIPCHK(c, hipEventElapsedTime(&ms[3], c->mr_ev[0], c->mr_ev[1]));
+    if (c->mr_clock.on()) {
+        HIPCHK(c, c->mr_clock.span(SpanMark::Begin, SpanMark::End, &ms[3]));
         std::memcpy(c->last_mr_stage_ms, ms, sizeof ms);
         c->last_mr_ms = (ms[0] + ms[1]) + (ms[2] + ms[3]);
     }
@@ -102,15 +102,7 @@ m2s_status m2s_download_mesh_visibility(m2s_ctx* c, uint64_t* dst, uint64_t capa
 }
 
 float m2s_last_mesh_render_ms(const m2s_ctx* c) { return c ? c->last_mr_ms : 0.0f; }
-m2s_status m2s_last_mesh_render_stage_ms(const m2s_ctx* c, float out_ms[4]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_mr_stage_ms, sizeof(c->last_mr_stage_ms));
-    return M2S_OK;
-}
-m2s_status m2s_last_mesh_render_counts(const m2s_ctx* c, uint64_t out[6]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 6; ++k) out[k] = c->last_mr_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_mesh_render_stage_ms(const m2s_ctx* c, float out_ms[4]) { return get_array(c, &m2s_ctx::last_mr_stage_ms, out_ms); }
+m2s_status m2s_last_mesh_render_counts(const m2s_ctx* c, uint64_t out[6]) { return get_array(c, &m2s_ctx::last_mr_counts, out); }
 
 }  // extern "C"

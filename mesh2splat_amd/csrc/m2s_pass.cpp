@@ -364,35 +364,31 @@ m2s_status ensure_lane(m2s_ctx* c, int L, bool multipass, uint32_t n_start) {
 }
 
 // enqueues the pipeline's kernels on `st` in lane L's work set, the counter written to *h_res (pinned) by k_count_scan's last
-// workgroup itself; no synchronisation.  prof: lane 0 only (the per-kernel events are the context's)
-m2s_status enqueue_multipass(m2s_ctx* c, int L, uint32_t R, float4* d_out, uint64_t limit, bool prof, unsigned long long* h_res, hipStream_t st) {
+// workgroup itself; no synchronisation.  marks: the conversion clock's where the caller reads its times (lane 0, synchronous), else none
+m2s_status enqueue_multipass(m2s_ctx* c, int L, uint32_t R, float4* d_out, uint64_t limit, const StageMarks& marks, unsigned long long* h_res, hipStream_t st) {
     const SceneDev& sc = c->scene;
     const Lane& ln = c->lane[L];
-    prof = prof && L == 0;
     uint32_t epoch;
     HIPCHK(c, next_epoch(c, &epoch));
-    if (prof) HIPCHK(c, hipEventRecord(c->ev[0], st));
+    HIPCHK(c, marks.mark((int)ConvMark::Count, st));
     launch_count_scan(sc, R, ln.off, ln.start, emit2_slices(limit), ln.chain, epoch, ln.total, ln.setup, reinterpret_cast<uint32_t*>(&h_res[1]),
                       &h_res[0], st);
-    if (prof) { HIPCHK(c, hipEventRecord(c->ev[1], st)); HIPCHK(c, hipEventRecord(c->ev[3], st)); }
+    HIPCHK(c, marks.mark((int)ConvMark::Counted, st)); HIPCHK(c, marks.mark((int)ConvMark::Emit, st));
     launch_emit2(sc, R, ln.off, ln.start, ln.total, limit, ln.setup, d_out, st);
-    if (prof) HIPCHK(c, hipEventRecord(c->ev[4], st));
+    HIPCHK(c, marks.mark((int)ConvMark::Emitted, st));
     HIPCHK(c, hipGetLastError());
     return M2S_OK;
 }
 }  // namespace m2s_host
 
 static m2s_status run_multipass(m2s_ctx* c, uint32_t R, float4* d_out, uint64_t limit, hipStream_t st) {
-    const bool prof = c->profiling;
     M2S_TRY(ensure_lane(c, 0, true, emit2_slices(limit)));
     c->h_total[0] = 0; c->h_total[1] = 0;
-    M2S_TRY(enqueue_multipass(c, 0, R, d_out, limit, prof, c->h_total, st));
+    M2S_TRY(enqueue_multipass(c, 0, R, d_out, limit, c->conv_clock.marks(), c->h_total, st));
     HIPCHK(c, wait_stream(st));  // glFinish + counter read-back (ConversionPass.cpp:54-59)
     if (c->h_total[1] >> 32) return fail(c, M2S_ERR_HIP, "multi-pass pipeline: look-back chain timed out");
-    if (prof) {
-        HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_COUNT], c->ev[0], c->ev[1]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_EMIT], c->ev[3], c->ev[4]));
-    }
+    HIPCHK(c, c->conv_clock.span(ConvMark::Count, ConvMark::Counted, &c->last_ms[M2S_K_COUNT]));
+    HIPCHK(c, c->conv_clock.span(ConvMark::Emit, ConvMark::Emitted, &c->last_ms[M2S_K_EMIT]));
     return M2S_OK;
 }
 
@@ -409,7 +405,8 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
     if (from_submit) drain_in_flight(c);
     const SceneDev& sc = c->scene;
     const uint64_t cap = resolve_cap(c, R);
-    const bool prof = c->profiling;
+    ClockOf<ConvMark>& clock = c->conv_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     c->conversion_started(R);
     memset(c->last_ms, 0, sizeof c->last_ms);
 
@@ -471,7 +468,7 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
             c->h_total[1] = 0;
             uint32_t epoch;
             HIPCHK(c, next_epoch(c, &epoch));
-            if (prof) HIPCHK(c, hipEventRecord(c->ev[5], st));
+            HIPCHK(c, clock.mark(ConvMark::Fused, st));
             const uint32_t unit = unit_of(ri.form);
             bool wrote_bands = false;
             const RunInfo runs = bands_for(c, ri, unit, true, &wrote_bands);
@@ -485,10 +482,10 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
             }
             wrote_plane = plane != nullptr;
             launch_single(c, ri, R, c->lane[0].chain, limit, d_out, c->h_total, epoch, runs, st, plane);
-            if (prof) HIPCHK(c, hipEventRecord(c->ev[6], st));
+            HIPCHK(c, clock.mark(ConvMark::FusedEnd, st));
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, wait_stream(st));  // glFinish + counter read-back (ConversionPass.cpp:54-59)
-            if (prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_FUSED], c->ev[5], c->ev[6]));
+            HIPCHK(c, clock.span(ConvMark::Fused, ConvMark::FusedEnd, &c->last_ms[M2S_K_FUSED]));
             const uint32_t any_big = (uint32_t)(c->h_total[1] & 0xFFFFFFFFull);
             const uint32_t err = (uint32_t)(c->h_total[1] >> 32);
             c->last_pipeline = ri.form;
@@ -535,12 +532,12 @@ m2s_status run_pass(m2s_ctx* c, uint32_t R, void* d_user, uint64_t user_cap, hip
                     continue;
                 }
                 // second stage: emit exactly the deferred triangles, one workgroup per 1024-fragment chunk
-                if (prof) HIPCHK(c, hipEventRecord(c->ev[3], st));
+                HIPCHK(c, clock.mark(ConvMark::Emit, st));
                 launch_emit_big(sc, R, c->d_biglist, meta[0], meta[1], limit, d_out, st);
-                if (prof) HIPCHK(c, hipEventRecord(c->ev[4], st));
+                HIPCHK(c, clock.mark(ConvMark::Emitted, st));
                 HIPCHK(c, hipGetLastError());
                 HIPCHK(c, hipStreamSynchronize(st));
-                if (prof) HIPCHK(c, hipEventElapsedTime(&c->last_ms[M2S_K_EMIT], c->ev[3], c->ev[4]));
+                HIPCHK(c, clock.span(ConvMark::Emit, ConvMark::Emitted, &c->last_ms[M2S_K_EMIT]));
             }
         }
         // unlimited policy, context-owned buffer: the prediction was too low — make room for the exact count and repeat

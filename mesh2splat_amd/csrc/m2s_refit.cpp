@@ -58,10 +58,10 @@ m2s_status m2s_refit_accumulate(m2s_ctx* c, const m2s_refit_params* p, const voi
     BinWork& w = c->splat_work;
     HIPCHK(c, refit_blend((const float4*)w.rec.get(), bins.vals, bins.ranges, bins.order, W, H, c->sq_src, (const uint32_t*)d_target,
                           (const uint32_t*)d_render, p->min_cover, refit_num(c), refit_den(c), w.d_totals + 3, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, c->bin_clock.mark(BinMark::Blended, c->stream));
     HIPCHK(c, hipMemcpyAsync(w.h_totals + 3, w.d_totals + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) M2S_TRY(splat_stage_ms(c, true, c->last_refit_stage_ms));
+    if (c->bin_clock.on()) M2S_TRY(splat_stage_ms(c, c->last_refit_stage_ms));
     if (out_counts) { out_counts[0] = w.h_totals[3]; out_counts[1] = bins.pairs; }
     return M2S_OK;
 }
@@ -101,14 +101,14 @@ m2s_status m2s_refit_apply(m2s_ctx* c, const m2s_refit_apply_params* p, uint64_t
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!refit_valid(c)) return fail(c, M2S_ERR_STATE, kNoRefitMsg);
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->refit_ev.ensure(c->err));
+    M2S_TRY(c->refit_apply_clock.begin(c->err, c->profiling));
     M2S_TRY(c->d_refit_counts.reserve(c->err, 3, sizeof(unsigned long long)));
     const uint64_t n = c->last_stored;
     const uint32_t R = c->last_R;
     const double dq = (double)p->min_weight_sum * 65536.0;
     const unsigned long long D = dq >= 9223372036854775808.0 ? ~0ull : (unsigned long long)std::llrint(dq);
     unsigned long long h[3] = { 0, 0, 0 };
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->refit_ev[0], c->stream));
+    HIPCHK(c, c->refit_apply_clock.mark(SpanMark::Begin, c->stream));
     if (n) {
         // the update happens in the pool: records that live elsewhere (uploaded, adopted, a second lane's) are copied there first
         if (c->last_records != c->lane[0].records) {
@@ -123,19 +123,15 @@ m2s_status m2s_refit_apply(m2s_ctx* c, const m2s_refit_apply_params* p, uint64_t
     } else {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
     }
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->refit_ev[1], c->stream));
+    HIPCHK(c, c->refit_apply_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_refit_apply_ms, c->refit_ev[0], c->refit_ev[1]));
+    if (c->refit_apply_clock.on()) HIPCHK(c, c->refit_apply_clock.span(SpanMark::Begin, SpanMark::End, &c->last_refit_apply_ms));
     c->rewritten(c->lane[0].records, n, R, Rewrite::RefitApply);   // (a plane of these records was baked from the old albedo: dropped)
     if (out_counts) { out_counts[0] = n; out_counts[1] = h[0]; out_counts[2] = h[1]; out_counts[3] = h[2]; }
     return M2S_OK;
 }
 
-m2s_status m2s_last_refit_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_refit_stage_ms, sizeof(c->last_refit_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_refit_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_refit_stage_ms, out_ms); }
 
 float m2s_last_refit_apply_ms(const m2s_ctx* c) { return c ? c->last_refit_apply_ms : 0.0f; }
 

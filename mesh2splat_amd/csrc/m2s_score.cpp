@@ -38,20 +38,20 @@ m2s_status m2s_score_frames(m2s_ctx* c, const m2s_score_params* p, const void* d
     constexpr size_t kWords = (size_t)kScoreShards * kScoreCounters;
     M2S_TRY(c->d_score_acc.reserve(c->err, kWords, sizeof(unsigned long long)));
     M2S_TRY(c->h_score.ensure(c->err, kWords * sizeof(unsigned long long)));
-    M2S_TRY(c->score_ev.ensure(c->err));
+    M2S_TRY(c->score_clock.begin(c->err, c->profiling));
     if (want_map) M2S_TRY(c->d_score_map.reserve(c->err, (uint64_t)W * (uint64_t)H, 4));
     ScoreK k;
     k.W = W; k.H = H;
     k.mask_mode = p->mask_mode;
     k.tiles_x = score_tiles(W);
     HIPCHK(c, hipMemsetAsync(c->d_score_acc, 0, kWords * sizeof(unsigned long long), c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->score_ev[0], c->stream));
+    HIPCHK(c, c->score_clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, launch_score(k, (const uint32_t*)d_a, (const uint32_t*)d_b, cover ? (const uint32_t*)d_cover_a : nullptr,
                            cover ? (const uint32_t*)d_cover_b : nullptr, want_map ? c->d_score_map.get() : nullptr, c->d_score_acc, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->score_ev[1], c->stream));
+    HIPCHK(c, c->score_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_score, c->d_score_acc, kWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_score_ms, c->score_ev[0], c->score_ev[1]));
+    if (c->score_clock.on()) HIPCHK(c, c->score_clock.span(SpanMark::Begin, SpanMark::End, &c->last_score_ms));
     // the shards are integers: their sum (max_abs: their maximum) does not depend on which workgroup added where
     unsigned long long t[kScoreCounters] = {};
     for (int s = 0; s < kScoreShards; ++s)

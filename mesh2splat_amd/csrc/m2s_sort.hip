@@ -175,10 +175,10 @@ size_t sort_temp_bytes(uint32_t n) {
 // Keys of the n records + their stable radix sort: vals_out = the permutation (record index of every sorted position), keys_out = the
 // sorted keys (minus *key_offset when the sort ran over the bits in which the keys differ).  mv == nullptr: key = view-space z by the
 // row view[2], view[6], view[10], view[14] (m2s_sort_by_depth); else the prepass's own depth bits (depth_key_mv).
-// plane: room for n float4 or nullptr; plane_valid: it already holds the positions of these records.  ev (or nullptr): events around the
-// key stage and the radix sort (ev[0], ev[1], ev[2]).  The values are the record indices: they come from a counting iterator, not from memory.
+// plane: room for n float4 or nullptr; plane_valid: it already holds the positions of these records.  marks: recorded around the
+// key stage and the radix sort (0, 1, 2).  The values are the record indices: they come from a counting iterator, not from memory.
 static hipError_t keys_and_sort(const float4* rec, uint32_t n, const float view[16], const DepthMVP* mv, uint32_t* keys_in, uint32_t* keys_out,
-                                uint32_t* vals_out, void* temp, size_t temp_bytes, float4* plane, bool plane_valid, hipEvent_t* ev, hipStream_t st,
+                                uint32_t* vals_out, void* temp, size_t temp_bytes, float4* plane, bool plane_valid, const m2s_host::StageMarks& marks, hipStream_t st,
                                 uint32_t* key_offset, uint32_t* pinned_mm /* mv && mv->cull: FOUR pinned words */, uint32_t* n_visible, bool* clash) {
     *key_offset = 0;
     if (n_visible) *n_visible = n;
@@ -195,7 +195,7 @@ static hipError_t keys_and_sort(const float4* rec, uint32_t n, const float view[
     hipError_t e = hipMemcpyAsync(minmax, init, sizeof init, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     const dim3 grid((n + kBlock - 1) / kBlock);
-    if (ev) (void)hipEventRecord(ev[0], st);
+    (void)marks.mark(0, st);
     const bool from_plane = plane && plane_valid;
     if (mv) hipLaunchKernelGGL(k_depth_keys_mv, grid, dim3(kBlock), 0, st, rec, from_plane ? (const float4*)plane : (const float4*)nullptr, n, *mv, keys_in,
                                from_plane ? (float4*)nullptr : plane, wave_mm, wave_cnt);
@@ -204,7 +204,7 @@ static hipError_t keys_and_sort(const float4* rec, uint32_t n, const float view[
     const dim3 fold(std::min<uint32_t>((n_waves + kBlock - 1) / kBlock, 256u));
     hipLaunchKernelGGL(k_reduce_minmax, fold, dim3(kBlock), 0, st, wave_mm, n_waves, minmax);
     if (cull) hipLaunchKernelGGL(k_reduce_counts, fold, dim3(kBlock), 0, st, wave_cnt, n_waves, minmax);
-    if (ev) (void)hipEventRecord(ev[1], st);
+    (void)marks.mark(1, st);
     // the keys' range decides how many radix passes the library makes: 8 (16) bytes come back to the host (one sync, ~15 us of a ~1.7 ms call)
     uint32_t mm_local[4] = { 0u, 0xFFFFFFFFu, n, 0u };
     uint32_t* mm = pinned_mm ? pinned_mm : mm_local;          // (pinned: the copy is a DMA the sync waits for, not a staged pageable copy)
@@ -214,7 +214,7 @@ static hipError_t keys_and_sort(const float4* rec, uint32_t n, const float view[
     if (cull) {
         if (n_visible) *n_visible = mm[2];
         if (clash) *clash = mm[3] != 0u;
-        if (mm[2] == 0u) { if (ev) (void)hipEventRecord(ev[2], st); return hipSuccess; }      // nothing survives: nothing to sort
+        if (mm[2] == 0u) { (void)marks.mark(2, st); return hipSuccess; }      // nothing survives: nothing to sort
     }
     const uint32_t range = mm[1] >= mm[0] ? mm[1] - mm[0] : 0xFFFFFFFFu;
     if (cull && range != 0xFFFFFFFFu) {
@@ -236,23 +236,23 @@ static hipError_t keys_and_sort(const float4* rec, uint32_t n, const float view[
         }
     }
     if (e != hipSuccess) return e;
-    if (ev) (void)hipEventRecord(ev[2], st);
+    (void)marks.mark(2, st);
     return hipSuccess;
 }
 
-// stage_ev (or nullptr): four events recorded around the three stages (keys | radix sort | gather).
+// marks: four, recorded around the three stages (keys | radix sort | gather).
 hipError_t sort_by_depth(const float4* rec, uint32_t n, const float view[16], uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out,
-                         void* temp, size_t temp_bytes, float4* sorted, float4* plane, bool plane_valid, hipEvent_t* stage_ev, hipStream_t st,
+                         void* temp, size_t temp_bytes, float4* sorted, float4* plane, bool plane_valid, const m2s_host::StageMarks& marks, hipStream_t st,
                          uint32_t* key_offset_out, uint32_t* pinned_mm) {
     if (key_offset_out) *key_offset_out = 0;
     if (!n) return hipSuccess;
     uint32_t key_offset = 0;
-    hipError_t e = keys_and_sort(rec, n, view, nullptr, keys_in, keys_out, vals_out, temp, temp_bytes, plane, plane_valid, stage_ev, st, &key_offset, pinned_mm,
+    hipError_t e = keys_and_sort(rec, n, view, nullptr, keys_in, keys_out, vals_out, temp, temp_bytes, plane, plane_valid, marks, st, &key_offset, pinned_mm,
                                  nullptr, nullptr);
     if (e != hipSuccess) return e;
     const size_t nq = (size_t)n * 6;
     hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((nq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rec, vals_out, n, sorted);
-    if (stage_ev) (void)hipEventRecord(stage_ev[3], st);
+    (void)marks.mark(3, st);
     if (key_offset_out) *key_offset_out = key_offset;            // keys_out holds key - offset (m2s_device_sorted_keys puts it back on demand)
     else launch_add_to_keys(keys_out, n, key_offset, st);
     return hipGetLastError();
@@ -267,7 +267,7 @@ hipError_t sort_by_depth(const float4* rec, uint32_t n, const float view[16], ui
 // *clash: a survivor's own key equals the marker of the culled ones (a NaN depth with an all-ones payload): call again without cull.
 hipError_t sort_prepass_permutation(const float4* rec, uint32_t n, const float model[16], const float view[16], const float proj[16], bool cull,
                                     uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, void* temp, size_t temp_bytes, float4* plane, bool plane_valid,
-                                    hipEvent_t* ev, hipStream_t st, uint32_t* pinned_mm4, uint32_t* n_visible, bool* clash) {
+                                    const m2s_host::StageMarks& marks, hipStream_t st, uint32_t* pinned_mm4, uint32_t* n_visible, bool* clash) {
     if (n_visible) *n_visible = n;
     if (clash) *clash = false;
     if (!n) return hipSuccess;
@@ -277,7 +277,7 @@ hipError_t sort_prepass_permutation(const float4* rec, uint32_t n, const float m
     memcpy(mv.P, proj, sizeof mv.P);
     mv.cull = cull ? 1u : 0u;
     uint32_t key_offset = 0;
-    const hipError_t e = keys_and_sort(rec, n, view, &mv, keys_in, keys_out, vals_out, temp, temp_bytes, plane, plane_valid, ev, st, &key_offset, pinned_mm4,
+    const hipError_t e = keys_and_sort(rec, n, view, &mv, keys_in, keys_out, vals_out, temp, temp_bytes, plane, plane_valid, marks, st, &key_offset, pinned_mm4,
                                        n_visible, clash);
     return e != hipSuccess ? e : hipGetLastError();
 }

@@ -15,24 +15,24 @@ m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H,
     const int tiles_x = (W + kSplatTile - 1) / kSplatTile, tiles_y = (H + kSplatTile - 1) / kSplatTile;
     const uint32_t n_tiles = (uint32_t)(tiles_x * tiles_y);
     HIPCHK(c, hipMemsetAsync(w.d_totals, 0, 4 * sizeof(unsigned long long), c->stream));
-    hipEvent_t* ev = c->ev;
-    const bool prof = c->profiling;
+    ClockOf<BinMark>& clock = c->bin_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     uint64_t pairs = 0;
     *out = SplatBins();
     if (nq) {
         // ---- setup: records, tile counts, their scan; the number of pairs read back once (the pair buffers are sized from it)
         M2S_TRY(w.reserve_items(c->err, nq, kSplatRecBytes));
         M2S_TRY(w.reserve_temp(c->err, splat_scan_temp_bytes(nq)));
-        if (prof) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, clock.mark(BinMark::Setup, c->stream));
         HIPCHK(c, splat_setup((const float4*)d_quads, nq, W, H, (float4*)w.rec.get(), w.cnt, w.off, w.temp, w.temp.cap(), w.d_totals, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+        HIPCHK(c, clock.mark(BinMark::SetupEnd, c->stream));
         HIPCHK(c, hipMemcpyAsync(w.h_totals, w.d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         pairs = w.h_totals[0];
         out->skipped = w.h_totals[1];
         if (pairs > 0x7FFFFFFFull) return fail(c, M2S_ERR_CAPACITY, "more than 2^31-1 (tile, quad) pairs");
     }
-    if (prof) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    HIPCHK(c, clock.mark(BinMark::Pairs, c->stream));
     out->pairs = pairs;
     if (pairs) {
         BinWork::Pairs pr;
@@ -45,22 +45,22 @@ m2s_status splat_bin(m2s_ctx* c, const void* d_quads, uint32_t nq, int W, int H,
         uint32_t* len_sorted = len + tc;
         uint32_t* ord = len_sorted + tc;
         HIPCHK(c, splat_pairs((const float4*)w.rec.get(), w.cnt, w.off, nq, tiles_x, pr.keys_in, pr.vals_in, c->stream));
-        if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+        HIPCHK(c, clock.mark(BinMark::Paired, c->stream));
         HIPCHK(c, splat_group(pr.keys_in, pr.vals_in, pr.keys_out, pr.vals_out, (uint32_t)pairs, n_tiles, rg, len, len_sorted, ord, w.temp,
                               w.temp.cap(), c->stream));
         out->vals = pr.vals_out; out->ranges = rg; out->order = ord;
-    } else if (prof) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(ev[4], c->stream));
+    } else HIPCHK(c, clock.mark(BinMark::Paired, c->stream));   // (no pairs: both spans close around nothing, small and not 0, as they always have)
+    HIPCHK(c, clock.mark(BinMark::Grouped, c->stream));
     return M2S_OK;
 }
 
-m2s_status splat_stage_ms(m2s_ctx* c, bool any_quads, float out[3]) {
-    hipEvent_t* ev = c->ev;
+m2s_status splat_stage_ms(m2s_ctx* c, float out[3]) {
+    const ClockOf<BinMark>& clock = c->bin_clock;
     float a = 0, b = 0, g = 0, bl = 0;
-    if (any_quads) HIPCHK(c, hipEventElapsedTime(&a, ev[0], ev[1]));
-    HIPCHK(c, hipEventElapsedTime(&b, ev[2], ev[3]));
-    HIPCHK(c, hipEventElapsedTime(&g, ev[3], ev[4]));
-    HIPCHK(c, hipEventElapsedTime(&bl, ev[4], ev[5]));
+    HIPCHK(c, clock.span(BinMark::Setup, BinMark::SetupEnd, &a));      // (0 without quads: no setup ran)
+    HIPCHK(c, clock.span(BinMark::Pairs, BinMark::Paired, &b));
+    HIPCHK(c, clock.span(BinMark::Paired, BinMark::Grouped, &g));
+    HIPCHK(c, clock.span(BinMark::Grouped, BinMark::Blended, &bl));
     out[0] = a + b; out[1] = g; out[2] = bl;
     return M2S_OK;
 }
@@ -110,18 +110,16 @@ m2s_status m2s_splat(m2s_ctx* c, const m2s_splat_params* p, const void* d_quads,
     const uint32_t* vals = bins.vals;
     const uint2* ranges = bins.ranges;
     const uint32_t* order = bins.order;
-    hipEvent_t* ev = c->ev;
-    const bool prof = c->profiling;
     // ---- blend: every tile writes its 16 x 16 pixels of all five planes once (tiles without quads write the cleared values)
     BinWork& w = c->splat_work;
     HIPCHK(c, splat_blend((const float4*)w.rec.get(), vals, ranges, order, W, H, p->render_mode, c->d_gbuf.ptr, w.d_totals + 2, c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(ev[5], c->stream));
+    HIPCHK(c, c->bin_clock.mark(BinMark::Blended, c->stream));
     HIPCHK(c, hipMemcpyAsync(w.h_totals + 2, w.d_totals + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->last_splat_counts[0] = pairs;
     c->last_splat_counts[1] = w.h_totals[2];
-    if (prof) {
-        if (m2s_status s = splat_stage_ms(c, nq != 0, c->last_splat_stage_ms)) return s;
+    if (c->bin_clock.on()) {
+        M2S_TRY(splat_stage_ms(c, c->last_splat_stage_ms));
         c->last_splat_ms = (c->last_splat_stage_ms[0] + c->last_splat_stage_ms[1]) + c->last_splat_stage_ms[2];
     }
     c->gbuf_w = W;
@@ -145,16 +143,8 @@ m2s_status m2s_download_gbuffer(m2s_ctx* c, uint32_t attachment, void* dst, uint
 
 float m2s_last_splat_ms(const m2s_ctx* c) { return c ? c->last_splat_ms : 0.0f; }
 
-m2s_status m2s_last_splat_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    std::memcpy(out_ms, c->last_splat_stage_ms, sizeof(c->last_splat_stage_ms));
-    return M2S_OK;
-}
+m2s_status m2s_last_splat_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_splat_stage_ms, out_ms); }
 
-m2s_status m2s_last_splat_counts(const m2s_ctx* c, uint64_t out[3]) {
-    if (!c || !out) return M2S_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) out[k] = c->last_splat_counts[k];
-    return M2S_OK;
-}
+m2s_status m2s_last_splat_counts(const m2s_ctx* c, uint64_t out[3]) { return get_array(c, &m2s_ctx::last_splat_counts, out); }
 
 }  // extern "C"

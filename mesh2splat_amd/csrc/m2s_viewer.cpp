@@ -49,15 +49,17 @@ m2s_status m2s_sort_by_depth(m2s_ctx* c, const float world_to_view[16], uint64_t
     M2S_TRY(c->d_sorted.reserve(c->err, n, sizeof(m2s_gaussian)));
     M2S_TRY(reserve_sort(c, n, sort_temp_bytes((uint32_t)n), true));
     const bool plane_valid = positions_valid(c, n);
+    ClockOf<SortMark>& clock = c->sort_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
     uint32_t* u = c->d_sort_u32;     // keys_in | (unused) | keys_out | vals_out
     HIPCHK(c, sort_by_depth((const float4*)c->last_records, (uint32_t)n, world_to_view, u, u + 2 * n, u + 3 * n, c->d_sort_temp,
-                            c->d_sort_temp.cap(), c->d_sorted, c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream,
+                            c->d_sort_temp.cap(), c->d_sorted, c->d_pos_plane, plane_valid, clock.marks(), c->stream,
                             &c->sorted_key_offset, reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM])));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->d_pos_plane) c->pos_plane_tag.set(*c, n);
-    if (c->profiling) {
-        for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventElapsedTime(&c->last_sort_stage_ms[k], c->ev[k], c->ev[k + 1]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_sort_ms, c->ev[0], c->ev[3]));
+    if (clock.on()) {
+        for (int k = 0; k < 3; ++k) HIPCHK(c, clock.span(k, k + 1, &c->last_sort_stage_ms[k]));
+        HIPCHK(c, clock.span(SortMark::Start, SortMark::Gathered, &c->last_sort_ms));
     }
     c->sorted_n = n;
     return M2S_OK;
@@ -93,11 +95,7 @@ m2s_status m2s_download_sorted(m2s_ctx* c, m2s_gaussian* dst, uint64_t capacity_
 }
 
 float m2s_last_sort_ms(const m2s_ctx* c) { return c ? c->last_sort_ms : 0.0f; }
-m2s_status m2s_last_sort_stage_ms(const m2s_ctx* c, float out_ms[3]) {
-    if (!c || !out_ms) return M2S_ERR_INVALID;
-    memcpy(out_ms, c->last_sort_stage_ms, sizeof c->last_sort_stage_ms);
-    return M2S_OK;
-}
+m2s_status m2s_last_sort_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_sort_stage_ms, out_ms); }
 
 // GaussiansPrepass::execute (GaussiansPrepass.cpp:8-56) + the counter read-back that follows it (RadixSortPass.cpp:18-22).
 // sorted = m2s_prepass_sorted: the depth sort of RadixSortPass::execute taken FIRST, as a permutation of the records by the depth bits this
@@ -119,6 +117,10 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     if (!sorted) M2S_TRY(c->d_quads.reserve(c->err, n, sizeof(m2s_quad)));
     M2S_TRY(c->d_pp_depths.reserve(c->err, n, sizeof(float)));
     const uint32_t* perm = nullptr;
+    // the plain prepass has a clock of its own; the sorted one chains its two marks behind the sort's
+    M2S_TRY(sorted ? c->sort_clock.begin(c->err, c->profiling) : c->prepass_clock.begin(c->err, c->profiling));
+    const StageMarks sort_marks = sorted ? c->sort_clock.marks() : StageMarks();
+    const StageMarks pp_marks = sorted ? c->sort_clock.marks(SortMark::Gathered) : c->prepass_clock.marks();
     if (sorted) {   // room for the sorted survivors, the keys / permutation, the radix sort's work area and the position plane
         M2S_TRY(c->d_sorted_quads.reserve(c->err, n, sizeof(m2s_quad)));
         M2S_TRY(reserve_sort(c, n, sort_temp_bytes((uint32_t)n), true));
@@ -158,12 +160,12 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         uint32_t* pinned4 = reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM]);
         bool cull = k.depth_test == 0u, clash = false;
         HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, cull, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
-                                           c->d_pos_plane, plane_valid, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
+                                           c->d_pos_plane, plane_valid, sort_marks, c->stream, pinned4, &n_run, &clash));
         if (c->d_pos_plane) c->pos_plane_tag.set(*c, n);
         if (cull && clash) {   // a survivor whose depth bits ARE the marker of the culled ones (a NaN with that payload): sort everything, compact in the prepass
             cull = false;
             HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, false, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
-                                               c->d_pos_plane, true, c->profiling ? c->ev : nullptr, c->stream, pinned4, &n_run, &clash));
+                                               c->d_pos_plane, true, sort_marks, c->stream, pinned4, &n_run, &clash));
         }
         dense = cull;
         perm = u + 3 * n;
@@ -172,19 +174,23 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         if (!dense && n_run) M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
     }
     uint32_t* src_out = sorted && !dense ? c->d_sq_src.get() : nullptr;
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+    HIPCHK(c, pp_marks.mark(0, c->stream));
     if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, sorted ? c->d_sorted_quads.get() : c->d_quads.get(), c->d_pp_depths, c->d_pp_chain + 1,
                                         epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense, src_out));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(c, pp_marks.mark(1, c->stream));
     if (k.arrival_order) HIPCHK(c, hipMemcpyAsync(&res[0], c->d_pp_chain, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) {
-        HIPCHK(c, hipEventElapsedTime(&c->last_prepass_ms, c->ev[3], c->ev[4]));
-        if (sorted) {
-            for (int j = 0; j < 2; ++j) HIPCHK(c, hipEventElapsedTime(&c->last_sort_stage_ms[j], c->ev[j], c->ev[j + 1]));
+    // (only the clock this call opened is read: the other one holds an earlier call's marks)
+    if (sorted) {
+        const ClockOf<SortMark>& clock = c->sort_clock;
+        if (clock.on()) {
+            HIPCHK(c, clock.span(SortMark::Gathered, SortMark::Prepassed, &c->last_prepass_ms));
+            for (int j = 0; j < 2; ++j) HIPCHK(c, clock.span(j, j + 1, &c->last_sort_stage_ms[j]));
             c->last_sort_stage_ms[2] = c->last_prepass_ms;
-            HIPCHK(c, hipEventElapsedTime(&c->last_sort_ms, c->ev[0], c->ev[4]));
+            HIPCHK(c, clock.span(SortMark::Start, SortMark::Prepassed, &c->last_sort_ms));
         }
+    } else if (c->prepass_clock.on()) {
+        HIPCHK(c, c->prepass_clock.span(SpanMark::Begin, SpanMark::End, &c->last_prepass_ms));
     }
     if (reinterpret_cast<uint32_t*>(&res[1])[1] == 2u) return fail(c, M2S_ERR_HIP, "prepass_sorted: the sort's frustum test and the prepass's disagree (internal error)");
     if (reinterpret_cast<uint32_t*>(&res[1])[1]) return fail(c, M2S_ERR_HIP, "prepass: look-back chain timed out");
@@ -235,11 +241,13 @@ m2s_status m2s_sort_prepass(m2s_ctx* c, uint64_t* out_n) {
     M2S_TRY(c->d_sorted_quads.reserve(c->err, n, sizeof(m2s_quad)));
     M2S_TRY(reserve_sort(c, n, sort_prepass_temp_bytes((uint32_t)n), false));
     uint32_t* u = c->d_sort_u32;
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    ClockOf<SpanMark>& clock = c->sort_prepass_clock;
+    M2S_TRY(clock.begin(c->err, c->profiling));
+    HIPCHK(c, clock.mark(SpanMark::Begin, c->stream));
     HIPCHK(c, sort_prepass(c->d_pp_depths, c->d_quads, (uint32_t)n, u, u + n, c->d_sort_temp, c->d_sort_temp.cap(), c->d_sorted_quads, c->stream));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(c, clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_sort_prepass_ms, c->ev[0], c->ev[1]));
+    if (clock.on()) HIPCHK(c, clock.span(SpanMark::Begin, SpanMark::End, &c->last_sort_prepass_ms));
     c->sq_n = n;
     return M2S_OK;
 }

@@ -17,8 +17,8 @@ m2s_status m2s_records_to_world_units(m2s_ctx* c, uint32_t* out_previous_R) {
     if (out_previous_R) *out_previous_R = R;
     if (R <= 1) return M2S_OK;                  // world units already (uploaded records: taken as R = 1): nothing of the context changes
     HIPCHK(c, hipSetDevice(c->device));
-    M2S_TRY(c->wu_ev.ensure(c->err));
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->wu_ev[0], c->stream));
+    M2S_TRY(c->wu_clock.begin(c->err, c->profiling));
+    HIPCHK(c, c->wu_clock.mark(SpanMark::Begin, c->stream));
     if (n) {
         // the pool holds the result: records that live elsewhere (adopted, a second lane's) are divided on their way there
         const float4* src = (const float4*)c->last_records;
@@ -27,10 +27,9 @@ m2s_status m2s_records_to_world_units(m2s_ctx* c, uint32_t* out_previous_R) {
     } else {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
     }
-    if (c->profiling) HIPCHK(c, hipEventRecord(c->wu_ev[1], c->stream));
+    HIPCHK(c, c->wu_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->last_world_units_ms = 0.0f;
-    if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->last_world_units_ms, c->wu_ev[0], c->wu_ev[1]));
+    HIPCHK(c, c->wu_clock.span(SpanMark::Begin, SpanMark::End, &c->last_world_units_ms));   // (0 without profiling)
     c->rewritten(c->lane[0].records, n, 1, Rewrite::WorldUnits);
     return M2S_OK;
 }
