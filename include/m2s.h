@@ -611,11 +611,26 @@ float m2s_last_refit_apply_ms(const m2s_ctx* ctx);
  *       normal.xyz = the normalised sum w_i normal_i, all zeros where the sum is zero or not finite; normal[3], pbr[2], pbr[3] are the
  *       first member's; pbr[0..1] = sum w_i pbr_i / W.
  *     (Plain moment matching of the rendered Gaussians' covariances is NOT this: it shrinks a 2 x 2 block to 0.82 h where 1.3 h is needed.)
+ *  5s. The baked SH plane (tests/merge_sh_ref.py restates it).  With m2s_set_carry_sh on, a call that is no dry run, and a plane of
+ *     exactly the current n records (a bake of them, m2s_upload_sh, or what an earlier call under this pin left):
+ *     5s.1 Segments are pin 3's (pin 2u's with M2S_MERGE_UNSIGNED_AXIS), unchanged: the plane is never read by the heads.  SH has no axis
+ *          sign to lose, so 5s is the same under both rules.
+ *     5s.2 A segment of one member: its 48 floats are copied bit for bit.  Invalid records are such segments.
+ *     5s.3 A segment of members i = 1..m >= 2 in sorted order, every product and sum in fp64 from the stored floats, in member order:
+ *          w_i = sx_i sy_i, W = sum w_i; where W == 0, w_i = 1 for every member and W = m (pin 5's own test, the same value);
+ *          a_i = w_i alpha_i, A = sum a_i; for k = 0..47: sh'_k = (float)(sum a_i sh_ik / A) where A != 0, else
+ *          (float)(sum w_i sh_ik / W) — the selector pin 5 uses for rgb; one rounding to fp32 per coefficient.  All 48 columns are
+ *          merged whatever the bake's degree: those above it are zero and stay zero for finite weights.  The colour 0.5 + sum_k sh_k
+ *          B_k(dir) is linear in the coefficients, so the parent's colour in every direction is the same weighted mean of its
+ *          members' colours in that direction that pin 5 takes of rgb.
+ *     5s.4 Afterwards the context is as pin 7 leaves it, except for the plane: it is the parents' plane, in segment order, valid for the
+ *          n' parents, its degree kept, its tap counts gone (as after a prune that compacts a plane).
+ *     5s.5 Switch off, no such plane, or a dry run: nothing of this happens — the bytes, the invalidation and the plane dropped are pin 7's.
  *  6. Output order is segment order: the canonical (mesh, triangle, row, column) order of a conversion is gone afterwards.
  *  7. Effect on the context, as m2s_prune: the parents are written into the context-owned pool (through a staging buffer where the
  *     sources live there; adopted memory is never written), the resolutionTarget is kept, the records epoch advances; cached positions,
- *     sorted quads, sources, the contribution and refit accumulators and a baked SH plane (as by m2s_refit_apply: it is not merged)
- *     are invalidated.  With M2S_MERGE_DRY_RUN nothing of the context changes: only the counts are produced.
+ *     sorted quads, sources, the contribution and refit accumulators and a baked SH plane (as by m2s_refit_apply: it is not merged
+ *     — unless pin 5s applies) are invalidated.  With M2S_MERGE_DRY_RUN nothing of the context changes: only the counts are produced.
  *  8. out_counts (may be NULL): [0] records before, [1] records after, [2] segments with two members or more, [3] invalid records
  *     carried.  The counts are monotone in level (a coarser cell only removes run breaks).
  * With M2S_MERGE_UNSIGNED_AXIS the sign of r_3 carries no meaning, as it carries none for the viewer (its covariance is
@@ -648,6 +663,12 @@ m2s_status m2s_merge(m2s_ctx* ctx, const m2s_merge_params* params, uint64_t out_
  * (0 for a dry run). */
 m2s_status m2s_last_merge_counts(const m2s_ctx* ctx, uint64_t out[4]);
 m2s_status m2s_last_merge_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+/* The switch of pins 5s (m2s_merge), 4s (m2s_lod_build) and 3s (the cuts): a baked SH plane of the records is carried through them
+ * instead of dropped.  Off by default; with it off every entry point behaves as it did before the switch existed.  m2s_carry_sh: 1 / 0.
+ * m2s_last_merge_sh_ms: the SH reduction of the last m2s_merge (ms; 0 where none ran); it lies inside stage [2] above. */
+m2s_status m2s_set_carry_sh(m2s_ctx* ctx, int enabled);
+int m2s_carry_sh(const m2s_ctx* ctx);
+float m2s_last_merge_sh_ms(const m2s_ctx* ctx);
 /* The map of the last merge that was not a dry run: a uint32 per record of the order before it, the index of its parent in the order
  * after it.  Valid until the records change again (NULL / M2S_ERR_STATE then); the maps of a chain of merges compose into a hierarchy.
  * m2s_download_merge_map: *out_n (may be NULL) = its entries; dst NULL with capacity 0 only asks for that; M2S_ERR_CAPACITY for a
@@ -668,6 +689,11 @@ m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity
  *     sort of the next step arrives at the same sequence either way, so the levels above are the same bytes.)
  *  4. Bounds.  Every node also has a 16-byte entry (x, y, z, e): position[0..2] and e = fmaxf(fabsf(scale[0]), fabsf(scale[1])), the
  *     longer edge of the flat footprint m2s_merge reads a record as.  The cut reads this plane, never the 96-byte records.
+ *  4s. The SH plane.  With m2s_set_carry_sh on and a baked plane of the current records at the build, the tree also owns
+ *     float[nodes][48]: the leaves' rows copied in leaf order, and behind them the rows pin 5s of m2s_merge made for every step that
+ *     merged (a step that merges nothing adds none); the tree remembers the plane's degree.  Afterwards the context's plane is the last
+ *     level's, or untouched where no step merged.  A tree built otherwise has no plane.  The plane costs 192 bytes per node beside the
+ *     116 of the other three: 2.4 GB for a tree of 12.68 M nodes, 0.8 GB for one of 4.23 M.
  *  5. Afterwards.  Where a step merged, the context's current records are the last level — what the chain left, in the context-owned
  *     pool — with everything m2s_merge invalidates invalid; where none did they are untouched.  The tree is a copy: it stays valid until
  *     the next m2s_lod_build (one refused for its arguments or the context's state leaves it; one that fails later leaves no tree),
@@ -700,7 +726,12 @@ m2s_status m2s_lod_levels(const m2s_ctx* ctx, uint32_t* out_levels, uint64_t fir
  * destination of fewer bytes than the plane. */
 const void* m2s_device_lod(const m2s_ctx* ctx, uint32_t which);
 m2s_status m2s_download_lod(m2s_ctx* ctx, uint32_t which, void* dst, uint64_t capacity_bytes);
-/* Frees the tree (M2S_OK without one too).  The current records are not touched. */
+/* The tree's SH plane (pin 4s), float[nodes][48] in node order.  m2s_device_lod_sh: NULL without a tree, without a plane, for an empty
+ * tree.  m2s_download_lod_sh: the errors of m2s_download_lod (capacity in rows), M2S_ERR_STATE for a tree without a plane;
+ * *out_degree (may be NULL) = the plane's degree. */
+const void* m2s_device_lod_sh(const m2s_ctx* ctx);
+m2s_status m2s_download_lod_sh(m2s_ctx* ctx, float* dst, uint64_t capacity_rows, uint32_t* out_degree);
+/* Frees the tree, its SH plane included (M2S_OK without one too).  The current records are not touched. */
 m2s_status m2s_lod_release(m2s_ctx* ctx);
 /* Duration (ms) of the last m2s_lod_build, its merges and host round trips included. */
 float m2s_last_lod_build_ms(const m2s_ctx* ctx);
@@ -720,6 +751,11 @@ float m2s_last_lod_build_ms(const m2s_ctx* ctx);
  *     into the context-owned pool.  They become the context's current records at the leaves' resolutionTarget; the records epoch
  *     advances, everything m2s_prune invalidates is invalid, and a baked SH plane is dropped.  Memory adopted through m2s_set_records
  *     is not written.  The tree is not changed.
+ *  3s. Where the tree has an SH plane (pin 4s of the tree) and the call is no dry run, the rows of the selected nodes go into the
+ *     context's plane instead, compacted in the same node-index order by the same flags and offsets as the records: the plane is valid
+ *     for the selected records, its degree is the tree's, it has no tap counts.  Zero selected nodes under a frustum give an empty
+ *     plane, which is valid.  m2s_lod_select, m2s_lod_select_budget and their _frustum forms behave alike.  The tree's property
+ *     decides, not m2s_set_carry_sh at the time of the cut; a tree without a plane cuts exactly as pin 3 says.
  *  4. out_counts (may be NULL): [0] nodes, [1] selected, [2] selected leaves, [3] nodes with `refine` (whatever their ancestors do).
  *     Integer sums, identical from run to run.
  *  5. With M2S_LOD_DRY_RUN only the counts are produced: nothing of the context changes.
@@ -1208,6 +1244,13 @@ m2s_status m2s_bake_directions(uint32_t n_theta, uint32_t n_phi, float* out, uin
 /* The plane of the last m2s_bake_light: float[n][48] on the device.  NULL before any. */
 const void* m2s_device_sh(const m2s_ctx* ctx);
 m2s_status m2s_download_sh(m2s_ctx* ctx, float* dst, uint64_t capacity_records);
+/* A plane made elsewhere (host float[n][48], the layout of m2s_download_sh, of this degree 0..3) becomes the context's plane of its
+ * current records, without tap counts: what loaded records need in front of m2s_merge / m2s_lod_build with m2s_set_carry_sh.
+ * M2S_ERR_INVALID: degree > 3, n != the stored records, NULL with n > 0.  M2S_ERR_STATE: no records, stale records, conversions in flight. */
+m2s_status m2s_upload_sh(m2s_ctx* ctx, const float* host, uint64_t n, uint32_t degree);
+/* The rows and the degree of the context's plane (either pointer may be NULL), whoever left it: a bake, m2s_upload_sh, a prune, and with
+ * m2s_set_carry_sh a merge or a cut.  M2S_ERR_STATE without a plane. */
+m2s_status m2s_sh_plane_info(const m2s_ctx* ctx, uint64_t* rows, uint32_t* degree);
 /* uint8[n]: the tap counts of the last m2s_bake_light (want_shadow_counts); M2S_ERR_STATE otherwise. */
 m2s_status m2s_download_bake_shadow_counts(m2s_ctx* ctx, uint8_t* dst, uint64_t capacity_bytes);
 /* Duration (ms) of the last profiled m2s_bake_light kernel. */

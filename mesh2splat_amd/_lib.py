@@ -61,6 +61,7 @@ EXPORTS = (
     "m2s_records_to_world_units", "m2s_last_world_units_ms",
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
+    "m2s_set_carry_sh", "m2s_carry_sh", "m2s_upload_sh", "m2s_sh_plane_info", "m2s_device_lod_sh", "m2s_download_lod_sh", "m2s_last_merge_sh_ms",
 )
 
 
@@ -312,6 +313,13 @@ def load():
         "m2s_last_compact_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_vertex_table": (C.c_int, [vp, C.POINTER(u64), C.POINTER(C.c_int)]),
         "m2s_geo_planes": (C.c_int, [vp, C.POINTER(u64), C.POINTER(C.c_int)]),
+        "m2s_set_carry_sh": (C.c_int, [vp, C.c_int]),
+        "m2s_carry_sh": (C.c_int, [vp]),
+        "m2s_upload_sh": (C.c_int, [vp, vp, u64, u32]),
+        "m2s_sh_plane_info": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u32)]),
+        "m2s_device_lod_sh": (vp, [vp]),
+        "m2s_download_lod_sh": (C.c_int, [vp, vp, u64, C.POINTER(u32)]),
+        "m2s_last_merge_sh_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -636,10 +636,41 @@ class Converter:
         return sh
 
     def download_sh(self) -> np.ndarray:
-        """The plane of the last bake_light(): (n, 48) float32 — f_dc[3], then f_rest[45] channel-major."""
-        sh = np.empty((self._last_bake_n, 48), np.float32)
+        """The context's SH plane: (n, 48) float32 — f_dc[3], then f_rest[45] channel-major.  It is the last bake_light()'s, or what
+        upload_sh(), a prune and, with carry_sh, a merge or a cut have made of it since (sized by sh_plane_info())."""
+        rows = C.c_uint64()
+        if self._L.m2s_sh_plane_info(self._h, C.byref(rows), None) == _lib.M2S_OK:
+            n = int(rows.value)
+        else:
+            n = self._last_bake_n
+        sh = np.empty((n, 48), np.float32)
         self._check(self._L.m2s_download_sh(self._h, sh.ctypes.data if sh.size else None, sh.shape[0]))
         return sh
+
+    @property
+    def carry_sh(self) -> bool:
+        """m2s_set_carry_sh: merge(), lod_build() and the cuts carry a baked SH plane of the records instead of dropping it.  Off by
+        default."""
+        return bool(self._L.m2s_carry_sh(self._h))
+
+    @carry_sh.setter
+    def carry_sh(self, on: bool):
+        self._check(self._L.m2s_set_carry_sh(self._h, 1 if on else 0))
+
+    def upload_sh(self, sh, degree: int = 3):
+        """m2s_upload_sh: `sh` (n, 48) float32, n the context's stored records, becomes their SH plane of this degree (no tap counts)."""
+        sh = np.ascontiguousarray(sh, np.float32)
+        if sh.ndim != 2 or sh.shape[1] != 48:
+            raise ValueError("sh must be (n, 48) float32")
+        self._check(self._L.m2s_upload_sh(self._h, sh.ctypes.data if sh.size else None, sh.shape[0], int(degree)))
+
+    def sh_plane_info(self) -> dict:
+        """m2s_sh_plane_info -> {"rows", "degree"} of the context's SH plane; M2SError (M2S_ERR_STATE) without one."""
+        rows, degree = C.c_uint64(), C.c_uint32()
+        st = self._L.m2s_sh_plane_info(self._h, C.byref(rows), C.byref(degree))
+        if st:
+            raise _lib.M2SError(st, "the context has no SH plane (bake_light, upload_sh)")
+        return {"rows": int(rows.value), "degree": int(degree.value)}
 
     @property
     def device_sh(self) -> int:
@@ -962,6 +993,8 @@ class Converter:
         counts are produced.  max_group = 4 and min_axis_dot = 0.5 are untuned guesses.  unsigned_axis (M2S_MERGE_UNSIGNED_AXIS): the sign
         of the third axis carries no meaning, as for the viewer — a run breaks where |dot| is below min_axis_dot and the members' axes
         are turned onto one side before they are averaged; a conversion stores the two triangles of a flat quad with opposite signs.
+        With carry_sh on and an SH plane of the records, the plane is merged too (pin 5s: the alpha-and-area-weighted mean of every
+        coefficient, the rule of the colour) and stays valid for the parents; last_merge_sh_ms is what that cost.
         -> {"before", "after", "merged": parents of two members or more, "invalid": invalid records carried}."""
         from . import merge as _mg
         pc = _mg.to_c(level, max_group, min_axis_dot, dry_run, unsigned_axis)
@@ -1006,6 +1039,11 @@ class Converter:
         return {"keys_sort": float(ms[0]), "heads_scans": float(ms[1]), "reduce": float(ms[2])}
 
     @property
+    def last_merge_sh_ms(self) -> float:
+        """The SH reduction of the last merge() (ms; 0.0 where none ran): a part of last_merge_stage_ms()["reduce"]."""
+        return float(self._L.m2s_last_merge_sh_ms(self._h))
+
+    @property
     def device_merge_map(self) -> int:
         return int(self._L.m2s_device_merge_map(self._h) or 0)
 
@@ -1025,6 +1063,8 @@ class Converter:
         are the leaves, and step s merges what the previous step left at merge level levels[s] (0..10, non-decreasing, at most 16) with
         merge()'s max_group, min_axis_dot and unsigned_axis; every step that merges something adds a tree level.  The coarsest level is the context's
         records afterwards; the tree is a copy and outlives them.  The default chain is an untuned guess, like max_group and min_axis_dot.
+        With carry_sh on and an SH plane of the records, the tree also owns a plane of its nodes (download_lod_sh; 192 bytes per node)
+        and every cut through it leaves the selected nodes' rows as the context's plane; a tree built otherwise has none.
         -> {"leaves", "nodes", "levels": tree levels, the leaves included, "skipped": steps that merged nothing, "first": first node of
         every level and the node count behind them}."""
         from . import lod as _ld
@@ -1057,7 +1097,9 @@ class Converter:
         of tan(angle) (mesh2splat_amd.lod.focal_px, .camera_position): walking down from the coarsest level, a node is drawn as soon as
         its longer edge projects to at most tau_px pixels at its distance from the camera (at least `near`), or it is a leaf
         (m2s_lod_select; the pin is in include/m2s.h).  Every leaf is covered exactly once.  The selected nodes become the context's
-        records, in node order; sorted quads, accumulators and a baked SH plane are invalid.  dry_run: only the counts.
+        records, in node order; sorted quads, accumulators and a baked SH plane are invalid — unless the tree was built with carry_sh
+        and has a plane: the selected nodes' rows are then the context's SH plane (download_sh, render_baked, export_ply_sh work on
+        the cut), whatever carry_sh says at the time of the cut.  dry_run: only the counts.
         -> {"nodes", "selected", "selected_leaves", "refine", "per_level": selected nodes of every tree level}.
         frustum (a mesh2splat_amd.lod.LodFrustumC: lod.frustum_to_c, lod.frustum_of): only nodes with a leaf inside it are selected
         (m2s_lod_select_frustum), possibly none; the dict then also has "visible_leaves" and "culled", the nodes the plain cut selects
@@ -1082,7 +1124,7 @@ class Converter:
         """Take the finest cut of lod_select() that holds at most `max_records` records for this camera, never finer than tau_min_px: the
         tau_px is found on the device, without a bisection on the host (m2s_lod_select_budget; the pin is in include/m2s.h).  A budget
         below the size of the coarsest level returns that level, with "met" False.  Everything else is lod_select()'s at the returned
-        tau_px.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
+        tau_px, the SH plane of a tree built with carry_sh included.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
         next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}.
         frustum: as for lod_select(); the budget is then spent on the nodes the camera sees (m2s_lod_select_budget_frustum)."""
         from . import lod as _ld
@@ -1114,6 +1156,19 @@ class Converter:
 
     def device_lod(self, which: int) -> int:
         return int(self._L.m2s_device_lod(self._h, int(which)) or 0)
+
+    def download_lod_sh(self):
+        """The tree's SH plane (m2s_download_lod_sh) -> ((nodes, 48) float32 in node order, degree).  M2SError (M2S_ERR_STATE) for a tree
+        built without carry_sh or without a plane."""
+        nodes = self.lod_levels()[-1]
+        out = np.empty((nodes, 48), np.float32)
+        degree = C.c_uint32()
+        self._check(self._L.m2s_download_lod_sh(self._h, out.ctypes.data if out.size else None, nodes, C.byref(degree)))
+        return out, int(degree.value)
+
+    @property
+    def device_lod_sh(self) -> int:
+        return int(self._L.m2s_device_lod_sh(self._h) or 0)
 
     @property
     def device_lod_nodes(self) -> int:

@@ -162,6 +162,32 @@ m2s_status m2s_download_sh(m2s_ctx* c, float* dst, uint64_t capacity_records) {
     return M2S_OK;
 }
 
+m2s_status m2s_upload_sh(m2s_ctx* c, const float* host, uint64_t n, uint32_t degree) {
+    if (!c) return M2S_ERR_INVALID;
+    if (degree > 3) return fail(c, M2S_ERR_INVALID, "degree above 3");
+    M2S_TRY(have_records(c));
+    if (n != c->last_stored) return fail(c, M2S_ERR_INVALID, "the number of rows is not the number of stored records");
+    if (n && !host) return fail(c, M2S_ERR_INVALID, "host is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->sh_tag.clear();
+    c->bake_has_counts = false;
+    M2S_TRY(c->d_sh.reserve(c->err, std::max<uint64_t>(n, 1), 48 * sizeof(float)));
+    if (n) HIPCHK(c, hipMemcpy(c->d_sh, host, n * 48 * sizeof(float), hipMemcpyHostToDevice));
+    c->sh_tag.set(*c, n);
+    c->sh_degree = degree;
+    return M2S_OK;
+}
+
+m2s_status m2s_sh_plane_info(const m2s_ctx* c, uint64_t* rows, uint32_t* degree) {
+    if (rows) *rows = 0;
+    if (degree) *degree = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!c->sh_tag.is_set()) return M2S_ERR_STATE;
+    if (rows) *rows = c->sh_tag.n;
+    if (degree) *degree = c->sh_degree;
+    return M2S_OK;
+}
+
 m2s_status m2s_download_bake_shadow_counts(m2s_ctx* c, uint8_t* dst, uint64_t capacity_bytes) {
     if (!c) return M2S_ERR_INVALID;
     if (!c->sh_tag.is_set() || !c->bake_has_counts) return fail(c, M2S_ERR_STATE, "the last m2s_bake_light kept no shadow counts (want_shadow_counts)");

@@ -222,6 +222,14 @@ m2s_status m2s_set_keep_positions(m2s_ctx* c, int enabled) {
     return M2S_OK;
 }
 
+m2s_status m2s_set_carry_sh(m2s_ctx* c, int enabled) {
+    if (!c) return M2S_ERR_INVALID;
+    c->carry_sh = enabled != 0;
+    return M2S_OK;
+}
+
+int m2s_carry_sh(const m2s_ctx* c) { return c && c->carry_sh ? 1 : 0; }
+
 m2s_status m2s_debug_set_launch_counter(m2s_ctx* c, uint32_t value) {
     if (!c) return M2S_ERR_INVALID;
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);

@@ -11,7 +11,7 @@
 //   m2s_contrib.cpp  the contribution pass and pruning (m2s_contrib_accumulate, m2s_prune)
 //   m2s_budget.cpp   pruning to a budget (m2s_prune_budget): the radix select in front of m2s_prune's compaction
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
-//   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent
+//   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent, a baked SH plane merged with them (m2s_set_carry_sh)
 //   m2s_worldunits.cpp  m2s_records_to_world_units: a conversion's scales divided by its resolutionTarget
 //   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their _frustum forms): a chain of merges kept and linked
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
@@ -229,11 +229,20 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     uint64_t last_merge_counts[4] = { 0, 0, 0, 0 };
     float last_merge_stage_ms[3] = { 0, 0, 0 };          // keys + sort, heads + scans, reduce + adopt
     m2s_host::ClockOf<m2s_host::MergeMark> merge_clock;                      // always on
+    // m2s_set_carry_sh (pin 5s): a merge reduces a baked plane of the current records with them, into d_sh_alt, which then trades places
+    // with d_sh (no copy back); a tree built with the switch on owns a plane of its nodes and its cuts compact it into d_sh
+    bool carry_sh = false;
+    m2s_host::DevBuf<float> d_sh_alt;                    // capacity in rows of 48 floats
+    float last_merge_sh_ms = 0.0f;                       // the SH reduction of the last merge (0: none ran); inside stage [2]
+    m2s_host::ClockOf<m2s_host::SpanMark> merge_sh_clock;    // always on
     // level-of-detail tree (m2s_lod.cpp): the node pool (leaves, then every level a merging step added), a parent word and a 16-byte
     // bound (x, y, z, longer edge) per node, one capacity of nodes each, grown together with their contents kept; lod_levels == 0: no tree
     m2s_host::DevBuf<float4> d_lod_nodes;                // capacity in records
     m2s_host::DevBuf<uint32_t> d_lod_parent;
     m2s_host::DevBuf<float4> d_lod_bounds;
+    m2s_host::DevBuf<float> d_lod_sh;                    // the fourth plane, 48 floats per node: only while lod_has_sh
+    bool lod_has_sh = false;                             // the tree was built with m2s_set_carry_sh on over records with a plane
+    uint32_t lod_sh_degree = 0;                          // ... of this degree
     uint32_t lod_levels = 0;
     uint64_t lod_first[M2S_LOD_MAX_STEPS + 2] = {};      // first node of every level; [lod_levels] = the nodes
     uint32_t lod_R = 0;                                  // resolutionTarget of the leaves

@@ -327,6 +327,11 @@ hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_
 // member i.  out: `segments` records, not the memory rec points into; map: n words.
 hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
                         uint32_t* map, bool unsigned_axis, hipStream_t st);
+// k_merge_reduce_sh (pin 5s), one lane per (segment, float4 column) of the SH plane: out row s = the weighted mean of the members' rows
+// of sh (a copy where it has one member).  sh: n rows of 48 floats; out: `segments` rows, not the memory sh points into.
+constexpr uint32_t kMergeShLanes = 12;     // float4 per row of the plane
+hipError_t merge_reduce_sh(const float4* rec, const float4* sh, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments,
+                           float4* out, hipStream_t st);
 
 // ---- level-of-detail tree and its cut (m2s_lod.hip) ------------------------------------------------------------------------------------
 // k_lod_link.  parent[t] = offset + map[t] for t < n_map (map NULL: M2S_LOD_NO_PARENT, the last level); bounds[t] = (position.xyz,

@@ -18,9 +18,24 @@ constexpr uint64_t kLodMaxNodes = 0xFFFFFFFFull;   // fewer than this: M2S_LOD_N
 
 bool lod_ids_valid(const m2s_ctx* c) { return c->lod_ids_tag.holds(*c); }
 
-// Room for `want` nodes in the three planes of the tree, the first `keep` nodes kept where they have to move.
-m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
-    if (c->d_lod_nodes.cap() >= want && c->d_lod_nodes) return M2S_OK;
+// Room for `want` nodes in the fourth plane (pin 4s: 48 floats per node), the first `keep` rows kept where they have to move.
+m2s_status lod_reserve_sh(m2s_ctx* c, uint64_t want, uint64_t keep) {
+    if (c->d_lod_sh.cap() >= want && c->d_lod_sh) return M2S_OK;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, c->d_lod_nodes.cap()), 1);   // (grown with the other three)
+    DevBuf<float> plane;
+    M2S_TRY(plane.reserve(c->err, cap, 48 * sizeof(float)));
+    if (keep) {
+        HIPCHK(c, hipMemcpyAsync(plane, c->d_lod_sh, keep * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->d_lod_sh.swap(plane);
+    return M2S_OK;
+}
+
+// Room for `want` nodes in the three planes of the tree — and in the fourth, for a tree that has one (sh) —, the first `keep` nodes kept
+// where they have to move.
+m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep, bool sh) {
+    if (c->d_lod_nodes.cap() >= want && c->d_lod_nodes) return sh ? lod_reserve_sh(c, want, keep) : M2S_OK;
     const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, 2 * c->d_lod_nodes.cap()), 1);
     DevBuf<float4> nodes, bounds;
     DevBuf<uint32_t> parent;
@@ -36,7 +51,7 @@ m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep) {
     c->d_lod_nodes.swap(nodes);
     c->d_lod_parent.swap(parent);
     c->d_lod_bounds.swap(bounds);
-    return M2S_OK;
+    return sh ? lod_reserve_sh(c, want, keep) : M2S_OK;
 }
 
 LodFrustumK lod_frustum_k(const m2s_lod_frustum* fr) {
@@ -79,6 +94,7 @@ enum class LodVis { None, Here, Enqueued };     // no frustum | lod_cut enqueues
 m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4], const m2s_lod_frustum* fr, LodVis vis) {
     if ((fr != nullptr) != (vis != LodVis::None)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
     const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
+    const bool with_sh = c->lod_has_sh && !dry;     // (pin 3s: the tree's property decides, not the switch at the time of the cut)
     ClockOf<LodCutMark>& clock = c->lod_cut_clock;
     const uint32_t levels = c->lod_levels;
     const uint64_t N = c->lod_first[levels];
@@ -119,6 +135,14 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
             return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
         if (!dry) {
             M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
+            if (with_sh) {
+                // the selected nodes' rows of the tree's plane, by the same flags and offsets, straight into the context's plane (the
+                // source is the tree's: nothing lands on itself); whatever plane the context had is gone from here on
+                c->sh_tag.clear();
+                c->bake_has_counts = false;
+                M2S_TRY(c->d_sh.reserve(c->err, std::max<uint64_t>(selected, 1), 48 * sizeof(float)));
+                if (selected) HIPCHK(c, prune_compact((const float4*)c->d_lod_sh.get(), flags, offsets, (uint32_t)N, kMergeShLanes, (float4*)c->d_sh.get(), c->stream));
+            }
             HIPCHK(c, clock.mark(LodCutMark::Compacted, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
@@ -137,7 +161,9 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         if (fr) HIPCHK(c, c->lod_vis_clock.span(SpanMark::Begin, SpanMark::End, &c->last_lod_frustum_ms));   // (an empty tree: 0 too)
     }
     if (!dry) {
-        c->rewritten(c->lane[0].records, selected, c->lod_R, Rewrite::LodCut);   // (a baked plane is one of other records: dropped)
+        // (a baked plane of the context is one of other records: dropped; a tree with a plane has left the selected nodes' rows in its place)
+        c->rewritten(c->lane[0].records, selected, c->lod_R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
+        if (with_sh) c->sh_degree = c->lod_sh_degree;
         c->lod_ids_tag.set(*c, selected);
     }
     c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
@@ -242,11 +268,15 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     if (n0 >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
     const uint32_t R = c->last_R;
     const bool unsigned_axis = (p->flags & M2S_MERGE_UNSIGNED_AXIS) != 0;   // (every step, the ones that merge nothing included)
+    const bool with_sh = c->carry_sh && c->sh_tag.holds(*c, n0);            // pin 4s: the tree owns a plane too
+    const uint32_t sh_degree = c->sh_degree;
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->lod_build_clock.begin(c->err, true));                    // (measured whatever m2s_set_profiling says)
     c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
+    c->lod_has_sh = false;
+    if (!with_sh) c->d_lod_sh.release();                                // (192 bytes per node: not kept for a tree that has no use for it)
     HIPCHK(c, c->lod_build_clock.mark(SpanMark::Begin, c->stream));
-    M2S_TRY(lod_reserve(c, n0 + n0 / 2, 0));
+    M2S_TRY(lod_reserve(c, n0 + n0 / 2, 0, with_sh));
     uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
     uint32_t levels = 1;
     uint64_t skipped = 0;
@@ -254,6 +284,7 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     if (n0) {
         HIPCHK(c, hipMemcpyAsync(c->d_lod_nodes, c->last_records, n0 * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, c->d_lod_nodes, (uint32_t)n0, c->d_lod_bounds, c->stream));
+        if (with_sh) HIPCHK(c, hipMemcpyAsync(c->d_lod_sh, c->d_sh, n0 * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     for (uint32_t s = 0; s < p->n_steps; ++s) {
         const uint64_t below = first[levels - 1], cnt = first[levels] - below;
@@ -262,9 +293,13 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
         if (after == cnt) { ++skipped; continue; }                      // (nothing merged and nothing changed: no level)
         const uint64_t total = first[levels] + after;
         if (total >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
-        M2S_TRY(lod_reserve(c, total, first[levels]));
+        M2S_TRY(lod_reserve(c, total, first[levels], with_sh));
         float4* const level = c->d_lod_nodes + 6 * first[levels];
         HIPCHK(c, hipMemcpyAsync(level, c->last_records, after * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        if (with_sh) {                                                  // (the rows pin 5s made for this step: the context's plane by now)
+            if (!c->sh_tag.holds(*c, after)) return fail(c, M2S_ERR_HIP, "the merge left no plane of its parents (internal error)");
+            HIPCHK(c, hipMemcpyAsync(c->d_lod_sh + 48 * first[levels], c->d_sh, after * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        }
         HIPCHK(c, lod_link(c->d_merge_map, (uint32_t)cnt, (uint32_t)first[levels], c->d_lod_parent + below, level, (uint32_t)after,
                            c->d_lod_bounds + first[levels], c->stream));
         first[++levels] = total;                                        // (the next step rewrites the map and the pool behind these, stream-ordered)
@@ -276,6 +311,8 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     for (uint32_t l = 0; l < M2S_LOD_MAX_STEPS + 2; ++l) c->lod_first[l] = first[std::min(l, levels)];
     c->lod_levels = levels;
     c->lod_R = R;
+    c->lod_has_sh = with_sh;
+    c->lod_sh_degree = sh_degree;
     if (out_counts) { out_counts[0] = n0; out_counts[1] = first[levels]; out_counts[2] = levels; out_counts[3] = skipped; }
     return M2S_OK;
 }
@@ -307,11 +344,32 @@ m2s_status m2s_download_lod(m2s_ctx* c, uint32_t which, void* dst, uint64_t capa
     return M2S_OK;
 }
 
+const void* m2s_device_lod_sh(const m2s_ctx* c) {
+    return c && c->lod_levels && c->lod_has_sh && c->lod_first[c->lod_levels] ? c->d_lod_sh.get() : nullptr;
+}
+
+m2s_status m2s_download_lod_sh(m2s_ctx* c, float* dst, uint64_t capacity_rows, uint32_t* out_degree) {
+    if (out_degree) *out_degree = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    if (!c->lod_has_sh) return fail(c, M2S_ERR_STATE, "the tree has no SH plane (m2s_set_carry_sh and a baked plane at m2s_lod_build)");
+    const uint64_t rows = c->lod_first[c->lod_levels];
+    if (capacity_rows < rows) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer rows than the plane");
+    if (out_degree) *out_degree = c->lod_sh_degree;
+    if (!rows) return M2S_OK;
+    if (!dst) return fail(c, M2S_ERR_INVALID, "no destination");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_lod_sh, rows * 48 * sizeof(float), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
 m2s_status m2s_lod_release(m2s_ctx* c) {
     if (!c) return M2S_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->lod_levels = 0;
+    c->lod_has_sh = false;
+    c->d_lod_sh.release();
     c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release(); c->d_lod_vis.release();
     return M2S_OK;
 }

@@ -1,6 +1,7 @@
 // m2s_merge.cpp — the merge pass (m2s_merge): host side of m2s_merge.hip.  Order comes from the compact export's helper
 // (compact_keys_and_sort, m2s_compact.hip) in the compact export's own buffers; the parents go into the pool the way m2s_prune's survivors
-// do (through the staging buffer where the sources live there); what the call does to the context: m2s_recstate.h, Rewrite::Merge.
+// do (through the staging buffer where the sources live there); what the call does to the context: m2s_recstate.h, Rewrite::Merge —
+// MergeWithSh where m2s_set_carry_sh is on and a baked plane of the records exists: k_merge_reduce_sh then reduces the plane too (pin 5s).
 // merge_run is the pass behind m2s_merge's argument checks: the steps of m2s_lod_build (m2s_lod.cpp) are calls of it.
 #include "m2s_ctx.h"
 
@@ -30,6 +31,10 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
     HIPCHK(c, hipSetDevice(c->device));
     ClockOf<MergeMark>& clock = c->merge_clock;
     M2S_TRY(clock.begin(c->err, true));            // (measured whatever m2s_set_profiling says)
+    // pin 5s: a plane of exactly these n records is reduced with them (decided here: the tag does not survive what follows)
+    const bool with_sh = c->carry_sh && c->sh_tag.holds(*c, n);
+    M2S_TRY(c->merge_sh_clock.begin(c->err, with_sh));
+    c->last_merge_sh_ms = 0.0f;
     uint64_t segments = 0, merged = 0, invalid = 0;
     float ms[3] = { 0, 0, 0 };
     if (n) {
@@ -73,11 +78,22 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
             if (in_pool) M2S_TRY(c->d_prune_stage.reserve(c->err, segments * sizeof(m2s_gaussian), 1));
             const void* src = c->last_records;
             if (!in_pool) M2S_TRY(ensure_records(c, segments));
+            if (with_sh) M2S_TRY(c->d_sh_alt.reserve(c->err, segments, kMergeShLanes * sizeof(float4)));
             float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
             HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, unsigned_axis, c->stream));
+            if (with_sh) {
+                // Pin 5s.  The members' rows come from d_sh through perm and the parents' rows go into the second buffer, which trades
+                // places with d_sh below: no lane lands on a row another still reads, and nothing is copied back.  The weights are the
+                // MEMBERS' alpha and scales: in front of the copy that puts the parents where the members were.
+                HIPCHK(c, c->merge_sh_clock.mark(SpanMark::Begin, c->stream));
+                HIPCHK(c, merge_reduce_sh((const float4*)src, (const float4*)c->d_sh.get(), perm, seg_start, c->d_merge_totals, (uint32_t)segments,
+                                          (float4*)c->d_sh_alt.get(), c->stream));
+                HIPCHK(c, c->merge_sh_clock.mark(SpanMark::End, c->stream));
+            }
             if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, segments * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, clock.mark(MergeMark::Reduced, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (with_sh) c->d_sh.swap(c->d_sh_alt);
         }
     } else if (!dry) {
         M2S_TRY(prune_compact_enqueue(c, 0, 0, nullptr, nullptr, false));
@@ -85,9 +101,11 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
         c->merge_map_tag.clear();
     }
     if (!dry) {
-        c->rewritten(c->lane[0].records, segments, R, Rewrite::Merge);   // (a plane of the members is not a plane of their parents: dropped)
+        // (without pin 5s a plane of the members is not a plane of their parents: dropped; with it, no records: an empty plane stays one)
+        c->rewritten(c->lane[0].records, segments, R, with_sh ? Rewrite::MergeWithSh : Rewrite::Merge);
         c->merge_map_tag.set(*c, n);
     }
+    HIPCHK(c, c->merge_sh_clock.span(SpanMark::Begin, SpanMark::End, &c->last_merge_sh_ms));   // (0 where the reduction did not run)
     // (no records: three zeros; a dry run records no Reduced: [2] is 0)
     HIPCHK(c, clock.span(MergeMark::Start, MergeMark::Sorted, &ms[0]));
     HIPCHK(c, clock.span(MergeMark::Segments, MergeMark::Segmented, &ms[1]));
@@ -118,6 +136,8 @@ m2s_status m2s_merge(m2s_ctx* c, const m2s_merge_params* p, uint64_t out_counts[
 m2s_status m2s_last_merge_counts(const m2s_ctx* c, uint64_t out[4]) { return get_array(c, &m2s_ctx::last_merge_counts, out); }
 
 m2s_status m2s_last_merge_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_merge_stage_ms, out_ms); }
+
+float m2s_last_merge_sh_ms(const m2s_ctx* c) { return c ? c->last_merge_sh_ms : 0.0f; }
 
 const void* m2s_device_merge_map(const m2s_ctx* c) { return c && merge_map_valid(c) && c->merge_map_tag.n ? c->d_merge_map.get() : nullptr; }
 

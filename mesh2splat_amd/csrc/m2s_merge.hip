@@ -219,6 +219,54 @@ __global__ void __launch_bounds__(kBlock) k_merge_reduce(const float4* __restric
     o[5] = make_float4((float)(pb0 / W), (float)(pb1 / W), pbr1.z, pbr1.w);
 }
 
+// Pin 5s: one walk over the members of a segment for one float4 column q of the SH plane.  kUnit: every weight is 1 (the areas add up to nothing).
+// Every product and sum is fp64 in member order, without contraction.  The twelve lanes of a segment read the same alpha and scale words.
+template <bool kUnit>
+__device__ __forceinline__ void merge_sh_walk(const float* __restrict__ rec, const float4* __restrict__ sh, const uint32_t* __restrict__ perm, uint32_t a,
+                                              uint32_t b, uint32_t q, double& W, double& A, double (&sa)[4], double (&sw)[4]) {
+    W = 0.0; A = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { sa[k] = 0.0; sw[k] = 0.0; }
+    uint32_t i = perm[a];
+    for (uint32_t j = a; j < b; ++j) {
+        const uint32_t nxt = j + 1 < b ? perm[j + 1] : i;      // (the next member's index is on its way while this one's rows are)
+        const float* g = rec + (size_t)i * 24;
+        const float4 v = sh[(size_t)i * kMergeShLanes + q];
+        const double w = kUnit ? 1.0 : (double)g[8] * (double)g[9];
+        const double wa = w * (double)g[7];
+        W += w;
+        A += wa;
+        sa[0] += wa * (double)v.x; sa[1] += wa * (double)v.y; sa[2] += wa * (double)v.z; sa[3] += wa * (double)v.w;
+        sw[0] += w * (double)v.x; sw[1] += w * (double)v.y; sw[2] += w * (double)v.z; sw[3] += w * (double)v.w;
+        i = nxt;
+    }
+}
+
+// Pin 5s.  A row of the plane is twelve float4: lane t = (segment t / 12, column t % 12), no lane idle but the tail of the last
+// workgroup.  Twelve against sixteen with four idle: a quarter fewer waves for the same bytes, at the price of a division by 12 per lane
+// and of segments that straddle two waves, which costs nothing here — the lanes share no state.  A wave reads whole 192-byte rows
+// through perm, 5 1/3 of them per load.  No atomics, a fixed order: the same bits from run to run.  out is not the memory sh points into.
+__global__ void __launch_bounds__(kBlock) k_merge_reduce_sh(const float4* __restrict__ rec, const float4* __restrict__ sh, const uint32_t* __restrict__ perm,
+                                                            const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ totals,
+                                                            float4* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t s = (uint32_t)(t / kMergeShLanes), q = (uint32_t)(t - (uint64_t)s * kMergeShLanes);
+    if (t / kMergeShLanes >= (uint64_t)totals[0]) return;
+    const uint32_t a = seg_start[s], b = seg_start[s + 1];
+    float4* o = out + (size_t)s * kMergeShLanes + q;
+    if (b - a == 1u) {
+        *o = sh[(size_t)perm[a] * kMergeShLanes + q];
+        return;
+    }
+    double W, A, sa[4], sw[4];
+    merge_sh_walk<false>((const float*)rec, sh, perm, a, b, q, W, A, sa, sw);
+    if (W == 0.0) merge_sh_walk<true>((const float*)rec, sh, perm, a, b, q, W, A, sa, sw);   // (pin 5's own test; rare: a second walk, no second set of sums)
+    const bool by_alpha = A != 0.0;
+    const double den = by_alpha ? A : W;
+    *o = make_float4((float)((by_alpha ? sa[0] : sw[0]) / den), (float)((by_alpha ? sa[1] : sw[1]) / den), (float)((by_alpha ? sa[2] : sw[2]) / den),
+                     (float)((by_alpha ? sa[3] : sw[3]) / den));
+}
+
 size_t merge_scan_temp_bytes(uint32_t n) {
     size_t a = 0, b = 0;
     (void)rocprim::inclusive_scan(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, rocprim::maximum<uint32_t>(), (hipStream_t)0);
@@ -251,6 +299,15 @@ hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t*
     const dim3 grid((segments + kBlock - 1) / kBlock);
     if (unsigned_axis) hipLaunchKernelGGL(k_merge_reduce<true>, grid, dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
     else hipLaunchKernelGGL(k_merge_reduce<false>, grid, dim3(kBlock), 0, st, rec, perm, seg_start, totals, out, map);
+    return hipGetLastError();
+}
+
+hipError_t merge_reduce_sh(const float4* rec, const float4* sh, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments,
+                           float4* out, hipStream_t st) {
+    if (!segments) return hipSuccess;
+    const uint64_t lanes = (uint64_t)segments * kMergeShLanes;
+    const dim3 grid((uint32_t)((lanes + kBlock - 1) / kBlock));      // (below 2^28 workgroups for any 32-bit segment count)
+    hipLaunchKernelGGL(k_merge_reduce_sh, grid, dim3(kBlock), 0, st, rec, sh, perm, seg_start, totals, out);
     return hipGetLastError();
 }
 

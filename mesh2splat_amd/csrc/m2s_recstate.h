@@ -23,7 +23,7 @@ struct RecordsTag {
 };
 
 // What a pass that rewrites the records into the pool was (RecordState::rewritten): the columns of the table's last rows.
-enum class Rewrite { Prune, PruneWithSh, RefitApply, Merge, LodCut, WorldUnits };
+enum class Rewrite { Prune, PruneWithSh, RefitApply, Merge, LodCut, WorldUnits, MergeWithSh, LodCutWithSh };
 
 struct RecordState {
     // ---- the current records
@@ -62,8 +62,11 @@ struct RecordState {
     //   PruneWithSh        |                                 keep                                                                      keep            tag    0
     //   RefitApply, Merge  |                                 keep                                                                      0               0      keep
     //   LodCut             |                                 keep                                                                      keep            0      keep
+    //   MergeWithSh        |                                 keep                                                                      0               tag    0
+    //   LodCutWithSh       |                                 keep                                                                      keep            tag    0
     //   WorldUnits         |                                 old R, unless set                                                         0               0      keep
-    // (Merge and LodCut then tag the map / the node indices, run_pass the position plane its sparse kernel wrote: what they produce.)
+    // (Merge and LodCut then tag the map / the node indices, run_pass the position plane its sparse kernel wrote: what they produce.
+    // MergeWithSh, LodCutWithSh: m2s_set_carry_sh — the plane was reduced with the records / compacted out of the tree's; as PruneWithSh.)
 
     // a conversion at R is about to be launched (written before it can fail: a failed one leaves the OLD records with the new R) ...
     void conversion_started(uint32_t R) { last_R = R; conv_R = 0; records_stale = false; }
@@ -90,8 +93,10 @@ struct RecordState {
         current(pool, n, n);
         last_R = R; records_stale = false; sorted_n = 0; pp_visible = 0; sq_n = 0; sq_src = nullptr;
         contrib_tag.clear();
-        if (as == Rewrite::RefitApply || as == Rewrite::Merge || as == Rewrite::WorldUnits) refit_tag.clear();
-        if (as == Rewrite::PruneWithSh) { sh_tag.set(*this, n); bake_has_counts = false; }   // (the plane was compacted with them, its tap counts were not)
+        if (as == Rewrite::RefitApply || as == Rewrite::Merge || as == Rewrite::MergeWithSh || as == Rewrite::WorldUnits) refit_tag.clear();
+        if (as == Rewrite::PruneWithSh || as == Rewrite::MergeWithSh || as == Rewrite::LodCutWithSh) {
+            sh_tag.set(*this, n); bake_has_counts = false;   // (the plane was compacted / reduced with them, its tap counts were not)
+        }
         else if (as != Rewrite::Prune) sh_tag.clear();
         if (as == Rewrite::WorldUnits && !conv_R) conv_R = old_R;   // (set already: a cut through a tree of stored-unit leaves brought their R back since)
     }

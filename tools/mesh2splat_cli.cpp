@@ -92,6 +92,7 @@ struct Options {
     long long lod_budget = 0;                                      // --lod-budget N: every camera takes the finest cut of at most N records (m2s_lod_select_budget); --lod-pixels is then its floor
     double lod_guard = -1.0;                                       // --lod-frustum [--lod-guard g]: the cuts select only what their camera sees (m2s_lod_select_frustum,
     bool lod_frustum = false;                                      //   m2s_lod_select_budget_frustum), the frustum test widened by g (>= 1; 1.05, the prepass's own, without --lod-guard)
+    std::string lod_ply;                                           // --lod-ply cut.ply: the --preview camera's cut as a .ply (with --bake-light: its carried SH plane, m2s_set_carry_sh)
     bool lod() const { return !lod_levels.empty(); }
     bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
     bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
@@ -115,7 +116,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]] [--lod-ply cut.ply]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -183,6 +184,10 @@ void usage() {
                  "  camera's frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum), and a budget is spent on those alone.  The `lod:`\n"
                  "  line then has \"frustum\": g, and every entry of `views` \"visible_leaves\" and \"culled\" (nodes the plain cut selects\n"
                  "  and this one dropped).\n"
+                 "--lod-ply cut.ply, with --lod-levels and --preview (one file, one GPU): right after the --preview camera's cut its records are\n"
+                 "  written to cut.ply, in --format (m2s_export_ply).  With --bake-light the baked plane is carried through the tree and the cut\n"
+                 "  (m2s_set_carry_sh, switched on in front of the bake) and cut.ply carries the SH element (m2s_export_ply_sh).  The `lod:` line\n"
+                 "  gains \"cut_ply\", and with a carried plane \"sh_degree\".\n"
                  "--merge-unsigned-axis, with --merge-level, --merge-to or --lod-levels: the sign of a record's third axis carries no meaning\n"
                  "  (M2S_MERGE_UNSIGNED_AXIS: a group ends where |dot| is below d, and the members' axes are turned onto one side before they\n"
                  "  are averaged).  A conversion stores the two triangles of a flat quad with opposite signs, which the viewer does not see; with\n"
@@ -321,7 +326,7 @@ void preview_light(const m2s_mesh* meshes, uint32_t n_meshes, double pos[3], dou
 
 // --lod-levels / --lod-pixels / --lod-budget: the tree over the context's records (Converter.lod_build), then one cut per camera (Converter.lod_select / .lod_select_budget)
 // in front of its frame; the views collect in `views` for the one `lod:` line
-struct LodReport { uint64_t build[4] = {}; std::vector<uint64_t> first; float build_ms = 0; std::string views; };
+struct LodReport { uint64_t build[4] = {}; std::vector<uint64_t> first; float build_ms = 0; std::string views; std::string cut_ply; };   // cut_ply: the keys of --lod-ply
 
 int lod_build(m2s_ctx* ctx, const Options& o, LodReport* rep) {
     m2s_lod_build_params bp;
@@ -401,7 +406,21 @@ void lod_print(const Options& o, const LodReport& rep) {
     }
     std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
-                budget.c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
+                (budget + rep.cut_ply).c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
+}
+
+// --lod-ply: the records the preview camera's cut left, as a .ply — with --bake-light the plane the tree carried (m2s_set_carry_sh) through
+// m2s_export_ply_sh, else --format through m2s_export_ply
+int lod_write_cut(m2s_ctx* ctx, const Options& o, LodReport* rep) {
+    std::string path;
+    for (char ch : o.lod_ply) { if (ch == '"' || ch == '\\') path += '\\'; path += ch; }
+    rep->cut_ply = ", \"cut_ply\": \"" + path + "\"";
+    if (!o.bake_light) return m2s_export_ply(ctx, o.lod_ply.c_str(), (uint32_t)o.format, (float)o.std_dev) == M2S_OK ? 0 : 1;
+    uint64_t rows = 0;
+    uint32_t degree = 0;
+    if (m2s_sh_plane_info(ctx, &rows, &degree) != M2S_OK || rows != m2s_num_stored(ctx)) return 1;
+    rep->cut_ply += ", \"sh_degree\": " + std::to_string(degree);
+    return m2s_export_ply_sh(ctx, o.lod_ply.c_str(), (float)o.std_dev) == M2S_OK ? 0 : 1;
 }
 
 // GaussiansPrepass -> RadixSortPass -> GaussianSplattingPass of the converted records; the albedo attachment to `path` — with
@@ -413,6 +432,7 @@ int write_preview(m2s_ctx* ctx, const m2s_mesh* meshes, uint32_t n_meshes, uint3
     double eye[3], ctr[3], near_p, far_p;
     preview_camera(meshes, n_meshes, W, H, pp.world_to_view, pp.view_to_clip, eye, ctr, &near_p, &far_p, o.view_distance);
     if (lod && lod_cut(ctx, o, eye, pp.world_to_view, pp.view_to_clip, H, near_p, false, lod) != 0) return 1;
+    if (lod && !o.lod_ply.empty() && lod_write_cut(ctx, o, lod) != 0) return 1;
     for (int k = 0; k < 4; ++k) pp.model_to_world[k * 5] = 1.0f;
     pp.resolution[0] = W; pp.resolution[1] = H;
     pp.near_far[0] = (float)near_p; pp.near_far[1] = (float)far_p;
@@ -851,6 +871,7 @@ int convert_one(const Options& o) {
     if (o.merging() && run_merge(ctx, o) != 0) return die("merge");
     if (o.refit_views > 0 && run_refit(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("refit");
     if (o.bake_light) {
+        if (!o.lod_ply.empty() && m2s_set_carry_sh(ctx, 1) != M2S_OK) return die("carry sh");   // (the tree below then carries the baked plane into its cuts)
         if (bake_light(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene), R, o) != 0) return die("bake");
         if (o.compact) { if (export_compact(ctx, o.out, o, true) != 0) return die("export"); }
         else if (m2s_export_ply_sh(ctx, o.out.c_str(), (float)o.std_dev) != M2S_OK) return die("export");
@@ -1242,6 +1263,7 @@ int main(int argc, char** argv) {
         else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
         else if (a == "--lod-pixels") { o.lod_pixels = std::atof(next()); if (!(o.lod_pixels >= 0.0) || !std::isfinite(o.lod_pixels)) { usage(); return 2; } }
         else if (a == "--lod-frustum") o.lod_frustum = true;
+        else if (a == "--lod-ply") o.lod_ply = next();
         else if (a == "--lod-guard") { o.lod_guard = std::atof(next()); if (!(o.lod_guard >= 1.0) || !std::isfinite(o.lod_guard)) { usage(); return 2; } }
         else if (a == "--lod-budget") {
             const std::string v = next();
@@ -1323,6 +1345,7 @@ int main(int argc, char** argv) {
     if ((o.lod_frustum && !o.lod()) || (o.lod_guard >= 0.0 && !o.lod_frustum)) { usage(); return 2; }   // (--lod-frustum: a mode of the cuts; --lod-guard: of --lod-frustum)
     if (o.lod_frustum && o.lod_guard < 0.0) o.lod_guard = 1.05;
     if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
+    if (!o.lod_ply.empty() && (!o.lod() || o.preview.empty() || !o.batch_dir.empty() || o.gpus > 1 || o.force_sharded)) { usage(); return 2; }
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
     if (!o.batch_dir.empty()) {
         if (o.out_dir.empty() || !pos.empty()) { usage(); return 2; }
