@@ -863,6 +863,48 @@ m2s_status m2s_lod_select_budget_frustum(m2s_ctx* ctx, const m2s_lod_budget_para
 m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* ctx, uint64_t out[2]);
 float      m2s_last_lod_frustum_ms(const m2s_ctx* ctx);
 
+/* The two frustum cuts behind an occluder: a leaf counts as inside only if it passes the frustum test AND is not behind a depth image
+ * under m2s_prepass's own depth test, so that the leaves on the far side of a closed mesh are neither selected nor charged to a record
+ * budget (tests/lod_occlusion_ref.py restates it).  Pinned, on top of the pins of the frustum cuts above:
+ *  1. Leaf test.  For leaf i with bound (x, y, z, e) and alpha = color[3] of its node record (tree plane 0): c and inside_frustum exactly
+ *     as in pin 1 above.  Where inside_frustum holds, in fp32, one rounding per operation, IEEE division:
+ *       u = (c.x / c.w) * 0.5f + 0.5f;  v = (c.y / c.w) * 0.5f + 0.5f;
+ *       ti = clamp(floorf(u * (float)depth_w));  tj = clamp(floorf(v * (float)depth_h));   (m2s_prepass's clamp: below 0 and NaN give 0,
+ *                                                                                            at or above the size gives size - 1)
+ *       d = depth[tj * depth_w + ti];  my = (c.z / c.w) * 0.5f + 0.5f;  behind = (my > d + depth_bias);
+ *       occluded = behind && alpha > .95f;  inside = inside_frustum && !occluded.
+ *     Every comparison is false for a NaN: a NaN position, a NaN texel and a NaN alpha all leave the leaf inside.  With guard_band ==
+ *     1.05f and depth_bias == 0.00002f the leaves that are not inside are exactly the records m2s_prepass culls with the same matrices,
+ *     format 0, depth_test_mesh 1 and the same image: the two share one definition of the test.
+ *  2. Pins 2 to 6 of the frustum cuts apply word for word with this `inside`: positions above the leaves are never tested, masking is
+ *     L := H, N_eff is the larger of max_records and the visible part of the last level, zero selected is a valid result, `refine` is
+ *     unmasked, m2s_last_lod_level_counts reports the counts after masking; order, adoption, invalidation, m2s_device_lod_nodes,
+ *     M2S_LOD_DRY_RUN and the SH plane (pin 3s) are m2s_lod_select's.
+ *  3. Counts.  m2s_last_lod_occlusion_counts (a dry run included): [0] leaves inside the frustum, [1] of those, occluded, [2] of those
+ *     inside the frustum, behind the image but kept because alpha <= .95 or is NaN, [3] nodes the plain cut selects at that tau_px and
+ *     this one dropped.  After an occluded call m2s_last_lod_frustum_counts reports [0] and [3] of these and m2s_last_lod_frustum_ms the
+ *     visibility stage.  Integer sums: identical from run to run.
+ *  4. Errors: those of the frustum forms; M2S_ERR_INVALID for a NULL occluder, a depth_bias that is not finite or negative, a reserved
+ *     word that is not 0, a depth_w or depth_h of 0 with a depth that is not NULL, a size that disagrees with the context's image where
+ *     depth is NULL; M2S_ERR_STATE where depth is NULL and no m2s_mesh_depth has run.  An empty tree behaves as in the frustum forms and
+ *     reads no image.
+ *  5. The m2s_prepass that follows an occluded cut is run with depth_test_mesh = 0: a selected node above the leaves is the mean of
+ *     points on a curved surface, lies under the surface its leaves lie on and would be culled by its own position where its leaves
+ *     pass.  A node is drawn whole as soon as one leaf below it is visible: the rule is conservative, it never removes visible surface. */
+typedef struct m2s_lod_occluder {
+    const float* depth;        /* depth_w x depth_h window-space depth in [0,1], row 0 = bottom: m2s_prepass_params.depth's layout.
+                                  NULL: the image of the context's last m2s_mesh_depth (depth_w / depth_h must then be 0 or equal to its size) */
+    uint32_t depth_w, depth_h;
+    uint32_t depth_on_device;  /* as m2s_prepass_params: 1 = device pointer on the context's device, 0 = host memory (copied) */
+    float    depth_bias;       /* finite, >= 0; 0.00002f is the prepass's own */
+    uint32_t reserved[2];      /* 0 */
+} m2s_lod_occluder;            /* 32 bytes */
+m2s_status m2s_lod_select_occluded(m2s_ctx* ctx, const m2s_lod_select_params* params, const m2s_lod_frustum* frustum,
+                                   const m2s_lod_occluder* occluder, uint64_t out_counts[4]);
+m2s_status m2s_lod_select_budget_occluded(m2s_ctx* ctx, const m2s_lod_budget_params* params, const m2s_lod_frustum* frustum,
+                                          const m2s_lod_occluder* occluder, m2s_lod_budget_result* out, uint64_t out_counts[4]);
+m2s_status m2s_last_lod_occlusion_counts(const m2s_ctx* ctx, uint64_t out[4]);
+
 /* ---- world units (no counterpart in the reference, which keeps the resolutionTarget beside its records) ---------------------------- */
 /* Brings the context's current records to world units: scale[k] = scale[k] / (float)R for k = 0, 1, 2, with R the records'
  * resolutionTarget; afterwards the records' resolutionTarget is 1.  A conversion stores scale = (|Ju|, |Jv|, 1e-7) and leaves the

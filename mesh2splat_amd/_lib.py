@@ -58,6 +58,7 @@ EXPORTS = (
     "m2s_last_lod_level_counts", "m2s_last_lod_select_stage_ms", "m2s_device_lod_nodes", "m2s_download_lod_nodes",
     "m2s_lod_select_budget", "m2s_last_lod_budget_stage_ms",
     "m2s_lod_select_frustum", "m2s_lod_select_budget_frustum", "m2s_last_lod_frustum_counts", "m2s_last_lod_frustum_ms",
+    "m2s_lod_select_occluded", "m2s_lod_select_budget_occluded", "m2s_last_lod_occlusion_counts",
     "m2s_records_to_world_units", "m2s_last_world_units_ms",
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
@@ -306,6 +307,9 @@ def load():
         "m2s_lod_select_budget_frustum": (C.c_int, [vp, vp, vp, vp, C.POINTER(u64)]),
         "m2s_last_lod_frustum_counts": (C.c_int, [vp, C.POINTER(u64)]),
         "m2s_last_lod_frustum_ms": (C.c_float, [vp]),
+        "m2s_lod_select_occluded": (C.c_int, [vp, vp, vp, vp, C.POINTER(u64)]),
+        "m2s_lod_select_budget_occluded": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(u64)]),
+        "m2s_last_lod_occlusion_counts": (C.c_int, [vp, C.POINTER(u64)]),
         "m2s_records_to_world_units": (C.c_int, [vp, C.POINTER(u32)]),
         "m2s_last_world_units_ms": (C.c_float, [vp]),
         "m2s_write_ply_compact": (C.c_int, [C.c_char_p, vp, vp, u32, u64, C.c_float, C.POINTER(u64)]),

@@ -1091,8 +1091,17 @@ class Converter:
         self._check(self._L.m2s_last_lod_frustum_counts(self._h, fc))
         out.update({name: int(fc[k]) for k, name in enumerate(_ld.FRUSTUM_COUNTS)})
 
+    def last_lod_occlusion_counts(self) -> dict:
+        """Of the last lod_select() / lod_select_budget() with an occluder, a dry run included (m2s_last_lod_occlusion_counts):
+        {"visible_leaves": leaves inside the frustum, "occluded_leaves": of those, hidden by the depth image, "translucent_kept": of
+        those inside, behind the image but kept for an alpha <= .95 or NaN, "culled": nodes the plain cut selects and this one dropped}."""
+        from . import lod as _ld
+        oc = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_last_lod_occlusion_counts(self._h, oc))
+        return {name: int(oc[k]) for k, name in enumerate(_ld.OCCLUSION_COUNTS)}
+
     def lod_select(self, camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False,
-                   frustum=None) -> dict:
+                   frustum=None, occluder=None) -> dict:
         """Take the cut through the tree for a camera at `camera_position` (world space) whose projection has `focal_px` pixels per unit
         of tan(angle) (mesh2splat_amd.lod.focal_px, .camera_position): walking down from the coarsest level, a node is drawn as soon as
         its longer edge projects to at most tau_px pixels at its distance from the camera (at least `near`), or it is a leaf
@@ -1103,12 +1112,20 @@ class Converter:
         -> {"nodes", "selected", "selected_leaves", "refine", "per_level": selected nodes of every tree level}.
         frustum (a mesh2splat_amd.lod.LodFrustumC: lod.frustum_to_c, lod.frustum_of): only nodes with a leaf inside it are selected
         (m2s_lod_select_frustum), possibly none; the dict then also has "visible_leaves" and "culled", the nodes the plain cut selects
-        and this one dropped."""
+        and this one dropped.
+        occluder (a mesh2splat_amd.lod.LodOccluderC: lod.occluder_to_c, lod.occluder_of_mesh_depth; needs a frustum): a leaf behind
+        this depth image under the prepass's own depth test is not inside either (m2s_lod_select_occluded); the dict then also has
+        "occluded_leaves" and "translucent_kept", and "visible_leaves" stays the leaves inside the frustum.  Run the prepass that
+        follows with depth_test_mesh = 0: a merged node lies under the surface its leaves lie on."""
         from . import lod as _ld
+        if occluder is not None and frustum is None:
+            raise ValueError("an occluder needs a frustum")
         pc = _ld.select_to_c(camera_position, focal_px, tau_px, near, dry_run)
         v = (C.c_uint64 * 4)()
         if frustum is None:
             self._check(self._L.m2s_lod_select(self._h, C.byref(pc), v))
+        elif occluder is not None:
+            self._check(self._L.m2s_lod_select_occluded(self._h, C.byref(pc), C.byref(frustum), C.byref(occluder), v))
         else:
             self._check(self._L.m2s_lod_select_frustum(self._h, C.byref(pc), C.byref(frustum), v))
         out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
@@ -1117,22 +1134,29 @@ class Converter:
         out["per_level"] = [int(per[k]) for k in range(len(self.lod_levels()) - 1)]
         if frustum is not None:
             self._lod_frustum_counts(out)
+        if occluder is not None:
+            out.update(self.last_lod_occlusion_counts())
         return out
 
     def lod_select_budget(self, camera_position, focal_px: float, max_records: int, tau_min_px: float = 0.0, near: float = 1e-3,
-                          dry_run: bool = False, frustum=None) -> dict:
+                          dry_run: bool = False, frustum=None, occluder=None) -> dict:
         """Take the finest cut of lod_select() that holds at most `max_records` records for this camera, never finer than tau_min_px: the
         tau_px is found on the device, without a bisection on the host (m2s_lod_select_budget; the pin is in include/m2s.h).  A budget
         below the size of the coarsest level returns that level, with "met" False.  Everything else is lod_select()'s at the returned
         tau_px, the SH plane of a tree built with carry_sh included.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
         next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}.
-        frustum: as for lod_select(); the budget is then spent on the nodes the camera sees (m2s_lod_select_budget_frustum)."""
+        frustum: as for lod_select(); the budget is then spent on the nodes the camera sees (m2s_lod_select_budget_frustum).
+        occluder: as for lod_select(); ... and that no mesh hides (m2s_lod_select_budget_occluded)."""
         from . import lod as _ld
+        if occluder is not None and frustum is None:
+            raise ValueError("an occluder needs a frustum")
         pc = _ld.budget_to_c(camera_position, focal_px, max_records, tau_min_px, near, dry_run)
         res = _ld.LodBudgetResultC()
         v = (C.c_uint64 * 4)()
         if frustum is None:
             self._check(self._L.m2s_lod_select_budget(self._h, C.byref(pc), C.byref(res), v))
+        elif occluder is not None:
+            self._check(self._L.m2s_lod_select_budget_occluded(self._h, C.byref(pc), C.byref(frustum), C.byref(occluder), C.byref(res), v))
         else:
             self._check(self._L.m2s_lod_select_budget_frustum(self._h, C.byref(pc), C.byref(frustum), C.byref(res), v))
         out = {name: int(v[k]) for k, name in enumerate(_ld.SELECT_COUNTS)}
@@ -1142,6 +1166,8 @@ class Converter:
         out["tau_px"], out["met"], out["selected_finer"] = float(res.tau_px), bool(res.met), int(res.selected_finer)
         if frustum is not None:
             self._lod_frustum_counts(out)
+        if occluder is not None:
+            out.update(self.last_lod_occlusion_counts())
         return out
 
     def download_lod(self, which: int) -> np.ndarray:

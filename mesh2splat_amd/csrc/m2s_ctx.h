@@ -268,6 +268,10 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     uint64_t last_lod_frustum_counts[2] = { 0, 0 };
     float last_lod_frustum_ms = 0.0f;
     m2s_host::ClockOf<m2s_host::SpanMark> lod_vis_clock;
+    // the same two cuts behind an occluder (m2s_lod_select_occluded, m2s_lod_select_budget_occluded): a host depth image's copy on the
+    // device (no other pass reads it), and the leaves inside the frustum, occluded, behind the image but kept, and the nodes dropped
+    m2s_host::DevBuf<float> d_lod_occ_depth;             // capacity in texels
+    uint64_t last_lod_occlusion_counts[4] = { 0, 0, 0, 0 };
     // world units (m2s_worldunits.cpp)
     float last_world_units_ms = 0.0f;
     m2s_host::ClockOf<m2s_host::SpanMark> wu_clock;

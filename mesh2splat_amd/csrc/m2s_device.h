@@ -341,8 +341,10 @@ hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32
 struct LodSelectK { float cx, cy, cz, focal, tau2, near2; };
 constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine,
 constexpr uint32_t kLodPlainWord = 18;     // [18] nodes the cut selects before the visibility plane masks it (written with a plane only),
-constexpr uint32_t kLodInsideWord = 19;    // [19] leaves inside the frustum (written by lod_visibility)
-constexpr uint32_t kLodCountWords = 20;
+constexpr uint32_t kLodInsideWord = 19;    // [19] leaves inside the frustum (written by lod_visibility),
+constexpr uint32_t kLodOccludedWord = 20;  // [20] of those, the leaves an occluder's depth image hides, [21] of those inside, the leaves behind
+constexpr uint32_t kLodKeptWord = 21;      // the image that stay for their alpha (both written by lod_visibility with an occluder only: the three are neighbours)
+constexpr uint32_t kLodCountWords = 22;
 // The sweep, one launch per level from the last to the leaves: per node of [first[l], first[l + 1]) the pinned comparison,
 // open[i] = refine && open[parent[i]] (levels above the leaves), flags[i] = selected; counts (zeroed by the caller) as above.
 // vis (NULL: none): the visibility plane of lod_visibility; flags[i] = selected && vis[i] then, and the per-level counts are the masked ones.
@@ -374,11 +376,17 @@ hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, bool 
 // ---- the visibility plane of the frustum cuts (m2s_lodfrustum.hip) -----------------------------------------------------------------------
 // The three matrices of m2s_prepass_params (column-major) and the guard band, as a kernel argument.
 struct LodFrustumK { float M[16], V[16], P[16]; float guard; };
+// The depth image behind m2s_lod_occluder, on the device: depth_w x depth_h floats, row 0 = bottom; the tree's node records (plane 0, 24
+// floats each), whose color[3] the test reads; the bias of the comparison.
+struct LodOccluderK { const float* depth; const float* nodes; uint32_t depth_w, depth_h; float bias; };
 // vis: one byte per node.  Zeroes them (stream-ordered memset), then one launch per level from the leaves up to the level below the last
 // (one launch for a tree of one level): vis[i] = 1 for a leaf whose position passes the prepass's frustum test with this guard band, and
 // for every node with a visible child; the leaves that pass are added to *inside_word (zeroed by the caller).
-hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f, uint8_t* vis,
-                          uint32_t* inside_word, hipStream_t st);
+// occ (NULL: none): a leaf that passes the frustum test, lies behind the image by more than the bias and has alpha > .95 is not
+// visible; inside_word[0] counts the leaves that pass the frustum test all the same, inside_word[1] the ones hidden, inside_word[2]
+// the ones behind the image that stay (kLodInsideWord, kLodOccludedWord, kLodKeptWord).
+hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f,
+                          const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st);
 
 // ---- world units (m2s_worldunits.hip) ------------------------------------------------------------------------------------------------
 // dst[i] = src[i] with scale[0..2] divided by (float)R (IEEE, correctly rounded), every other word with its bits, for the n records.

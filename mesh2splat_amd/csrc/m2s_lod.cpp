@@ -1,5 +1,5 @@
-// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and their
-// _frustum forms): host side of m2s_lod.hip, m2s_lodbudget.hip and m2s_lodfrustum.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
+// m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their
+// _frustum and _occluded forms): host side of m2s_lod.hip, m2s_lodbudget.hip and m2s_lodfrustum.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
 // copied into a node pool and linked by their maps; the
 // cut's flags and offsets live where m2s_prune leaves its own, and the compaction is m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue);
 // what a cut does to the context: m2s_recstate.h, Rewrite::LodCut.
@@ -73,15 +73,51 @@ m2s_status lod_frustum_check(m2s_ctx* c, const m2s_lod_frustum* fr) {
     return M2S_OK;
 }
 
+// pin 4 of the occluded cuts, but for the state of the context (lod_occluder_state)
+m2s_status lod_occluder_check(m2s_ctx* c, const m2s_lod_occluder* oc) {
+    if (!oc) return fail(c, M2S_ERR_INVALID, "no occluder");
+    if (!std::isfinite(oc->depth_bias) || !(oc->depth_bias >= 0.0f)) return fail(c, M2S_ERR_INVALID, "depth_bias is not finite or negative");
+    if (oc->reserved[0] || oc->reserved[1]) return fail(c, M2S_ERR_INVALID, "a reserved word of the occluder is not 0");
+    if (oc->depth && (!oc->depth_w || !oc->depth_h)) return fail(c, M2S_ERR_INVALID, "a depth image of width or height 0");
+    if (!oc->depth && c->md_w && (oc->depth_w || oc->depth_h) && (oc->depth_w != (uint32_t)c->md_w || oc->depth_h != (uint32_t)c->md_h))
+        return fail(c, M2S_ERR_INVALID, "depth is NULL and depth_w x depth_h is not the size of the context's mesh depth image");
+    return M2S_OK;
+}
+
+m2s_status lod_occluder_state(m2s_ctx* c, const m2s_lod_occluder* oc) {
+    if (!oc->depth && !c->md_w) return fail(c, M2S_ERR_STATE, "depth is NULL and no m2s_mesh_depth has run");
+    return M2S_OK;
+}
+
 // The visibility plane of the tree's N > 0 nodes for one frustum, timed by lod_vis_clock, which whoever calls this has opened for the call
 // (in front of its test for an empty tree, so that the cut reads 0 where this never ran).
 // The cut's count words are zeroed here, in front of the stage that writes the first of them.
-m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr) {
+// oc (NULL: none): the leaves are tested against this depth image too; a host image is copied in front of the stage, into a buffer
+// that no other pass reads.
+m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr, const m2s_lod_occluder* oc) {
     M2S_TRY(c->d_lod_vis.reserve(c->err, c->lod_first[c->lod_levels], 1));
     M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+    LodOccluderK ok = {};
+    if (oc) {
+        ok.nodes = reinterpret_cast<const float*>(c->d_lod_nodes.get());
+        ok.bias = oc->depth_bias;
+        if (!oc->depth) {
+            ok.depth = c->d_md_image; ok.depth_w = (uint32_t)c->md_w; ok.depth_h = (uint32_t)c->md_h;
+        } else {
+            ok.depth_w = oc->depth_w; ok.depth_h = oc->depth_h;
+            if (oc->depth_on_device) ok.depth = oc->depth;
+            else {
+                const uint64_t texels = (uint64_t)oc->depth_w * oc->depth_h;
+                M2S_TRY(c->d_lod_occ_depth.reserve(c->err, texels, sizeof(float)));
+                HIPCHK(c, hipMemcpyAsync(c->d_lod_occ_depth, oc->depth, texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
+                ok.depth = c->d_lod_occ_depth;
+            }
+        }
+        if (!ok.depth || !ok.depth_w || !ok.depth_h) return fail(c, M2S_ERR_STATE, "the occluder has no depth image (internal error)");
+    }
     HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
     HIPCHK(c, c->lod_vis_clock.mark(SpanMark::Begin, c->stream));
-    HIPCHK(c, lod_visibility(c->d_lod_bounds, c->d_lod_parent, c->lod_first, c->lod_levels, lod_frustum_k(fr), c->d_lod_vis,
+    HIPCHK(c, lod_visibility(c->d_lod_bounds, c->d_lod_parent, c->lod_first, c->lod_levels, lod_frustum_k(fr), oc ? &ok : nullptr, c->d_lod_vis,
                              c->d_lod_counts + kLodInsideWord, c->stream));
     HIPCHK(c, c->lod_vis_clock.mark(SpanMark::End, c->stream));
     return M2S_OK;
@@ -89,10 +125,11 @@ m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr) {
 
 // The cut behind m2s_lod_select's checks of its arguments and the context's state (m2s_lod_select_budget takes its own through it).
 // fr (NULL: the plain cut): only nodes with a leaf inside this frustum are selected.  vis: who runs lod_vis_enqueue for it, which also
-// zeroes the cut's count words in front of the inside count it adds to them.
+// zeroes the cut's count words in front of the inside count it adds to them.  oc (NULL: none; only with fr): ... and not behind this image.
 enum class LodVis { None, Here, Enqueued };     // no frustum | lod_cut enqueues it | the caller has, earlier on the stream (the budget search reads the plane first)
-m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4], const m2s_lod_frustum* fr, LodVis vis) {
-    if ((fr != nullptr) != (vis != LodVis::None)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
+m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_counts[4], const m2s_lod_frustum* fr, LodVis vis,
+                   const m2s_lod_occluder* oc = nullptr) {
+    if ((fr != nullptr) != (vis != LodVis::None) || (oc && !fr)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
     const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
     const bool with_sh = c->lod_has_sh && !dry;     // (pin 3s: the tree's property decides, not the switch at the time of the cut)
     ClockOf<LodCutMark>& clock = c->lod_cut_clock;
@@ -115,7 +152,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         uint32_t* const flags = c->d_prune_u32;
         uint32_t* const offsets = flags + c->d_prune_u32.cap();
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near };
-        if (vis == LodVis::Here) M2S_TRY(lod_vis_enqueue(c, fr));
+        if (vis == LodVis::Here) M2S_TRY(lod_vis_enqueue(c, fr, oc));
         HIPCHK(c, clock.mark(LodCutMark::Start, c->stream));
         // (with a frustum the words were zeroed by lod_vis_enqueue, here or in the caller, and hold the inside count by now: not again)
         if (vis == LodVis::None) HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
@@ -131,7 +168,8 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t l = 0; l < levels; ++l) selected += h[l];
         // (a frustum may leave nothing; the plain cut holds every leaf's ancestor-or-self)
-        if ((selected < 1 && !fr) || selected > N || h[kLodRefineWord] > N || (fr && (h[kLodPlainWord] < selected || h[kLodPlainWord] > N || h[kLodInsideWord] > N)))
+        if ((selected < 1 && !fr) || selected > N || h[kLodRefineWord] > N || (fr && (h[kLodPlainWord] < selected || h[kLodPlainWord] > N || h[kLodInsideWord] > N)) ||
+            (uint64_t)h[kLodOccludedWord] + h[kLodKeptWord] > h[kLodInsideWord])
             return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
         if (!dry) {
             M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
@@ -170,6 +208,10 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
     c->last_lod_select_counts[3] = h[kLodRefineWord];
     for (uint32_t l = 0; l <= M2S_LOD_MAX_STEPS; ++l) c->last_lod_level_counts[l] = l < levels ? h[l] : 0;
     if (fr) { c->last_lod_frustum_counts[0] = h[kLodInsideWord]; c->last_lod_frustum_counts[1] = h[kLodPlainWord] - selected; }
+    if (oc) {
+        c->last_lod_occlusion_counts[0] = h[kLodInsideWord]; c->last_lod_occlusion_counts[1] = h[kLodOccludedWord];
+        c->last_lod_occlusion_counts[2] = h[kLodKeptWord]; c->last_lod_occlusion_counts[3] = h[kLodPlainWord] - selected;
+    }
     if (out_counts) std::memcpy(out_counts, c->last_lod_select_counts, sizeof(c->last_lod_select_counts));
     return M2S_OK;
 }
@@ -196,8 +238,9 @@ m2s_status lod_budget_check(m2s_ctx* c, const m2s_lod_budget_params* p) {
 }
 
 // m2s_lod_select_budget behind its checks.  fr (NULL: the plain search): the nodes without a leaf inside are selected at no key, and
-// the budget is raised to the visible nodes of the last level on the device.
-m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out, uint64_t out_counts[4]) {
+// the budget is raised to the visible nodes of the last level on the device.  oc (NULL: none; only with fr): as for lod_cut.
+m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out, uint64_t out_counts[4],
+                      const m2s_lod_occluder* oc = nullptr) {
     ClockOf<LodBudgetMark>& clock = c->lod_budget_clock;
     const uint32_t levels = c->lod_levels;
     const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
@@ -212,7 +255,7 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
         M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
         const uint32_t n_eff = fr ? p->max_records : (uint32_t)std::max<uint64_t>(p->max_records, last);
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
-        if (fr) M2S_TRY(lod_vis_enqueue(c, fr));
+        if (fr) M2S_TRY(lod_vis_enqueue(c, fr, oc));
         HIPCHK(c, clock.mark(LodBudgetMark::Start, c->stream));
         HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, fr ? c->d_lod_vis.get() : nullptr, c->stream));
         HIPCHK(c, clock.mark(LodBudgetMark::Thresholds, c->stream));
@@ -232,7 +275,7 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
     sp.near = p->near;
     sp.flags = p->flags;
     uint64_t counts[4] = {};
-    M2S_TRY(lod_cut(c, &sp, counts, fr, fr ? LodVis::Enqueued : LodVis::None));
+    M2S_TRY(lod_cut(c, &sp, counts, fr, fr ? LodVis::Enqueued : LodVis::None, oc));
     if (clock.on()) {
         float* ms = c->last_lod_budget_stage_ms;
         HIPCHK(c, clock.span(LodBudgetMark::Start, LodBudgetMark::Thresholds, &ms[0]));      // (an empty tree: 0, like the next)
@@ -371,6 +414,7 @@ m2s_status m2s_lod_release(m2s_ctx* c) {
     c->lod_has_sh = false;
     c->d_lod_sh.release();
     c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release(); c->d_lod_vis.release();
+    c->d_lod_occ_depth.release();
     return M2S_OK;
 }
 
@@ -416,6 +460,35 @@ m2s_status m2s_lod_select_budget_frustum(m2s_ctx* c, const m2s_lod_budget_params
     if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
     return lod_budget(c, p, fr, out, out_counts);
 }
+
+m2s_status m2s_lod_select_occluded(m2s_ctx* c, const m2s_lod_select_params* p, const m2s_lod_frustum* fr, const m2s_lod_occluder* oc,
+                                   uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    M2S_TRY(lod_select_check(c, p));
+    M2S_TRY(lod_frustum_check(c, fr));
+    M2S_TRY(lod_occluder_check(c, oc));
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_occluder_state(c, oc));
+    return lod_cut(c, p, out_counts, fr, LodVis::Here, oc);
+}
+
+m2s_status m2s_lod_select_budget_occluded(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, const m2s_lod_occluder* oc,
+                                          m2s_lod_budget_result* out, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!c || !p) return M2S_ERR_INVALID;
+    M2S_TRY(lod_budget_check(c, p));
+    M2S_TRY(lod_frustum_check(c, fr));
+    M2S_TRY(lod_occluder_check(c, oc));
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_occluder_state(c, oc));
+    return lod_budget(c, p, fr, out, out_counts, oc);
+}
+
+m2s_status m2s_last_lod_occlusion_counts(const m2s_ctx* c, uint64_t out[4]) { return get_array(c, &m2s_ctx::last_lod_occlusion_counts, out); }
 
 m2s_status m2s_last_lod_frustum_counts(const m2s_ctx* c, uint64_t out[2]) { return get_array(c, &m2s_ctx::last_lod_frustum_counts, out); }
 

@@ -57,14 +57,7 @@ __device__ __forceinline__ bool prepass_one(const PrepassK& k, const float4 (&g)
     if (!view_project(k.M, k.V, k.P, gpos.x, gpos.y, gpos.z, ws, vs, pos2d)) vis = false;   // :67-77
 
     if (k.depth_test == 1u && gcol.w > .95f && k.format == 0u && vis) {          // :80-92
-        const float u = (pos2d.x / pos2d.w) * 0.5f + 0.5f, v = (pos2d.y / pos2d.w) * 0.5f + 0.5f;
-        // GL_NEAREST, CLAMP_TO_EDGE (renderer.cpp:290-296): texel floor(u*W), clamped; NaN -> 0
-        const float fu = floorf(u * (float)k.depth_w), fv = floorf(v * (float)k.depth_h);
-        const uint32_t ti = fu >= 0.0f ? (fu < (float)k.depth_w ? (uint32_t)fu : k.depth_w - 1u) : 0u;
-        const uint32_t tj = fv >= 0.0f ? (fv < (float)k.depth_h ? (uint32_t)fv : k.depth_h - 1u) : 0u;
-        const float depth = k.depth[(size_t)tj * k.depth_w + ti];
-        const float my_depth = (pos2d.z / pos2d.w) * 0.5f + 0.5f;
-        if (my_depth > depth + 0.00002f) vis = false;
+        if (depth_behind(pos2d, k.depth, k.depth_w, k.depth_h, 0.00002f)) vis = false;   // (m2s_viewmath.h, shared with the occluded LOD cuts)
     }
 
     M3 rot;

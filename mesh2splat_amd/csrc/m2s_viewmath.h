@@ -31,6 +31,20 @@ __device__ __forceinline__ bool clip_inside(float4 pos2d, float guard) {
     return !(pos2d.z < -clip || pos2d.x < -clip || pos2d.x > clip || pos2d.y < -clip || pos2d.y > clip);
 }
 
+// :82-91: the test against the mesh depth texture for a clip-space position that passed the frustum test (true = behind the mesh by
+// more than `bias`; the shader's own bias is 0.00002).  depth: depth_w x depth_h window-space depths, row 0 = bottom, sampled
+// GL_NEAREST, CLAMP_TO_EDGE (renderer.cpp:290-296): texel floor(u * W), clamped; NaN -> 0.  Every comparison is false for a NaN.
+// One definition for k_prepass (m2s_prepass.hip) and the occluded leaf test of the level-of-detail cuts (m2s_lodfrustum.hip).
+__device__ __forceinline__ bool depth_behind(float4 pos2d, const float* depth, uint32_t depth_w, uint32_t depth_h, float bias) {
+    const float u = (pos2d.x / pos2d.w) * 0.5f + 0.5f, v = (pos2d.y / pos2d.w) * 0.5f + 0.5f;
+    const float fu = floorf(u * (float)depth_w), fv = floorf(v * (float)depth_h);
+    const uint32_t ti = fu >= 0.0f ? (fu < (float)depth_w ? (uint32_t)fu : depth_w - 1u) : 0u;
+    const uint32_t tj = fv >= 0.0f ? (fv < (float)depth_h ? (uint32_t)fv : depth_h - 1u) : 0u;
+    const float d = depth[(size_t)tj * depth_w + ti];
+    const float my_depth = (pos2d.z / pos2d.w) * 0.5f + 0.5f;
+    return my_depth > d + bias;
+}
+
 // :67-77.  ws = u_modelToWorld * vec4(P, 1); vs = u_worldToView * vec4(ws.xyz, 1); pos2d = u_viewToClip * vs; inside = the guard-band
 // frustum test (false = culled; every comparison is false for NaN: such a record is NOT culled here, as in the shader).
 __device__ __forceinline__ bool view_project(const float* M, const float* V, const float* P, float px, float py, float pz, float4& ws, float4& vs, float4& pos2d) {

@@ -1,6 +1,6 @@
 """The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_select_budget` / `.lod_levels` /
-`.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and the _frustum forms
-of the two cuts): the ctypes mirrors of their parameters and the two numbers a cut takes from a camera.  The pins are in include/m2s.h.
+`.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and the _frustum and
+_occluded forms of the two cuts): the ctypes mirrors of their parameters and the two numbers a cut takes from a camera.  The pins are in include/m2s.h.
 
 The default chain of merge levels (1 .. 8), like max_group = 4 and min_axis_dot = 0.5, is a guess: nothing in the repository has
 tuned it (tools/lod_probe.py reports what it does on one scene)."""
@@ -18,6 +18,7 @@ DEFAULT_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8)
 BUILD_COUNTS = ("leaves", "nodes", "levels", "skipped")      # m2s_lod_build's out_counts, in order
 SELECT_COUNTS = ("nodes", "selected", "selected_leaves", "refine")   # m2s_lod_select's
 FRUSTUM_COUNTS = ("visible_leaves", "culled")                # m2s_last_lod_frustum_counts', in order
+OCCLUSION_COUNTS = ("visible_leaves", "occluded_leaves", "translucent_kept", "culled")   # m2s_last_lod_occlusion_counts', in order
 PLANES = {0: (np.float32, 24), 1: (np.uint32, None), 2: (np.float32, 4)}    # m2s_download_lod: which -> (dtype, row length)
 
 
@@ -57,6 +58,12 @@ class LodFrustumC(C.Structure):
     """== m2s_lod_frustum (include/m2s.h)."""
     _fields_ = [("model_to_world", C.c_float * 16), ("world_to_view", C.c_float * 16), ("view_to_clip", C.c_float * 16),
                 ("guard_band", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class LodOccluderC(C.Structure):
+    """== m2s_lod_occluder (include/m2s.h)."""
+    _fields_ = [("depth", C.c_void_p), ("depth_w", C.c_uint32), ("depth_h", C.c_uint32), ("depth_on_device", C.c_uint32),
+                ("depth_bias", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
 def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> LodBuildParamsC:
@@ -100,6 +107,38 @@ def frustum_to_c(model_to_world, world_to_view, view_to_clip, guard_band: float 
             raise ValueError(f"{name}: 16 floats expected")
         getattr(c, name)[:] = a.tolist()
     c.guard_band = float(np.float32(guard_band))
+    return c
+
+
+def occluder_to_c(depth_hw_float32, depth_bias: float = 2e-5) -> LodOccluderC:
+    """A host depth image (H, W) float32, window-space depth in [0, 1], row 0 = the bottom row (the layout of PrepassParams' depth
+    image), as the occluder of lod_select / lod_select_budget; 2e-5 is the prepass's own bias.  The array is kept alive by the
+    returned structure."""
+    a = np.ascontiguousarray(depth_hw_float32, np.float32)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("depth image: a non-empty (H, W) array expected")
+    c = LodOccluderC()
+    c.depth = a.ctypes.data
+    c.depth_h, c.depth_w = int(a.shape[0]), int(a.shape[1])
+    c.depth_on_device, c.depth_bias = 0, float(np.float32(depth_bias))
+    c._keep = a
+    return c
+
+
+def occluder_on_device(pointer: int, depth_w: int, depth_h: int, depth_bias: float = 2e-5) -> LodOccluderC:
+    """A depth image that already lies on the context's device (depth_h rows of depth_w floats, row 0 = bottom), not copied."""
+    c = LodOccluderC()
+    c.depth, c.depth_w, c.depth_h = int(pointer), int(depth_w), int(depth_h)
+    c.depth_on_device, c.depth_bias = 1, float(np.float32(depth_bias))
+    return c
+
+
+def occluder_of_mesh_depth(conv=None, depth_bias: float = 2e-5) -> LodOccluderC:
+    """The image of the context's last mesh_depth() as occluder: a NULL image, which the library reads as the context's own.  `conv`
+    (the Converter the cut will run on) is not read; it documents whose image is meant."""
+    c = LodOccluderC()
+    c.depth, c.depth_w, c.depth_h = None, 0, 0
+    c.depth_on_device, c.depth_bias = 1, float(np.float32(depth_bias))
     return c
 
 

@@ -9,6 +9,7 @@ against the mesh for the cut, for the full records and for merge_to_budget to th
     python tools/lod_probe.py --world-units --unsigned-axis [--frames] --out profiles/lod/probe_unsigned.json
     python tools/lod_probe.py --budget [--budgets 50000,200000,1000000] [--out profiles/lod/probe_budget.json]
     python tools/lod_probe.py --frustum [--factors 0.25,0.5,1,2] [--tau 1,2,4] [--budgets ...] [--out profiles/lod/probe_frustum.json]
+    python tools/lod_probe.py --occlusion [--factors 0.25,0.5,1,2] [--tau 1,2,4] [--budgets ...] [--out profiles/lod/probe_occlusion.json]
 
 --world-units: every conversion is followed by m2s_records_to_world_units, so the tree's edges are world lengths and tau_px counts
 screen pixels (default --tau 1,2,4); the result also carries the pass's own time (in place, and out of place from adopted memory) beside
@@ -30,6 +31,12 @@ factor with the preview camera's own matrices and the prepass's guard band: the 
 three cut stages beside the plain m2s_lod_select at the same tau, the counts of both, and m2s_prepass_sorted (keys with the frustum
 test, radix sort, prepass over the survivors) + m2s_splat of the frame drawn from either result; per budget the tau_px, the counts and
 the stages of both budget functions.  The yardstick is the plain calls; which of the two runs first alternates between repetitions.
+
+--occlusion: m2s_lod_select_occluded and m2s_lod_select_budget_occluded in the cells of --frustum (the same tree, cameras, taus and
+budgets), each beside the frustum call of the same cell, which is the yardstick: the depth image is the context's own, drawn by
+m2s_mesh_depth through the cell's camera at 1920 x 1080, whose time is reported apart (it is what the occluded cut costs on top); per
+call the leaves inside the frustum, the occluded ones, the tau_px, the selected records, the quads the frame after it draws (its prepass
+runs without the depth test), the visibility stage, the stages of the cut and the whole call on the host's clock.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
 tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
@@ -56,14 +63,15 @@ def main():
     ap.add_argument("--budget", action="store_true")
     ap.add_argument("--budgets", default="50000,200000,1000000")
     ap.add_argument("--frustum", action="store_true")
+    ap.add_argument("--occlusion", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    if a.frustum and a.budget:
-        ap.error("--frustum and --budget are two runs: give one of them")
-    a.factors = a.factors or ("0.25,0.5,1,2" if a.frustum else "1,2,4,8")
-    if a.frustum:
+    if a.frustum + a.budget + a.occlusion > 1:
+        ap.error("--frustum, --occlusion and --budget are three runs: give one of them")
+    a.factors = a.factors or ("0.25,0.5,1,2" if a.frustum or a.occlusion else "1,2,4,8")
+    if a.frustum or a.occlusion:
         a.world_units = True
-        a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_frustum.json")
+        a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_occlusion.json" if a.occlusion else "probe_frustum.json")
     if a.budget:
         a.world_units = True
         a.out = a.out or os.path.join(ROOT, "profiles", "lod", "probe_budget.json")
@@ -140,8 +148,11 @@ def main():
                 rows.append(ms)
         return counts, median_of(rows)
 
-    if a.frustum:
+    if a.frustum or a.occlusion:
+        import time
+        from mesh2splat_amd.meshdepth import MeshDepthParams
         from mesh2splat_amd.splat import SplatParams
+        yard, mine = ("frustum", "occluded") if a.occlusion else ("plain", "frustum")     # the yardstick and the call measured against it
         records = convert()
         build = conv.lod_build(unsigned_axis=True)
         first = build["first"]
@@ -163,17 +174,22 @@ def main():
             ms["total"] = ms["prepass_sorted"] + ms["splat"]
             return drawn, ms
 
-        def pair(cam, call, stages, fr):
-            """warmup + reps of one cut without and with the frustum, each followed by its frame; which of the two runs first alternates
-            from one repetition to the next -> {"plain" | "frustum": (result, quads drawn, median stages, median frame passes)}"""
-            modes = (("plain", None), ("frustum", fr))
-            rows, frames, got, drawn = {"plain": [], "frustum": []}, {"plain": [], "frustum": []}, {}, {}
+        def pair(cam, call, stages, fr, occ=None):
+            """warmup + reps of one cut without and with the frustum (--occlusion: with the frustum, without and with the occluder), each
+            followed by its frame; which of the two runs first alternates from one repetition to the next
+            -> {yard | mine: (result, quads drawn, median stages, median frame passes)}"""
+            modes = ((yard, {"frustum": fr}), (mine, {"frustum": fr, "occluder": occ})) if a.occlusion else ((yard, {"frustum": None}), (mine, {"frustum": fr}))
+            rows, frames, got, drawn = {yard: [], mine: []}, {yard: [], mine: []}, {}, {}
             for k in range(a.warmup + a.reps):
-                for name, frustum in (modes if k % 2 == 0 else modes[::-1]):
-                    now = call(frustum)
+                for name, kw in (modes if k % 2 == 0 else modes[::-1]):
+                    t0 = time.perf_counter()
+                    now = call(**kw)
+                    call_ms = (time.perf_counter() - t0) * 1e3
                     assert name not in got or now == got[name]                        # integer sums: the same from run to run
                     got[name] = now
-                    ms = stages(frustum)
+                    ms = stages(kw["frustum"])
+                    if a.occlusion:
+                        ms["call"] = call_ms                                          # (the host's clock: the counts' round trips and the dict included)
                     drawn[name], fm = draw(cam)
                     if k >= a.warmup:
                         rows[name].append(ms)
@@ -187,6 +203,15 @@ def main():
             ms["total"] = sum(ms.values())
             return ms
 
+        def mesh_depth_ms(cam):
+            """m2s_mesh_depth through this camera at W x H, warmup + reps times: the image stays the context's -> median ms"""
+            rows = []
+            for k in range(a.warmup + a.reps):
+                conv.mesh_depth(MeshDepthParams(cam.view_mat, cam.proj_mat, np.eye(4, dtype=np.float32), (W, H)), download=False)
+                if k >= a.warmup:
+                    rows.append(conv.last_mesh_depth_ms)
+            return statistics.median(rows)
+
         def budget_stages(frustum):
             ms = dict(conv.last_lod_budget_stage_ms)
             if frustum:
@@ -199,16 +224,22 @@ def main():
             eye, focal = lod.camera_position(cam.view_mat), lod.focal_px(cam.proj_mat, H)
             fr = lod.frustum_to_c(np.eye(4, dtype=np.float32), cam.view_mat, cam.proj_mat, 1.05)
             cell = {"factor": f, "cuts": [], "budgets": []}
+            occ = None
+            if a.occlusion:
+                cell["mesh_depth_ms"] = mesh_depth_ms(cam)                            # counted apart: no cut's time holds it
+                occ = lod.occluder_of_mesh_depth(conv)
             for tau in [float(v) for v in a.tau.split(",")]:
                 row = {"tau_px": tau}
-                for name, (got, drawn, stage, fm) in pair(cam, lambda frustum: conv.lod_select(eye, focal, tau, cam.near, frustum=frustum), select_stages, fr).items():
+                for name, (got, drawn, stage, fm) in pair(cam, lambda **kw: conv.lod_select(eye, focal, tau, cam.near, **kw), select_stages, fr, occ).items():
                     row[name] = {"counts": got, "quads_drawn": drawn, "select_stage_ms": stage, "frame_pass_ms": fm}
-                cell["visible_leaves"] = row["frustum"]["counts"]["visible_leaves"]
+                cell["visible_leaves"] = row[mine]["counts"]["visible_leaves"]
+                if a.occlusion:
+                    cell["occluded_leaves"] = row[mine]["counts"]["occluded_leaves"]
                 cell["cuts"].append(row)
             for budget in [int(v) for v in a.budgets.split(",")]:
                 row = {"budget": budget}
-                for name, (got, drawn, stage, fm) in pair(cam, lambda frustum: conv.lod_select_budget(eye, focal, budget, near=cam.near, frustum=frustum),
-                                                          budget_stages, fr).items():
+                for name, (got, drawn, stage, fm) in pair(cam, lambda **kw: conv.lod_select_budget(eye, focal, budget, near=cam.near, **kw),
+                                                          budget_stages, fr, occ).items():
                     row[name] = {"result": got, "quads_drawn": drawn, "budget_stage_ms": stage, "frame_pass_ms": fm}
                 cell["budgets"].append(row)
             res["cells"].append(cell)

@@ -91,6 +91,8 @@ struct Options {
     double view_distance = 1.0;                                    // --view-distance f (0.25..64): the --preview / --score eyes at f x the preview rule's distance, the far plane f x as far
     long long lod_budget = 0;                                      // --lod-budget N: every camera takes the finest cut of at most N records (m2s_lod_select_budget); --lod-pixels is then its floor
     double lod_guard = -1.0;                                       // --lod-frustum [--lod-guard g]: the cuts select only what their camera sees (m2s_lod_select_frustum,
+    bool lod_occlusion = false;                                    // --lod-occlusion [--lod-depth-bias b]: ... and that the mesh does not hide (m2s_mesh_depth per camera, then
+    double lod_depth_bias = -1.0;                                  //   m2s_lod_select_occluded, m2s_lod_select_budget_occluded); implies --lod-frustum; b >= 0, 0.00002 without --lod-depth-bias
     bool lod_frustum = false;                                      //   m2s_lod_select_budget_frustum), the frustum test widened by g (>= 1; 1.05, the prepass's own, without --lod-guard)
     std::string lod_ply;                                           // --lod-ply cut.ply: the --preview camera's cut as a .ply (with --bake-light: its carried SH plane, m2s_set_carry_sh)
     bool lod() const { return !lod_levels.empty(); }
@@ -116,7 +118,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]] [--lod-ply cut.ply]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]] [--lod-occlusion [--lod-depth-bias b]] [--lod-ply cut.ply]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -184,6 +186,12 @@ void usage() {
                  "  camera's frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum), and a budget is spent on those alone.  The `lod:`\n"
                  "  line then has \"frustum\": g, and every entry of `views` \"visible_leaves\" and \"culled\" (nodes the plain cut selects\n"
                  "  and this one dropped).\n"
+                 "--lod-occlusion [--lod-depth-bias b] (b >= 0, default 0.00002), with --lod-levels; implies --lod-frustum: in front of every cut the\n"
+                 "  mesh is drawn depth-only through that cut's camera at --preview-size (m2s_mesh_depth), and a leaf behind that image under the\n"
+                 "  prepass's own depth test is not inside either (m2s_lod_select_occluded, m2s_lod_select_budget_occluded): the far side of a\n"
+                 "  closed mesh is neither selected nor charged to a budget.  The `lod:` line then has \"depth_bias\": b, and every entry of `views`\n"
+                 "  \"occluded\" and \"translucent_kept\" (leaves behind the image kept for an alpha <= .95).  Not with --mesh-depth-test: a merged\n"
+                 "  node lies under the surface its leaves lie on, and the prepass's depth test of its own position would cull it.\n"
                  "--lod-ply cut.ply, with --lod-levels and --preview (one file, one GPU): right after the --preview camera's cut its records are\n"
                  "  written to cut.ply, in --format (m2s_export_ply).  With --bake-light the baked plane is carried through the tree and the cut\n"
                  "  (m2s_set_carry_sh, switched on in front of the bake) and cut.ply carries the SH element (m2s_export_ply_sh).  The `lod:` line\n"
@@ -361,6 +369,19 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float wor
     std::memcpy(fr.world_to_view, world_to_view, sizeof(fr.world_to_view));
     std::memcpy(fr.view_to_clip, view_to_clip, sizeof(fr.view_to_clip));
     fr.guard_band = (float)o.lod_guard;
+    m2s_lod_occluder oc;                                                // --lod-occlusion: the mesh through this camera, the context's own image (depth NULL)
+    std::memset(&oc, 0, sizeof(oc));
+    oc.depth_on_device = 1;
+    oc.depth_bias = (float)o.lod_depth_bias;
+    if (o.lod_occlusion) {
+        m2s_mesh_depth_params mp;
+        std::memset(&mp, 0, sizeof(mp));
+        std::memcpy(mp.world_to_view, fr.world_to_view, sizeof(mp.world_to_view));
+        std::memcpy(mp.view_to_clip, fr.view_to_clip, sizeof(mp.view_to_clip));
+        std::memcpy(mp.model_to_world, fr.model_to_world, sizeof(mp.model_to_world));
+        mp.resolution[0] = o.preview_w; mp.resolution[1] = o.preview_h;
+        if (m2s_mesh_depth(ctx, &mp, nullptr) != M2S_OK) return 1;
+    }
     if (o.lod_budget > 0) {                                             // the cut that fits: --lod-pixels, where given, is its floor
         m2s_lod_budget_params bp;
         std::memset(&bp, 0, sizeof(bp));
@@ -371,18 +392,25 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float wor
         bp.max_records = (uint32_t)o.lod_budget;
         bp.flags = sp.flags;
         m2s_lod_budget_result res;
-        if ((o.lod_frustum ? m2s_lod_select_budget_frustum(ctx, &bp, &fr, &res, c) : m2s_lod_select_budget(ctx, &bp, &res, c)) != M2S_OK) return 1;
+        if ((o.lod_occlusion ? m2s_lod_select_budget_occluded(ctx, &bp, &fr, &oc, &res, c)
+             : o.lod_frustum ? m2s_lod_select_budget_frustum(ctx, &bp, &fr, &res, c) : m2s_lod_select_budget(ctx, &bp, &res, c)) != M2S_OK) return 1;
         char tau[40];
         std::snprintf(tau, sizeof tau, "%.9g", (double)res.tau_px);
         budget = std::string(", \"tau_px\": ") + tau + ", \"met\": " + (res.met ? "true" : "false") + ", \"selected_finer\": " +
                  std::to_string((unsigned long long)res.selected_finer);
-    } else if ((o.lod_frustum ? m2s_lod_select_frustum(ctx, &sp, &fr, c) : m2s_lod_select(ctx, &sp, c)) != M2S_OK) {
+    } else if ((o.lod_occlusion ? m2s_lod_select_occluded(ctx, &sp, &fr, &oc, c)
+                : o.lod_frustum ? m2s_lod_select_frustum(ctx, &sp, &fr, c) : m2s_lod_select(ctx, &sp, c)) != M2S_OK) {
         return 1;
     }
     if (o.lod_frustum) {
         uint64_t fc[2] = {};
         if (m2s_last_lod_frustum_counts(ctx, fc) != M2S_OK) return 1;
         budget += ", \"visible_leaves\": " + std::to_string((unsigned long long)fc[0]) + ", \"culled\": " + std::to_string((unsigned long long)fc[1]);
+    }
+    if (o.lod_occlusion) {
+        uint64_t ocn[4] = {};
+        if (m2s_last_lod_occlusion_counts(ctx, ocn) != M2S_OK) return 1;
+        budget += ", \"occluded\": " + std::to_string((unsigned long long)ocn[1]) + ", \"translucent_kept\": " + std::to_string((unsigned long long)ocn[2]);
     }
     if (m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
     std::string levels;
@@ -403,6 +431,11 @@ void lod_print(const Options& o, const LodReport& rep) {
         char g[40];
         std::snprintf(g, sizeof g, "%.9g", (double)(float)o.lod_guard);
         budget += std::string(", \"frustum\": ") + g;
+    }
+    if (o.lod_occlusion) {
+        char b[40];
+        std::snprintf(b, sizeof b, "%.9g", (double)(float)o.lod_depth_bias);
+        budget += std::string(", \"depth_bias\": ") + b;
     }
     std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
@@ -1263,6 +1296,8 @@ int main(int argc, char** argv) {
         else if (a == "--merge-dot") { o.merge_dot = std::atof(next()); if (std::isnan(o.merge_dot)) { usage(); return 2; } }
         else if (a == "--lod-pixels") { o.lod_pixels = std::atof(next()); if (!(o.lod_pixels >= 0.0) || !std::isfinite(o.lod_pixels)) { usage(); return 2; } }
         else if (a == "--lod-frustum") o.lod_frustum = true;
+        else if (a == "--lod-occlusion") o.lod_occlusion = true;
+        else if (a == "--lod-depth-bias") { o.lod_depth_bias = std::atof(next()); if (!(o.lod_depth_bias >= 0.0) || !std::isfinite(o.lod_depth_bias)) { usage(); return 2; } }
         else if (a == "--lod-ply") o.lod_ply = next();
         else if (a == "--lod-guard") { o.lod_guard = std::atof(next()); if (!(o.lod_guard >= 1.0) || !std::isfinite(o.lod_guard)) { usage(); return 2; } }
         else if (a == "--lod-budget") {
@@ -1342,6 +1377,10 @@ int main(int argc, char** argv) {
     // --lod-*: the levels with a bound in pixels, a budget or both, or none of them; the cuts need cameras (--preview / --score; a batch
     // draws no preview) and one context
     if (o.lod() != (o.lod_pixels >= 0.0 || o.lod_budget > 0)) { usage(); return 2; }
+    // (--lod-occlusion: a mode of the frustum cuts; --lod-depth-bias: of --lod-occlusion; not beside the prepass's own depth test, which
+    //  would cull a merged node by its own position under the surface; the mesh depth image is one context's)
+    if ((o.lod_occlusion && (!o.lod() || o.mesh_depth_test || o.gpus > 1)) || (o.lod_depth_bias >= 0.0 && !o.lod_occlusion)) { usage(); return 2; }
+    if (o.lod_occlusion) { o.lod_frustum = true; if (o.lod_depth_bias < 0.0) o.lod_depth_bias = 0.00002; }
     if ((o.lod_frustum && !o.lod()) || (o.lod_guard >= 0.0 && !o.lod_frustum)) { usage(); return 2; }   // (--lod-frustum: a mode of the cuts; --lod-guard: of --lod-frustum)
     if (o.lod_frustum && o.lod_guard < 0.0) o.lod_guard = 1.05;
     if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
