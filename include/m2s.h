@@ -905,6 +905,72 @@ m2s_status m2s_lod_select_budget_occluded(m2s_ctx* ctx, const m2s_lod_budget_par
                                           const m2s_lod_occluder* occluder, m2s_lod_budget_result* out, uint64_t out_counts[4]);
 m2s_status m2s_last_lod_occlusion_counts(const m2s_ctx* ctx, uint64_t out[4]);
 
+/* The blend: after any of the six cuts, every record of the cut is moved towards its node's parent as tau_px approaches the value at
+ * which the parent takes over, so that the records just before a switch are, up to rounding, the parent just after it — the cut no
+ * longer pops between levels (tests/lod_blend_ref.py restates it).  Which nodes are drawn does not change: counts, order,
+ * node indices and the tree stay as the cut left them.  All arithmetic is fp32, one rounding per operation, no contraction; every `/`
+ * is the IEEE division; no root.  Pinned:
+ *  1. Precondition.  The context's current records are what the last cut that was no dry run left (m2s_device_lod_nodes is valid for
+ *     them) and the tree that cut went through exists; M2S_ERR_STATE otherwise.  Record j is node i = ids[j]; p = parent[i].
+ *  2. Weight.  For a node n with bound (x, y, z, e): d2 and s exactly as in pin 1 of the cut, q(n) = (s * s) / d2.
+ *       t = 0 where p == M2S_LOD_NO_PARENT; otherwise
+ *       den = q(p) - q(i);  num = tau_px * tau_px - q(i);  t_raw = num / den;
+ *       t = fminf(fmaxf((t_raw - (1.0f - band)) / band, 0.0f), 1.0f);   t = 0 where !(den > 0).
+ *     A NaN anywhere gives 0 (fmaxf returns its other operand), a parent that projects no larger than its child gives 0, invalid
+ *     records — byte-identical singletons on every level, den == 0 — give 0.  t is linear in tau_px squared: the comparison's own
+ *     operands, no root.  For a fixed node and camera t does not decrease as the bits of tau_px increase.
+ *  3. Copy.  t == 0: the 96 bytes of tree node i, bit for bit.  The source of every record is the TREE (planes 0, 1 and the bounds),
+ *     never the context's records: the pass is idempotent and may be called again with another band.
+ *  4. Lerp.  u = 1.0f - t;  lerp(a, b) = u * a + t * b (two products, one sum; exactly b at t == 1 for finite a).  Lerped between node i
+ *     and node p: position[0..2], color[0..3], scale[2], normal[0..2], pbr[0..1].  The child's own bits are kept in position[3],
+ *     scale[3], normal[3], pbr[2..3].  The normal is not renormalised (the relighting and bake shaders normalise it).
+ *  5. Frame.  A flat record's covariance does not change when its frame turns by 90 degrees about r_3 with the two edges swapped, or by
+ *     180 degrees about r_1, and m2s_merge picks a parent's e1 by eigen-decomposition: child and parent frames may differ by such a
+ *     turn.  With the stored quaternion (w, x, y, z) = rotation[0..3] of the PARENT, eight candidates raw_k, each component one fp32 sum
+ *     or a copy (right-multiplication turns the body axes):
+ *       k = 0  none          ( w,       x,      y,      z     )
+ *       k = 1  Rz 90         ( w - z,   x + y,  y - x,  z + w )   scaled by kC, edges swapped
+ *       k = 2  Rz 180        (-z,       y,     -x,      w     )
+ *       k = 3  Rz 270        ( w + z,   x - y,  y + x,  z - w )   scaled by kC, edges swapped
+ *       k = 4  Rx 180        (-x,       w,      z,     -y     )
+ *       k = 5  diagonal      (-(x + y), w - z,  w + z,  x - y )   scaled by kC, edges swapped
+ *       k = 6  Ry 180        (-y,      -z,      w,      x     )
+ *       k = 7  antidiagonal  ( y - x,   w + z,  z - w, -(x + y))  scaled by kC, edges swapped
+ *     kC = 0.70710678118654752f.  With the child's quaternion c: d_k = (c0 r0 + c1 r1) + (c2 r2 + c3 r3) over raw_k; the score is
+ *     d_k * d_k, times 0.5f for odd k; the candidate is the first k with the strictly greatest score (a NaN score never wins over
+ *     k = 0).  Candidates 1 .. 7 are considered only where the parent is unit, fabsf(((w w + x x) + (y y + z z)) - 1.0f) <= 0x1p-10f
+ *     (the viewer does not normalise a quaternion: the turns of a non-unit frame do not preserve its covariance); other parents take
+ *     k = 0.  cand = raw_k, times kC per component for odd k, negated as a whole where d_k < 0; the target edges are the parent's
+ *     (scale[0], scale[1]), swapped for odd k.  rotation = lerp(c, cand) per component, not normalised; scale[0..1] = lerp(own, target).
+ *  6. SH rows.  Where the tree has an SH plane and the context's plane holds for these records: row j = lerp of tree rows i and p in
+ *     all 48 columns, copied at t == 0; the plane stays valid with its degree.  A tree without a plane touches none.
+ *  7. Effect on the context: m2s_lod_select's own — the records epoch advances, what a cut invalidates is invalid —, after which
+ *     m2s_device_lod_nodes is valid again and m2s_device_lod_blend_t holds the weights.  Zero records: a valid no-op.
+ *  8. out_counts (may be NULL): [0] records, [1] records with t > 0, [2] records with t == 1, [3] records with t > 0 and k != 0.
+ *     Integer sums, identical from run to run.
+ * Known limit: alpha is lerped like the colour, and near t = 1 the m children of a parent are m coincident copies of it; front-to-back
+ * blending of m copies is 1 - (1 - a g)^m against a g, so a change in edge softness remains at the switch.
+ * Synchronous.  M2S_ERR_INVALID: as m2s_lod_select, a band that is not finite or outside (0, 1], reserved != 0.  M2S_ERR_STATE: no tree,
+ * conversions in flight, records that are not the last cut's. */
+typedef struct m2s_lod_blend_params {
+    float    camera_position[3];  /* as m2s_lod_select_params: the values the cut was taken with */
+    float    focal_px;            /* finite, > 0 */
+    float    tau_px;              /* finite, >= 0: the cut's tau (for a budget cut: the returned tau_px) */
+    float    near;                /* finite, > 0 */
+    float    band;                /* finite, 0 < band <= 1: the upper share of a node's tau^2 interval over which it moves to its parent */
+    uint32_t reserved;            /* 0 */
+} m2s_lod_blend_params;           /* 32 bytes */
+m2s_status m2s_lod_blend(m2s_ctx* ctx, const m2s_lod_blend_params* params, uint64_t out_counts[4]);
+/* The weight t of every record of the last m2s_lod_blend, a float each, in their order.  Valid until the records change again (NULL /
+ * M2S_ERR_STATE then; NULL for zero records too).  m2s_download_lod_blend_t: as m2s_download_lod_nodes. */
+const void* m2s_device_lod_blend_t(const m2s_ctx* ctx);
+m2s_status  m2s_download_lod_blend_t(m2s_ctx* ctx, float* dst, uint64_t capacity, uint64_t* out_n);
+/* The counts of the last m2s_lod_blend; its duration on the device (ms, measured whatever m2s_set_profiling says) and its stages:
+ * [0] weights, [1] records, [2] SH rows (0 without a plane). */
+m2s_status m2s_last_lod_blend_counts(const m2s_ctx* ctx, uint64_t out[4]);
+float       m2s_last_lod_blend_ms(const m2s_ctx* ctx);
+m2s_status  m2s_last_lod_blend_stage_ms(const m2s_ctx* ctx, float out_ms[3]);
+
 /* ---- world units (no counterpart in the reference, which keeps the resolutionTarget beside its records) ---------------------------- */
 /* Brings the context's current records to world units: scale[k] = scale[k] / (float)R for k = 0, 1, 2, with R the records'
  * resolutionTarget; afterwards the records' resolutionTarget is 1.  A conversion stores scale = (|Ju|, |Jv|, 1e-7) and leaves the

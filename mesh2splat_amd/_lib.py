@@ -59,6 +59,8 @@ EXPORTS = (
     "m2s_lod_select_budget", "m2s_last_lod_budget_stage_ms",
     "m2s_lod_select_frustum", "m2s_lod_select_budget_frustum", "m2s_last_lod_frustum_counts", "m2s_last_lod_frustum_ms",
     "m2s_lod_select_occluded", "m2s_lod_select_budget_occluded", "m2s_last_lod_occlusion_counts",
+    "m2s_lod_blend", "m2s_device_lod_blend_t", "m2s_download_lod_blend_t", "m2s_last_lod_blend_counts", "m2s_last_lod_blend_ms",
+    "m2s_last_lod_blend_stage_ms",
     "m2s_records_to_world_units", "m2s_last_world_units_ms",
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
@@ -310,6 +312,12 @@ def load():
         "m2s_lod_select_occluded": (C.c_int, [vp, vp, vp, vp, C.POINTER(u64)]),
         "m2s_lod_select_budget_occluded": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(u64)]),
         "m2s_last_lod_occlusion_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_lod_blend": (C.c_int, [vp, vp, C.POINTER(u64)]),
+        "m2s_device_lod_blend_t": (vp, [vp]),
+        "m2s_download_lod_blend_t": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
+        "m2s_last_lod_blend_counts": (C.c_int, [vp, C.POINTER(u64)]),
+        "m2s_last_lod_blend_ms": (C.c_float, [vp]),
+        "m2s_last_lod_blend_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "m2s_records_to_world_units": (C.c_int, [vp, C.POINTER(u32)]),
         "m2s_last_world_units_ms": (C.c_float, [vp]),
         "m2s_write_ply_compact": (C.c_int, [C.c_char_p, vp, vp, u32, u64, C.c_float, C.POINTER(u64)]),

@@ -1101,7 +1101,7 @@ class Converter:
         return {name: int(oc[k]) for k, name in enumerate(_ld.OCCLUSION_COUNTS)}
 
     def lod_select(self, camera_position, focal_px: float, tau_px: float = 1.0, near: float = 1e-3, dry_run: bool = False,
-                   frustum=None, occluder=None) -> dict:
+                   frustum=None, occluder=None, blend=None) -> dict:
         """Take the cut through the tree for a camera at `camera_position` (world space) whose projection has `focal_px` pixels per unit
         of tan(angle) (mesh2splat_amd.lod.focal_px, .camera_position): walking down from the coarsest level, a node is drawn as soon as
         its longer edge projects to at most tau_px pixels at its distance from the camera (at least `near`), or it is a leaf
@@ -1116,10 +1116,14 @@ class Converter:
         occluder (a mesh2splat_amd.lod.LodOccluderC: lod.occluder_to_c, lod.occluder_of_mesh_depth; needs a frustum): a leaf behind
         this depth image under the prepass's own depth test is not inside either (m2s_lod_select_occluded); the dict then also has
         "occluded_leaves" and "translucent_kept", and "visible_leaves" stays the leaves inside the frustum.  Run the prepass that
-        follows with depth_test_mesh = 0: a merged node lies under the surface its leaves lie on."""
+        follows with depth_test_mesh = 0: a merged node lies under the surface its leaves lie on.
+        blend (a band, 0 < blend <= 1; None: none): after a cut that is no dry run, lod_blend() with the same camera, this tau_px and
+        this band; the dict then also has "blend": lod_blend()'s dict."""
         from . import lod as _ld
         if occluder is not None and frustum is None:
             raise ValueError("an occluder needs a frustum")
+        if blend is not None:
+            _ld.blend_to_c(camera_position, focal_px, tau_px, near, blend)           # (a band outside (0, 1]: refused before the cut)
         pc = _ld.select_to_c(camera_position, focal_px, tau_px, near, dry_run)
         v = (C.c_uint64 * 4)()
         if frustum is None:
@@ -1136,20 +1140,25 @@ class Converter:
             self._lod_frustum_counts(out)
         if occluder is not None:
             out.update(self.last_lod_occlusion_counts())
+        if blend is not None and not dry_run:
+            out["blend"] = self.lod_blend(camera_position, focal_px, tau_px, near, blend)
         return out
 
     def lod_select_budget(self, camera_position, focal_px: float, max_records: int, tau_min_px: float = 0.0, near: float = 1e-3,
-                          dry_run: bool = False, frustum=None, occluder=None) -> dict:
+                          dry_run: bool = False, frustum=None, occluder=None, blend=None) -> dict:
         """Take the finest cut of lod_select() that holds at most `max_records` records for this camera, never finer than tau_min_px: the
         tau_px is found on the device, without a bisection on the host (m2s_lod_select_budget; the pin is in include/m2s.h).  A budget
         below the size of the coarsest level returns that level, with "met" False.  Everything else is lod_select()'s at the returned
         tau_px, the SH plane of a tree built with carry_sh included.  -> lod_select()'s dict plus {"tau_px": the float32 the cut was taken at, "met", "selected_finer": the records of the
         next finer cut, the one that did not fit (= "selected" where there is none or tau_min_px decided)}.
         frustum: as for lod_select(); the budget is then spent on the nodes the camera sees (m2s_lod_select_budget_frustum).
-        occluder: as for lod_select(); ... and that no mesh hides (m2s_lod_select_budget_occluded)."""
+        occluder: as for lod_select(); ... and that no mesh hides (m2s_lod_select_budget_occluded).
+        blend: as for lod_select(), with the tau_px the search returned."""
         from . import lod as _ld
         if occluder is not None and frustum is None:
             raise ValueError("an occluder needs a frustum")
+        if blend is not None:
+            _ld.blend_to_c(camera_position, focal_px, 0.0, near, blend)
         pc = _ld.budget_to_c(camera_position, focal_px, max_records, tau_min_px, near, dry_run)
         res = _ld.LodBudgetResultC()
         v = (C.c_uint64 * 4)()
@@ -1168,7 +1177,45 @@ class Converter:
             self._lod_frustum_counts(out)
         if occluder is not None:
             out.update(self.last_lod_occlusion_counts())
+        if blend is not None and not dry_run:
+            out["blend"] = self.lod_blend(camera_position, focal_px, out["tau_px"], near, blend)
         return out
+
+    def lod_blend(self, camera_position, focal_px: float, tau_px: float, near: float = 1e-3, band: float = 1.0) -> dict:
+        """Rewrite the records of the last cut (lod_select / lod_select_budget, any form, no dry run) in place so that they do not pop
+        between levels: every record becomes its node at weight 1 - t and its node's parent at weight t, with t rising from 0 to 1
+        over the upper `band` share of the node's interval of tau_px^2, and reaching 1 where the parent takes over (m2s_lod_blend; the
+        pin is in include/m2s.h).  Pass the camera, focal_px and near of the cut and its tau_px (a budget cut: the "tau_px" it
+        returned).  Which nodes are drawn, their order and download_lod_nodes() do not change; the SH plane of a tree built with
+        carry_sh is blended with the records.  The source is the tree: calling it again, with another band too, starts afresh.
+        -> {"records", "blended": t > 0, "saturated": t == 1, "turned": t > 0 and the parent's frame was turned to the child's}."""
+        from . import lod as _ld
+        pc = _ld.blend_to_c(camera_position, focal_px, tau_px, near, band)
+        v = (C.c_uint64 * 4)()
+        self._check(self._L.m2s_lod_blend(self._h, C.byref(pc), v))
+        return {name: int(v[k]) for k, name in enumerate(_ld.BLEND_COUNTS)}
+
+    def download_lod_blend_t(self) -> np.ndarray:
+        """float32 per record the last lod_blend() left: its weight t (m2s_download_lod_blend_t).  Valid until the records change again."""
+        n = C.c_uint64()
+        self._check(self._L.m2s_download_lod_blend_t(self._h, None, 0, C.byref(n)))
+        out = np.empty(int(n.value), np.float32)
+        if out.size:
+            self._check(self._L.m2s_download_lod_blend_t(self._h, out.ctypes.data, out.size, None))
+        return out
+
+    @property
+    def device_lod_blend_t(self) -> int:
+        return int(self._L.m2s_device_lod_blend_t(self._h) or 0)
+
+    def last_lod_blend_ms(self) -> float:
+        """The last lod_blend() on the device (ms)."""
+        return float(self._L.m2s_last_lod_blend_ms(self._h))
+
+    def last_lod_blend_stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self._L.m2s_last_lod_blend_stage_ms(self._h, ms))
+        return {"weights": float(ms[0]), "records": float(ms[1]), "sh": float(ms[2])}
 
     def download_lod(self, which: int) -> np.ndarray:
         """A plane of the tree (m2s_download_lod): 0 the node records (nodes, 24) float32, 1 parent (nodes,) uint32 with 0xFFFFFFFF on the

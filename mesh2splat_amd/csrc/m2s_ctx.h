@@ -13,7 +13,7 @@
 //   m2s_refit.cpp    the colour refit (m2s_refit_accumulate, m2s_refit_apply): the albedo error of K views carried back to the records
 //   m2s_merge.cpp    the merge pass (m2s_merge): neighbouring records replaced by their moment-matched parent, a baked SH plane merged with them (m2s_set_carry_sh)
 //   m2s_worldunits.cpp  m2s_records_to_world_units: a conversion's scales divided by its resolutionTarget
-//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their _frustum forms): a chain of merges kept and linked
+//   m2s_lod.cpp      the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their _frustum forms): a chain of merges kept and linked; the blend of a cut towards its parents (m2s_lod_blend)
 //   m2s_bake.cpp     the light baked into spherical harmonics (m2s_bake_light, m2s_sh_shade_records, m2s_export_ply_sh)
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
@@ -272,6 +272,16 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     // device (no other pass reads it), and the leaves inside the frustum, occluded, behind the image but kept, and the nodes dropped
     m2s_host::DevBuf<float> d_lod_occ_depth;             // capacity in texels
     uint64_t last_lod_occlusion_counts[4] = { 0, 0, 0, 0 };
+    // the blend (m2s_lod_blend): the weight of every record of the last cut, valid while lod_blend_tag holds, and its three count words.
+    // lod_tree_gen counts the trees this context has had (a build or a release ends one); lod_ids_gen is the tree d_lod_ids indexes.
+    m2s_host::DevBuf<float> d_lod_blend_t;
+    m2s_host::DevBuf<uint32_t> d_lod_blend_counts;       // kLodBlendCountWords
+    m2s_host::RecordsTag lod_blend_tag;
+    uint64_t lod_tree_gen = 0, lod_ids_gen = 0;
+    uint64_t last_lod_blend_counts[4] = { 0, 0, 0, 0 };
+    float last_lod_blend_ms = 0.0f;
+    float last_lod_blend_stage_ms[3] = { 0, 0, 0 };      // weights, records, SH rows (profiling on)
+    m2s_host::ClockOf<m2s_host::LodBlendMark> lod_blend_clock;
     // world units (m2s_worldunits.cpp)
     float last_world_units_ms = 0.0f;
     m2s_host::ClockOf<m2s_host::SpanMark> wu_clock;

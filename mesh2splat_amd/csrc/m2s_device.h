@@ -388,6 +388,20 @@ struct LodOccluderK { const float* depth; const float* nodes; uint32_t depth_w, 
 hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f,
                           const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st);
 
+// ---- the blend of a cut's records towards their parents (m2s_lodblend.hip; the pin: include/m2s.h, m2s_lod_blend) -----------------------
+struct LodBlendK { float cx, cy, cz, focal, tau2, near2, band; };
+constexpr uint32_t kLodBlendBlended = 0, kLodBlendSaturated = 1, kLodBlendTurned = 2, kLodBlendCountWords = 3;
+// k_lod_blend_t: t[j] for the n records whose nodes are ids[j] (pin 2); counts[kLodBlendBlended] += #{t > 0},
+// counts[kLodBlendSaturated] += #{t == 1} (zeroed by the caller).
+hipError_t lod_blend_weights(const uint32_t* ids, const uint32_t* parent, const float4* bounds, uint32_t n, const LodBlendK& k, float* t,
+                             uint32_t* counts, hipStream_t st);
+// k_lod_blend: out[j] = node ids[j] of `nodes` at weight 1 - t[j], its parent at t[j] (pins 3 to 5); counts[kLodBlendTurned] +=
+// #{t > 0, k != 0}.  out: n records, not memory `nodes` points into.
+hipError_t lod_blend_records(const float4* nodes, const uint32_t* ids, const uint32_t* parent, const float* t, uint32_t n, float4* out,
+                             uint32_t* counts, hipStream_t st);
+// k_lod_blend_sh: the same for the rows of the SH plane (pin 6).  out: n rows of 48 floats, not memory `sh` points into.
+hipError_t lod_blend_sh(const float4* sh, const uint32_t* ids, const uint32_t* parent, const float* t, uint32_t n, float4* out, hipStream_t st);
+
 // ---- world units (m2s_worldunits.hip) ------------------------------------------------------------------------------------------------
 // dst[i] = src[i] with scale[0..2] divided by (float)R (IEEE, correctly rounded), every other word with its bits, for the n records.
 // src == dst: in place, only the scale words move; else the two do not overlap.  R >= 1.

@@ -1,5 +1,5 @@
 // m2s_lod.cpp — the level-of-detail tree and its per-camera cut (m2s_lod_build, m2s_lod_select, m2s_lod_select_budget, their
-// _frustum and _occluded forms): host side of m2s_lod.hip, m2s_lodbudget.hip and m2s_lodfrustum.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
+// _frustum and _occluded forms, m2s_lod_blend): host side of m2s_lod.hip, m2s_lodbudget.hip, m2s_lodfrustum.hip and m2s_lodblend.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
 // copied into a node pool and linked by their maps; the
 // cut's flags and offsets live where m2s_prune leaves its own, and the compaction is m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue);
 // what a cut does to the context: m2s_recstate.h, Rewrite::LodCut.
@@ -203,6 +203,7 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         c->rewritten(c->lane[0].records, selected, c->lod_R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
         if (with_sh) c->sh_degree = c->lod_sh_degree;
         c->lod_ids_tag.set(*c, selected);
+        c->lod_ids_gen = c->lod_tree_gen;                                // (which tree the indices are of: m2s_lod_blend reads it through them)
     }
     c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
     c->last_lod_select_counts[3] = h[kLodRefineWord];
@@ -291,9 +292,98 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
     return M2S_OK;
 }
 
+m2s_status lod_blend_check(m2s_ctx* c, const m2s_lod_blend_params* p) {
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
+    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    if (!std::isfinite(p->band) || !(p->band > 0.0f) || !(p->band <= 1.0f)) return fail(c, M2S_ERR_INVALID, "band is not finite or outside (0, 1]");
+    if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
+    return M2S_OK;
+}
+
+// m2s_lod_blend behind its checks of the arguments and the state: the n records of the last cut, which live in the pool, are rewritten
+// there out of the tree (the source is never the pool: nothing lands on itself), and the rows of the context's plane out of the tree's.
+m2s_status lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out_counts[4]) {
+    const uint64_t n = c->lod_ids_tag.n;
+    const bool with_sh = c->lod_has_sh && c->sh_tag.holds(*c, n);       // (pin 6)
+    ClockOf<LodBlendMark>& clock = c->lod_blend_clock;
+    uint32_t h[kLodBlendCountWords] = {};
+    HIPCHK(c, hipSetDevice(c->device));
+    M2S_TRY(clock.begin(c->err, true));                                 // (measured whatever m2s_set_profiling says)
+    c->lod_blend_tag.clear();
+    if (n) {
+        M2S_TRY(c->d_lod_blend_t.reserve(c->err, n, sizeof(float)));
+        M2S_TRY(c->d_lod_blend_counts.reserve(c->err, kLodBlendCountWords, sizeof(uint32_t)));
+        float4* const pool = (float4*)c->lane[0].records.get();
+        const LodBlendK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near, p->band };
+        HIPCHK(c, hipMemsetAsync(c->d_lod_blend_counts, 0, kLodBlendCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, clock.mark(LodBlendMark::Start, c->stream));
+        HIPCHK(c, lod_blend_weights(c->d_lod_ids, c->d_lod_parent, c->d_lod_bounds, (uint32_t)n, k, c->d_lod_blend_t, c->d_lod_blend_counts, c->stream));
+        HIPCHK(c, clock.mark(LodBlendMark::Weighted, c->stream));
+        HIPCHK(c, lod_blend_records(c->d_lod_nodes, c->d_lod_ids, c->d_lod_parent, c->d_lod_blend_t, (uint32_t)n, pool, c->d_lod_blend_counts, c->stream));
+        HIPCHK(c, clock.mark(LodBlendMark::Blended, c->stream));
+        if (with_sh) {
+            HIPCHK(c, lod_blend_sh((const float4*)c->d_lod_sh.get(), c->d_lod_ids, c->d_lod_parent, c->d_lod_blend_t, (uint32_t)n, (float4*)c->d_sh.get(), c->stream));
+            HIPCHK(c, clock.mark(LodBlendMark::ShBlended, c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_blend_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h[kLodBlendBlended] > n || h[kLodBlendSaturated] > h[kLodBlendBlended] || h[kLodBlendTurned] > h[kLodBlendBlended])
+            return fail(c, M2S_ERR_HIP, "the blend's counts came back inconsistent");
+    }
+    float* ms = c->last_lod_blend_stage_ms;                             // (zero records record nothing: those spans are 0)
+    HIPCHK(c, clock.span(LodBlendMark::Start, LodBlendMark::Weighted, &ms[0]));
+    HIPCHK(c, clock.span(LodBlendMark::Weighted, LodBlendMark::Blended, &ms[1]));
+    HIPCHK(c, clock.span(LodBlendMark::Blended, LodBlendMark::ShBlended, &ms[2]));
+    HIPCHK(c, clock.span(LodBlendMark::Start, with_sh ? LodBlendMark::ShBlended : LodBlendMark::Blended, &c->last_lod_blend_ms));
+    // pin 7: what a cut does to the context, then the two planes the cut and this pass left are the new records' again
+    c->rewritten(c->lane[0].records, n, c->lod_R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
+    if (with_sh) c->sh_degree = c->lod_sh_degree;
+    c->lod_ids_tag.set(*c, n);
+    c->lod_blend_tag.set(*c, n);
+    c->last_lod_blend_counts[0] = n; c->last_lod_blend_counts[1] = h[kLodBlendBlended]; c->last_lod_blend_counts[2] = h[kLodBlendSaturated];
+    c->last_lod_blend_counts[3] = h[kLodBlendTurned];
+    if (out_counts) std::memcpy(out_counts, c->last_lod_blend_counts, sizeof(c->last_lod_blend_counts));
+    return M2S_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+m2s_status m2s_lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out_counts[4]) {
+    if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+    if (!c || !p) return M2S_ERR_INVALID;
+    M2S_TRY(lod_blend_check(c, p));
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    if (!lod_ids_valid(c) || c->lod_ids_gen != c->lod_tree_gen || c->last_records != c->lane[0].records.get() || c->last_stored != c->lod_ids_tag.n)
+        return fail(c, M2S_ERR_STATE, "the current records are not what the last cut of this tree left (m2s_lod_select without M2S_LOD_DRY_RUN first)");
+    return lod_blend(c, p, out_counts);
+}
+
+const void* m2s_device_lod_blend_t(const m2s_ctx* c) { return c && c->lod_blend_tag.holds(*c) && c->lod_blend_tag.n ? c->d_lod_blend_t.get() : nullptr; }
+
+m2s_status m2s_download_lod_blend_t(m2s_ctx* c, float* dst, uint64_t capacity, uint64_t* out_n) {
+    if (out_n) *out_n = 0;
+    if (!c) return M2S_ERR_INVALID;
+    if (!c->lod_blend_tag.holds(*c)) return fail(c, M2S_ERR_STATE, "no blend weights of the current records (m2s_lod_blend; the records changed since)");
+    if (out_n) *out_n = c->lod_blend_tag.n;
+    if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
+    if (capacity < c->lod_blend_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!c->lod_blend_tag.n) return M2S_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->d_lod_blend_t, c->lod_blend_tag.n * sizeof(float), hipMemcpyDeviceToHost));
+    return M2S_OK;
+}
+
+m2s_status m2s_last_lod_blend_counts(const m2s_ctx* c, uint64_t out[4]) { return get_array(c, &m2s_ctx::last_lod_blend_counts, out); }
+
+float m2s_last_lod_blend_ms(const m2s_ctx* c) { return c ? c->last_lod_blend_ms : 0.0f; }
+
+m2s_status m2s_last_lod_blend_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_lod_blend_stage_ms, out_ms); }
 
 m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out_counts[4]) {
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
@@ -316,6 +406,7 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->lod_build_clock.begin(c->err, true));                    // (measured whatever m2s_set_profiling says)
     c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
+    ++c->lod_tree_gen;
     c->lod_has_sh = false;
     if (!with_sh) c->d_lod_sh.release();                                // (192 bytes per node: not kept for a tree that has no use for it)
     HIPCHK(c, c->lod_build_clock.mark(SpanMark::Begin, c->stream));
@@ -411,8 +502,10 @@ m2s_status m2s_lod_release(m2s_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->lod_levels = 0;
+    ++c->lod_tree_gen;
     c->lod_has_sh = false;
     c->d_lod_sh.release();
+    c->d_lod_blend_t.release(); c->lod_blend_tag.clear();
     c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release(); c->d_lod_vis.release();
     c->d_lod_occ_depth.release();
     return M2S_OK;

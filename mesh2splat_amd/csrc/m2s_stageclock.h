@@ -84,6 +84,7 @@ enum class BudgetMark { Start, Selected, Scanned, Compact, Compacted, N };      
 enum class MergeMark { Start, Keyed, Sorted, Segments, Segmented, Reduced, N };
 enum class LodCutMark { Start, Swept, Indexed, Compacted, N };
 enum class LodBudgetMark { Start, Thresholds, Searched, N };
+enum class LodBlendMark { Start, Weighted, Blended, ShBlended, N };
 enum class ShadowMark { Count, Counted, Emit, Emitted, Setup, SetupEnd, Bin, Binned, Rastered, N };   // stage A: 0-3 | stage B: 4-8
 enum class MeshMark { Start, SetupEnd, Deferred, Binned, Rastered, N };
 enum class CompactMark { Start, Keyed, Sorted, Pack, Packed, N };

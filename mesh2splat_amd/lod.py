@@ -1,6 +1,6 @@
 """The level-of-detail tree and its per-camera cut (`Converter.lod_build` / `.lod_select` / `.lod_select_budget` / `.lod_levels` /
 `.download_lod` / `.download_lod_nodes` / `.lod_release`, m2s_lod_build, m2s_lod_select, m2s_lod_select_budget and the _frustum and
-_occluded forms of the two cuts): the ctypes mirrors of their parameters and the two numbers a cut takes from a camera.  The pins are in include/m2s.h.
+_occluded forms of the two cuts, and m2s_lod_blend behind them: `Converter.lod_blend`): the ctypes mirrors of their parameters and the two numbers a cut takes from a camera.  The pins are in include/m2s.h.
 
 The default chain of merge levels (1 .. 8), like max_group = 4 and min_axis_dot = 0.5, is a guess: nothing in the repository has
 tuned it (tools/lod_probe.py reports what it does on one scene)."""
@@ -18,6 +18,7 @@ DEFAULT_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8)
 BUILD_COUNTS = ("leaves", "nodes", "levels", "skipped")      # m2s_lod_build's out_counts, in order
 SELECT_COUNTS = ("nodes", "selected", "selected_leaves", "refine")   # m2s_lod_select's
 FRUSTUM_COUNTS = ("visible_leaves", "culled")                # m2s_last_lod_frustum_counts', in order
+BLEND_COUNTS = ("records", "blended", "saturated", "turned")   # m2s_lod_blend's out_counts, in order
 OCCLUSION_COUNTS = ("visible_leaves", "occluded_leaves", "translucent_kept", "culled")   # m2s_last_lod_occlusion_counts', in order
 PLANES = {0: (np.float32, 24), 1: (np.uint32, None), 2: (np.float32, 4)}    # m2s_download_lod: which -> (dtype, row length)
 
@@ -64,6 +65,24 @@ class LodOccluderC(C.Structure):
     """== m2s_lod_occluder (include/m2s.h)."""
     _fields_ = [("depth", C.c_void_p), ("depth_w", C.c_uint32), ("depth_h", C.c_uint32), ("depth_on_device", C.c_uint32),
                 ("depth_bias", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class LodBlendParamsC(C.Structure):
+    """== m2s_lod_blend_params (include/m2s.h)."""
+    _fields_ = [("camera_position", C.c_float * 3), ("focal_px", C.c_float), ("tau_px", C.c_float), ("near", C.c_float),
+                ("band", C.c_float), ("reserved", C.c_uint32)]
+
+
+def blend_to_c(camera_position, focal_px: float, tau_px: float, near: float = 1e-3, band: float = 1.0) -> LodBlendParamsC:
+    """The camera, focal and tau_px the cut was taken with (for a budget cut: the tau_px it returned) and the band: the upper share of
+    a node's tau^2 interval over which it moves to its parent, 0 < band <= 1."""
+    band = float(band)
+    if not 0.0 < band <= 1.0:                                # (a NaN too)
+        raise ValueError("band outside (0, 1]")
+    c = LodBlendParamsC()
+    c.camera_position[:] = [float(v) for v in camera_position]
+    c.focal_px, c.tau_px, c.near, c.band = float(focal_px), float(tau_px), float(near), band
+    return c
 
 
 def build_to_c(levels=DEFAULT_LEVELS, max_group: int = 4, min_axis_dot: float = 0.5, unsigned_axis: bool = False) -> LodBuildParamsC:

@@ -94,6 +94,7 @@ struct Options {
     bool lod_occlusion = false;                                    // --lod-occlusion [--lod-depth-bias b]: ... and that the mesh does not hide (m2s_mesh_depth per camera, then
     double lod_depth_bias = -1.0;                                  //   m2s_lod_select_occluded, m2s_lod_select_budget_occluded); implies --lod-frustum; b >= 0, 0.00002 without --lod-depth-bias
     bool lod_frustum = false;                                      //   m2s_lod_select_budget_frustum), the frustum test widened by g (>= 1; 1.05, the prepass's own, without --lod-guard)
+    double lod_blend = -1.0;                                       // --lod-blend b (0 < b <= 1): every cut is blended towards its nodes' parents over this band (m2s_lod_blend)
     std::string lod_ply;                                           // --lod-ply cut.ply: the --preview camera's cut as a .ply (with --bake-light: its carried SH plane, m2s_set_carry_sh)
     bool lod() const { return !lod_levels.empty(); }
     bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
@@ -118,7 +119,7 @@ void usage() {
                  "         [--budget N] [--bake-light [--bake-degree 0..3]] [--compact]\n"
                  "         [--refit K [--refit-iters n] [--refit-step s] [--refit-elevations e1,e2,...]]\n"
                  "         [--merge-level L | --merge-to N] [--merge-group g] [--merge-dot d]\n"
-                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]] [--lod-occlusion [--lod-depth-bias b]] [--lod-ply cut.ply]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
+                 "         [--lod-levels a,b,... --lod-pixels t | --lod-budget N [--lod-frustum [--lod-guard g]] [--lod-occlusion [--lod-depth-bias b]] [--lod-blend b] [--lod-ply cut.ply]] [--merge-unsigned-axis] [--view-distance f] [--world-units]\n"
                  "--preview: after the conversion, m2s_prepass (render mode 0) + m2s_sort_prepass + m2s_splat, and the albedo plane\n"
                  "  (top row first) as an 8-bit RGBA PNG.  Camera (double precision, matrices rounded to float; glm::lookAt / perspective):\n"
                  "  box = cumulative bounding box of the meshes, centre = (min + max) / 2, radius = |max - min| / 2,\n"
@@ -192,6 +193,11 @@ void usage() {
                  "  closed mesh is neither selected nor charged to a budget.  The `lod:` line then has \"depth_bias\": b, and every entry of `views`\n"
                  "  \"occluded\" and \"translucent_kept\" (leaves behind the image kept for an alpha <= .95).  Not with --mesh-depth-test: a merged\n"
                  "  node lies under the surface its leaves lie on, and the prepass's depth test of its own position would cull it.\n"
+                 "--lod-blend b (0 < b <= 1), with --lod-levels: every --preview / --score / --lod-ply cut is blended afterwards (m2s_lod_blend with\n"
+                 "  the cut's camera and tau_px, a budget's being the one it found): each record moves towards its node's parent over the upper\n"
+                 "  share b of its interval of tau_px^2, so that retaking the cut for a moving camera does not pop between levels.  The `lod:`\n"
+                 "  line then has \"blend\": b and every entry of `views` \"blended\" (records with a weight above 0) and \"blend_ms\".  With\n"
+                 "  --batch the cuts are dry runs: nothing is blended and only \"blend\": b is reported.  Not with --gpus N > 1.\n"
                  "--lod-ply cut.ply, with --lod-levels and --preview (one file, one GPU): right after the --preview camera's cut its records are\n"
                  "  written to cut.ply, in --format (m2s_export_ply).  With --bake-light the baked plane is carried through the tree and the cut\n"
                  "  (m2s_set_carry_sh, switched on in front of the bake) and cut.ply carries the SH element (m2s_export_ply_sh).  The `lod:` line\n"
@@ -363,6 +369,7 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float wor
     sp.flags = dry ? (uint32_t)M2S_LOD_DRY_RUN : 0u;
     uint64_t c[4] = {}, per[M2S_LOD_MAX_STEPS + 1] = {};
     std::string budget;
+    float blend_tau = sp.tau_px;
     m2s_lod_frustum fr;                                                 // --lod-frustum: the camera's matrices, the records' space being the world's
     std::memset(&fr, 0, sizeof(fr));
     for (int k = 0; k < 4; ++k) fr.model_to_world[k * 5] = 1.0f;
@@ -394,9 +401,10 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float wor
         m2s_lod_budget_result res;
         if ((o.lod_occlusion ? m2s_lod_select_budget_occluded(ctx, &bp, &fr, &oc, &res, c)
              : o.lod_frustum ? m2s_lod_select_budget_frustum(ctx, &bp, &fr, &res, c) : m2s_lod_select_budget(ctx, &bp, &res, c)) != M2S_OK) return 1;
+        blend_tau = res.tau_px;
         char tau[40];
         std::snprintf(tau, sizeof tau, "%.9g", (double)res.tau_px);
-        budget = std::string(", \"tau_px\": ") + tau + ", \"met\": " + (res.met ? "true" : "false") + ", \"selected_finer\": " +
+        budget =std::string(", \"tau_px\": ") + tau + ", \"met\": " + (res.met ? "true" : "false") + ", \"selected_finer\": " +
                  std::to_string((unsigned long long)res.selected_finer);
     } else if ((o.lod_occlusion ? m2s_lod_select_occluded(ctx, &sp, &fr, &oc, c)
                 : o.lod_frustum ? m2s_lod_select_frustum(ctx, &sp, &fr, c) : m2s_lod_select(ctx, &sp, c)) != M2S_OK) {
@@ -411,6 +419,20 @@ int lod_cut(m2s_ctx* ctx, const Options& o, const double eye[3], const float wor
         uint64_t ocn[4] = {};
         if (m2s_last_lod_occlusion_counts(ctx, ocn) != M2S_OK) return 1;
         budget += ", \"occluded\": " + std::to_string((unsigned long long)ocn[1]) + ", \"translucent_kept\": " + std::to_string((unsigned long long)ocn[2]);
+    }
+    if (o.lod_blend > 0.0 && !dry) {                                    // --lod-blend: the cut just taken, with its own camera and tau (a budget's: the one it found)
+        m2s_lod_blend_params bl;
+        std::memset(&bl, 0, sizeof(bl));
+        std::memcpy(bl.camera_position, sp.camera_position, sizeof(bl.camera_position));
+        bl.focal_px = sp.focal_px;
+        bl.tau_px = blend_tau;
+        bl.near = sp.near;
+        bl.band = (float)o.lod_blend;
+        uint64_t bc[4] = {};
+        if (m2s_lod_blend(ctx, &bl, bc) != M2S_OK) return 1;
+        char ms[40];
+        std::snprintf(ms, sizeof ms, "%.4f", (double)m2s_last_lod_blend_ms(ctx));
+        budget += ", \"blended\": " + std::to_string((unsigned long long)bc[1]) + ", \"blend_ms\": " + ms;
     }
     if (m2s_last_lod_level_counts(ctx, per) != M2S_OK) return 1;
     std::string levels;
@@ -436,6 +458,11 @@ void lod_print(const Options& o, const LodReport& rep) {
         char b[40];
         std::snprintf(b, sizeof b, "%.9g", (double)(float)o.lod_depth_bias);
         budget += std::string(", \"depth_bias\": ") + b;
+    }
+    if (o.lod_blend > 0.0) {
+        char b[40];
+        std::snprintf(b, sizeof b, "%.9g", (double)(float)o.lod_blend);
+        budget += std::string(", \"blend\": ") + b;
     }
     std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
@@ -1299,6 +1326,7 @@ int main(int argc, char** argv) {
         else if (a == "--lod-occlusion") o.lod_occlusion = true;
         else if (a == "--lod-depth-bias") { o.lod_depth_bias = std::atof(next()); if (!(o.lod_depth_bias >= 0.0) || !std::isfinite(o.lod_depth_bias)) { usage(); return 2; } }
         else if (a == "--lod-ply") o.lod_ply = next();
+        else if (a == "--lod-blend") { o.lod_blend = std::atof(next()); if (!(o.lod_blend > 0.0) || !(o.lod_blend <= 1.0) || !((float)o.lod_blend > 0.0f)) { usage(); return 2; } }
         else if (a == "--lod-guard") { o.lod_guard = std::atof(next()); if (!(o.lod_guard >= 1.0) || !std::isfinite(o.lod_guard)) { usage(); return 2; } }
         else if (a == "--lod-budget") {
             const std::string v = next();
@@ -1383,6 +1411,7 @@ int main(int argc, char** argv) {
     if (o.lod_occlusion) { o.lod_frustum = true; if (o.lod_depth_bias < 0.0) o.lod_depth_bias = 0.00002; }
     if ((o.lod_frustum && !o.lod()) || (o.lod_guard >= 0.0 && !o.lod_frustum)) { usage(); return 2; }   // (--lod-frustum: a mode of the cuts; --lod-guard: of --lod-frustum)
     if (o.lod_frustum && o.lod_guard < 0.0) o.lod_guard = 1.05;
+    if (o.lod_blend > 0.0 && (!o.lod() || o.gpus > 1)) { usage(); return 2; }                          // (--lod-blend: a mode of the cuts)
     if (o.lod() && (o.gpus > 1 || o.force_sharded || (o.score_views == 0 && (o.preview.empty() || !o.batch_dir.empty())))) { usage(); return 2; }
     if (!o.lod_ply.empty() && (!o.lod() || o.preview.empty() || !o.batch_dir.empty() || o.gpus > 1 || o.force_sharded)) { usage(); return 2; }
     if (o.bake_light && (o.format != 0 || o.gpus > 1 || o.force_sharded || !o.batch_dir.empty())) { usage(); return 2; }
