@@ -20,7 +20,7 @@ void free_scene(m2s_ctx* c) {
     // everything below lived inside the arena (lane 0's chain and offsets too)
     c->d_meshes = nullptr; c->d_mesh_first = nullptr;
     c->d_cnt = c->d_partials = nullptr;
-    c->d_biglist = nullptr; c->d_bigmeta = nullptr; c->d_bands = nullptr; c->run_table_words = 0; c->d_run_order = nullptr; c->run_order_unit = 0;
+    c->d_biglist = nullptr; c->d_bigmeta = nullptr; c->d_bands = nullptr; c->run_table_words = 0; c->d_run_order = nullptr; c->d_run_rank = nullptr; c->run_order_unit = 0;
     c->d_batch_first = nullptr; c->n_batch_tab = 0; c->chain_words = 0;
     c->rinfo.clear();
     ++c->rinfo_gen;

@@ -119,12 +119,12 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     bool warm_mismatch_seen = false;        // a launch in runs disagreed with that count once (run_pass): not retried again
     uint32_t hint_R = 0;                    // m2s_set_resolution_hint: the R the next upload prepares for (0: the last R converted at, else 1024)
     uint32_t warm_R = 0;                    // the R the resident scene was prepared for
-    int warm_spec_form = 0;                             // ... ordered for the first resident set of this single-pass form's kernel
     uint32_t warm_spec_unit = 0, warm_spec_shift = 0;   // run table + dispatch order enqueued with the upload's count, for units of this many triangles (0: none)
     unsigned long long* d_bands = nullptr;  // kBandSlots run tables of run_table_words words each (RunInfo, m2s_device.h)
     size_t run_table_words = 0;
     uint32_t* d_run_order = nullptr;        // dispatch order of the runs (launch_run_order), built by warm_scene from the exact counts ...
     uint32_t run_order_unit = 0, run_order_shift = 0;   // ... for runs of (1 << shift) units of this many triangles (0: none)
+    void* d_run_rank = nullptr;             // launch_run_order's scratch: the runs' costs and ids in rank order (run_order_scratch_bytes)
     uint32_t* d_batch_first = nullptr;      // work-balanced batches of k_fused2 (small scenes; built from the first exact count)
     uint32_t n_batch_tab = 0;               // batches in it (0: uniform batches)
     size_t chain_words = 0;                 // words of every lane's chain

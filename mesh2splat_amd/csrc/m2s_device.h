@@ -108,16 +108,16 @@ void launch_big_share(const uint32_t* cnt, uint32_t n_tri, uint32_t threshold, u
 // where the output of every RUN (1 << shift units of `unit` = 256 / 512 triangles) starts, from launch_count's counts and the
 // scanned partial sums: the table a launch in runs reads (RunInfo::base)
 void launch_unit_bases(const uint32_t* cnt, const uint32_t* partials, uint32_t n_tri, uint32_t unit, uint32_t shift, unsigned long long* run_base, hipStream_t st);
-// Dispatch order of the runs of a launch in runs: order[slot] = run, runs sorted by fragment count, heaviest first (LPT).  A launch
-// lasts until its last workgroup has finished; in mesh order the units dispatched last are as heavy as any (config 3: 9 ... 1592
-// fragments per unit), so the GPU drains for a whole heavy workgroup's lifetime.  With the light runs last the drain is short.  Runs
-// are independent (the look-back chain restarts at every run, whose base comes from the table), so any order is correct.
+// Dispatch order of the runs of a launch in runs: order[slot] = run.  A launch lasts until its last workgroup has finished; in mesh
+// order the units dispatched last are as heavy as any (config 3: 9 ... 1592 fragments per unit), so the GPU drains for a whole heavy
+// workgroup's lifetime.  Slot s is dispatched on XCD s % 8: the runs are dealt to the eight XCD queues so that the queues hold equal
+// numbers of fragments, and every queue holds its heaviest runs first — the light runs last, a short drain, on every XCD at about the
+// same time (m2s_run_balance.h).  Runs are independent (the look-back chain restarts at every run, whose base comes from the table),
+// so any order is correct.
 // n_slots = runs rounded up to whole groups of eight (slots past the last run map to themselves: their workgroups exit at once).
-// first_set (0: none, the shipping build; m2s_pass.cpp first_resident_slots) = the slots whose workgroups all start with the launch: the
-// order is descending behind them; among them every XCD gets heavy and light runs side by side, so that its co-resident workgroups do not
-// all end together (k_run_order).
+// scratch: run_order_scratch_bytes(n_slots) bytes of device memory (the runs' costs and ids in rank order).
 void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots,
-                      uint32_t first_set, hipStream_t st);
+                      void* scratch, hipStream_t st);
 // workgroups of `kernel` (of `threads` threads, no dynamic LDS) the current device holds at once: occupancy per CU x CUs; 0 if unknown
 inline uint32_t resident_workgroups(const void* kernel, int threads) {
     int dev = 0, cus = 0, per_cu = 0;
@@ -132,6 +132,7 @@ uint32_t fused2_resident_workgroups();
 uint32_t fused3_resident_workgroups();
 uint32_t sparse_resident_workgroups();
 inline uint32_t run_order_slots(uint32_t n_units, uint32_t shift) { return ((n_units + (8u << shift) - 1u) / (8u << shift)) * 8u; }
+inline size_t run_order_scratch_bytes(uint32_t n_slots) { return (size_t)n_slots * (sizeof(unsigned long long) + sizeof(uint32_t)); }
 // multi-pass pipeline (m2s_emit2.hip): count + scan + offsets in one kernel, wave-granular emit
 uint32_t emit2_slices(uint64_t limit);       // entries of start[] needed for `limit` output records
 uint32_t count_scan_blocks(uint32_t n_tri);  // chain words k_count_scan uses
@@ -155,12 +156,15 @@ void launch_encode_rows(const float4* rec, uint64_t n, uint32_t format, float sc
 // next launches of the scene at that R read it.  No counting pass, no host round trip, no picker kernel.
 // (Rounds 1-3 cut the unit list into EIGHT contiguous bands of equal estimated work, one per XCD.  A launch then lasted as long as
 // its slowest band — the linear work model left the XCDs' finishing times 4-9 % apart — and as wide as its widest; the cuts had to
-// travel to the host.  With ~30 runs per XCD the work evens out statistically and every XCD gets work until the end.)
+// travel to the host.  With runs every XCD gets work until the end; how much work depends on which runs it gets.  In mesh order ~15
+// runs per XCD leave the heaviest XCD of config 3 2.1 % above the mean; sorted by weight and dealt round-robin, as rounds 7-11 shipped
+// it, XCD 0 got the heaviest run of every group of eight and XCD 7 the lightest: 5.1 % above, 8.8 % between them.  launch_run_order
+// deals the sorted runs by weight instead: 2.1 % above the mean, the bound that 123 runs of 32 units allow (tools/xcd_balance.py).)
 struct RunInfo {
     const unsigned long long* base;  // launch in runs: base[j] = record index at which the output of run j starts; else nullptr
     unsigned long long* out;         // launch without runs: out[j] = the same, recorded for the next launches (or nullptr)
     uint32_t shift;                  // log2 of the run length in units
-    const uint32_t* order;           // launch in runs: dispatch slot -> run (heaviest runs first, see launch_run_order); nullptr: identity
+    const uint32_t* order;           // launch in runs: dispatch slot -> run (equal work per XCD queue, heaviest runs first: launch_run_order); nullptr: identity
 };
 // run length for a scene of n_units units (0: too few units for runs to make sense — plain order): 32 units (8192 triangles of
 // k_fused2) where that still leaves every XCD four runs, else 16 or 8.  Measured on config 3 (3916 units), kernel time / read

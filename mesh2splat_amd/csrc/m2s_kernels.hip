@@ -5,7 +5,7 @@
 //
 // What lives here: the upload-time kernels (repack, mips, combo textures, mesh table), the exact count the upload takes
 // (k_count + k_scan_partials: AUTO's decision, run tables, m2s_download_triangle_counts) with its by-products (k_big_share,
-// k_unit_bases, k_run_order), and k_emit_big, the second stage of the single-pass kernels for triangles they defer.  The
+// k_unit_bases, k_run_rank + k_run_assign), and k_emit_big, the second stage of the single-pass kernels for triangles they defer.  The
 // conversion kernels proper are m2s_fused*.hip, m2s_sparse.hip (single pass) and m2s_emit2.hip (multi-pass); the first-
 // generation multi-pass emission that started here in round 1 (k_offsets, k_emit) was removed in round 6 (tag r5-final has it).
 // Output order is deterministic: (mesh, triangle, pixel row, pixel column) — the reference's order
@@ -15,6 +15,7 @@
 // default correctly-rounded fp32 divide/sqrt), integer rasterisation on a 24.8 grid with int64
 // edge functions: see DESIGN.md "Pinned semantics".  No MFMA: nothing here is a contraction.
 #include "m2s_devfn.h"
+#include "m2s_run_balance.h"
 
 #pragma clang fp contract(off)
 
@@ -259,30 +260,16 @@ void launch_unit_bases(const uint32_t* cnt, const uint32_t* partials, uint32_t n
 }
 
 // ============================================================================================
-// K_run_order: rank sort of the runs by fragment count, descending (ties: lower run first), then the slot of every rank.  n_runs <= a few
-// thousand.  The slots past the FIRST RESIDENT SET (the `first_set` slots whose workgroups all start when the launch does) hold the ranking
-// in descending order: the light runs last, a short drain.  Inside the first set the four (first_set / 8) slots of one XCD would otherwise
-// hold runs of nearly the same weight, whose workgroups live equally long and hand their phase to the next generation (m2s_fused3.hip,
-// phase classes); there the earlier half of an XCD's slots takes the heaviest runs and the later half the lightest ones, the lightest in
-// the last slot.  first_set = 0 (the shipping build: measured, config 3 is slower with it — DESIGN 6.3): descending throughout.
+// K_run_rank + k_run_assign: the dispatch order of the runs (RunInfo::order).  k_run_rank sorts the runs by fragment count, descending
+// (rank sort; ties: lower run first; n_runs <= a few thousand) and stores every run's cost and id at its rank.  k_run_assign then deals
+// the ranks to the eight XCD queues so that the queues hold equal work, each heaviest first (run_balance_assign, m2s_run_balance.h: one
+// lane walks the ranks), and replaces the ranks in order[] by the runs.  Slots past the last run map to themselves.
 // ============================================================================================
-__device__ __forceinline__ uint32_t run_order_slot_of_rank(uint32_t rank, uint32_t n_runs, uint32_t first_set) {
-    const uint32_t groups = (first_set < n_runs ? first_set : n_runs) / 8u;   // slots per XCD in the first set
-    if (groups < 2u) return rank;
-    const uint32_t heavy = ((groups + 1u) / 2u) * 8u, light = (groups / 2u) * 8u;
-    if (rank < heavy) return rank;
-    if (rank >= n_runs - light) {
-        const uint32_t j = n_runs - 1u - rank;                         // 0: the lightest run
-        return (groups - 1u - (j >> 3)) * 8u + (j & 7u);
-    }
-    return rank + light;                                                // (first set = heavy + light slots)
-}
-__global__ void __launch_bounds__(kBlock) k_run_order(const unsigned long long* __restrict__ run_base, uint32_t n_runs,
-                                                      const unsigned long long* __restrict__ total, uint32_t* __restrict__ order, uint32_t n_slots,
-                                                      uint32_t first_set) {
+__global__ void __launch_bounds__(kBlock) k_run_rank(const unsigned long long* __restrict__ run_base, uint32_t n_runs,
+                                                     const unsigned long long* __restrict__ total, unsigned long long* __restrict__ cost_by_rank,
+                                                     uint32_t* __restrict__ run_by_rank) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_slots) return;
-    if (i >= n_runs) { order[i] = i; return; }
+    if (i >= n_runs) return;
     const unsigned long long end = *total;
     auto cost = [&](uint32_t j) { return (j + 1u < n_runs ? run_base[j + 1u] : end) - run_base[j]; };
     const unsigned long long mine = cost(i);
@@ -291,12 +278,22 @@ __global__ void __launch_bounds__(kBlock) k_run_order(const unsigned long long* 
         const unsigned long long cj = cost(j);
         rank += (cj > mine || (cj == mine && j < i)) ? 1u : 0u;
     }
-    order[run_order_slot_of_rank(rank, n_runs, first_set)] = i;
+    cost_by_rank[rank] = mine;
+    run_by_rank[rank] = i;
+}
+__global__ void __launch_bounds__(kBlock) k_run_assign(const unsigned long long* __restrict__ cost_by_rank, const uint32_t* __restrict__ run_by_rank,
+                                                       uint32_t n_runs, uint32_t n_slots, uint32_t* order) {
+    if (threadIdx.x == 0) run_balance_assign(cost_by_rank, n_runs, n_slots, order);   // order[slot] = rank
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < n_runs; s += kBlock) order[s] = run_by_rank[order[s]];
 }
 void launch_run_order(const unsigned long long* run_base, uint32_t n_runs, const unsigned long long* total, uint32_t* order, uint32_t n_slots,
-                      uint32_t first_set, hipStream_t st) {
-    if (!n_slots) return;
-    hipLaunchKernelGGL(k_run_order, dim3((n_slots + kBlock - 1) / kBlock), dim3(kBlock), 0, st, run_base, n_runs, total, order, n_slots, first_set);
+                      void* scratch, hipStream_t st) {
+    if (!n_slots || !n_runs || n_runs > n_slots) return;
+    unsigned long long* cost_by_rank = static_cast<unsigned long long*>(scratch);
+    uint32_t* run_by_rank = reinterpret_cast<uint32_t*>(cost_by_rank + n_slots);
+    hipLaunchKernelGGL(k_run_rank, dim3((n_runs + kBlock - 1) / kBlock), dim3(kBlock), 0, st, run_base, n_runs, total, cost_by_rank, run_by_rank);
+    hipLaunchKernelGGL(k_run_assign, dim3(1), dim3(kBlock), 0, st, cost_by_rank, run_by_rank, n_runs, n_slots, order);
 }
 
 // ============================================================================================

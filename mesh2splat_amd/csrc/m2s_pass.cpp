@@ -23,18 +23,6 @@ static uint32_t band_workgroups(const m2s_ctx* c, uint32_t unit) {
     const uint32_t team = fused2_band_workgroups(c->scene.n_tri);
     return !team ? 0u : unit == 256u ? team : sparse_workgroups(c->scene.n_tri);
 }
-// The first resident set of a launch of `form` in runs of (1 << shift) units: the dispatch slots whose workgroups all start when the
-// launch does — the workgroups this device holds at once, in runs — which launch_run_order can fill with heavy and light runs side by
-// side.  Only in a -DM2S_RUN_ORDER_SPREAD build (A/B): config 3 is 1.5 % slower that way, so the order stays heaviest first.
-static uint32_t first_resident_slots([[maybe_unused]] int form, [[maybe_unused]] uint32_t shift) {
-#ifdef M2S_RUN_ORDER_SPREAD
-    const uint32_t wgs = form == M2S_PIPELINE_SPARSE ? sparse_resident_workgroups() : form == M2S_PIPELINE_LEAN ? fused3_resident_workgroups()
-                                                                                                                 : fused2_resident_workgroups();
-    return wgs >> shift;
-#else
-    return 0u;
-#endif
-}
 }  // namespace
 
 namespace m2s_host {
@@ -197,11 +185,10 @@ m2s_status warm_count_enqueue(m2s_ctx* c, uint32_t R) {
         if (writes) {
             const uint32_t n_units = band_workgroups(c, unit);
             launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, unit, table.shift, table.out, st);
-            const int form = lean_eligible(c, R) ? M2S_PIPELINE_LEAN : M2S_PIPELINE_TEAM;
             launch_run_order(table.out, n_runs(n_units, table.shift), c->lane[0].total, c->d_run_order, run_order_slots(n_units, table.shift),
-                             first_resident_slots(form, table.shift), st);
+                             c->d_run_rank, st);
             HIPCHK(c, hipGetLastError());
-            c->warm_spec_unit = unit; c->warm_spec_shift = table.shift; c->warm_spec_form = form;
+            c->warm_spec_unit = unit; c->warm_spec_shift = table.shift;
         }
     }
     return M2S_OK;
@@ -287,13 +274,11 @@ m2s_status warm_scene(m2s_ctx* c, uint32_t R, bool counted) {
         const RunInfo table = bands_for(c, ri, unit, true, &writes);
         if (writes) {
             // (already there if the count was enqueued by the upload and the expectation — units of 256 triangles — held)
-            // (... and the order, which depends on the form only where it has a first resident set to arrange)
-            const bool spec_order = c->warm_spec_form == ri.form || first_resident_slots(ri.form, table.shift) == 0u;
-            if (!(counted && c->warm_spec_unit == unit && c->warm_spec_shift == table.shift && spec_order)) {
+            if (!(counted && c->warm_spec_unit == unit && c->warm_spec_shift == table.shift)) {
                 launch_unit_bases(c->d_cnt, c->d_partials, sc.n_tri, unit, table.shift, table.out, st);
                 const uint32_t n_units = band_workgroups(c, unit);
                 launch_run_order(table.out, n_runs(n_units, table.shift), c->lane[0].total, c->d_run_order, run_order_slots(n_units, table.shift),
-                                 first_resident_slots(ri.form, table.shift), st);
+                                 c->d_run_rank, st);
                 HIPCHK(c, hipGetLastError());
                 HIPCHK(c, hipStreamSynchronize(st));
             }

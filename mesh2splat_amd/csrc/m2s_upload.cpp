@@ -189,6 +189,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     const size_t run_words = run_shift_for(units) ? (size_t)n_runs(units, run_shift_for(units)) + 1 : 0;
     const size_t o_bands = take(std::max<size_t>((size_t)kBandSlots * run_words, 1) * sizeof(unsigned long long));
     const size_t o_run_order = take(std::max<size_t>(run_shift_for(units) ? run_order_slots(units, run_shift_for(units)) : 0, 1) * sizeof(uint32_t));
+    const size_t o_run_rank = take(run_order_scratch_bytes(run_shift_for(units) ? run_order_slots(units, run_shift_for(units)) : 0));
     const size_t o_batch = take(std::max<size_t>(batch_table_capacity(n_tri), 1) * sizeof(uint32_t));
     M2S_TRY(c->scene_arena.reserve(c->err, arena, 1));
     M2S_TRY(ensure_stage(c));
@@ -263,6 +264,7 @@ m2s_status m2s_upload_scene(m2s_ctx* c, const m2s_mesh* meshes, uint32_t n_meshe
     c->d_bands = (unsigned long long*)(A + o_bands);
     c->run_table_words = run_words;
     c->d_run_order = (uint32_t*)(A + o_run_order);
+    c->d_run_rank = A + o_run_rank;
     c->run_order_unit = 0; c->run_order_shift = 0;
     c->d_batch_first = (uint32_t*)(A + o_batch);
     c->n_batch_tab = 0;

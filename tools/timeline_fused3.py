@@ -1,7 +1,8 @@
 """Per-wave timeline of k_fused3 (the lean team kernel) on a -DM2S_TIMELINE build of the library: when workgroups start, how long the
 triangle phase, the wait for the base / the other waves' entries and the strips take, how many waves are alive over time; and how far
 the workgroups age in lockstep: the spread of "waves in strips" over the plateau, the triangle phase per phase class, the classes that
-met on one CU (m2s_fused3.hip, phase classes; the hardware ids are recorded by builds from round 7 on).
+met on one CU (m2s_fused3.hip, phase classes; the hardware ids are recorded by builds from round 7 on); and per XCD what the dispatch
+order of the runs gave it (runs, fragments) and when it ran dry (start of its last workgroup, end of its last wave).
     M2S_LIB_PATH=mesh2splat_amd/_build_tl/libm2s_hip.so python tools/timeline_fused3.py [c3|c2] [out.json]"""
 import ctypes as C
 import json
@@ -91,6 +92,28 @@ if have_hw:
     print("SIMD of a workgroup's first wave, first generation:", np.bincount(simd[gen1], minlength=4).tolist())
 else:
     print("first generation: hardware ids not recorded by this build")
+# --- per XCD: what the dispatch order gave it and when it ran dry (RunInfo, m2s_device.h; tools/xcd_balance.py is the model) --------
+if have_hw:
+    lb = t[:, 0, 7] & 0xFFFFFFFF                                # the unit every workgroup converted
+    cnt = c.download_triangle_counts().astype(np.int64)
+    per_unit = np.add.reduceat(cnt, np.arange(0, len(cnt), 256))
+    n_units = len(per_unit)
+    shift = next((s for s in (5, 4, 3) if n_units >= (32 << s)), 0)     # run_shift_for
+    wg_end = ts[:, :, 5].max(axis=1)
+    wg_start = ts[:, :, 0].min(axis=1)
+    rows = []
+    for x in sorted(set(xcc[ok].tolist())):
+        sel = ok & (xcc == x)
+        rows.append({"xcc": int(x), "dispatched_as": sorted(set((np.nonzero(sel)[0] & 7).tolist())), "workgroups": int(sel.sum()),
+                     "runs": int(len(set((lb[sel] >> shift).tolist()))) if shift else 0, "fragments": int(per_unit[lb[sel]].sum()),
+                     "last_workgroup_start_ns": int(wg_start[sel].max()), "last_wave_end_ns": int(wg_end[sel].max())})
+    mean_f = np.mean([r["fragments"] for r in rows])
+    ends = np.array([r["last_wave_end_ns"] for r in rows])
+    print(f"per XCD (runs of {1 << shift} units): fragments heaviest / mean {max(r['fragments'] for r in rows) / mean_f:.4f}; "
+          f"last wave ends {ends.min()} ... {ends.max()} ns (spread {ends.max() - ends.min()} ns = {100.0 * (ends.max() - ends.min()) / en.max():.1f} % of the span)")
+    for r in rows:
+        print(f"  XCC {r['xcc']} (workgroups h % 8 in {r['dispatched_as']}): {r['workgroups']} workgroups, {r['runs']} runs, {r['fragments']} fragments "
+              f"({r['fragments'] / mean_f:.4f} of the mean); last workgroup starts {r['last_workgroup_start_ns']} ns, last wave ends {r['last_wave_end_ns']} ns")
 if out:
     json.dump({"t": ts.tolist(), "strips": strips.tolist(), "lb": (t[:, :, 7] & 0xFFFFFFFF).tolist(), "class": cls.tolist(),
                "xcc": xcc.tolist(), "hw_id": hwid.tolist()}, open(out, "w"))
