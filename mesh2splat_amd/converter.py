@@ -581,7 +581,7 @@ class Converter:
         split_screen (None: off, the frame is what it was without the argument; else a position in [0, 1]): the mesh render pass of the
         uploaded scene runs with the frame's camera and render mode (mesh_render) and the relighting pass composes the reference's
         split screen (relight_split): mesh left of the divider, splats right.  (Both of those frames carry the white divider; the fidelity
-        figure of a conversion is score(), which compares the splat frame with a mesh frame that has none.)  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: see ADVICE.md.)  `light_params`'s
+        figure of a conversion is score(), which compares the splat frame with a mesh frame that has none.)  (m2s_prepass + m2s_sort_prepass rather than the fused m2s_prepass_sorted: the benchmark reads the two calls' stage times.)  `light_params`'s
         renderer_resolution must equal `prepass_params`'s.  mesh_depth_test: the frame starts with the mesh depth prepass of the uploaded
         scene (mesh_depth) and the Gaussian prepass — then m2s_prepass_sorted — tests against its image on the device, the reference's
         "use the mesh as occluder in depth prepass".  -> what relight() returns (download=False: None, the frame stays on the device)."""

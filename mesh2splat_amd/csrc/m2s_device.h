@@ -236,7 +236,8 @@ struct m2s_prepass_params;
 namespace m2s {
 void prepass_prepare(const m2s_prepass_params& p, uint64_t n, PrepassK* out);
 // perm (or nullptr): record index of every position — the prepass then reads record perm[i] at position i (m2s_prepass_sorted);
-// dense: every one of the n positions is known to survive (the sort in front applied the frustum test): written at its own position, no append
+// dense: every one of the n positions passed the frustum test (the sort in front applied it): written at its own position, no append;
+// status[1] = 2 when one of them fails the prepass's last test (lambda2 < 0) — the output is then to be discarded and the frame repeated compacting
 hipError_t launch_prepass(const PrepassK& k, const float4* rec, uint32_t n, float4* quads, float* depths, unsigned long long* chain,
                           uint32_t epoch, unsigned long long* counter, unsigned long long* total, uint32_t* status, hipStream_t st,
                           const uint32_t* perm = nullptr, bool dense = false, uint32_t* sources = nullptr);

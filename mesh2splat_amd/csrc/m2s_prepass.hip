@@ -157,7 +157,8 @@ __global__ void __launch_bounds__(kPPWaves * 64) k_prepass(const PrepassK k, con
         vis[r] = prepass_one(k, g[r], perm ? src[r] : first + (uint32_t)r * 64u + (uint32_t)lane, valid[r], q[r], dvs[r]);   // (gid = the RECORD's index)
         if (dense) {
             // the sort in front of this launch already applied the frustum test (same function: m2s_viewmath.h) and put the survivors first:
-            // every one of the n positions survives, position i is written at i.  A disagreement would be a bug: reported, never silent.
+            // position i is written at i.  The one test the sort cannot apply is the last (lambda2 < 0 above, a matter of scale and
+            // rotation): a position that fails it is reported in status[1], and the host repeats the frame compacting (m2s_viewer.cpp).
             if (valid[r] && !vis[r]) __hip_atomic_store(&status[1], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             vis[r] = valid[r];
         }

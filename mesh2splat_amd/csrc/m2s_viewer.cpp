@@ -131,7 +131,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     // it is (re)allocated and when the tag wraps (see next_epoch)
     bool clear_chain = false;
     M2S_TRY(c->d_pp_chain.reserve(c->err, words, sizeof(unsigned long long), &clear_chain));
-    const uint32_t epoch = ++c->pp_epoch;
+    uint32_t epoch = ++c->pp_epoch;
     if (clear_chain || (epoch & 0xFFFFu) == 0)
         HIPCHK(c, hipMemsetAsync(c->d_pp_chain, 0, c->d_pp_chain.cap() * sizeof(unsigned long long), c->stream));
     PrepassK k;
@@ -149,9 +149,11 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     unsigned long long* res = &c->h_total[m2s_ctx::kPinnedPrepass];
     res[0] = 0; res[1] = 0;
     if (k.arrival_order) HIPCHK(c, hipMemsetAsync(c->d_pp_chain, 0, sizeof(unsigned long long), c->stream));
-    // Without a depth image the prepass's only test is the frustum test, a function of the position: the sort applies it to the keys
+    // Without a depth image the prepass's first test is the frustum test, a function of the position: the sort applies it to the keys
     // (view_project, the prepass's own function), the culled records sort behind the survivors, and the prepass runs over the survivors
-    // alone — dense: no compaction, no look-back, no read of a record that is not drawn.
+    // alone — dense: no compaction, no look-back, no read of a record that is not drawn.  The shader's LAST test (lambda2 < 0, :183) depends
+    // on scale and rotation and is not known to the sort: a record that passes the first and fails the last makes the dense launch report a
+    // disagreement, and the frame is then repeated as in the `clash` case below — everything sorted, the prepass compacting.
     bool dense = false;
     uint32_t n_run = (uint32_t)n;
     if (sorted) {
@@ -174,12 +176,32 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
         if (!dense && n_run) M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
     }
     uint32_t* src_out = sorted && !dense ? c->d_sq_src.get() : nullptr;
-    HIPCHK(c, pp_marks.mark(0, c->stream));
-    if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, sorted ? c->d_sorted_quads.get() : c->d_quads.get(), c->d_pp_depths, c->d_pp_chain + 1,
-                                        epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense, src_out));
-    HIPCHK(c, pp_marks.mark(1, c->stream));
-    if (k.arrival_order) HIPCHK(c, hipMemcpyAsync(&res[0], c->d_pp_chain, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t* status = reinterpret_cast<const uint32_t*>(&res[1]);
+    for (;;) {
+        HIPCHK(c, pp_marks.mark(0, c->stream));
+        if (n_run) HIPCHK(c, launch_prepass(k, (const float4*)d_records, n_run, sorted ? c->d_sorted_quads.get() : c->d_quads.get(), c->d_pp_depths, c->d_pp_chain + 1,
+                                            epoch, c->d_pp_chain, &res[0], reinterpret_cast<uint32_t*>(&res[1]), c->stream, perm, dense, src_out));
+        HIPCHK(c, pp_marks.mark(1, c->stream));
+        if (k.arrival_order) HIPCHK(c, hipMemcpyAsync(&res[0], c->d_pp_chain, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!(dense && status[1] == 2u)) break;
+        // A survivor of the sort's frustum test fails the prepass's last test (lambda2 < 0: a needle whose screen-space covariance is
+        // numerically of rank 1).  The dense launch wrote a quad for it; the frame is taken again the way a depth image takes it: every
+        // record sorted, the prepass compacting through the permutation and storing the sources beside the quads.  The positions are in
+        // the plane by now (where there is one), the chain gets an epoch of its own under the rule above, and the stage times read
+        // below are those of this second attempt.
+        uint32_t* u = c->d_sort_u32;
+        bool clash = false;
+        res[0] = 0; res[1] = 0;
+        HIPCHK(c, sort_prepass_permutation((const float4*)d_records, (uint32_t)n, k.M, k.V, k.P, false, u, u + 2 * n, u + 3 * n, c->d_sort_temp, c->d_sort_temp.cap(),
+                                           c->d_pos_plane, true, sort_marks, c->stream, reinterpret_cast<uint32_t*>(&c->h_total[m2s_ctx::kPinnedSortMM]), &n_run,
+                                           &clash));
+        M2S_TRY(c->d_sq_src.reserve(c->err, n, sizeof(uint32_t)));
+        epoch = ++c->pp_epoch;
+        if ((epoch & 0xFFFFu) == 0) HIPCHK(c, hipMemsetAsync(c->d_pp_chain, 0, c->d_pp_chain.cap() * sizeof(unsigned long long), c->stream));
+        dense = false;
+        src_out = c->d_sq_src.get();
+    }
     // (only the clock this call opened is read: the other one holds an earlier call's marks)
     if (sorted) {
         const ClockOf<SortMark>& clock = c->sort_clock;
@@ -192,8 +214,7 @@ static m2s_status prepass_impl(m2s_ctx* c, const m2s_prepass_params* p, const vo
     } else if (c->prepass_clock.on()) {
         HIPCHK(c, c->prepass_clock.span(SpanMark::Begin, SpanMark::End, &c->last_prepass_ms));
     }
-    if (reinterpret_cast<uint32_t*>(&res[1])[1] == 2u) return fail(c, M2S_ERR_HIP, "prepass_sorted: the sort's frustum test and the prepass's disagree (internal error)");
-    if (reinterpret_cast<uint32_t*>(&res[1])[1]) return fail(c, M2S_ERR_HIP, "prepass: look-back chain timed out");
+    if (status[1]) return fail(c, M2S_ERR_HIP, "prepass: look-back chain timed out");
     if (dense) res[0] = n_run;                  // (the survivors were counted by the sort; the dense prepass appends nothing)
     if (sorted) {
         c->sq_n = res[0];

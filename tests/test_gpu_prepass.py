@@ -238,23 +238,7 @@ def test_prepass_full_size_against_oracle(conv, oracle):
     assert 0.0 < conv.last_prepass_ms < 50.0
 
 
-def _needles(n, seed=11):
-    """Needle-shaped Gaussians in front of the default camera: one scale 10^4..10^6 times the others, random orientation.  Their
-    screen-space covariance is numerically rank 1, so lambda2 = (mid - delta) / 2 is pure rounding noise and comes out negative
-    for part of them — the shader's LAST cull test (gaussianSplattingPrepassCS.glsl:183) then removes them."""
-    rng = np.random.default_rng(seed)
-    r = np.zeros((n, 24), np.float32)
-    r[:, 0:3] = rng.uniform(-0.6, 0.6, (n, 3))
-    r[:, 3] = 1
-    r[:, 4:8] = rng.uniform(0.2, 1, (n, 4))
-    r[:, 8] = np.exp(rng.uniform(np.log(3e2), np.log(3e4), n))
-    r[:, 9:11] = 1e-2
-    q = rng.normal(size=(n, 4))
-    r[:, 16:20] = q / np.linalg.norm(q, axis=1, keepdims=True)
-    r[:, 12:15] = (0, 0, 1)
-    r[:, 20:22] = 0.5
-    r[:, 23] = 1
-    return r
+_needles = prepass_cases.needle_records          # (moved: shared with the tests of m2s_prepass_sorted on such records)
 
 
 def test_the_last_cull_test_is_reproduced_on_needles(conv, oracle):
