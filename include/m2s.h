@@ -681,6 +681,55 @@ float m2s_last_merge_sh_ms(const m2s_ctx* ctx);
  * smaller destination. */
 const void* m2s_device_merge_map(const m2s_ctx* ctx);
 m2s_status m2s_download_merge_map(m2s_ctx* ctx, uint32_t* dst, uint64_t capacity, uint64_t* out_n);
+/* The record model of m2s_merge, m2s_lod_build and everything built on them.  M2S_MERGE_MODEL_FOOTPRINT (the default) is the pin above:
+ * right for what the conversion emits.  M2S_MERGE_MODEL_GAUSSIAN reads a record as the viewer draws one of any other origin
+ * (m2s_read_ply, m2s_upload_records, m2s_prepass_params.format = 1): a 3D Gaussian with three standard deviations sigma |scale[k]| along
+ * r_1, r_2, r_3 and covariance C = sigma^2 sum_k s_k^2 r_k r_k^T.  sigma multiplies every stored scale before it is read as a standard
+ * deviation in the units of the positions: 1 for a .ply (it holds the drawn deviations), gaussian_std for a conversion behind
+ * m2s_records_to_world_units.  A parent's covariance is the sum of a term that scales with sigma^2 and the spread of the members'
+ * positions, which does not: the merge must know sigma.  Under FOOTPRINT every entry point behaves as it did before the switch existed
+ * and sigma is not read.  The switch invalidates nothing; a tree remembers the model and sigma it was built under.  No flag bit is
+ * involved: the valid flag words of m2s_merge and m2s_lod_build are what they were.
+ * M2S_ERR_INVALID: a model other than 0 or 1, a sigma that is NaN, infinite or <= 0.  M2S_ERR_STATE: conversions in flight.
+ * Under M2S_MERGE_MODEL_GAUSSIAN pins 1, 3, 4, 6, 7, 8 of m2s_merge hold unchanged and (tests/merge_gauss_ref.py restates these):
+ *  2g. Runs.  The axis of a record is the row r_k whose |scale[k]| is smallest: k = 0; k = 1 where |scale[1]| < |scale[0]|; k = 2 where
+ *     |scale[2]| < |scale[k]| — the lower k on a tie (m2s_prepass's choice for format 1, except that a tie of the two smaller scales
+ *     goes to the lower of THEM; a flat record, scale[2] = 0, has its r_3).  The rows in fp32 exactly as written in front of pin 1, one
+ *     rounding per operation.  Position j starts a run iff one of pin 2's other conditions holds or !(fabsf(d) >= min_axis_dot), d the
+ *     fp32 dot of the two axes as in pin 2.  The rule is always sign-free: M2S_MERGE_UNSIGNED_AXIS is accepted and changes nothing.
+ *  5g. A segment of members i = 1..m >= 2 in sorted order, all arithmetic in fp64 from the stored floats without contraction, every
+ *     field rounded to fp32 once:
+ *       a_i = the product of the two largest of |s_i1|, |s_i2|, |s_i3| (the splat's area measure; |sx sy| for a flat record);
+ *       w_i = a_i, or 1 for every member where their sum is 0;  W, d_i, mu, position as in pin 5;
+ *       C_i = sigma^2 ((s_i1^2 r1 r1^T + s_i2^2 r2 r2^T) + s_i3^2 r3 r3^T), sigma the float widened, sigma^2 its fp64 square;
+ *       M = sum w_i (C_i + (d_i - mu)(d_i - mu)^T) / W, symmetric, held as six doubles m00, m01, m02, m11, m12, m22.
+ *       Eigenpairs by cyclic Jacobi rotations.  V = the identity.  A sweep visits the pairs (p, q) = (0, 1), (0, 2), (1, 2) in this
+ *       order; the iteration stops in front of a sweep where m01, m02, m12 are all exactly 0, and after 16 sweeps.  A pair with
+ *       m_pq == 0 is skipped; otherwise, with r the third index,
+ *         theta = (m_qq - m_pp) / (2 m_pq);  t = sgn / (|theta| + sqrt(theta^2 + 1)), sgn = -1 where theta < 0, else 1;
+ *         c = 1 / sqrt(t^2 + 1), s = t c;  m_pp -= t m_pq, m_qq += t m_pq (both with the old m_pq), then m_pq = 0 exactly;
+ *         (m_rp, m_rq) = (c m_rp - s m_rq, s m_rp + c m_rq);  for k = 0..2: (V_kp, V_kq) = (c V_kp - s V_kq, s V_kp + c V_kq)
+ *       (a theta that overflows gives t = 0: the element is dropped).  l_k = max(m_kk, 0) with eigenvector column k of V.  The pairs
+ *       are sorted descending in l, the lower original index first on a tie (three compare-and-swaps of neighbours, (0,1), (1,2),
+ *       (0,1), each only where the later one is strictly larger); e1, e2 = the first two eigenvectors, e3 = e1 x e2;
+ *       scale = (sqrt(l1) / sigma, sqrt(l2) / sigma, sqrt(l3) / sigma, the first member's scale[3]);
+ *       rotation = pin 5's quat_cast of the matrix with columns e1, e2, e3, stored the same way;
+ *       rgb, normal, pbr, normal[3], pbr[2..3]: pin 5's rules with these w_i;
+ *       alpha = min(1, sum a_i alpha_i / a_p) — alpha-weighted area is conserved — with a_p = (sqrt(l1) / sigma)(sqrt(l2) / sigma) in
+ *       fp64; where a_p is 0 or not finite, pin 5's mean sum w_i alpha_i / W.  (The a_i here are the areas themselves: under the
+ *       unit weights every one of them is 0 and so is alpha, where a_p > 0.)
+ *     Valid records are finite and their squares fit fp64, so M is finite: there is no other fallback.  Two coincident identical records
+ *     give their own scales and twice their alpha; a 2 x 2 block of flat records of deviation s at spacing h gives in-plane variance
+ *     s^2 + h^2 / 4 and thickness 0.
+ *  5sg. The SH plane: pin 5s with w_i = a_i of pin 5g (and 1 where their sum is 0).  Everything else of 5s is unchanged.
+ *  4g. Tree bounds (m2s_lod_build): e = sigma * fmaxf(fmaxf(|scale[0]|, |scale[1]|), |scale[2]|) in fp32, one rounding for the product:
+ *     tau_px counts one standard deviation in pixels.  The cuts read only bounds and parents and are what they were.  m2s_lod_blend on
+ *     a tree built under this model returns M2S_ERR_STATE: its eight frame turns and its axis-by-axis lerp assume the footprint's axis
+ *     order (scale[2] a thickness along r_3), which pin 5g's descending order does not keep. */
+enum { M2S_MERGE_MODEL_FOOTPRINT = 0, M2S_MERGE_MODEL_GAUSSIAN = 1 };
+m2s_status m2s_set_merge_model(m2s_ctx* ctx, uint32_t model, float sigma);
+uint32_t m2s_merge_model(const m2s_ctx* ctx);
+float m2s_merge_sigma(const m2s_ctx* ctx);
 
 /* ---- level-of-detail tree and its per-camera cut (no counterpart in the reference, which draws every Gaussian it converted) ------- */
 /* m2s_lod_build keeps a chain of m2s_merge steps resident and linked; m2s_lod_select takes a cut through it for one camera: each part
@@ -957,7 +1006,8 @@ m2s_status m2s_last_lod_occlusion_counts(const m2s_ctx* ctx, uint64_t out[4]);
  * Known limit: alpha is lerped like the colour, and near t = 1 the m children of a parent are m coincident copies of it; front-to-back
  * blending of m copies is 1 - (1 - a g)^m against a g, so a change in edge softness remains at the switch.
  * Synchronous.  M2S_ERR_INVALID: as m2s_lod_select, a band that is not finite or outside (0, 1], reserved != 0.  M2S_ERR_STATE: no tree,
- * conversions in flight, records that are not the last cut's. */
+ * conversions in flight, records that are not the last cut's, a tree built under M2S_MERGE_MODEL_GAUSSIAN (m2s_set_merge_model, pin
+ * 4g: the eight turns and the axis-by-axis lerp assume the footprint's axis order; the model is the tree's, whatever the switch says now). */
 typedef struct m2s_lod_blend_params {
     float    camera_position[3];  /* as m2s_lod_select_params: the values the cut was taken with */
     float    focal_px;            /* finite, > 0 */
@@ -1448,6 +1498,15 @@ const char* m2s_host_scene_warnings(const m2s_host_scene* scene);               
  * alpha = sigmoid, colour = SH -> RGB, quaternion normalised; or a compact .ply ("compact export" above).  Free with m2s_free_records. */
 m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr);
 void m2s_free_records(m2s_gaussian* records);
+/* m2s_read_ply that keeps the view-dependent colour.  Records, *out_n and *out_has_pbr are m2s_read_ply's, bit for bit.  For a file
+ * with f_dc (every layout above but the compact one) *out_sh = float[n][48] in the layout of the baked plane (m2s_upload_sh,
+ * m2s_write_ply_sh): f_dc_0..2, then 15 coefficients per colour channel.  *out_degree comes from the number of f_rest properties:
+ * 0, 9, 24, 45 -> 0..3; a file of 45 has its row copied across, one of 3 c per channel c < 15 has channel k's c coefficients at
+ * 3 + 15 k and +0 above them.  Any other number, an f_rest_* that is not a float or not one of f_rest_0 .. f_rest_{count-1}:
+ * M2S_ERR_IO with m2s_io_last_error.  A compact .ply and a file of zero rows: *out_sh = NULL (degree 0, resp. the header's).  On
+ * failure nothing is allocated.  out_sh and out_degree must not be NULL.  Free the plane with m2s_free_sh (NULL is fine). */
+m2s_status m2s_read_ply_sh(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr, float** out_sh, uint32_t* out_degree);
+void m2s_free_sh(float* sh);
 /* Message of the last failed scene-I/O call on this thread. */
 const char* m2s_io_last_error(void);
 

@@ -3,4 +3,7 @@ def __getattr__(name):
     if name in ("write_ply_compact", "write_ply"):
         from . import converter
         return getattr(converter, name)
+    if name == "read_ply_sh":
+        from . import gltf_io
+        return gltf_io.read_ply_sh
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -65,6 +65,7 @@ EXPORTS = (
     "m2s_write_ply_compact", "m2s_export_ply_compact", "m2s_last_compact_stage_ms",
     "m2s_vertex_table", "m2s_geo_planes",
     "m2s_set_carry_sh", "m2s_carry_sh", "m2s_upload_sh", "m2s_sh_plane_info", "m2s_device_lod_sh", "m2s_download_lod_sh", "m2s_last_merge_sh_ms",
+    "m2s_set_merge_model", "m2s_merge_model", "m2s_merge_sigma", "m2s_read_ply_sh", "m2s_free_sh",
 )
 
 
@@ -332,6 +333,11 @@ def load():
         "m2s_device_lod_sh": (vp, [vp]),
         "m2s_download_lod_sh": (C.c_int, [vp, vp, u64, C.POINTER(u32)]),
         "m2s_last_merge_sh_ms": (C.c_float, [vp]),
+        "m2s_set_merge_model": (C.c_int, [vp, u32, C.c_float]),
+        "m2s_merge_model": (u32, [vp]),
+        "m2s_merge_sigma": (C.c_float, [vp]),
+        "m2s_read_ply_sh": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(u32)]),
+        "m2s_free_sh": (None, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

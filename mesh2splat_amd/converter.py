@@ -657,6 +657,22 @@ class Converter:
     def carry_sh(self, on: bool):
         self._check(self._L.m2s_set_carry_sh(self._h, 1 if on else 0))
 
+    @property
+    def merge_model(self) -> tuple:
+        """m2s_merge_model / m2s_merge_sigma -> ("footprint" | "gaussian", sigma): the record model merge(), merge_count(),
+        merge_to_budget() and lod_build() act under (include/m2s.h, pins 2g, 5g, 5sg, 4g)."""
+        from . import merge as _mg
+        return _mg.MODELS[int(self._L.m2s_merge_model(self._h))], float(self._L.m2s_merge_sigma(self._h))
+
+    def set_merge_model(self, model: str = "footprint", sigma: float = 1.0):
+        """m2s_set_merge_model.  "footprint" (the default): a record is the flat texel footprint the conversion emits.  "gaussian": a 3D
+        Gaussian with standard deviations sigma * scale[0..2], what a loaded .ply holds (sigma = 1) or a conversion behind
+        records_to_world_units (sigma = gaussian_std).  lod_blend() refuses a tree built under "gaussian"."""
+        from . import merge as _mg
+        if model not in _mg.MODELS:
+            raise ValueError(f"merge model {model!r}: one of {_mg.MODELS}")
+        self._check(self._L.m2s_set_merge_model(self._h, _mg.MODELS.index(model), float(sigma)))
+
     def upload_sh(self, sh, degree: int = 3):
         """m2s_upload_sh: `sh` (n, 48) float32, n the context's stored records, becomes their SH plane of this degree (no tap counts)."""
         sh = np.ascontiguousarray(sh, np.float32)

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -229,6 +230,20 @@ m2s_status m2s_set_carry_sh(m2s_ctx* c, int enabled) {
 }
 
 int m2s_carry_sh(const m2s_ctx* c) { return c && c->carry_sh ? 1 : 0; }
+
+m2s_status m2s_set_merge_model(m2s_ctx* c, uint32_t model, float sigma) {
+    if (!c) return M2S_ERR_INVALID;
+    if (model != M2S_MERGE_MODEL_FOOTPRINT && model != M2S_MERGE_MODEL_GAUSSIAN) return fail(c, M2S_ERR_INVALID, "model is neither M2S_MERGE_MODEL_FOOTPRINT nor M2S_MERGE_MODEL_GAUSSIAN");
+    if (!std::isfinite(sigma) || !(sigma > 0.0f)) return fail(c, M2S_ERR_INVALID, "sigma is not finite or not positive");
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    c->merge_model = model;
+    c->merge_sigma = sigma;
+    return M2S_OK;
+}
+
+uint32_t m2s_merge_model(const m2s_ctx* c) { return c ? c->merge_model : (uint32_t)M2S_MERGE_MODEL_FOOTPRINT; }
+
+float m2s_merge_sigma(const m2s_ctx* c) { return c ? c->merge_sigma : 1.0f; }
 
 m2s_status m2s_debug_set_launch_counter(m2s_ctx* c, uint32_t value) {
     if (!c) return M2S_ERR_INVALID;

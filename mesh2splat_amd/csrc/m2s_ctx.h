@@ -233,6 +233,10 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     // with d_sh (no copy back); a tree built with the switch on owns a plane of its nodes and its cuts compact it into d_sh
     bool carry_sh = false;
     m2s_host::DevBuf<float> d_sh_alt;                    // capacity in rows of 48 floats
+    // m2s_set_merge_model: how a merge reads a record (pins 2g, 5g, 5sg, 4g under M2S_MERGE_MODEL_GAUSSIAN), and what its scales are
+    // multiplied with to be standard deviations; not read under M2S_MERGE_MODEL_FOOTPRINT
+    uint32_t merge_model = M2S_MERGE_MODEL_FOOTPRINT;
+    float merge_sigma = 1.0f;
     float last_merge_sh_ms = 0.0f;                       // the SH reduction of the last merge (0: none ran); inside stage [2]
     m2s_host::ClockOf<m2s_host::SpanMark> merge_sh_clock;    // always on
     // level-of-detail tree (m2s_lod.cpp): the node pool (leaves, then every level a merging step added), a parent word and a 16-byte
@@ -243,6 +247,8 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     m2s_host::DevBuf<float> d_lod_sh;                    // the fourth plane, 48 floats per node: only while lod_has_sh
     bool lod_has_sh = false;                             // the tree was built with m2s_set_carry_sh on over records with a plane
     uint32_t lod_sh_degree = 0;                          // ... of this degree
+    uint32_t lod_model = M2S_MERGE_MODEL_FOOTPRINT;      // the merge model the tree was built under, and its sigma (m2s_lod_blend refuses
+    float lod_sigma = 1.0f;                              // a Gaussian tree)
     uint32_t lod_levels = 0;
     uint64_t lod_first[M2S_LOD_MAX_STEPS + 2] = {};      // first node of every level; [lod_levels] = the nodes
     uint32_t lod_R = 0;                                  // resolutionTarget of the leaves

@@ -324,25 +324,30 @@ size_t merge_scan_temp_bytes(uint32_t n);
 // keys / perm: the sorted keys and the permutation of compact_keys_and_sort (n words each).  flag, run_start: n words each, packed,
 // sums: n 64-bit words each of work area; seg_start: n + 1 words, afterwards the first sorted position of every segment and n behind
 // the last; totals: kMergeTotalsWords; temp: merge_scan_temp_bytes(n).  level 0..10, max_group >= 1, n > 0.  unsigned_axis: the
-// M2S_MERGE_UNSIGNED_AXIS instances of k_merge_heads / k_merge_reduce (pins 2u, 5u), here and in merge_reduce.
+// M2S_MERGE_UNSIGNED_AXIS instances of k_merge_heads / k_merge_reduce (pins 2u, 5u), here and in merge_reduce.  gauss: the heads of
+// pin 2g (M2S_MERGE_MODEL_GAUSSIAN), whatever unsigned_axis says.
 hipError_t merge_segments(const float4* rec, const uint32_t* keys, const uint32_t* perm, uint32_t n, uint32_t level, uint32_t max_group, float min_axis_dot,
                           uint32_t* flag, uint32_t* run_start, unsigned long long* packed, unsigned long long* sums, uint32_t* seg_start, uint32_t* totals,
-                          void* temp, size_t temp_bytes, bool unsigned_axis, hipStream_t st);
+                          void* temp, size_t temp_bytes, bool unsigned_axis, bool gauss, hipStream_t st);
 // k_merge_reduce, one lane per segment: out[s] = the parent of segment s (a copy of its member where it has one), map[i] = s for every
 // member i.  out: `segments` records, not the memory rec points into; map: n words.
 hipError_t merge_reduce(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float4* out,
                         uint32_t* map, bool unsigned_axis, hipStream_t st);
-// k_merge_reduce_sh (pin 5s), one lane per (segment, float4 column) of the SH plane: out row s = the weighted mean of the members' rows
+// k_merge_reduce_gauss (pins 4, 5g), as merge_reduce under M2S_MERGE_MODEL_GAUSSIAN; sigma: m2s_merge_sigma, finite and > 0
+hipError_t merge_reduce_gauss(const float4* rec, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments, float sigma,
+                              float4* out, uint32_t* map, hipStream_t st);
+// k_merge_reduce_sh (pin 5s; gauss: the weights of pin 5sg), one lane per (segment, float4 column) of the SH plane: out row s = the weighted mean of the members' rows
 // of sh (a copy where it has one member).  sh: n rows of 48 floats; out: `segments` rows, not the memory sh points into.
 constexpr uint32_t kMergeShLanes = 12;     // float4 per row of the plane
 hipError_t merge_reduce_sh(const float4* rec, const float4* sh, const uint32_t* perm, const uint32_t* seg_start, const uint32_t* totals, uint32_t segments,
-                           float4* out, hipStream_t st);
+                           float4* out, bool gauss, hipStream_t st);
 
 // ---- level-of-detail tree and its cut (m2s_lod.hip) ------------------------------------------------------------------------------------
 // k_lod_link.  parent[t] = offset + map[t] for t < n_map (map NULL: M2S_LOD_NO_PARENT, the last level); bounds[t] = (position.xyz,
 // fmaxf(|scale[0]|, |scale[1]|)) of rec[t] for t < n_rec.  parent, rec and bounds point at the first node they concern.
+// gauss (pin 4g): the bound's fourth float is sigma * fmaxf(fmaxf(|scale[0]|, |scale[1]|), |scale[2]|) (k_lod_link_gauss); sigma is not read otherwise.
 hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32_t* parent, const float4* rec, uint32_t n_rec, float4* bounds,
-                    hipStream_t st);
+                    bool gauss, float sigma, hipStream_t st);
 struct LodSelectK { float cx, cy, cz, focal, tau2, near2; };
 constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine,
 constexpr uint32_t kLodPlainWord = 18;     // [18] nodes the cut selects before the visibility plane masks it (written with a plane only),

@@ -59,10 +59,13 @@ const char* m2s_host_scene_warnings(const m2s_host_scene* s) { return s ? s->war
 // all present (hasPbr).  The fourteen mandatory properties must be stored as float (happly's getProperty<float> refuses anything
 // it would have to narrow); the vertex element must come first (what every 3DGS writer produces; list properties of later elements
 // are never touched).  ASCII numbers are parsed the way happly parses them: operator>> of an istringstream on the token.
-m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr) {
+// out_sh / out_degree (both or neither; m2s_read_ply_sh): the rows' f_dc and f_rest too, as float[n][48] in the plane's channel-major
+// layout (f_dc[3], then 15 coefficients per channel), the degree from the number of f_rest properties; NULL for a file without f_dc.
+static m2s_status read_ply_any(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr, float** out_sh, uint32_t* out_degree) {
     if (!path || !out_records || !out_n) { g_io_error = "NULL argument"; return M2S_ERR_INVALID; }
     *out_records = nullptr;
     *out_n = 0;
+    if (out_sh) { *out_sh = nullptr; *out_degree = 0; }
     {   // the compact layout (a `chunk` element + the four packed_* properties) has its own decoder; every other file is read as before
         m2s_status cs = M2S_OK;
         const int compact = m2s_host::read_compact_ply(path, out_records, out_n, g_io_error, &cs);
@@ -72,9 +75,10 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
     FILE* f = std::fopen(path, "rb");
     if (!f) { g_io_error = std::string("Error loading PLY file: ") + path; return M2S_ERR_IO; }
     m2s_gaussian* rec = nullptr;
+    float* sh = nullptr;
     // nothing may throw across the C ABI: std::string / std::map / std::vector operations below are inside the try
     try {
-        auto fail = [&](const std::string& m) { std::fclose(f); std::free(rec); g_io_error = m; return M2S_ERR_IO; };
+        auto fail = [&](const std::string& m) { std::fclose(f); std::free(rec); std::free(sh); g_io_error = m; return M2S_ERR_IO; };
         char line[512];
         if (!std::fgets(line, sizeof line, f) || std::strncmp(line, "ply", 3) != 0) return fail("not a PLY file");
         uint64_t n = 0;
@@ -130,6 +134,18 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
         bool has_pbr = true;
         for (int i = 0; i < 5; ++i) has_pbr = has_pbr && has_f(kPbr[i]);
         if (has_pbr) for (int i = 0; i < 5; ++i) op[i] = props[index[kPbr[i]]].off;
+        // f_rest_0 .. f_rest_{c-1}: 3 ((degree + 1)^2 - 1) of them, every one a float, no other f_rest_* beside them
+        size_t orest[45];
+        uint32_t n_rest = 0, per_channel = 0, degree = 0;
+        if (out_sh) {
+            uint32_t named = 0;
+            for (const Prop& pr : props) named += pr.name.compare(0, 7, "f_rest_") == 0 ? 1u : 0u;
+            while (n_rest < 45 && has_f(("f_rest_" + std::to_string(n_rest)).c_str())) { orest[n_rest] = props[index["f_rest_" + std::to_string(n_rest)]].off; ++n_rest; }
+            if (named != n_rest) return fail("the f_rest properties are not float f_rest_0 .. f_rest_" + std::to_string(named ? named - 1 : 0));
+            if (n_rest != 0 && n_rest != 9 && n_rest != 24 && n_rest != 45) return fail("the number of f_rest properties is none of 0, 9, 24, 45");
+            degree = n_rest == 0 ? 0u : n_rest == 9 ? 1u : n_rest == 24 ? 2u : 3u;
+            per_channel = n_rest / 3;
+        }
         // the header's vertex count is untrusted: it must fit the bytes that are actually in the file
         const long body0 = std::ftell(f);
         if (body0 < 0 || std::fseek(f, 0, SEEK_END) != 0) return fail("cannot seek in PLY file");
@@ -141,6 +157,11 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
         if (n > SIZE_MAX / sizeof(m2s_gaussian)) return fail("PLY vertex count too large");
         rec = n ? (m2s_gaussian*)std::malloc((size_t)n * sizeof(m2s_gaussian)) : nullptr;
         if (n && !rec) { std::fclose(f); g_io_error = "host allocation failed"; return M2S_ERR_OOM; }
+        if (out_sh && n) {
+            if (n > SIZE_MAX / (48 * sizeof(float))) return fail("PLY vertex count too large");
+            sh = (float*)std::calloc((size_t)n, 48 * sizeof(float));             // (coefficients above the degree stay +0)
+            if (!sh) { std::fclose(f); std::free(rec); g_io_error = "host allocation failed"; return M2S_ERR_OOM; }
+        }
         const float sh_c0 = 0.28209479177387814f;
         // one row (little-endian bytes at the header's offsets) -> one record
         auto convert = [&](const uint8_t* r, m2s_gaussian& g) {
@@ -157,6 +178,11 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
             else { const float inv = 1.0f / len; g.rotation[0] = qw * inv; g.rotation[1] = qx * inv; g.rotation[2] = qy * inv; g.rotation[3] = qz * inv; }
             if (has_pbr) { g.pbr[0] = F(op[3]); g.pbr[1] = F(op[4]); g.pbr[2] = 0.0f; g.pbr[3] = 0.0f; }
             else g.pbr[0] = g.pbr[1] = g.pbr[2] = g.pbr[3] = 0.0f;
+            if (sh) {
+                float* row48 = sh + (size_t)(&g - rec) * 48;
+                row48[0] = F(o[3]); row48[1] = F(o[4]); row48[2] = F(o[5]);
+                for (uint32_t k = 0; k < n_rest; ++k) row48[3 + (k / per_channel) * 15 + k % per_channel] = F(orest[k]);
+            }
         };
         if (format == kAscii) {
             // happly: one line per vertex (empty lines skipped), split at whitespace, one token per property, each parsed by
@@ -201,18 +227,30 @@ m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* 
         *out_records = rec;
         *out_n = n;
         if (out_has_pbr) *out_has_pbr = has_pbr ? 1 : 0;
+        if (out_sh) { *out_sh = sh; *out_degree = degree; }
         return M2S_OK;
     } catch (const std::bad_alloc&) {
-        std::fclose(f); std::free(rec);
+        std::fclose(f); std::free(rec); std::free(sh);
         g_io_error = "host allocation failed";
         return M2S_ERR_OOM;
     } catch (...) {
-        std::fclose(f); std::free(rec);
+        std::fclose(f); std::free(rec); std::free(sh);
         g_io_error = "unexpected failure while reading the PLY file";
         return M2S_ERR_IO;
     }
 }
 
+m2s_status m2s_read_ply(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr) {
+    return read_ply_any(path, out_records, out_n, out_has_pbr, nullptr, nullptr);
+}
+
+m2s_status m2s_read_ply_sh(const char* path, m2s_gaussian** out_records, uint64_t* out_n, int* out_has_pbr, float** out_sh, uint32_t* out_degree) {
+    if (!out_sh || !out_degree) { g_io_error = "NULL argument"; return M2S_ERR_INVALID; }
+    return read_ply_any(path, out_records, out_n, out_has_pbr, out_sh, out_degree);
+}
+
 void m2s_free_records(m2s_gaussian* records) { std::free(records); }
+
+void m2s_free_sh(float* sh) { std::free(sh); }
 
 }  // extern "C"

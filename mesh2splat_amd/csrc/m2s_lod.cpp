@@ -359,6 +359,8 @@ m2s_status m2s_lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out
     M2S_TRY(lod_blend_check(c, p));
     if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
     if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    if (c->lod_model != M2S_MERGE_MODEL_FOOTPRINT)
+        return fail(c, M2S_ERR_STATE, "the tree was built under M2S_MERGE_MODEL_GAUSSIAN: the blend's frame turns and axis-by-axis lerp assume the footprint's axis order");
     if (!lod_ids_valid(c) || c->lod_ids_gen != c->lod_tree_gen || c->last_records != c->lane[0].records.get() || c->last_stored != c->lod_ids_tag.n)
         return fail(c, M2S_ERR_STATE, "the current records are not what the last cut of this tree left (m2s_lod_select without M2S_LOD_DRY_RUN first)");
     return lod_blend(c, p, out_counts);
@@ -403,6 +405,8 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     const bool unsigned_axis = (p->flags & M2S_MERGE_UNSIGNED_AXIS) != 0;   // (every step, the ones that merge nothing included)
     const bool with_sh = c->carry_sh && c->sh_tag.holds(*c, n0);            // pin 4s: the tree owns a plane too
     const uint32_t sh_degree = c->sh_degree;
+    const bool gauss = c->merge_model == M2S_MERGE_MODEL_GAUSSIAN;          // pin 4g: every step merges under it (merge_run) and the bounds follow
+    const float sigma = c->merge_sigma;
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->lod_build_clock.begin(c->err, true));                    // (measured whatever m2s_set_profiling says)
     c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
@@ -417,7 +421,7 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     first[1] = n0;
     if (n0) {
         HIPCHK(c, hipMemcpyAsync(c->d_lod_nodes, c->last_records, n0 * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, c->d_lod_nodes, (uint32_t)n0, c->d_lod_bounds, c->stream));
+        HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, c->d_lod_nodes, (uint32_t)n0, c->d_lod_bounds, gauss, sigma, c->stream));
         if (with_sh) HIPCHK(c, hipMemcpyAsync(c->d_lod_sh, c->d_sh, n0 * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     for (uint32_t s = 0; s < p->n_steps; ++s) {
@@ -435,10 +439,10 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
             HIPCHK(c, hipMemcpyAsync(c->d_lod_sh + 48 * first[levels], c->d_sh, after * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         }
         HIPCHK(c, lod_link(c->d_merge_map, (uint32_t)cnt, (uint32_t)first[levels], c->d_lod_parent + below, level, (uint32_t)after,
-                           c->d_lod_bounds + first[levels], c->stream));
+                           c->d_lod_bounds + first[levels], gauss, sigma, c->stream));
         first[++levels] = total;                                        // (the next step rewrites the map and the pool behind these, stream-ordered)
     }
-    HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, c->d_lod_parent + first[levels - 1], nullptr, 0, nullptr, c->stream));
+    HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, c->d_lod_parent + first[levels - 1], nullptr, 0, nullptr, gauss, sigma, c->stream));
     HIPCHK(c, c->lod_build_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->lod_build_clock.span(SpanMark::Begin, SpanMark::End, &c->last_lod_build_ms));
@@ -447,6 +451,8 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     c->lod_R = R;
     c->lod_has_sh = with_sh;
     c->lod_sh_degree = sh_degree;
+    c->lod_model = gauss ? M2S_MERGE_MODEL_GAUSSIAN : M2S_MERGE_MODEL_FOOTPRINT;
+    c->lod_sigma = sigma;
     if (out_counts) { out_counts[0] = n0; out_counts[1] = first[levels]; out_counts[2] = levels; out_counts[3] = skipped; }
     return M2S_OK;
 }

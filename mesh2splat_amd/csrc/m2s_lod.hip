@@ -3,6 +3,7 @@
 //
 //   k_lod_link      after every step that merged: parent = first node of the new level + the merge's map, for the level below; the
 //                   16-byte bound (position, longer edge of the flat footprint) of every new node.  The last level gets M2S_LOD_NO_PARENT.
+//                   k_lod_link_gauss: the same with pin 4g's bound, for a tree built under M2S_MERGE_MODEL_GAUSSIAN.
 //   k_lod_select    one launch per level, from the coarsest to the leaves, on one stream: a lane reads its bound (16 B), its parent (4 B)
 //                   and the parent's `open` byte (a gather, but the parents of neighbouring nodes are neighbours: every level above the
 //                   leaves is in the merge's Morton order), evaluates the pinned comparison, writes its own `open` byte (not for leaves:
@@ -37,6 +38,17 @@ __global__ void __launch_bounds__(256) k_lod_link(const uint32_t* __restrict__ m
     if (t < n_rec) {
         const float4 p = rec[(size_t)6 * t], s = rec[(size_t)6 * t + 2];
         bounds[t] = make_float4(p.x, p.y, p.z, fmaxf(fabsf(s.x), fabsf(s.y)));
+    }
+}
+
+// Pin 4g (a tree built under M2S_MERGE_MODEL_GAUSSIAN): the bound is one standard deviation along the longest of the three axes
+__global__ void __launch_bounds__(256) k_lod_link_gauss(const uint32_t* __restrict__ map, uint32_t n_map, uint32_t offset, uint32_t* __restrict__ parent,
+                                                        const float4* __restrict__ rec, uint32_t n_rec, float sigma, float4* __restrict__ bounds) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t < n_map) parent[t] = map ? offset + map[t] : M2S_LOD_NO_PARENT;
+    if (t < n_rec) {
+        const float4 p = rec[(size_t)6 * t], s = rec[(size_t)6 * t + 2];
+        bounds[t] = make_float4(p.x, p.y, p.z, sigma * fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fabsf(s.z)));
     }
 }
 
@@ -110,10 +122,11 @@ __global__ void __launch_bounds__(256) k_lod_ids(const uint32_t* __restrict__ fl
 }  // namespace
 
 hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32_t* parent, const float4* rec, uint32_t n_rec, float4* bounds,
-                    hipStream_t st) {
+                    bool gauss, float sigma, hipStream_t st) {
     const uint32_t n = n_map > n_rec ? n_map : n_rec;
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_lod_link, dim3((n + 255u) / 256u), dim3(256), 0, st, map, n_map, offset, parent, rec, n_rec, bounds);
+    if (gauss) hipLaunchKernelGGL(k_lod_link_gauss, dim3((n + 255u) / 256u), dim3(256), 0, st, map, n_map, offset, parent, rec, n_rec, sigma, bounds);
+    else hipLaunchKernelGGL(k_lod_link, dim3((n + 255u) / 256u), dim3(256), 0, st, map, n_map, offset, parent, rec, n_rec, bounds);
     return hipGetLastError();
 }
 

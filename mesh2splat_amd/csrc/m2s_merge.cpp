@@ -2,6 +2,7 @@
 // (compact_keys_and_sort, m2s_compact.hip) in the compact export's own buffers; the parents go into the pool the way m2s_prune's survivors
 // do (through the staging buffer where the sources live there); what the call does to the context: m2s_recstate.h, Rewrite::Merge —
 // MergeWithSh where m2s_set_carry_sh is on and a baked plane of the records exists: k_merge_reduce_sh then reduces the plane too (pin 5s).
+// The record model (m2s_set_merge_model, m2s_context.cpp) picks the kernels' instances here: nothing else of the pass knows about it.
 // merge_run is the pass behind m2s_merge's argument checks: the steps of m2s_lod_build (m2s_lod.cpp) are calls of it.
 #include "m2s_ctx.h"
 
@@ -33,6 +34,8 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
     M2S_TRY(clock.begin(c->err, true));            // (measured whatever m2s_set_profiling says)
     // pin 5s: a plane of exactly these n records is reduced with them (decided here: the tag does not survive what follows)
     const bool with_sh = c->carry_sh && c->sh_tag.holds(*c, n);
+    // m2s_set_merge_model: pins 2g, 5g, 5sg take the place of 2 / 2u, 5 / 5u, 5s (unsigned_axis then changes nothing)
+    const bool gauss = c->merge_model == M2S_MERGE_MODEL_GAUSSIAN;
     M2S_TRY(c->merge_sh_clock.begin(c->err, with_sh));
     c->last_merge_sh_ms = 0.0f;
     uint64_t segments = 0, merged = 0, invalid = 0;
@@ -58,7 +61,7 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
                                         c->d_compact_temp.cap(), clock.marks(), c->stream));
         HIPCHK(c, clock.mark(MergeMark::Segments, c->stream));
         HIPCHK(c, merge_segments((const float4*)c->last_records, keys, perm, n, level, max_group, min_axis_dot, m, m + mcap, packed, sums, seg_start,
-                                 c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), unsigned_axis, c->stream));
+                                 c->d_merge_totals, c->d_compact_temp, c->d_compact_temp.cap(), unsigned_axis, gauss, c->stream));
         HIPCHK(c, clock.mark(MergeMark::Segmented, c->stream));
         uint32_t h[kMergeTotalsWords] = {}, skipped = 0;
         HIPCHK(c, hipMemcpyAsync(h, c->d_merge_totals, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -80,14 +83,15 @@ m2s_status merge_run(m2s_ctx* c, uint32_t level, uint32_t max_group, float min_a
             if (!in_pool) M2S_TRY(ensure_records(c, segments));
             if (with_sh) M2S_TRY(c->d_sh_alt.reserve(c->err, segments, kMergeShLanes * sizeof(float4)));
             float4* dst = in_pool ? c->d_prune_stage.get() : (float4*)c->lane[0].records.get();
-            HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, unsigned_axis, c->stream));
+            if (gauss) HIPCHK(c, merge_reduce_gauss((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, c->merge_sigma, dst, c->d_merge_map, c->stream));
+            else HIPCHK(c, merge_reduce((const float4*)src, perm, seg_start, c->d_merge_totals, (uint32_t)segments, dst, c->d_merge_map, unsigned_axis, c->stream));
             if (with_sh) {
                 // Pin 5s.  The members' rows come from d_sh through perm and the parents' rows go into the second buffer, which trades
                 // places with d_sh below: no lane lands on a row another still reads, and nothing is copied back.  The weights are the
                 // MEMBERS' alpha and scales: in front of the copy that puts the parents where the members were.
                 HIPCHK(c, c->merge_sh_clock.mark(SpanMark::Begin, c->stream));
                 HIPCHK(c, merge_reduce_sh((const float4*)src, (const float4*)c->d_sh.get(), perm, seg_start, c->d_merge_totals, (uint32_t)segments,
-                                          (float4*)c->d_sh_alt.get(), c->stream));
+                                          (float4*)c->d_sh_alt.get(), gauss, c->stream));
                 HIPCHK(c, c->merge_sh_clock.mark(SpanMark::End, c->stream));
             }
             if (in_pool) HIPCHK(c, hipMemcpyAsync(c->lane[0].records, c->d_prune_stage, segments * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));

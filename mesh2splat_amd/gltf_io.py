@@ -69,6 +69,26 @@ def read_ply(path: str):
     return out, bool(pbr.value)
 
 
+def read_ply_sh(path: str):
+    """m2s_read_ply_sh: read_ply() that keeps f_dc / f_rest -> (records (n,24) float32, has_pbr, sh (n,48) float32 in the baked
+    plane's layout or None for a file without f_dc or without rows, degree 0..3 from the number of f_rest properties)."""
+    L = _lib.load()
+    rec, sh = C.c_void_p(), C.c_void_p()
+    n, deg = C.c_uint64(), C.c_uint32()
+    pbr = C.c_int()
+    st = L.m2s_read_ply_sh(os.fsencode(path), C.byref(rec), C.byref(n), C.byref(pbr), C.byref(sh), C.byref(deg))
+    if st != _lib.M2S_OK:
+        raise _lib.M2SError(st, L.m2s_io_last_error().decode())
+    try:
+        out = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_float)), shape=(n.value, 24)).copy() if n.value else \
+            np.zeros((0, 24), np.float32)
+        plane = np.ctypeslib.as_array(C.cast(sh, C.POINTER(C.c_float)), shape=(n.value, 48)).copy() if sh.value else None
+    finally:
+        L.m2s_free_records(rec)
+        L.m2s_free_sh(sh)
+    return out, bool(pbr.value), plane, int(deg.value)
+
+
 # ---------------------------------------------------------------------------------------------------
 # writer (test / benchmark tooling)
 # ---------------------------------------------------------------------------------------------------

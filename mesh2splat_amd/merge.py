@@ -11,6 +11,7 @@ DRY_RUN = 1                                                  # M2S_MERGE_DRY_RUN
 UNSIGNED_AXIS = 4                                            # M2S_MERGE_UNSIGNED_AXIS (bit 1 names nothing: flags 2 and 3 stay refused)
 VALID_FLAGS = (0, DRY_RUN, UNSIGNED_AXIS, DRY_RUN | UNSIGNED_AXIS)
 MAX_LEVEL = 10
+MODELS = ("footprint", "gaussian")                           # M2S_MERGE_MODEL_FOOTPRINT = 0, M2S_MERGE_MODEL_GAUSSIAN = 1 (m2s_set_merge_model)
 COUNTS = ("before", "after", "merged", "invalid")            # m2s_merge's out_counts, in order
 
 

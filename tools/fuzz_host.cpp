@@ -5,7 +5,7 @@
 //
 // Every iteration takes one seed file, applies a few mutations (bit flips, byte splats, truncation, 16/32-bit length
 // fields set to extreme values, chunk duplication, a block copied from another seed) and hands the result to the reader for
-// its kind: *.png / *.jpg straight to decode_png / decode_jpeg, *.glb to m2s_load_glb, *.ply to m2s_read_ply (formats 0 / 1 and the compact
+// its kind: *.png / *.jpg straight to decode_png / decode_jpeg, *.glb to m2s_load_glb, *.ply to m2s_read_ply and m2s_read_ply_sh (formats 0 / 1 and the compact
 // layout; a .ply also gets the counts of its header replaced by extreme decimal numbers).  The readers
 // may accept or reject the file; the run fails only when a sanitizer reports, a reader crashes, or an accepted image has
 // an inconsistent size.  A line of statistics is printed at the end.
@@ -223,6 +223,19 @@ int main(int argc, char** argv) {
                     if (n) sink = sink + rec[n - 1].pbr[3];
                     m2s_free_records(rec);
                 }
+                // ... and the same bytes through the reader that keeps f_dc / f_rest: it accepts what m2s_read_ply accepts unless the
+                // f_rest properties are not a whole degree's, and every row of its plane is there
+                float* sh = nullptr;
+                uint32_t degree = 0;
+                rec = nullptr;
+                if (m2s_read_ply_sh(tmp.c_str(), &rec, &n, &pbr, &sh, &degree) == M2S_OK) {
+                    volatile float sink = 0;
+                    if (n) sink = sink + rec[n - 1].pbr[3];
+                    if (sh && n) sink = sink + sh[n * 48 - 1];
+                    if (degree > 3) { std::fprintf(stderr, "m2s_read_ply_sh: degree %u\n", degree); return 1; }
+                    m2s_free_records(rec);
+                    m2s_free_sh(sh);
+                } else if (rec || sh) { std::fprintf(stderr, "m2s_read_ply_sh failed and left an allocation\n"); return 1; }
             }
         }
     }

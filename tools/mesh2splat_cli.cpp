@@ -97,6 +97,9 @@ struct Options {
     double lod_blend = -1.0;                                       // --lod-blend b (0 < b <= 1): every cut is blended towards its nodes' parents over this band (m2s_lod_blend)
     std::string lod_ply;                                           // --lod-ply cut.ply: the --preview camera's cut as a .ply (with --bake-light: its carried SH plane, m2s_set_carry_sh)
     bool lod() const { return !lod_levels.empty(); }
+    bool conversion_flag = false;                                  // one of --density / --quality / --max-res / --std / --cap / --pipeline was given: refused with a .ply input, which is not converted
+    int merge_model = -1;                                          // --merge-model footprint|gaussian (m2s_set_merge_model) for --merge-level / --merge-to / --lod-levels; -1: not given
+    double merge_sigma = -1.0;                                     // --merge-sigma s (> 0), with --merge-model: what a stored scale is multiplied with to be a standard deviation; < 0: 1
     bool merge_unsigned_axis = false;                              // --merge-unsigned-axis: M2S_MERGE_UNSIGNED_AXIS for --merge-level / --merge-to / --lod-levels
     bool world_units = false;                                      // --world-units: the scales divided by the density right after the conversion (m2s_records_to_world_units)
     long long budget = 0;                                          // --budget N: keep the N most important Gaussians (m2s_prune_budget); 0: off
@@ -108,7 +111,7 @@ struct Options {
 
 void usage() {
     std::fprintf(stderr,
-                 "usage: mesh2splat in.glb out.ply [options]\n"
+                 "usage: mesh2splat in.glb|in.ply out.ply [options]\n"
                  "       mesh2splat --batch in_dir --out out_dir [options]\n"
                  "options: [--density R | --quality q [--max-res M]] [--std s] [--format 0|1|2] [--device d] [--gpus N [--gather]]\n"
                  "         [--cap n (0 = unlimited, default: reference formula)] [--pipeline auto|multipass] [--timing]\n"
@@ -209,6 +212,16 @@ void usage() {
                  "  --gpus N > 1.\n"
                  "--view-distance f (0.25..64, default 1: what it was): the --preview and --score eyes stand at f x the camera rule's distance\n"
                  "  and the far plane is f x as far; near stays.\n"
+                 "--merge-model footprint|gaussian [--merge-sigma s (> 0, default 1)], with --merge-level, --merge-to or --lod-levels: how those\n"
+                 "  passes read a record (m2s_set_merge_model).  footprint, the default: the flat texel rectangle the conversion emits.  gaussian:\n"
+                 "  a 3D Gaussian with standard deviations s * scale[0..2], what a .ply of another origin holds (s = 1) or a conversion behind\n"
+                 "  --world-units (s = --std).  The `merge:` and `lod:` lines gain \"model\" and \"sigma\".  Not with --lod-blend under gaussian.\n"
+                 "in.ply in place of in.glb: the file's Gaussians are read (m2s_read_ply_sh) and uploaded, nothing is converted.  --budget N (by\n"
+                 "  area), --merge-level / --merge-to [--merge-model ...], --format, --compact and the export follow as after a conversion; a file\n"
+                 "  with f_rest coefficients keeps them through all of these (--format 0 or --compact).  Prints ONE line `ply_in: {...}`: rows,\n"
+                 "  has_pbr, sh_degree.  Everything that needs the mesh, a camera or a conversion is a usage error: --preview, --score, --refit,\n"
+                 "  --prune, --bake-light, --split-screen, --mesh-depth-test, every --lod-*, --world-units, --density, --quality, --max-res, --std,\n"
+                 "  --cap, --pipeline, --gpus N > 1, --batch.\n"
                  "--world-units: right after the conversion, in front of --prune, --budget, --merge-*, --refit, --bake-light, --score, --preview,\n"
                  "  --compact, the export and --lod-*, the records' scales are divided by the density and their resolutionTarget becomes 1\n"
                  "  (m2s_records_to_world_units); every later stage takes the divisor from the context.  --merge-* and --lod-* read scales as\n"
@@ -338,6 +351,19 @@ void preview_light(const m2s_mesh* meshes, uint32_t n_meshes, double pos[3], dou
     *intensity = 4.0 * radius * radius;
 }
 
+// --merge-model / --merge-sigma: the context's record model for the merges and the tree (nothing is set without the flag), and the
+// two keys the `merge:` and `lod:` lines gain with it
+m2s_status apply_merge_model(m2s_ctx* ctx, const Options& o) {
+    return o.merge_model < 0 ? M2S_OK : m2s_set_merge_model(ctx, (uint32_t)o.merge_model, o.merge_sigma > 0.0 ? (float)o.merge_sigma : 1.0f);
+}
+std::string merge_model_json(const Options& o) {
+    if (o.merge_model < 0) return "";
+    char b[96];
+    std::snprintf(b, sizeof b, ", \"model\": \"%s\", \"sigma\": %.9g", o.merge_model == M2S_MERGE_MODEL_GAUSSIAN ? "gaussian" : "footprint",
+                  (double)(o.merge_sigma > 0.0 ? (float)o.merge_sigma : 1.0f));
+    return b;
+}
+
 // --lod-levels / --lod-pixels / --lod-budget: the tree over the context's records (Converter.lod_build), then one cut per camera (Converter.lod_select / .lod_select_budget)
 // in front of its frame; the views collect in `views` for the one `lod:` line
 struct LodReport { uint64_t build[4] = {}; std::vector<uint64_t> first; float build_ms = 0; std::string views; std::string cut_ply; };   // cut_ply: the keys of --lod-ply
@@ -464,9 +490,9 @@ void lod_print(const Options& o, const LodReport& rep) {
         std::snprintf(b, sizeof b, "%.9g", (double)(float)o.lod_blend);
         budget += std::string(", \"blend\": ") + b;
     }
-    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s}\n",
+    std::printf("lod: {\"levels\": [%s], \"nodes\": %llu, \"per_level_nodes\": [%s], \"skipped\": %llu, \"tau_px\": %s, \"build_ms\": %.4f, \"views\": [%s]%s%s%s}\n",
                 levels.c_str(), (unsigned long long)rep.build[1], per.c_str(), (unsigned long long)rep.build[3], tau, rep.build_ms, rep.views.c_str(),
-                (budget + rep.cut_ply).c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
+                (budget + rep.cut_ply).c_str(), o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "", merge_model_json(o).c_str());
 }
 
 // --lod-ply: the records the preview camera's cut left, as a .ply — with --bake-light the plane the tree carried (m2s_set_carry_sh) through
@@ -762,10 +788,10 @@ int run_merge(m2s_ctx* ctx, const Options& o) {
     char target[32] = "null";
     if (o.merge_to > 0) std::snprintf(target, sizeof(target), "%lld", o.merge_to);
     std::printf("merge: {\"level\": %u, \"max_group\": %u, \"min_axis_dot\": %s, \"target\": %s, \"met\": %s, \"before\": %llu, \"after\": %llu, "
-                "\"merged\": %llu, \"invalid\": %llu, \"stage_ms\": [%.4f, %.4f, %.4f]%s}\n",
+                "\"merged\": %llu, \"invalid\": %llu, \"stage_ms\": [%.4f, %.4f, %.4f]%s%s}\n",
                 mp.level, mp.max_group, json_num((double)mp.min_axis_dot).c_str(), target, met ? "true" : "false", (unsigned long long)c[0],
                 (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], ms[0], ms[1], ms[2],
-                o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "");
+                o.merge_unsigned_axis ? ", \"unsigned_axis\": true" : "", merge_model_json(o).c_str());
     return 0;
 }
 
@@ -918,6 +944,7 @@ int convert_one(const Options& o) {
     auto die = [&](const char* what) { std::fprintf(stderr, "%s: %s\n", what, m2s_last_error(ctx)); m2s_destroy(ctx); m2s_free_host_scene(scene); return 1; };
     if (m2s_set_pipeline(ctx, o.pipeline) != M2S_OK) return die("set_pipeline");
     if (m2s_set_max_gaussians(ctx, o.conversion_cap()) != M2S_OK) return die("set_max_gaussians");
+    if (apply_merge_model(ctx, o) != M2S_OK) return die("merge model");
     (void)m2s_set_resolution_hint(ctx, o.R());   // the upload prepares for the conversion below
     if (m2s_upload_scene(ctx, m2s_host_scene_meshes(scene), m2s_host_scene_num_meshes(scene)) != M2S_OK) return die("upload");
     const auto t2 = Clock::now();
@@ -964,6 +991,53 @@ int convert_one(const Options& o) {
     }
     m2s_destroy(ctx);
     m2s_free_host_scene(scene);
+    return 0;
+}
+
+// ---- a .ply in place of a .glb: no conversion ----------------------------------------------------------------------------
+// The file's Gaussians (m2s_read_ply_sh) become the context's records; --budget (AREA), --merge-* and the export follow as after a
+// conversion.  A plane of degree >= 1 is uploaded with them and carried (m2s_set_carry_sh) into a standard-layout or compact file.
+// Uploaded records carry no resolutionTarget, which m2s_export_ply and m2s_export_ply_sh divide by: the records come back to the
+// host and the host writers take them with scale multiplier 1 (a .ply holds the drawn deviations); the compact export takes 0 as 1.
+int convert_ply(const Options& o) {
+    m2s_gaussian* rec = nullptr;
+    float* sh = nullptr;
+    uint64_t n = 0;
+    int has_pbr = 0;
+    uint32_t degree = 0;
+    if (m2s_read_ply_sh(o.in.c_str(), &rec, &n, &has_pbr, &sh, &degree) != M2S_OK) { std::fprintf(stderr, "%s: %s\n", o.in.c_str(), m2s_io_last_error()); return 1; }
+    m2s_ctx* ctx = nullptr;
+    if (m2s_create((int)o.device, &ctx) != M2S_OK) { std::fprintf(stderr, "%s\n", m2s_last_error(nullptr)); m2s_free_records(rec); m2s_free_sh(sh); return 1; }
+    auto die = [&](const char* what) { std::fprintf(stderr, "%s: %s\n", what, m2s_last_error(ctx)); m2s_destroy(ctx); m2s_free_records(rec); m2s_free_sh(sh); return 1; };
+    const bool carried = sh && degree >= 1;
+    if (apply_merge_model(ctx, o) != M2S_OK) return die("merge model");
+    if (m2s_upload_records(ctx, rec, n) != M2S_OK) return die("upload");
+    if (carried && (m2s_set_carry_sh(ctx, 1) != M2S_OK || m2s_upload_sh(ctx, sh, n, degree) != M2S_OK)) return die("upload sh");
+    std::printf("ply_in: {\"rows\": %llu, \"has_pbr\": %s, \"sh_degree\": %u}\n", (unsigned long long)n, has_pbr ? "true" : "false", degree);
+    m2s_free_records(rec); rec = nullptr;
+    m2s_free_sh(sh); sh = nullptr;
+    if (o.budget > 0 && run_budget(ctx, M2S_IMPORTANCE_AREA, 0.0f, 0, o) != 0) return die("budget");
+    if (o.merging() && run_merge(ctx, o) != 0) return die("merge");
+    const uint64_t stored = m2s_num_stored(ctx);
+    if (o.compact) {
+        Options one = o;
+        one.std_dev = 1.0;
+        if (export_compact(ctx, o.out, one, carried) != 0) return die("export");
+    } else {
+        std::vector<m2s_gaussian> out((size_t)std::max<uint64_t>(stored, 1));
+        std::vector<float> plane;
+        if (m2s_download(ctx, out.data(), stored) != M2S_OK) return die("download");
+        if (carried && o.format == 0) {
+            plane.resize((size_t)std::max<uint64_t>(stored, 1) * 48);
+            if (m2s_download_sh(ctx, plane.data(), stored) != M2S_OK) return die("download sh");
+        }
+        const m2s_status ws = plane.empty() ? m2s_write_ply(o.out.c_str(), out.data(), stored, (uint32_t)o.format, 1.0f)
+                                            : m2s_write_ply_sh(o.out.c_str(), out.data(), plane.data(), stored, 1.0f);
+        if (ws != M2S_OK) { std::fprintf(stderr, "cannot write %s\n", o.out.c_str()); m2s_destroy(ctx); return 1; }
+    }
+    std::printf("%s: %llu Gaussians (%llu stored) -> %s (%s)\n", o.in.c_str(), (unsigned long long)n, (unsigned long long)stored, o.out.c_str(),
+                o.compact ? "compact" : ("format " + std::to_string(o.format)).c_str());
+    m2s_destroy(ctx);
     return 0;
 }
 
@@ -1163,7 +1237,7 @@ int batch_on_device(const Options& o, const std::vector<std::pair<std::string, s
     m2s_ctx* ctx[2] = { nullptr, nullptr };
     for (auto& c : ctx)
         if (m2s_create(device, &c) != M2S_OK) { std::fprintf(stderr, "%s\n", m2s_last_error(nullptr)); return 1; }
-    for (auto c : ctx) { (void)m2s_set_pipeline(c, o.pipeline); (void)m2s_set_max_gaussians(c, o.conversion_cap()); }
+    for (auto c : ctx) { (void)m2s_set_pipeline(c, o.pipeline); (void)m2s_set_max_gaussians(c, o.conversion_cap()); (void)apply_merge_model(c, o); }
     Channel<Loaded> loaded(2);
     Channel<Converted> converted(1);
     std::mutex slot_m; std::condition_variable slot_cv; bool slot_busy[2] = { false, false };   // a context's records are being exported
@@ -1295,6 +1369,7 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        if (a == "--density" || a == "--quality" || a == "--max-res" || a == "--std" || a == "--cap" || a == "--pipeline") o.conversion_flag = true;
         if (a == "--density") o.density = std::atol(next());
         else if (a == "--quality") o.quality = std::atof(next());
         else if (a == "--max-res") o.max_res = std::atol(next());
@@ -1380,6 +1455,12 @@ int main(int argc, char** argv) {
         else if (a == "--compact") o.compact = true;
         else if (a == "--world-units") o.world_units = true;
         else if (a == "--merge-unsigned-axis") o.merge_unsigned_axis = true;
+        else if (a == "--merge-model") {
+            const std::string v = next();
+            o.merge_model = v == "footprint" ? (int)M2S_MERGE_MODEL_FOOTPRINT : v == "gaussian" ? (int)M2S_MERGE_MODEL_GAUSSIAN : -1;
+            if (o.merge_model < 0) { usage(); return 2; }
+        }
+        else if (a == "--merge-sigma") { o.merge_sigma = std::atof(next()); if (!(o.merge_sigma > 0.0) || !std::isfinite(o.merge_sigma) || !((float)o.merge_sigma > 0.0f) || !std::isfinite((float)o.merge_sigma)) { usage(); return 2; } }
         else if (a == "--bake-degree") { o.bake_degree = std::atoi(next()); if (o.bake_degree < 0 || o.bake_degree > 3) { usage(); return 2; } }
         else if (a == "--light") {
             const int got = std::sscanf(next(), "%lf,%lf,%lf,%lf", &o.light[0], &o.light[1], &o.light[2], &o.light[3]);
@@ -1399,6 +1480,8 @@ int main(int argc, char** argv) {
     if (o.budget > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (multi-rank budgets: out of scope)
     if (o.merging() && (o.gpus > 1 || o.force_sharded || (o.merge_level >= 0 && o.merge_to > 0))) { usage(); return 2; }   // (multi-rank merges: out of scope)
     if (o.merge_unsigned_axis && !o.merging() && !o.lod()) { usage(); return 2; }   // (a mode of those passes, refused with --gpus N > 1 as they are)
+    if ((o.merge_model >= 0 && !o.merging() && !o.lod()) || (o.merge_sigma > 0.0 && o.merge_model < 0)) { usage(); return 2; }   // (--merge-model: a mode of those passes; --merge-sigma: of --merge-model)
+    if (o.merge_model == M2S_MERGE_MODEL_GAUSSIAN && o.lod_blend > 0.0) { usage(); return 2; }   // (m2s_lod_blend refuses a tree built under the Gaussian model)
     if (o.refit_views > 0 && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the refit reads one context's records and scene)
     if (o.world_units && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (a rank's slice writer and the gather hand on the density)
     if (o.compact && (o.gpus > 1 || o.force_sharded)) { usage(); return 2; }   // (the Morton order is global: no slice writers)
@@ -1421,5 +1504,12 @@ int main(int argc, char** argv) {
     }
     if (pos.size() != 2) { usage(); return 2; }
     o.in = pos[0]; o.out = pos[1];
+    if (o.in.size() > 4 && o.in.compare(o.in.size() - 4, 4, ".ply") == 0) {
+        // a .ply has no mesh and no camera rule: everything that needs one, or a conversion, is a usage error
+        if (!o.preview.empty() || o.score_views > 0 || o.refit_views > 0 || o.prune_views > 0 || o.bake_light || o.split_screen >= 0.0 || o.mesh_depth_test ||
+            o.lod() || o.lod_pixels >= 0.0 || o.lod_budget > 0 || o.lod_frustum || o.lod_occlusion || o.lod_blend > 0.0 || !o.lod_ply.empty() || o.world_units ||
+            o.conversion_flag || o.gpus > 1 || o.force_sharded) { usage(); return 2; }
+        return convert_ply(o);
+    }
     return (o.gpus > 1 || o.force_sharded) ? convert_sharded(o) : convert_one(o);
 }
