@@ -18,11 +18,13 @@
 //   m2s_compact.cpp  the compact .ply export (m2s_export_ply_compact); its host writer and decoder: m2s_compact_host.cpp
 //   m2s_devbuf.h     the owners of everything the context keeps: DevBuf, PinnedBuf, EventSet, StreamSet; BinWork (viewer passes), Lane (conversions)
 //   m2s_stageclock.h stage timing: StageClock, one per pass below and the marks of each (the enums of that header), StageMarks for the launchers
+//   m2s_lodtree.h    the level-of-detail tree and what its passes work in: LodTree (planes, levels, generation; the only code that grows, ends or commits one), LodWork
 //   m2s_recstate.h   the current records, what hangs on them and the transitions between them: RecordState (a base of m2s_ctx), RecordsTag
 #pragma once
 #include "../../include/m2s.h"
 #include "m2s_devbuf.h"
 #include "m2s_device.h"
+#include "m2s_lodtree.h"
 #include "m2s_recstate.h"
 #include "m2s_vdedup.h"
 
@@ -239,51 +241,23 @@ struct m2s_ctx : m2s_host::RecordState {   // (the current records and their dep
     float merge_sigma = 1.0f;
     float last_merge_sh_ms = 0.0f;                       // the SH reduction of the last merge (0: none ran); inside stage [2]
     m2s_host::ClockOf<m2s_host::SpanMark> merge_sh_clock;    // always on
-    // level-of-detail tree (m2s_lod.cpp): the node pool (leaves, then every level a merging step added), a parent word and a 16-byte
-    // bound (x, y, z, longer edge) per node, one capacity of nodes each, grown together with their contents kept; lod_levels == 0: no tree
-    m2s_host::DevBuf<float4> d_lod_nodes;                // capacity in records
-    m2s_host::DevBuf<uint32_t> d_lod_parent;
-    m2s_host::DevBuf<float4> d_lod_bounds;
-    m2s_host::DevBuf<float> d_lod_sh;                    // the fourth plane, 48 floats per node: only while lod_has_sh
-    bool lod_has_sh = false;                             // the tree was built with m2s_set_carry_sh on over records with a plane
-    uint32_t lod_sh_degree = 0;                          // ... of this degree
-    uint32_t lod_model = M2S_MERGE_MODEL_FOOTPRINT;      // the merge model the tree was built under, and its sigma (m2s_lod_blend refuses
-    float lod_sigma = 1.0f;                              // a Gaussian tree)
-    uint32_t lod_levels = 0;
-    uint64_t lod_first[M2S_LOD_MAX_STEPS + 2] = {};      // first node of every level; [lod_levels] = the nodes
-    uint32_t lod_R = 0;                                  // resolutionTarget of the leaves
+    // level-of-detail tree (m2s_lod.cpp; m2s_lodtree.h): the tree — its node planes, levels and generation — and what its passes work in;
+    // below them what the passes report, per pass: the build, the cut (m2s_lod_select), the cut that fits a budget (m2s_lod_select_budget),
+    // the cuts over a frustum (_frustum) and behind an occluder (_occluded), the blend (m2s_lod_blend)
+    m2s_host::LodTree lod;
+    m2s_host::LodWork lod_work;
     float last_lod_build_ms = 0.0f;
     m2s_host::ClockOf<m2s_host::SpanMark> lod_build_clock;   // always on
-    // the cut (m2s_lod_select): a byte per node (every ancestor-or-self refines), the selected counts per level and the refining nodes
-    // behind them, the node index of every output record, valid while lod_ids_tag holds; flags, offsets and the scan area are m2s_prune's
-    m2s_host::DevBuf<uint8_t> d_lod_open;
-    m2s_host::DevBuf<uint32_t> d_lod_counts;             // kLodCountWords
-    m2s_host::DevBuf<uint32_t> d_lod_ids;
     uint64_t last_lod_select_counts[4] = { 0, 0, 0, 0 };
     uint64_t last_lod_level_counts[M2S_LOD_MAX_STEPS + 1] = {};
     float last_lod_select_stage_ms[3] = { 0, 0, 0 };     // level sweep, scan + node indices, compaction (profiling on)
     m2s_host::ClockOf<m2s_host::LodCutMark> lod_cut_clock;
-    // the cut that fits a budget (m2s_lod_select_budget): the keys (L, H) per node and the words of the search
-    m2s_host::DevBuf<uint2> d_lod_lh;
-    m2s_host::DevBuf<uint32_t> d_lod_budget_state;       // kLodBudgetStateWords
     float last_lod_budget_stage_ms[3] = { 0, 0, 0 };     // thresholds, the four select rounds, the cut (profiling on)
     m2s_host::ClockOf<m2s_host::LodBudgetMark> lod_budget_clock;
-    // the cuts over a frustum (m2s_lod_select_frustum, m2s_lod_select_budget_frustum): a visibility byte per node, the leaves inside
-    // and the nodes the plain cut selects and the frustum dropped (two more words of d_lod_counts), the visibility stage
-    m2s_host::DevBuf<uint8_t> d_lod_vis;
-    uint64_t last_lod_frustum_counts[2] = { 0, 0 };
+    uint64_t last_lod_frustum_counts[2] = { 0, 0 };      // the leaves inside, the nodes the plain cut selects and the frustum dropped
     float last_lod_frustum_ms = 0.0f;
-    m2s_host::ClockOf<m2s_host::SpanMark> lod_vis_clock;
-    // the same two cuts behind an occluder (m2s_lod_select_occluded, m2s_lod_select_budget_occluded): a host depth image's copy on the
-    // device (no other pass reads it), and the leaves inside the frustum, occluded, behind the image but kept, and the nodes dropped
-    m2s_host::DevBuf<float> d_lod_occ_depth;             // capacity in texels
-    uint64_t last_lod_occlusion_counts[4] = { 0, 0, 0, 0 };
-    // the blend (m2s_lod_blend): the weight of every record of the last cut, valid while lod_blend_tag holds, and its three count words.
-    // lod_tree_gen counts the trees this context has had (a build or a release ends one); lod_ids_gen is the tree d_lod_ids indexes.
-    m2s_host::DevBuf<float> d_lod_blend_t;
-    m2s_host::DevBuf<uint32_t> d_lod_blend_counts;       // kLodBlendCountWords
-    m2s_host::RecordsTag lod_blend_tag;
-    uint64_t lod_tree_gen = 0, lod_ids_gen = 0;
+    m2s_host::ClockOf<m2s_host::SpanMark> lod_vis_clock;     // the visibility stage
+    uint64_t last_lod_occlusion_counts[4] = { 0, 0, 0, 0 };  // the leaves inside the frustum, occluded, behind the image but kept, and the nodes dropped
     uint64_t last_lod_blend_counts[4] = { 0, 0, 0, 0 };
     float last_lod_blend_ms = 0.0f;
     float last_lod_blend_stage_ms[3] = { 0, 0, 0 };      // weights, records, SH rows (profiling on)

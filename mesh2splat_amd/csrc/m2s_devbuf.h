@@ -36,7 +36,7 @@ public:
         p_ = nullptr;
         cap_ = 0;
     }
-    // Trade places with another buffer: how a caller grows one whose contents it has copied over (m2s_lod.cpp).
+    // Trade places with another buffer: how a caller grows one whose contents it has copied over (LodTree::reserve, m2s_lodtree.h).
     void swap(DevBuf& o) {
         T* const p = p_; p_ = o.p_; o.p_ = p;
         const uint64_t c = cap_; cap_ = o.cap_; o.cap_ = c;

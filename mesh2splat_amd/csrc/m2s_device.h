@@ -349,6 +349,9 @@ hipError_t merge_reduce_sh(const float4* rec, const float4* sh, const uint32_t* 
 hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32_t* parent, const float4* rec, uint32_t n_rec, float4* bounds,
                     bool gauss, float sigma, hipStream_t st);
 struct LodSelectK { float cx, cy, cz, focal, tau2, near2; };
+// What a launcher that goes through the tree level by level reads of it (LodTree::levels_k, m2s_lodtree.h): the bound and the parent
+// word of every node, the first node of every level ([levels]: the nodes; host memory), the levels.
+struct LodLevelsK { const float4* bounds; const uint32_t* parent; const uint64_t* first; uint32_t levels; };
 constexpr uint32_t kLodRefineWord = 17;    // counts: [l] selected nodes of level l (0..16), [17] nodes that refine,
 constexpr uint32_t kLodPlainWord = 18;     // [18] nodes the cut selects before the visibility plane masks it (written with a plane only),
 constexpr uint32_t kLodInsideWord = 19;    // [19] leaves inside the frustum (written by lod_visibility),
@@ -358,8 +361,7 @@ constexpr uint32_t kLodCountWords = 22;
 // The sweep, one launch per level from the last to the leaves: per node of [first[l], first[l + 1]) the pinned comparison,
 // open[i] = refine && open[parent[i]] (levels above the leaves), flags[i] = selected; counts (zeroed by the caller) as above.
 // vis (NULL: none): the visibility plane of lod_visibility; flags[i] = selected && vis[i] then, and the per-level counts are the masked ones.
-hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
-                     uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st);
+hipError_t lod_sweep(const LodLevelsK& t, const LodSelectK& k, uint8_t* open, uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st);
 // ids[offsets[i]] = i where flags[i] is set
 hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t* ids, hipStream_t st);
 // offsets = exclusive scan of flags (n words each); temp: prune_scan_temp_bytes(n)
@@ -374,8 +376,7 @@ constexpr uint32_t kLodBudgetStateWords = kLodBudgetHist + 4 * kLodBudgetShards 
 // One launch per level from the last to the leaves: lh[i] = (L, H), the keys (bits of tau_px) from which node i is no longer refined
 // (0 for a leaf) and from which one of its proper ancestors is not (0xFFFFFFFF on the last level); k.tau2 is not read.
 // vis (NULL: none): the visibility plane of lod_visibility; a node whose byte is 0 gets L = H (selected at no key), H as without.
-hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
-                          const uint8_t* vis, hipStream_t st);
+hipError_t lod_thresholds(const LodLevelsK& t, const LodSelectK& k, uint2* lh, const uint8_t* vis, hipStream_t st);
 // The four histogram / pick rounds over the n nodes: afterwards state[kLodBudgetPrefix] is the smallest key whose cut holds at most
 // `budget` nodes (budget >= the nodes of the last level, n > 0), state[kLodBudgetFiner] the count at the key before it where
 // that key is not 0.  state: kLodBudgetStateWords, zeroed here.
@@ -395,8 +396,7 @@ struct LodOccluderK { const float* depth; const float* nodes; uint32_t depth_w, 
 // occ (NULL: none): a leaf that passes the frustum test, lies behind the image by more than the bias and has alpha > .95 is not
 // visible; inside_word[0] counts the leaves that pass the frustum test all the same, inside_word[1] the ones hidden, inside_word[2]
 // the ones behind the image that stay (kLodInsideWord, kLodOccludedWord, kLodKeptWord).
-hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f,
-                          const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st);
+hipError_t lod_visibility(const LodLevelsK& t, const LodFrustumK& f, const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st);
 
 // ---- the blend of a cut's records towards their parents (m2s_lodblend.hip; the pin: include/m2s.h, m2s_lod_blend) -----------------------
 struct LodBlendK { float cx, cy, cz, focal, tau2, near2, band; };

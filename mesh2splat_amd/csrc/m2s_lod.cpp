@@ -2,7 +2,8 @@
 // _frustum and _occluded forms, m2s_lod_blend): host side of m2s_lod.hip, m2s_lodbudget.hip, m2s_lodfrustum.hip and m2s_lodblend.hip.  The tree is a chain of the merge pass's steps (merge_run, m2s_merge.cpp) whose results are
 // copied into a node pool and linked by their maps; the
 // cut's flags and offsets live where m2s_prune leaves its own, and the compaction is m2s_prune's (m2s_contrib.cpp: prune_compact_enqueue);
-// what a cut does to the context: m2s_recstate.h, Rewrite::LodCut.
+// what a cut does to the context: m2s_recstate.h, Rewrite::LodCut.  The tree itself (c->lod) and what the passes work in (c->lod_work):
+// m2s_lodtree.h.
 #include "m2s_ctx.h"
 
 #include <algorithm>
@@ -16,42 +17,26 @@ namespace {
 
 constexpr uint64_t kLodMaxNodes = 0xFFFFFFFFull;   // fewer than this: M2S_LOD_NO_PARENT is no node
 
+const char* const kNoTreeMsg = "no level-of-detail tree (m2s_lod_build)";
+
 bool lod_ids_valid(const m2s_ctx* c) { return c->lod_ids_tag.holds(*c); }
 
-// Room for `want` nodes in the fourth plane (pin 4s: 48 floats per node), the first `keep` rows kept where they have to move.
-m2s_status lod_reserve_sh(m2s_ctx* c, uint64_t want, uint64_t keep) {
-    if (c->d_lod_sh.cap() >= want && c->d_lod_sh) return M2S_OK;
-    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, c->d_lod_nodes.cap()), 1);   // (grown with the other three)
-    DevBuf<float> plane;
-    M2S_TRY(plane.reserve(c->err, cap, 48 * sizeof(float)));
-    if (keep) {
-        HIPCHK(c, hipMemcpyAsync(plane, c->d_lod_sh, keep * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    c->d_lod_sh.swap(plane);
+// The state every cut and the blend need behind their argument checks: nothing in flight, a tree.
+m2s_status lod_ready(m2s_ctx* c) {
+    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
+    if (!c->lod.levels) return fail(c, M2S_ERR_STATE, kNoTreeMsg);
     return M2S_OK;
 }
 
-// Room for `want` nodes in the three planes of the tree — and in the fourth, for a tree that has one (sh) —, the first `keep` nodes kept
-// where they have to move.
-m2s_status lod_reserve(m2s_ctx* c, uint64_t want, uint64_t keep, bool sh) {
-    if (c->d_lod_nodes.cap() >= want && c->d_lod_nodes) return sh ? lod_reserve_sh(c, want, keep) : M2S_OK;
-    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, 2 * c->d_lod_nodes.cap()), 1);
-    DevBuf<float4> nodes, bounds;
-    DevBuf<uint32_t> parent;
-    M2S_TRY(nodes.reserve(c->err, cap, sizeof(m2s_gaussian)));
-    M2S_TRY(parent.reserve(c->err, cap, sizeof(uint32_t)));
-    M2S_TRY(bounds.reserve(c->err, cap, sizeof(float4)));
-    if (keep) {
-        HIPCHK(c, hipMemcpyAsync(nodes, c->d_lod_nodes, keep * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(parent, c->d_lod_parent, keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(bounds, c->d_lod_bounds, keep * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    c->d_lod_nodes.swap(nodes);
-    c->d_lod_parent.swap(parent);
-    c->d_lod_bounds.swap(bounds);
-    return sh ? lod_reserve_sh(c, want, keep) : M2S_OK;
+// The camera of a cut, a budget search or a blend, in the order their parameter checks report it; tau_px (NULL: the caller has none, or
+// checks its own later) between the focal length and the near distance.
+m2s_status lod_camera_check(m2s_ctx* c, const float position[3], float focal_px, float near, const float* tau_px = nullptr) {
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
+    if (!std::isfinite(focal_px) || !(focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
+    if (tau_px && (!std::isfinite(*tau_px) || !(*tau_px >= 0.0f))) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
+    if (!std::isfinite(near) || !(near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    return M2S_OK;
 }
 
 LodFrustumK lod_frustum_k(const m2s_lod_frustum* fr) {
@@ -95,11 +80,11 @@ m2s_status lod_occluder_state(m2s_ctx* c, const m2s_lod_occluder* oc) {
 // oc (NULL: none): the leaves are tested against this depth image too; a host image is copied in front of the stage, into a buffer
 // that no other pass reads.
 m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr, const m2s_lod_occluder* oc) {
-    M2S_TRY(c->d_lod_vis.reserve(c->err, c->lod_first[c->lod_levels], 1));
-    M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+    M2S_TRY(c->lod_work.vis.reserve(c->err, c->lod.nodes(), 1));
+    M2S_TRY(c->lod_work.counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
     LodOccluderK ok = {};
     if (oc) {
-        ok.nodes = reinterpret_cast<const float*>(c->d_lod_nodes.get());
+        ok.nodes = c->lod.rows<const float>(kLodRecords);
         ok.bias = oc->depth_bias;
         if (!oc->depth) {
             ok.depth = c->d_md_image; ok.depth_w = (uint32_t)c->md_w; ok.depth_h = (uint32_t)c->md_h;
@@ -108,17 +93,16 @@ m2s_status lod_vis_enqueue(m2s_ctx* c, const m2s_lod_frustum* fr, const m2s_lod_
             if (oc->depth_on_device) ok.depth = oc->depth;
             else {
                 const uint64_t texels = (uint64_t)oc->depth_w * oc->depth_h;
-                M2S_TRY(c->d_lod_occ_depth.reserve(c->err, texels, sizeof(float)));
-                HIPCHK(c, hipMemcpyAsync(c->d_lod_occ_depth, oc->depth, texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
-                ok.depth = c->d_lod_occ_depth;
+                M2S_TRY(c->lod_work.occ_depth.reserve(c->err, texels, sizeof(float)));
+                HIPCHK(c, hipMemcpyAsync(c->lod_work.occ_depth, oc->depth, texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
+                ok.depth = c->lod_work.occ_depth;
             }
         }
         if (!ok.depth || !ok.depth_w || !ok.depth_h) return fail(c, M2S_ERR_STATE, "the occluder has no depth image (internal error)");
     }
-    HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->lod_work.counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
     HIPCHK(c, c->lod_vis_clock.mark(SpanMark::Begin, c->stream));
-    HIPCHK(c, lod_visibility(c->d_lod_bounds, c->d_lod_parent, c->lod_first, c->lod_levels, lod_frustum_k(fr), oc ? &ok : nullptr, c->d_lod_vis,
-                             c->d_lod_counts + kLodInsideWord, c->stream));
+    HIPCHK(c, lod_visibility(c->lod.levels_k<LodLevelsK>(), lod_frustum_k(fr), oc ? &ok : nullptr, c->lod_work.vis, c->lod_work.counts + kLodInsideWord, c->stream));
     HIPCHK(c, c->lod_vis_clock.mark(SpanMark::End, c->stream));
     return M2S_OK;
 }
@@ -131,22 +115,22 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
                    const m2s_lod_occluder* oc = nullptr) {
     if ((fr != nullptr) != (vis != LodVis::None) || (oc && !fr)) return fail(c, M2S_ERR_INVALID, "lod_cut: frustum and visibility mode disagree (internal error)");
     const bool dry = (p->flags & M2S_LOD_DRY_RUN) != 0;
-    const bool with_sh = c->lod_has_sh && !dry;     // (pin 3s: the tree's property decides, not the switch at the time of the cut)
+    const bool with_sh = c->lod.has_sh && !dry;     // (pin 3s: the tree's property decides, not the switch at the time of the cut)
     ClockOf<LodCutMark>& clock = c->lod_cut_clock;
-    const uint32_t levels = c->lod_levels;
-    const uint64_t N = c->lod_first[levels];
+    const uint32_t levels = c->lod.levels;
+    const uint64_t N = c->lod.nodes();
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(clock.begin(c->err, c->profiling));
     if (vis == LodVis::Here) M2S_TRY(c->lod_vis_clock.begin(c->err, c->profiling));
     uint32_t h[kLodCountWords] = {};
     uint64_t selected = 0;
     if (N) {
-        M2S_TRY(c->d_lod_open.reserve(c->err, N, 1));
-        M2S_TRY(c->d_lod_counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
+        M2S_TRY(c->lod_work.open.reserve(c->err, N, 1));
+        M2S_TRY(c->lod_work.counts.reserve(c->err, kLodCountWords, sizeof(uint32_t)));
         M2S_TRY(c->d_prune_u32.reserve(c->err, N, 2 * sizeof(uint32_t)));
         if (!dry) {
             M2S_TRY(c->d_prune_temp.reserve(c->err, align_up(prune_scan_temp_bytes((uint32_t)N), 16) + 2 * sizeof(unsigned long long), 1));
-            M2S_TRY(c->d_lod_ids.reserve(c->err, N, sizeof(uint32_t)));
+            M2S_TRY(c->lod_work.ids.reserve(c->err, N, sizeof(uint32_t)));
             c->lod_ids_tag.clear();
         }
         uint32_t* const flags = c->d_prune_u32;
@@ -155,16 +139,15 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
         if (vis == LodVis::Here) M2S_TRY(lod_vis_enqueue(c, fr, oc));
         HIPCHK(c, clock.mark(LodCutMark::Start, c->stream));
         // (with a frustum the words were zeroed by lod_vis_enqueue, here or in the caller, and hold the inside count by now: not again)
-        if (vis == LodVis::None) HIPCHK(c, hipMemsetAsync(c->d_lod_counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
-        HIPCHK(c, lod_sweep(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_open, flags, c->d_lod_counts,
-                            fr ? c->d_lod_vis.get() : nullptr, c->stream));
+        if (vis == LodVis::None) HIPCHK(c, hipMemsetAsync(c->lod_work.counts, 0, kLodCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, lod_sweep(c->lod.levels_k<LodLevelsK>(), k, c->lod_work.open, flags, c->lod_work.counts, fr ? c->lod_work.vis.get() : nullptr, c->stream));
         HIPCHK(c, clock.mark(LodCutMark::Swept, c->stream));
         if (!dry) {
             HIPCHK(c, lod_scan(flags, offsets, (uint32_t)N, c->d_prune_temp, c->d_prune_temp.cap() - 2 * sizeof(unsigned long long), c->stream));
-            HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->d_lod_ids, c->stream));
+            HIPCHK(c, lod_node_ids(flags, offsets, (uint32_t)N, c->lod_work.ids, c->stream));
             HIPCHK(c, clock.mark(LodCutMark::Indexed, c->stream));
         }
-        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h, c->lod_work.counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint32_t l = 0; l < levels; ++l) selected += h[l];
         // (a frustum may leave nothing; the plain cut holds every leaf's ancestor-or-self)
@@ -172,14 +155,14 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
             (uint64_t)h[kLodOccludedWord] + h[kLodKeptWord] > h[kLodInsideWord])
             return fail(c, M2S_ERR_HIP, "the cut's counts came back inconsistent");
         if (!dry) {
-            M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->d_lod_nodes));
+            M2S_TRY(prune_compact_enqueue(c, N, selected, flags, offsets, false, c->lod.rows<const void>(kLodRecords)));
             if (with_sh) {
                 // the selected nodes' rows of the tree's plane, by the same flags and offsets, straight into the context's plane (the
                 // source is the tree's: nothing lands on itself); whatever plane the context had is gone from here on
                 c->sh_tag.clear();
                 c->bake_has_counts = false;
                 M2S_TRY(c->d_sh.reserve(c->err, std::max<uint64_t>(selected, 1), 48 * sizeof(float)));
-                if (selected) HIPCHK(c, prune_compact((const float4*)c->d_lod_sh.get(), flags, offsets, (uint32_t)N, kMergeShLanes, (float4*)c->d_sh.get(), c->stream));
+                if (selected) HIPCHK(c, prune_compact(c->lod.rows<const float4>(kLodSh), flags, offsets, (uint32_t)N, kMergeShLanes, (float4*)c->d_sh.get(), c->stream));
             }
             HIPCHK(c, clock.mark(LodCutMark::Compacted, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -200,10 +183,10 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
     }
     if (!dry) {
         // (a baked plane of the context is one of other records: dropped; a tree with a plane has left the selected nodes' rows in its place)
-        c->rewritten(c->lane[0].records, selected, c->lod_R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
-        if (with_sh) c->sh_degree = c->lod_sh_degree;
+        c->rewritten(c->lane[0].records, selected, c->lod.R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
+        if (with_sh) c->sh_degree = c->lod.sh_degree;
         c->lod_ids_tag.set(*c, selected);
-        c->lod_ids_gen = c->lod_tree_gen;                                // (which tree the indices are of: m2s_lod_blend reads it through them)
+        c->lod_work.ids_gen = c->lod.gen;                                // (which tree the indices are of: m2s_lod_blend reads it through them)
     }
     c->last_lod_select_counts[0] = N; c->last_lod_select_counts[1] = selected; c->last_lod_select_counts[2] = h[0];
     c->last_lod_select_counts[3] = h[kLodRefineWord];
@@ -218,20 +201,13 @@ m2s_status lod_cut(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t out_coun
 }
 
 m2s_status lod_select_check(m2s_ctx* c, const m2s_lod_select_params* p) {
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
-    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
-    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
-    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    M2S_TRY(lod_camera_check(c, p->camera_position, p->focal_px, p->near, &p->tau_px));
     if ((p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) || p->reserved != 0) return fail(c, M2S_ERR_INVALID, "unknown flag bits or reserved != 0");
     return M2S_OK;
 }
 
 m2s_status lod_budget_check(m2s_ctx* c, const m2s_lod_budget_params* p) {
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
-    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
-    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    M2S_TRY(lod_camera_check(c, p->camera_position, p->focal_px, p->near));
     if (!std::isfinite(p->tau_min_px) || !(p->tau_min_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_min_px is not finite or negative");
     if (p->max_records < 1) return fail(c, M2S_ERR_INVALID, "max_records is 0");
     if (p->flags & ~(uint32_t)M2S_LOD_DRY_RUN) return fail(c, M2S_ERR_INVALID, "unknown flag bits");
@@ -243,8 +219,7 @@ m2s_status lod_budget_check(m2s_ctx* c, const m2s_lod_budget_params* p) {
 m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_frustum* fr, m2s_lod_budget_result* out, uint64_t out_counts[4],
                       const m2s_lod_occluder* oc = nullptr) {
     ClockOf<LodBudgetMark>& clock = c->lod_budget_clock;
-    const uint32_t levels = c->lod_levels;
-    const uint64_t N = c->lod_first[levels], last = N - c->lod_first[levels - 1];
+    const uint64_t N = c->lod.nodes(), last = N - c->lod.first[c->lod.levels - 1];
     uint32_t floor_key = 0, key = 0;
     if (p->tau_min_px > 0.0f) std::memcpy(&floor_key, &p->tau_min_px, sizeof(floor_key));
     uint32_t h[3] = {};                                                 // prefix, below, finer
@@ -252,17 +227,18 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
     M2S_TRY(clock.begin(c->err, c->profiling));
     if (fr) M2S_TRY(c->lod_vis_clock.begin(c->err, c->profiling));
     if (N) {
-        M2S_TRY(c->d_lod_lh.reserve(c->err, N, sizeof(uint2)));
-        M2S_TRY(c->d_lod_budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
+        M2S_TRY(c->lod_work.lh.reserve(c->err, N, sizeof(uint2)));
+        M2S_TRY(c->lod_work.budget_state.reserve(c->err, kLodBudgetStateWords, sizeof(uint32_t)));
         const uint32_t n_eff = fr ? p->max_records : (uint32_t)std::max<uint64_t>(p->max_records, last);
         const LodSelectK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, 0.0f, p->near * p->near };
         if (fr) M2S_TRY(lod_vis_enqueue(c, fr, oc));
         HIPCHK(c, clock.mark(LodBudgetMark::Start, c->stream));
-        HIPCHK(c, lod_thresholds(c->d_lod_bounds, c->d_lod_parent, c->lod_first, levels, k, c->d_lod_lh, fr ? c->d_lod_vis.get() : nullptr, c->stream));
+        uint2* const lh = static_cast<uint2*>(c->lod_work.lh.get());
+        HIPCHK(c, lod_thresholds(c->lod.levels_k<LodLevelsK>(), k, lh, fr ? c->lod_work.vis.get() : nullptr, c->stream));
         HIPCHK(c, clock.mark(LodBudgetMark::Thresholds, c->stream));
-        HIPCHK(c, lod_budget_search(c->d_lod_lh, (uint32_t)N, n_eff, fr != nullptr, c->d_lod_budget_state, c->stream));
+        HIPCHK(c, lod_budget_search(lh, (uint32_t)N, n_eff, fr != nullptr, c->lod_work.budget_state, c->stream));
         HIPCHK(c, clock.mark(LodBudgetMark::Searched, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h, c->lod_work.budget_state, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         key = h[kLodBudgetPrefix];
         if (key > 0x7F7FFFFFu) return fail(c, M2S_ERR_HIP, "the budget search came back with no finite tau_px");
@@ -293,11 +269,7 @@ m2s_status lod_budget(m2s_ctx* c, const m2s_lod_budget_params* p, const m2s_lod_
 }
 
 m2s_status lod_blend_check(m2s_ctx* c, const m2s_lod_blend_params* p) {
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->camera_position[k])) return fail(c, M2S_ERR_INVALID, "camera_position is not finite");
-    if (!std::isfinite(p->focal_px) || !(p->focal_px > 0.0f)) return fail(c, M2S_ERR_INVALID, "focal_px is not finite or not positive");
-    if (!std::isfinite(p->tau_px) || !(p->tau_px >= 0.0f)) return fail(c, M2S_ERR_INVALID, "tau_px is not finite or negative");
-    if (!std::isfinite(p->near) || !(p->near > 0.0f)) return fail(c, M2S_ERR_INVALID, "near is not finite or not positive");
+    M2S_TRY(lod_camera_check(c, p->camera_position, p->focal_px, p->near, &p->tau_px));
     if (!std::isfinite(p->band) || !(p->band > 0.0f) || !(p->band <= 1.0f)) return fail(c, M2S_ERR_INVALID, "band is not finite or outside (0, 1]");
     if (p->reserved != 0) return fail(c, M2S_ERR_INVALID, "reserved != 0");
     return M2S_OK;
@@ -307,28 +279,29 @@ m2s_status lod_blend_check(m2s_ctx* c, const m2s_lod_blend_params* p) {
 // there out of the tree (the source is never the pool: nothing lands on itself), and the rows of the context's plane out of the tree's.
 m2s_status lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out_counts[4]) {
     const uint64_t n = c->lod_ids_tag.n;
-    const bool with_sh = c->lod_has_sh && c->sh_tag.holds(*c, n);       // (pin 6)
+    const bool with_sh = c->lod.has_sh && c->sh_tag.holds(*c, n);       // (pin 6)
     ClockOf<LodBlendMark>& clock = c->lod_blend_clock;
     uint32_t h[kLodBlendCountWords] = {};
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(clock.begin(c->err, true));                                 // (measured whatever m2s_set_profiling says)
-    c->lod_blend_tag.clear();
+    c->lod_work.blend_tag.clear();
     if (n) {
-        M2S_TRY(c->d_lod_blend_t.reserve(c->err, n, sizeof(float)));
-        M2S_TRY(c->d_lod_blend_counts.reserve(c->err, kLodBlendCountWords, sizeof(uint32_t)));
+        M2S_TRY(c->lod_work.blend_t.reserve(c->err, n, sizeof(float)));
+        M2S_TRY(c->lod_work.blend_counts.reserve(c->err, kLodBlendCountWords, sizeof(uint32_t)));
         float4* const pool = (float4*)c->lane[0].records.get();
+        const uint32_t* const parent = c->lod.rows<const uint32_t>(kLodParent);
         const LodBlendK k = { p->camera_position[0], p->camera_position[1], p->camera_position[2], p->focal_px, p->tau_px * p->tau_px, p->near * p->near, p->band };
-        HIPCHK(c, hipMemsetAsync(c->d_lod_blend_counts, 0, kLodBlendCountWords * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->lod_work.blend_counts, 0, kLodBlendCountWords * sizeof(uint32_t), c->stream));
         HIPCHK(c, clock.mark(LodBlendMark::Start, c->stream));
-        HIPCHK(c, lod_blend_weights(c->d_lod_ids, c->d_lod_parent, c->d_lod_bounds, (uint32_t)n, k, c->d_lod_blend_t, c->d_lod_blend_counts, c->stream));
+        HIPCHK(c, lod_blend_weights(c->lod_work.ids, parent, c->lod.rows<const float4>(kLodBounds), (uint32_t)n, k, c->lod_work.blend_t, c->lod_work.blend_counts, c->stream));
         HIPCHK(c, clock.mark(LodBlendMark::Weighted, c->stream));
-        HIPCHK(c, lod_blend_records(c->d_lod_nodes, c->d_lod_ids, c->d_lod_parent, c->d_lod_blend_t, (uint32_t)n, pool, c->d_lod_blend_counts, c->stream));
+        HIPCHK(c, lod_blend_records(c->lod.rows<const float4>(kLodRecords), c->lod_work.ids, parent, c->lod_work.blend_t, (uint32_t)n, pool, c->lod_work.blend_counts, c->stream));
         HIPCHK(c, clock.mark(LodBlendMark::Blended, c->stream));
         if (with_sh) {
-            HIPCHK(c, lod_blend_sh((const float4*)c->d_lod_sh.get(), c->d_lod_ids, c->d_lod_parent, c->d_lod_blend_t, (uint32_t)n, (float4*)c->d_sh.get(), c->stream));
+            HIPCHK(c, lod_blend_sh(c->lod.rows<const float4>(kLodSh), c->lod_work.ids, parent, c->lod_work.blend_t, (uint32_t)n, (float4*)c->d_sh.get(), c->stream));
             HIPCHK(c, clock.mark(LodBlendMark::ShBlended, c->stream));
         }
-        HIPCHK(c, hipMemcpyAsync(h, c->d_lod_blend_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h, c->lod_work.blend_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (h[kLodBlendBlended] > n || h[kLodBlendSaturated] > h[kLodBlendBlended] || h[kLodBlendTurned] > h[kLodBlendBlended])
             return fail(c, M2S_ERR_HIP, "the blend's counts came back inconsistent");
@@ -339,10 +312,10 @@ m2s_status lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out_cou
     HIPCHK(c, clock.span(LodBlendMark::Blended, LodBlendMark::ShBlended, &ms[2]));
     HIPCHK(c, clock.span(LodBlendMark::Start, with_sh ? LodBlendMark::ShBlended : LodBlendMark::Blended, &c->last_lod_blend_ms));
     // pin 7: what a cut does to the context, then the two planes the cut and this pass left are the new records' again
-    c->rewritten(c->lane[0].records, n, c->lod_R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
-    if (with_sh) c->sh_degree = c->lod_sh_degree;
+    c->rewritten(c->lane[0].records, n, c->lod.R, with_sh ? Rewrite::LodCutWithSh : Rewrite::LodCut);
+    if (with_sh) c->sh_degree = c->lod.sh_degree;
     c->lod_ids_tag.set(*c, n);
-    c->lod_blend_tag.set(*c, n);
+    c->lod_work.blend_tag.set(*c, n);
     c->last_lod_blend_counts[0] = n; c->last_lod_blend_counts[1] = h[kLodBlendBlended]; c->last_lod_blend_counts[2] = h[kLodBlendSaturated];
     c->last_lod_blend_counts[3] = h[kLodBlendTurned];
     if (out_counts) std::memcpy(out_counts, c->last_lod_blend_counts, sizeof(c->last_lod_blend_counts));
@@ -357,27 +330,26 @@ m2s_status m2s_lod_blend(m2s_ctx* c, const m2s_lod_blend_params* p, uint64_t out
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
     if (!c || !p) return M2S_ERR_INVALID;
     M2S_TRY(lod_blend_check(c, p));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    if (c->lod_model != M2S_MERGE_MODEL_FOOTPRINT)
+    M2S_TRY(lod_ready(c));
+    if (c->lod.model != M2S_MERGE_MODEL_FOOTPRINT)
         return fail(c, M2S_ERR_STATE, "the tree was built under M2S_MERGE_MODEL_GAUSSIAN: the blend's frame turns and axis-by-axis lerp assume the footprint's axis order");
-    if (!lod_ids_valid(c) || c->lod_ids_gen != c->lod_tree_gen || c->last_records != c->lane[0].records.get() || c->last_stored != c->lod_ids_tag.n)
+    if (!lod_ids_valid(c) || c->lod_work.ids_gen != c->lod.gen || c->last_records != c->lane[0].records.get() || c->last_stored != c->lod_ids_tag.n)
         return fail(c, M2S_ERR_STATE, "the current records are not what the last cut of this tree left (m2s_lod_select without M2S_LOD_DRY_RUN first)");
     return lod_blend(c, p, out_counts);
 }
 
-const void* m2s_device_lod_blend_t(const m2s_ctx* c) { return c && c->lod_blend_tag.holds(*c) && c->lod_blend_tag.n ? c->d_lod_blend_t.get() : nullptr; }
+const void* m2s_device_lod_blend_t(const m2s_ctx* c) { return c && c->lod_work.blend_tag.holds(*c) && c->lod_work.blend_tag.n ? c->lod_work.blend_t.get() : nullptr; }
 
 m2s_status m2s_download_lod_blend_t(m2s_ctx* c, float* dst, uint64_t capacity, uint64_t* out_n) {
     if (out_n) *out_n = 0;
     if (!c) return M2S_ERR_INVALID;
-    if (!c->lod_blend_tag.holds(*c)) return fail(c, M2S_ERR_STATE, "no blend weights of the current records (m2s_lod_blend; the records changed since)");
-    if (out_n) *out_n = c->lod_blend_tag.n;
+    if (!c->lod_work.blend_tag.holds(*c)) return fail(c, M2S_ERR_STATE, "no blend weights of the current records (m2s_lod_blend; the records changed since)");
+    if (out_n) *out_n = c->lod_work.blend_tag.n;
     if (!dst) return capacity ? fail(c, M2S_ERR_INVALID, "no destination") : M2S_OK;
-    if (capacity < c->lod_blend_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
-    if (!c->lod_blend_tag.n) return M2S_OK;
+    if (capacity < c->lod_work.blend_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
+    if (!c->lod_work.blend_tag.n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_lod_blend_t, c->lod_blend_tag.n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->lod_work.blend_t, c->lod_work.blend_tag.n * sizeof(float), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -409,20 +381,19 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
     const float sigma = c->merge_sigma;
     HIPCHK(c, hipSetDevice(c->device));
     M2S_TRY(c->lod_build_clock.begin(c->err, true));                    // (measured whatever m2s_set_profiling says)
-    c->lod_levels = 0;                                                  // (the tree of an earlier call ends here, whatever follows)
-    ++c->lod_tree_gen;
-    c->lod_has_sh = false;
-    if (!with_sh) c->d_lod_sh.release();                                // (192 bytes per node: not kept for a tree that has no use for it)
+    LodTree& t = c->lod;
+    t.end();                                                            // (the tree of an earlier call ends here, whatever follows)
+    if (!with_sh) t.drop_sh();
     HIPCHK(c, c->lod_build_clock.mark(SpanMark::Begin, c->stream));
-    M2S_TRY(lod_reserve(c, n0 + n0 / 2, 0, with_sh));
+    M2S_TRY(t.reserve(c->err, c->stream, n0 + n0 / 2, 0, with_sh));
     uint64_t first[M2S_LOD_MAX_STEPS + 2] = {};
     uint32_t levels = 1;
     uint64_t skipped = 0;
     first[1] = n0;
     if (n0) {
-        HIPCHK(c, hipMemcpyAsync(c->d_lod_nodes, c->last_records, n0 * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, c->d_lod_nodes, (uint32_t)n0, c->d_lod_bounds, gauss, sigma, c->stream));
-        if (with_sh) HIPCHK(c, hipMemcpyAsync(c->d_lod_sh, c->d_sh, n0 * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(t.rows<float4>(kLodRecords), c->last_records, n0 * t.row_bytes(kLodRecords), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, lod_link(nullptr, 0, 0, nullptr, t.rows<float4>(kLodRecords), (uint32_t)n0, t.rows<float4>(kLodBounds), gauss, sigma, c->stream));
+        if (with_sh) HIPCHK(c, hipMemcpyAsync(t.rows<float>(kLodSh), c->d_sh, n0 * t.row_bytes(kLodSh), hipMemcpyDeviceToDevice, c->stream));
     }
     for (uint32_t s = 0; s < p->n_steps; ++s) {
         const uint64_t below = first[levels - 1], cnt = first[levels] - below;
@@ -431,28 +402,22 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
         if (after == cnt) { ++skipped; continue; }                      // (nothing merged and nothing changed: no level)
         const uint64_t total = first[levels] + after;
         if (total >= kLodMaxNodes) return fail(c, M2S_ERR_CAPACITY, "2^32-1 nodes or more");
-        M2S_TRY(lod_reserve(c, total, first[levels], with_sh));
-        float4* const level = c->d_lod_nodes + 6 * first[levels];
-        HIPCHK(c, hipMemcpyAsync(level, c->last_records, after * sizeof(m2s_gaussian), hipMemcpyDeviceToDevice, c->stream));
+        M2S_TRY(t.reserve(c->err, c->stream, total, first[levels], with_sh));
+        float4* const level = t.rows<float4>(kLodRecords, first[levels]);
+        HIPCHK(c, hipMemcpyAsync(level, c->last_records, after * t.row_bytes(kLodRecords), hipMemcpyDeviceToDevice, c->stream));
         if (with_sh) {                                                  // (the rows pin 5s made for this step: the context's plane by now)
             if (!c->sh_tag.holds(*c, after)) return fail(c, M2S_ERR_HIP, "the merge left no plane of its parents (internal error)");
-            HIPCHK(c, hipMemcpyAsync(c->d_lod_sh + 48 * first[levels], c->d_sh, after * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(t.rows<float>(kLodSh, first[levels]), c->d_sh, after * t.row_bytes(kLodSh), hipMemcpyDeviceToDevice, c->stream));
         }
-        HIPCHK(c, lod_link(c->d_merge_map, (uint32_t)cnt, (uint32_t)first[levels], c->d_lod_parent + below, level, (uint32_t)after,
-                           c->d_lod_bounds + first[levels], gauss, sigma, c->stream));
+        HIPCHK(c, lod_link(c->d_merge_map, (uint32_t)cnt, (uint32_t)first[levels], t.rows<uint32_t>(kLodParent, below), level, (uint32_t)after,
+                           t.rows<float4>(kLodBounds, first[levels]), gauss, sigma, c->stream));
         first[++levels] = total;                                        // (the next step rewrites the map and the pool behind these, stream-ordered)
     }
-    HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, c->d_lod_parent + first[levels - 1], nullptr, 0, nullptr, gauss, sigma, c->stream));
+    HIPCHK(c, lod_link(nullptr, (uint32_t)(first[levels] - first[levels - 1]), 0, t.rows<uint32_t>(kLodParent, first[levels - 1]), nullptr, 0, nullptr, gauss, sigma, c->stream));
     HIPCHK(c, c->lod_build_clock.mark(SpanMark::End, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->lod_build_clock.span(SpanMark::Begin, SpanMark::End, &c->last_lod_build_ms));
-    for (uint32_t l = 0; l < M2S_LOD_MAX_STEPS + 2; ++l) c->lod_first[l] = first[std::min(l, levels)];
-    c->lod_levels = levels;
-    c->lod_R = R;
-    c->lod_has_sh = with_sh;
-    c->lod_sh_degree = sh_degree;
-    c->lod_model = gauss ? M2S_MERGE_MODEL_GAUSSIAN : M2S_MERGE_MODEL_FOOTPRINT;
-    c->lod_sigma = sigma;
+    t.commit(levels, first, R, with_sh, sh_degree, gauss ? M2S_MERGE_MODEL_GAUSSIAN : M2S_MERGE_MODEL_FOOTPRINT, sigma);
     if (out_counts) { out_counts[0] = n0; out_counts[1] = first[levels]; out_counts[2] = levels; out_counts[3] = skipped; }
     return M2S_OK;
 }
@@ -460,46 +425,41 @@ m2s_status m2s_lod_build(m2s_ctx* c, const m2s_lod_build_params* p, uint64_t out
 m2s_status m2s_lod_levels(const m2s_ctx* c, uint32_t* out_levels, uint64_t first[M2S_LOD_MAX_STEPS + 2]) {
     if (out_levels) *out_levels = 0;
     if (!c) return M2S_ERR_INVALID;
-    if (!c->lod_levels) return M2S_ERR_STATE;
-    if (out_levels) *out_levels = c->lod_levels;
-    if (first) std::memcpy(first, c->lod_first, sizeof(c->lod_first));
+    if (!c->lod.levels) return M2S_ERR_STATE;
+    if (out_levels) *out_levels = c->lod.levels;
+    if (first) std::memcpy(first, c->lod.first, sizeof(c->lod.first));
     return M2S_OK;
 }
 
-const void* m2s_device_lod(const m2s_ctx* c, uint32_t which) {
-    if (!c || !c->lod_levels || which > 2 || !c->lod_first[c->lod_levels]) return nullptr;
-    return which == 0 ? (const void*)c->d_lod_nodes.get() : which == 1 ? (const void*)c->d_lod_parent.get() : (const void*)c->d_lod_bounds.get();
-}
+const void* m2s_device_lod(const m2s_ctx* c, uint32_t which) { return c && which <= kLodBounds ? c->lod.plane(which) : nullptr; }
 
 m2s_status m2s_download_lod(m2s_ctx* c, uint32_t which, void* dst, uint64_t capacity_bytes) {
     if (!c) return M2S_ERR_INVALID;
     if (which > 2) return fail(c, M2S_ERR_INVALID, "which outside 0..2");
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    const uint64_t bytes = c->lod_first[c->lod_levels] * (which == 0 ? sizeof(m2s_gaussian) : which == 1 ? sizeof(uint32_t) : sizeof(float4));
+    if (!c->lod.levels) return fail(c, M2S_ERR_STATE, kNoTreeMsg);
+    const uint64_t bytes = c->lod.nodes() * c->lod.row_bytes(which);
     if (capacity_bytes < bytes) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer bytes than the plane");
     if (!bytes) return M2S_OK;
     if (!dst) return fail(c, M2S_ERR_INVALID, "no destination");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, m2s_device_lod(c, which), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->lod.plane(which), bytes, hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
-const void* m2s_device_lod_sh(const m2s_ctx* c) {
-    return c && c->lod_levels && c->lod_has_sh && c->lod_first[c->lod_levels] ? c->d_lod_sh.get() : nullptr;
-}
+const void* m2s_device_lod_sh(const m2s_ctx* c) { return c ? c->lod.plane(kLodSh) : nullptr; }
 
 m2s_status m2s_download_lod_sh(m2s_ctx* c, float* dst, uint64_t capacity_rows, uint32_t* out_degree) {
     if (out_degree) *out_degree = 0;
     if (!c) return M2S_ERR_INVALID;
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
-    if (!c->lod_has_sh) return fail(c, M2S_ERR_STATE, "the tree has no SH plane (m2s_set_carry_sh and a baked plane at m2s_lod_build)");
-    const uint64_t rows = c->lod_first[c->lod_levels];
+    if (!c->lod.levels) return fail(c, M2S_ERR_STATE, kNoTreeMsg);
+    if (!c->lod.has_sh) return fail(c, M2S_ERR_STATE, "the tree has no SH plane (m2s_set_carry_sh and a baked plane at m2s_lod_build)");
+    const uint64_t rows = c->lod.nodes();
     if (capacity_rows < rows) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer rows than the plane");
-    if (out_degree) *out_degree = c->lod_sh_degree;
+    if (out_degree) *out_degree = c->lod.sh_degree;
     if (!rows) return M2S_OK;
     if (!dst) return fail(c, M2S_ERR_INVALID, "no destination");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_lod_sh, rows * 48 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->lod.plane(kLodSh), rows * c->lod.row_bytes(kLodSh), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 
@@ -507,13 +467,8 @@ m2s_status m2s_lod_release(m2s_ctx* c) {
     if (!c) return M2S_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->lod_levels = 0;
-    ++c->lod_tree_gen;
-    c->lod_has_sh = false;
-    c->d_lod_sh.release();
-    c->d_lod_blend_t.release(); c->lod_blend_tag.clear();
-    c->d_lod_nodes.release(); c->d_lod_parent.release(); c->d_lod_bounds.release(); c->d_lod_open.release(); c->d_lod_lh.release(); c->d_lod_vis.release();
-    c->d_lod_occ_depth.release();
+    c->lod.release();
+    c->lod_work.release_tree_sized();
     return M2S_OK;
 }
 
@@ -523,8 +478,7 @@ m2s_status m2s_lod_select(m2s_ctx* c, const m2s_lod_select_params* p, uint64_t o
     if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
     if (!c || !p) return M2S_ERR_INVALID;
     M2S_TRY(lod_select_check(c, p));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     return lod_cut(c, p, out_counts, nullptr, LodVis::None);
 }
 
@@ -533,8 +487,7 @@ m2s_status m2s_lod_select_frustum(m2s_ctx* c, const m2s_lod_select_params* p, co
     if (!c || !p) return M2S_ERR_INVALID;
     M2S_TRY(lod_select_check(c, p));
     M2S_TRY(lod_frustum_check(c, fr));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     return lod_cut(c, p, out_counts, fr, LodVis::Here);
 }
 
@@ -543,8 +496,7 @@ m2s_status m2s_lod_select_budget(m2s_ctx* c, const m2s_lod_budget_params* p, m2s
     if (out) std::memset(out, 0, sizeof(*out));
     if (!c || !p) return M2S_ERR_INVALID;
     M2S_TRY(lod_budget_check(c, p));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     return lod_budget(c, p, nullptr, out, out_counts);
 }
 
@@ -555,8 +507,7 @@ m2s_status m2s_lod_select_budget_frustum(m2s_ctx* c, const m2s_lod_budget_params
     if (!c || !p) return M2S_ERR_INVALID;
     M2S_TRY(lod_budget_check(c, p));
     M2S_TRY(lod_frustum_check(c, fr));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     return lod_budget(c, p, fr, out, out_counts);
 }
 
@@ -567,8 +518,7 @@ m2s_status m2s_lod_select_occluded(m2s_ctx* c, const m2s_lod_select_params* p, c
     M2S_TRY(lod_select_check(c, p));
     M2S_TRY(lod_frustum_check(c, fr));
     M2S_TRY(lod_occluder_check(c, oc));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     M2S_TRY(lod_occluder_state(c, oc));
     return lod_cut(c, p, out_counts, fr, LodVis::Here, oc);
 }
@@ -581,8 +531,7 @@ m2s_status m2s_lod_select_budget_occluded(m2s_ctx* c, const m2s_lod_budget_param
     M2S_TRY(lod_budget_check(c, p));
     M2S_TRY(lod_frustum_check(c, fr));
     M2S_TRY(lod_occluder_check(c, oc));
-    if (c->slot_count) return fail(c, M2S_ERR_STATE, kInFlightMsg);
-    if (!c->lod_levels) return fail(c, M2S_ERR_STATE, "no level-of-detail tree (m2s_lod_build)");
+    M2S_TRY(lod_ready(c));
     M2S_TRY(lod_occluder_state(c, oc));
     return lod_budget(c, p, fr, out, out_counts, oc);
 }
@@ -599,7 +548,7 @@ m2s_status m2s_last_lod_level_counts(const m2s_ctx* c, uint64_t out[M2S_LOD_MAX_
 
 m2s_status m2s_last_lod_select_stage_ms(const m2s_ctx* c, float out_ms[3]) { return get_array(c, &m2s_ctx::last_lod_select_stage_ms, out_ms); }
 
-const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_tag.n ? c->d_lod_ids.get() : nullptr; }
+const void* m2s_device_lod_nodes(const m2s_ctx* c) { return c && lod_ids_valid(c) && c->lod_ids_tag.n ? c->lod_work.ids.get() : nullptr; }
 
 m2s_status m2s_download_lod_nodes(m2s_ctx* c, uint32_t* dst, uint64_t capacity, uint64_t* out_n) {
     if (out_n) *out_n = 0;
@@ -610,7 +559,7 @@ m2s_status m2s_download_lod_nodes(m2s_ctx* c, uint32_t* dst, uint64_t capacity, 
     if (capacity < c->lod_ids_tag.n) return fail(c, M2S_ERR_CAPACITY, "destination holds fewer entries than there are records");
     if (!c->lod_ids_tag.n) return M2S_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(dst, c->d_lod_ids, c->lod_ids_tag.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->lod_work.ids, c->lod_ids_tag.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return M2S_OK;
 }
 

@@ -133,20 +133,19 @@ hipError_t lod_link(const uint32_t* map, uint32_t n_map, uint32_t offset, uint32
 namespace {
 
 template <bool kVis>
-hipError_t lod_sweep_levels(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
-                            uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
-    for (uint32_t l = levels; l-- > 0;) {
-        const uint32_t f = (uint32_t)first[l], n = (uint32_t)(first[l + 1] - first[l]);
+hipError_t lod_sweep_levels(const LodLevelsK& t, const LodSelectK& k, uint8_t* open, uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
+    for (uint32_t l = t.levels; l-- > 0;) {
+        const uint32_t f = (uint32_t)t.first[l], n = (uint32_t)(t.first[l + 1] - t.first[l]);
         if (!n) continue;
         const dim3 grid(std::min((n + 255u) / 256u, kLodGrid)), block(256);
-        const bool top = l + 1 == levels, leaf = l == 0;
+        const bool top = l + 1 == t.levels, leaf = l == 0;
         uint32_t* const sel = counts + l;
         uint32_t* const ref = counts + kLodRefineWord;
         uint32_t* const pln = counts + kLodPlainWord;
-        if (top && leaf) hipLaunchKernelGGL((k_lod_select<true, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
-        else if (top) hipLaunchKernelGGL((k_lod_select<true, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
-        else if (leaf) hipLaunchKernelGGL((k_lod_select<false, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
-        else hipLaunchKernelGGL((k_lod_select<false, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, open, flags, sel, ref, vis, pln);
+        if (top && leaf) hipLaunchKernelGGL((k_lod_select<true, true, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else if (top) hipLaunchKernelGGL((k_lod_select<true, false, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else if (leaf) hipLaunchKernelGGL((k_lod_select<false, true, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, open, flags, sel, ref, vis, pln);
+        else hipLaunchKernelGGL((k_lod_select<false, false, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, open, flags, sel, ref, vis, pln);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -155,10 +154,8 @@ hipError_t lod_sweep_levels(const float4* bounds, const uint32_t* parent, const 
 
 }  // namespace
 
-hipError_t lod_sweep(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint8_t* open,
-                     uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
-    return vis ? lod_sweep_levels<true>(bounds, parent, first, levels, k, open, flags, counts, vis, st)
-               : lod_sweep_levels<false>(bounds, parent, first, levels, k, open, flags, counts, nullptr, st);
+hipError_t lod_sweep(const LodLevelsK& t, const LodSelectK& k, uint8_t* open, uint32_t* flags, uint32_t* counts, const uint8_t* vis, hipStream_t st) {
+    return vis ? lod_sweep_levels<true>(t, k, open, flags, counts, vis, st) : lod_sweep_levels<false>(t, k, open, flags, counts, nullptr, st);
 }
 
 hipError_t lod_node_ids(const uint32_t* flags, const uint32_t* offsets, uint32_t n, uint32_t* ids, hipStream_t st) {

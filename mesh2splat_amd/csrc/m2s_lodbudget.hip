@@ -154,17 +154,16 @@ __global__ void __launch_bounds__(256) k_lod_budget_pick(uint32_t pass, uint32_t
 }
 
 template <bool kVis>
-hipError_t lod_thresholds_levels(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
-                                 const uint8_t* vis, hipStream_t st) {
-    for (uint32_t l = levels; l-- > 0;) {
-        const uint32_t f = (uint32_t)first[l], n = (uint32_t)(first[l + 1] - first[l]);
+hipError_t lod_thresholds_levels(const LodLevelsK& t, const LodSelectK& k, uint2* lh, const uint8_t* vis, hipStream_t st) {
+    for (uint32_t l = t.levels; l-- > 0;) {
+        const uint32_t f = (uint32_t)t.first[l], n = (uint32_t)(t.first[l + 1] - t.first[l]);
         if (!n) continue;
         const dim3 grid(std::min((n + 255u) / 256u, 2u * kLodBudgetGrid)), block(256);
-        const bool top = l + 1 == levels, leaf = l == 0;
-        if (top && leaf) hipLaunchKernelGGL((k_lod_thresholds<true, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
-        else if (top) hipLaunchKernelGGL((k_lod_thresholds<true, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
-        else if (leaf) hipLaunchKernelGGL((k_lod_thresholds<false, true, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
-        else hipLaunchKernelGGL((k_lod_thresholds<false, false, kVis>), grid, block, 0, st, bounds, parent, f, n, k, lh, vis);
+        const bool top = l + 1 == t.levels, leaf = l == 0;
+        if (top && leaf) hipLaunchKernelGGL((k_lod_thresholds<true, true, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, lh, vis);
+        else if (top) hipLaunchKernelGGL((k_lod_thresholds<true, false, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, lh, vis);
+        else if (leaf) hipLaunchKernelGGL((k_lod_thresholds<false, true, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, lh, vis);
+        else hipLaunchKernelGGL((k_lod_thresholds<false, false, kVis>), grid, block, 0, st, t.bounds, t.parent, f, n, k, lh, vis);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -173,10 +172,8 @@ hipError_t lod_thresholds_levels(const float4* bounds, const uint32_t* parent, c
 
 }  // namespace
 
-hipError_t lod_thresholds(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodSelectK& k, uint2* lh,
-                          const uint8_t* vis, hipStream_t st) {
-    return vis ? lod_thresholds_levels<true>(bounds, parent, first, levels, k, lh, vis, st)
-               : lod_thresholds_levels<false>(bounds, parent, first, levels, k, lh, nullptr, st);
+hipError_t lod_thresholds(const LodLevelsK& t, const LodSelectK& k, uint2* lh, const uint8_t* vis, hipStream_t st) {
+    return vis ? lod_thresholds_levels<true>(t, k, lh, vis, st) : lod_thresholds_levels<false>(t, k, lh, nullptr, st);
 }
 
 hipError_t lod_budget_search(const uint2* lh, uint32_t n, uint32_t budget, bool raise_to_last, uint32_t* state, hipStream_t st) {

@@ -103,24 +103,23 @@ __global__ void __launch_bounds__(256) k_lod_visible(const float4* __restrict__ 
 
 }  // namespace
 
-hipError_t lod_visibility(const float4* bounds, const uint32_t* parent, const uint64_t* first, uint32_t levels, const LodFrustumK& f,
-                          const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(vis, 0, (size_t)first[levels], st);
+hipError_t lod_visibility(const LodLevelsK& t, const LodFrustumK& f, const LodOccluderK* occ, uint8_t* vis, uint32_t* inside_word, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(vis, 0, (size_t)t.first[t.levels], st);
     if (e != hipSuccess) return e;
-    for (uint32_t l = 0; l < levels && (l == 0 || l + 1 < levels); ++l) {
-        const uint32_t fl = (uint32_t)first[l], n = (uint32_t)(first[l + 1] - first[l]);
+    for (uint32_t l = 0; l < t.levels && (l == 0 || l + 1 < t.levels); ++l) {
+        const uint32_t fl = (uint32_t)t.first[l], n = (uint32_t)(t.first[l + 1] - t.first[l]);
         if (!n) continue;
         const dim3 grid(std::min((n + 255u) / 256u, kLodVisGrid)), block(256);
         if (l == 0 && occ) {
             LodVisArgs<true> fo;
             static_cast<LodFrustumK&>(fo) = f;
             fo.occ = *occ;
-            hipLaunchKernelGGL((k_lod_visible<true, true>), grid, block, 0, st, bounds, parent, fl, n, fo, vis, inside_word);
+            hipLaunchKernelGGL((k_lod_visible<true, true>), grid, block, 0, st, t.bounds, t.parent, fl, n, fo, vis, inside_word);
         } else {
             LodVisArgs<false> fp;
             static_cast<LodFrustumK&>(fp) = f;
-            if (l == 0) hipLaunchKernelGGL((k_lod_visible<true, false>), grid, block, 0, st, bounds, parent, fl, n, fp, vis, inside_word);
-            else hipLaunchKernelGGL((k_lod_visible<false, false>), grid, block, 0, st, bounds, parent, fl, n, fp, vis, inside_word);
+            if (l == 0) hipLaunchKernelGGL((k_lod_visible<true, false>), grid, block, 0, st, t.bounds, t.parent, fl, n, fp, vis, inside_word);
+            else hipLaunchKernelGGL((k_lod_visible<false, false>), grid, block, 0, st, t.bounds, t.parent, fl, n, fp, vis, inside_word);
         }
         e = hipGetLastError();
         if (e != hipSuccess) return e;

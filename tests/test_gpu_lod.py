@@ -126,6 +126,35 @@ def test_build_and_select_against_single_merges_and_the_restatement(conv, ref, n
                         check_select(conv, tree, parent, b, first, cam, tau)
 
 
+def test_a_tree_that_outgrows_its_first_reservation(ref):
+    """A fresh context (the module's has planes that only ever grew): 1031 leaves under the chain 1..10 in pairs make the levels that
+    tests/merge_ref.py gives for this input, 8921 nodes against a first reservation of 1031 + 515 — the planes grow at 1910, 3544 and
+    6888 nodes, every time with the levels linked so far kept."""
+    n, levels, sizes = 1031, tuple(range(1, 11)), [1031, 879, 830, 804, 791, 780, 773, 764, 762, 754, 753]
+    rec = mr.crafted_records(n, n)
+    want_levels, maps, skipped = chain_one_by_one(ref, rec, levels, 2, 0.5)
+    counts = [len(v) for v in want_levels]
+    conv = Converter(0)
+    try:
+        conv.upload_records(rec)
+        out = conv.lod_build(levels, 2, 0.5)
+        tree, parent, b, first = download_tree(conv)
+        print(f"lod build n={n} chain={levels} group=2 dot=0.5 on a fresh context: {out}")
+        assert out["nodes"] > n + n // 2
+        assert out["nodes"] == 8921 and counts == sizes
+        assert out["leaves"] == n and out["nodes"] == sum(counts) == first[-1] and out["levels"] == len(counts) and out["skipped"] == skipped == 0
+        assert out["first"] == first == [int(v) for v in np.concatenate([[0], np.cumsum(counts)])]
+        for l, want in enumerate(want_levels):
+            assert np.array_equal(bits(tree[first[l]:first[l + 1]]), bits(want)), ("level", l)
+        wparent, wfirst = lr.link(maps, counts)
+        assert wfirst == first and np.array_equal(parent, wparent)
+        assert np.array_equal(bits(b), bits(lr.bounds(tree)))
+        assert conv.num_stored == counts[-1] and np.array_equal(bits(conv.download()), bits(want_levels[-1]))
+        check_select(conv, tree, parent, b, first, cameras(tree, b, first)[2], 0.5)
+    finally:
+        conv.close()
+
+
 def test_steps_that_merge_nothing_add_no_level(conv):
     rec = mr.crafted_records(65, 0)
     conv.upload_records(rec)

@@ -120,6 +120,41 @@ def test_tree_planes_and_the_four_cuts(conv, ref, n, levels, max_group, dot):
         assert got["selected"] == len(ids)
 
 
+def test_a_tree_with_a_plane_that_outgrows_its_first_reservation(ref):
+    """The twin of tests/test_gpu_lod.py's case with the switch on, on a fresh context: 1031 leaves under the chain 1..10 in pairs, 8921
+    nodes against a first reservation of 1546 — the four planes grow three times, each time with the rows written so far kept.  The
+    tree's plane against tests/merge_sh_ref.py's chain by that file's comparison, and against the single merges byte for byte."""
+    n, levels = 1031, tuple(range(1, 11))
+    rec = mr.crafted_records(n, n)
+    sh = ms.random_plane(n, n)
+    recs, planes, wparent, wfirst = ms.chain(rec, sh, levels, 2, 0.5)
+    assert len(recs) == len(levels) + 1                                              # (every step merges: step s made level s + 1)
+    conv = Converter(0)
+    try:
+        out, tree, parent, b, plane = build(conv, rec, sh, levels, 2, 0.5)
+        first = out["first"]
+        print(f"lod build with a plane n={n} chain={levels} group=2 dot=0.5 on a fresh context: {out}")
+        assert out["nodes"] > n + n // 2
+        assert out["nodes"] == 8921 and first == wfirst and np.array_equal(parent, wparent)
+        assert np.array_equal(bits(plane[:n]), bits(sh))
+        for s, lv in enumerate(levels):
+            perm, heads = ms.heads_of(recs[s], lv, 2, 0.5)
+            wplane, pinfo = ms.merge_plane(recs[s], planes[s], perm, heads)
+            assert np.array_equal(bits(wplane), bits(planes[s + 1]))
+            ulps = ms.compare(plane[first[s + 1]:first[s + 2]], planes[s + 1], pinfo)
+            print(f"  level {s + 1}: plane within {ulps:.4f} ulp of max|sh|")
+            assert ulps <= ms.PLANE_ULPS_BAR
+        want = levels_one_by_one(ref, rec, sh, levels, 2, 0.5)
+        assert len(want) == out["levels"]
+        for l, w in enumerate(want):
+            assert np.array_equal(bits(plane[first[l]:first[l + 1]]), bits(w)), ("level", l)
+        cam = (0.4, 0.1, -0.3)
+        conv.lod_select(cam, FOCAL, 0.5, NEAR)
+        check_cut(conv, tree, plane, lr.select(b, parent, first, cam, FOCAL, 0.5, NEAR)["nodes"])
+    finally:
+        conv.close()
+
+
 def test_nothing_inside_gives_an_empty_plane_and_a_plain_cut_follows(conv):
     rec = mr.crafted_records(600, 21, invalid=False)
     sh = ms.random_plane(600, 21)

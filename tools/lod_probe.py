@@ -39,13 +39,14 @@ call the leaves inside the frustum, the occluded ones, the tau_px, the selected 
 runs without the depth test), the visibility stage, the stages of the cut and the whole call on the host's clock.
 
 A conversion stores a record's edges in units the viewer divides by the resolutionTarget, and those are the edges the cut's pin reads:
-tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events;
-medians of --reps calls after --warmup."""
+tau_px = 1024 is one SCREEN pixel per texel edge at R = 1024, tau_px = 1 the pin's own unit.  Stage times come from device events, `host_wall`
+is the whole call on the host's clock; medians of --reps calls after --warmup."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -139,17 +140,19 @@ def main():
     def cut_rows(eye, focal, tau, cam):
         rows, counts = [], None
         for k in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
             got = conv.lod_select(eye, focal, tau, cam.near)
+            wall = (time.perf_counter() - t0) * 1e3
             assert counts is None or got == counts                                    # integer sums: the same from run to run
             counts = got
             ms = conv.last_lod_select_stage_ms()
             ms["total"] = ms["sweep"] + ms["scan_ids"] + ms["compact"]
+            ms["host_wall"] = wall                                                    # (the whole call on the host's clock, the binding included)
             if k >= a.warmup:
                 rows.append(ms)
         return counts, median_of(rows)
 
     if a.frustum or a.occlusion:
-        import time
         from mesh2splat_amd.meshdepth import MeshDepthParams
         from mesh2splat_amd.splat import SplatParams
         yard, mine = ("frustum", "occluded") if a.occlusion else ("plain", "frustum")     # the yardstick and the call measured against it
@@ -250,7 +253,6 @@ def main():
         conv.close()
         return
     if a.budget:
-        import time
         records = convert()
         build = conv.lod_build(unsigned_axis=True)
         first = build["first"]
